@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/sec of SAC on 4096 vectorised two-series CSTR envs per GPU (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 N > 1 runs N ranks, one per GPU, over RCCL. Either the caller starts them (torch.distributed.run: WORLD_SIZE / RANK /
 LOCAL_RANK / MASTER_* in the environment), or -- plain `python bench.py --gpus N` -- this file does: the parent, BEFORE
@@ -17,12 +17,17 @@ EIGHT iterations recorded per graph: `model.enable_graph_capture(True, unroll=8)
 alone launches eagerly and CSTR_GRAPH_UNROLL defaults to 1; the host bookkeeping (episode statistics, lazily read loss
 means) of those eight iterations runs after the replay. `config.hip_graph` / `config.graph_unroll` say so on the line and
 `unroll1_variant` is the same run with one iteration per graph. Inputs are resident in HBM
-before the timed region. The timed region is bracketed by a barrier + torch.cuda.synchronize() on both sides; the MAX
-over ranks is reported. A K-step region shorter than MIN_TIMED_S is repeated (whole multiples of K, every repeat
-bracketed the same way) until the total reaches it: `steps` stays the CLI value, `timed_steps_total` is the real count.
+before the timed region. The timed region is exactly K steps, bracketed by a barrier + torch.cuda.synchronize() on both
+sides; the MAX over ranks is reported and `ms_per_step` is that duration / K.
 The run FAILS (non-zero exit) if hipGraph replay was requested but the timed iterations ran eagerly.
 
-Extra objects on the JSON line:
+--dump-outputs DIR writes, after the timed steps, what the last timed step left for a caller of learn() (rank 0): every
+tensor of the policy's state_dict (actor, critics, target networks), SAC's log entropy coefficient, the envs' observations
+and the replay-ring row that step wrote, as DIR/<name>.npy (float32, well under 64 MB). The seeds are fixed, so the same
+arguments give the same inputs from run to run and two builds can be compared output for output.
+
+A plain run does only what the headline needs (set-up, warm-up, the K timed steps, --dump-outputs, the line). --full adds
+the extra objects below (each still subject to --no-roofline / --no-variant / --no-cpu-baseline):
   roofline      the dominant kernel OF THE REPLAYED GRAPH: `rollout_step_kernel` (policy network + collect step of all
                 envs + replay index draw in one launch). Matrix-core bound: the policy network's algorithmic FLOPs per
                 launch / its launch duration (HIP events on the launch stream, graph-replayed back-to-back launches right
@@ -57,7 +62,6 @@ import torch as th  # noqa: E402
 
 F32_MFMA_PEAK_TFLOPS = 157.3  # dense f32-input MFMA, MI355X_MICROARCH.md
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s measured achievable)
-MIN_TIMED_S = 0.25  # a timed region shorter than this is repeated (20 steps = 2.9 ms must not stand alone)
 # the reference's own Python on CPU, measured in the survey container (8 cores, no GPU; SURVEY 6 / BASELINE.md 2): unmodified
 # reference SAC("MlpPolicy").learn() on DummyVecEnv(4096 x TwoSeriesCSTREnv), class defaults. It cannot travel to the GPU box.
 REFERENCE_PYTHON_ENV_STEPS_PER_S = 4.2e3
@@ -82,6 +86,9 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-variant", action="store_true", help="skip the secondary north_star-shaped run (obs 8, RK4)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true", help="also run the rooflines, per-kernel timings, variants, CPU baseline and "
+                                                        "reference comparison (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -454,6 +461,27 @@ def iteration_model(algo: str, n_envs: int, obs_dim: int, act_dim: int, batch: i
     return dict(bytes=by, bytes_total=sum(by.values()), flops=fl, flops_total=sum(fl.values()))
 
 
+def dump_outputs(model, env, out_dir: str) -> None:
+    """What the last timed step left for a caller of learn(), as out_dir/<name>.npy (float32): the policy's state_dict
+    (actor, critics, targets), SAC's log entropy coefficient, the envs' observations and the replay-ring row that step wrote."""
+    th.cuda.synchronize()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f"policy.{k}": v for k, v in model.policy.state_dict().items() if v.is_floating_point()}
+    if getattr(model, "log_ent_coef", None) is not None:
+        arrays["log_ent_coef"] = model.log_ent_coef
+    arrays["env_obs"] = env.obs
+    ring = model.replay_buffer.ring
+    row = (int(ring.ctl[0]) - 1) % ring.rows  # ring_ctl = {pos, full, ticket, adds}: pos is the next row to write
+    for name in ("observations", "next_observations", "actions", "rewards", "dones"):
+        arrays[f"ring_last_row.{name}"] = getattr(ring, name)[row]
+    total = 0
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes (limit 64 MB)"
+
+
 def launch_ranks(args) -> int:
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes of this file (RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_* set), relay rank 0's JSON line, return non-zero unless every rank exited 0 and the line says n_gpus == N.
@@ -642,22 +670,13 @@ def main():
     run_steps(args.steps)
     host_dt = time.perf_counter() - t0  # host time to ENQUEUE the K steps (before the closing synchronize): ~ ms_per_step means host-bound
     barrier()
-    dt = agreed_max(time.perf_counter() - t0)
-    # a K-step region shorter than MIN_TIMED_S is repeated in whole multiples of K until the total reaches it (every rank sees
-    # the same MAX-reduced durations, so every rank takes the same decision)
-    repeats = 1
-    while dt < MIN_TIMED_S and repeats < 100000:
-        barrier()
-        t0 = time.perf_counter()
-        run_steps(args.steps)
-        barrier()
-        dt += agreed_max(time.perf_counter() - t0)
-        repeats += 1
-    timed_steps = args.steps * repeats
+    dt = agreed_max(time.perf_counter() - t0)  # seconds per K steps
+    timed_steps = args.steps
     st1 = model.graph_status()
     graph_replays = st1["replays"] - st0["replays"]
     eager_in_timed = st1["eager_iterations"] - st0["eager_iterations"]
-    dt_steps = dt / repeats  # seconds per K steps
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, env, args.dump_outputs)
     # proof of the rank count: a summing all-reduce on the job's backend, and the weights of every rank after training
     checksum = dict(expected=world * (world + 1) // 2, got=rank + 1, backend="none")
     weights_identical = None
@@ -673,7 +692,6 @@ def main():
         th.distributed.all_reduce(hmax, op=th.distributed.ReduceOp.MAX)
         th.distributed.all_reduce(hmin, op=th.distributed.ReduceOp.MIN)
         weights_identical = bool(th.equal(hmax, hmin))
-    dt = dt_steps
     value = args.steps * N * world / dt
     rccl_world = th.distributed.get_world_size() if th.distributed.is_initialized() else 1
     line = {
@@ -684,13 +702,9 @@ def main():
         "dtype": "f32", "data": "synthetic", "rccl_world": rccl_world, "allreduce_checksum": checksum,
         "weights_identical_across_ranks": weights_identical, "graph_collectives": st1["graph_collectives"],
         "host_enqueue_ms_per_step": round(1e3 * host_dt / args.steps, 4),
-        "timed_steps_total": timed_steps, "timed_repeats": repeats, "timed_seconds_total": round(dt * repeats, 4),
+        "timed_steps_total": timed_steps, "timed_seconds_total": round(dt, 6),
         "graph_prewarm_steps": prewarm, "hip_graph_active": st1["active"], "hip_graph_replays_in_timed_region": graph_replays,
         "eager_iterations_in_timed_region": eager_in_timed, "hip_graph_error": st1["error"],
-        "reference_python_env_steps_per_s": {"value": REFERENCE_PYTHON_ENV_STEPS_PER_S, "provenance": "unmodified reference SAC.learn() on "
-                                             "DummyVecEnv(4096), survey container, 8 CPU cores, no GPU (SURVEY 6 / BASELINE.md 2); "
-                                             "not re-measurable on the GPU box (the reference cannot travel)",
-                                             "cross_machine_ratio": round(value / REFERENCE_PYTHON_ENV_STEPS_PER_S, 1)},
         "config": {"workload": f"{args.algo.upper()} MlpPolicy class defaults on {N} vectorised two-series CSTR envs per GPU "
                                f"(obs {env_obs_dim}/act {env_act_dim}{' twin-train env, 4 agents' if args.algo == 'maddpg' else ''}, {args.integrator}, batch 256, "
                                f"ring {ring_rows}x{N}, 1 gradient step per vec-step; hipGraph replay, {args.graph_unroll} iterations per graph)",
@@ -700,7 +714,12 @@ def main():
     if rank == 0:
         launches = st1["abi_launches_per_iteration"]
         n_launch = round(sum(launches.values()) / max(len(launches), 1), 2) if launches else None
-        if not args.no_roofline and args.algo != "maddpg":
+        if args.full:
+            line["reference_python_env_steps_per_s"] = {
+                "value": REFERENCE_PYTHON_ENV_STEPS_PER_S, "provenance": "unmodified reference SAC.learn() on DummyVecEnv(4096), survey "
+                "container, 8 CPU cores, no GPU (SURVEY 6 / BASELINE.md 2); not re-measurable here (the reference is not part of this "
+                "repository)", "cross_machine_ratio": round(value / REFERENCE_PYTHON_ENV_STEPS_PER_S, 1)}
+        if args.full and not args.no_roofline and args.algo != "maddpg":
             rc = roofline_collect(N, args.obs_dim, args.integrator, 500)
             rc["note"] = ("the fused collect kernel ALONE (the eager path's and MADDPG's launch; inside captured SAC / TD3 iterations it is "
                           "part of rollout_step_kernel): 4096 envs x 104 B = 426 KB per launch, cache-resident and launch-latency-bound; "
@@ -754,7 +773,7 @@ def main():
                                                             traffic=rtraffic, traffic_source=rsrc)
             else:
                 line["roofline"] = rc
-        if args.algo == "sac":
+        if args.full and args.algo == "sac":
             n_crit = sum(p.numel() for p in model.critic.parameters())
             im = iteration_model("sac", N, args.obs_dim, 2, B, (256, 256), n_crit)
             ms = line["ms_per_step"]
@@ -767,7 +786,7 @@ def main():
                 note="whole iteration / ms_per_step: launch-latency-bound (a chain of dependent sub-10-us launches), far from either roofline; "
                      "launches = C-ABI launches recorded into the graph per iteration (rocprofv3 cross-check: tools/count_launches.sh)")
         line["config"]["launches_per_iteration"] = n_launch
-        if world == 1 and not args.no_variant and args.algo == "sac" and (args.obs_dim, args.integrator) == (4, "euler"):
+        if args.full and world == 1 and not args.no_variant and args.algo == "sac" and (args.obs_dim, args.integrator) == (4, "euler"):
             del model, env
             dev = f"cuda:{local_rank}"
             u = args.graph_unroll
@@ -776,7 +795,7 @@ def main():
             line["unroll1_variant"] = variant_run(N, dev, use_graph, 4, "euler", unroll=1, steps=320)
             line["td3_variant"] = variant_run(N, dev, use_graph, 4, "euler", algo="td3", unroll=u, warm=40, steps=320)
             line["maddpg_variant"] = variant_run(1024, dev, use_graph, 8, "euler", algo="maddpg", unroll=u, warm=40, steps=160)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(N, B, args.cpu_seconds)
             line["speedup_vs_cpu_port"] = round(value / line["cpu_baseline"]["value"], 2)
         os.write(result_fd, (json.dumps(line) + "\n").encode())

@@ -5,12 +5,12 @@ set -e
 ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out
 TAG=${1:-final}
-[ -n "$SKIP_BENCH" ] || python $ROOT/bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
+[ -n "$SKIP_BENCH" ] || python $ROOT/bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err
 cd /tmp && export TMPDIR=/tmp
 for algo in sac td3 maddpg; do
   extra=""; [ $algo = maddpg ] && extra="--n-envs 1024"
   rm -rf $OUT/prof_$algo
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$algo -o $algo -- python3 $ROOT/bench.py --algo $algo $extra --steps 150 --warmup 50 --no-variant --no-cpu-baseline > $OUT/prof_$algo.json 2> $OUT/prof_$algo.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$algo -o $algo -- python3 $ROOT/bench.py --full --algo $algo $extra --steps 150 --warmup 50 --no-variant --no-cpu-baseline > $OUT/prof_$algo.json 2> $OUT/prof_$algo.err
   find $OUT/prof_$algo -name "*kernel_stats.csv" -exec cp {} $OUT/${TAG}_${algo}_kernel_stats.csv \;
   rm -rf $OUT/prof_$algo
 done
