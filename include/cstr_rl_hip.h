@@ -504,6 +504,23 @@ int cstr_hidden_head_bwd_root_f32(const cstr_head_root_t *root, const float *y, 
 int cstr_sac_actor_loss_f32(const float *logp, const float *q1, const float *q2, const float *ent_coef, float *g_logp, float *gq1,
                             float *gq2, float *loss_out, float *loss_sum, int64_t batch, cstr_stream_t stream);
 
+/* Critic ensembles (policy_kwargs n_critics = N, 1 <= N <= CSTR_MAX_ENS_CRITICS; reference core/common/policies.py:934-965): the
+ * N-critic forms of cstr_td_twin_q_loss_f32 and cstr_sac_actor_loss_f32, one single-workgroup launch each (batch <= 16384). Q values
+ * are [N][batch] with a row stride (the stacked critic output [G, B, 1]; unused for N = 1), gq is [N][batch] contiguous. Per critic
+ * the twin kernels' expressions and block-sum tree: at N = 2 both are bit-identical to their twin counterparts.
+ * cstr_td_ens_q_loss_f32 (core/sac/sac.py:249-261, core/td3/td3.py:174-182): t = rew + (1 - done) * gamma * (min_i q_t[i] - alpha *
+ *   next_logp); gq[i] = scale * 2 / B * (q[i] - t); loss = scale * (((s_0 / B + s_1 / B) + s_2 / B) + ...), s_i = sum_b (q[i] - t)^2
+ *   in critic order. next_logp, ent_coef, alpha, target_out as in cstr_td_twin_q_loss_f32.
+ * cstr_sac_actor_ens_loss_f32 (core/sac/sac.py:273-275): loss = mean(ent_coef * logp - min_i q_i); g_logp = ent_coef / B; gq[i][b] =
+ *   -1/B for the FIRST index attaining the minimum (th.min's convention), 0 for the others. */
+#define CSTR_MAX_ENS_CRITICS 16
+int cstr_td_ens_q_loss_f32(const float *q_t, int64_t q_t_stride, const float *next_logp, const float *rew, const float *done,
+                           const float *ent_coef, float gamma, const float *q, int64_t q_stride, float scale, float *target_out, float *gq,
+                           float *loss_out, float *loss_sum, const cstr_alpha_part_t *alpha, int n_critics, int64_t batch,
+                           cstr_stream_t stream);
+int cstr_sac_actor_ens_loss_f32(const float *logp, const float *q, int64_t q_stride, const float *ent_coef, float *g_logp, float *gq,
+                                float *loss_out, float *loss_sum, int n_critics, int64_t batch, cstr_stream_t stream);
+
 /* Deterministic-policy actor loss (core/td3/td3.py:194, core/maddpg/maddpg.py:174): loss = -mean(q), gq = -1/B. */
 int cstr_neg_mean_loss_f32(const float *q, float *gq, float *loss_out, float *loss_sum, int64_t batch, cstr_stream_t stream);
 

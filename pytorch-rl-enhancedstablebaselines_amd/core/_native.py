@@ -16,6 +16,7 @@ RING_CTL_WORDS, ADAM_CTL_WORDS, MT_STATE_WORDS, PCG_STATE_WORDS, MAX_SAMPLE_BATC
 MAX_NOISE_PERIOD = 8
 VECNORM_STATE_WORDS = 20
 RNG_CTL_WORDS, MAX_HEAD_ACT, MAX_LINEAR_SETS, MAX_ADAM_SEGS = 16, 4, 16, 4
+MAX_ENS_CRITICS = 16
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -23,7 +24,7 @@ SYMBOLS = (
     "cstr_adam_multi_f32", "cstr_gaussian_head_fwd_f32", "cstr_gaussian_head_gemm_fwd_f32", "cstr_gaussian_head_bwd_f32", "cstr_gaussian_head_bwd_input_f32", "cstr_linear_act_fwd_f32", "cstr_linear_act_fwd_sets_f32", "cstr_linear_bwd_input_f32", "cstr_linear_bwd_weight_f32", "cstr_linear_bwd_weight_sets_f32", "cstr_td_twin_q_loss_f32", "cstr_policy_rows_fwd_f32", "cstr_policy_swizzle_f32", "cstr_target_smooth_f32", "cstr_linear_smooth_fwd_f32", "cstr_hidden_head_fwd_f32", "cstr_hidden_head_bwd_f32", "cstr_hidden_head_bwd_root_f32", "cstr_vecnorm_init_f64", "cstr_vecnorm_step_f64", "cstr_vecnorm_apply_f32",
     "cstr_td_target_min_f32", "cstr_polyak_f32", "cstr_adam_f32", "cstr_bias_act_fwd_f32", "cstr_bias_act_bwd_f32", "cstr_bias_act_bwd_rows_f32",
     "cstr_squashed_gaussian_fwd_f32", "cstr_squashed_gaussian_bwd_f32", "cstr_sac_alpha_f32", "cstr_twin_q_loss_f32",
-    "cstr_sac_actor_loss_f32", "cstr_neg_mean_loss_f32",
+    "cstr_sac_actor_loss_f32", "cstr_neg_mean_loss_f32", "cstr_td_ens_q_loss_f32", "cstr_sac_actor_ens_loss_f32",
     "cstr_sac_actor_chain_fwd_f32", "cstr_q_chain_fwd_f32", "cstr_q_chain_bwd_f32", "cstr_sac_actor_chain_bwd_f32",
     "cstr_linear_bwd_weight_adam_sets_f32", "cstr_chain_sum_parts_f32",
 )

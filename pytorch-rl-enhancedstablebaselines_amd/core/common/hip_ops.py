@@ -891,6 +891,79 @@ def sac_actor_loss(logp, q1, q2, ent_coef, g_logp, gq1, gq2, loss_out=None, loss
                                            ptr(loss_out), ptr(loss_sum), C.c_int64(b), stream_ptr()), "cstr_sac_actor_loss_f32")
 
 
+def _critic_rows(q, name, b):
+    """(base pointer, row stride in elements, N) of N critics' Q values over a batch of b: a stacked tensor [N, b] / [N, b, 1] whose rows
+    are contiguous (a `fused.QOut` is taken by its `.stacked` tensor), or a sequence of N contiguous [b] / [b, 1] tensors that lie
+    equally spaced in memory (one tensor for N = 1)."""
+    stacked = getattr(q, "stacked", None)
+    if stacked is not None:
+        q = stacked
+    if isinstance(q, th.Tensor):
+        if not (q.is_cuda and q.dtype == th.float32 and q.dim() in (2, 3) and q.shape[1] == b and (q.dim() == 2 or q.shape[2] == 1)):
+            raise ValueError(f"{name}: needs a float32 device tensor [N, {b}] or [N, {b}, 1], got {tuple(q.shape)} {q.dtype} on {q.device}")
+        if q.stride(1) != 1 or (q.shape[0] > 1 and q.stride(0) < b):
+            raise ValueError(f"{name}: every critic's row must be contiguous and the rows must not overlap")
+        n, rows = q.shape[0], [q.data_ptr() + 4 * i * q.stride(0) for i in range(q.shape[0])]
+    else:
+        ts = list(q)
+        for i, t in enumerate(ts):
+            _vec(t, f"{name}[{i}]", b)
+        n, rows = len(ts), [t.data_ptr() for t in ts]
+    if not 1 <= n <= nv.MAX_ENS_CRITICS:
+        raise ValueError(f"{name}: {n} critics; the ensemble loss heads take 1..{nv.MAX_ENS_CRITICS}")
+    stride = (rows[1] - rows[0]) // 4 if n > 1 else b
+    if n > 1 and (stride < b or any(r != rows[0] + 4 * i * stride for i, r in enumerate(rows))):
+        raise ValueError(f"{name}: the critics' rows must lie equally spaced in one allocation (a stacked [N, B, 1] output)")
+    return rows[0], stride, n
+
+
+def td_ens_q_loss(q_t, next_logp, rew, done, ent_coef, gamma: float, q, scale: float, target_out, gq, loss_out=None, loss_sum=None,
+                  alpha=None):
+    """`td_twin_q_loss` for N critics (cstr_td_ens_q_loss_f32): q_t / q = the target critics' / the critics' Q values (stacked [N, B, 1],
+    a `fused.QOut`, or N equally spaced [B, 1] views), gq [N, B, 1] contiguous. At N = 2 bit-identical to `td_twin_q_loss`."""
+    b = rew.numel()
+    qt_ptr, qt_stride, n = _critic_rows(q_t, "q_t", b)
+    q_ptr, q_stride, n_q = _critic_rows(q, "q", b)
+    if n_q != n:
+        raise ValueError(f"q_t has {n} critics, q has {n_q}")
+    _vec(gq, "gq", n * b)  # [N, B, 1] contiguous
+    for t, nm in ((rew, "rew"), (done, "done")):
+        _vec(t, nm, b)
+    if next_logp is not None:
+        _vec(next_logp, "next_logp", b)
+        if alpha is None:
+            if ent_coef is None:
+                raise ValueError("next_logp needs ent_coef or the alpha part")
+            _vec(ent_coef, "ent_coef", 1)
+    if target_out is not None:
+        _vec(target_out, "target_out", b)
+    part = None
+    if alpha is not None:
+        _vec(alpha["logp_pi"], "logp_pi", b)
+        for nm in ("log_alpha", "grad_out", "ent_coef_out"):
+            _vec(alpha[nm], nm, 1)
+        part = nv.AlphaPart(alpha["log_alpha"].data_ptr(), alpha["logp_pi"].data_ptr(), float(alpha["target_entropy"]),
+                            alpha["grad_out"].data_ptr(), alpha["ent_coef_out"].data_ptr(),
+                            *(None if alpha.get(k) is None else alpha[k].data_ptr() for k in ("loss_out", "loss_sum", "ent_coef_sum")))
+    check(nv.lib().cstr_td_ens_q_loss_f32(C.c_void_p(qt_ptr), C.c_int64(qt_stride), ptr(next_logp), ptr(rew), ptr(done),
+                                          ptr(None if alpha is not None else ent_coef), C.c_float(gamma), C.c_void_p(q_ptr),
+                                          C.c_int64(q_stride), C.c_float(scale), ptr(target_out), ptr(gq), ptr(loss_out), ptr(loss_sum),
+                                          None if part is None else C.byref(part), C.c_int(n), C.c_int64(b), stream_ptr()),
+          "cstr_td_ens_q_loss_f32")
+
+
+def sac_actor_ens_loss(logp, q, ent_coef, g_logp, gq, loss_out=None, loss_sum=None):
+    """`sac_actor_loss` for N critics (cstr_sac_actor_ens_loss_f32): loss = mean(ent_coef * logp - min_i q_i); q as in `td_ens_q_loss`,
+    gq [N, B, 1] contiguous. At N = 2 bit-identical to `sac_actor_loss`."""
+    b = logp.numel()
+    q_ptr, q_stride, n = _critic_rows(q, "q", b)
+    _vec(gq, "gq", n * b)  # [N, B, 1] contiguous
+    _vec(logp, "logp", b), _vec(g_logp, "g_logp", b), _vec(ent_coef, "ent_coef", 1)
+    check(nv.lib().cstr_sac_actor_ens_loss_f32(ptr(logp), C.c_void_p(q_ptr), C.c_int64(q_stride), ptr(ent_coef), ptr(g_logp), ptr(gq),
+                                               ptr(loss_out), ptr(loss_sum), C.c_int(n), C.c_int64(b), stream_ptr()),
+          "cstr_sac_actor_ens_loss_f32")
+
+
 def neg_mean_loss(q, gq, loss_out=None, loss_sum=None):
     b = q.numel()
     _vec(q, "q", b), _vec(gq, "gq", b)

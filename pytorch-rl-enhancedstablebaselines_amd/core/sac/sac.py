@@ -87,7 +87,7 @@ class SAC(OffPolicyAlgorithm):
     def _fused_supported(self) -> bool:
         from core.common.arena import FlatAdam
 
-        return (len(self.critic.q_networks) == 2 and isinstance(self.actor.optimizer, FlatAdam)
+        return (1 <= len(self.critic.q_networks) <= hip_ops.nv.MAX_ENS_CRITICS and isinstance(self.actor.optimizer, FlatAdam)
                 and isinstance(self.critic.optimizer, FlatAdam) and fused.FastMLP.supported(self.actor.latent_pi)
                 and all(fused.FastMLP.supported(q) for q in self.critic.q_networks))
 
@@ -192,11 +192,14 @@ class SAC(OffPolicyAlgorithm):
         else:
             rd = self.replay_buffer.sample_into(self._batch(batch_size))  # :215
         B = rd.observations.shape[0]
+        n_q = len(self.critic.q_networks)
+        ens = n_q != 2  # critic ensembles (policy_kwargs n_critics): the N-critic loss heads, per-layer critic passes
         if not hasattr(self, "_g_bufs") or self._g_bufs[0].shape[0] != B:
             e = lambda *sh: th.empty(*sh, dtype=th.float32, device=self.device)  # noqa: E731
-            self._g_bufs = (e(2, B, 1), e(B))
+            self._g_bufs = (e(n_q, B, 1), e(B))
         gq, g_lp = self._g_bufs
-        gq1, gq2 = gq[0], gq[1]
+        if not ens:
+            gq1, gq2 = gq[0], gq[1]
 
         pair = pb is not None and self._fast_actor.pair_supported(pb)
         assert gather is None or pair
@@ -217,14 +220,17 @@ class SAC(OffPolicyAlgorithm):
                 x_next, next_log_prob = self._fast_actor.action_log_prob(rd.next_observations, train_params=False, xbuf=pb.x_next)
             if pb is None:
                 next_actions, next_log_prob = self._fast_actor.action_log_prob(rd.next_observations, train_params=False)
-                q1_t, q2_t = self._fast_critic_target(rd.next_observations, next_actions, train_params=False)
+                qs_t = self._fast_critic_target(rd.next_observations, next_actions, train_params=False)
             elif not twin_pair:
-                q1_t, q2_t = self._fast_critic_target.forward_input(x_next, train_params=False)
+                qs_t = self._fast_critic_target.forward_input(x_next, train_params=False)
+            if not twin_pair and not ens:
+                q1_t, q2_t = qs_t
         if twin_pair:  # :258 and :250 as ONE four-network chain (three launches instead of six)
             qs, (q1_t, q2_t) = fused.twin_pair_forward(self._fast_critic, self._fast_critic_target, pb.x_data, x_next)
         else:
             qs = self._fast_critic.forward_input(pb.x_data) if pb is not None else self._fast_critic(rd.observations, rd.actions)  # :258
-        q1, q2 = qs
+        if not ens:
+            q1, q2 = qs
         if self.ent_coef_optimizer is not None:
             ent_coef = s["ent_coef"] if single else self._ent_coef_buf
             alpha = dict(log_alpha=self.log_ent_coef.detach(), logp_pi=log_prob.detach(), target_entropy=self.target_entropy,
@@ -240,8 +246,12 @@ class SAC(OffPolicyAlgorithm):
                            ent_coef=ent_coef, gamma=self.gamma, scale=0.5, q1=q1.detach(), q2=q2.detach(), target_out=self._target_q,
                            loss_out=sto("critic", self._loss_now["critic"]), loss_sum=acc("critic"), alpha=alpha)
         else:
-            hip_ops.td_twin_q_loss(q1_t, q2_t, next_log_prob, rd.rewards, rd.dones, ent_coef, self.gamma, q1, q2, 0.5, self._target_q,
-                                   gq1, gq2, sto("critic", self._loss_now["critic"]), acc("critic"), alpha=alpha)
+            if ens:  # :249-250 and :261 over all N critics
+                hip_ops.td_ens_q_loss(qs_t, next_log_prob, rd.rewards, rd.dones, ent_coef, self.gamma, qs, 0.5, self._target_q, gq,
+                                      sto("critic", self._loss_now["critic"]), acc("critic"), alpha=alpha)
+            else:
+                hip_ops.td_twin_q_loss(q1_t, q2_t, next_log_prob, rd.rewards, rd.dones, ent_coef, self.gamma, q1, q2, 0.5, self._target_q,
+                                       gq1, gq2, sto("critic", self._loss_now["critic"]), acc("critic"), alpha=alpha)
             if self.ent_coef_optimizer is not None and not self._ent_rides_critic:
                 self._allreduce_grads(self._ent_arena)
                 self.ent_coef_optimizer.step()
@@ -261,17 +271,22 @@ class SAC(OffPolicyAlgorithm):
         # :273-275 (critic weights frozen)
         qs_pi = (self._fast_critic.forward_input(x_pi, train_params=False) if pb is not None
                  else self._fast_critic(rd.observations, actions_pi, train_params=False))
-        q1_pi, q2_pi = qs_pi
+        if not ens:
+            q1_pi, q2_pi = qs_pi
         root = qs_pi.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critic)
         actor_root = None
         if root:  # the actor loss rides in the first launch of the backward through the (frozen) critic
             actor_root = dict(mode="sac_actor", logp=log_prob.detach(), q1=q1_pi.detach(), q2=q2_pi.detach(), ent_coef=ent_coef, g_logp=g_lp,
                               loss_out=sto("actor", self._loss_now["actor"]), loss_sum=acc("actor"))
+        elif ens:  # min over all N critics
+            hip_ops.sac_actor_ens_loss(log_prob, qs_pi, ent_coef, g_lp, gq, sto("actor", self._loss_now["actor"]), acc("actor"))
         else:
             hip_ops.sac_actor_loss(log_prob, q1_pi, q2_pi, ent_coef, g_lp, gq1, gq2, sto("actor", self._loss_now["actor"]), acc("actor"))
         with fused.loss_root(actor_root), fused.deferred_weight_grads():  # :279-281; the actor's dW / db of all layers in one launch
             if qs_pi.stacked is not None:
                 th.autograd.backward([log_prob, qs_pi.stacked], [g_lp, gq])
+            elif ens:  # one Q network: no stack
+                th.autograd.backward([log_prob, *qs_pi], [g_lp, *gq])
             else:
                 th.autograd.backward([log_prob, q1_pi, q2_pi], [g_lp, gq1, gq2])
         self._allreduce_grads(pol.actor_arena)
@@ -281,7 +296,7 @@ class SAC(OffPolicyAlgorithm):
             self.actor.optimizer.step()
 
         if self.debug_capture:
-            self.last_train_tensors = dict(target_q=self._target_q.clone(), current_q=[q1.detach().clone(), q2.detach().clone()],
+            self.last_train_tensors = dict(target_q=self._target_q.clone(), current_q=[q.detach().clone() for q in qs],
                                            critic_loss=sto("critic", self._loss_now["critic"]).clone(),
                                            actor_loss=sto("actor", self._loss_now["actor"]).clone(),
                                            ent_coef=ent_coef.detach().clone(), log_prob=log_prob.detach().clone())
@@ -300,7 +315,7 @@ class SAC(OffPolicyAlgorithm):
 
     def _gradient_step_aten(self, batch_size: int, gradient_step: int) -> None:
         """Stock-ATen evaluation of the step (nn.Module forwards, autograd losses): the fallback for configurations the
-        fused path does not cover (custom activations / optimisers / n_critics) and the A/B reference in tests."""
+        fused path does not cover (custom activations / optimisers, more than 16 critics) and the A/B reference in tests."""
         s = self._loss_sums
         replay_data = self.replay_buffer.sample_into(self._batch(batch_size))  # :215
 
@@ -321,12 +336,16 @@ class SAC(OffPolicyAlgorithm):
 
         with th.no_grad():  # :245-254
             next_actions, next_log_prob = self.actor.action_log_prob(replay_data.next_observations)
-            q1_t, q2_t = self.critic_target(replay_data.next_observations, next_actions)[:2]
-            if len(self.critic_target.q_networks) != 2:
-                raise NotImplementedError("td_target_min kernel is built for n_critics=2 (the reference default)")
-            target_q_values = self._target_q
-            hip_ops.td_target_min(q1_t.contiguous(), q2_t.contiguous(), next_log_prob.reshape(-1, 1).contiguous(),
-                                  replay_data.rewards, replay_data.dones, ent_coef.contiguous(), self.gamma, target_q_values)
+            qs_t = self.critic_target(replay_data.next_observations, next_actions)
+            if len(qs_t) == 2:
+                q1_t, q2_t = qs_t
+                target_q_values = self._target_q
+                hip_ops.td_target_min(q1_t.contiguous(), q2_t.contiguous(), next_log_prob.reshape(-1, 1).contiguous(),
+                                      replay_data.rewards, replay_data.dones, ent_coef.contiguous(), self.gamma, target_q_values)
+            else:  # critic ensembles: the reference's own statements (:248-253)
+                next_q_values, _ = th.min(th.cat(qs_t, dim=1), dim=1, keepdim=True)
+                next_q_values = next_q_values - ent_coef * next_log_prob.reshape(-1, 1)
+                target_q_values = replay_data.rewards + (1 - replay_data.dones) * self.gamma * next_q_values
 
         current_q_values = self.critic(replay_data.observations, replay_data.actions)  # :258
         critic_loss = 0.5 * sum(F.mse_loss(current_q, target_q_values) for current_q in current_q_values)  # :261

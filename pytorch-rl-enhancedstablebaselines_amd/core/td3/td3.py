@@ -132,10 +132,14 @@ class TD3(OffPolicyAlgorithm):
                 noise = noise.clamp(-self.target_noise_clip, self.target_noise_clip)
                 next_actions = (self.actor_target(replay_data.next_observations) + noise).clamp(-1, 1)
                 qs = self.critic_target(replay_data.next_observations, next_actions)
-                q1_t, q2_t = qs[0], qs[-1]  # n_critics == 1 (DDPG): min over one network
-                hip_ops.td_target_min(q1_t.contiguous(), q2_t.contiguous(), None, replay_data.rewards, replay_data.dones,
-                                      None, self.gamma, self._target_q)
-                target_q_values = self._target_q
+                if len(qs) <= 2:
+                    q1_t, q2_t = qs[0], qs[-1]  # n_critics == 1 (DDPG): min over one network
+                    hip_ops.td_target_min(q1_t.contiguous(), q2_t.contiguous(), None, replay_data.rewards, replay_data.dones,
+                                          None, self.gamma, self._target_q)
+                    target_q_values = self._target_q
+                else:  # critic ensembles: the reference's own statements (:174-176)
+                    next_q_values, _ = th.min(th.cat(qs, dim=1), dim=1, keepdim=True)
+                    target_q_values = replay_data.rewards + (1 - replay_data.dones) * self.gamma * next_q_values
             current_q_values = self.critic(replay_data.observations, replay_data.actions)
             critic_loss = sum(F.mse_loss(current_q, target_q_values) for current_q in current_q_values)  # no 0.5 (:182)
             self._loss_sums["critic"] += critic_loss.detach()
@@ -180,8 +184,10 @@ class TD3(OffPolicyAlgorithm):
         else:
             rd = self.replay_buffer.sample_into(self._batch(batch_size))
         B = rd.observations.shape[0]
+        n_q = len(self.critic.q_networks)
+        ens = n_q > 2  # critic ensembles (policy_kwargs n_critics): min over all N targets, the loss and backward through all N critics
         if not hasattr(self, "_g_bufs") or self._g_bufs[0].shape[0] != B:
-            self._g_bufs = th.empty(2, B, 1, device=self.device)
+            self._g_bufs = th.empty(max(n_q, 2), B, 1, device=self.device)
         gq = self._g_bufs
         gq1, gq2 = gq[0], gq[1]
         with th.no_grad():  # :167-176
@@ -206,6 +212,7 @@ class TD3(OffPolicyAlgorithm):
                 next_actions = (self._fast_actor_target(rd.next_observations, train_params=False) + noise).clamp(-1, 1)
                 qs = self._fast_critic_target(rd.next_observations, next_actions, train_params=False)
             if pb is None or not twin_pair:
+                qs_t = qs
                 q1_t, q2_t = qs[0], qs[-1]
         if pb is not None and twin_pair:  # :179 and :173 as ONE four-network chain (three launches instead of six)
             qs, (q1_t, q2_t) = fused.twin_pair_forward(self._fast_critic, self._fast_critic_target, pb.x_data, pb.x_next)
@@ -222,10 +229,12 @@ class TD3(OffPolicyAlgorithm):
             td_root = dict(mode="td", q1_t=q1_t, q2_t=q2_t, next_logp=None, rew=rd.rewards, done=rd.dones, ent_coef=None,
                            gamma=self.gamma, scale=1.0, q1=q1.detach(), q2=q2.detach(), target_out=self._target_q,
                            loss_out=c_out, loss_sum=c_sum, alpha=None)
+        elif ens:
+            hip_ops.td_ens_q_loss(qs_t, None, rd.rewards, rd.dones, None, self.gamma, qs, 1.0, self._target_q, gq, c_out, c_sum)
         else:
             hip_ops.td_twin_q_loss(q1_t, q2_t, None, rd.rewards, rd.dones, None, self.gamma, q1, q2, 1.0 if len(qs) == 2 else 0.5,
                                    self._target_q, gq1, gq2, c_out, c_sum)
-        if len(qs) == 2:
+        if len(qs) >= 2:
             with fused.loss_root(td_root):
                 fused.backward_q(qs, gq)
         else:

@@ -2132,6 +2132,107 @@ __global__ __launch_bounds__(256) void sac_actor_loss_kernel(const float *__rest
     }
 }
 
+// The N-critic forms of the two loss heads above (policy_kwargs n_critics, 1 <= N <= CSTR_MAX_ENS_CRITICS): Q values [N][batch] with a
+// row stride (the stacked critic output [G, B, 1]), d(loss)/dQ [N][batch] contiguous. Per element and per critic the expressions of
+// td_twin_q_loss_kernel / sac_actor_loss_kernel, the same block_sum_256 tree per critic and the same final combination, so N = 2
+// reproduces the twin kernels bit for bit. The per-critic accumulators sit in registers: loops over CSTR_MAX_ENS_CRITICS unrolled,
+// guarded by the (workgroup-uniform) n.
+//   t = rew + (1 - done) * gamma * (min_i q_t[i] - alpha * next_logp);  loss = scale * (((s_0/B + s_1/B) + s_2/B) + ...)
+// (core/sac/sac.py:249-261, core/td3/td3.py:174-182)
+__global__ __launch_bounds__(256) void td_ens_q_loss_kernel(const float *__restrict__ q_t, const int64_t q_t_stride,
+                                                            const float *__restrict__ next_logp, const float *__restrict__ rew,
+                                                            const float *__restrict__ done, const float *__restrict__ ent_coef,
+                                                            const float gamma, const float *__restrict__ q, const int64_t q_stride,
+                                                            const float scale, float *__restrict__ target_out, float *__restrict__ gq,
+                                                            float *__restrict__ loss_out, float *__restrict__ loss_sum,
+                                                            const cstr_alpha_part_t ap, const int n, const int batch)
+{
+    __shared__ float sm[4];
+    const bool with_alpha = ap.log_alpha != nullptr;
+    const float la = with_alpha ? ap.log_alpha[0] : 0.0f;
+    const float ec = with_alpha ? expf(la) : (ent_coef ? ent_coef[0] : 0.0f);
+    const float k = scale * 2.0f / (float)batch;
+    float a[CSTR_MAX_ENS_CRITICS], aa = 0.0f;
+#pragma unroll
+    for (int i = 0; i < CSTR_MAX_ENS_CRITICS; ++i) a[i] = 0.0f;
+    for (int b = threadIdx.x; b < batch; b += 256) {
+        float qm = q_t[b];
+#pragma unroll
+        for (int i = 1; i < CSTR_MAX_ENS_CRITICS; ++i)
+            if (i < n) qm = fminf(qm, q_t[i * q_t_stride + b]);
+        if (next_logp) qm = qm - ec * next_logp[b];
+        const float t = rew[b] + (1.0f - done[b]) * gamma * qm;
+        if (target_out) target_out[b] = t;
+#pragma unroll
+        for (int i = 0; i < CSTR_MAX_ENS_CRITICS; ++i) {
+            if (i < n) {
+                const float d = q[i * q_stride + b] - t;
+                gq[(int64_t)i * batch + b] = k * d;
+                a[i] += d * d;
+            }
+        }
+        if (with_alpha) aa += ap.logp_pi[b] + ap.target_entropy;
+    }
+    float l = 0.0f;
+#pragma unroll
+    for (int i = 0; i < CSTR_MAX_ENS_CRITICS; ++i) {
+        if (i < n) {  // n is uniform over the workgroup: every thread reaches the same barriers
+            const float s = block_sum_256(a[i], sm);
+            l = i == 0 ? s / (float)batch : l + s / (float)batch;
+        }
+    }
+    const float mean = with_alpha ? block_sum_256(aa, sm) / (float)batch : 0.0f;
+    if (threadIdx.x == 0) {
+        const float loss = scale * l;
+        if (loss_out) loss_out[0] = loss;
+        if (loss_sum) loss_sum[0] += loss;
+        if (with_alpha) {
+            ap.grad_out[0] = -mean;
+            ap.ent_coef_out[0] = ec;
+            if (ap.loss_out) ap.loss_out[0] = -(la * mean);
+            if (ap.loss_sum) ap.loss_sum[0] += -(la * mean);
+            if (ap.ent_coef_sum) ap.ent_coef_sum[0] += ec;
+        }
+    }
+}
+
+// loss = mean(ent_coef * logp - min_i q_i);  d/d logp = ent_coef / B;  d/d q_i = -1/B for the FIRST index that attains the minimum
+// (th.min's convention; `!(m <= v)` is sac_actor_loss_kernel's `a <= c` test, NaN included), 0 for the others
+__global__ __launch_bounds__(256) void sac_actor_ens_loss_kernel(const float *__restrict__ logp, const float *__restrict__ q,
+                                                                 const int64_t q_stride, const float *__restrict__ ent_coef,
+                                                                 float *__restrict__ g_logp, float *__restrict__ gq,
+                                                                 float *__restrict__ loss_out, float *__restrict__ loss_sum, const int n,
+                                                                 const int batch)
+{
+    __shared__ float sm[4];
+    const float ec = ent_coef[0], inv = 1.0f / (float)batch;
+    float acc = 0.0f;
+    for (int b = threadIdx.x; b < batch; b += 256) {
+        float m = q[b];
+        int arg = 0;
+#pragma unroll
+        for (int i = 1; i < CSTR_MAX_ENS_CRITICS; ++i) {
+            if (i < n) {
+                const float v = q[i * q_stride + b];
+                const bool keep = m <= v;
+                m = keep ? m : v;
+                arg = keep ? arg : i;
+            }
+        }
+        acc += ec * logp[b] - m;
+        g_logp[b] = ec * inv;
+#pragma unroll
+        for (int i = 0; i < CSTR_MAX_ENS_CRITICS; ++i)
+            if (i < n) gq[(int64_t)i * batch + b] = i == arg ? -inv : 0.0f;
+    }
+    const float s = block_sum_256(acc, sm);
+    if (threadIdx.x == 0) {
+        const float loss = s * inv;
+        if (loss_out) loss_out[0] = loss;
+        if (loss_sum) loss_sum[0] += loss;
+    }
+}
+
 constexpr int HEAD_ROOT_MAX_ROWS = 1024;  // batch rows of the loss-root form (its per-row gradients sit in LDS)
 
 // block_sum_256 inside a larger workgroup: every thread calls it, waves 0-3 contribute (the same tree, the same bits)
@@ -2435,6 +2536,36 @@ extern "C" int cstr_sac_actor_loss_f32(const float *logp, const float *q1, const
     if (!logp || !q1 || !q2 || !ent_coef || !g_logp || !gq1 || !gq2 || batch <= 0) return CSTR_E_BADARG;
     if (batch > CSTR_MAX_SAMPLE_BATCH) return CSTR_E_UNSUPPORTED;
     sac_actor_loss_kernel<<<1, 256, 0, (hipStream_t)stream>>>(logp, q1, q2, ent_coef, g_logp, gq1, gq2, loss_out, loss_sum, (int)batch);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_td_ens_q_loss_f32(const float *q_t, int64_t q_t_stride, const float *next_logp, const float *rew, const float *done,
+                                      const float *ent_coef, float gamma, const float *q, int64_t q_stride, float scale, float *target_out,
+                                      float *gq, float *loss_out, float *loss_sum, const cstr_alpha_part_t *alpha, int n_critics,
+                                      int64_t batch, cstr_stream_t stream)
+{
+    if (!q_t || !rew || !done || !q || !gq || batch <= 0 || n_critics <= 0) return CSTR_E_BADARG;
+    if (n_critics > 1 && (q_t_stride < batch || q_stride < batch)) return CSTR_E_BADARG;  // rows must not overlap
+    cstr_alpha_part_t ap = {};
+    if (alpha && alpha->log_alpha) {
+        if (!alpha->logp_pi || !alpha->grad_out || !alpha->ent_coef_out) return CSTR_E_BADARG;
+        ap = *alpha;
+    }
+    if (next_logp && !ap.log_alpha && !ent_coef) return CSTR_E_BADARG;  // an entropy term needs its coefficient
+    if (n_critics > CSTR_MAX_ENS_CRITICS || batch > CSTR_MAX_SAMPLE_BATCH) return CSTR_E_UNSUPPORTED;
+    td_ens_q_loss_kernel<<<1, 256, 0, (hipStream_t)stream>>>(q_t, q_t_stride, next_logp, rew, done, ent_coef, gamma, q, q_stride, scale,
+                                                             target_out, gq, loss_out, loss_sum, ap, n_critics, (int)batch);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_sac_actor_ens_loss_f32(const float *logp, const float *q, int64_t q_stride, const float *ent_coef, float *g_logp,
+                                           float *gq, float *loss_out, float *loss_sum, int n_critics, int64_t batch, cstr_stream_t stream)
+{
+    if (!logp || !q || !ent_coef || !g_logp || !gq || batch <= 0 || n_critics <= 0) return CSTR_E_BADARG;
+    if (n_critics > 1 && q_stride < batch) return CSTR_E_BADARG;
+    if (n_critics > CSTR_MAX_ENS_CRITICS || batch > CSTR_MAX_SAMPLE_BATCH) return CSTR_E_UNSUPPORTED;
+    sac_actor_ens_loss_kernel<<<1, 256, 0, (hipStream_t)stream>>>(logp, q, q_stride, ent_coef, g_logp, gq, loss_out, loss_sum, n_critics,
+                                                                  (int)batch);
     return (int)hipGetLastError();
 }
 

@@ -286,6 +286,19 @@ def _make_venv(N):
 
 
 def gen_sac():
+    for tag, net_arch, B, n_steps in (("small", [64, 64], 64, 3), ("default", None, 256, 2)):
+        _gen_sac(tag, net_arch, B, n_steps)
+
+
+def gen_sac_ncrit():
+    """SAC with policy_kwargs n_critics != 2 (reference core/common/policies.py:934-965; core/sac/sac.py:249-250, :261, :273-275):
+    every critic's mse_loss call is recorded, N per gradient step."""
+    _gen_sac("ncrit3", [64, 64], 64, 3, n_critics=3)
+    _gen_sac("ncrit3_default", None, 256, 2, n_critics=3)
+    _gen_sac("ncrit1", [64, 64], 64, 3, n_critics=1)
+
+
+def _gen_sac(tag, net_arch, B, n_steps, n_critics=2):
     import torch.distributions.normal as tdn
     import torch.nn.functional as F_real
 
@@ -293,85 +306,87 @@ def gen_sac():
     from core.common.logger import Logger
     from core.sac.sac import SAC
 
-    for tag, net_arch, B, n_steps in (("small", [64, 64], 64, 3), ("default", None, 256, 2)):
-        rec = _Recorder()
-        orig_sn = tdn._standard_normal
+    rec = _Recorder()
+    orig_sn = tdn._standard_normal
 
-        def rec_sn(shape, dtype, device):
-            e = orig_sn(shape, dtype, device)
-            rec.eps.append(e.clone())
-            return e
+    def rec_sn(shape, dtype, device):
+        e = orig_sn(shape, dtype, device)
+        rec.eps.append(e.clone())
+        return e
 
-        class FProxy:
-            def __getattr__(self, name):
-                return getattr(F_real, name)
+    class FProxy:
+        def __getattr__(self, name):
+            return getattr(F_real, name)
 
-            @staticmethod
-            def mse_loss(a, b, *args, **kw):
-                rec.mse.append((a.detach().clone(), b.detach().clone()))
-                return F_real.mse_loss(a, b, *args, **kw)
+        @staticmethod
+        def mse_loss(a, b, *args, **kw):
+            rec.mse.append((a.detach().clone(), b.detach().clone()))
+            return F_real.mse_loss(a, b, *args, **kw)
 
-        N, D, A = 4, 4, 2
-        venv = _make_venv(N)
-        pk = {} if net_arch is None else {"policy_kwargs": dict(net_arch=net_arch)}
-        model = SAC("MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
-        model.set_logger(Logger(folder=None, output_formats=[]))
-        rng = np.random.default_rng(99)
-        _fill_buffer(model, rng, 40, N, D, A)
-        out = {}
-        out.update(_flat_sd("before/actor", model.actor.state_dict()))
-        out.update(_flat_sd("before/critic", model.critic.state_dict()))
-        out.update(_flat_sd("before/critic_target", model.critic_target.state_dict()))
-        out["before/log_ent_coef"] = model.log_ent_coef.detach().numpy().copy()
-        rb = model.replay_buffer
-        out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
-                   ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
-                   ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
-        np.random.seed(2024)
-        th.manual_seed(77)
-        orig_sample = rb.sample
-        batches = []
+    N, D, A = 4, 4, 2
+    venv = _make_venv(N)
+    pk = {} if net_arch is None else {"policy_kwargs": dict(net_arch=net_arch)}
+    if n_critics != 2:
+        pk.setdefault("policy_kwargs", {})["n_critics"] = n_critics
+    model = SAC("MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
+    assert len(model.critic.q_networks) == n_critics
+    model.set_logger(Logger(folder=None, output_formats=[]))
+    rng = np.random.default_rng(99)
+    _fill_buffer(model, rng, 40, N, D, A)
+    out = {}
+    out.update(_flat_sd("before/actor", model.actor.state_dict()))
+    out.update(_flat_sd("before/critic", model.critic.state_dict()))
+    out.update(_flat_sd("before/critic_target", model.critic_target.state_dict()))
+    out["before/log_ent_coef"] = model.log_ent_coef.detach().numpy().copy()
+    rb = model.replay_buffer
+    out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
+               ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
+               ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
+    np.random.seed(2024)
+    th.manual_seed(77)
+    orig_sample = rb.sample
+    batches = []
 
-        def rec_sample(batch_size, env=None):
-            s = orig_sample(batch_size, env=env)
-            batches.append([x.numpy().copy() for x in s])
-            return s
+    def rec_sample(batch_size, env=None):
+        s = orig_sample(batch_size, env=env)
+        batches.append([x.numpy().copy() for x in s])
+        return s
 
-        rb.sample = rec_sample
-        tdn._standard_normal = rec_sn
-        sacmod.F = FProxy()
-        try:
-            for k in range(n_steps):
-                model.train(gradient_steps=1, batch_size=B)
-                lv = model.logger.name_to_value
-                out[f"step{k}/critic_loss"] = np.float32(lv["train/critic_loss"])
-                out[f"step{k}/actor_loss"] = np.float32(lv["train/actor_loss"])
-                out[f"step{k}/ent_coef_loss"] = np.float32(lv["train/ent_coef_loss"])
-                out[f"step{k}/ent_coef"] = np.float32(lv["train/ent_coef"])
-        finally:
-            tdn._standard_normal = orig_sn
-            sacmod.F = F_real
-            rb.sample = orig_sample
-        assert len(rec.eps) == 2 * n_steps and len(rec.mse) == 2 * n_steps
+    rb.sample = rec_sample
+    tdn._standard_normal = rec_sn
+    sacmod.F = FProxy()
+    try:
         for k in range(n_steps):
-            for fi, fname in enumerate(["observations", "actions", "next_observations", "dones", "rewards"]):
-                out[f"step{k}/batch_{fname}"] = batches[k][fi]
-            out[f"step{k}/eps_pi"] = rec.eps[2 * k].numpy()
-            out[f"step{k}/eps_next"] = rec.eps[2 * k + 1].numpy()
-            out[f"step{k}/current_q1"] = rec.mse[2 * k][0].numpy()
-            out[f"step{k}/current_q2"] = rec.mse[2 * k + 1][0].numpy()
-            out[f"step{k}/target_q"] = rec.mse[2 * k][1].numpy()
-        out.update(_flat_sd("after/actor", model.actor.state_dict()))
-        out.update(_flat_sd("after/critic", model.critic.state_dict()))
-        out.update(_flat_sd("after/critic_target", model.critic_target.state_dict()))
-        out["after/log_ent_coef"] = model.log_ent_coef.detach().numpy().copy()
-        out["hyper"] = np.array([model.gamma, model.tau, model.target_entropy, model.lr_schedule(1), B, n_steps], np.float64)
-        out["np_seed"], out["th_seed"] = np.int64(2024), np.int64(77)
-        if tag == "default":
-            # keep the committed fixture small: weights are reproducible from seed 0 (checked by the
-            # init KAT), so store only digests of the big tensors for the default-size nets
-            out = slim_weights(out, with_shape=False)
-        save(f"sac_train_kat_{tag}.npz", **out)
+            model.train(gradient_steps=1, batch_size=B)
+            lv = model.logger.name_to_value
+            out[f"step{k}/critic_loss"] = np.float32(lv["train/critic_loss"])
+            out[f"step{k}/actor_loss"] = np.float32(lv["train/actor_loss"])
+            out[f"step{k}/ent_coef_loss"] = np.float32(lv["train/ent_coef_loss"])
+            out[f"step{k}/ent_coef"] = np.float32(lv["train/ent_coef"])
+    finally:
+        tdn._standard_normal = orig_sn
+        sacmod.F = F_real
+        rb.sample = orig_sample
+    assert len(rec.eps) == 2 * n_steps and len(rec.mse) == n_critics * n_steps
+    for k in range(n_steps):
+        for fi, fname in enumerate(["observations", "actions", "next_observations", "dones", "rewards"]):
+            out[f"step{k}/batch_{fname}"] = batches[k][fi]
+        out[f"step{k}/eps_pi"] = rec.eps[2 * k].numpy()
+        out[f"step{k}/eps_next"] = rec.eps[2 * k + 1].numpy()
+        for i in range(n_critics):
+            out[f"step{k}/current_q{i + 1}"] = rec.mse[n_critics * k + i][0].numpy()
+        out[f"step{k}/target_q"] = rec.mse[n_critics * k][1].numpy()
+    out.update(_flat_sd("after/actor", model.actor.state_dict()))
+    out.update(_flat_sd("after/critic", model.critic.state_dict()))
+    out.update(_flat_sd("after/critic_target", model.critic_target.state_dict()))
+    out["after/log_ent_coef"] = model.log_ent_coef.detach().numpy().copy()
+    out["hyper"] = np.array([model.gamma, model.tau, model.target_entropy, model.lr_schedule(1), B, n_steps], np.float64)
+    out["np_seed"], out["th_seed"] = np.int64(2024), np.int64(77)
+    if net_arch is None:
+        # keep the committed fixture small: weights are reproducible from seed 0 (checked by the
+        # init KAT), so store only digests of the big tensors for the default-size nets
+        out = slim_weights(out, with_shape=False)
+    save(f"sac_train_kat_{tag}.npz", **out)
 
 
 def gen_td3():
@@ -384,10 +399,16 @@ def gen_ddpg():
     _gen_td3("default", algo="ddpg")
 
 
-def _gen_td3(tag, algo="td3"):
+def gen_td3_ncrit():
+    """TD3 with policy_kwargs n_critics=3 (core/td3/td3.py:174-175, :182): small nets, four steps (two policy updates)."""
+    _gen_td3("small", n_critics=3)
+
+
+def _gen_td3(tag, algo="td3", n_critics=None):
     """tag "small": net_arch [48, 32], batch 64; "default": the class default [400, 300] (td3/policies.py:141-145), batch 256.
     algo "ddpg": core/ddpg/ddpg.py:14-130 -- TD3.train with policy_delay 1, ONE critic (one mse_loss per step) and a
-    target-smoothing draw clamped to [-0, 0] (target_policy_noise 0.1, target_noise_clip 0.0)."""
+    target-smoothing draw clamped to [-0, 0] (target_policy_noise 0.1, target_noise_clip 0.0).
+    n_critics: policy_kwargs n_critics (None: the class default), written as {algo}_train_kat_ncrit{n}.npz."""
     import torch.nn.functional as F_real
 
     import core.td3.td3 as td3mod
@@ -396,7 +417,7 @@ def _gen_td3(tag, algo="td3"):
 
     if algo == "ddpg":
         from core.ddpg.ddpg import DDPG as TD3
-    n_q = 1 if algo == "ddpg" else 2
+    n_q = n_critics or (1 if algo == "ddpg" else 2)
 
     rec = _Recorder()
 
@@ -413,6 +434,8 @@ def _gen_td3(tag, algo="td3"):
     B = 64 if tag == "small" else 256
     venv = _make_venv(N)
     pk = dict(policy_kwargs=dict(net_arch=[48, 32])) if tag == "small" else {}
+    if n_critics is not None:
+        pk.setdefault("policy_kwargs", {})["n_critics"] = n_critics
     model = TD3("MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
     model.set_logger(Logger(folder=None, output_formats=[]))
     rng = np.random.default_rng(314)
@@ -453,16 +476,17 @@ def _gen_td3(tag, algo="td3"):
     for k in range(n_steps):
         for fi, fname in enumerate(["observations", "actions", "next_observations", "dones", "rewards"]):
             out[f"step{k}/batch_{fname}"] = batches[k][fi]
-        out[f"step{k}/current_q1"] = rec.mse[n_q * k][0].numpy()
-        if n_q == 2:
-            out[f"step{k}/current_q2"] = rec.mse[2 * k + 1][0].numpy()
+        for i in range(n_q):
+            out[f"step{k}/current_q{i + 1}"] = rec.mse[n_q * k + i][0].numpy()
         out[f"step{k}/target_q"] = rec.mse[n_q * k][1].numpy()
     for nm in ("actor", "actor_target", "critic", "critic_target"):
         out.update(_flat_sd(f"after/{nm}", getattr(model, nm).state_dict()))
     out["hyper"] = np.array([model.gamma, model.tau, model.target_policy_noise, model.target_noise_clip,
                              model.policy_delay, model.lr_schedule(1), B, n_steps], np.float64)
     out["np_seed"] = np.int64(555)
-    if tag == "default":
+    if n_critics is not None:
+        save(f"{algo}_train_kat_ncrit{n_critics}.npz", **out)
+    elif tag == "default":
         assert model.actor.mu[0].out_features == 400 and model.actor.mu[2].out_features == 300
         save(f"{algo}_train_kat_default.npz", **slim_weights(out))
     else:
@@ -899,6 +923,7 @@ def gen_vecnorm():
 
 
 GENS = {"maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+        "sac_ncrit": gen_sac_ncrit, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint}
 
 if __name__ == "__main__":
