@@ -521,6 +521,36 @@ int cstr_td_ens_q_loss_f32(const float *q_t, int64_t q_t_stride, const float *ne
 int cstr_sac_actor_ens_loss_f32(const float *logp, const float *q, int64_t q_stride, const float *ent_coef, float *g_logp, float *gq,
                                 float *loss_out, float *loss_sum, int n_critics, int64_t batch, cstr_stream_t stream);
 
+/* gSDE: generalized State-Dependent Exploration of SAC's actor (csrc/cstr_sde.hip; reference core/sac/policies.py:89-175,
+ * core/common/distributions.py:421-617). latent = L (last hidden width, <= CSTR_SDE_MAX_LATENT), act_dim = A (<= CSTR_MAX_HEAD_ACT).
+ * std [L][A] = get_std(log_std): exp, or expln when use_expln; log_std is [L][log_std_cols] with log_std_cols = A (full_std) or 1.
+ * cstr_sde_draw_f32: mats[k][L][A] = z[k][L][A] * std for k < n_mats (Normal(0, std).rsample); z is drawn when rng_ctl is given
+ *   (Philox4x32-10 stream of cstr_gaussian_head_fwd_f32's layout, the last workgroup advances rng_ctl[1]) and read otherwise; a drawn z
+ *   is stored for the first z_keep (0..n_mats) matrices only (the rollout's per-env matrices need no z).
+ *   std_out [L][A] is optional.
+ * cstr_sde_head_fwd_f32: per row of h [batch][ldh]: pre = h W^T + b, mean = Hardtanh(pre, +-clip_mean) (none when clip_mean <= 0),
+ *   x = mean + h M (M = mats + row * mat_stride: mat_stride 0 = one shared matrix; mats NULL = the mode), action = tanh(x),
+ *   logp = sum Normal(mean, sqrt((h^2)(std^2) + 1e-6)).log_prob(atanh(clamp(action))) - sum log(1 - tanh(.)^2 + 1e-6).
+ *   aux [batch][2A] (pre, variance) is what the backward needs; logp and aux are optional.
+ * cstr_sde_head_bwd_f32: the autograd gradient of the forward (through the atanh round trip): g_pre / g_x / g_var [batch][A] (each
+ *   optional) and dh [batch][L] (optional) times the activation gradient below_act (0 none, 1 ReLU, 2 tanh) of the layer that made h.
+ * cstr_sde_param_grad_f32: dw_mu [A][L] = g_pre^T h, db_mu [A], dlog_std [L][log_std_cols] = std' * (z * h^T g_x + 2 std * (h^2)^T g_var)
+ *   for a shared matrix M = z * std (z NULL: no noise term). */
+#define CSTR_SDE_MAX_LATENT 4096
+#define CSTR_SDE_MAX_MATS 65537
+int cstr_sde_draw_f32(const float *log_std, int log_std_cols, int latent, int act_dim, int use_expln, int64_t n_mats, float *std_out,
+                      float *z, int64_t z_keep, float *mats, uint64_t *rng_ctl, cstr_stream_t stream);
+int cstr_sde_head_fwd_f32(const float *h, int64_t ldh, int64_t batch, int latent, int act_dim, const float *w_mu, const float *b_mu,
+                          float clip_mean, const float *mats, int64_t mat_stride, const float *std_mat, float *action, int64_t action_stride,
+                          float *logp, float *aux, cstr_stream_t stream);
+int cstr_sde_head_bwd_f32(const float *g_action, int64_t g_action_stride, const float *g_logp, const float *action, int64_t action_stride,
+                          const float *aux, const float *h, int64_t ldh, int64_t batch, int latent, int act_dim, const float *w_mu,
+                          float clip_mean, const float *mats, int64_t mat_stride, const float *std_mat, int below_act, float *g_pre,
+                          float *g_x, float *g_var, float *dh, cstr_stream_t stream);
+int cstr_sde_param_grad_f32(const float *h, int64_t ldh, int64_t batch, int latent, int act_dim, const float *g_pre, const float *g_x,
+                            const float *g_var, const float *z, const float *std_mat, const float *log_std, int log_std_cols, int use_expln,
+                            float *dw_mu, float *db_mu, float *dlog_std, cstr_stream_t stream);
+
 /* Deterministic-policy actor loss (core/td3/td3.py:194, core/maddpg/maddpg.py:174): loss = -mean(q), gq = -1/B. */
 int cstr_neg_mean_loss_f32(const float *q, float *gq, float *loss_out, float *loss_sum, int64_t batch, cstr_stream_t stream);
 

@@ -17,6 +17,7 @@ MAX_NOISE_PERIOD = 8
 VECNORM_STATE_WORDS = 20
 RNG_CTL_WORDS, MAX_HEAD_ACT, MAX_LINEAR_SETS, MAX_ADAM_SEGS = 16, 4, 16, 4
 MAX_ENS_CRITICS = 16
+SDE_MAX_LATENT, SDE_MAX_MATS = 4096, 65537
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -27,6 +28,7 @@ SYMBOLS = (
     "cstr_sac_actor_loss_f32", "cstr_neg_mean_loss_f32", "cstr_td_ens_q_loss_f32", "cstr_sac_actor_ens_loss_f32",
     "cstr_sac_actor_chain_fwd_f32", "cstr_q_chain_fwd_f32", "cstr_q_chain_bwd_f32", "cstr_sac_actor_chain_bwd_f32",
     "cstr_linear_bwd_weight_adam_sets_f32", "cstr_chain_sum_parts_f32",
+    "cstr_sde_draw_f32", "cstr_sde_head_fwd_f32", "cstr_sde_head_bwd_f32", "cstr_sde_param_grad_f32",
 )
 
 

@@ -42,8 +42,6 @@ class BaseAlgorithm:
         self._last_episode_starts = None
         self._last_original_obs = None
         self._episode_num = 0
-        if use_sde:
-            raise NotImplementedError("gSDE is out of scope for the CSTR path (SURVEY 2)")
         self.use_sde, self.sde_sample_freq = use_sde, sde_sample_freq
         self._current_progress_remaining = 1.0
         self._stats_window_size = stats_window_size
@@ -124,6 +122,9 @@ class BaseAlgorithm:
         fa = getattr(self, "_fast_actor", None)
         if fa is not None and hasattr(fa, "seed_rng"):
             fa.seed_rng(seed + 1000003 * self.rank)
+        dist = getattr(getattr(getattr(self, "policy", None), "actor", None), "action_dist", None)  # gSDE exploration-matrix stream
+        if hasattr(dist, "seed_rng"):
+            dist.seed_rng(seed + 1000003 * self.rank)
         ctl = getattr(self, "_rng_ctl", None)  # target-smoothing noise stream (TD3 / MADDPG)
         if ctl is not None:
             from core.common import hip_ops
@@ -316,6 +317,8 @@ class BaseAlgorithm:
         for k in ("num_timesteps", "_n_updates", "_episode_num", "_total_timesteps", "_num_timesteps_at_start"):
             if k in data:
                 setattr(model, k, data[k])
+        if model.use_sde:
+            model.policy.reset_noise()  # :823-824
         return model
 
     @classmethod

@@ -50,6 +50,8 @@ class SacChain:
     def supported(model, batch_size: int) -> bool:
         if not (USE_CHAIN and fused.USE_FUSED_LINEAR and model.fused_learner and model._use_packed_batch()):
             return False
+        if getattr(model, "use_sde", False):  # gSDE actors run on the per-layer fused path
+            return False
         if len(model.critic.q_networks) != 2:  # the chain root has twin slots: other n_critics run on the per-layer fused path
             return False
         fa = model._fast_actor

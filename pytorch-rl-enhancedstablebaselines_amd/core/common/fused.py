@@ -640,9 +640,10 @@ class FastSacActor:
     def __init__(self, actor, head=None):
         self.actor = actor
         self.latent = FastMLP(actor.latent_pi)
-        self.mu, self.log_std = actor.mu, actor.log_std
-        self.act_dim = actor.mu.weight.shape[0]
-        self.head = head
+        self.sde = getattr(actor, "use_sde", False)  # gSDE actor: the head is _SdeHeadFn, no merged head, no pair / rollout forms
+        self.mu, self.log_std = (actor.mu_linear, None) if self.sde else (actor.mu, actor.log_std)
+        self.act_dim = self.mu.weight.shape[0]
+        self.head = None if self.sde else head
         self.rng_ctl = None  # in-kernel Philox stream of the sampling head, seeded from torch's seed at first use
         self.deferred_rng = None  # (rng_ctl, rows) of a whole-network launch that left the stream offset to its caller (`defer_rng`)
         if head is not None:
@@ -672,7 +673,7 @@ class FastSacActor:
 
     def rollout_operands(self, obs: th.Tensor) -> Optional[dict]:
         """The sampling actor as operands of hip_ops.rollout_step (Philox noise from this actor's stream), or None."""
-        if self.head is None or self.act_dim > hip_ops.nv.MAX_HEAD_ACT or self.actor.action_dist.eps_queue:
+        if self.sde or self.head is None or self.act_dim > hip_ops.nv.MAX_HEAD_ACT or self.actor.action_dist.eps_queue:
             return None
         with th.no_grad():
             if not self._whole_net_ok(obs, train_params=False):
@@ -691,6 +692,8 @@ class FastSacActor:
     def pair_supported(self, pb) -> bool:
         """`action_log_prob_pair` applies: fused Linear kernels, two hidden layers with one activation, merged head, a packed
         batch whose x_pi / x_next are the halves of one buffer, and zero or two teacher-forced noise tensors queued."""
+        if self.sde:  # the 2B-row pass has the squashed-Gaussian head only
+            return False
         layers = self.latent.layers
         q = self.actor.action_dist.eps_queue
         return (USE_FUSED_LINEAR and USE_ACTOR_PAIR and self.head is not None and self.act_dim <= hip_ops.nv.MAX_HEAD_ACT and len(layers) == 2
@@ -732,6 +735,10 @@ class FastSacActor:
         `defer_rng`: the rollout's caller advances the Philox offset itself (the fused collect launch that consumes the action
         does it in its last-workgroup epilogue): when the whole-network launch runs it skips its own 256-workgroup ticket and
         `self.deferred_rng` = (rng_ctl, rows) tells the caller what to pass on; otherwise `self.deferred_rng` stays None."""
+        if self.sde:
+            if xbuf is not None or eps is not None:
+                raise NotImplementedError("gSDE actor: no critic-input buffer / explicit eps form")
+            return self.sde_action_log_prob(obs, train_params, want_logp)
         dist = self.actor.action_dist
         if eps is None and dist.eps_queue:  # teacher-forced draw (tests)
             eps = dist.draw_eps((obs.shape[0], self.act_dim), obs.device)
@@ -770,6 +777,71 @@ class FastSacActor:
             with th.no_grad():
                 out = _GaussianHeadFn.apply(*args)
         return (out[0], out[1]) if want_logp else (out[0], None)
+
+
+    def sde_action_log_prob(self, obs: th.Tensor, train_params: bool = True, want_logp: bool = True, deterministic: bool = False):
+        """gSDE (core/sac/policies.py:147-175 with use_sde): the latent net, then ONE head launch (_SdeHeadFn) with the exploration
+        matrices of the last reset: one per row when the batch has their count (get_noise), the shared `exploration_mat` otherwise."""
+        dist = self.actor.action_dist
+        std_b, z, mats, n = dist.current
+        rows = obs.shape[0]
+        m = None if deterministic else (mats[1:] if dist.noise_rows(rows) else mats[0])
+        h = self.latent(obs, train_params, out_grad_is_dz=True)  # the head runs the latent net's last activation gradient
+        grad = th.is_grad_enabled() and (h.requires_grad or train_params)
+        tp = train_params and grad
+        below = self.latent.tail_below(train_params) if h.requires_grad else None
+        lin, log_std = self.mu, self.actor.log_std
+        grads = (lin.weight.grad, lin.bias.grad, log_std.grad) if tp else None
+        if tp and any(g is None for g in grads):
+            raise RuntimeError("gSDE head: parameter gradients must be views of a ParamArena gradient buffer")
+        clip = float(self.actor.clip_mean)
+        args = (h, lin.weight, lin.bias, log_std, m, z[0] if m is not None and m.dim() == 2 else None, std_b, clip, dist.use_expln, grads,
+                tp, want_logp, below)
+        if grad:
+            out = _SdeHeadFn.apply(*args, *((lin.weight, log_std) if tp else ()))
+        else:
+            with th.no_grad():
+                out = _SdeHeadFn.apply(*args)
+        return (out[0], out[1]) if want_logp else (out[0], None)
+
+
+class _SdeHeadFn(th.autograd.Function):
+    """gSDE head: forward = ONE launch (mean GEMV + bias + Hardtanh, noise, variance, tanh, the reference's log-prob); backward = ONE
+    launch for the per-row gradients and dh (the latent's last activation gradient inside) + ONE for dW, db and d log_std."""
+
+    @staticmethod
+    def forward(ctx, h, w, b, log_std, mats, z, std_b, clip: float, expln: bool, grads, train_params: bool, want_logp: bool, below, *owners):
+        n, a = h.shape[0], w.shape[0]
+        e = lambda *sh: th.empty(*sh, dtype=h.dtype, device=h.device)  # noqa: E731
+        action, logp, aux = e(n, a), (e(n) if want_logp else None), e(n, 2 * a)
+        hip_ops.sde_head_fwd(h, w, b, clip, mats, std_b, action, logp, aux)
+        ctx.save_for_backward(h, w, log_std, action, aux)
+        ctx.mats, ctx.z, ctx.std_b, ctx.clip, ctx.expln = mats, z, std_b, clip, expln  # reset-time buffers: not redrawn before the backward
+        ctx.grads, ctx.train_params, ctx.below, ctx.n_owners = grads, train_params, below, len(owners)
+        ctx.set_materialize_grads(False)
+        return (action, logp) if want_logp else (action,)
+
+    @staticmethod
+    def backward(ctx, g_action, g_logp=None):
+        h, w, log_std, action, aux = ctx.saved_tensors
+        n_none = 12 + ctx.n_owners
+        if g_action is None and g_logp is None:
+            return (None,) * (n_none + 1)
+        if g_action is not None and g_action.stride(1) != 1:
+            g_action = g_action.contiguous()
+        g_logp = None if g_logp is None else g_logp.contiguous()
+        n, a = action.shape
+        e = lambda *sh: th.empty(*sh, dtype=h.dtype, device=h.device)  # noqa: E731
+        g_pre, g_x, g_var = e(n, a), e(n, a), e(n, a)
+        dh = e(n, h.shape[1]) if ctx.needs_input_grad[0] else None
+        below = ACT_NONE if ctx.below is None else ctx.below[0]
+        hip_ops.sde_head_bwd(g_action, g_logp, action, aux, h, w, ctx.clip, ctx.mats, ctx.std_b, below, g_pre, g_x, g_var, dh)
+        if ctx.train_params:
+            if ctx.mats is not None and ctx.mats.dim() == 3:
+                raise NotImplementedError("gSDE head: log_std gradient through per-row matrices (the learner uses the shared one)")
+            wg, bg, lsg = ctx.grads
+            hip_ops.sde_param_grad(h, g_pre, g_x, g_var, ctx.z, ctx.std_b, log_std.detach(), ctx.expln, wg, bg, lsg)
+        return (dh,) + (None,) * n_none
 
 
 class _MergedHeadFn(th.autograd.Function):

@@ -964,6 +964,93 @@ def sac_actor_ens_loss(logp, q, ent_coef, g_logp, gq, loss_out=None, loss_sum=No
           "cstr_sac_actor_ens_loss_f32")
 
 
+# ---- gSDE (csrc/cstr_sde.hip, include/cstr_rl_hip.h "gSDE") ------------------------------------------------------------------
+def _sde_dims(log_std, act_dim: int):
+    if log_std.dim() != 2 or log_std.shape[1] not in (1, act_dim):
+        raise ValueError(f"log_std: needs [L, {act_dim}] or [L, 1], got {tuple(log_std.shape)}")
+    L = log_std.shape[0]
+    if not 1 <= act_dim <= nv.MAX_HEAD_ACT or not 1 <= L <= nv.SDE_MAX_LATENT:
+        raise ValueError(f"gSDE head: latent width {L} / action dim {act_dim} out of range (<= {nv.SDE_MAX_LATENT} / <= {nv.MAX_HEAD_ACT})")
+    _chk(log_std, "log_std", tuple(log_std.shape), th.float32)
+    return L, log_std.shape[1]
+
+
+def sde_draw(log_std, act_dim: int, use_expln: bool, z, mats, std_out=None, rng_ctl=None, z_keep: Optional[int] = None):
+    """mats [n, L, A] = z * get_std(log_std) (cstr_sde_draw_f32); z [n, L, A] is drawn from `rng_ctl`'s Philox stream (whose offset
+    the launch advances on the device) when given and read otherwise; a drawn z is stored for the first `z_keep` matrices (default:
+    all); std_out [L, A] optional."""
+    L, cols = _sde_dims(log_std, act_dim)
+    n = mats.shape[0]
+    _chk(mats, "mats", (n, L, act_dim), th.float32), _chk(z, "z", (n, L, act_dim), th.float32)
+    _opt(std_out, "std_out", (L, act_dim), th.float32), _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    check(nv.lib().cstr_sde_draw_f32(ptr(log_std), C.c_int(cols), C.c_int(L), C.c_int(act_dim), C.c_int(int(use_expln)), C.c_int64(n),
+                                     ptr(std_out), ptr(z), C.c_int64(n if z_keep is None else z_keep), ptr(mats), ptr(rng_ctl),
+                                     stream_ptr()), "cstr_sde_draw_f32")
+
+
+def _sde_mats(mats, b: int, L: int, a: int):
+    """(pointer owner, row stride of the matrices): [L, A] = one shared matrix, [B, L, A] = one per row, None = the mode."""
+    if mats is None:
+        return None, 0
+    if mats.dim() == 2:
+        return _chk(mats, "mats", (L, a), th.float32), 0
+    return _chk(mats, "mats", (b, L, a), th.float32), L * a
+
+
+def sde_head_fwd(h, w_mu, b_mu, clip_mean: float, mats, std_mat, action, logp=None, aux=None):
+    """The gSDE head forward (cstr_sde_head_fwd_f32) from the latent h [B, L] (row stride allowed): action [B, A] (row-strided view
+    allowed) = tanh(Hardtanh(h W^T + b) + h M); logp [B] and aux [B, 2A] optional. mats: see `_sde_mats`."""
+    b, L = h.shape
+    a = w_mu.shape[0]
+    if h.stride(1) != 1 or h.stride(0) < L or not h.is_cuda or h.dtype != th.float32:
+        raise ValueError("h: needs a float32 device matrix with unit column stride")
+    _chk(w_mu, "w_mu", (a, L), th.float32), _chk(b_mu, "b_mu", (a,), th.float32), _chk(std_mat, "std_mat", (L, a), th.float32)
+    m, ms = _sde_mats(mats, b, L, a)
+    stride = _rows(action, "action", b, a)
+    _opt(logp, "logp", (b,), th.float32), _opt(aux, "aux", (b, 2 * a), th.float32)
+    check(nv.lib().cstr_sde_head_fwd_f32(ptr(h), C.c_int64(h.stride(0)), C.c_int64(b), C.c_int(L), C.c_int(a), ptr(w_mu), ptr(b_mu),
+                                         C.c_float(clip_mean), ptr(m), C.c_int64(ms), ptr(std_mat), ptr(action), C.c_int64(stride), ptr(logp),
+                                         ptr(aux), stream_ptr()), "cstr_sde_head_fwd_f32")
+
+
+def sde_head_bwd(g_action, g_logp, action, aux, h, w_mu, clip_mean: float, mats, std_mat, below_act: int, g_pre, g_x, g_var, dh=None):
+    """Per-row gradients of the gSDE head (cstr_sde_head_bwd_f32): g_pre / g_x / g_var [B, A] and dh [B, L] (times the activation
+    gradient `below_act` of the layer that produced h)."""
+    b, L = h.shape
+    a = w_mu.shape[0]
+    if h.stride(1) != 1 or h.stride(0) < L:
+        raise ValueError("h: needs unit column stride")
+    gs = _rows(g_action, "g_action", b, a) if g_action is not None else 0
+    _opt(g_logp, "g_logp", (b,), th.float32)
+    astr = _rows(action, "action", b, a)
+    _chk(aux, "aux", (b, 2 * a), th.float32), _chk(w_mu, "w_mu", (a, L), th.float32), _chk(std_mat, "std_mat", (L, a), th.float32)
+    m, ms = _sde_mats(mats, b, L, a)
+    for t, nm in ((g_pre, "g_pre"), (g_x, "g_x"), (g_var, "g_var")):
+        _opt(t, nm, (b, a), th.float32)
+    _opt(dh, "dh", (b, L), th.float32)
+    check(nv.lib().cstr_sde_head_bwd_f32(ptr(g_action), C.c_int64(gs), ptr(g_logp), ptr(action), C.c_int64(astr), ptr(aux), ptr(h),
+                                         C.c_int64(h.stride(0)), C.c_int64(b), C.c_int(L), C.c_int(a), ptr(w_mu), C.c_float(clip_mean), ptr(m),
+                                         C.c_int64(ms), ptr(std_mat), C.c_int(below_act), ptr(g_pre), ptr(g_x), ptr(g_var), ptr(dh),
+                                         stream_ptr()), "cstr_sde_head_bwd_f32")
+
+
+def sde_param_grad(h, g_pre, g_x, g_var, z, std_mat, log_std, use_expln: bool, dw_mu=None, db_mu=None, dlog_std=None):
+    """dW_mu [A, L], db_mu [A] and d log_std (log_std's shape) of a batch, reduced in one launch (cstr_sde_param_grad_f32); z [L, A] is
+    the shared matrix's standard-normal draw (None: no noise term)."""
+    b, L = h.shape
+    a = g_pre.shape[1]
+    if h.stride(1) != 1 or h.stride(0) < L:
+        raise ValueError("h: needs unit column stride")
+    _, cols = _sde_dims(log_std, a)
+    for t, nm in ((g_pre, "g_pre"), (g_x, "g_x"), (g_var, "g_var")):
+        _chk(t, nm, (b, a), th.float32)
+    _opt(z, "z", (L, a), th.float32), _chk(std_mat, "std_mat", (L, a), th.float32)
+    _opt(dw_mu, "dw_mu", (a, L), th.float32), _opt(db_mu, "db_mu", (a,), th.float32), _opt(dlog_std, "dlog_std", (L, cols), th.float32)
+    check(nv.lib().cstr_sde_param_grad_f32(ptr(h), C.c_int64(h.stride(0)), C.c_int64(b), C.c_int(L), C.c_int(a), ptr(g_pre), ptr(g_x),
+                                           ptr(g_var), ptr(z), ptr(std_mat), ptr(log_std), C.c_int(cols), C.c_int(int(use_expln)),
+                                           ptr(dw_mu), ptr(db_mu), ptr(dlog_std), stream_ptr()), "cstr_sde_param_grad_f32")
+
+
 def neg_mean_loss(q, gq, loss_out=None, loss_sum=None):
     b = q.numel()
     _vec(q, "q", b), _vec(gq, "gq", b)

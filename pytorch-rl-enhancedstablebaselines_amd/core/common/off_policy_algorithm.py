@@ -23,6 +23,7 @@ from core import _native as nv
 from core.common.base_class import BaseAlgorithm
 from core.common.buffers import ReplayBuffer
 from core.common.callbacks import BaseCallback, MaybeCallback, to_callback
+from core.common.logger import DeviceMean
 from core.common.type_aliases import RolloutReturn, TrainFreq, TrainFrequencyUnit
 from core.common.utils import should_collect_more_steps
 from core.common.vec_env import CSTRVecEnv, VecEnv
@@ -44,10 +45,14 @@ class OffPolicyAlgorithm(BaseAlgorithm):
                  tensorboard_log: Optional[str] = None, verbose: int = 0, device="auto", support_multi_env: bool = False,
                  monitor_wrapper: bool = True, seed: Optional[int] = None, use_sde: bool = False, sde_sample_freq: int = -1,
                  use_sde_at_warmup: bool = False, sde_support: bool = True, supported_action_spaces: Optional[tuple] = None):
+        if use_sde and not sde_support:  # TD3 / DDPG / MADDPG / IDDPG (sde_support=False in the reference too)
+            raise ValueError(f"{type(self).__name__} does not support gSDE (use_sde=True)")
         super().__init__(policy=policy, env=env, learning_rate=learning_rate, policy_kwargs=policy_kwargs,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, verbose=verbose, device=device,
                          support_multi_env=support_multi_env, monitor_wrapper=monitor_wrapper, seed=seed, use_sde=use_sde,
                          sde_sample_freq=sde_sample_freq, supported_action_spaces=supported_action_spaces)
+        if sde_support and (use_sde or "use_sde" in self.policy_kwargs):
+            self.policy_kwargs["use_sde"] = self.use_sde  # reference :137-138
         self.buffer_size = buffer_size
         self.batch_size = batch_size
         self.learning_starts = learning_starts
@@ -228,6 +233,7 @@ class OffPolicyAlgorithm(BaseAlgorithm):
     def _graph_body(self) -> None:
         env, rb, vn = self._denv, self.replay_buffer, self._vec_normalize_env
         self.policy.set_training_mode(False)
+        self._sde_rollout_resets(0)
         noise = None if self.action_noise is None else self.action_noise().contiguous()
         net = self._rollout_net() if (FUSED_ROLLOUT and vn is None and self._use_packed_batch()) else None
         if net is not None:
@@ -440,6 +446,20 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         cap["graph"] = th.cuda.CUDAGraph()
         cap["graph"].capture_begin(pool=cap["pool"], capture_error_mode="thread_local")
 
+    def _sde_rollout_resets(self, num_collected_steps: int) -> None:
+        """gSDE: the exploration matrices are redrawn (one per env) when a rollout starts (:550-551) and every `sde_sample_freq`
+        collected steps (:556-558); a graph-captured iteration is a one-step rollout and records both draws."""
+        if not self.use_sde:
+            return
+        if num_collected_steps == 0:
+            self.policy.reset_noise(self.env.num_envs)
+        if self.sde_sample_freq > 0 and num_collected_steps % self.sde_sample_freq == 0:
+            self.policy.reset_noise(self.env.num_envs)
+
+    def _warmup(self, learning_starts: int) -> bool:
+        """:386: uniform warm-up actions, unless gSDE acts from the start (use_sde_at_warmup)"""
+        return self.num_timesteps < learning_starts and not (self.use_sde and self.use_sde_at_warmup)
+
     # ---- action selection -----------------------------------------------------------------------------------------
     def _action_mode(self, warmup: bool) -> int:
         """`squashed` bit field of cstr_collect_step_f32: bit 0 = the input is the actor's tanh output (predict()
@@ -457,7 +477,7 @@ class OffPolicyAlgorithm(BaseAlgorithm):
 
     def _sample_action(self, learning_starts: int, action_noise=None, n_envs: int = 1):
         """reference: off_policy_algorithm.py:364-411 (NumPy compatibility path)"""
-        if self.num_timesteps < learning_starts:
+        if self._warmup(learning_starts):
             unscaled_action = self.action_space.sample_batch(n_envs)
         else:
             assert self._last_obs is not None, "self._last_obs was not set"
@@ -484,6 +504,9 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         self.logger.record("time/fps", fps)
         self.logger.record("time/time_elapsed", int(time_elapsed), exclude="tensorboard")
         self.logger.record("time/total_timesteps", self.num_timesteps, exclude="tensorboard")
+        if self.use_sde:  # :429-430, resolved when the logger writes
+            with th.no_grad():
+                self.logger.record("train/std", DeviceMean(self.actor.get_std().mean(), 1))
         self.logger.dump(step=self.num_timesteps)
 
     def _sync_episode_stats(self, log_interval: Optional[int], force: bool = False) -> None:
@@ -530,6 +553,7 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         callback.on_rollout_start()
         continue_training = True
         while should_collect_more_steps(train_freq, num_collected_steps, num_collected_episodes):
+            self._sde_rollout_resets(num_collected_steps)
             if fast:
                 self._collect_one_fused(env.unwrapped, replay_buffer, action_noise, learning_starts)
                 new_obs, rewards, dones = self._last_obs, env._rew, env._done  # device tensors (for callbacks)
@@ -568,7 +592,7 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         """One vec-step entirely in HBM: reference statements :561 (_sample_action), :564 (env.step), :580
         (_store_transition -> ReplayBuffer.add) in one HIP launch after the actor forward."""
         n, vn = env.num_envs, self._vec_normalize_env
-        if self.num_timesteps < learning_starts:
+        if self._warmup(learning_starts):
             # warm-up: uniform actions from the action space's own generator (:386-388); drawn on the host
             pol = th.as_tensor(self.action_space.sample_batch(n)).to(self.device)
             squashed = self._action_mode(warmup=True)

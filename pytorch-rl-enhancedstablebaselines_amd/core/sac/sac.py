@@ -83,6 +83,8 @@ class SAC(OffPolicyAlgorithm):
             self._fast_actor = fused.FastSacActor(self.actor, self.policy.actor_head)
             self._fast_critic = fused.FastTwinCritic(self.critic, self.policy.critic_stack)
             self._fast_critic_target = fused.FastTwinCritic(self.critic_target, self.policy.critic_target_stack)
+        if self.use_sde:  # the ATen path differentiates the matrices as torch expressions; the fused head reads the draw buffers
+            self.actor.action_dist.torch_matrices = not self.fused_learner
 
     def _fused_supported(self) -> bool:
         from core.common.arena import FlatAdam
@@ -162,6 +164,8 @@ class SAC(OffPolicyAlgorithm):
             self.logger.record("train/ent_coef_loss", DeviceMean(s["ent_coef_loss"], gradient_steps))
 
     def _gradient_step(self, batch_size: int, gradient_step: int) -> None:
+        if self.use_sde:  # :218-219 -- log_std may have changed since the last draw
+            self.actor.reset_noise()
         if self.fused_learner:
             return self._gradient_step_fused(batch_size, gradient_step)
         return self._gradient_step_aten(batch_size, gradient_step)
@@ -380,11 +384,14 @@ class SAC(OffPolicyAlgorithm):
         return state_dicts, ["ent_coef_tensor"]
 
     def _extra_save_data(self) -> dict:
-        return dict(ent_coef=self.ent_coef, target_update_interval=self.target_update_interval, target_entropy=self.target_entropy)
+        data = dict(ent_coef=self.ent_coef, target_update_interval=self.target_update_interval, target_entropy=self.target_entropy)
+        if self.use_sde:
+            data.update(use_sde=True, sde_sample_freq=self.sde_sample_freq, use_sde_at_warmup=self.use_sde_at_warmup)
+        return data
 
     @classmethod
     def _ctor_keys(cls) -> tuple:
-        return super()._ctor_keys() + ("ent_coef", "target_update_interval", "target_entropy")
+        return super()._ctor_keys() + ("ent_coef", "target_update_interval", "target_entropy", "use_sde", "sde_sample_freq", "use_sde_at_warmup")
 
     def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "SAC",
               reset_num_timesteps: bool = True, progress_bar: bool = False):

@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,td3,init,vecenv]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,init,vecenv]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -298,7 +298,79 @@ def gen_sac_ncrit():
     _gen_sac("ncrit1", [64, 64], 64, 3, n_critics=1)
 
 
-def _gen_sac(tag, net_arch, B, n_steps, n_critics=2):
+def gen_sac_sde():
+    """SAC with gSDE (use_sde=True; reference core/sac/policies.py:89-175, core/common/distributions.py:421-617, core/sac/sac.py:218-219):
+    the construction draws (exploration_mat [L, A], then exploration_matrices [1, L, A]) and the two draws of every gradient step's
+    reset_noise() are recorded from torch's _standard_normal, in call order."""
+    _gen_sac("sde_small", [64, 64], 64, 3, sde={})
+    _gen_sac("sde_default", None, 256, 2, sde={})
+    _gen_sac("sde_variants", [64, 64], 64, 3, sde=dict(use_expln=True, full_std=False, clip_mean=0.0))
+    _gen_sac_sde_predict()
+
+
+def _gen_sac_sde_predict():
+    """predict() of a gSDE SAC on 4 envs: per-env matrices (reset_noise(4)), one env (exploration_mat), deterministic, and after one
+    gradient step (its batch-1 draw: every row uses exploration_mat)."""
+    import torch.distributions.normal as tdn
+
+    from core.common.logger import Logger
+    from core.sac.sac import SAC
+
+    draws = []
+    orig_sn = tdn._standard_normal
+
+    def rec_sn(shape, dtype, device):
+        e = orig_sn(shape, dtype, device)
+        draws.append(e.clone())
+        return e
+
+    N, D, A, B = 4, 4, 2, 64
+    tdn._standard_normal = rec_sn
+    try:
+        model = SAC("MlpPolicy", _make_venv(N), seed=0, device="cpu", batch_size=B, buffer_size=64 * N, use_sde=True,
+                    policy_kwargs=dict(net_arch=[64, 64]))
+        model.set_logger(Logger(folder=None, output_formats=[]))
+        out = {}
+        out.update(_flat_sd("before/actor", model.actor.state_dict()))
+        out.update(_flat_sd("before/critic", model.critic.state_dict()))
+        out.update(_flat_sd("before/critic_target", model.critic_target.state_dict()))
+        assert len(draws) == 2
+        out["init/z_mat"], out["init/z_mats"] = draws[0].numpy(), draws[1].numpy()
+        rng = np.random.default_rng(5)
+        obs = rng.uniform(-1, 1, (N, D)).astype(np.float32)
+        out["obs"] = obs
+
+        def actor_out(x, deterministic=False):
+            with th.no_grad():
+                return model.actor(th.as_tensor(x), deterministic=deterministic).numpy().copy()
+
+        model.actor.reset_noise(N)
+        out["per_env/z_mat"], out["per_env/z_mats"] = draws[2].numpy(), draws[3].numpy()
+        out["per_env/actions"] = actor_out(obs)
+        out["per_env/predict"] = model.predict(obs)[0]
+        out["single/actions"] = actor_out(obs[:1])
+        out["single/predict"] = model.predict(obs[:1])[0]
+        out["deterministic/actions"] = actor_out(obs, True)
+        out["deterministic/predict"] = model.predict(obs, deterministic=True)[0]
+        _fill_buffer(model, np.random.default_rng(99), 40, N, D, A)
+        rb = model.replay_buffer
+        out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
+                   ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
+                   ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
+        np.random.seed(2024)
+        model.train(gradient_steps=1, batch_size=B)
+        assert len(draws) == 6
+        out["train/z_mat"], out["train/z_mats"] = draws[4].numpy(), draws[5].numpy()
+        out.update(_flat_sd("after/actor", model.actor.state_dict()))
+        out["after_train/actions"] = actor_out(obs)
+        out["after_train/predict"] = model.predict(obs)[0]
+    finally:
+        tdn._standard_normal = orig_sn
+    out["np_seed"] = np.int64(2024)
+    save("sac_sde_predict_kat.npz", **out)
+
+
+def _gen_sac(tag, net_arch, B, n_steps, n_critics=2, sde=None):
     import torch.distributions.normal as tdn
     import torch.nn.functional as F_real
 
@@ -328,7 +400,31 @@ def _gen_sac(tag, net_arch, B, n_steps, n_critics=2):
     pk = {} if net_arch is None else {"policy_kwargs": dict(net_arch=net_arch)}
     if n_critics != 2:
         pk.setdefault("policy_kwargs", {})["n_critics"] = n_critics
-    model = SAC("MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
+    if sde is not None:  # gSDE: the construction draws are recorded too
+        sde = dict(sde)
+        policy = "MlpPolicy"
+        if "full_std" in sde:  # the reference's SACPolicy has no full_std argument: its Actor's, set through the actor kwargs
+            from core.sac.policies import SACPolicy
+
+            full_std = sde.pop("full_std")
+
+            class FullStdPolicy(SACPolicy):
+                def make_actor(self, features_extractor=None):
+                    self.actor_kwargs["full_std"] = full_std
+                    return super().make_actor(features_extractor)
+
+            policy = FullStdPolicy
+        if sde:
+            pk.setdefault("policy_kwargs", {}).update(sde)
+        tdn._standard_normal = rec_sn
+        try:
+            model = SAC(policy, venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, use_sde=True, **pk)
+        finally:
+            tdn._standard_normal = orig_sn
+        assert len(rec.eps) == 2
+        init_draws, rec.eps = rec.eps, []
+    else:
+        model = SAC("MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
     assert len(model.critic.q_networks) == n_critics
     model.set_logger(Logger(folder=None, output_formats=[]))
     rng = np.random.default_rng(99)
@@ -368,11 +464,17 @@ def _gen_sac(tag, net_arch, B, n_steps, n_critics=2):
         sacmod.F = F_real
         rb.sample = orig_sample
     assert len(rec.eps) == 2 * n_steps and len(rec.mse) == n_critics * n_steps
+    if sde is not None:  # per gradient step: reset_noise()'s exploration_mat, then exploration_matrices
+        out["init/z_mat"], out["init/z_mats"] = init_draws[0].numpy(), init_draws[1].numpy()
     for k in range(n_steps):
         for fi, fname in enumerate(["observations", "actions", "next_observations", "dones", "rewards"]):
             out[f"step{k}/batch_{fname}"] = batches[k][fi]
-        out[f"step{k}/eps_pi"] = rec.eps[2 * k].numpy()
-        out[f"step{k}/eps_next"] = rec.eps[2 * k + 1].numpy()
+        if sde is not None:
+            out[f"step{k}/z_mat"] = rec.eps[2 * k].numpy()
+            out[f"step{k}/z_mats"] = rec.eps[2 * k + 1].numpy()
+        else:
+            out[f"step{k}/eps_pi"] = rec.eps[2 * k].numpy()
+            out[f"step{k}/eps_next"] = rec.eps[2 * k + 1].numpy()
         for i in range(n_critics):
             out[f"step{k}/current_q{i + 1}"] = rec.mse[n_critics * k + i][0].numpy()
         out[f"step{k}/target_q"] = rec.mse[n_critics * k][1].numpy()
@@ -386,7 +488,7 @@ def _gen_sac(tag, net_arch, B, n_steps, n_critics=2):
         # keep the committed fixture small: weights are reproducible from seed 0 (checked by the
         # init KAT), so store only digests of the big tensors for the default-size nets
         out = slim_weights(out, with_shape=False)
-    save(f"sac_train_kat_{tag}.npz", **out)
+    save(f"sac_sde_train_kat_{tag[len('sde_'):]}.npz" if sde is not None else f"sac_train_kat_{tag}.npz", **out)
 
 
 def gen_td3():
@@ -923,7 +1025,7 @@ def gen_vecnorm():
 
 
 GENS = {"maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
-        "sac_ncrit": gen_sac_ncrit, "td3_ncrit": gen_td3_ncrit,
+        "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint}
 
 if __name__ == "__main__":
