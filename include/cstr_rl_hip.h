@@ -713,6 +713,54 @@ int cstr_sac_actor_chain_bwd_f32(const cstr_sac_actor_t *actor, const float *gac
                                  const float *x_pi, const float *params, const float *eps, const float *a_h1, const float *a_h2,
                                  float *g_params, float *dz2, float *dz1, int64_t batch, int kind, int tiles, cstr_stream_t stream);
 
+/* ---- BCQ: the arithmetic around the Linear layers of an offline gradient step (core/bcq/bcq.py:137-213) ---------------------------
+ * Row-major f32 operands; `ld*` = row stride in floats (a column block of a wider matrix is fine). Each entry point validates on the
+ * host (NULL, sizes, strides, overlapping input / output rows -> CSTR_E_BADARG; latent > CSTR_BCQ_MAX_LATENT, act_dim >
+ * CSTR_BCQ_MAX_ACT, samples > CSTR_BCQ_MAX_SAMPLES, more than CSTR_BCQ_MAX_ROWS rows -> CSTR_E_UNSUPPORTED), then only enqueues.
+ * Noise: exactly one of a noise array (read) or rng_ctl [CSTR_RNG_CTL_WORDS] (drawn: Philox4x32-10 + Box-Muller on BCQ's own
+ * stream tag, element pair p uses counter rng_ctl[1] + p; the last workgroup advances rng_ctl[1] by the pairs drawn).
+ * cstr_bcq_latent_fwd_f32 (core/bcq/policies.py:76-85): params [batch][ldp] = [mean | log_std_raw] (2 latent columns);
+ *   std = exp(clamp(log_std_raw, -4, 15)); xdec [batch][ldx] = [obs | mean + std * eps]; std_out, eps_out [batch][latent] for the
+ *   backward (eps_out optional when eps_in is given).
+ * cstr_bcq_vae_loss_f32 (bcq.py:145-149): loss = mse(recon, act) + 0.5 * (-0.5 * mean(1 + log(std * std) - mean^2 - std^2));
+ *   g_recon [batch][act_dim], g_mean / g_std [batch][latent] (the KL term's gradients) -- each optional; loss_out[0] = loss,
+ *   loss_sum[0] += loss (each optional).
+ * cstr_bcq_latent_bwd_f32: g_params [batch][2 latent] = [g_z + g_mean_kl | (g_z * eps + g_std_kl) * std where -4 <= log_std_raw <= 15,
+ *   else 0]; g_z [batch][ldg] (the latent columns of the decoder input's gradient), g_mean_kl, g_std_kl: each optional, not all NULL.
+ * cstr_bcq_expand_f32 (policies.py:122-124, :247; bcq.py:164): rows = n_states * samples; xdec row r = [state[r % n_states] |
+ *   clamp(noise, -clip, clip)]; xa / xb (optional, [rows][ld]): their first obs_dim columns = state[r % n_states].
+ * cstr_bcq_perturb_fwd_f32 (policies.py:165-166): out = clamp(a_vae + p * max_perturbation, -1, 1).
+ * cstr_bcq_perturb_bwd_f32: g_p [rows][act_dim] = g_out * max_perturbation where the clamp is inactive (closed interval), else 0.
+ * cstr_bcq_target_f32 (bcq.py:167-173): q [n_critics][q_stride], rows = n_states * samples in [sample][state] order; per row the min
+ *   over the critics, then per state i the max over a group of `samples` rows: grouping 0 = rows samples * i ... samples * i +
+ *   samples - 1 (the reference's reshape(B, samples)), grouping 1 = rows i + n_states * s (the state's own candidates);
+ *   max_q_out[i] = that (optional), target_out[i] = rew[i] + (1 - done[i]) * gamma * that (optional; needs rew, done).
+ * cstr_bcq_select_f32 (policies.py:429-435, per state): index_out[i] (optional) = the row i + n_states * s with the largest q1
+ *   (first maximum wins), action_out [n_states][act_dim] = cand[that row]. */
+#define CSTR_BCQ_MAX_LATENT 256
+#define CSTR_BCQ_MAX_ACT 64
+#define CSTR_BCQ_MAX_SAMPLES 4096
+#define CSTR_BCQ_MAX_ROWS 16777216
+int cstr_bcq_latent_fwd_f32(const float *params, int64_t ldp, const float *obs, int64_t ldo, const float *eps_in, uint64_t *rng_ctl,
+                            float *xdec, int64_t ldx, float *std_out, float *eps_out, int64_t batch, int obs_dim, int latent,
+                            cstr_stream_t stream);
+int cstr_bcq_vae_loss_f32(const float *recon, int64_t ldr, const float *act, int64_t lda, const float *params, int64_t ldp,
+                          const float *std, int64_t batch, int act_dim, int latent, float *g_recon, float *g_mean, float *g_std,
+                          float *loss_out, float *loss_sum, cstr_stream_t stream);
+int cstr_bcq_latent_bwd_f32(const float *g_z, int64_t ldg, const float *g_mean_kl, const float *g_std_kl, const float *params, int64_t ldp,
+                            const float *std, const float *eps, float *g_params, int64_t batch, int latent, cstr_stream_t stream);
+int cstr_bcq_expand_f32(const float *state, int64_t lds, int64_t n_states, int samples, int obs_dim, int latent, const float *noise,
+                        uint64_t *rng_ctl, float clip, float *xdec, int64_t ldx, float *xa, int64_t lda, float *xb, int64_t ldb,
+                        cstr_stream_t stream);
+int cstr_bcq_perturb_fwd_f32(const float *a_vae, int64_t lda, const float *p, int64_t ldp, float max_perturbation, float *out, int64_t ldo,
+                             int64_t rows, int act_dim, cstr_stream_t stream);
+int cstr_bcq_perturb_bwd_f32(const float *g_out, int64_t ldg, const float *a_vae, int64_t lda, const float *p, int64_t ldp,
+                             float max_perturbation, float *g_p, int64_t rows, int act_dim, cstr_stream_t stream);
+int cstr_bcq_target_f32(const float *q, int64_t q_stride, int n_critics, int64_t n_states, int samples, int grouping, const float *rew,
+                        const float *done, float gamma, float *target_out, float *max_q_out, cstr_stream_t stream);
+int cstr_bcq_select_f32(const float *q1, const float *cand, int64_t ldc, int64_t n_states, int samples, int act_dim, int64_t *index_out,
+                        float *action_out, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,7 @@ VECNORM_STATE_WORDS = 20
 RNG_CTL_WORDS, MAX_HEAD_ACT, MAX_LINEAR_SETS, MAX_ADAM_SEGS = 16, 4, 16, 4
 MAX_ENS_CRITICS = 16
 SDE_MAX_LATENT, SDE_MAX_MATS = 4096, 65537
+BCQ_MAX_LATENT, BCQ_MAX_ACT, BCQ_MAX_SAMPLES, BCQ_MAX_ROWS = 256, 64, 4096, 1 << 24
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -29,6 +30,8 @@ SYMBOLS = (
     "cstr_sac_actor_chain_fwd_f32", "cstr_q_chain_fwd_f32", "cstr_q_chain_bwd_f32", "cstr_sac_actor_chain_bwd_f32",
     "cstr_linear_bwd_weight_adam_sets_f32", "cstr_chain_sum_parts_f32",
     "cstr_sde_draw_f32", "cstr_sde_head_fwd_f32", "cstr_sde_head_bwd_f32", "cstr_sde_param_grad_f32",
+    "cstr_bcq_latent_fwd_f32", "cstr_bcq_vae_loss_f32", "cstr_bcq_latent_bwd_f32", "cstr_bcq_expand_f32", "cstr_bcq_perturb_fwd_f32",
+    "cstr_bcq_perturb_bwd_f32", "cstr_bcq_target_f32", "cstr_bcq_select_f32",
 )
 
 

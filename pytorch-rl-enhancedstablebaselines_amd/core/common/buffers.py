@@ -120,6 +120,20 @@ class ReplayBuffer(BaseBuffer):
         self.normalizer = None
         self._predrawn = None
 
+    @classmethod
+    def from_arrays(cls, observation_space, action_space, device, observations, next_observations, actions, rewards, dones, timeouts,
+                    pos: int = 0, full: bool = True) -> "ReplayBuffer":
+        """A buffer holding the given host arrays: observations / next_observations [R, N, D], actions [R, N, A], rewards / dones /
+        timeouts [R, N] (the reference's attribute shapes, buffers.py:212-234); `pos`, `full` as the reference keeps them."""
+        rows, n_envs = np.shape(rewards)
+        rb = cls(rows * n_envs, observation_space, action_space, device=device, n_envs=n_envs)
+        for name, arr in zip(cls._FIELDS, (observations, next_observations, actions, rewards, dones, timeouts)):
+            field = getattr(rb, name)
+            field.copy_(th.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).reshape(field.shape))
+        rb._adds = int(pos) + (rb.buffer_size if full else 0)
+        rb.ring.ctl.copy_(th.tensor([int(pos), int(bool(full)), 0, rb._adds], dtype=th.int64))
+        return rb
+
     def to(self, device) -> "ReplayBuffer":
         """Move the ring to another GPU (load_replay_buffer: 'update saved replay buffer device', :252-253)."""
         device = get_device(device)

@@ -12,7 +12,9 @@ leaves every GEMM to PyTorch-ROCm (`torch.mm` -> rocBLAS) with the HIP epilogues
     carry the loss that roots it (`set_loss_root`: TD critic loss, SAC actor loss);
   * deterministic actors write their action into the critic input and read its gradient columns in place (`_LinearXbufFn`,
     `_ActorGroupFn`): no torch.cat, no gather copies;
-  * `squashed_gaussian([mean | log_std], eps)` = 1 launch forward, 1 launch backward (analytic).
+  * `squashed_gaussian([mean | log_std], eps)` = 1 launch forward, 1 launch backward (analytic);
+  * BCQ (`FastBcq`): the VAE latent (`_VaeLatentFn`) and the perturbation step (`_PerturbFn`) = 1 launch forward, 1 backward each,
+    candidates expanded into the decoder / perturbation / critic inputs by one launch.
 
 The nn.Modules keep owning the parameters (state_dict / API); `FastMLP` only reads their tensors. Arithmetic per
 element is the reference's (core/common/torch_layers.py:110-183, core/common/distributions.py:161-260).
@@ -844,6 +846,157 @@ class _SdeHeadFn(th.autograd.Function):
         return (dh,) + (None,) * n_none
 
 
+class _VaeLatentFn(th.autograd.Function):
+    """BCQ's VAE latent (core/bcq/policies.py:76-85): the merged (mean | log_std) head Linear on the encoder output + ONE launch for
+    clamp, exp, z = mean + std * eps and the decoder input [obs | z] (`xdec`, which is the output); eps is read when given and drawn
+    in the kernel otherwise. Backward = ONE launch (g_z from the decoder input's gradient + the KL term's gradients that the loss
+    launch has left in `gkl` = (d/dmean, d/dstd) buffers) + the head's dW / db + its input gradient carried through the encoder's
+    last activation. Also returns (params, std) for the loss launch, non-differentiable."""
+
+    @staticmethod
+    def forward(ctx, h, w, b, wg, bg, obs, eps, rng_ctl, xdec, gkl, train_params: bool, below, *owners):
+        params = _linear_fwd(h, w, b, ACT_NONE)
+        n, lat = params.shape[0], params.shape[1] // 2
+        std = th.empty(n, lat, dtype=params.dtype, device=params.device)
+        eps_kept = eps if eps is not None else th.empty(n, lat, dtype=params.dtype, device=params.device)
+        hip_ops.bcq_latent_fwd(params, obs, eps, None if eps is not None else rng_ctl, xdec, std, None if eps is not None else eps_kept)
+        ctx.save_for_backward(h, w, params, std, eps_kept)
+        ctx.wgrad, ctx.bgrad, ctx.train_params, ctx.below, ctx.gkl = wg, bg, train_params, below, gkl
+        ctx.obs_dim, ctx.n_owners = obs.shape[1], len(owners)
+        ctx.set_materialize_grads(False)
+        ctx.mark_dirty(xdec)
+        ctx.mark_non_differentiable(params, std)
+        return xdec, params, std
+
+    @staticmethod
+    def backward(ctx, g_xdec, _gp=None, _gs=None):
+        h, w, params, std, eps = ctx.saved_tensors
+        g_z = None
+        if g_xdec is not None:
+            if g_xdec.stride(1) != 1:
+                g_xdec = g_xdec.contiguous()
+            g_z = g_xdec[:, ctx.obs_dim:]
+        gkl_mean, gkl_std = ctx.gkl if ctx.gkl is not None else (None, None)
+        g_params = hip_ops.bcq_latent_bwd(g_z, gkl_mean, gkl_std, params, std, eps, th.empty_like(params))
+        _param_grads(ctx, g_params, h)
+        dx = _input_grad(g_params, w, h, ctx.below) if ctx.needs_input_grad[0] else None
+        return (dx,) + (None,) * (11 + ctx.n_owners)
+
+
+class _PerturbFn(th.autograd.Function):
+    """BCQ's perturbation step (core/bcq/policies.py:165-166): a = clamp(a_vae + max_perturbation * p, -1, 1) written into the action
+    columns of a critic input `xbuf` (observation columns already filled), which is the output; backward: g_p = max_perturbation *
+    g_a where the clamp is inactive, read from those columns of the buffer's gradient in place. a_vae is a constant (the VAE takes
+    no gradient from the actor loss, bcq.py:196-198)."""
+
+    @staticmethod
+    def forward(ctx, p, a_vae, max_perturbation: float, xbuf):
+        a = p.shape[1]
+        hip_ops.bcq_perturb_fwd(a_vae, p, max_perturbation, xbuf[:, xbuf.shape[1] - a:])
+        ctx.save_for_backward(p, a_vae)
+        ctx.mp, ctx.a = max_perturbation, a
+        ctx.mark_dirty(xbuf)
+        return xbuf
+
+    @staticmethod
+    def backward(ctx, g_buf):
+        p, a_vae = ctx.saved_tensors
+        if g_buf.stride(1) != 1:
+            g_buf = g_buf.contiguous()
+        g_p = hip_ops.bcq_perturb_bwd(g_buf[:, g_buf.shape[1] - ctx.a:], a_vae, p, ctx.mp, th.empty_like(p))
+        return g_p, None, None, None
+
+
+class FastBcq:
+    """core/bcq/policies.py on the kernel path: the VAE (encoder, merged head, latent launch, decoder), the candidate expansion, the
+    perturbation step, the twin critics and predict's selection. Buffers are static per row count (graph-capturable)."""
+
+    def __init__(self, policy):
+        a, at = policy.actor, policy.actor_target
+        self.policy = policy
+        self.enc, self.dec, self.pert = FastMLP(a.vae.encoder), FastMLP(a.vae.decoder), FastMLP(a.perturbation.model)
+        self.dec_t, self.pert_t = FastMLP(at.vae.decoder), FastMLP(at.perturbation.model)
+        self.critic = FastTwinCritic(policy.critic, policy.critic_stack)
+        self.critic_t = FastTwinCritic(policy.critic_target, policy.critic_target_stack)
+        self.head = policy.vae_head
+        self.head_owners = (a.vae.mean.weight, a.vae.log_std.weight)
+        self.obs_dim, self.latent = a.features_dim, a.vae.latent_dim
+        self.act_dim = a.vae.decoder[-2].out_features
+        self.max_perturbation = float(a.perturbation.max_perturbation)
+        self.rng_ctl = None  # Philox stream of the latent / candidate draws (the algorithm shares its own with this object)
+        self._bufs: dict = {}
+
+    @staticmethod
+    def supported(policy) -> bool:
+        a = policy.actor
+        mlps = (a.vae.encoder, a.vae.decoder, a.perturbation.model, *policy.critic.q_networks)
+        return (len(policy.critic.q_networks) == 2 and getattr(policy, "critic_stack", None) is not None
+                and hip_ops.bcq_supported(a.vae.latent_dim, a.vae.action_dim, 100) and all(FastMLP.supported(m) for m in mlps)
+                and len(FastMLP(a.vae.decoder).layers) >= 2)
+
+    def _rng(self, device):
+        if self.rng_ctl is None:
+            self.rng_ctl = hip_ops.new_rng_ctl(th.initial_seed(), device)
+        return self.rng_ctl
+
+    def bufs(self, rows: int, device, tag: str = ""):
+        """(decoder input [rows, D + L], perturbation-net input [rows, D + A], critic input [rows, D + A])"""
+        key = (rows, tag)
+        if key not in self._bufs:
+            d, z = self.obs_dim, lambda *sh: th.zeros(*sh, dtype=th.float32, device=device)  # noqa: E731
+            self._bufs[key] = (z(rows, d + self.latent), z(rows, d + self.act_dim), z(rows, d + self.act_dim))
+        return self._bufs[key]
+
+    def candidates(self, state: th.Tensor, samples: int, noise, target: bool, with_grad: bool = False, tag: str = "") -> th.Tensor:
+        """The critic input [n S, D + A] of `samples` perturbed candidates per state (core/bcq/policies.py:244-253): ONE expansion launch
+        (no repeat / cat / randn / clamp launches), the decoder's last layer writes a_vae into the perturbation net's input, the
+        perturbation launch writes the action columns of the critic input. with_grad: the perturbation net is differentiated (the
+        actor step); the decoder never is."""
+        n = state.shape[0]
+        xdec, xp, xc = self.bufs(n * samples, state.device, tag)
+        d = self.obs_dim
+        dec, pert = (self.dec_t, self.pert_t) if target else (self.dec, self.pert)
+        with th.no_grad():
+            hip_ops.bcq_expand(state, samples, noise, None if noise is not None else self._rng(state.device), xdec, xp, xc)
+            h = xdec
+            for lin, act in dec.layers[:-1]:
+                h = _linear_fwd(h, lin.weight, lin.bias, act)
+            lin, act = dec.layers[-1]
+            if USE_FUSED_LINEAR:
+                hip_ops.linear_act_fwd_sets([(h, lin.weight, lin.bias, xp[:, d:])], act)
+            else:
+                xp[:, d:].copy_(_linear_fwd(h, lin.weight, lin.bias, act))
+            if not with_grad:
+                p = xp
+                for lin, act in pert.layers:
+                    p = _linear_fwd(p, lin.weight, lin.bias, act)
+                hip_ops.bcq_perturb_fwd(xp[:, d:], p, self.max_perturbation, xc[:, d:])
+                return xc
+        p = self.pert(xp, train_params=True)
+        return _PerturbFn.apply(p, xp[:, d:], self.max_perturbation, xc.detach())  # detached: the static buffer carries no history
+
+    def vae_forward(self, x_data: th.Tensor, obs: th.Tensor, eps, gkl):
+        """(recon with the VAE's autograd history, params [B, 2L], std [B, L]) of core/bcq/policies.py:67-87 on x_data = [obs | act]."""
+        h = self.enc(x_data, train_params=True, out_grad_is_dz=True)
+        hw, hb, hwg, hbg = self.head
+        xdec = self.bufs(x_data.shape[0], x_data.device, "vae")[0]
+        out, params, std = _VaeLatentFn.apply(h, hw, hb, hwg, hbg, obs, eps, None if eps is not None else self._rng(x_data.device),
+                                              xdec.detach(), gkl, True, self.enc.tail_below(True), *self.head_owners)
+        return self.dec(out, train_params=True), params, std
+
+    def predict(self, obs: th.Tensor, samples: int, noise=None) -> th.Tensor:
+        """core/bcq/policies.py:426-435 per observation: [n, A]."""
+        n = obs.shape[0]
+        with th.no_grad():
+            xc = self.candidates(obs, samples, noise, target=False, tag="predict")
+            q1 = self.critic.forward_input(xc, train_params=False, only_first=True)[0]
+            action = th.empty(n, self.act_dim, dtype=th.float32, device=obs.device)
+            hip_ops.bcq_select(q1.reshape(-1), xc[:, self.obs_dim:], n, samples, None, action)
+            if getattr(self.policy, "debug_capture", False):
+                self.policy.last_predict = dict(q1=q1.clone(), candidates=xc[:, self.obs_dim:].clone())
+        return action
+
+
 class _MergedHeadFn(th.autograd.Function):
     @staticmethod
     def forward(ctx, h, w, b, wg, bg, train_params: bool, *owners):
@@ -1108,6 +1261,28 @@ def twin_pair_forward(critic: "FastTwinCritic", target: "FastTwinCritic", x_data
     out = QOut(q_c[i] for i in range(2))
     out.stacked = q_c
     return out, (q_t[0], q_t[1])
+
+
+def twin_chain_forward(critic: "FastTwinCritic", x_data: th.Tensor) -> "QOut":
+    """The critic half of `twin_pair_forward` on its own (BCQ: the target critics see ten times the rows, so the two passes cannot share
+    launches): every layer of both Q networks as ONE pointer-table launch, the backward of `_TwinPairFn`. Needs `twin_chain_supported`."""
+    cs = [(w, b) for w, _, b, _ in critic.stack]
+    m = x_data.shape[0]
+    e = lambda n: th.empty(2, m, n, dtype=x_data.dtype, device=x_data.device)  # noqa: E731
+    outs = (e(cs[0][0].shape[1]), e(cs[1][0].shape[1]), e(1))
+    for li, ((w, b), out) in enumerate(zip(cs, outs)):
+        hip_ops.linear_act_fwd_sets([(x_data if li == 0 else outs[li - 1][g], w[g], b[g], out[g]) for g in range(2)],
+                                    critic.acts[0] if li < 2 else ACT_NONE)
+    grads = [(wg, bg) for _, wg, _, bg in critic.stack]
+    owners = [p for layer in critic.owners for p in layer]
+    q_c, _ = _TwinPairFn.apply(x_data, x_data, cs, cs, grads, critic.acts[0], outs, *owners)
+    out = QOut(q_c[i] for i in range(2))
+    out.stacked = q_c
+    return out
+
+
+def twin_chain_supported(critic: "FastTwinCritic") -> bool:
+    return twin_pair_supported(critic, critic)
 
 
 def twin_pair_forward_many(critics, targets, x_data: th.Tensor, x_next: th.Tensor) -> list:

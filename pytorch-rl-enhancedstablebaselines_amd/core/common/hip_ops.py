@@ -1051,6 +1051,138 @@ def sde_param_grad(h, g_pre, g_x, g_var, z, std_mat, log_std, use_expln: bool, d
                                            ptr(dw_mu), ptr(db_mu), ptr(dlog_std), stream_ptr()), "cstr_sde_param_grad_f32")
 
 
+# ---- BCQ (csrc/cstr_bcq.hip; reference core/bcq/bcq.py:137-213, core/bcq/policies.py) ------------------------------------------------
+def bcq_supported(latent: int, act_dim: int, samples: int = 1) -> bool:
+    """Widths the BCQ kernels take (cstr_bcq_*: CSTR_E_UNSUPPORTED beyond them)."""
+    return 0 < latent <= nv.BCQ_MAX_LATENT and 0 < act_dim <= nv.BCQ_MAX_ACT and 0 < samples <= nv.BCQ_MAX_SAMPLES
+
+
+def _one_noise(noise, rng_ctl, shape, what: str):
+    if (noise is None) == (rng_ctl is None):
+        raise ValueError(f"{what} needs exactly one noise source: a noise tensor or rng_ctl")
+    _opt(noise, "noise", shape, th.float32), _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+
+
+def bcq_latent_fwd(params, obs, eps, rng_ctl, xdec, std_out, eps_out=None):
+    """xdec [B, D + L] = [obs | mean + exp(clamp(log_std_raw, -4, 15)) * eps] from params [B, 2L] = [mean | log_std_raw]; eps [B, L] is
+    read, or drawn (rng_ctl) and stored in eps_out; std_out [B, L] (policies.py:76-85)."""
+    b, l2 = params.shape
+    L = l2 // 2
+    d = obs.shape[1]
+    _chk(params, "params", (b, 2 * L), th.float32), _chk(xdec, "xdec", (b, d + L), th.float32), _chk(std_out, "std_out", (b, L), th.float32)
+    ldo = _rows(obs, "obs", b, d)
+    _one_noise(eps, rng_ctl, (b, L), "bcq_latent_fwd")
+    _opt(eps_out, "eps_out", (b, L), th.float32)
+    if rng_ctl is not None and eps_out is None:
+        raise ValueError("bcq_latent_fwd: drawn noise needs eps_out")
+    check(nv.lib().cstr_bcq_latent_fwd_f32(ptr(params), C.c_int64(2 * L), ptr(obs), C.c_int64(ldo), ptr(eps), ptr(rng_ctl), ptr(xdec),
+                                           C.c_int64(d + L), ptr(std_out), ptr(eps_out), C.c_int64(b), C.c_int(d), C.c_int(L), stream_ptr()),
+          "cstr_bcq_latent_fwd_f32")
+    return xdec
+
+
+def bcq_vae_loss(recon, act, params, std, g_recon=None, g_mean=None, g_std=None, loss_out=None, loss_sum=None):
+    """mse(recon, act) + 0.5 * (-0.5 * mean(1 + log(std^2) - mean^2 - std^2)) (bcq.py:145-149): the logged scalar and the gradients
+    w.r.t. recon and, for the KL term, mean / std."""
+    b, a = recon.shape
+    L = std.shape[1]
+    ldr, lda = _rows(recon, "recon", b, a), _rows(act, "act", b, a)
+    _chk(params, "params", (b, 2 * L), th.float32), _chk(std, "std", (b, L), th.float32)
+    _opt(g_recon, "g_recon", (b, a), th.float32), _opt(g_mean, "g_mean", (b, L), th.float32), _opt(g_std, "g_std", (b, L), th.float32)
+    for t, nm in ((loss_out, "loss_out"), (loss_sum, "loss_sum")):
+        if t is not None:
+            _vec(t, nm, 1)
+    check(nv.lib().cstr_bcq_vae_loss_f32(ptr(recon), C.c_int64(ldr), ptr(act), C.c_int64(lda), ptr(params), C.c_int64(2 * L), ptr(std),
+                                         C.c_int64(b), C.c_int(a), C.c_int(L), ptr(g_recon), ptr(g_mean), ptr(g_std), ptr(loss_out),
+                                         ptr(loss_sum), stream_ptr()), "cstr_bcq_vae_loss_f32")
+
+
+def bcq_latent_bwd(g_z, g_mean_kl, g_std_kl, params, std, eps, g_params):
+    """g_params [B, 2L] = [g_z + g_mean_kl | (g_z * eps + g_std_kl) * std masked by the clamp]; g_z may be the latent columns of the
+    decoder input's gradient (row-strided view)."""
+    b, L = std.shape
+    _chk(params, "params", (b, 2 * L), th.float32), _chk(std, "std", (b, L), th.float32), _chk(eps, "eps", (b, L), th.float32)
+    _chk(g_params, "g_params", (b, 2 * L), th.float32)
+    ldg = L if g_z is None else _rows(g_z, "g_z", b, L)
+    _opt(g_mean_kl, "g_mean_kl", (b, L), th.float32), _opt(g_std_kl, "g_std_kl", (b, L), th.float32)
+    check(nv.lib().cstr_bcq_latent_bwd_f32(ptr(g_z), C.c_int64(ldg), ptr(g_mean_kl), ptr(g_std_kl), ptr(params), C.c_int64(2 * L), ptr(std),
+                                           ptr(eps), ptr(g_params), C.c_int64(b), C.c_int(L), stream_ptr()), "cstr_bcq_latent_bwd_f32")
+    return g_params
+
+
+def bcq_expand(state, samples: int, noise, rng_ctl, xdec, xa=None, xb=None, clip: float = 0.5):
+    """xdec [n S, D + L] row r = [state[r % n] | clamp(noise, -clip, clip)] (noise [n S, L] raw, or drawn from rng_ctl); the first D
+    columns of xa / xb [n S, >= D] (the perturbation net's and the critics' inputs) receive state[r % n] too (policies.py:122-124)."""
+    if (noise is None) == (rng_ctl is None):
+        raise ValueError("bcq_expand needs exactly one noise source: a noise tensor or rng_ctl")
+    n, d = state.shape
+    lds = _rows(state, "state", n, d)
+    rows = n * samples
+    if xdec.dim() != 2 or xdec.shape[1] <= d:
+        raise ValueError("xdec: needs [n * samples, obs_dim + latent]")
+    L = xdec.shape[1] - d
+    _chk(xdec, "xdec", (rows, d + L), th.float32)
+    _one_noise(noise, rng_ctl, (rows, L), "bcq_expand")
+    lds_x = []
+    for t, nm in ((xa, "xa"), (xb, "xb")):
+        if t is not None and (t.dim() != 2 or t.shape[1] < d):
+            raise ValueError(f"{nm}: needs at least obs_dim columns")
+        lds_x.append(0 if t is None else _rows(t, nm, rows, t.shape[1]))
+    check(nv.lib().cstr_bcq_expand_f32(ptr(state), C.c_int64(lds), C.c_int64(n), C.c_int(samples), C.c_int(d), C.c_int(L), ptr(noise),
+                                       ptr(rng_ctl), C.c_float(clip), ptr(xdec), C.c_int64(d + L), ptr(xa), C.c_int64(lds_x[0]), ptr(xb),
+                                       C.c_int64(lds_x[1]), stream_ptr()), "cstr_bcq_expand_f32")
+    return xdec
+
+
+def bcq_perturb_fwd(a_vae, p, max_perturbation: float, out):
+    """out = clamp(a_vae + p * max_perturbation, -1, 1) (policies.py:165-166); a_vae / out may be column blocks of wider buffers."""
+    rows, a = p.shape
+    lda, ldp, ldo = _rows(a_vae, "a_vae", rows, a), _rows(p, "p", rows, a), _rows(out, "out", rows, a)
+    check(nv.lib().cstr_bcq_perturb_fwd_f32(ptr(a_vae), C.c_int64(lda), ptr(p), C.c_int64(ldp), C.c_float(max_perturbation), ptr(out),
+                                            C.c_int64(ldo), C.c_int64(rows), C.c_int(a), stream_ptr()), "cstr_bcq_perturb_fwd_f32")
+    return out
+
+
+def bcq_perturb_bwd(g_out, a_vae, p, max_perturbation: float, g_p):
+    """g_p [rows, A] = g_out * max_perturbation where -1 <= a_vae + p * max_perturbation <= 1, else 0."""
+    rows, a = p.shape
+    ldg, lda, ldp = _rows(g_out, "g_out", rows, a), _rows(a_vae, "a_vae", rows, a), _rows(p, "p", rows, a)
+    _chk(g_p, "g_p", (rows, a), th.float32)
+    check(nv.lib().cstr_bcq_perturb_bwd_f32(ptr(g_out), C.c_int64(ldg), ptr(a_vae), C.c_int64(lda), ptr(p), C.c_int64(ldp),
+                                            C.c_float(max_perturbation), ptr(g_p), C.c_int64(rows), C.c_int(a), stream_ptr()),
+          "cstr_bcq_perturb_bwd_f32")
+    return g_p
+
+
+def bcq_target(q, n_states: int, samples: int, reference_grouping: bool, rew, done, gamma: float, target_out, max_q_out=None):
+    """q [N, n S, 1] or [N, n S] (contiguous): min over the N critics per row, max over groups of S rows -- the reference's grouping
+    (S consecutive flat rows, bcq.py:171-172) or the state's own candidates (rows i + n s) -- and the TD target (bcq.py:173)."""
+    nq = q.shape[0]
+    rows = n_states * samples
+    if not (isinstance(q, th.Tensor) and q.is_cuda and q.dtype == th.float32 and q.is_contiguous() and q.numel() == nq * rows):
+        raise ValueError(f"q: needs a contiguous float32 device tensor [N, {rows}(, 1)]")
+    if target_out is not None:
+        _vec(target_out, "target_out", n_states), _vec(rew, "rew", n_states), _vec(done, "done", n_states)
+    if max_q_out is not None:
+        _vec(max_q_out, "max_q_out", n_states)
+    check(nv.lib().cstr_bcq_target_f32(ptr(q), C.c_int64(rows), C.c_int(nq), C.c_int64(n_states), C.c_int(samples),
+                                       C.c_int(0 if reference_grouping else 1), ptr(rew), ptr(done), C.c_float(gamma), ptr(target_out),
+                                       ptr(max_q_out), stream_ptr()), "cstr_bcq_target_f32")
+    return target_out
+
+
+def bcq_select(q1, cand, n_states: int, samples: int, index_out, action_out):
+    """Per state the row (i + n s) of its largest q1 (first maximum wins, as argmax) and that row of cand [n S, A] (policies.py:429-435)."""
+    rows = n_states * samples
+    _vec(q1, "q1", rows)
+    a = cand.shape[1]
+    ldc = _rows(cand, "cand", rows, a)
+    _opt(index_out, "index_out", (n_states,), th.int64), _chk(action_out, "action_out", (n_states, a), th.float32)
+    check(nv.lib().cstr_bcq_select_f32(ptr(q1), ptr(cand), C.c_int64(ldc), C.c_int64(n_states), C.c_int(samples), C.c_int(a), ptr(index_out),
+                                       ptr(action_out), stream_ptr()), "cstr_bcq_select_f32")
+    return action_out
+
+
 def neg_mean_loss(q, gq, loss_out=None, loss_sum=None):
     b = q.numel()
     _vec(q, "q", b), _vec(gq, "gq", b)

@@ -296,13 +296,11 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         return max(u, 1)
 
     def _graph_iteration(self, log_interval: Optional[int], callback: Optional[BaseCallback] = None) -> None:
-        vn = self._vec_normalize_env
         opt = getattr(getattr(self.policy, "actor", None), "optimizer", None)
         if getattr(opt, "shadow", None) is not None:  # torch changed the actor's weights (a callback, load_state_dict): the
             opt.refresh_shadow(force=False)           # replayed graph reads their tile-major copy -- one version compare
         unroll = self._graph_unroll_now()
-        key = (id(self._denv.coef), self.batch_size, self.gradient_steps, self._graph_phase(), None if vn is None else (id(vn), vn.cfg_key),
-               unroll)
+        key = self._graph_cache_key(unroll)
         if not isinstance(self._graph, dict):
             self._graph, self._graph_warm = {}, {}
         if key not in self._graph:
@@ -336,6 +334,12 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         self._graph_replays += unroll
         for _ in range(unroll):
             self._graph_host_bookkeeping(log_interval)
+
+    def _graph_cache_key(self, unroll: int) -> tuple:
+        """What a captured graph depends on besides the device state it reads: one graph per distinct key."""
+        vn = self._vec_normalize_env
+        return (id(self._denv.coef), self.batch_size, self.gradient_steps, self._graph_phase(), None if vn is None else (id(vn), vn.cfg_key),
+                unroll)
 
     def _noop_callback(self) -> BaseCallback:
         cb = to_callback(None)

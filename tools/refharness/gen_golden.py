@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,init,vecenv]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,init,vecenv]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -15,6 +15,7 @@ Reference entry points exercised (file:line in /root/reference):
   core/common/buffers.py:106-115,247-325 ReplayBuffer.add / sample / _get_samples
   core/sac/sac.py:199-296                SAC.train
   core/td3/td3.py:154-211                TD3.train
+  core/bcq/bcq.py:129-213                BCQ.train; core/bcq/policies.py:426-435 BCQPolicy._predict
   core/common/utils.py:457-481           polyak_update
 """
 import argparse
@@ -1024,7 +1025,198 @@ def gen_vecnorm():
     save("vecnormalize_kat.npz", **out)
 
 
-GENS = {"maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+# --------------------------------------------------------------------------------------- BCQ
+def _bcq_dataset(tmpdir, n_rows, D=4, A=2, seed=2718):
+    """A pickle of the reference's own ReplayBuffer (one env, `_fill_buffer`-style seeded rows): what BCQ(dataset=<path>) loads
+    (core/common/offline_policy_algorithm.py:196-242)."""
+    import types
+
+    from core.common.buffers import ReplayBuffer
+    from core.common.save_util import save_to_pkl
+    from gymnasium import spaces
+
+    buf = ReplayBuffer(n_rows + 56, spaces.Box(-1, 1, (D,), np.float32), spaces.Box(-1, 1, (A,), np.float32), device="cpu", n_envs=1)
+    _fill_buffer(types.SimpleNamespace(replay_buffer=buf), np.random.default_rng(seed), n_rows, 1, D, A)
+    path = os.path.join(tmpdir, "bcq_dataset.pkl")
+    save_to_pkl(path, buf, 0)
+    return path
+
+
+class _BcqHooks:
+    """th.randn / th.randn_like of core/bcq/policies.py and F.mse_loss of core/bcq/bcq.py, recorded in call order."""
+
+    def __init__(self):
+        import torch.nn.functional as F_real
+
+        import core.bcq.bcq as bcqmod
+        import core.bcq.policies as polmod
+
+        self.draws, self.mse, self.F_real, self.bcqmod, self.polmod = [], [], F_real, bcqmod, polmod
+        hooks = self
+
+        class ThProxy:
+            def __getattr__(self, name):
+                return getattr(th, name)
+
+            @staticmethod
+            def randn(*a, **k):
+                e = th.randn(*a, **k)
+                hooks.draws.append(e.clone())
+                return e
+
+            @staticmethod
+            def randn_like(*a, **k):
+                e = th.randn_like(*a, **k)
+                hooks.draws.append(e.clone())
+                return e
+
+        class FProxy:
+            def __getattr__(self, name):
+                return getattr(F_real, name)
+
+            @staticmethod
+            def mse_loss(a, b, *args, **kw):
+                hooks.mse.append((a.detach().clone(), b.detach().clone()))
+                return F_real.mse_loss(a, b, *args, **kw)
+
+        self._th, self._F = ThProxy(), FProxy()
+
+    def __enter__(self):
+        self.polmod.th, self.bcqmod.F = self._th, self._F
+        return self
+
+    def __exit__(self, *exc):
+        self.polmod.th, self.bcqmod.F = th, self.F_real
+
+
+def _bcq_train(tag, tmpdir):
+    """The teacher-forced BCQ run (core/bcq/bcq.py:129-213): returns (model, out). Per step: th.manual_seed(1000 + k), so the three
+    draws -- randn_like [B, L] (policies.py:82), randn [10B, L] (:123), on actor steps randn [B, L] (:123) -- are the first
+    consumers of a generator seeded with `step{k}/th_seed`; the [10B, L] draw is stored as that seed + digests."""
+    from core.bcq.bcq import BCQ
+    from core.common.logger import Logger
+
+    D, A = 4, 2
+    B, n_steps = (64, 4) if tag == "small" else (256, 2)
+    pk = dict(policy_kwargs=dict(critic_net_arch=[64, 64])) if tag == "small" else {}
+    model = BCQ("MlpPolicy", _make_venv(1), dataset=_bcq_dataset(tmpdir, 200), seed=0, device="cpu", batch_size=B, **pk)
+    model.set_logger(Logger(folder=None, output_formats=[]))
+    L = model.actor.vae.latent_dim
+    out = {}
+    mods = ("actor", "actor_target", "critic", "critic_target")
+    for nm in mods:
+        out.update(_flat_sd(f"before/{nm}", getattr(model, nm).state_dict()))
+    out["state_dict_keys"] = np.array(list(model.policy.state_dict().keys()))
+    rb = model.replay_buffer
+    assert rb.n_envs == 1 and rb.size() == 200
+    out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
+               ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
+               ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
+    np.random.seed(777)
+    orig_sample = rb.sample
+    batches = []
+
+    def rec_sample(batch_size, env=None):
+        s = orig_sample(batch_size, env=env)
+        batches.append([x.numpy().copy() for x in s])
+        return s
+
+    rb.sample = rec_sample
+    with _BcqHooks() as hk:
+        try:
+            for k in range(n_steps):
+                th.manual_seed(1000 + k)
+                d0, m0 = len(hk.draws), len(hk.mse)
+                model.train(gradient_steps=1, batch_size=B)
+                actor_step = model._n_updates % model.actor_delay == 0
+                draws, mse = hk.draws[d0:], hk.mse[m0:]
+                assert len(draws) == (3 if actor_step else 2) and len(mse) == 3
+                assert tuple(draws[0].shape) == (B, L) and tuple(draws[1].shape) == (10 * B, L)
+                gen = th.Generator().manual_seed(1000 + k)  # the stored seed reproduces the draws
+                assert th.equal(th.randn(B, L, generator=gen), draws[0]) and th.equal(th.randn(10 * B, L, generator=gen), draws[1])
+                out[f"step{k}/th_seed"] = np.int64(1000 + k)
+                out[f"step{k}/draw_vae"] = draws[0].numpy()
+                out[f"step{k}/draw_target#sum"] = np.float64(draws[1].double().sum())
+                out[f"step{k}/draw_target#head"] = draws[1].reshape(-1)[:64].numpy().copy()
+                if actor_step:
+                    assert th.equal(th.randn(B, L, generator=gen), draws[2])
+                    out[f"step{k}/draw_actor"] = draws[2].numpy()
+                out[f"step{k}/recon"] = mse[0][0].numpy()
+                out[f"step{k}/current_q1"], out[f"step{k}/current_q2"] = mse[1][0].numpy(), mse[2][0].numpy()
+                out[f"step{k}/target_q"] = mse[1][1].numpy()
+                lv = model.logger.name_to_value
+                out[f"step{k}/vae_loss"] = np.float32(lv["train/vae_loss"])
+                out[f"step{k}/critic_loss"] = np.float32(lv["train/critic_loss"])
+                if actor_step:
+                    out[f"step{k}/actor_loss"] = np.float32(lv["train/actor_loss"])
+                for fi, fname in enumerate(["observations", "actions", "next_observations", "dones", "rewards"]):
+                    out[f"step{k}/batch_{fname}"] = batches[k][fi]
+        finally:
+            rb.sample = orig_sample
+    for nm in mods:
+        out.update(_flat_sd(f"after/{nm}", getattr(model, nm).state_dict()))
+    out["hyper"] = np.array([model.gamma, model.tau, model.actor_delay, model.lr_schedule(1), B, n_steps, L,
+                             model.actor.perturbation.max_perturbation], np.float64)
+    out["np_seed"] = np.int64(777)
+    out["n_params"] = np.array([sum(p.numel() for g in o.param_groups for p in g["params"])
+                                for o in (model.actor.vae_optimizer, model.actor.perturbation_optimizer, model.critic.optimizer)], np.int64)
+    return model, out
+
+
+def gen_bcq():
+    """BCQ.train (core/bcq/bcq.py:129-213): bcq_train_kat_small.npz (critics [64, 64], B = 64, 4 steps = two actor steps) and
+    bcq_train_kat_default.npz (class defaults, B = 256, 2 steps, digests for the large tensors)."""
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as tmp:
+        _, out = _bcq_train("small", tmp)
+        save("bcq_train_kat_small.npz", **out)
+        model, out = _bcq_train("default", tmp)
+        assert [l.out_features for l in model.critic.q_networks[0] if hasattr(l, "out_features")] == [400, 300, 1]
+        save("bcq_train_kat_default.npz", **slim_weights(out, with_shape=False))
+
+
+def gen_bcq_predict():
+    """BCQ.predict (core/bcq/policies.py:426-435) after the four steps of the small case on 64 seeded single observations. Every call
+    is made with the generator seeded alike, so ONE raw [100, L] draw serves all of them. The 100 q1 values are the reference's own
+    modules evaluated on the recorded draw (asserted to select the action predict() returned)."""
+    import tempfile
+
+    with tempfile.TemporaryDirectory() as tmp:
+        model, _ = _bcq_train("small", tmp)
+    n_obs, S = 64, 100
+    obs = np.random.default_rng(4242).uniform(-1, 1, (n_obs, 4)).astype(np.float32)
+    out = dict(obs=obs, q1=np.zeros((n_obs, S), np.float32), action=np.zeros((n_obs, 2), np.float32),
+               scaled_action=np.zeros((n_obs, 2), np.float32), index=np.zeros(n_obs, np.int64))
+    pol = model.policy
+    draw0 = None
+    with _BcqHooks() as hk:
+        for i in range(n_obs):
+            th.manual_seed(4000)
+            d0 = len(hk.draws)
+            action, _ = model.predict(obs[i:i + 1], deterministic=True)
+            (draw,) = hk.draws[d0:]
+            draw0 = draw if draw0 is None else draw0
+            assert th.equal(draw, draw0) and action.shape == (1, 2)
+            with th.no_grad():
+                rep = th.as_tensor(obs[i:i + 1]).repeat(S, 1)
+                cand = pol.actor.perturbation(rep, pol.actor.vae.decode(rep, draw.clamp(-0.5, 0.5)))
+                q1 = pol.critic.q1_forward(rep, cand)[:, 0]
+            idx = int(q1.argmax())
+            np.testing.assert_array_equal(pol.unscale_action(cand[idx:idx + 1].numpy()), action)
+            out["q1"][i], out["action"][i], out["scaled_action"][i], out["index"][i] = q1.numpy(), action[0], cand[idx].numpy(), idx
+    out["draw"] = draw0.numpy()
+    top = np.sort(out["q1"], axis=1)
+    gap = (top[:, -1] - top[:, -2]) / np.abs(top[:, -1])
+    out["rel_gap"] = gap.astype(np.float64)
+    close = float((gap <= 4 * 1e-4).mean())
+    print(f"bcq predict: {100 * close:.1f} % of {n_obs} observations have a top-two relative q1 gap <= 4e-4; smallest {gap.min():.2e}")
+    assert close <= 0.15
+    out["low"], out["high"] = np.asarray(model.action_space.low, np.float32), np.asarray(model.action_space.high, np.float32)
+    save("bcq_predict_kat.npz", **out)
+
+
+GENS = {"bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint}
 
