@@ -22,6 +22,8 @@ TRAIN_SAMPLES = 10  # candidates per next state in train() (:161)
 
 class BCQ(OfflineAlgorithm):
     policy_aliases = {"MlpPolicy": MlpPolicy}
+    train_batch_size = 100
+    packed_batch_with_pi = False  # the candidates have their own rows (fused.FastBcq)
 
     def __init__(self, policy, env, dataset=None, learning_rate=3e-4, buffer_size: int = 1_000_000, batch_size: int = 256,
                  tau: float = 0.005, gamma: float = 0.99, gradient_steps: int = 1, behavior_cloning_warmup: int = 0,
@@ -77,22 +79,11 @@ class BCQ(OfflineAlgorithm):
         self.policy.fast = self._fast if value else None
 
     # ---- batches -----------------------------------------------------------------------------------------------------
-    def _batch(self, batch_size: int):
-        if self._static_batch is None or self._static_batch.observations.shape[0] != batch_size or self._packed is not None:
-            self._static_batch, self._packed = self.replay_buffer.alloc_batch(batch_size), None
-        return self._static_batch
+    def _alloc_step_tensors(self, batch_size: int) -> None:
+        pass  # `_step_bufs`: the kernel path's step tensors follow the batch it actually sampled
 
     def _use_packed_batch(self) -> bool:
-        from core.common.buffers import ReplayBuffer
-
-        rb = self.replay_buffer
-        return self._fused_learner and type(rb) is ReplayBuffer and rb.normalizer is None
-
-    def _packed_batch(self, batch_size: int):
-        if self._packed is None or self._packed.x_data.shape[0] != batch_size:
-            self._packed = self.replay_buffer.alloc_packed_batch(batch_size, with_pi=False)
-            self._static_batch = self._packed.samples
-        return self._packed
+        return self._fused_learner and self._stock_buffer()
 
     def _step_bufs(self, batch_size: int):
         b = getattr(self, "_bufs", None)
@@ -104,13 +95,6 @@ class BCQ(OfflineAlgorithm):
         return b
 
     # ---- train -------------------------------------------------------------------------------------------------------
-    def train(self, gradient_steps: int, batch_size: int = 100) -> None:
-        """reference: bcq.py:129-213"""
-        self.policy.set_training_mode(True)
-        self._train_host_pre()
-        self._train_device_only(gradient_steps, batch_size)
-        self._train_host_only(gradient_steps)
-
     def _train_host_pre(self) -> None:
         self._update_learning_rate([self.actor.perturbation_optimizer, self.actor.vae_optimizer, self.critic.optimizer])  # :134
 
@@ -120,11 +104,8 @@ class BCQ(OfflineAlgorithm):
     def _graph_phase(self) -> int:
         return self._n_updates % self.actor_delay  # the delayed actor step: one captured graph per residue
 
-    def _n_actor(self, gradient_steps: int) -> int:
-        return (self._n_updates + gradient_steps) // self.actor_delay - self._n_updates // self.actor_delay
-
     def _train_host_only(self, gradient_steps: int) -> None:
-        n_actor = self._n_actor(gradient_steps)
+        n_actor = self._n_delayed_updates(gradient_steps, self.actor_delay)
         self._n_updates += gradient_steps
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         if n_actor > 0:  # :210-211 (the last mean stays logged until the next actor step)
@@ -136,17 +117,17 @@ class BCQ(OfflineAlgorithm):
         return self.noise_queue.pop(0).to(self.device, th.float32).contiguous() if self.noise_queue else None
 
     def _train_device_only(self, gradient_steps: int, batch_size: int) -> None:
-        n_actor = self._n_actor(gradient_steps)
+        n_actor = self._n_delayed_updates(gradient_steps, self.actor_delay)
         # one gradient step per call on the kernel path: the loss kernels STORE the logged values (an actor-less call leaves the actor's
         # slot alone, so a log dump after it still resolves the last actor loss), no zero-fill launch
-        single = gradient_steps == 1 and self._fused_learner
-        if not single:
+        self._single_step = gradient_steps == 1 and self._fused_learner
+        if not self._single_step:
             (self._loss_sum_buf if n_actor > 0 else self._loss_sum_buf[1:3]).zero_()
         n_updates = self._n_updates  # the host counter advances in _train_host_only
         for _ in range(gradient_steps):
             n_updates += 1
             if self._fused_learner:
-                self._gradient_step_fused(batch_size, n_updates, single)
+                self._gradient_step_fused(batch_size, n_updates)
             else:
                 self._gradient_step_torch(batch_size, n_updates)
 
@@ -195,10 +176,9 @@ class BCQ(OfflineAlgorithm):
                                            recon=recon.detach().clone(), next_q_min=next_q_min.clone(),
                                            actor_loss=None if actor_loss is None else actor_loss.detach().clone())
 
-    def _gradient_step_fused(self, batch_size: int, n_updates: int, single: bool = False) -> None:
-        """bcq.py:137-207 on the kernel path (core/common/fused.py FastBcq, csrc/cstr_bcq.hip). `single`: the only step of this train()
-        call -- the loss kernels store the logged values straight into the sums; otherwise they add to the (zeroed) sums."""
-        s, pol, fast = self._loss_sums, self.policy, self._fast
+    def _gradient_step_fused(self, batch_size: int, n_updates: int) -> None:
+        """bcq.py:137-207 on the kernel path (core/common/fused.py FastBcq, csrc/cstr_bcq.hip)."""
+        pol, fast = self.policy, self._fast
         if self._use_packed_batch():
             pb = self._packed_batch(batch_size)
             self.replay_buffer.sample_packed_into(pb)  # :140 + cat([obs, act]) for the encoder and the critics
@@ -208,11 +188,10 @@ class BCQ(OfflineAlgorithm):
             x_data = th.cat([rd.observations, rd.actions], dim=1)
         B = x_data.shape[0]
         bufs = self._step_bufs(B)
-        out = lambda k: (s[k], None) if single else (self._loss_now[k], s[k])  # noqa: E731
         # VAE step (:143-154): encoder, merged head + latent launch, decoder, loss launch, backward, Adam; the copy into the target
         # actor (:160) rides in the Adam launch (own_target with tau = 1: target = 1 * p + 0 * target)
         recon, params, std = fast.vae_forward(x_data, rd.observations, self._pop_noise(), bufs["gkl"])
-        v_out, v_sum = out("vae")
+        v_out, v_sum = self._loss_slot("vae")
         hip_ops.bcq_vae_loss(recon.detach(), rd.actions, params, std, bufs["g_recon"], bufs["gkl"][0], bufs["gkl"][1], v_out, v_sum)
         with fused.deferred_weight_grads():
             th.autograd.backward([recon], [bufs["g_recon"]])
@@ -226,7 +205,7 @@ class BCQ(OfflineAlgorithm):
         # both Q networks per layer in one pointer-table launch, as SAC / TD3 evaluate their critics (fused._TwinPairFn)
         qs = fused.twin_chain_forward(fast.critic, x_data) if fused.twin_chain_supported(fast.critic) else fast.critic.forward_input(x_data)
         gq = bufs["gq"]
-        c_out, c_sum = out("critic")
+        c_out, c_sum = self._loss_slot("critic")
         hip_ops.twin_q_loss(qs[0], qs[1], bufs["target_q"], 1.0, gq[0], gq[1], c_out, c_sum)
         fused.backward_q(qs, gq)
         self.critic.optimizer.step()
@@ -234,7 +213,7 @@ class BCQ(OfflineAlgorithm):
         if n_updates % self.actor_delay == 0:  # :189-207
             x_pi = fast.candidates(rd.observations, 1, self._pop_noise(), target=False, with_grad=True)
             qs_pi = fast.critic.forward_input(x_pi, train_params=False, only_first=True)
-            a_out, a_sum = out("actor")
+            a_out, a_sum = self._loss_slot("actor")
             hip_ops.neg_mean_loss(qs_pi[0], gq[0], a_out, a_sum)
             fused.backward_q(qs_pi, gq)
             # the perturbation net's step, its own soft target update and the critics' in ONE launch; the target VAE already equals

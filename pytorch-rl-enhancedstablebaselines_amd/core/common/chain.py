@@ -38,6 +38,12 @@ TILES = tuple(int(v) for v in os.environ.get("CSTR_CHAIN_TILES", "2,2,2,2,1").sp
 TD3_TILES = tuple(int(v) for v in os.environ.get("CSTR_CHAIN_TILES_TD3", "2,2,2,2,2").split(","))
 
 
+def _adam_in_wgrad(model, B: int) -> bool:
+    """The dW / db launch applies the Adam step to the tiles it has reduced: only when no collective stands between a gradient and
+    its optimiser step (`model._grads_need_allreduce`), and above the batch size where that launch wins."""
+    return USE_WGRAD_ADAM and B > 32 and not model._grads_need_allreduce()
+
+
 def _q_layers(qnet: nn.Sequential):
     lin = [m for m in qnet if isinstance(m, nn.Linear)]
     return tuple((m.weight, m.bias) for m in lin)
@@ -114,9 +120,7 @@ class SacChain:
     def step(self, model, pb, gather, gradient_step: int) -> None:
         s, pol, B, W, D, A = model._loss_sums, model.policy, self.B, self.W, self.D, self.A
         fa = model._fast_actor
-        single = getattr(model, "_single_step", False)
-        acc = (lambda k: None) if single else (lambda k: s[k])
-        sto = (lambda k, other: s[k]) if single else (lambda k, other: other)
+        (c_out, c_sum), (a_out, a_sum) = model._loss_slot("critic"), model._loss_slot("actor")
         rd = pb.samples
         dist = fa.actor.action_dist
         eps2 = None
@@ -156,21 +160,20 @@ class SacChain:
         hip_ops.q_chain_fwd(nets4, W, D, self.cH1, self.cH2, B, self.t_q4, fin)
         # -- entropy-coefficient loss, TD target, critic loss and the critic backward down to dz1
         if model.ent_coef_optimizer is not None:
-            ent_coef = s["ent_coef"] if single else model._ent_coef_buf
+            (ent_coef, ent_coef_sum), (e_out, e_sum) = model._loss_slot("ent_coef"), model._loss_slot("ent_coef_loss")
             alpha = dict(log_alpha=model.log_ent_coef.detach(), logp_pi=self.logp_pi, target_entropy=model.target_entropy,
-                         grad_out=model._ent_arena.grad[0:1], ent_coef_out=ent_coef, loss_out=s["ent_coef_loss"] if single else None,
-                         loss_sum=acc("ent_coef_loss"), ent_coef_sum=acc("ent_coef"))
+                         grad_out=model._ent_arena.grad[0:1], ent_coef_out=ent_coef, loss_out=e_out, loss_sum=e_sum, ent_coef_sum=ent_coef_sum)
         else:
             ent_coef, alpha = model.ent_coef_tensor.reshape(1), None
             s["ent_coef"] += ent_coef
         b3s = [self.crit[0][2][1], self.crit[1][2][1], self.targ[0][2][1], self.targ[1][2][1]]
         # one GPU: no collective between a gradient and its optimiser step -> the dW / db launch applies Adam to its tiles; the step
         # counters are advanced by the loss workgroup of the launch in front of it
-        fuse_opt = USE_WGRAD_ADAM and model.world_size == 1 and B > 32 and not getattr(model, "_force_segment_boundaries", False)
+        fuse_opt = _adam_in_wgrad(model, B)
         ent_opt = model.ent_coef_optimizer
         root = hip_ops.chain_root("td", B, [self.q_part4[g] for g in range(4)], b3s, self.n_q4, gamma=model.gamma, scale=0.5,
                                   next_logp=self.logp_next, rew=rd.rewards, done=rd.dones, ent_coef=ent_coef, target_out=model._target_q,
-                                  q_out=self.q_out, gq_out=self.gq, loss_out=sto("critic", model._loss_now["critic"]), loss_sum=acc("critic"),
+                                  q_out=self.q_out, gq_out=self.gq, loss_out=c_out, loss_sum=c_sum,
                                   alpha=alpha, rng_advance=rng_total,
                                   adam_advance=([model.critic.optimizer] + ([ent_opt] if ent_opt is not None else [])) if fuse_opt else ())
         back = [hip_ops.chain_net(self.crit[g], None, self.c_h1[g], self.c_h2[g]) for g in range(2)]
@@ -201,7 +204,7 @@ class SacChain:
         nets2 = [hip_ops.chain_net(self.crit[g], pb.x_pi, self.c_h1[g], self.c_h2[g], self.q_part2[g]) for g in range(2)]
         hip_ops.q_chain_fwd(nets2, W, D, self.cH1, self.cH2, B, self.t_q2)
         aroot = hip_ops.chain_root("sac_actor", B, [self.q_part2[0], self.q_part2[1]], b3s[:2], self.n_q2, ent_coef=ent_coef, logp=self.logp_pi,
-                                   q_out=self.qpi_out, loss_out=sto("actor", model._loss_now["actor"]), loss_sum=acc("actor"),
+                                   q_out=self.qpi_out, loss_out=a_out, loss_sum=a_sum,
                                    adam_advance=[model.actor.optimizer] if fuse_opt else ())
         hip_ops.q_chain_bwd(back, aroot, W, D, self.cH1, self.cH2, self.t_qb, gact_part=self.gact_part)
         hip_ops.sac_actor_chain_bwd(self.actor, self.gact_part, 2, self.n_gact, ent_coef, pb.x_pi, self.params, eps, self.a_h1, self.a_h2,
@@ -229,8 +232,7 @@ class SacChain:
                 model.actor.optimizer.step()
         if model.debug_capture:
             model.last_train_tensors = dict(target_q=model._target_q.clone(), current_q=[self.q_out[0].clone().view(B, 1), self.q_out[1].clone().view(B, 1)],
-                                            critic_loss=sto("critic", model._loss_now["critic"]).clone(),
-                                            actor_loss=sto("actor", model._loss_now["actor"]).clone(),
+                                            critic_loss=c_out.clone(), actor_loss=a_out.clone(),
                                             ent_coef=ent_coef.detach().clone(), log_prob=self.logp_pi.clone())
 
 
@@ -310,16 +312,15 @@ class Td3Chain:
         self.g_params, self.dz2a, self.dz1a = e(B, A), e(B, H2), e(B, H1)
 
     def step(self, model, pb, gather, n_updates: int) -> None:
-        s, pol, B, W, D, A = model._loss_sums, model.policy, self.B, self.W, self.D, self.A
+        pol, B, W, D, A = model.policy, self.B, self.W, self.D, self.A
         rd = pb.samples
-        single = getattr(model, "_single_step", False)
-        c_out, c_sum = (s["critic"], None) if single else (model._loss_now["critic"], s["critic"])
+        c_out, c_sum = model._loss_slot("critic")
         queued = model.noise_queue.pop(0).to(model.device, th.float32).contiguous() if model.noise_queue else None  # teacher-forced, scaled
         rng = None if queued is not None else model._device_rng()
         noise = {} if queued is not None else dict(head_rng_ctl=rng, eps_all=self.eps)
         eps = self.eps if queued is None else queued
         sigma = model.target_policy_noise if queued is None else 1.0
-        fuse_opt = USE_WGRAD_ADAM and model.world_size == 1 and B > 32 and not getattr(model, "_force_segment_boundaries", False)
+        fuse_opt = _adam_in_wgrad(model, B)
         # -- critic step: target actor on next_obs (:171), four Q networks (:173, :179), TD target + loss + backward (:174-186)
         kw = dict(rows_mode=nv.CHAIN_ROWS_NEXT, head_n=A, **noise)
         if gather is not None:
@@ -363,7 +364,7 @@ class Td3Chain:
         actor_done = False
         a_out = None
         if n_updates % model.policy_delay == 0:  # :192-206
-            a_out, a_sum = (s["actor"], None) if single else (model._loss_now["actor"], s["actor"])
+            a_out, a_sum = model._loss_slot("actor")
             a1, a2, a3 = self.actor_layers
             hip_ops.sac_actor_chain_fwd(self.actor, B, None, pb.x_pi, None, None, None, self.a_h1, self.a_h2, self.head_part, self.t_act,
                                         rows_mode=nv.CHAIN_ROWS_OBS, head_n=A)
@@ -495,10 +496,6 @@ class MaddpgCriticChain:
                          (self.gq[i, g].view(B, 1), self.c_h2[i, g], w3.grad, b3.grad)]
         return sets
 
-    @staticmethod
-    def _fuse_opt(model, B: int) -> bool:
-        return USE_WGRAD_ADAM and model.world_size == 1 and B > 32 and not getattr(model, "_force_segment_boundaries", False)
-
     def captured(self, model, i: int) -> dict:
         B = self.B
         return dict(target_q=model._target_q[i].clone(), current_q=[self.q_out[i, 0].clone().view(B, 1), self.q_out[i, 1].clone().view(B, 1)],
@@ -506,7 +503,7 @@ class MaddpgCriticChain:
 
     def critic_step(self, model, i: int, x_cur, x_next, rd) -> None:
         """Agent i's critic step (:146-164): 3 launches."""
-        fuse_opt = self._fuse_opt(model, self.B)
+        fuse_opt = _adam_in_wgrad(model, self.B)
         hip_ops.q_chain_fwd(self._nets4(i, x_cur, x_next), self.W, self.D, self.H1, self.H2, self.B, self.t_q)
         self._backward(model, i, rd, fuse_opt)
         opt = model.critic.optimizer_list[i]
@@ -521,7 +518,7 @@ class MaddpgCriticChain:
         """Every agent's critic step of an update WITHOUT a policy step: the agents' steps do not depend on each other (no soft update in
         between), so their 4 x n_agents networks share ONE forward launch; a backward launch per agent; a dW / db + Adam launch per two
         agents. The same kernels on the same operands as `critic_step`: bit-identical."""
-        fuse_opt = self._fuse_opt(model, self.B)
+        fuse_opt = _adam_in_wgrad(model, self.B)
         nets = [net for i in range(self.n) for net in self._nets4(i, x_cur, x_next)]
         hip_ops.q_chain_fwd(nets, self.W, self.D, self.H1, self.H2, self.B, self.t_q)
         for i in range(self.n):

@@ -9,7 +9,7 @@ latency-bound, not xGMI link-bound, so the two dependent all-reduces are issued 
 RCCL picks its low-latency (tree / one-shot) protocol; no bucketing beyond the per-optimiser arena is useful.
 Under hipGraph replay the collectives are recorded into the iteration's graph when `graph_collectives_ok` (a start-up
 capture-and-replay trial on every rank) passes, and stay between graph segments otherwise
-(OffPolicyAlgorithm._capture_segments; CSTR_GRAPH_COLLECTIVES=auto|0|1).
+(GraphReplay._capture_segments; CSTR_GRAPH_COLLECTIVES=auto|0|1).
 """
 import datetime
 import os

@@ -16,28 +16,27 @@ from typing import Any, Optional, Union
 import numpy as np
 import torch as th
 
-from core.common import blas
-from core.common import distributed as dist_util
-from core.common import hip_ops
-from core import _native as nv
+from core.common import blas, chain, fused, hip_ops
 from core.common.base_class import BaseAlgorithm
 from core.common.buffers import ReplayBuffer
-from core.common.callbacks import BaseCallback, MaybeCallback, to_callback
+from core.common.callbacks import BaseCallback, MaybeCallback
+from core.common.graph_replay import GraphReplay
 from core.common.logger import DeviceMean
 from core.common.type_aliases import RolloutReturn, TrainFreq, TrainFrequencyUnit
 from core.common.utils import should_collect_more_steps
 from core.common.vec_env import CSTRVecEnv, VecEnv
 
-# Data-parallel runs under hipGraph replay. "auto" (default): record the RCCL all-reduces INTO the iteration's graph when a
-# start-up trial (distributed.graph_collectives_ok: capture + replay of one all-reduce, result checked on every rank) passes,
-# else run them eagerly BETWEEN graph segments; "0": always between segments; "1": always inside (no trial).
-GRAPH_COLLECTIVES = os.environ.get("CSTR_GRAPH_COLLECTIVES", "auto")
 # the captured iteration's rollout as ONE launch (policy + collect step + replay index draw; hip_ops.rollout_step). "0": the
 # separate policy / collect / sampler launches (A/B knob; both forms are bit-identical, tests/test_rollout_step.py)
 FUSED_ROLLOUT = os.environ.get("CSTR_FUSED_ROLLOUT", "1") != "0"
 
 
-class OffPolicyAlgorithm(BaseAlgorithm):
+class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
+    train_batch_size: Optional[int] = None  # `batch_size` of a train() call that names none (the reference's per-class default)
+    packed_batch_with_pi = True             # the packed batch carries x_pi = (obs | pi(obs)) rows for the actor step
+    chain_type: Optional[type] = None       # the row-chain form of this class's gradient step (core/common/chain.py)
+    _single_step = False                    # this train() call is ONE gradient step whose loss kernels store the logged values
+
     def __init__(self, policy, env, learning_rate, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = (1, "step"),
                  gradient_steps: int = 1, action_noise=None, replay_buffer_class=None, replay_buffer_kwargs: Optional[dict] = None,
@@ -66,11 +65,8 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         self.replay_buffer_kwargs = replay_buffer_kwargs or {}
         self.train_freq = train_freq
         self.use_sde_at_warmup = use_sde_at_warmup
-        self._graph_enabled, self._graph, self._graph_key = False, None, None
+        self._init_graph_state()
         self._rng_advance = None  # (rng_ctl, rows) the next fused collect launch owes the rollout policy launch (SAC)
-        self._graph_error: Optional[str] = None  # text of the exception that ended hipGraph replay (None = never failed)
-        self._graph_replays = 0                  # iterations served by a captured graph / by eager launches (bench.py reports both)
-        self._eager_iterations = 0
         self.stats_sync_interval = 100   # vec-steps between host reads of the device episode counters
         self._steps_since_sync = 0
         self._episodes_at_last_dump = 0
@@ -108,7 +104,7 @@ class OffPolicyAlgorithm(BaseAlgorithm):
                                                           optimize_memory_usage=self.optimize_memory_usage, **kw)
         # built on the CPU generator in the reference's construction order (same seed -> same initial weights),
         # then moved into the HBM arenas by the policy itself
-        self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule, **self.policy_kwargs)
+        self.policy = self._make_policy()
         self.policy.to_device_arenas(self.device)
         if self.world_size > 1:
             self.policy.broadcast_from_rank0()
@@ -120,6 +116,9 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         n = self.n_envs
         self._ep_return = th.zeros(n, dtype=th.float32, device=self.device)
         self._ep_stats = th.zeros(4, dtype=th.float64, device=self.device)
+
+    def _make_policy(self):
+        return self.policy_class(self.observation_space, self.action_space, self.lr_schedule, **self.policy_kwargs)
 
     def save_replay_buffer(self, path) -> None:
         """reference: off_policy_algorithm.py:214-222"""
@@ -185,14 +184,8 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         callback.on_training_end()
         return self
 
-    def _learn_iteration(self, callback: BaseCallback, log_interval: Optional[int]) -> bool:
-        """Body of the reference's `while` loop (off_policy_algorithm.py:331-351): one rollout, then train.
-        When the iteration is eligible it is replayed from a captured hipGraph instead (same launches, same
-        order, one host call)."""
-        if self._graph_enabled and self._graph_eligible(callback):
-            self._graph_iteration(log_interval, callback)
-            return True
-        self._eager_iterations += 1
+    def _eager_iteration(self, callback: BaseCallback, log_interval: Optional[int]) -> bool:
+        """Body of the reference's `while` loop (off_policy_algorithm.py:331-351): one rollout, then train."""
         rollout = self.collect_rollouts(self.env, train_freq=self.train_freq, action_noise=self.action_noise,
                                         callback=callback, learning_starts=self.learning_starts,
                                         replay_buffer=self.replay_buffer, log_interval=log_interval)
@@ -204,22 +197,7 @@ class OffPolicyAlgorithm(BaseAlgorithm):
                 self.train(batch_size=self.batch_size, gradient_steps=gradient_steps)
         return True
 
-    # ---- hipGraph capture of the steady-state iteration ------------------------------------------------------------
-    def enable_graph_capture(self, enabled: bool = True, unroll: Optional[int] = None) -> None:
-        """Replay the steady-state iteration (actor forward, fused collect, `gradient_steps` gradient steps) from a
-        captured hipGraph: ~250 launches become one host call. Every per-call control word the kernels need (ring
-        position, Adam step, MT19937 stream, learning rate, env / RNG state) lives in HBM, so a replay is exact.
-        Falls back to the eager path whenever the iteration is not capturable (warm-up, callbacks, host-side action noise,
-        episodic train_freq).
-
-        `unroll` (default 1, env CSTR_GRAPH_UNROLL): consecutive iterations recorded into ONE graph -- the ~10 us the GPU
-        idles between two graph launches is paid once per `unroll` iterations. Used on one GPU, and data-parallel when the
-        all-reduces are recorded into the graph (every rank replays the same graphs in the same order), with a constant learning
-        rate while at least `unroll` iterations remain; the tail of a run replays graphs of unroll / 2, unroll / 4, ... 1 iterations."""
-        self._graph_enabled = enabled
-        self._graph, self._graph_error, self._abi_launches = None, None, {}
-        self.graph_unroll = max(1, int(unroll if unroll is not None else os.environ.get("CSTR_GRAPH_UNROLL", "1")))
-
+    # ---- hipGraph replay of the steady-state iteration: the hooks of core/common/graph_replay.py ------------------------
     def _graph_eligible(self, callback: BaseCallback) -> bool:
         from core.common.noise import DeviceNormalActionNoise, LegacyStreamNormalActionNoise, LegacyStreamOUActionNoise
 
@@ -230,13 +208,20 @@ class OffPolicyAlgorithm(BaseAlgorithm):
                 and self.gradient_steps >= 1 and self.num_timesteps >= self.learning_starts
                 and self.num_timesteps + self.n_envs > self.learning_starts and not getattr(self, "debug_capture", False))
 
+    def _graph_cache_key(self, unroll: int) -> tuple:
+        vn = self._vec_normalize_env
+        return (id(self._denv.coef), self.batch_size, self.gradient_steps, self._graph_phase(), None if vn is None else (id(vn), vn.cfg_key),
+                unroll)
+
     def _graph_body(self) -> None:
-        env, rb, vn = self._denv, self.replay_buffer, self._vec_normalize_env
+        env, rb = self._denv, self.replay_buffer
         self.policy.set_training_mode(False)
         self._sde_rollout_resets(0)
         noise = None if self.action_noise is None else self.action_noise().contiguous()
-        net = self._rollout_net() if (FUSED_ROLLOUT and vn is None and self._use_packed_batch()) else None
-        if net is not None:
+        net = self._rollout_net() if (FUSED_ROLLOUT and self._vec_normalize_env is None and self._use_packed_batch()) else None
+        if net is None:
+            self._device_collect_step(self._policy_out_device(self._rollout_obs()), self._action_mode(False), noise, self.action_noise)
+        else:
             # policy network + sampling + collect step + the first gradient step's replay index draw in ONE launch; the gather
             # launch of that gradient step advances the ring position and the policy's Philox offset (hip_ops.rollout_step)
             idx = rb.predraw_indices(self.batch_size)
@@ -246,209 +231,33 @@ class OffPolicyAlgorithm(BaseAlgorithm):
                                  reward_out=env._rew, done_out=env._done, ep_return=self._ep_return, ep_stats=self._ep_stats,
                                  mt_state=rb.sampler_stream, sample_idx=idx)
             rb.note_predrawn(idx, None if net["rng_ctl"] is None else (net["rng_ctl"], env.num_envs))
-            if hasattr(self.action_noise, "reset_done"):
-                self.action_noise.reset_done(env._done)
-            self.policy.set_training_mode(True)
-            self._train_device_only(self.gradient_steps, self.batch_size)
-            rb._no_predrawn("the iteration's first gradient step")
-            return
-        pol = self._policy_out_device(env.obs if vn is None else vn.norm_obs_dev)
-        hip_ops.collect_step(env.coef, env.integrator, rb.ring, env.obs, env.step_count, pol, self._action_mode(False),
-                             self.action_space.low, self.action_space.high, noise=noise, pcg_state=env.pcg_state, static_init=env.static_init, reward_out=env._rew, done_out=env._done,
-                             ep_return=self._ep_return, ep_stats=self._ep_stats, rng_advance=self._take_rng_advance())
-        if hasattr(self.action_noise, "reset_done"):
-            self.action_noise.reset_done(env._done)  # action_noise.reset(indices of finished envs), :596-599
-        if vn is not None:
-            vn.after_device_step()
+            self._after_device_step(self.action_noise)
         self.policy.set_training_mode(True)
         self._train_device_only(self.gradient_steps, self.batch_size)
+        if net is not None:
+            rb._no_predrawn("the iteration's first gradient step")
 
     def _rollout_net(self) -> Optional[dict]:
         """The rollout policy as operands of hip_ops.rollout_step (weights = (w1, b1, w2, b2, w3, b3), act, head, out_act, w2_swz,
         rng_ctl), or None when the one-launch rollout does not cover this algorithm / network (the separate launches run then)."""
         return None
 
-    def _use_packed_batch(self) -> bool:
-        return False
-
     def _graph_host_bookkeeping(self, log_interval: Optional[int]) -> None:
         self.replay_buffer.note_fused_add()
-        self._last_obs = self._denv.obs if self._vec_normalize_env is None else self._vec_normalize_env.norm_obs_dev
+        self._last_obs = self._rollout_obs()
         self.num_timesteps += self.n_envs
         self._update_current_progress_remaining(self.num_timesteps, self._total_timesteps)
         self._train_host_only(self.gradient_steps)
         self._sync_episode_stats(log_interval)
 
-    def _graph_phase(self) -> int:
-        """Iterations that launch different kernel sequences need different graphs (TD3 / MADDPG: the delayed policy
-        update happens every `policy_delay`-th gradient step)."""
-        return 0
-
-    def _graph_unroll_now(self) -> int:
-        u = getattr(self, "graph_unroll", 1)
-        if u <= 1 or not isinstance(self.learning_rate, float):
-            return 1
-        if (self.world_size > 1 or getattr(self, "_force_segment_boundaries", False)) and not self._collectives_in_graph():
-            return 1  # data-parallel with the collectives BETWEEN graph segments: one iteration per replay list
-        remaining = (self._total_timesteps - self.num_timesteps) // self.n_envs
-        while u > 1 and remaining < u:  # the tail of a run: the largest of u, u / 2, u / 4, ... that still fits
-            u //= 2
-        return max(u, 1)
-
-    def _graph_iteration(self, log_interval: Optional[int], callback: Optional[BaseCallback] = None) -> None:
-        opt = getattr(getattr(self.policy, "actor", None), "optimizer", None)
-        if getattr(opt, "shadow", None) is not None:  # torch changed the actor's weights (a callback, load_state_dict): the
-            opt.refresh_shadow(force=False)           # replayed graph reads their tile-major copy -- one version compare
-        unroll = self._graph_unroll_now()
-        key = self._graph_cache_key(unroll)
-        if not isinstance(self._graph, dict):
-            self._graph, self._graph_warm = {}, {}
-        if key not in self._graph:
-            # side-stream warm-up (these are REAL iterations: they advance env, ring, RNG and optimiser state)
-            warm = self._graph_warm.get(key, 0)
-            if warm < 3:
-                self._train_host_pre()
-                side = th.cuda.Stream(device=self.device)
-                side.wait_stream(th.cuda.current_stream(self.device))
-                with th.cuda.stream(side):
-                    self._graph_body()
-                th.cuda.current_stream(self.device).wait_stream(side)
-                self._graph_warm[key] = warm + 1
-                self._eager_iterations += 1
-                self._graph_host_bookkeeping(log_interval)
-                return
-            self._train_host_pre()
-            try:
-                self._graph[key] = self._capture_segments(unroll)
-            except Exception as exc:  # something in the iteration is not capturable: run eagerly from now on
-                import warnings
-
-                self._graph_error = f"{type(exc).__name__}: {exc}"
-                warnings.warn(f"hipGraph capture failed ({self._graph_error}); falling back to eager launches")
-                self._graph_enabled, self._graph = False, None
-                self._learn_iteration(callback if callback is not None else self._noop_callback(), log_interval)
-                return
-        self._train_host_pre()
-        for item in self._graph[key]:  # hipGraph segments interleaved with the eager collectives that separate them
-            item.replay() if isinstance(item, th.cuda.CUDAGraph) else item()
-        self._graph_replays += unroll
-        for _ in range(unroll):
-            self._graph_host_bookkeeping(log_interval)
-
-    def _graph_cache_key(self, unroll: int) -> tuple:
-        """What a captured graph depends on besides the device state it reads: one graph per distinct key."""
-        vn = self._vec_normalize_env
-        return (id(self._denv.coef), self.batch_size, self.gradient_steps, self._graph_phase(), None if vn is None else (id(vn), vn.cfg_key),
-                unroll)
-
-    def _noop_callback(self) -> BaseCallback:
-        cb = to_callback(None)
-        cb.init_callback(self)
-        return cb
-
-    def graph_status(self) -> dict:
-        """What actually runs (not what was requested): bench.py refuses to report a run whose graphs fell back to eager."""
-        graphs = self._graph if isinstance(self._graph, dict) else {}
-        segs = [sum(isinstance(i, th.cuda.CUDAGraph) for i in items) for items in graphs.values()]
-        mode = "none"
-        if self.world_size > 1 or getattr(self, "_force_segment_boundaries", False):
-            mode = "in-graph" if getattr(self, "_graph_collectives", False) else "segmented"
-        return dict(requested=bool(self._graph_enabled or self._graph_error), active=bool(self._graph_enabled and len(graphs) > 0),
-                    graphs=len(graphs), segments_per_graph=segs, replays=self._graph_replays, eager_iterations=self._eager_iterations,
-                    error=self._graph_error, graph_collectives=mode,
-                    abi_launches_per_iteration={int(k): v for k, v in sorted(getattr(self, "_abi_launches", {}).items())})
-
-    def _capture_segments(self, unroll: int = 1) -> list:
-        """`_record_segments`, and if recording WITH the collectives inside the graph raises (every rank runs the same code,
-        so every rank gets here), once more with the collectives between graph segments."""
-        try:
-            return self._record_segments(unroll)
-        except Exception as exc:  # noqa: BLE001
-            if not (self.world_size > 1 and getattr(self, "_graph_collectives", False) and GRAPH_COLLECTIVES == "auto"):
-                raise
-            print(f"[graph] recording the collectives into the graph failed ({exc!r}); keeping them between graph segments", file=sys.stderr)
-            self._graph_collectives = False
-            th.cuda.synchronize(self.device)
-            return self._record_segments(unroll)
-
-    def _record_segments(self, unroll: int = 1) -> list:
-        """Record the iteration as hipGraph segments. A data-parallel run has an RCCL all-reduce between backward and
-        the optimiser step (two per SAC gradient step). When the start-up trial passes (`_collectives_in_graph`) they are
-        recorded into the graph; otherwise collectives stay OUTSIDE the captured graphs -- every `_eager_boundary` closes the
-        current segment, runs the collective eagerly and opens the next segment in the same memory pool (activations saved
-        for a later segment's backward stay alive). Single-GPU runs have no boundary and get one graph."""
-        import gc
-
-        # like torch.cuda.graph(): collect garbage BEFORE recording and keep the collector off while recording -- a cycle
-        # collection that destroys another model's CUDAGraph (or frees device memory) in the middle of a capture aborts
-        self._collectives_in_graph()  # decided (start-up trial, world > 1) before anything is being recorded
-        gc.collect()
-        gc_was_enabled = gc.isenabled()
-        gc.disable()
-        th.cuda.synchronize(self.device)
-        side = th.cuda.Stream(device=self.device)
-        side.wait_stream(th.cuda.current_stream(self.device))
-        items: list = []
-        with th.cuda.stream(side):
-            self._cap = dict(pool=th.cuda.graph_pool_handle(), graph=th.cuda.CUDAGraph(), items=items)
-            self._cap["graph"].capture_begin(pool=self._cap["pool"], capture_error_mode="thread_local")
-            n_updates = self._n_updates
-            calls0 = nv.ABI_CALLS[0]
-            try:
-                for _ in range(unroll):
-                    self._graph_body()
-                    self._n_updates += self.gradient_steps  # the next body sees its own policy-delay phase
-                self._cap["graph"].capture_end()
-                items.append(self._cap["graph"])
-                # launches recorded per iteration of this policy-delay phase (every launch of the captured body goes through the
-                # C ABI; bench.py reports it, tools/count_launches.sh is the rocprofv3 cross-check)
-                self._abi_launches[self._graph_phase()] = (nv.ABI_CALLS[0] - calls0) / unroll
-            except Exception:
-                try:  # leave capture mode before the graph object is destroyed
-                    self._cap["graph"].capture_end()
-                except Exception:
-                    pass
-                # nothing of the recorded body ran: host-side debts of the one-launch rollout (indices "drawn" by a launch that was
-                # only recorded, a Philox advance handed to a consumer that was never reached) must not reach the eager fallback
-                self._drop_recording_debts()
-                raise
-            finally:
-                self._cap = None
-                self._n_updates = n_updates  # nothing ran while recording
-                if gc_was_enabled:
-                    gc.enable()
-        th.cuda.current_stream(self.device).wait_stream(side)
-        th.cuda.synchronize(self.device)
-        return items
+    def _graph_shift_phase(self, iterations: int) -> None:
+        self._n_updates += iterations * self.gradient_steps  # what `_train_host_only` adds per iteration (TD3 / MADDPG / BCQ phases)
 
     def _drop_recording_debts(self) -> None:
         rb = getattr(self, "replay_buffer", None)
         if rb is not None and hasattr(rb, "_predrawn"):
             rb._predrawn = None
         self._rng_advance = None
-
-    def _collectives_in_graph(self) -> bool:
-        if getattr(self, "_graph_collectives", None) is None:
-            if GRAPH_COLLECTIVES in ("0", "1"):
-                self._graph_collectives = GRAPH_COLLECTIVES == "1"
-            else:
-                self._graph_collectives = self.world_size > 1 and dist_util.graph_collectives_ok(self.device)
-        return self._graph_collectives
-
-    def _eager_boundary(self, fn) -> None:
-        """Run `fn` (a collective) eagerly; when a capture is in progress, split the graph around it."""
-        cap = getattr(self, "_cap", None)
-        if cap is None or self._collectives_in_graph():
-            # no capture in progress, or the collective is recorded into the graph like any other launch (RCCL issues a
-            # blocking collective on the current stream) and the iteration stays ONE graph
-            fn()
-            return
-        cap["graph"].capture_end()
-        cap["items"].append(cap["graph"])
-        fn()
-        cap["items"].append(fn)
-        cap["graph"] = th.cuda.CUDAGraph()
-        cap["graph"].capture_begin(pool=cap["pool"], capture_error_mode="thread_local")
 
     def _sde_rollout_resets(self, num_collected_steps: int) -> None:
         """gSDE: the exploration matrices are redrawn (one per env) when a rollout starts (:550-551) and every `sde_sample_freq`
@@ -492,6 +301,65 @@ class OffPolicyAlgorithm(BaseAlgorithm):
         buffer_action = scaled_action
         action = self.policy.unscale_action(scaled_action)
         return action, buffer_action
+
+    # ---- train(): the plumbing every learner shares -----------------------------------------------------------------
+    def train(self, gradient_steps: int, batch_size: Optional[int] = None) -> None:
+        """reference: sac.py:199-296, td3.py:154-211, maddpg.py:117-191, bcq.py:129-213 = host prologue (lr schedule) + device work +
+        host epilogue (logger)."""
+        if batch_size is None:
+            batch_size = self.train_batch_size
+            if batch_size is None:
+                raise TypeError(f"{type(self).__name__}.train() missing 1 required positional argument: 'batch_size'")
+        self.policy.set_training_mode(True)
+        self._train_host_pre()
+        self._train_device_only(gradient_steps, batch_size)
+        self._train_host_only(gradient_steps)
+
+    def _use_packed_batch(self) -> bool:
+        return False
+
+    def _stock_buffer(self) -> bool:
+        """The HBM `ReplayBuffer` itself, without a VecNormalize normaliser: its rows can be sampled straight into critic-input rows."""
+        return type(self.replay_buffer) is ReplayBuffer and self.replay_buffer.normalizer is None
+
+    def _batch(self, batch_size: int):
+        """The contiguous sample tensors (and this class's step tensors) for `batch_size`; they replace a packed batch."""
+        if self._static_batch is None or self._static_batch.observations.shape[0] != batch_size or self._packed is not None:
+            self._static_batch, self._packed = self.replay_buffer.alloc_batch(batch_size), None
+            self._alloc_step_tensors(batch_size)
+        return self._static_batch
+
+    def _packed_batch(self, batch_size: int):
+        """The critic-input rows (obs | act) the sampler writes directly; `_static_batch` becomes views of them."""
+        if self._packed is None or self._packed.x_data.shape[0] != batch_size:
+            self._packed = self.replay_buffer.alloc_packed_batch(batch_size, with_pi=self.packed_batch_with_pi)
+            self._static_batch = self._packed.samples
+            self._alloc_packed_step_tensors(batch_size)
+        return self._packed
+
+    def _alloc_step_tensors(self, batch_size: int) -> None:
+        """Hook of `_batch`: the per-step tensors whose shape follows the batch size."""
+        self._target_q = th.empty(batch_size, 1, dtype=th.float32, device=self.device)
+
+    def _alloc_packed_step_tensors(self, batch_size: int) -> None:
+        """Hook of `_packed_batch` (`self._packed` is the new batch)."""
+        self._alloc_step_tensors(batch_size)
+
+    def _n_delayed_updates(self, gradient_steps: int, delay: int) -> int:
+        """How many of the next `gradient_steps` updates are a `delay`-th one (the delayed policy update of TD3 / MADDPG / BCQ)."""
+        return (self._n_updates + gradient_steps) // delay - self._n_updates // delay
+
+    def _loss_slot(self, key: str) -> tuple:
+        """(store_target, accumulate_target) of the loss kernel that logs `key`: the only gradient step of a train() call stores the
+        value straight into the logged sum (no zero-fill launch); otherwise it goes to the `_loss_now` scratch and is added to the sum."""
+        return (self._loss_sums[key], None) if self._single_step else (self._loss_now.get(key), self._loss_sums[key])
+
+    def _chain_for(self, batch_size: int):
+        """The row-chain form of the gradient step for this batch size (`chain_type`), or None: per-layer fused path."""
+        cache, key = self._chain_cache, (batch_size, chain.USE_CHAIN, fused.USE_FUSED_LINEAR)
+        if key not in cache:
+            cache[key] = self.chain_type(self, batch_size) if self.chain_type.supported(self, batch_size) else None
+        return cache[key]
 
     # ---- logging ---------------------------------------------------------------------------------------------------
     def _dump_logs(self) -> None:
@@ -595,13 +463,13 @@ class OffPolicyAlgorithm(BaseAlgorithm):
     def _collect_one_fused(self, env: CSTRVecEnv, rb: ReplayBuffer, action_noise, learning_starts: int) -> None:
         """One vec-step entirely in HBM: reference statements :561 (_sample_action), :564 (env.step), :580
         (_store_transition -> ReplayBuffer.add) in one HIP launch after the actor forward."""
-        n, vn = env.num_envs, self._vec_normalize_env
+        n = env.num_envs
         if self._warmup(learning_starts):
             # warm-up: uniform actions from the action space's own generator (:386-388); drawn on the host
             pol = th.as_tensor(self.action_space.sample_batch(n)).to(self.device)
             squashed = self._action_mode(warmup=True)
         else:
-            pol = self._policy_out_device(env.obs if vn is None else vn.norm_obs_dev)
+            pol = self._policy_out_device(self._rollout_obs())
             squashed = self._action_mode(warmup=False)
         noise = None
         if action_noise is not None:
@@ -609,20 +477,27 @@ class OffPolicyAlgorithm(BaseAlgorithm):
             noise = z if isinstance(z, th.Tensor) else th.as_tensor(np.asarray(z, np.float32))
             noise = noise.to(self.device, th.float32).reshape(n, -1).contiguous()
         with th.cuda.device(self.device):
-            hip_ops.collect_step(env.coef, env.integrator, rb.ring, env.obs, env.step_count, pol, squashed,
-                                 self.action_space.low, self.action_space.high, noise=noise, pcg_state=env.pcg_state, static_init=env.static_init,
-                                 reward_out=env._rew, done_out=env._done, ep_return=self._ep_return, ep_stats=self._ep_stats,
-                                 rng_advance=self._take_rng_advance())
-            if hasattr(action_noise, "reset_done"):
-                action_noise.reset_done(env._done)  # action_noise.reset(indices of finished envs), :596-599
-            if vn is not None:
-                vn.after_device_step()  # VecNormalize.step_wait on the raw outputs (vec_normalize.py:174-204)
+            self._device_collect_step(pol, squashed, noise, action_noise)
         rb.note_fused_add()
-        self._last_obs = env.obs if vn is None else vn.norm_obs_dev
+        self._last_obs = self._rollout_obs()
 
-    # ---- data-parallel helper used by train() ----------------------------------------------------------------------
-    def _allreduce_grads(self, arena) -> None:
-        if self.world_size > 1 or getattr(self, "_force_segment_boundaries", False):
-            buf = getattr(arena, "grad_full", None)
-            buf = arena.grad if buf is None else buf
-            self._eager_boundary(lambda: dist_util.allreduce_sum_(buf))
+    def _rollout_obs(self) -> th.Tensor:
+        """What the rollout policy sees: the env's observation, through VecNormalize when the env is wrapped in one."""
+        vn = self._vec_normalize_env
+        return self._denv.obs if vn is None else vn.norm_obs_dev
+
+    def _device_collect_step(self, pol: th.Tensor, squashed: int, noise: Optional[th.Tensor], action_noise) -> None:
+        """The device rollout step behind the policy output `pol`, for the eager and the captured iteration alike: the fused collect
+        launch (action scaling chain + env step + auto-reset + ring row write + episode statistics), then `_after_device_step`."""
+        env, rb = self._denv, self.replay_buffer
+        hip_ops.collect_step(env.coef, env.integrator, rb.ring, env.obs, env.step_count, pol, squashed,
+                             self.action_space.low, self.action_space.high, noise=noise, pcg_state=env.pcg_state, static_init=env.static_init,
+                             reward_out=env._rew, done_out=env._done, ep_return=self._ep_return, ep_stats=self._ep_stats,
+                             rng_advance=self._take_rng_advance())
+        self._after_device_step(action_noise)
+
+    def _after_device_step(self, action_noise) -> None:
+        if hasattr(action_noise, "reset_done"):
+            action_noise.reset_done(self._denv._done)  # action_noise.reset(indices of finished envs), :596-599
+        if self._vec_normalize_env is not None:
+            self._vec_normalize_env.after_device_step()  # VecNormalize.step_wait on the raw outputs (vec_normalize.py:174-204)

@@ -155,11 +155,7 @@ class OfflineAlgorithm(OffPolicyAlgorithm):
         callback.on_training_end()
         return self
 
-    def _learn_iteration(self, callback: BaseCallback, log_interval: Optional[int]) -> bool:
-        if self._graph_enabled and self._graph_eligible(callback):
-            self._graph_iteration(log_interval, callback)
-            return True
-        self._eager_iterations += 1
+    def _eager_iteration(self, callback: BaseCallback, log_interval: Optional[int]) -> bool:
         self.train(gradient_steps=self.gradient_steps, batch_size=self.batch_size)
         self.num_timesteps += self.n_envs
         self._update_current_progress_remaining(self.num_timesteps, self._total_timesteps)
@@ -172,7 +168,7 @@ class OfflineAlgorithm(OffPolicyAlgorithm):
             self._dump_logs()
         return True
 
-    # ---- hipGraph: one replay = one iteration's gradient steps (no rollout) ------------------------------------------
+    # ---- hipGraph hooks (core/common/graph_replay.py): one replay = one iteration's gradient steps, no rollout ------------
     def _graph_eligible(self, callback: BaseCallback) -> bool:
         return (type(self.replay_buffer) is ReplayBuffer and getattr(callback, "is_noop", False) and self.gradient_steps >= 1
                 and getattr(self, "fused_learner", False) and not getattr(self, "debug_capture", False))
@@ -196,9 +192,6 @@ class OfflineAlgorithm(OffPolicyAlgorithm):
 
     def _behavior_cloning_update(self, observations: np.ndarray, actions: np.ndarray) -> float:
         raise NotImplementedError("Subclasses must implement _behavior_cloning_update method")  # :312-321
-
-    def train(self, gradient_steps: int, batch_size: int) -> None:
-        raise NotImplementedError("Each offline RL algorithm must implement its own train method")  # :323-331
 
     def collect_rollouts(self, env, callback, train_freq, replay_buffer, action_noise=None, learning_starts: int = 0,
                          log_interval: Optional[int] = None) -> None:

@@ -19,13 +19,12 @@ from typing import List, Optional, Union
 import torch as th
 from torch.nn import functional as F
 
-from core.common import blas, fused, hip_ops
-from core.common.buffers import ReplayBuffer
+from core.common import fused, hip_ops
+from core.common.chain import MaddpgCriticChain
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
 from core.common.spaces import split_spaces
 from core.common.utils import get_schedule_fn, update_learning_rate
-from core.common.vec_env import CSTRVecEnv
 from core.maddpg.policies import MlpPolicy
 
 
@@ -36,6 +35,7 @@ BATCH_AGENT_CRITIC_STEPS = os.environ.get("CSTR_MADDPG_BATCH_AGENTS", "1") != "0
 
 class MADDPG(OffPolicyAlgorithm):
     policy_aliases = {"MlpPolicy": MlpPolicy}
+    chain_type = MaddpgCriticChain  # the critic steps (and the actor loss through the critic) only
 
     def __init__(self, n_agents: int, policy, env, observation_splits: List[List[int]], action_splits: List[List[int]],
                  learning_rate_list=1e-3, buffer_size: int = 1_000_000, learning_starts: int = 100, batch_size: int = 256,
@@ -76,31 +76,13 @@ class MADDPG(OffPolicyAlgorithm):
         self.lr_schedule_list = [get_schedule_fn(lr) for lr in self.learning_rate_list]
         self.lr_schedule = self.lr_schedule_list[0]
 
+    def _make_policy(self):
+        return self.policy_class(self.n_agents, self.observation_space, self.action_space, self.observation_space_list,
+                                 self.action_space_list, self.lr_schedule_list, **self.policy_kwargs)
+
     def _setup_model(self) -> None:
         """reference: multiagent_policy_algorithm.py:172-212"""
-        self._setup_lr_schedule()
-        blas.configure()
-        if self.world_size > 1 and isinstance(self.env, CSTRVecEnv):
-            self.env.seed_offset = self.rank * self.n_envs
-        self.set_random_seed(self.seed)
-        if self.replay_buffer_class is None:
-            self.replay_buffer_class = ReplayBuffer
-        if self.replay_buffer is None:
-            self.replay_buffer = self.replay_buffer_class(self.buffer_size, self.observation_space, self.action_space,
-                                                          device=self.device, n_envs=self.n_envs,
-                                                          optimize_memory_usage=self.optimize_memory_usage, **self.replay_buffer_kwargs)
-        self.policy = self.policy_class(self.n_agents, self.observation_space, self.action_space, self.observation_space_list,
-                                        self.action_space_list, self.lr_schedule_list, **self.policy_kwargs)
-        self.policy.to_device_arenas(self.device)
-        if self.world_size > 1:
-            self.policy.broadcast_from_rank0()
-            for opt in self.policy.flat_optimizers():
-                opt.grad_scale = 1.0 / self.world_size
-            if self.seed is not None:
-                th.manual_seed(self.seed + 1000003 * self.rank)
-        self._convert_train_freq()
-        self._ep_return = th.zeros(self.n_envs, dtype=th.float32, device=self.device)
-        self._ep_stats = th.zeros(4, dtype=th.float64, device=self.device)
+        super()._setup_model()
         self.actor, self.actor_target = self.policy.actor, self.policy.actor_target
         self.critic, self.critic_target = self.policy.critic, self.policy.critic_target
         z = lambda: th.zeros(1, dtype=th.float32, device=self.device)  # noqa: E731
@@ -181,33 +163,13 @@ class MADDPG(OffPolicyAlgorithm):
     def _use_packed_batch(self) -> bool:
         """Joint critics whose input is exactly (obs | actions): sample straight into the critic-input rows and let the
         target-smoothing kernel write every agent's next action into its columns (no gathers, no torch.cat)."""
-        from core.common.buffers import ReplayBuffer
-
-        rb, C = self.replay_buffer, self.critic
-        return (self.fused_learner and not C.local and type(rb) is ReplayBuffer and rb.normalizer is None
+        C = self.critic
+        return (self.fused_learner and not C.local and self._stock_buffer()
                 and C._tiles_in_order("obs") and C._tiles_in_order("act")
                 and all(C._range("act", i) is not None and C._range("obs", i) is not None for i in range(self.n_agents)))
 
-    def _packed_batch(self, batch_size: int):
-        if self._packed is None or self._packed.x_data.shape[0] != batch_size:
-            self._packed = self.replay_buffer.alloc_packed_batch(batch_size, with_pi=True)  # x_pi = (obs | .) for the actor step
-            self._static_batch = self._packed.samples
-            self._target_q = [th.empty(batch_size, 1, dtype=th.float32, device=self.device) for _ in range(self.n_agents)]
-        return self._packed
-
-    def _batch(self, batch_size: int):
-        if self._static_batch is None or self._static_batch.observations.shape[0] != batch_size or self._packed is not None:
-            self._packed = None
-            self._static_batch = self.replay_buffer.alloc_batch(batch_size)
-            self._target_q = [th.empty(batch_size, 1, dtype=th.float32, device=self.device) for _ in range(self.n_agents)]
-        return self._static_batch
-
-    def train(self, gradient_steps: int, batch_size: int) -> None:
-        """reference: maddpg.py:117-191"""
-        self.policy.set_training_mode(True)
-        self._train_host_pre()
-        self._train_device_only(gradient_steps, batch_size)
-        self._train_host_only(gradient_steps)
+    def _alloc_step_tensors(self, batch_size: int) -> None:
+        self._target_q = [th.empty(batch_size, 1, dtype=th.float32, device=self.device) for _ in range(self.n_agents)]
 
     def _train_host_pre(self) -> None:
         for agent_id in range(self.n_agents):
@@ -220,7 +182,7 @@ class MADDPG(OffPolicyAlgorithm):
         return self._n_updates % self.policy_delay
 
     def _train_host_only(self, gradient_steps: int) -> None:
-        n_actor = (self._n_updates + gradient_steps) // self.policy_delay - self._n_updates // self.policy_delay
+        n_actor = self._n_delayed_updates(gradient_steps, self.policy_delay)
         self._n_updates += gradient_steps
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         for i in range(self.n_agents):
@@ -231,7 +193,7 @@ class MADDPG(OffPolicyAlgorithm):
     def _train_device_only(self, gradient_steps: int, batch_size: int) -> None:
         # a call without a policy update keeps the actors' last loss sums (slots [0, n_agents)), like maddpg.py:183-191 keeps
         # the last recorded value until the next actor update; the critics' slots are zeroed every call
-        n_actor = (self._n_updates + gradient_steps) // self.policy_delay - self._n_updates // self.policy_delay
+        n_actor = self._n_delayed_updates(gradient_steps, self.policy_delay)
         (self._loss_sum_buf if n_actor > 0 else self._loss_sum_buf[self.n_agents:]).zero_()
         n_updates = self._n_updates
         A, C = self.actor, self.critic
@@ -343,7 +305,7 @@ class MADDPG(OffPolicyAlgorithm):
                 shared_next = None if C.local else self.critic_target._input(0, rd.next_observations, next_actions)
         if pb is None:
             shared_cur = None if C.local else C._input(0, rd.observations, rd.actions)
-        cchain = self._critic_chain_for(B) if (pb is not None and shared_next is not None) else None
+        cchain = self._chain_for(B) if (pb is not None and shared_next is not None) else None
         if cchain is not None and BATCH_AGENT_CRITIC_STEPS and n_updates % self.policy_delay != 0:
             # a step WITHOUT a policy update on the row-chain kernels (core/common/chain.py:MaddpgCriticChain): one forward launch for
             # every agent's critic and target critic, a backward launch per agent, one dW / db + Adam launch per two agents
@@ -474,16 +436,6 @@ class MADDPG(OffPolicyAlgorithm):
             pol.actor_target_arena.polyak_from(pol.actor_arena, self.tau)
         if self.debug_capture:
             self.last_train_tensors = dict(agents=captured)
-
-    def _critic_chain_for(self, batch_size: int):
-        """The critic steps on the row-chain kernels for this batch size (core/common/chain.py:MaddpgCriticChain), or None."""
-        from core.common import chain
-
-        cache = self.__dict__.setdefault("_chain_cache", {})
-        key = (batch_size, chain.USE_CHAIN, fused.USE_FUSED_LINEAR)
-        if key not in cache:
-            cache[key] = chain.MaddpgCriticChain(self, batch_size) if chain.MaddpgCriticChain.supported(self, batch_size) else None
-        return cache[key]
 
     def learn(self, total_timesteps: int, callback=None, log_interval: int = 4, tb_log_name: str = "MADDPG",
               reset_num_timesteps: bool = True, progress_bar: bool = False):

@@ -14,6 +14,7 @@ from torch.nn import functional as F
 
 from core.common import fused, hip_ops
 from core.common.arena import FlatAdam, ParamArena
+from core.common.chain import SacChain
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
 from core.sac.policies import MlpPolicy
@@ -21,6 +22,8 @@ from core.sac.policies import MlpPolicy
 
 class SAC(OffPolicyAlgorithm):
     policy_aliases = {"MlpPolicy": MlpPolicy}
+    train_batch_size = 64
+    chain_type = SacChain
 
     def __init__(self, policy, env, learning_rate=3e-4, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = 1,
@@ -74,8 +77,7 @@ class SAC(OffPolicyAlgorithm):
         self._loss_sum_buf = th.zeros(4, dtype=th.float32, device=self.device)  # one fill per train() instead of four
         sb = self._loss_sum_buf
         self._loss_sums = dict(actor=sb[0:1], critic=sb[1:2], ent_coef_loss=sb[2:3], ent_coef=sb[3:4])
-        self._loss_now = dict(actor=z(), critic=z())
-        self._ent_coef_buf = z()
+        self._loss_now = dict(actor=z(), critic=z(), ent_coef=z())  # no ent_coef_loss: a step that is not stored is only summed
         self._static_batch, self._packed = None, None
         # fused learner path (core/common/fused.py): GEMMs in rocBLAS, everything else hand-written HIP
         self.fused_learner = self._fused_supported()
@@ -87,8 +89,6 @@ class SAC(OffPolicyAlgorithm):
             self.actor.action_dist.torch_matrices = not self.fused_learner
 
     def _fused_supported(self) -> bool:
-        from core.common.arena import FlatAdam
-
         return (1 <= len(self.critic.q_networks) <= hip_ops.nv.MAX_ENS_CRITICS and isinstance(self.actor.optimizer, FlatAdam)
                 and isinstance(self.critic.optimizer, FlatAdam) and fused.FastMLP.supported(self.actor.latent_pi)
                 and all(fused.FastMLP.supported(q) for q in self.critic.q_networks))
@@ -110,34 +110,11 @@ class SAC(OffPolicyAlgorithm):
         self.critic = self.policy.critic
         self.critic_target = self.policy.critic_target
 
-    def _batch(self, batch_size: int):
-        if self._static_batch is None or self._static_batch.observations.shape[0] != batch_size or self._packed is not None:
-            self._static_batch, self._packed = self.replay_buffer.alloc_batch(batch_size), None
-            self._target_q = th.empty(batch_size, 1, dtype=th.float32, device=self.device)
-        return self._static_batch
-
     def _use_packed_batch(self) -> bool:
         """Sample straight into the critics' input rows (no torch.cat launches): the fused path with the merged actor head and
         the stock ReplayBuffer without a VecNormalize normaliser."""
-        from core.common.buffers import ReplayBuffer
-
-        rb = self.replay_buffer
-        return (self.fused_learner and self._fast_actor.head is not None and type(rb) is ReplayBuffer and rb.normalizer is None
+        return (self.fused_learner and self._fast_actor.head is not None and self._stock_buffer()
                 and self._fast_actor.act_dim <= hip_ops.nv.MAX_HEAD_ACT)
-
-    def _packed_batch(self, batch_size: int):
-        if self._packed is None or self._packed.x_data.shape[0] != batch_size:
-            self._packed = self.replay_buffer.alloc_packed_batch(batch_size)
-            self._static_batch = self._packed.samples
-            self._target_q = th.empty(batch_size, 1, dtype=th.float32, device=self.device)
-        return self._packed
-
-    def train(self, gradient_steps: int, batch_size: int = 64) -> None:
-        """reference: sac.py:199-296 = host prologue (lr schedule) + device work + host epilogue (logger)."""
-        self.policy.set_training_mode(True)
-        self._train_host_pre()
-        self._train_device_only(gradient_steps, batch_size)
-        self._train_host_only(gradient_steps)
 
     def _train_host_pre(self) -> None:
         optimizers = [self.actor.optimizer, self.critic.optimizer]
@@ -174,9 +151,7 @@ class SAC(OffPolicyAlgorithm):
         """The same statements as `_gradient_step_aten` (sac.py:215-287), evaluated on the fused path: losses are
         backward roots whose kernels emit d(loss)/d(inputs) directly; parameter gradients land in the arenas."""
         s, pol = self._loss_sums, self.policy
-        single = getattr(self, "_single_step", False)
-        acc = (lambda k: None) if single else (lambda k: s[k])  # accumulate into the sums ...
-        sto = (lambda k, other: s[k]) if single else (lambda k, other: other)  # ... or store straight into them
+        (c_out, c_sum), (a_out, a_sum) = self._loss_slot("critic"), self._loss_slot("actor")
         pb, gather = None, None
         chain = self._chain_for(batch_size)
         if chain is not None:  # the row-chain kernels (core/common/chain.py): 10 launches instead of 20
@@ -236,10 +211,9 @@ class SAC(OffPolicyAlgorithm):
         if not ens:
             q1, q2 = qs
         if self.ent_coef_optimizer is not None:
-            ent_coef = s["ent_coef"] if single else self._ent_coef_buf
+            (ent_coef, ent_coef_sum), (e_out, e_sum) = self._loss_slot("ent_coef"), self._loss_slot("ent_coef_loss")
             alpha = dict(log_alpha=self.log_ent_coef.detach(), logp_pi=log_prob.detach(), target_entropy=self.target_entropy,
-                         grad_out=self._ent_arena.grad[0:1], ent_coef_out=ent_coef, loss_out=s["ent_coef_loss"] if single else None,
-                         loss_sum=acc("ent_coef_loss"), ent_coef_sum=acc("ent_coef"))
+                         grad_out=self._ent_arena.grad[0:1], ent_coef_out=ent_coef, loss_out=e_out, loss_sum=e_sum, ent_coef_sum=ent_coef_sum)
         else:
             ent_coef, alpha = self.ent_coef_tensor.reshape(1), None
             s["ent_coef"] += ent_coef
@@ -248,14 +222,14 @@ class SAC(OffPolicyAlgorithm):
         if root:  # the three reductions ride in the critic backward's first launch (cstr_hidden_head_bwd_root_f32)
             td_root = dict(mode="td", q1_t=q1_t, q2_t=q2_t, next_logp=next_log_prob, rew=rd.rewards, done=rd.dones,
                            ent_coef=ent_coef, gamma=self.gamma, scale=0.5, q1=q1.detach(), q2=q2.detach(), target_out=self._target_q,
-                           loss_out=sto("critic", self._loss_now["critic"]), loss_sum=acc("critic"), alpha=alpha)
+                           loss_out=c_out, loss_sum=c_sum, alpha=alpha)
         else:
             if ens:  # :249-250 and :261 over all N critics
                 hip_ops.td_ens_q_loss(qs_t, next_log_prob, rd.rewards, rd.dones, ent_coef, self.gamma, qs, 0.5, self._target_q, gq,
-                                      sto("critic", self._loss_now["critic"]), acc("critic"), alpha=alpha)
+                                      c_out, c_sum, alpha=alpha)
             else:
                 hip_ops.td_twin_q_loss(q1_t, q2_t, next_log_prob, rd.rewards, rd.dones, ent_coef, self.gamma, q1, q2, 0.5, self._target_q,
-                                       gq1, gq2, sto("critic", self._loss_now["critic"]), acc("critic"), alpha=alpha)
+                                       gq1, gq2, c_out, c_sum, alpha=alpha)
             if self.ent_coef_optimizer is not None and not self._ent_rides_critic:
                 self._allreduce_grads(self._ent_arena)
                 self.ent_coef_optimizer.step()
@@ -281,11 +255,11 @@ class SAC(OffPolicyAlgorithm):
         actor_root = None
         if root:  # the actor loss rides in the first launch of the backward through the (frozen) critic
             actor_root = dict(mode="sac_actor", logp=log_prob.detach(), q1=q1_pi.detach(), q2=q2_pi.detach(), ent_coef=ent_coef, g_logp=g_lp,
-                              loss_out=sto("actor", self._loss_now["actor"]), loss_sum=acc("actor"))
+                              loss_out=a_out, loss_sum=a_sum)
         elif ens:  # min over all N critics
-            hip_ops.sac_actor_ens_loss(log_prob, qs_pi, ent_coef, g_lp, gq, sto("actor", self._loss_now["actor"]), acc("actor"))
+            hip_ops.sac_actor_ens_loss(log_prob, qs_pi, ent_coef, g_lp, gq, a_out, a_sum)
         else:
-            hip_ops.sac_actor_loss(log_prob, q1_pi, q2_pi, ent_coef, g_lp, gq1, gq2, sto("actor", self._loss_now["actor"]), acc("actor"))
+            hip_ops.sac_actor_loss(log_prob, q1_pi, q2_pi, ent_coef, g_lp, gq1, gq2, a_out, a_sum)
         with fused.loss_root(actor_root), fused.deferred_weight_grads():  # :279-281; the actor's dW / db of all layers in one launch
             if qs_pi.stacked is not None:
                 th.autograd.backward([log_prob, qs_pi.stacked], [g_lp, gq])
@@ -301,21 +275,14 @@ class SAC(OffPolicyAlgorithm):
 
         if self.debug_capture:
             self.last_train_tensors = dict(target_q=self._target_q.clone(), current_q=[q.detach().clone() for q in qs],
-                                           critic_loss=sto("critic", self._loss_now["critic"]).clone(),
-                                           actor_loss=sto("actor", self._loss_now["actor"]).clone(),
+                                           critic_loss=c_out.clone(), actor_loss=a_out.clone(),
                                            ent_coef=ent_coef.detach().clone(), log_prob=log_prob.detach().clone())
 
     def _chain_for(self, batch_size: int):
-        """The row-chain form of the gradient step for this batch size (core/common/chain.py), or None: per-layer fused path."""
-        from core.common import chain
-
-        cache = self.__dict__.setdefault("_chain_cache", {})
-        key = (batch_size, chain.USE_CHAIN, fused.USE_FUSED_LINEAR)
-        if key not in cache:
-            cache[key] = chain.SacChain(self, batch_size) if chain.SacChain.supported(self, batch_size) else None
-        if cache[key] is not None and len(self.actor.action_dist.eps_queue) not in (0, 2):
-            return None
-        return cache[key]
+        step = super()._chain_for(batch_size)
+        if step is not None and len(self.actor.action_dist.eps_queue) not in (0, 2):
+            return None  # the chain step takes queued (teacher-forced) draws as the pi(obs) / pi(next_obs) pair only
+        return step
 
     def _gradient_step_aten(self, batch_size: int, gradient_step: int) -> None:
         """Stock-ATen evaluation of the step (nn.Module forwards, autograd losses): the fallback for configurations the

@@ -6,6 +6,7 @@ import torch as th
 from torch.nn import functional as F
 
 from core.common import fused, hip_ops
+from core.common.chain import Td3Chain
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
 from core.td3.policies import MlpPolicy
@@ -13,6 +14,8 @@ from core.td3.policies import MlpPolicy
 
 class TD3(OffPolicyAlgorithm):
     policy_aliases = {"MlpPolicy": MlpPolicy}
+    train_batch_size = 100
+    chain_type = Td3Chain
 
     def __init__(self, policy, env, learning_rate=1e-3, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = 1,
@@ -62,33 +65,13 @@ class TD3(OffPolicyAlgorithm):
     def _rollout_net(self):
         return self._fast_actor.rollout_operands(self._denv.obs) if self.fused_learner else None
 
-    def _batch(self, batch_size: int):
-        if self._static_batch is None or self._static_batch.observations.shape[0] != batch_size or self._packed is not None:
-            self._static_batch, self._packed = self.replay_buffer.alloc_batch(batch_size), None
-            self._target_q = th.empty(batch_size, 1, dtype=th.float32, device=self.device)
-        return self._static_batch
-
     def _use_packed_batch(self) -> bool:
         """Sample straight into the critics' input rows (no torch.cat launches) on the fused path with the stock buffer."""
-        from core.common.buffers import ReplayBuffer
+        return self.fused_learner and self._stock_buffer()
 
-        rb = self.replay_buffer
-        return self.fused_learner and type(rb) is ReplayBuffer and rb.normalizer is None
-
-    def _packed_batch(self, batch_size: int):
-        if self._packed is None or self._packed.x_data.shape[0] != batch_size:
-            self._packed = self.replay_buffer.alloc_packed_batch(batch_size)  # x_pi: the actor writes its action into the critic input
-            self._static_batch = self._packed.samples
-            self._target_q = th.empty(batch_size, 1, dtype=th.float32, device=self.device)
-            self._act_t = th.empty(batch_size, self._packed.act_dim, dtype=th.float32, device=self.device)
-        return self._packed
-
-    def train(self, gradient_steps: int, batch_size: int = 100) -> None:
-        """reference: td3.py:154-211"""
-        self.policy.set_training_mode(True)
-        self._train_host_pre()
-        self._train_device_only(gradient_steps, batch_size)
-        self._train_host_only(gradient_steps)
+    def _alloc_packed_step_tensors(self, batch_size: int) -> None:
+        super()._alloc_packed_step_tensors(batch_size)
+        self._act_t = th.empty(batch_size, self._packed.act_dim, dtype=th.float32, device=self.device)
 
     def _train_host_pre(self) -> None:
         self._update_learning_rate([self.actor.optimizer, self.critic.optimizer])
@@ -101,7 +84,7 @@ class TD3(OffPolicyAlgorithm):
         return self._n_updates % self.policy_delay
 
     def _train_host_only(self, gradient_steps: int) -> None:
-        n_actor = (self._n_updates + gradient_steps) // self.policy_delay - self._n_updates // self.policy_delay
+        n_actor = self._n_delayed_updates(gradient_steps, self.policy_delay)
         self._n_updates += gradient_steps
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         if n_actor > 0:
@@ -111,7 +94,7 @@ class TD3(OffPolicyAlgorithm):
     def _train_device_only(self, gradient_steps: int, batch_size: int) -> None:
         # the reference keeps the last np.mean(actor_losses) until the next actor update (td3.py:207-211): a call without a
         # policy update zeroes the critic slot only, so a log dump after it still resolves the lazily-read actor loss
-        n_actor = (self._n_updates + gradient_steps) // self.policy_delay - self._n_updates // self.policy_delay
+        n_actor = self._n_delayed_updates(gradient_steps, self.policy_delay)
         # one gradient step per train() call (the default) on the fused path: the loss kernels STORE the logged values into the
         # sums (an actor-less call leaves the actor's slot alone), no zero-fill launch
         self._single_step = gradient_steps == 1 and self.fused_learner
@@ -164,7 +147,7 @@ class TD3(OffPolicyAlgorithm):
 
     def _gradient_step_fused(self, batch_size: int, n_updates: int) -> None:
         """td3.py:161-206 on the fused path (core/common/fused.py)."""
-        s, pol = self._loss_sums, self.policy
+        pol = self.policy
         pb, gather = None, None
         chain = self._chain_for(batch_size)
         if chain is not None:  # the row-chain kernels (core/common/chain.py): 4 launches (9 with the policy step) instead of 13 (22)
@@ -221,8 +204,7 @@ class TD3(OffPolicyAlgorithm):
         q1, q2 = qs[0], qs[-1]
         # TD target (:174-176) + critic loss (:182) in one launch; n_critics == 1 (DDPG): loss = mse(q1, t) -> scale 0.5 of
         # the doubled term. Twin critics: inside the critic backward's first launch (cstr_hidden_head_bwd_root_f32).
-        single = getattr(self, "_single_step", False)
-        c_out, c_sum = (s["critic"], None) if single else (self._loss_now["critic"], s["critic"])
+        c_out, c_sum = self._loss_slot("critic")
         root = len(qs) == 2 and qs.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critic)
         td_root = None
         if root:
@@ -252,7 +234,7 @@ class TD3(OffPolicyAlgorithm):
             else:
                 a = self._fast_actor(rd.observations)
                 qs_pi = self._fast_critic(rd.observations, a, train_params=False, only_first=True)
-            a_out, a_sum = (s["actor"], None) if single else (self._loss_now["actor"], s["actor"])
+            a_out, a_sum = self._loss_slot("actor")
             if qs_pi.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critic):
                 # -mean(Q1) (:194) rides in the first launch of the backward through the (frozen) first Q network
                 with fused.loss_root(dict(mode="neg_mean", q1=qs_pi[0].detach(), loss_out=a_out, loss_sum=a_sum)):
@@ -272,16 +254,6 @@ class TD3(OffPolicyAlgorithm):
             self.last_train_tensors = dict(target_q=self._target_q.clone(), current_q=[q.detach().clone() for q in qs],
                                            critic_loss=c_out.clone(),
                                            actor_loss=a_out.clone() if actor_done else None)
-
-    def _chain_for(self, batch_size: int):
-        """The row-chain form of the gradient step for this batch size (core/common/chain.py), or None: per-layer fused path."""
-        from core.common import chain
-
-        cache = self.__dict__.setdefault("_chain_cache", {})
-        key = (batch_size, chain.USE_CHAIN, fused.USE_FUSED_LINEAR)
-        if key not in cache:
-            cache[key] = chain.Td3Chain(self, batch_size) if chain.Td3Chain.supported(self, batch_size) else None
-        return cache[key]
 
     def _get_torch_save_params(self) -> tuple:
         """reference: td3.py:234-240"""
