@@ -761,6 +761,78 @@ int cstr_bcq_target_f32(const float *q, int64_t q_stride, int n_critics, int64_t
 int cstr_bcq_select_f32(const float *q1, const float *cand, int64_t ldc, int64_t n_states, int samples, int act_dim, int64_t *index_out,
                         float *action_out, cstr_stream_t stream);
 
+/* ---- PPO: the arithmetic around the Linear layers of an on-policy rollout step and minibatch step (core/ppo/ppo.py:184-300,
+ * core/common/on_policy_algorithm.py:162-268, core/common/buffers.py:343-521) ------------------------------------------------------
+ * All f32; obs_dim in {4, 8}, act_dim in {2, 4} (CSTR_E_UNSUPPORTED otherwise, as for more than CSTR_PPO_MAX_ROWS rows); any row
+ * count >= 1. Every entry point validates on the host (NULL, non-positive sizes, misaligned rows -- 4 * width bytes for [.][width]
+ * matrices, 16 for observations --, overlapping input / output rows -> CSTR_E_BADARG), then only enqueues. Batch reductions are
+ * deterministic (per-workgroup f64 partials summed in workgroup order; no float atomics).
+ * cstr_rollout_t: the RolloutBuffer's field arrays, [rows][n_envs][.] row-major. rollout ctl: int64[CSTR_ROLLOUT_CTL_WORDS] in HBM
+ * = { pos, full, ticket, adds }, the convention of ring_ctl, except that pos stops at rows (a full buffer takes no further row).
+ * workspace: uint64[CSTR_PPO_WS_WORDS] in HBM, zero before the first use (word 0 is a ticket that resets itself), private to one
+ * stream.
+ * cstr_diag_gaussian_act_f32: action [n][act_dim] = mean + exp(log_std) * eps (deterministic != 0: = mean), env_action (optional) =
+ * clip(action, low, high) (low / high both NULL: = action), log_prob [n] (optional) = sum_a -(a - mu)^2 / (2 sigma^2) - log sigma -
+ * log sqrt(2 pi). Noise unless deterministic: exactly one of eps_in [n][act_dim] (read) or rng_ctl [CSTR_RNG_CTL_WORDS] (drawn:
+ * Philox4x32-10 + Box-Muller on PPO's own stream, offset advanced by n by the last workgroup); eps_out (optional) keeps the draws.
+ * cstr_rollout_add_f32: writes row ctl[0] of all eight fields (advantages / returns: 0) and advances ctl; reward + gamma * terminal_value
+ * where timeout != 0 (both NULL: no bootstrap), gamma as given (the caller rounds to f32). done [n_envs] (optional): episode_start is
+ * overwritten with it after it was stored (the next step's episode starts). Episode statistics (all three or none, they need done):
+ * ep_return [n_envs] / ep_len int32[n_envs] accumulate the env's own reward (before the bootstrap) and the step count,
+ * and ep_stats double[4] = { episodes, sum of returns, sum of lengths, - } += { 1, return, length } for every env whose episode ends (the convention of cstr_collect_step_f32).
+ * cstr_gae_f32: per env, t = n_steps - 1 ... 0: delta = r + (g * v_next) * nnt - v; gae = delta + ((gl * nnt) * gae); g = (float)gamma,
+ * gl = (float)(gamma * gae_lambda); nnt = 1 - dones (last step) / 1 - episode_starts[t + 1]; returns = advantages + values.
+ * Bit-identical to NumPy's evaluation of buffers.py:423-438.
+ * cstr_ppo_gather_f32: idx int64[batch], flat index i = env i / rows, step i % rows (swap_and_flatten); indices outside
+ * [0, rows * n_envs) are the caller's bug and are clamped into it.
+ * cstr_ppo_loss_f32 (ppo.py:213-264): see cstr_ppo_loss_t. scalars = { policy_gradient_loss, value_loss, entropy_loss, loss, approx_kl,
+ * clip_fraction }; g_mean [batch][act_dim] / g_value [batch] / g_log_std [act_dim] = d loss / d (action mean, value, log_std).
+ * cstr_grad_clip_f32 (torch.nn.utils.clip_grad_norm_): grad[0..n) *= min(1, max_norm / (||grad||_2 + 1e-6)), two launches; norm_out
+ * (optional) receives the norm before clipping. */
+#define CSTR_ROLLOUT_CTL_WORDS 4
+#define CSTR_PPO_WS_WORDS 1024
+#define CSTR_PPO_MAX_BLOCKS 64
+#define CSTR_PPO_MAX_ROWS 1073741824
+typedef struct {
+    float *obs, *act, *rew, *episode_start, *values, *log_probs, *advantages, *returns;
+    int64_t rows, n_envs;
+    int32_t obs_dim, act_dim;
+} cstr_rollout_t;
+typedef struct {
+    const float *mean;         /* [batch][ldm], act_dim columns used */
+    int64_t ldm;
+    const float *log_std;      /* [act_dim] */
+    const float *actions;      /* [batch][act_dim] */
+    const float *values;       /* [batch]: the value net's output */
+    const float *old_values;   /* [batch]; may be NULL when clip_range_vf <= 0 */
+    const float *old_log_prob; /* [batch] */
+    const float *adv;          /* [batch] */
+    const float *returns;      /* [batch] */
+    int64_t batch;
+    int32_t act_dim;
+    int32_t normalize_advantage; /* != 0: (adv - mean) / (unbiased std + 1e-8) over the batch, skipped when batch == 1 */
+    double clip_range;
+    double clip_range_vf;        /* <= 0: no value clipping */
+    float ent_coef, vf_coef;
+    float *g_mean, *g_value, *g_log_std;
+    float *scalars_out;          /* [6] or NULL */
+    float *scalars_sum;          /* [6] or NULL: += */
+    float *log_prob_out;         /* [batch] or NULL: the new log-prob */
+} cstr_ppo_loss_t;
+int cstr_diag_gaussian_act_f32(const float *mean, const float *log_std, const float *eps_in, uint64_t *rng_ctl, const float *low,
+                               const float *high, int deterministic, float *action, float *env_action, float *log_prob, float *eps_out,
+                               int64_t n, int act_dim, cstr_stream_t stream);
+int cstr_rollout_add_f32(const cstr_rollout_t *rb, int64_t *ctl, const float *obs, const float *act, const float *reward,
+                         float *episode_start, const float *value, const float *log_prob, const float *timeout,
+                         const float *terminal_value, float gamma, const float *done, float *ep_return, int32_t *ep_len, double *ep_stats,
+                         cstr_stream_t stream);
+int cstr_gae_f32(const float *rewards, const float *values, const float *episode_starts, const float *last_values, const float *dones,
+                 double gamma, double gae_lambda, float *advantages, float *returns, int64_t n_steps, int64_t n_envs, cstr_stream_t stream);
+int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx, int64_t batch, float *obs, float *act, float *old_value,
+                        float *old_log_prob, float *adv, float *ret, cstr_stream_t stream);
+int cstr_ppo_loss_f32(const cstr_ppo_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
+int cstr_grad_clip_f32(float *grad, int64_t n, float max_norm, uint64_t *workspace, float *norm_out, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

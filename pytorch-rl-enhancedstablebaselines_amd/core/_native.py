@@ -19,6 +19,7 @@ RNG_CTL_WORDS, MAX_HEAD_ACT, MAX_LINEAR_SETS, MAX_ADAM_SEGS = 16, 4, 16, 4
 MAX_ENS_CRITICS = 16
 SDE_MAX_LATENT, SDE_MAX_MATS = 4096, 65537
 BCQ_MAX_LATENT, BCQ_MAX_ACT, BCQ_MAX_SAMPLES, BCQ_MAX_ROWS = 256, 64, 4096, 1 << 24
+ROLLOUT_CTL_WORDS, PPO_WS_WORDS, PPO_MAX_BLOCKS, PPO_MAX_ROWS = 4, 1024, 64, 1 << 30
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -32,6 +33,7 @@ SYMBOLS = (
     "cstr_sde_draw_f32", "cstr_sde_head_fwd_f32", "cstr_sde_head_bwd_f32", "cstr_sde_param_grad_f32",
     "cstr_bcq_latent_fwd_f32", "cstr_bcq_vae_loss_f32", "cstr_bcq_latent_bwd_f32", "cstr_bcq_expand_f32", "cstr_bcq_perturb_fwd_f32",
     "cstr_bcq_perturb_bwd_f32", "cstr_bcq_target_f32", "cstr_bcq_select_f32",
+    "cstr_diag_gaussian_act_f32", "cstr_rollout_add_f32", "cstr_gae_f32", "cstr_ppo_gather_f32", "cstr_ppo_loss_f32", "cstr_grad_clip_f32",
 )
 
 
@@ -140,6 +142,21 @@ class VecNormCfg(C.Structure):
     """cstr_vecnorm_cfg_t"""
     _fields_ = [("training", C.c_int32), ("norm_obs", C.c_int32), ("norm_reward", C.c_int32), ("obs_dim", C.c_int32),
                 ("clip_obs", C.c_double), ("clip_reward", C.c_double), ("gamma", C.c_double), ("epsilon", C.c_double)]
+
+
+class Rollout(C.Structure):
+    """cstr_rollout_t"""
+    _fields_ = [(n, C.c_void_p) for n in ("obs", "act", "rew", "episode_start", "values", "log_probs", "advantages", "returns")] + [
+        ("rows", C.c_int64), ("n_envs", C.c_int64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32)]
+
+
+class PpoLoss(C.Structure):
+    """cstr_ppo_loss_t"""
+    _fields_ = [("mean", C.c_void_p), ("ldm", C.c_int64)] + [(n, C.c_void_p) for n in (
+        "log_std", "actions", "values", "old_values", "old_log_prob", "adv", "returns")] + [
+        ("batch", C.c_int64), ("act_dim", C.c_int32), ("normalize_advantage", C.c_int32), ("clip_range", C.c_double),
+        ("clip_range_vf", C.c_double), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [(n, C.c_void_p) for n in (
+            "g_mean", "g_value", "g_log_std", "scalars_out", "scalars_sum", "log_prob_out")]
 
 
 class NativeError(RuntimeError):

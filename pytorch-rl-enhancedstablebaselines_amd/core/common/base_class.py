@@ -208,10 +208,15 @@ class BaseAlgorithm:
                 np.random.seed(reseed)
                 legacy_rng.seed(reseed, self.device)
                 (self._denv or self.env).numpy_reseed = None
+                self._numpy_reseeded(reseed)
         if not self._custom_logger:
             self._logger = configure_logger(self.verbose, self.tensorboard_log, tb_log_name, reset_num_timesteps)
         callback = self._init_callback(callback)
         return total_timesteps, callback
+
+    def _numpy_reseeded(self, seed: int) -> None:
+        """This model's own envs have just reseeded NumPy's global stream with `seed` (a seeded reset); for subclasses that keep a
+        host image of that stream."""
 
     def predict(self, observation, state=None, episode_start=None, deterministic: bool = False):
         """reference: base_class.py:560-580"""

@@ -7,15 +7,19 @@
   * `sample` draws `np.random.randint` indices from the device image of NumPy's legacy global MT19937
     stream -- bit-identical to the reference's `batch_inds` / `env_indices` -- and gathers the five
     fields in the same launch.
+
+`RolloutBuffer` (reference: core/common/buffers.py:343-521) is the on-policy counterpart: SoA in HBM with the reference's array names
+and `[T, N, ...]` shapes, `add` one launch at a device-resident position, GAE one launch, minibatches gathered by the host-drawn
+permutation (the reference's `np.random.permutation` stream), copied to the device once per epoch.
 """
-from typing import Any, Optional, Union
+from typing import Any, Generator, Optional, Union
 
 import numpy as np
 import torch as th
 
 from core.common import hip_ops, legacy_rng
 from core.common.spaces import as_box, get_action_dim, get_obs_shape
-from core.common.type_aliases import ReplayBufferSamples
+from core.common.type_aliases import ReplayBufferSamples, RolloutBufferSamples
 from core.common.utils import get_device
 
 
@@ -285,3 +289,132 @@ class PackedBatch:
         self.x_pi = self.x_pn[:batch_size] if with_pi else None
         self.samples = ReplayBufferSamples(self.x_data[:, :obs_dim], self.x_data[:, obs_dim:], self.x_next[:, :obs_dim],
                                            e(batch_size, 1), e(batch_size, 1))
+
+
+class RolloutBuffer(BaseBuffer):
+    """reference: core/common/buffers.py:343-521.
+
+    `get()` yields STATIC device tensors (one set per minibatch size): a sample is valid until the next one is drawn.
+    :param permutation_rng: the `np.random.RandomState` `get()` draws `permutation(T * N)` from; None = NumPy's global legacy
+        stream, which is what the reference consumes (:483)
+    """
+
+    _FIELDS = hip_ops.DeviceRollout.FIELDS
+
+    def __init__(self, buffer_size: int, observation_space, action_space, device: Union[th.device, str] = "auto",
+                 gae_lambda: float = 1, gamma: float = 0.99, n_envs: int = 1, permutation_rng=None):
+        super().__init__(buffer_size, observation_space, action_space, device, n_envs=n_envs)
+        self.gae_lambda, self.gamma = gae_lambda, gamma
+        if len(self.obs_shape) != 1:
+            raise ValueError(f"RolloutBuffer supports flat Box observations, got shape {self.obs_shape}")
+        with th.cuda.device(self.device):
+            self.rb = hip_ops.DeviceRollout(buffer_size, n_envs, self.obs_shape[0], self.action_dim, self.device)
+        for name in self._FIELDS:
+            setattr(self, name, getattr(self.rb, name))
+        self.permutation_rng = permutation_rng
+        self.forced_permutations: list = []  # teacher-forcing hook: each get() pops its permutation from here first (tests)
+        self._mb: dict = {}
+
+    @property
+    def pos(self) -> int:
+        return min(self._adds, self.buffer_size)
+
+    @property
+    def full(self) -> bool:
+        return self._adds >= self.buffer_size  # :478-479
+
+    def reset(self) -> None:
+        """:391-401"""
+        for name in self._FIELDS:
+            getattr(self, name).zero_()
+        self.rb.ctl.zero_()
+        self._adds = 0
+
+    @classmethod
+    def from_arrays(cls, observation_space, action_space, device, observations, actions, rewards, episode_starts, values, log_probs,
+                    advantages=None, returns=None, gae_lambda: float = 1, gamma: float = 0.99) -> "RolloutBuffer":
+        """A FULL buffer holding the given host arrays with the reference's shapes: observations [T, N, D], actions [T, N, A], the
+        others [T, N] (advantages / returns: zeros when absent, to be filled by compute_returns_and_advantage)."""
+        rows, n_envs = np.shape(rewards)
+        buf = cls(rows, observation_space, action_space, device=device, gae_lambda=gae_lambda, gamma=gamma, n_envs=n_envs)
+        given = dict(observations=observations, actions=actions, rewards=rewards, episode_starts=episode_starts, values=values,
+                     log_probs=log_probs, advantages=advantages, returns=returns)
+        for name, arr in given.items():
+            if arr is not None:
+                field = getattr(buf, name)
+                field.copy_(th.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).reshape(field.shape))
+        buf._adds = rows
+        buf.rb.ctl.copy_(th.tensor([rows, 1, 0, rows], dtype=th.int64))
+        return buf
+
+    def _dev(self, x, shape) -> th.Tensor:
+        if isinstance(x, th.Tensor):
+            t = x.detach().to(self.device, th.float32)
+        else:
+            t = th.as_tensor(np.ascontiguousarray(np.asarray(x), dtype=np.float32)).to(self.device)
+        return t.reshape(shape).contiguous()
+
+    def add(self, obs, action, reward, episode_start, value, log_prob) -> None:
+        """:440-479. Accepts NumPy (compatibility) or device tensors."""
+        n = self.n_envs
+        if self.full:
+            raise IndexError(f"index {self.buffer_size} is out of bounds for axis 0 with size {self.buffer_size}")  # what :471 raises
+        with th.cuda.device(self.device):
+            hip_ops.rollout_add(self.rb, self._dev(obs, (n, *self.obs_shape)), self._dev(action, (n, self.action_dim)), self._dev(reward, (n,)),
+                                self._dev(episode_start, (n,)).clone(), self._dev(value, (n,)), self._dev(log_prob, (n,)))
+        self._adds += 1
+
+    def add_device(self, obs, action, reward, episode_start, value, log_prob, timeout=None, terminal_value=None, done=None,
+                   ep_return=None, ep_len=None, ep_stats=None) -> None:
+        """`add` for the device rollout: every operand is a static [N, .] device tensor, so consecutive calls pass identical
+        arguments (the write position lives in HBM). reward += gamma * terminal_value where timeout
+        (on_policy_algorithm.py:236-245); with `done`, `episode_start` is overwritten with it for the next call."""
+        if self.full:
+            raise IndexError(f"index {self.buffer_size} is out of bounds for axis 0 with size {self.buffer_size}")
+        hip_ops.rollout_add(self.rb, obs, action, reward, episode_start, value, log_prob, timeout, terminal_value, self.gamma, done,
+                            ep_return, ep_len, ep_stats)
+        self._adds += 1
+
+    def compute_returns_and_advantage(self, last_values, dones) -> None:
+        """:403-438, one launch (bit-identical to the reference's NumPy loop)"""
+        n = self.n_envs
+        with th.cuda.device(self.device):
+            hip_ops.gae(self.rb, self._dev(last_values, (n,)), self._dev(np.asarray(dones, np.float32) if not isinstance(dones, th.Tensor) else dones, (n,)),
+                        self.gamma, self.gae_lambda)
+
+    @staticmethod
+    def swap_and_flatten(arr):
+        """:86-99: [T, N, ...] -> [N * T, ...], env-major (flat index i = env i // T, step i % T)"""
+        shape = arr.shape
+        if len(shape) < 3:
+            shape = (*shape, 1)
+        return arr.swapaxes(0, 1).reshape(shape[0] * shape[1], *shape[2:])
+
+    def _minibatch(self, rows: int) -> RolloutBufferSamples:
+        mb = self._mb.get(rows)
+        if mb is None:
+            e = lambda *s: th.empty(*s, dtype=th.float32, device=self.device)  # noqa: E731
+            mb = self._mb[rows] = RolloutBufferSamples(e(rows, self.obs_shape[0]), e(rows, self.action_dim), e(rows), e(rows), e(rows), e(rows))
+        return mb
+
+    def get(self, batch_size: Optional[int] = None) -> Generator[RolloutBufferSamples, None, None]:
+        """:481-506. One permutation per call, copied to the device once; the last minibatch may be shorter than batch_size."""
+        assert self.full, ""
+        total = self.buffer_size * self.n_envs
+        if self.forced_permutations:
+            indices = np.asarray(self.forced_permutations.pop(0), dtype=np.int64)
+            if indices.shape != (total,) or indices.min() < 0 or indices.max() >= total:
+                raise ValueError(f"a forced permutation must hold {total} indices in [0, {total})")
+        else:
+            indices = (np.random if self.permutation_rng is None else self.permutation_rng).permutation(total).astype(np.int64)
+        idx = th.from_numpy(np.ascontiguousarray(indices)).to(self.device)
+        if batch_size is None:
+            batch_size = total
+        start = 0
+        while start < total:
+            part = idx[start:start + batch_size]
+            mb = self._minibatch(part.shape[0])
+            with th.cuda.device(self.device):
+                hip_ops.ppo_gather(self.rb, part, *mb)
+            yield mb
+            start += batch_size

@@ -7,6 +7,7 @@ import math
 from typing import List, Optional
 
 import torch as th
+from torch import nn
 
 
 class SquashedDiagGaussianDistribution:
@@ -205,4 +206,52 @@ class StateDependentNoiseDistribution:
 
     def log_prob_from_params(self, mean_actions, log_std, latent_sde):
         actions = self.actions_from_params(mean_actions, log_std, latent_sde)
+        return actions, self.log_prob(actions)
+
+
+class DiagGaussianDistribution:
+    """reference: core/common/distributions.py:125-204 -- the unsquashed diagonal Gaussian of the on-policy algorithms (torch
+    statements: the API and the torch-statement path; the kernel path evaluates the same expressions in csrc/cstr_ppo.hip).
+    `eps_queue`: teacher-forcing hook, each `sample()` pops its standard-normal draw from here first (tests)."""
+
+    def __init__(self, action_dim: int):
+        self.action_dim = action_dim
+        self.distribution = None
+        self.eps_queue: list = []
+
+    def proba_distribution_net(self, latent_dim: int, log_std_init: float = 0.0):
+        mean_actions = nn.Linear(latent_dim, self.action_dim)
+        log_std = nn.Parameter(th.ones(self.action_dim) * log_std_init, requires_grad=True)
+        return mean_actions, log_std
+
+    def proba_distribution(self, mean_actions: th.Tensor, log_std: th.Tensor) -> "DiagGaussianDistribution":
+        action_std = th.ones_like(mean_actions) * log_std.exp()
+        self.distribution = th.distributions.Normal(mean_actions, action_std)
+        return self
+
+    def log_prob(self, actions: th.Tensor) -> th.Tensor:
+        return self.distribution.log_prob(actions).sum(dim=1)  # sum_independent_dims
+
+    def entropy(self) -> th.Tensor:
+        return self.distribution.entropy().sum(dim=1)
+
+    def sample(self) -> th.Tensor:
+        d = self.distribution
+        if self.eps_queue:
+            eps = self.eps_queue.pop(0).to(d.loc.device, d.loc.dtype).reshape(d.loc.shape)
+            return d.loc + eps * d.scale  # rsample's statement with the draw given
+        return d.rsample()
+
+    def mode(self) -> th.Tensor:
+        return self.distribution.mean
+
+    def get_actions(self, deterministic: bool = False) -> th.Tensor:
+        return self.mode() if deterministic else self.sample()
+
+    def actions_from_params(self, mean_actions: th.Tensor, log_std: th.Tensor, deterministic: bool = False) -> th.Tensor:
+        self.proba_distribution(mean_actions, log_std)
+        return self.get_actions(deterministic=deterministic)
+
+    def log_prob_from_params(self, mean_actions: th.Tensor, log_std: th.Tensor):
+        actions = self.actions_from_params(mean_actions, log_std)
         return actions, self.log_prob(actions)

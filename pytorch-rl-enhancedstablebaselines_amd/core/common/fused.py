@@ -1335,3 +1335,69 @@ def twin_stack(arena, first_group: int = 0, n_layers: Optional[int] = None):
         b, bg = arena.stacked(first_group + 2 * li + 1)
         out.append((w, wg, b.view(b.shape[0], -1), None if bg is None else bg.view(bg.shape[0], -1)))
     return out or None
+
+
+class FastActorCritic:
+    """The on-policy ActorCriticPolicy (core/common/policies.py) on the kernel path: both trunks and both heads through the per-layer
+    Linear kernels (`linear`: forward, and backward with deferred weight gradients), the diagonal Gaussian head in one launch
+    (hip_ops.diag_gaussian_act). Noise: `eps_queue` (teacher-forced [n, A] draws, tests) first, the Philox stream `rng_ctl` otherwise."""
+
+    def __init__(self, policy, rng_ctl: Optional[th.Tensor] = None):
+        self.policy = policy
+        self.pi_layers = FastMLP(policy.mlp_extractor.policy_net).layers + [(policy.action_net, ACT_NONE)]
+        self.vf_layers = FastMLP(policy.mlp_extractor.value_net).layers + [(policy.value_net, ACT_NONE)]
+        self.act_dim = policy.action_net.out_features
+        dev = policy.log_std.device
+        self.low = th.as_tensor(policy.action_space.low, dtype=th.float32).reshape(-1).to(dev).contiguous()
+        self.high = th.as_tensor(policy.action_space.high, dtype=th.float32).reshape(-1).to(dev).contiguous()
+        self.rng_ctl = rng_ctl
+        self.eps_queue: list = []
+        self._bufs: dict = {}
+
+    @staticmethod
+    def supported(policy) -> bool:
+        ext = policy.mlp_extractor
+        return (FastMLP.supported(ext.policy_net) and FastMLP.supported(ext.value_net)
+                and hip_ops.ppo_supported(policy.features_dim, policy.action_net.out_features)
+                and all(p.grad is not None for p in policy.parameters()))
+
+    @staticmethod
+    def _run(layers, x: th.Tensor, train_params: bool) -> th.Tensor:
+        below, last = None, len(layers) - 1
+        for i, (lin, act) in enumerate(layers):
+            x = linear(x, lin.weight, lin.bias, act, train_params, below, grad_is_dz=i < last)
+            below = (act, None)
+        return x
+
+    def mean(self, obs: th.Tensor, train_params: bool = False) -> th.Tensor:
+        """the action mean [n, A]"""
+        return self._run(self.pi_layers, obs, train_params)
+
+    def values(self, obs: th.Tensor, train_params: bool = False) -> th.Tensor:
+        """the value estimate [n, 1]"""
+        return self._run(self.vf_layers, obs, train_params)
+
+    def bufs(self, n: int, device) -> dict:
+        b = self._bufs.get(n)
+        if b is None:
+            e = lambda *sh: th.empty(*sh, dtype=th.float32, device=device)  # noqa: E731
+            b = self._bufs[n] = dict(action=e(n, self.act_dim), env_action=e(n, self.act_dim), log_prob=e(n))
+        return b
+
+    def act(self, obs: th.Tensor, deterministic: bool = False, want_value: bool = True):
+        """ActorCriticPolicy.forward without gradients -> (actions [n, A] unclipped, values [n, 1] or None, log_prob [n], env_action =
+        clip(actions, low, high)). The outputs are static per row count: valid until the next call with as many rows."""
+        with th.no_grad():
+            n = obs.shape[0]
+            b = self.bufs(n, obs.device)
+            mean = self.mean(obs)
+            values = self.values(obs) if want_value else None
+            eps = None
+            if not deterministic and self.eps_queue:
+                eps = self.eps_queue.pop(0).to(obs.device, th.float32).reshape(n, self.act_dim).contiguous()
+            rng = None if (deterministic or eps is not None) else self.rng_ctl
+            if not deterministic and eps is None and rng is None:
+                raise RuntimeError("FastActorCritic.act: no noise source (neither a queued draw nor a Philox stream)")
+            hip_ops.diag_gaussian_act(mean, self.policy.log_std.detach(), eps, rng, self.low, self.high, deterministic, b["action"],
+                                      b["env_action"], b["log_prob"])
+            return b["action"], values, b["log_prob"], b["env_action"]

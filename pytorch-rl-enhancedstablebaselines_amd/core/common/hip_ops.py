@@ -1355,3 +1355,120 @@ def chain_sum_parts(part, out):
         raise ValueError("out: needs a float32 device matrix with unit inner stride")
     check(nv.lib().cstr_chain_sum_parts_f32(ptr(part), C.c_int(n_parts), C.c_int64(rows), C.c_int(cols), ptr(out), C.c_int64(out.stride(0)), stream_ptr()),
           "cstr_chain_sum_parts_f32")
+
+
+# ---- PPO: rollout head, rollout buffer, GAE, minibatch gather, loss, gradient clip (csrc/cstr_ppo.hip) ---------------------------
+PPO_SCALARS = ("policy_gradient_loss", "value_loss", "entropy_loss", "loss", "approx_kl", "clip_fraction")
+
+
+def ppo_supported(obs_dim: int, act_dim: int) -> bool:
+    return obs_dim in (4, 8) and act_dim in (2, 4)
+
+
+def new_ppo_workspace(device) -> th.Tensor:
+    """uint64[CSTR_PPO_WS_WORDS] (as int64) for cstr_ppo_loss_f32 / cstr_grad_clip_f32: zero before the first use, one per stream"""
+    return th.zeros(nv.PPO_WS_WORDS, dtype=th.int64, device=device)
+
+
+class DeviceRollout:
+    """cstr_rollout_t + its control words over torch tensors (HBM). Field arrays have the reference's names and shapes
+    (core/common/buffers.py:392-399): [T, N, D] / [T, N, A] / [T, N]; ctl = {pos, full, ticket, adds}."""
+
+    FIELDS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
+
+    def __init__(self, rows: int, n_envs: int, obs_dim: int, act_dim: int, device):
+        if not ppo_supported(obs_dim, act_dim):
+            raise ValueError(f"DeviceRollout supports obs_dim in (4, 8) and act_dim in (2, 4), got {obs_dim}/{act_dim}")
+        if rows <= 0 or n_envs <= 0:
+            raise ValueError(f"DeviceRollout needs rows >= 1 and n_envs >= 1, got {rows}/{n_envs}")
+        z = lambda *s: th.zeros(*s, dtype=th.float32, device=device)  # noqa: E731
+        self.observations, self.actions = z(rows, n_envs, obs_dim), z(rows, n_envs, act_dim)
+        self.rewards, self.episode_starts, self.values, self.log_probs, self.advantages, self.returns = (z(rows, n_envs) for _ in range(6))
+        self.ctl = th.zeros(nv.ROLLOUT_CTL_WORDS, dtype=th.int64, device=device)
+        self.rows, self.n_envs, self.obs_dim, self.act_dim = rows, n_envs, obs_dim, act_dim
+        self.c = nv.Rollout(*(getattr(self, f).data_ptr() for f in self.FIELDS), rows, n_envs, obs_dim, act_dim)
+
+
+def diag_gaussian_act(mean, log_std, eps, rng_ctl, low, high, deterministic: bool, action, env_action=None, log_prob=None, eps_out=None):
+    """action = mean + exp(log_std) * eps (deterministic: mean); env_action = clip(action, low, high); log_prob [n]. eps is read when
+    given, drawn from the Philox stream `rng_ctl` otherwise."""
+    n, a = mean.shape
+    _chk(mean, "mean", (n, a), th.float32), _chk(log_std, "log_std", (a,), th.float32), _chk(action, "action", (n, a), th.float32)
+    _opt(eps, "eps", (n, a), th.float32), _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    _opt(env_action, "env_action", (n, a), th.float32), _opt(log_prob, "log_prob", (n,), th.float32), _opt(eps_out, "eps_out", (n, a), th.float32)
+    _opt(low, "low", (a,), th.float32), _opt(high, "high", (a,), th.float32)
+    check(nv.lib().cstr_diag_gaussian_act_f32(ptr(mean), ptr(log_std), ptr(eps), ptr(rng_ctl), ptr(low), ptr(high), C.c_int(int(bool(deterministic))),
+                                              ptr(action), ptr(env_action), ptr(log_prob), ptr(eps_out), C.c_int64(n), C.c_int(a), stream_ptr()),
+          "cstr_diag_gaussian_act_f32")
+
+
+def rollout_add(rb: DeviceRollout, obs, act, reward, episode_start, value, log_prob, timeout=None, terminal_value=None, gamma: float = 0.99,
+                done=None, ep_return=None, ep_len=None, ep_stats=None):
+    """RolloutBuffer.add at the device position (+ reward += f32(gamma) * terminal_value where timeout: c_float rounds gamma). With `done`, `episode_start`
+    becomes `done` for the next call; with ep_return / ep_len / ep_stats the episode statistics accumulate in the same launch."""
+    n, d, a = rb.n_envs, rb.obs_dim, rb.act_dim
+    _chk(obs, "obs", (n, d), th.float32), _chk(act, "act", (n, a), th.float32)
+    for t, nm in ((reward, "reward"), (episode_start, "episode_start"), (value, "value"), (log_prob, "log_prob")):
+        _chk(t, nm, (n,), th.float32)
+    for t, nm in ((timeout, "timeout"), (terminal_value, "terminal_value"), (done, "done"), (ep_return, "ep_return")):
+        _opt(t, nm, (n,), th.float32)
+    _opt(ep_len, "ep_len", (n,), th.int32), _opt(ep_stats, "ep_stats", (4,), th.float64)
+    check(nv.lib().cstr_rollout_add_f32(C.byref(rb.c), ptr(rb.ctl), ptr(obs), ptr(act), ptr(reward), ptr(episode_start), ptr(value),
+                                        ptr(log_prob), ptr(timeout), ptr(terminal_value), C.c_float(gamma), ptr(done), ptr(ep_return),
+                                        ptr(ep_len), ptr(ep_stats), stream_ptr()), "cstr_rollout_add_f32")
+
+
+def gae(rb: DeviceRollout, last_values, dones, gamma: float, gae_lambda: float):
+    """compute_returns_and_advantage over the whole buffer (bit-identical to NumPy's evaluation)"""
+    t, n = rb.rows, rb.n_envs
+    _chk(last_values, "last_values", (n,), th.float32), _chk(dones, "dones", (n,), th.float32)
+    check(nv.lib().cstr_gae_f32(ptr(rb.rewards), ptr(rb.values), ptr(rb.episode_starts), ptr(last_values), ptr(dones), C.c_double(gamma),
+                                C.c_double(gae_lambda), ptr(rb.advantages), ptr(rb.returns), C.c_int64(t), C.c_int64(n), stream_ptr()),
+          "cstr_gae_f32")
+
+
+def ppo_gather(rb: DeviceRollout, idx, obs, act, old_value, old_log_prob, adv, ret):
+    """rows idx (flat swap_and_flatten order: env idx // T, step idx % T) of the six minibatch fields into contiguous tensors"""
+    b = idx.shape[0]
+    _chk(idx, "idx", (b,), th.int64), _chk(obs, "obs", (b, rb.obs_dim), th.float32), _chk(act, "act", (b, rb.act_dim), th.float32)
+    for t, nm in ((old_value, "old_value"), (old_log_prob, "old_log_prob"), (adv, "adv"), (ret, "ret")):
+        _chk(t, nm, (b,), th.float32)
+    check(nv.lib().cstr_ppo_gather_f32(C.byref(rb.c), ptr(idx), C.c_int64(b), ptr(obs), ptr(act), ptr(old_value), ptr(old_log_prob), ptr(adv),
+                                       ptr(ret), stream_ptr()), "cstr_ppo_gather_f32")
+
+
+def ppo_loss(mean, log_std, actions, values, old_values, old_log_prob, adv, returns, clip_range: float, clip_range_vf: Optional[float],
+             normalize_advantage: bool, ent_coef: float, vf_coef: float, g_mean, g_value, g_log_std, workspace, scalars_out=None,
+             scalars_sum=None, log_prob_out=None):
+    """ppo.py:213-264 in one launch: the six scalars (PPO_SCALARS order) and d loss / d (mean, value, log_std)."""
+    b, a = actions.shape
+    ldm = _rows(mean, "mean", b, a)
+    _chk(log_std, "log_std", (a,), th.float32), _chk(actions, "actions", (b, a), th.float32)
+    for t, nm in ((values, "values"), (old_log_prob, "old_log_prob"), (adv, "adv"), (returns, "returns"), (g_value, "g_value")):
+        _vec(t, nm, b)
+    if old_values is not None:
+        _vec(old_values, "old_values", b)
+    _chk(g_mean, "g_mean", (b, a), th.float32), _vec(g_log_std, "g_log_std", a)
+    _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+    for t, nm in ((scalars_out, "scalars_out"), (scalars_sum, "scalars_sum")):
+        if t is not None:
+            _vec(t, nm, 6)
+    if log_prob_out is not None:
+        _vec(log_prob_out, "log_prob_out", b)
+    p = nv.PpoLoss(mean.data_ptr(), ldm, log_std.data_ptr(), actions.data_ptr(), values.data_ptr(),
+                   None if old_values is None else old_values.data_ptr(), old_log_prob.data_ptr(), adv.data_ptr(), returns.data_ptr(), b, a,
+                   int(bool(normalize_advantage)), float(clip_range), -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef),
+                   float(vf_coef), g_mean.data_ptr(), g_value.data_ptr(), g_log_std.data_ptr(),
+                   None if scalars_out is None else scalars_out.data_ptr(), None if scalars_sum is None else scalars_sum.data_ptr(),
+                   None if log_prob_out is None else log_prob_out.data_ptr())
+    check(nv.lib().cstr_ppo_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_ppo_loss_f32")
+
+
+def grad_clip(grad, max_norm: float, workspace, norm_out=None):
+    """torch.nn.utils.clip_grad_norm_ over one flat gradient buffer, in place; the coefficient never visits the host"""
+    n = grad.numel()
+    _vec(grad, "grad", n), _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+    if norm_out is not None:
+        _vec(norm_out, "norm_out", 1)
+    check(nv.lib().cstr_grad_clip_f32(ptr(grad), C.c_int64(n), C.c_float(max_norm), ptr(workspace), ptr(norm_out), stream_ptr()),
+          "cstr_grad_clip_f32")

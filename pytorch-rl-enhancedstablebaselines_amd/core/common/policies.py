@@ -1,4 +1,5 @@
 """Policy base classes and the continuous critic (reference: core/common/policies.py:39-414, :912-987)."""
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -125,3 +126,115 @@ class ContinuousCritic(BaseModel):
         with th.no_grad():
             features = self.extract_features(obs, self.features_extractor)
         return self.q_networks[0](th.cat([features, actions], dim=1))
+
+
+class ActorCriticPolicy(BasePolicy):
+    """reference: core/common/policies.py:416-771 -- policy and value networks of the on-policy algorithms, Box actions and a
+    FlattenExtractor only. Built on the CPU generator in the reference's order (same seed -> the same default initial weights; the
+    orthogonal initialisation goes through LAPACK's QR), then `to_device_arenas` moves EVERY parameter, `log_std` included, into one
+    flat arena under one optimiser (Adam: eps = 1e-5, :468-472). `fast` (core/common/fused.py FastActorCritic): the kernel form of
+    forward / evaluate / predict_values, set by the algorithm."""
+
+    def __init__(self, observation_space, action_space, lr_schedule, net_arch=None, activation_fn=nn.Tanh, ortho_init: bool = True,
+                 use_sde: bool = False, log_std_init: float = 0.0, full_std: bool = True, use_expln: bool = False,
+                 squash_output: bool = False, features_extractor_class=FlattenExtractor, features_extractor_kwargs: Optional[dict] = None,
+                 share_features_extractor: bool = True, normalize_images: bool = True, optimizer_class=th.optim.Adam,
+                 optimizer_kwargs: Optional[dict] = None):
+        from core.common.distributions import DiagGaussianDistribution
+        from core.common.torch_layers import MlpExtractor
+
+        if optimizer_kwargs is None:
+            optimizer_kwargs = {}
+            if optimizer_class == th.optim.Adam:
+                optimizer_kwargs["eps"] = 1e-5  # :470-472
+        super().__init__(observation_space, action_space, features_extractor_class, features_extractor_kwargs,
+                         optimizer_class=optimizer_class, optimizer_kwargs=optimizer_kwargs, squash_output=squash_output,
+                         normalize_images=normalize_images)
+        if use_sde:
+            raise ValueError("ActorCriticPolicy does not support gSDE (use_sde=True): on-policy gSDE is not built")
+        assert not squash_output, "squash_output=True is only available when using gSDE (use_sde=True)"  # :519
+        if isinstance(net_arch, list) and len(net_arch) > 0 and isinstance(net_arch[0], dict):
+            warnings.warn("As shared layers in the mlp_extractor are removed since SB3 v1.8.0, you should now pass directly a dictionary "
+                          "and not a list (net_arch=dict(pi=..., vf=...) instead of net_arch=[dict(pi=..., vf=...)])")
+            net_arch = net_arch[0]
+        if net_arch is None:
+            net_arch = dict(pi=[64, 64], vf=[64, 64])
+        self.net_arch, self.activation_fn, self.ortho_init = net_arch, activation_fn, ortho_init
+        self.share_features_extractor = share_features_extractor
+        self.features_extractor = self.make_features_extractor()  # raises for anything but the FlattenExtractor
+        self.features_dim = self.features_extractor.features_dim
+        self.pi_features_extractor = self.vf_features_extractor = self.features_extractor  # a FlattenExtractor has no parameters
+        self.log_std_init, self.use_sde, self.dist_kwargs = log_std_init, False, None
+        self.action_dist = DiagGaussianDistribution(get_action_dim(self.action_space))
+        self._lr_schedule = lr_schedule
+        self.fast = None
+        # :585-631
+        self.mlp_extractor = MlpExtractor(self.features_dim, net_arch=self.net_arch, activation_fn=self.activation_fn)
+        self.action_net, self.log_std = self.action_dist.proba_distribution_net(latent_dim=self.mlp_extractor.latent_dim_pi,
+                                                                                log_std_init=self.log_std_init)
+        self.value_net = nn.Linear(self.mlp_extractor.latent_dim_vf, 1)
+        if self.ortho_init:
+            for module, gain in ((self.mlp_extractor, np.sqrt(2)), (self.action_net, 0.01), (self.value_net, 1)):
+                module.apply(lambda m, gain=gain: self.init_weights(m, gain=gain))
+        self.optimizer = None  # to_device_arenas
+
+    @staticmethod
+    def init_weights(module: nn.Module, gain: float = 1) -> None:
+        """reference: policies.py:312-320"""
+        if isinstance(module, nn.Linear):
+            nn.init.orthogonal_(module.weight, gain=gain)
+            if module.bias is not None:
+                module.bias.data.fill_(0.0)
+
+    def to_device_arenas(self, device) -> None:
+        from core.common.arena import make_optimizer
+
+        self.arena, self.optimizer = make_optimizer(self.parameters(), device, self._lr_schedule(1), self.optimizer_class, self.optimizer_kwargs)
+
+    def flat_optimizers(self) -> list:
+        from core.common.arena import FlatAdam
+
+        return [self.optimizer] if isinstance(self.optimizer, FlatAdam) else []
+
+    # ---- the reference's statements on the arena parameters ----------------------------------------------------------
+    def _get_action_dist_from_latent(self, latent_pi: th.Tensor):
+        return self.action_dist.proba_distribution(self.action_net(latent_pi), self.log_std)
+
+    def forward(self, obs: th.Tensor, deterministic: bool = False) -> tuple:
+        """:636-658 -> (actions, values [n, 1], log_prob [n])"""
+        if self.fast is not None and obs.is_cuda and not th.is_grad_enabled():
+            return self.fast.act(obs.float().contiguous(), deterministic)[:3]
+        features = self.extract_features(obs, self.features_extractor)
+        latent_pi, latent_vf = self.mlp_extractor(features)
+        values = self.value_net(latent_vf)
+        distribution = self._get_action_dist_from_latent(latent_pi)
+        actions = distribution.get_actions(deterministic=deterministic)
+        log_prob = distribution.log_prob(actions)
+        return actions.reshape((-1, *self.action_space.shape)), values, log_prob
+
+    def evaluate_actions(self, obs: th.Tensor, actions: th.Tensor) -> tuple:
+        """:719-741 -> (values [n, 1], log_prob [n], entropy [n])"""
+        features = self.extract_features(obs, self.features_extractor)
+        latent_pi, latent_vf = self.mlp_extractor(features)
+        distribution = self._get_action_dist_from_latent(latent_pi)
+        log_prob = distribution.log_prob(actions)
+        values = self.value_net(latent_vf)
+        return values, log_prob, distribution.entropy()
+
+    def get_distribution(self, obs: th.Tensor):
+        """:743-752"""
+        features = self.extract_features(obs, self.pi_features_extractor)
+        return self._get_action_dist_from_latent(self.mlp_extractor.forward_actor(features))
+
+    def predict_values(self, obs: th.Tensor) -> th.Tensor:
+        """:754-763 -> [n, 1]"""
+        if self.fast is not None and obs.is_cuda and not th.is_grad_enabled():
+            return self.fast.values(obs.float().contiguous()).reshape(-1, 1)
+        features = self.extract_features(obs, self.vf_features_extractor)
+        return self.value_net(self.mlp_extractor.forward_critic(features))
+
+    def _predict(self, observation: th.Tensor, deterministic: bool = False) -> th.Tensor:
+        """:709-717"""
+        if self.fast is not None and observation.is_cuda and not th.is_grad_enabled():
+            return self.fast.act(observation.float().contiguous(), deterministic, want_value=False)[0]
+        return self.get_distribution(observation).get_actions(deterministic=deterministic)

@@ -38,3 +38,30 @@ def get_actor_critic_arch(net_arch: Union[list, dict]) -> tuple:
     assert "pi" in net_arch, "Error: no key 'pi' was provided in net_arch for the actor network"
     assert "qf" in net_arch, "Error: no key 'qf' was provided in net_arch for the critic network"
     return net_arch["pi"], net_arch["qf"]
+
+
+class MlpExtractor(nn.Module):
+    """reference: core/common/torch_layers.py:186-264 -- the policy and the value trunk of an actor-critic policy. Every policy layer
+    is created before the first value layer (the reference's order: the same seed gives the same default initial weights)."""
+
+    def __init__(self, feature_dim: int, net_arch: Union[list, dict], activation_fn):
+        super().__init__()
+        if isinstance(net_arch, dict):
+            pi_dims, vf_dims = net_arch.get("pi", []), net_arch.get("vf", [])  # a missing key: a linear network
+        else:
+            pi_dims = vf_dims = net_arch
+        policy_net = create_mlp(feature_dim, 0, list(pi_dims), activation_fn)
+        value_net = create_mlp(feature_dim, 0, list(vf_dims), activation_fn)
+        self.latent_dim_pi = pi_dims[-1] if len(pi_dims) else feature_dim
+        self.latent_dim_vf = vf_dims[-1] if len(vf_dims) else feature_dim
+        self.policy_net = nn.Sequential(*policy_net)
+        self.value_net = nn.Sequential(*value_net)
+
+    def forward(self, features: th.Tensor) -> tuple:
+        return self.forward_actor(features), self.forward_critic(features)
+
+    def forward_actor(self, features: th.Tensor) -> th.Tensor:
+        return self.policy_net(features)
+
+    def forward_critic(self, features: th.Tensor) -> th.Tensor:
+        return self.value_net(features)

@@ -13,6 +13,15 @@ class ReplayBufferSamples(NamedTuple):
     rewards: th.Tensor
 
 
+class RolloutBufferSamples(NamedTuple):
+    observations: th.Tensor
+    actions: th.Tensor
+    old_values: th.Tensor
+    old_log_prob: th.Tensor
+    advantages: th.Tensor
+    returns: th.Tensor
+
+
 class RolloutReturn(NamedTuple):
     episode_timesteps: int
     n_episodes: int

@@ -1,0 +1,591 @@
+// cstr_ppo.hip -- PPO's own arithmetic around the Linear layers (reference core/ppo/ppo.py:184-300,
+// core/common/on_policy_algorithm.py:162-268, core/common/buffers.py:343-521 RolloutBuffer, core/common/distributions.py
+// DiagGaussianDistribution), f32, gfx950:
+//   * the rollout head: action = mean + exp(log_std) * eps (stored unclipped), env_action = clip(action, low, high), log_prob;
+//   * RolloutBuffer.add at the device-resident position, with the timeout bootstrap reward += gamma * V(terminal observation);
+//   * compute_returns_and_advantage (GAE), one lane per env, NumPy's expression order and rounding points (bit-identical);
+//   * the minibatch gather by flat swap_and_flatten indices (index i = env i / T, step i % T);
+//   * everything between evaluate_actions' outputs and loss.backward() (ppo.py:213-264): advantage normalisation, the diagonal
+//     Gaussian's log-prob and entropy, ratio and clipped surrogate, the (clipped) value loss, the six logged scalars and the
+//     gradients w.r.t. the action mean, the value and log_std;
+//   * clip_grad_norm_ over the flat gradient arena (the coefficient stays on the device).
+// Noise is READ when given and DRAWN otherwise: Philox4x32-10 keyed by rng_ctl[0], counter (rng_ctl[1] + row, 0, PPO tag) -> two
+// Box-Muller pairs = the row's (up to four) draws; the last workgroup advances rng_ctl[1] by the row count.
+// Batch reductions have a fixed order and no float atomics: every thread sums its rows in f64, a fixed LDS tree per workgroup, the
+// per-workgroup partials are published (agent-scope stores, release fence, ticket) and the workgroup that draws the last ticket sums
+// them in workgroup order behind an acquire fence. The grid is a function of the row count alone, so a given batch always reduces
+// the same way. The gradient clip is two launches (partials, then every workgroup sums the partials in the same order and scales
+// its share), so no workgroup waits for another inside a launch.
+// NOT a batch reduction, and not order-deterministic: the Monitor-style episode statistics of the add launch (ep_stats: f64
+// atomicAdd per finished episode, the convention of cstr_collect_step_f32). The count and the sum of lengths are integers in f64 and
+// so exact in any order; the sum of returns, which only feeds the logged rollout/ep_rew_mean, may differ in its last f64 bits.
+// NaN: fminf / fmaxf in the clips DROP a NaN operand where torch.min / clamp propagate it; the losses still go NaN through the
+// unclipped terms.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cstr_rl_hip.h"
+#include "cstr_device.h"
+#include "cstr_rng_device.h"
+
+namespace {
+
+constexpr uint32_t PPO_STREAM_TAG = 0x990A11C7u;  // counter word 3: never shares counters with the other heads' streams
+constexpr float LOG_SQRT_2PI = 0.918938533204672742f;  // math.log(math.sqrt(2 * math.pi)) (torch Normal.log_prob)
+constexpr float HALF_LOG_2PI_E = 1.418938533204672742f;  // 0.5 + 0.5 * math.log(2 * math.pi) (torch Normal.entropy)
+constexpr int LOSS_PARTS = 8;  // policy sum, value sum, kl sum, clipped count, d log_std[0..3]
+constexpr int WS_PART0 = 8;    // workspace word of the first partial (word 0: the ticket; 64-byte offset keeps it on its own line)
+
+template <int W> struct VecOf;
+template <> struct VecOf<2> { typedef float2 type; };
+template <> struct VecOf<4> { typedef float4 type; };
+
+template <int W> __device__ __forceinline__ void load_row(const float *p, float (&v)[W])
+{
+    const typename VecOf<W>::type t = *reinterpret_cast<const typename VecOf<W>::type *>(p);
+    const float *f = reinterpret_cast<const float *>(&t);
+#pragma unroll
+    for (int k = 0; k < W; ++k) v[k] = f[k];
+}
+
+template <int W> __device__ __forceinline__ void store_row(float *p, const float (&v)[W])
+{
+    typename VecOf<W>::type t;
+    float *f = reinterpret_cast<float *>(&t);
+#pragma unroll
+    for (int k = 0; k < W; ++k) f[k] = v[k];
+    *reinterpret_cast<typename VecOf<W>::type *>(p) = t;
+}
+
+// distributions.py DiagGaussianDistribution.log_prob = sum over the action dimensions of torch's Normal.log_prob:
+// -((a - mu)^2) / (2 sigma^2) - log(sigma) - log(sqrt(2 pi)), sigma = exp(log_std)
+template <int A> __device__ __forceinline__ float diag_log_prob(const float (&act)[A], const float (&mu)[A], const float (&sig)[A])
+{
+    float lp = 0.0f;
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+        const float d = act[k] - mu[k];
+        lp += (-(d * d) / (2.0f * (sig[k] * sig[k])) - logf(sig[k])) - LOG_SQRT_2PI;
+    }
+    return lp;
+}
+
+// on_policy_algorithm.py:199-216: one lane per env
+template <int A>
+__global__ __launch_bounds__(64) void diag_gaussian_act_kernel(const float *__restrict__ mean, const float *__restrict__ log_std,
+                                                               const float *__restrict__ eps_in, uint64_t *__restrict__ rng_ctl,
+                                                               const float *__restrict__ low, const float *__restrict__ high,
+                                                               const int deterministic, float *__restrict__ action,
+                                                               float *__restrict__ env_action, float *__restrict__ log_prob,
+                                                               float *__restrict__ eps_out, const int64_t n)
+{
+    const bool draw = !deterministic && rng_ctl != nullptr;
+    const uint64_t seed = draw ? rng_ctl[0] : 0ull, base = draw ? rng_ctl[1] : 0ull;
+    float sig[A];
+#pragma unroll
+    for (int k = 0; k < A; ++k) sig[k] = expf(log_std[k]);
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float mu[A], e[A], a[A];
+        load_row<A>(mean + i * A, mu);
+        if (deterministic) {
+#pragma unroll
+            for (int k = 0; k < A; ++k) e[k] = 0.0f;
+        } else if (draw) {
+            const uint64_t ctr = base + (uint64_t)i;
+            uint32_t r[4];
+            float z[4];
+            philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, PPO_STREAM_TAG, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+            box_muller(r[0], r[1], z[0], z[1]);
+            if (A > 2) box_muller(r[2], r[3], z[2], z[3]);
+#pragma unroll
+            for (int k = 0; k < A; ++k) e[k] = z[k];
+        } else {
+            load_row<A>(eps_in + i * A, e);
+        }
+#pragma unroll
+        for (int k = 0; k < A; ++k) a[k] = deterministic ? mu[k] : mu[k] + sig[k] * e[k];
+        store_row<A>(action + i * A, a);
+        if (eps_out) store_row<A>(eps_out + i * A, e);
+        if (log_prob) log_prob[i] = diag_log_prob<A>(a, mu, sig);
+        if (env_action) {
+            float c[A];
+#pragma unroll
+            for (int k = 0; k < A; ++k) c[k] = low ? fminf(fmaxf(a[k], low[k]), high[k]) : a[k];  // np.clip
+            store_row<A>(env_action + i * A, c);
+        }
+    }
+    if (draw && last_block_ticket(reinterpret_cast<unsigned long long *>(rng_ctl + 2)) && threadIdx.x == 0)
+        rng_ctl[1] = base + (uint64_t)n;
+}
+
+// buffers.py:440-479 + on_policy_algorithm.py:236-245. ctl = { pos, full, ticket, adds }; a full buffer takes no row.
+template <int D, int A>
+__global__ __launch_bounds__(64) void rollout_add_kernel(const cstr_rollout_t rb, int64_t *__restrict__ ctl, const float *__restrict__ obs,
+                                                         const float *__restrict__ act, const float *__restrict__ reward,
+                                                         float *episode_start, const float *__restrict__ value,
+                                                         const float *__restrict__ log_prob, const float *__restrict__ timeout,
+                                                         const float *__restrict__ terminal_value, const float gamma,
+                                                         const float *__restrict__ done, float *__restrict__ ep_return,
+                                                         int32_t *__restrict__ ep_len, double *__restrict__ ep_stats)
+{
+    const int64_t pos = ctl[0], n = rb.n_envs;
+    const bool room = pos >= 0 && pos < rb.rows;
+    if (room) {
+        for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+            const int64_t r = pos * n + i;
+#pragma unroll
+            for (int c = 0; c < D; c += 4) {
+                float v[4];
+                load_row<4>(obs + i * D + c, v);
+                store_row<4>(rb.obs + r * D + c, v);
+            }
+            float a[A];
+            load_row<A>(act + i * A, a);
+            store_row<A>(rb.act + r * A, a);
+            float rw = reward[i];
+            if (ep_stats) {  // Monitor semantics on the env's own reward: return / length of the episode that ends here
+                const float ret = ep_return[i] + rw;
+                const int32_t len = ep_len[i] + 1;
+                const bool d = done[i] != 0.0f;
+                ep_return[i] = d ? 0.0f : ret;
+                ep_len[i] = d ? 0 : len;
+                if (d) {
+                    atomicAdd(ep_stats + 0, 1.0);
+                    atomicAdd(ep_stats + 1, (double)ret);
+                    atomicAdd(ep_stats + 2, (double)len);
+                }
+            }
+            if (timeout && timeout[i] != 0.0f) rw = rw + gamma * terminal_value[i];
+            rb.rew[r] = rw;
+            rb.episode_start[r] = episode_start[i];
+            if (done) episode_start[i] = done[i];  // _last_episode_starts = dones (on_policy_algorithm.py:256)
+            rb.values[r] = value[i];
+            rb.log_probs[r] = log_prob[i];
+            rb.advantages[r] = 0.0f;
+            rb.returns[r] = 0.0f;
+        }
+    }
+    if (last_block_ticket(reinterpret_cast<unsigned long long *>(ctl + 2)) && threadIdx.x == 0 && room) {
+        ctl[0] = pos + 1;
+        if (pos + 1 == rb.rows) ctl[1] = 1;
+        ctl[3] += 1;
+    }
+}
+
+// buffers.py:403-438 in NumPy's order: delta = r + (g * v_next) * nnt - v;  gae = delta + ((gl * nnt) * gae);  g = f32(gamma),
+// gl = f32(gamma * gae_lambda) (the product is formed in double); returns = advantages + values
+__global__ __launch_bounds__(64) void gae_kernel(const float *__restrict__ rewards, const float *__restrict__ values,
+                                                 const float *__restrict__ episode_starts, const float *__restrict__ last_values,
+                                                 const float *__restrict__ dones, const float g, const float gl,
+                                                 float *__restrict__ advantages, float *__restrict__ returns, const int64_t T,
+                                                 const int64_t N)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x) {
+        float gae = 0.0f, nnt = 1.0f - dones[i], v_next = last_values[i];
+        for (int64_t t = T - 1; t >= 0; --t) {
+            const int64_t r = t * N + i;
+            const float v = values[r];
+            const float delta = (rewards[r] + (g * v_next) * nnt) - v;
+            gae = delta + (gl * nnt) * gae;
+            advantages[r] = gae;
+            returns[r] = gae + v;
+            nnt = 1.0f - episode_starts[r];
+            v_next = v;
+        }
+    }
+}
+
+// buffers.py:481-521: flat index i (swap_and_flatten) = env i / T, step i % T; indices are clamped into the buffer
+template <int D, int A>
+__global__ __launch_bounds__(256) void ppo_gather_kernel(const cstr_rollout_t rb, const int64_t *__restrict__ idx, const int64_t batch,
+                                                         float *__restrict__ obs, float *__restrict__ act, float *__restrict__ old_value,
+                                                         float *__restrict__ old_log_prob, float *__restrict__ adv, float *__restrict__ ret)
+{
+    const int64_t T = rb.rows, N = rb.n_envs, total = T * N;
+    for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < batch; b += (int64_t)gridDim.x * blockDim.x) {
+        int64_t i = idx[b];
+        i = i < 0 ? 0 : (i >= total ? total - 1 : i);
+        const int64_t env = i / T, step = i - env * T, r = step * N + env;
+#pragma unroll
+        for (int c = 0; c < D; c += 4) {
+            float v[4];
+            load_row<4>(rb.obs + r * D + c, v);
+            store_row<4>(obs + b * D + c, v);
+        }
+        float a[A];
+        load_row<A>(rb.act + r * A, a);
+        store_row<A>(act + b * A, a);
+        old_value[b] = rb.values[r];
+        old_log_prob[b] = rb.log_probs[r];
+        adv[b] = rb.advantages[r];
+        ret[b] = rb.returns[r];
+    }
+}
+
+// sum of v over the workgroup's 256 threads in a fixed tree; every thread gets the result
+__device__ __forceinline__ double block_sum_f64(double v, double *red)
+{
+    __syncthreads();
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    return red[0];
+}
+
+__device__ __forceinline__ void publish_f64(unsigned long long *w, double v)
+{
+    __hip_atomic_store(w, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__device__ __forceinline__ double consume_f64(unsigned long long *w)
+{
+    return __longlong_as_double((long long)__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// ppo.py:213-264
+template <int A>
+__global__ __launch_bounds__(256) void ppo_loss_kernel(const cstr_ppo_loss_t p, unsigned long long *__restrict__ ws)
+{
+    __shared__ double red[256];
+    __shared__ double tot[LOSS_PARTS];
+    const int64_t B = p.batch;
+    // advantage statistics over the whole minibatch: every workgroup computes them itself, in the same order
+    const bool norm = p.normalize_advantage && B > 1;
+    float a_mean = 0.0f, a_den = 1.0f;
+    if (norm) {
+        double s = 0.0;
+        for (int64_t i = threadIdx.x; i < B; i += 256) s += (double)p.adv[i];
+        a_mean = (float)(block_sum_f64(s, red) / (double)B);
+        double q = 0.0;
+        for (int64_t i = threadIdx.x; i < B; i += 256) {
+            const float d = p.adv[i] - a_mean;
+            q += (double)(d * d);
+        }
+        a_den = (float)sqrt(block_sum_f64(q, red) / (double)(B - 1)) + 1e-8f;  // unbiased std, ppo.py:219
+    }
+    float sig[A], var[A];
+#pragma unroll
+    for (int k = 0; k < A; ++k) {
+        sig[k] = expf(p.log_std[k]);
+        var[k] = sig[k] * sig[k];
+    }
+    const float lo = (float)(1.0 - p.clip_range), hi = (float)(1.0 + p.clip_range), cr = (float)p.clip_range;
+    const bool vclip = p.clip_range_vf > 0.0;
+    const float cv = (float)p.clip_range_vf;
+    const float inv_b = 1.0f / (float)B;
+    double acc[LOSS_PARTS];
+#pragma unroll
+    for (int k = 0; k < LOSS_PARTS; ++k) acc[k] = 0.0;
+    for (int64_t b = blockIdx.x * 256ll + threadIdx.x; b < B; b += (int64_t)gridDim.x * 256ll) {
+        float mu[A], act[A];
+        load_row<A>(p.mean + b * p.ldm, mu);
+        load_row<A>(p.actions + b * A, act);
+        const float logp = diag_log_prob<A>(act, mu, sig);
+        if (p.log_prob_out) p.log_prob_out[b] = logp;
+        const float lr = logp - p.old_log_prob[b];
+        const float ratio = expf(lr);
+        const float advn = norm ? (p.adv[b] - a_mean) / a_den : p.adv[b];
+        const float pl1 = advn * ratio, pl2 = advn * fminf(fmaxf(ratio, lo), hi);
+        acc[0] += (double)fminf(pl1, pl2);
+        acc[2] += (double)((ratio - 1.0f) - lr);
+        acc[3] += fabsf(ratio - 1.0f) > cr ? 1.0 : 0.0;
+        // d min(pl1, pl2) / d ratio: the clamp passes the gradient on the closed interval (there pl1 == pl2, torch splits the
+        // gradient between the two equal operands and both halves arrive); outside it only pl1 carries one
+        const float dmin = ((ratio >= lo && ratio <= hi) || pl1 < pl2) ? advn : 0.0f;
+        const float g_logp = -(inv_b * dmin) * ratio;
+        float gm[A];
+#pragma unroll
+        for (int k = 0; k < A; ++k) {
+            const float d = act[k] - mu[k];
+            gm[k] = g_logp * (d / var[k]);
+            acc[4 + k] += (double)(g_logp * ((d * d) / var[k] - 1.0f));
+        }
+        store_row<A>(p.g_mean + b * A, gm);
+        const float v = p.values[b], ret = p.returns[b];
+        float vp = v;
+        bool pass = true;
+        if (vclip) {
+            const float vo = p.old_values[b], dv = v - vo;
+            vp = vo + fminf(fmaxf(dv, -cv), cv);
+            pass = dv >= -cv && dv <= cv;
+        }
+        const float dr = ret - vp;
+        acc[1] += (double)(dr * dr);
+        p.g_value[b] = pass ? p.vf_coef * ((2.0f * inv_b) * (vp - ret)) : 0.0f;
+    }
+#pragma unroll
+    for (int k = 0; k < LOSS_PARTS; ++k) {
+        const double s = (k < 4 + A) ? block_sum_f64(acc[k], red) : 0.0;
+        if (threadIdx.x == 0) publish_f64(ws + WS_PART0 + (int64_t)blockIdx.x * LOSS_PARTS + k, s);
+    }
+    __threadfence();  // release: the partials are visible chip-wide before this workgroup's ticket is
+    if (!last_block_ticket(ws)) return;
+    __threadfence();  // acquire: behind the last ticket every workgroup's partials are read from memory
+    if (threadIdx.x < LOSS_PARTS) {
+        double s = 0.0;
+        for (unsigned j = 0; j < gridDim.x; ++j) s += consume_f64(ws + WS_PART0 + (int64_t)j * LOSS_PARTS + threadIdx.x);
+        tot[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float ent = 0.0f;
+#pragma unroll
+        for (int k = 0; k < A; ++k) ent += HALF_LOG_2PI_E + logf(sig[k]);
+        float out[6];
+        out[0] = -(float)(tot[0] / (double)B);          // policy_gradient_loss
+        out[1] = (float)(tot[1] / (double)B);           // value_loss
+        out[2] = -ent;                                  // entropy_loss = -mean(entropy); the entropy does not depend on the row
+        out[3] = (out[0] + p.ent_coef * out[2]) + p.vf_coef * out[1];  // loss
+        out[4] = (float)(tot[2] / (double)B);           // approx_kl
+        out[5] = (float)(tot[3] / (double)B);           // clip_fraction
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            if (p.scalars_out) p.scalars_out[k] = out[k];
+            if (p.scalars_sum) p.scalars_sum[k] += out[k];
+        }
+#pragma unroll
+        for (int k = 0; k < A; ++k) p.g_log_std[k] = (float)tot[4 + k] - p.ent_coef;  // d(ent_coef * entropy_loss) / d log_std = -ent_coef
+    }
+}
+
+// clip_grad_norm_ (torch.nn.utils): launch 1, per-workgroup sums of squares
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float *__restrict__ grad, const int64_t n, double *__restrict__ part)
+{
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256ll) {
+        const float g = grad[i];
+        s += (double)(g * g);
+    }
+    const double t = block_sum_f64(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+// launch 2: coef = min(1, max_norm / (norm + 1e-6)); grad *= coef (torch multiplies also when the coefficient is 1)
+__global__ __launch_bounds__(256) void grad_scale_kernel(float *__restrict__ grad, const int64_t n, const double *__restrict__ part,
+                                                         const int n_part, const float max_norm, float *__restrict__ norm_out)
+{
+    double s = 0.0;
+    for (int j = 0; j < n_part; ++j) s += part[j];
+    const float norm = (float)sqrt(s);
+    const float coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+    for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256ll) grad[i] = grad[i] * coef;
+    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+}
+
+inline bool overlap(const void *a, int64_t a_floats, const void *b, int64_t b_floats)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + 4u * (uintptr_t)b_floats && b0 < a0 + 4u * (uintptr_t)a_floats;
+}
+
+inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+inline bool row_aligned(const void *p, int width) { return width == 4 ? aligned16(p) : aligned8(p); }
+inline bool widths_ok(int obs_dim, int act_dim) { return (obs_dim == 4 || obs_dim == 8) && (act_dim == 2 || act_dim == 4); }
+
+inline unsigned lane_grid(int64_t n, int block, int64_t cap)
+{
+    int64_t g = (n + block - 1) / block;
+    if (g < 1) g = 1;
+    return (unsigned)(g < cap ? g : cap);
+}
+
+inline int rollout_check(const cstr_rollout_t *rb)
+{
+    if (!rb || !rb->obs || !rb->act || !rb->rew || !rb->episode_start || !rb->values || !rb->log_probs || !rb->advantages ||
+        !rb->returns || rb->rows <= 0 || rb->n_envs <= 0 || rb->obs_dim <= 0 || rb->act_dim <= 0)
+        return CSTR_E_BADARG;
+    if (!widths_ok(rb->obs_dim, rb->act_dim)) return CSTR_E_UNSUPPORTED;
+    if (rb->rows > CSTR_PPO_MAX_ROWS / rb->n_envs) return CSTR_E_UNSUPPORTED;
+    if (!aligned16(rb->obs) || !row_aligned(rb->act, rb->act_dim) || !aligned4(rb->rew) || !aligned4(rb->episode_start) ||
+        !aligned4(rb->values) || !aligned4(rb->log_probs) || !aligned4(rb->advantages) || !aligned4(rb->returns))
+        return CSTR_E_BADARG;
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int cstr_diag_gaussian_act_f32(const float *mean, const float *log_std, const float *eps_in, uint64_t *rng_ctl, const float *low,
+                                          const float *high, int deterministic, float *action, float *env_action, float *log_prob,
+                                          float *eps_out, int64_t n, int act_dim, cstr_stream_t stream)
+{
+    if (!mean || !log_std || !action || n <= 0 || act_dim <= 0) return CSTR_E_BADARG;
+    if (!deterministic && (eps_in == nullptr) == (rng_ctl == nullptr)) return CSTR_E_BADARG;  // exactly one noise source
+    if ((low == nullptr) != (high == nullptr)) return CSTR_E_BADARG;
+    if (act_dim != 2 && act_dim != 4) return CSTR_E_UNSUPPORTED;
+    if (n > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
+    if (!row_aligned(mean, act_dim) || !row_aligned(action, act_dim) || (eps_in && !row_aligned(eps_in, act_dim)) ||
+        (env_action && !row_aligned(env_action, act_dim)) || (eps_out && !row_aligned(eps_out, act_dim)) || !aligned4(log_std) ||
+        (log_prob && !aligned4(log_prob)) || (rng_ctl && !aligned8(rng_ctl)))
+        return CSTR_E_BADARG;
+    {
+        const int64_t na = n * act_dim;
+        const void *ins[2] = {mean, deterministic ? nullptr : eps_in};
+        const void *outs[4] = {action, env_action, log_prob, eps_out};
+        const int64_t out_n[4] = {na, na, n, na};
+        for (int o = 0; o < 4; ++o) {
+            if (!outs[o]) continue;
+            for (int i = 0; i < 2; ++i)
+                if (ins[i] && overlap(outs[o], out_n[o], ins[i], na)) return CSTR_E_BADARG;
+            if (overlap(outs[o], out_n[o], log_std, act_dim)) return CSTR_E_BADARG;
+            for (int q = o + 1; q < 4; ++q)
+                if (outs[q] && overlap(outs[o], out_n[o], outs[q], out_n[q])) return CSTR_E_BADARG;
+        }
+    }
+    const unsigned grid = lane_grid(n, 64, 4096);
+    if (act_dim == 2)
+        diag_gaussian_act_kernel<2><<<grid, 64, 0, (hipStream_t)stream>>>(mean, log_std, eps_in, rng_ctl, low, high, deterministic, action,
+                                                                         env_action, log_prob, eps_out, n);
+    else
+        diag_gaussian_act_kernel<4><<<grid, 64, 0, (hipStream_t)stream>>>(mean, log_std, eps_in, rng_ctl, low, high, deterministic, action,
+                                                                         env_action, log_prob, eps_out, n);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_rollout_add_f32(const cstr_rollout_t *rb, int64_t *ctl, const float *obs, const float *act, const float *reward,
+                                    float *episode_start, const float *value, const float *log_prob, const float *timeout,
+                                    const float *terminal_value, float gamma, const float *done, float *ep_return, int32_t *ep_len,
+                                    double *ep_stats, cstr_stream_t stream)
+{
+    const int rc = rollout_check(rb);
+    if (rc) return rc;
+    if (!ctl || !obs || !act || !reward || !episode_start || !value || !log_prob) return CSTR_E_BADARG;
+    if ((timeout == nullptr) != (terminal_value == nullptr)) return CSTR_E_BADARG;
+    if ((ep_stats == nullptr) != (ep_return == nullptr) || (ep_stats == nullptr) != (ep_len == nullptr) || (ep_stats && !done))
+        return CSTR_E_BADARG;  // the episode statistics: all three or none, and they need `done`
+    if ((done && (!aligned4(done) || overlap(done, rb->n_envs, episode_start, rb->n_envs))) ||
+        (ep_stats && (!aligned8(ep_stats) || !aligned4(ep_return) || !aligned4(ep_len))))
+        return CSTR_E_BADARG;
+    if (!aligned8(ctl) || !aligned16(obs) || !row_aligned(act, rb->act_dim) || !aligned4(reward) || !aligned4(episode_start) ||
+        !aligned4(value) || !aligned4(log_prob) || (timeout && (!aligned4(timeout) || !aligned4(terminal_value))))
+        return CSTR_E_BADARG;
+    const int64_t n = rb->n_envs, cells = rb->rows * n;
+    if (overlap(rb->obs, cells * rb->obs_dim, obs, n * rb->obs_dim) || overlap(rb->act, cells * rb->act_dim, act, n * rb->act_dim) ||
+        overlap(rb->rew, cells, reward, n) || overlap(rb->episode_start, cells, episode_start, n) || overlap(rb->values, cells, value, n) ||
+        overlap(rb->log_probs, cells, log_prob, n))
+        return CSTR_E_BADARG;
+    const unsigned grid = lane_grid(n, 64, 4096);
+    const int d = rb->obs_dim, a = rb->act_dim;
+#define ADD_LAUNCH(D, A)                                                                                                              \
+    rollout_add_kernel<D, A><<<grid, 64, 0, (hipStream_t)stream>>>(*rb, ctl, obs, act, reward, episode_start, value, log_prob, timeout, \
+                                                                  terminal_value, gamma, done, ep_return, ep_len, ep_stats)
+    if (d == 4 && a == 2) ADD_LAUNCH(4, 2);
+    else if (d == 4) ADD_LAUNCH(4, 4);
+    else if (a == 2) ADD_LAUNCH(8, 2);
+    else ADD_LAUNCH(8, 4);
+#undef ADD_LAUNCH
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_gae_f32(const float *rewards, const float *values, const float *episode_starts, const float *last_values,
+                            const float *dones, double gamma, double gae_lambda, float *advantages, float *returns, int64_t n_steps,
+                            int64_t n_envs, cstr_stream_t stream)
+{
+    if (!rewards || !values || !episode_starts || !last_values || !dones || !advantages || !returns || n_steps <= 0 || n_envs <= 0)
+        return CSTR_E_BADARG;
+    if (n_steps > CSTR_PPO_MAX_ROWS / n_envs) return CSTR_E_UNSUPPORTED;
+    const void *all[7] = {rewards, values, episode_starts, last_values, dones, advantages, returns};
+    for (int i = 0; i < 7; ++i)
+        if (!aligned4(all[i])) return CSTR_E_BADARG;
+    const int64_t cells = n_steps * n_envs;
+    const void *ins[5] = {rewards, values, episode_starts, last_values, dones};
+    const int64_t in_n[5] = {cells, cells, cells, n_envs, n_envs};
+    for (int i = 0; i < 5; ++i)
+        if (overlap(advantages, cells, ins[i], in_n[i]) || overlap(returns, cells, ins[i], in_n[i])) return CSTR_E_BADARG;
+    if (overlap(advantages, cells, returns, cells)) return CSTR_E_BADARG;
+    // NEP 50: a Python float times a float32 array rounds the float to float32; gamma * gae_lambda is a product of two Python floats
+    gae_kernel<<<lane_grid(n_envs, 64, 4096), 64, 0, (hipStream_t)stream>>>(rewards, values, episode_starts, last_values, dones, (float)gamma,
+                                                                           (float)(gamma * gae_lambda), advantages, returns, n_steps,
+                                                                           n_envs);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx, int64_t batch, float *obs, float *act, float *old_value,
+                                   float *old_log_prob, float *adv, float *ret, cstr_stream_t stream)
+{
+    const int rc = rollout_check(rb);
+    if (rc) return rc;
+    if (!idx || !obs || !act || !old_value || !old_log_prob || !adv || !ret || batch <= 0) return CSTR_E_BADARG;
+    if (batch > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
+    if (!aligned8(idx) || !aligned16(obs) || !row_aligned(act, rb->act_dim) || !aligned4(old_value) || !aligned4(old_log_prob) ||
+        !aligned4(adv) || !aligned4(ret))
+        return CSTR_E_BADARG;
+    const int64_t cells = rb->rows * rb->n_envs;
+    const void *outs[6] = {obs, act, old_value, old_log_prob, adv, ret};
+    const int64_t out_n[6] = {batch * rb->obs_dim, batch * rb->act_dim, batch, batch, batch, batch};
+    const void *ins[6] = {rb->obs, rb->act, rb->values, rb->log_probs, rb->advantages, rb->returns};
+    const int64_t in_n[6] = {cells * rb->obs_dim, cells * rb->act_dim, cells, cells, cells, cells};
+    for (int o = 0; o < 6; ++o) {
+        for (int i = 0; i < 6; ++i)
+            if (overlap(outs[o], out_n[o], ins[i], in_n[i])) return CSTR_E_BADARG;
+        if (overlap(outs[o], out_n[o], idx, 2 * batch)) return CSTR_E_BADARG;
+        for (int q = o + 1; q < 6; ++q)
+            if (overlap(outs[o], out_n[o], outs[q], out_n[q])) return CSTR_E_BADARG;
+    }
+    const unsigned grid = lane_grid(batch, 256, 2048);
+    const int d = rb->obs_dim, a = rb->act_dim;
+#define GATHER_LAUNCH(D, A) \
+    ppo_gather_kernel<D, A><<<grid, 256, 0, (hipStream_t)stream>>>(*rb, idx, batch, obs, act, old_value, old_log_prob, adv, ret)
+    if (d == 4 && a == 2) GATHER_LAUNCH(4, 2);
+    else if (d == 4) GATHER_LAUNCH(4, 4);
+    else if (a == 2) GATHER_LAUNCH(8, 2);
+    else GATHER_LAUNCH(8, 4);
+#undef GATHER_LAUNCH
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_ppo_loss_f32(const cstr_ppo_loss_t *p, uint64_t *workspace, cstr_stream_t stream)
+{
+    if (!p || !workspace || !p->mean || !p->log_std || !p->actions || !p->values || !p->old_log_prob || !p->adv || !p->returns ||
+        !p->g_mean || !p->g_value || !p->g_log_std || p->batch <= 0 || p->act_dim <= 0)
+        return CSTR_E_BADARG;
+    if (!(p->clip_range >= 0.0) || (p->clip_range_vf > 0.0 && !p->old_values)) return CSTR_E_BADARG;
+    if (p->act_dim != 2 && p->act_dim != 4) return CSTR_E_UNSUPPORTED;
+    if (p->batch > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
+    const int A = p->act_dim;
+    if (p->ldm < A || (p->ldm * 4) % (A == 4 ? 16 : 8)) return CSTR_E_BADARG;
+    if (!aligned8(workspace) || !row_aligned(p->mean, A) || !row_aligned(p->actions, A) || !row_aligned(p->g_mean, A) ||
+        !aligned4(p->log_std) || !aligned4(p->values) || !aligned4(p->old_log_prob) || !aligned4(p->adv) || !aligned4(p->returns) ||
+        !aligned4(p->g_value) || !aligned4(p->g_log_std) || (p->old_values && !aligned4(p->old_values)) ||
+        (p->scalars_out && !aligned4(p->scalars_out)) || (p->scalars_sum && !aligned4(p->scalars_sum)) ||
+        (p->log_prob_out && !aligned4(p->log_prob_out)))
+        return CSTR_E_BADARG;
+    {
+        const int64_t B = p->batch;
+        const void *ins[8] = {p->mean, p->log_std, p->actions, p->values, p->old_values, p->old_log_prob, p->adv, p->returns};
+        const int64_t in_n[8] = {(B - 1) * p->ldm + A, A, B * A, B, B, B, B, B};
+        const void *outs[7] = {p->g_mean, p->g_value, p->g_log_std, p->scalars_out, p->scalars_sum, p->log_prob_out, workspace};
+        const int64_t out_n[7] = {B * A, B, A, 6, 6, B, 2 * CSTR_PPO_WS_WORDS};
+        for (int o = 0; o < 7; ++o) {
+            if (!outs[o]) continue;
+            for (int i = 0; i < 8; ++i)
+                if (ins[i] && overlap(outs[o], out_n[o], ins[i], in_n[i])) return CSTR_E_BADARG;
+            for (int q = o + 1; q < 7; ++q)
+                if (outs[q] && overlap(outs[o], out_n[o], outs[q], out_n[q])) return CSTR_E_BADARG;
+        }
+    }
+    const unsigned grid = lane_grid(p->batch, 256, CSTR_PPO_MAX_BLOCKS);
+    unsigned long long *ws = reinterpret_cast<unsigned long long *>(workspace);
+    if (A == 2) ppo_loss_kernel<2><<<grid, 256, 0, (hipStream_t)stream>>>(*p, ws);
+    else ppo_loss_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(*p, ws);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_grad_clip_f32(float *grad, int64_t n, float max_norm, uint64_t *workspace, float *norm_out, cstr_stream_t stream)
+{
+    if (!grad || !workspace || n <= 0 || !(max_norm >= 0.0f)) return CSTR_E_BADARG;
+    if (!aligned4(grad) || !aligned8(workspace) || (norm_out && !aligned4(norm_out))) return CSTR_E_BADARG;
+    if (overlap(grad, n, workspace, 2 * CSTR_PPO_WS_WORDS) || (norm_out && overlap(grad, n, norm_out, 1)) ||
+        (norm_out && overlap(workspace, 2 * CSTR_PPO_WS_WORDS, norm_out, 1)))
+        return CSTR_E_BADARG;
+    const unsigned grid = lane_grid(n, 256, CSTR_PPO_MAX_BLOCKS);
+    double *part = reinterpret_cast<double *>(workspace) + WS_PART0;
+    grad_sumsq_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(grad, n, part);
+    const int rc = (int)hipGetLastError();
+    if (rc) return rc;
+    grad_scale_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(grad, n, part, (int)grid, max_norm, norm_out);
+    return (int)hipGetLastError();
+}

@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,init,vecenv]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,init,vecenv]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -16,6 +16,7 @@ Reference entry points exercised (file:line in /root/reference):
   core/sac/sac.py:199-296                SAC.train
   core/td3/td3.py:154-211                TD3.train
   core/bcq/bcq.py:129-213                BCQ.train; core/bcq/policies.py:426-435 BCQPolicy._predict
+  core/ppo/ppo.py:184-300                PPO.train; core/common/on_policy_algorithm.py:162-268 collect_rollouts
   core/common/utils.py:457-481           polyak_update
 """
 import argparse
@@ -1216,7 +1217,186 @@ def gen_bcq_predict():
     save("bcq_predict_kat.npz", **out)
 
 
-GENS = {"bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+
+# --------------------------------------------------------------------------------------- PPO
+class _PpoHooks:
+    """Records, around the UNMODIFIED reference: every standard-normal draw of Normal.rsample, every np.random.permutation, the infos of
+    every vec-step, and -- read from train()'s frame when it calls clip_grad_norm_ (core/ppo/ppo.py:277) -- each minibatch's values,
+    log-probs, the six scalars and the gradient norm."""
+
+    def __enter__(self):
+        import sys as _sys
+
+        import torch.distributions.normal as tdn
+        from core.common.vec_env.dummy_vec_env import DummyVecEnv
+
+        self.draws, self.perms, self.infos, self.minibatches = [], [], [], []
+        self._tdn, self._std_normal = tdn, tdn._standard_normal
+        self._perm, self._clip, self._step_wait, self._dummy = np.random.permutation, th.nn.utils.clip_grad_norm_, DummyVecEnv.step_wait, DummyVecEnv
+
+        def std_normal(shape, dtype, device):
+            e = self._std_normal(shape, dtype, device)
+            self.draws.append(e.clone())
+            return e
+
+        def permutation(n):
+            pm = self._perm(n)
+            self.perms.append(np.asarray(pm).copy())
+            return pm
+
+        def clip(parameters, max_norm, *a, **kw):
+            norm = self._clip(parameters, max_norm, *a, **kw)
+            f = _sys._getframe(1).f_locals
+            self.minibatches.append(dict(values=f["values"].detach().numpy().copy(), log_prob=f["log_prob"].detach().numpy().copy(),
+                                         scalars=np.array([float(f["policy_loss"]), float(f["value_loss"]), float(f["entropy_loss"]),
+                                                           float(f["loss"]), float(f["approx_kl_div"]), float(f["clip_fraction"])], np.float32),
+                                         grad_norm=np.float32(float(norm)), ratio=f["ratio"].detach().numpy().copy(), epoch=int(f["epoch"]),
+                                         old_values=f["rollout_data"].old_values.numpy().copy()))
+            return norm
+
+        def step_wait(env_self):
+            out = self._step_wait(env_self)
+            self.infos.append([dict(i) for i in out[3]])
+            return out
+
+        tdn._standard_normal, np.random.permutation, th.nn.utils.clip_grad_norm_, DummyVecEnv.step_wait = std_normal, permutation, clip, step_wait
+        return self
+
+    def __exit__(self, *exc):
+        self._tdn._standard_normal, np.random.permutation, th.nn.utils.clip_grad_norm_ = self._std_normal, self._perm, self._clip
+        self._dummy.step_wait = self._step_wait
+
+
+def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, target_kl=None, **kw):
+    """One teacher-forceable PPO iteration of the reference on the CPU: _setup_learn (which resets the envs), THEN the step counters of
+    the envs in `late` are set near the time limit (set before learn() they would be undone by the reset), collect_rollouts, train()."""
+    from core.common.logger import Logger
+    from core.common.utils import obs_as_tensor
+    from core.ppo.ppo import PPO
+
+    import warnings as _w
+
+    pk = {} if net_arch is None else dict(policy_kwargs=dict(net_arch=net_arch))
+    with _w.catch_warnings():
+        _w.simplefilter("ignore")
+        model = PPO("MlpPolicy", _make_venv(n_envs), seed=seed, device="cpu", n_steps=n_steps, batch_size=batch_size, n_epochs=n_epochs,
+                    learning_rate=lr, ent_coef=ent_coef, target_kl=target_kl, **pk, **kw)
+    model.set_logger(Logger(folder=None, output_formats=[]))
+    out = _flat_sd("before/policy", model.policy.state_dict())
+    out["state_dict_keys"] = np.array(list(model.policy.state_dict().keys()))
+    _, cb = model._setup_learn(n_envs * n_steps, None, True, "PPO", False)
+    for i, st in late:
+        model.env.envs[i].unwrapped.current_step = st
+    out["init_obs"] = np.array(model._last_obs, np.float32).copy()
+    out["init_steps"] = np.array([e.unwrapped.current_step for e in model.env.envs], np.int32)
+    with _PpoHooks() as hk:
+        assert model.collect_rollouts(model.env, cb, model.rollout_buffer, n_steps)
+        rb = model.rollout_buffer
+        for f in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
+            out[f"rollout/{f}"] = np.array(getattr(rb, f), np.float32).copy()
+        assert len(hk.draws) == n_steps and len(hk.infos) == n_steps
+        out["eps"] = np.stack([d.numpy() for d in hk.draws])
+        out["timeouts"] = np.array([[bool(i.get("TimeLimit.truncated", False)) and "terminal_observation" in i for i in step] for step in hk.infos],
+                                   np.float32)
+        with th.no_grad():
+            out["last_values"] = model.policy.predict_values(obs_as_tensor(model._last_obs, model.device)).numpy().reshape(-1).copy()
+        out["dones"] = np.array(model._last_episode_starts, np.float32)
+        out["last_obs"] = np.array(model._last_obs, np.float32).copy()
+        model.train()
+    out["permutations"] = np.stack(hk.perms) if hk.perms else np.zeros((0, n_envs * n_steps), np.int64)
+    for k, mb in enumerate(hk.minibatches):
+        for name in ("values", "log_prob", "scalars", "grad_norm"):
+            out[f"mb{k}/{name}"] = mb[name]
+    out["n_minibatches"], out["mb_epochs"] = np.int64(len(hk.minibatches)), np.array([mb["epoch"] for mb in hk.minibatches], np.int64)
+    lv = model.logger.name_to_value
+    out["logged_keys"] = np.array(sorted(lv.keys()))
+    out["logged_values"] = np.array([float(lv[k]) for k in sorted(lv.keys())], np.float64)
+    out.update(_flat_sd("after/policy", model.policy.state_dict()))
+    out["optimizer_steps"] = np.int64(next(iter(model.policy.optimizer.state.values()))["step"]) if model.policy.optimizer.state else np.int64(0)
+    out["n_updates"], out["n_truncations"] = np.int64(model._n_updates), np.int64(out["timeouts"].sum())
+    arch = net_arch if net_arch is not None else [64, 64]
+    out.update(seed=np.int64(seed), n_envs=np.int64(n_envs), n_steps=np.int64(n_steps), batch_size=np.int64(batch_size), n_epochs=np.int64(n_epochs),
+               net_arch=np.array(arch, np.int64), gamma=np.float64(model.gamma), gae_lambda=np.float64(model.gae_lambda),
+               learning_rate=np.float64(lr), ent_coef=np.float64(ent_coef), vf_coef=np.float64(model.vf_coef),
+               max_grad_norm=np.float64(model.max_grad_norm), clip_range=np.float64(model.clip_range(1)))
+    return model, out, hk
+
+
+def _ppo_margins_ok(hk, clip_range, clip_range_vf):
+    """no row within 1e-4 of a clip bound, so clip_fraction (and which side of a clamp a row is on) compares exactly"""
+    for mb in hk.minibatches:
+        if np.min(np.abs(np.abs(mb["ratio"] - 1) - clip_range)) <= 1e-4:
+            return False
+        if clip_range_vf is not None and np.min(np.abs(np.abs(mb["values"] - mb["old_values"]) - clip_range_vf)) <= 1e-4:
+            return False
+    return True
+
+
+def gen_ppo():
+    """PPO.collect_rollouts + train (core/common/on_policy_algorithm.py:162-268, core/ppo/ppo.py:184-300):
+    ppo_train_kat_small.npz (4 envs, n_steps 8, batch 12 -> a last minibatch of 8 rows, 3 epochs, nets [32, 32]; + a target_kl run),
+    ppo_train_kat_vfclip.npz (the same with clip_range_vf = 0.2, advantage normalisation on and off), ppo_train_kat_default.npz (class
+    default nets, 8 envs, n_steps 16, batch 64, 2 epochs) and ppo_predict_kat.npz."""
+    late = ((1, 396), (2, 399), (3, 395))
+    small = dict(n_envs=4, n_steps=8, batch_size=12, n_epochs=3, net_arch=[32, 32], late=late)
+    for seed in range(7, 60):
+        model, out, hk = _ppo_run(seed, **small)
+        clipped = max(float(mb["scalars"][5]) for mb in hk.minibatches)
+        if not (clipped > 0 and int(out["n_truncations"]) >= 2 and _ppo_margins_ok(hk, 0.2, None)):
+            continue
+        # the target_kl run: the same iteration stops at the first minibatch whose approx_kl clearly exceeds every earlier one
+        kl = np.array([float(mb["scalars"][4]) for mb in hk.minibatches])
+        per_epoch = -(-32 // 12)
+        cand = [(kl[k] / kl[:k].max(), k) for k in range(per_epoch, len(kl)) if kl[:k].max() > 0 and kl[k] > 1.3 * kl[:k].max()]
+        if not cand:
+            continue
+        _, k = max(cand)
+        thr = float(np.sqrt(kl[k] * kl[:k].max()))
+        m2, out2, hk2 = _ppo_run(seed, target_kl=thr / 1.5, **small)
+        assert len(hk2.minibatches) == k and int(out2["n_updates"]) == k // per_epoch + 1
+        out.update({"tkl/target_kl": np.float64(thr / 1.5), "tkl/stop_minibatch": np.int64(k), "tkl/n_updates": out2["n_updates"],
+                    "tkl/optimizer_steps": out2["optimizer_steps"], "tkl/approx_kl": np.float64(kl[k])})
+        out.update({f"tkl/{key}": v for key, v in out2.items() if key.startswith("after/")})
+        print(f"ppo small: seed {seed}, max clip_fraction {clipped:.3f}, truncations {int(out['n_truncations'])}, target_kl stop at minibatch {k}")
+        save("ppo_train_kat_small.npz", **out)
+        break
+    else:
+        raise RuntimeError("no seed met the conditions of the small PPO fixture")
+    for seed in range(int(out["seed"]), 60):
+        runs = {}
+        for tag, norm in (("norm", True), ("raw", False)):
+            model, o, hk = _ppo_run(seed, clip_range_vf=0.2, normalize_advantage=norm, **small)
+            engaged = any((np.abs(mb["values"] - mb["old_values"]) > 0.2).any() for mb in hk.minibatches)
+            ok = engaged and int(o["n_truncations"]) >= 2 and _ppo_margins_ok(hk, 0.2, 0.2) and max(float(mb["scalars"][5]) for mb in hk.minibatches) > 0
+            runs[tag] = (o, ok)
+        if all(ok for _, ok in runs.values()):
+            o = dict(runs["norm"][0])
+            o.update({f"raw/{k}": v for k, v in runs["raw"][0].items() if k.startswith(("mb", "after/", "logged_", "n_minibatches", "n_updates",
+                                                                                        "optimizer_steps", "permutations"))})
+            o["clip_range_vf"] = np.float64(0.2)
+            print(f"ppo vfclip: seed {seed}")
+            save("ppo_train_kat_vfclip.npz", **o)
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the vfclip PPO fixture")
+    model, o, hk = _ppo_run(11, n_envs=8, n_steps=16, batch_size=64, n_epochs=2, late=((0, 390), (5, 397), (6, 399)))
+    assert int(o["n_truncations"]) >= 2 and _ppo_margins_ok(hk, 0.2, None)
+    save("ppo_train_kat_default.npz", **o)
+    # predict: the trained small model on seeded observations, deterministic and sampled (the draw is recorded), and predict_values
+    model, _, _ = _ppo_run(int(out["seed"]), **small)
+    obs = np.random.default_rng(99).uniform(-1, 1, (16, 4)).astype(np.float32)
+    p = _flat_sd("policy", model.policy.state_dict())
+    p["obs"], p["net_arch"], p["seed"] = obs, np.array([32, 32], np.int64), out["seed"]
+    p["deterministic"], _ = model.predict(obs, deterministic=True)
+    with _PpoHooks() as hk:
+        p["sampled"], _ = model.predict(obs, deterministic=False)
+        p["eps"] = hk.draws[0].numpy()
+    with th.no_grad():
+        p["values"] = model.policy.predict_values(th.as_tensor(obs)).numpy()
+    save("ppo_predict_kat.npz", **p)
+
+
+GENS = {"ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint}
 
