@@ -833,6 +833,42 @@ int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx, int64_t ba
 int cstr_ppo_loss_f32(const cstr_ppo_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
 int cstr_grad_clip_f32(float *grad, int64_t n, float max_norm, uint64_t *workspace, float *norm_out, cstr_stream_t stream);
 
+/* ---- A2C: the loss launch and the optimiser of core/a2c/a2c.py:132-190 ---------------------------------------------------------------
+ * Same conventions as the PPO block above: f32, act_dim in {2, 4} (CSTR_E_UNSUPPORTED otherwise, as for more than CSTR_PPO_MAX_ROWS
+ * rows), any row count >= 1, host-side validation (NULL, non-positive sizes, misaligned rows, overlapping input / output ->
+ * CSTR_E_BADARG), then only enqueues; deterministic batch reductions; the workspace is a uint64[CSTR_PPO_WS_WORDS] as above.
+ * cstr_a2c_loss_f32 (a2c.py:150-171, one launch): see cstr_a2c_loss_t. policy_loss = -mean(adv * log_prob), value_loss =
+ * mse(returns, values), entropy_loss = -mean(entropy), loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss; g_mean
+ * [batch][act_dim] / g_value [batch] / g_log_std [act_dim] = d loss / d (action mean, value, log_std). normalize_advantage != 0:
+ * (adv - mean) / (unbiased std + 1e-8) over the batch WITHOUT a batch > 1 guard (the reference has none): batch == 1 gives NaN, as
+ * torch.std of one element does.
+ * cstr_rmsprop_f32: torch.optim.RMSprop (momentum 0, not centred, no weight decay) over one flat arena (16-byte-aligned, param /
+ * grad / square_avg disjoint) with clip_grad_norm_ folded in. Per element, every operation rounded to f32:
+ *   g' = g * coef;  sq = sq * (float)alpha + ((float)(1 - alpha) * g') * g';  param = param + ((float)(-lr) * g') / (sqrtf(sq) + (float)eps)
+ * lr is a DEVICE scalar (f64), as for cstr_adam_f32. max_norm > 0: two launches -- the sum-of-squares pass of cstr_grad_clip_f32
+ * (same grid, same partials), then coef = min(1, max_norm / (norm + 1e-6)), the clipped gradient written back to grad and the step;
+ * the result is bit-identical to cstr_grad_clip_f32 followed by the unclipped call. workspace is required, norm_out (optional)
+ * receives the norm before clipping. max_norm <= 0: coef = 1, one launch, grad is not written, workspace and norm_out may be NULL. */
+typedef struct {
+    const float *mean;         /* [batch][ldm], act_dim columns used */
+    int64_t ldm;
+    const float *log_std;      /* [act_dim] */
+    const float *actions;      /* [batch][act_dim] */
+    const float *values;       /* [batch]: the value net's output */
+    const float *adv;          /* [batch] */
+    const float *returns;      /* [batch] */
+    int64_t batch;
+    int32_t act_dim;
+    int32_t normalize_advantage;
+    float ent_coef, vf_coef;
+    float *g_mean, *g_value, *g_log_std;
+    float *scalars_out;        /* [4] = { policy_loss, value_loss, entropy_loss, loss } or NULL */
+    float *log_prob_out;       /* [batch] or NULL: the log-prob of the actions */
+} cstr_a2c_loss_t;
+int cstr_a2c_loss_f32(const cstr_a2c_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
+int cstr_rmsprop_f32(float *param, float *grad, float *square_avg, const double *lr, double alpha, double eps, float max_norm,
+                     uint64_t *workspace, float *norm_out, int64_t n, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ SYMBOLS = (
     "cstr_bcq_latent_fwd_f32", "cstr_bcq_vae_loss_f32", "cstr_bcq_latent_bwd_f32", "cstr_bcq_expand_f32", "cstr_bcq_perturb_fwd_f32",
     "cstr_bcq_perturb_bwd_f32", "cstr_bcq_target_f32", "cstr_bcq_select_f32",
     "cstr_diag_gaussian_act_f32", "cstr_rollout_add_f32", "cstr_gae_f32", "cstr_ppo_gather_f32", "cstr_ppo_loss_f32", "cstr_grad_clip_f32",
+    "cstr_a2c_loss_f32", "cstr_rmsprop_f32",
 )
 
 
@@ -157,6 +158,13 @@ class PpoLoss(C.Structure):
         ("batch", C.c_int64), ("act_dim", C.c_int32), ("normalize_advantage", C.c_int32), ("clip_range", C.c_double),
         ("clip_range_vf", C.c_double), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [(n, C.c_void_p) for n in (
             "g_mean", "g_value", "g_log_std", "scalars_out", "scalars_sum", "log_prob_out")]
+
+
+class A2cLoss(C.Structure):
+    """cstr_a2c_loss_t"""
+    _fields_ = [("mean", C.c_void_p), ("ldm", C.c_int64)] + [(n, C.c_void_p) for n in ("log_std", "actions", "values", "adv", "returns")] + [
+        ("batch", C.c_int64), ("act_dim", C.c_int32), ("normalize_advantage", C.c_int32), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [
+        (n, C.c_void_p) for n in ("g_mean", "g_value", "g_log_std", "scalars_out", "log_prob_out")]
 
 
 class NativeError(RuntimeError):

@@ -1,0 +1,4 @@
+from core.a2c.a2c import A2C
+from core.a2c.policies import MlpPolicy
+
+__all__ = ["A2C", "MlpPolicy"]

@@ -1,7 +1,7 @@
 """Flat parameter arenas: the learner-side HBM layout.
 
 Each optimiser group (actor, critic, ...) owns ONE contiguous fp32 buffer for its parameters, one for its
-gradients and two for the Adam moments; a target network owns a buffer with the identical layout. The
+gradients and two for the Adam moments (one for RMSprop's square average); a target network owns a buffer with the identical layout. The
 nn.Module parameters are views into the arena, `.grad`s are views into the gradient buffer, so:
 
   * `polyak_update` over a whole network is one HIP launch on two flat buffers
@@ -274,12 +274,92 @@ class FlatAdam:
         self.sync_lr()
 
 
+class FlatRMSprop:
+    """torch.optim.RMSprop (alpha 0.99, eps 1e-8; momentum 0, not centred, no weight decay -- what A2C asks for, reference
+    core/a2c/a2c.py:125-127) over one `ParamArena`, learning rate resident in HBM. `step(max_norm=...)` folds clip_grad_norm_ into
+    the step: two launches instead of the three of a clip followed by a step. There is no bias correction, so the step counter is a
+    host integer that only the checkpoints read."""
+
+    def __init__(self, arena: ParamArena, lr: float = 1e-2, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0,
+                 momentum: float = 0, centered: bool = False):
+        if weight_decay != 0 or momentum != 0 or centered:
+            raise ValueError("FlatRMSprop has no weight decay, momentum or centred form")
+        self.arena = arena
+        self.defaults = dict(lr=lr, alpha=alpha, eps=eps, weight_decay=0, momentum=0, centered=False)
+        self.param_groups = [dict(params=arena.params, lr=lr, alpha=alpha, eps=eps, weight_decay=0, momentum=0, centered=False)]
+        self.square_avg = th.zeros_like(arena.flat)
+        self.lr_dev = th.tensor([lr], dtype=th.float64, device=arena.device)
+        self._lr_on_device = float(lr)
+        self._steps = 0
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        self.arena.zero_grad()
+
+    def sync_lr(self) -> None:
+        """Push `param_groups[0]["lr"]` (set by update_learning_rate) to HBM; a constant schedule never copies."""
+        lr = float(self.param_groups[0]["lr"])
+        if lr != self._lr_on_device:
+            self.lr_dev.fill_(lr)
+            self._lr_on_device = lr
+
+    def step(self, closure=None, max_norm: Optional[float] = None, workspace: Optional[th.Tensor] = None,
+             norm_out: Optional[th.Tensor] = None) -> None:
+        """max_norm > 0: th.nn.utils.clip_grad_norm_(parameters, max_norm) first, in the same two launches (needs `workspace`,
+        hip_ops.new_ppo_workspace; `norm_out` [1] receives the norm before clipping, the clipped gradient is written back)."""
+        g = self.param_groups[0]
+        with th.cuda.device(self.arena.device):
+            hip_ops.rmsprop(self.arena.flat, self.arena.grad, self.square_avg, self.lr_dev, g["alpha"], g["eps"], max_norm, workspace, norm_out)
+        self._steps += 1
+
+    @property
+    def step_count(self) -> int:
+        return self._steps
+
+    def state_dict(self) -> dict:
+        """torch.optim.RMSprop's state_dict layout (per-parameter `step` / `square_avg`), so checkpoints are interchangeable with the
+        reference's `policy.optimizer.pth`."""
+        state = {}
+        for i, p in enumerate(self.arena.input_params):  # torch.optim indexes parameters in the order they were given
+            o = self.arena.offset_of[id(p)]
+            state[i] = {"step": th.tensor(float(self._steps)), "square_avg": self.square_avg[o:o + p.numel()].view(p.shape).clone()}
+        g = self.param_groups[0]
+        group = {"lr": float(g["lr"]), "momentum": 0, "alpha": g["alpha"], "eps": g["eps"], "centered": False, "weight_decay": 0,
+                 "capturable": False, "foreach": None, "maximize": False, "differentiable": False,
+                 "params": list(range(len(self.arena.input_params)))}
+        return {"state": state if self._steps > 0 else {}, "param_groups": [group]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        state = sd.get("state", {})
+        self.square_avg.zero_()
+        steps = set()
+        for i, p in enumerate(self.arena.input_params):
+            st = state.get(i, state.get(str(i)))
+            if st is None:
+                continue
+            if "momentum_buffer" in st or "grad_avg" in st:
+                raise ValueError("FlatRMSprop cannot load a checkpoint of RMSprop with momentum or centred=True")
+            o = self.arena.offset_of[id(p)]
+            self.square_avg[o:o + p.numel()].view(p.shape).copy_(st["square_avg"])
+            steps.add(int(float(st["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"FlatRMSprop needs one common step count, checkpoint has {sorted(steps)}")
+        self._steps = steps.pop() if steps else 0
+        groups = sd.get("param_groups") or [{}]
+        if "lr" in groups[0]:
+            self.param_groups[0]["lr"] = float(groups[0]["lr"])
+        self.sync_lr()
+
+
 def make_optimizer(module_params: Iterable[nn.Parameter], device, lr: float, optimizer_class=None,
-                   optimizer_kwargs: Optional[dict] = None, groups: Optional[list] = None, extra_grad: int = 0):
-    """Default (optimizer_class None or torch.optim.Adam with default kwargs) -> arena + FlatAdam. Any other
+                   optimizer_kwargs: Optional[dict] = None, groups: Optional[list] = None, extra_grad: int = 0, flat_rmsprop: bool = False):
+    """Default (optimizer_class None or torch.optim.Adam with default kwargs) -> arena + FlatAdam. flat_rmsprop (only A2C asks):
+    torch.optim.RMSprop with kwargs within {alpha, eps, weight_decay=0, momentum=0, centered=False} -> arena + FlatRMSprop. Any other
     optimiser class is honoured with the stock torch implementation on the arena's parameter views."""
     optimizer_kwargs = dict(optimizer_kwargs or {})
     arena = ParamArena(module_params, device, groups=groups, extra_grad=extra_grad)
     if optimizer_class in (None, th.optim.Adam) and set(optimizer_kwargs) <= {"betas", "eps"}:
         return arena, FlatAdam(arena, lr=lr, **optimizer_kwargs)
+    if flat_rmsprop and optimizer_class is th.optim.RMSprop and set(optimizer_kwargs) <= {"alpha", "eps", "weight_decay", "momentum", "centered"} \
+            and not optimizer_kwargs.get("weight_decay") and not optimizer_kwargs.get("momentum") and not optimizer_kwargs.get("centered"):
+        return arena, FlatRMSprop(arena, lr=lr, **optimizer_kwargs)
     return arena, optimizer_class(arena.params, lr=lr, **optimizer_kwargs)

@@ -313,6 +313,7 @@ class RolloutBuffer(BaseBuffer):
             setattr(self, name, getattr(self.rb, name))
         self.permutation_rng = permutation_rng
         self.forced_permutations: list = []  # teacher-forcing hook: each get() pops its permutation from here first (tests)
+        self.last_indices: Optional[np.ndarray] = None  # the permutation the last get() used
         self._mb: dict = {}
 
     @property
@@ -407,6 +408,7 @@ class RolloutBuffer(BaseBuffer):
                 raise ValueError(f"a forced permutation must hold {total} indices in [0, {total})")
         else:
             indices = (np.random if self.permutation_rng is None else self.permutation_rng).permutation(total).astype(np.int64)
+        self.last_indices = indices
         idx = th.from_numpy(np.ascontiguousarray(indices)).to(self.device)
         if batch_size is None:
             batch_size = total

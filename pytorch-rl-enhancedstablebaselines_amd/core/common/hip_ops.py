@@ -1472,3 +1472,46 @@ def grad_clip(grad, max_norm: float, workspace, norm_out=None):
         _vec(norm_out, "norm_out", 1)
     check(nv.lib().cstr_grad_clip_f32(ptr(grad), C.c_int64(n), C.c_float(max_norm), ptr(workspace), ptr(norm_out), stream_ptr()),
           "cstr_grad_clip_f32")
+
+
+# ---- A2C: the loss launch and the flat RMSprop step with the gradient clip folded in (csrc/cstr_a2c.hip) ----------------------------
+A2C_SCALARS = ("policy_loss", "value_loss", "entropy_loss", "loss")
+
+
+def a2c_loss(mean, log_std, actions, values, adv, returns, normalize_advantage: bool, ent_coef: float, vf_coef: float, g_mean, g_value,
+             g_log_std, workspace, scalars_out=None, log_prob_out=None):
+    """a2c.py:150-171 in one launch: the four scalars (A2C_SCALARS order) and d loss / d (mean, value, log_std). With
+    normalize_advantage a single row gives NaN, as torch.std of one element does (the reference has no guard)."""
+    b, a = actions.shape
+    ldm = _rows(mean, "mean", b, a)
+    _chk(log_std, "log_std", (a,), th.float32), _chk(actions, "actions", (b, a), th.float32)
+    for t, nm in ((values, "values"), (adv, "adv"), (returns, "returns"), (g_value, "g_value")):
+        _vec(t, nm, b)
+    _chk(g_mean, "g_mean", (b, a), th.float32), _vec(g_log_std, "g_log_std", a)
+    _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+    if scalars_out is not None:
+        _vec(scalars_out, "scalars_out", 4)
+    if log_prob_out is not None:
+        _vec(log_prob_out, "log_prob_out", b)
+    p = nv.A2cLoss(mean.data_ptr(), ldm, log_std.data_ptr(), actions.data_ptr(), values.data_ptr(), adv.data_ptr(), returns.data_ptr(), b, a,
+                   int(bool(normalize_advantage)), float(ent_coef), float(vf_coef), g_mean.data_ptr(), g_value.data_ptr(), g_log_std.data_ptr(),
+                   None if scalars_out is None else scalars_out.data_ptr(), None if log_prob_out is None else log_prob_out.data_ptr())
+    check(nv.lib().cstr_a2c_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_a2c_loss_f32")
+
+
+def rmsprop(param, grad, square_avg, lr_dev, alpha: float = 0.99, eps: float = 1e-8, max_norm: Optional[float] = None, workspace=None,
+            norm_out=None):
+    """torch.optim.RMSprop (momentum 0, not centred, no weight decay) over one flat arena. max_norm > 0: clip_grad_norm_ folded in
+    (two launches, the clipped gradient is written back); None or <= 0: one launch, the gradient is only read."""
+    n = param.numel()
+    for t, nm in ((param, "param"), (grad, "grad"), (square_avg, "square_avg")):
+        _chk(t, nm, (n,), th.float32)
+    _chk(lr_dev, "lr", (1,), th.float64)
+    clip = max_norm is not None and max_norm > 0
+    if clip:
+        _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+        if norm_out is not None:
+            _vec(norm_out, "norm_out", 1)
+    check(nv.lib().cstr_rmsprop_f32(ptr(param), ptr(grad), ptr(square_avg), ptr(lr_dev), C.c_double(alpha), C.c_double(eps),
+                                    C.c_float(max_norm if clip else 0.0), ptr(workspace if clip else None), ptr(norm_out if clip else None),
+                                    C.c_int64(n), stream_ptr()), "cstr_rmsprop_f32")

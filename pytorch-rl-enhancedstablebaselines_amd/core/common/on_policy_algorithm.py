@@ -26,6 +26,8 @@ from core.common.vec_env import VecEnv
 
 
 class OnPolicyAlgorithm(BaseAlgorithm):
+    flat_rmsprop = False  # True (A2C): torch.optim.RMSprop in the policy's kwargs becomes the flat kernel form (arena.FlatRMSprop)
+
     def __init__(self, policy, env, learning_rate, n_steps: int, gamma: float, gae_lambda: float, ent_coef: float, vf_coef: float,
                  max_grad_norm: float, use_sde: bool, sde_sample_freq: int, rollout_buffer_class=None,
                  rollout_buffer_kwargs: Optional[dict] = None, stats_window_size: int = 100, tensorboard_log: Optional[str] = None,
@@ -74,7 +76,7 @@ class OnPolicyAlgorithm(BaseAlgorithm):
         # built on the CPU generator in the reference's construction order, then moved into ONE flat arena by the policy itself
         self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule, use_sde=self.use_sde,
                                         **self.policy_kwargs)
-        self.policy.to_device_arenas(self.device)
+        self.policy.to_device_arenas(self.device, flat_rmsprop=self.flat_rmsprop)
         n, dev = self.n_envs, self.device
         self._fast = None
         if self.policy.flat_optimizers() and fused.FastActorCritic.supported(self.policy):
@@ -89,7 +91,7 @@ class OnPolicyAlgorithm(BaseAlgorithm):
 
     @property
     def fused_learner(self) -> bool:
-        """True: the kernel path (per-layer Linear kernels, or rocBLAS GEMMs with CSTR_FUSED_LINEAR=0, and csrc/cstr_ppo.hip);
+        """True: the kernel path (per-layer Linear kernels, or rocBLAS GEMMs with CSTR_FUSED_LINEAR=0, and csrc/cstr_ppo.hip / cstr_a2c.hip);
         False: the reference's own torch statements on the arena parameters (another optimiser class, widths the kernels decline)."""
         return self._fused_learner
 

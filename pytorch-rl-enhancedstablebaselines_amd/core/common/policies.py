@@ -186,15 +186,17 @@ class ActorCriticPolicy(BasePolicy):
             if module.bias is not None:
                 module.bias.data.fill_(0.0)
 
-    def to_device_arenas(self, device) -> None:
+    def to_device_arenas(self, device, flat_rmsprop: bool = False) -> None:
+        """flat_rmsprop: torch.optim.RMSprop in A2C's form becomes a FlatRMSprop (arena.make_optimizer); only A2C passes True"""
         from core.common.arena import make_optimizer
 
-        self.arena, self.optimizer = make_optimizer(self.parameters(), device, self._lr_schedule(1), self.optimizer_class, self.optimizer_kwargs)
+        self.arena, self.optimizer = make_optimizer(self.parameters(), device, self._lr_schedule(1), self.optimizer_class, self.optimizer_kwargs,
+                                                    flat_rmsprop=flat_rmsprop)
 
     def flat_optimizers(self) -> list:
-        from core.common.arena import FlatAdam
+        from core.common.arena import FlatAdam, FlatRMSprop
 
-        return [self.optimizer] if isinstance(self.optimizer, FlatAdam) else []
+        return [self.optimizer] if isinstance(self.optimizer, (FlatAdam, FlatRMSprop)) else []
 
     # ---- the reference's statements on the arena parameters ----------------------------------------------------------
     def _get_action_dist_from_latent(self, latent_pi: th.Tensor):

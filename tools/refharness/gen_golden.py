@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,init,vecenv]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,init,vecenv]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -17,6 +17,7 @@ Reference entry points exercised (file:line in /root/reference):
   core/td3/td3.py:154-211                TD3.train
   core/bcq/bcq.py:129-213                BCQ.train; core/bcq/policies.py:426-435 BCQPolicy._predict
   core/ppo/ppo.py:184-300                PPO.train; core/common/on_policy_algorithm.py:162-268 collect_rollouts
+  core/a2c/a2c.py:132-190                A2C.train
   core/common/utils.py:457-481           polyak_update
 """
 import argparse
@@ -1246,12 +1247,7 @@ class _PpoHooks:
 
         def clip(parameters, max_norm, *a, **kw):
             norm = self._clip(parameters, max_norm, *a, **kw)
-            f = _sys._getframe(1).f_locals
-            self.minibatches.append(dict(values=f["values"].detach().numpy().copy(), log_prob=f["log_prob"].detach().numpy().copy(),
-                                         scalars=np.array([float(f["policy_loss"]), float(f["value_loss"]), float(f["entropy_loss"]),
-                                                           float(f["loss"]), float(f["approx_kl_div"]), float(f["clip_fraction"])], np.float32),
-                                         grad_norm=np.float32(float(norm)), ratio=f["ratio"].detach().numpy().copy(), epoch=int(f["epoch"]),
-                                         old_values=f["rollout_data"].old_values.numpy().copy()))
+            self.minibatches.append(self.capture(_sys._getframe(1).f_locals, norm))
             return norm
 
         def step_wait(env_self):
@@ -1261,6 +1257,14 @@ class _PpoHooks:
 
         tdn._standard_normal, np.random.permutation, th.nn.utils.clip_grad_norm_, DummyVecEnv.step_wait = std_normal, permutation, clip, step_wait
         return self
+
+    @staticmethod
+    def capture(f, norm):
+        return dict(values=f["values"].detach().numpy().copy(), log_prob=f["log_prob"].detach().numpy().copy(),
+                    scalars=np.array([float(f["policy_loss"]), float(f["value_loss"]), float(f["entropy_loss"]),
+                                      float(f["loss"]), float(f["approx_kl_div"]), float(f["clip_fraction"])], np.float32),
+                    grad_norm=np.float32(float(norm)), ratio=f["ratio"].detach().numpy().copy(), epoch=int(f["epoch"]),
+                    old_values=f["rollout_data"].old_values.numpy().copy())
 
     def __exit__(self, *exc):
         self._tdn._standard_normal, np.random.permutation, th.nn.utils.clip_grad_norm_ = self._std_normal, self._perm, self._clip
@@ -1396,7 +1400,131 @@ def gen_ppo():
     save("ppo_predict_kat.npz", **p)
 
 
-GENS = {"ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+# --------------------------------------------------------------------------------------- A2C
+class _A2cHooks(_PpoHooks):
+    """The same recorders around the UNMODIFIED reference's A2C.train (core/a2c/a2c.py:178 calls clip_grad_norm_): per-row values and
+    log-probs in the order of get(None), the four scalars and the gradient norm."""
+
+    @staticmethod
+    def capture(f, norm):
+        return dict(values=f["values"].detach().numpy().copy(), log_prob=f["log_prob"].detach().numpy().copy(),
+                    scalars=np.array([float(f["policy_loss"]), float(f["value_loss"]), float(f["entropy_loss"]), float(f["loss"])], np.float32),
+                    grad_norm=np.float32(float(norm)))
+
+
+def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, iterations=2, opt_state=True, **kw):
+    """`iterations` consecutive teacher-forceable A2C iterations of the reference on the CPU (rollout, train, rollout, train: the
+    second step meets a non-zero square_avg): _setup_learn, THEN the step counters of the envs in `late` are set near the time limit."""
+    from core.a2c.a2c import A2C
+    from core.common.logger import Logger
+    from core.common.utils import obs_as_tensor
+
+    pk = {} if net_arch is None else dict(policy_kwargs=dict(net_arch=net_arch))
+    model = A2C("MlpPolicy", _make_venv(n_envs), seed=seed, device="cpu", n_steps=n_steps, learning_rate=lr, ent_coef=ent_coef, **pk, **kw)
+    model.set_logger(Logger(folder=None, output_formats=[]))
+    out = _flat_sd("before/policy", model.policy.state_dict())
+    out["state_dict_keys"] = np.array(list(model.policy.state_dict().keys()))
+    _, cb = model._setup_learn(iterations * n_envs * n_steps, None, True, "A2C", False)
+    for i, st in late:
+        model.env.envs[i].unwrapped.current_step = st
+    out["init_obs"] = np.array(model._last_obs, np.float32).copy()
+    out["init_steps"] = np.array([e.unwrapped.current_step for e in model.env.envs], np.int32)
+    names = [n for n, _ in model.policy.named_parameters()]
+    n_trunc = 0
+    for it in range(iterations):
+        pre = f"it{it}/"
+        with _A2cHooks() as hk:
+            assert model.collect_rollouts(model.env, cb, model.rollout_buffer, n_steps)
+            rb = model.rollout_buffer
+            for f in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
+                out[f"{pre}rollout/{f}"] = np.array(getattr(rb, f), np.float32).copy()
+            assert len(hk.draws) == n_steps and len(hk.infos) == n_steps
+            out[pre + "eps"] = np.stack([d.numpy() for d in hk.draws])
+            out[pre + "timeouts"] = np.array([[bool(i.get("TimeLimit.truncated", False)) and "terminal_observation" in i for i in step]
+                                              for step in hk.infos], np.float32)
+            n_trunc += int(out[pre + "timeouts"].sum())
+            with th.no_grad():
+                out[pre + "last_values"] = model.policy.predict_values(obs_as_tensor(model._last_obs, model.device)).numpy().reshape(-1).copy()
+            out[pre + "dones"] = np.array(model._last_episode_starts, np.float32)
+            out[pre + "last_obs"] = np.array(model._last_obs, np.float32).copy()
+            model._update_current_progress_remaining(model.num_timesteps, iterations * n_envs * n_steps)
+            model.train()
+        assert len(hk.perms) == 1 and len(hk.minibatches) == 1
+        out[pre + "permutation"] = np.asarray(hk.perms[0], np.int64)
+        for name in ("values", "log_prob", "scalars", "grad_norm"):
+            out[pre + name] = hk.minibatches[0][name]
+        lv = model.logger.name_to_value
+        out[pre + "logged_keys"] = np.array(sorted(lv.keys()))
+        out[pre + "logged_values"] = np.array([float(lv[k]) for k in sorted(lv.keys())], np.float64)
+        out.update(_flat_sd(pre + "after/policy", model.policy.state_dict()))
+        st = model.policy.optimizer.state
+        out[pre + "optimizer_steps"] = np.int64(next(iter(st.values()))["step"]) if st else np.int64(0)
+        out[pre + "n_updates"] = np.int64(model._n_updates)
+        if opt_state and isinstance(model.policy.optimizer, th.optim.RMSprop):
+            for name, p_ in zip(names, model.policy.optimizer.param_groups[0]["params"]):
+                out[f"{pre}opt/square_avg/{name}"] = st[p_]["square_avg"].numpy().copy()
+    arch = net_arch if net_arch is not None else [64, 64]
+    out.update(seed=np.int64(seed), n_envs=np.int64(n_envs), n_steps=np.int64(n_steps), iterations=np.int64(iterations),
+               net_arch=np.array(arch, np.int64), gamma=np.float64(model.gamma), gae_lambda=np.float64(model.gae_lambda),
+               learning_rate=np.float64(lr), ent_coef=np.float64(ent_coef), vf_coef=np.float64(model.vf_coef),
+               max_grad_norm=np.float64(model.max_grad_norm), n_truncations=np.int64(n_trunc),
+               optimizer=np.array(type(model.policy.optimizer).__name__), rms_prop_eps=np.float64(1e-5))
+    return model, out
+
+
+def gen_a2c():
+    """A2C.collect_rollouts + train (core/a2c/a2c.py:132-190), two consecutive iterations each: a2c_train_kat_small.npz (4 envs,
+    n_steps 5, nets [32, 32], ent_coef 0.01, lr 3e-3; the clip engaged in both steps), a2c_train_kat_variants.npz (normalize_advantage,
+    a max_grad_norm that never engages, use_rms_prop=False, as prefixes norm/ noclip/ adam/ over the same initial weights) and
+    a2c_train_kat_default.npz (class defaults, 8 envs, the big tensors after each step as digests)."""
+    late = ((1, 396), (2, 399), (3, 392))
+    small = dict(n_envs=4, net_arch=[32, 32], late=late)
+    for seed in range(7, 60):
+        model, out = _a2c_run(seed, **small)
+        norms = [float(out[f"it{k}/grad_norm"]) for k in range(2)]
+        trunc = [int(out[f"it{k}/timeouts"].sum()) for k in range(2)]
+        if min(norms) > 1.05 * 0.5 and min(trunc) >= 1:
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the small A2C fixture")
+    assert all(n > 0.5 for n in norms) and int(out["n_truncations"]) >= 2  # the clip is engaged in both steps
+    assert float(np.abs(out["it0/opt/square_avg/log_std"]).max()) > 0 and str(out["optimizer"]) == "RMSprop"
+    print(f"a2c small: seed {seed}, gradient norms {norms}, truncations {trunc}")
+    save("a2c_train_kat_small.npz", **out)
+    # the variants: smaller nets, their own initial weights; what does not depend on the variant (initial weights, env states, the
+    # first rollout) is stored once, the recorded draws / last observations / logger values only in the small fixture
+    variants, tiny = {}, dict(n_envs=4, net_arch=[16, 16], late=late)
+    shared = ("before/", "it0/rollout/", "state_dict_keys", "init_obs", "init_steps", "seed", "n_envs", "n_steps", "iterations", "net_arch",
+              "gamma", "gae_lambda", "learning_rate", "ent_coef", "vf_coef", "rms_prop_eps")
+    dropped = ("eps", "timeouts", "last_values", "dones", "last_obs", "logged_keys", "logged_values")
+    for tag, kw in (("norm", dict(normalize_advantage=True)), ("noclip", dict(max_grad_norm=1e6)), ("adam", dict(use_rms_prop=False))):
+        _, o = _a2c_run(seed, opt_state=False, **tiny, **kw)
+        assert int(o["n_truncations"]) >= 2
+        for key in list(o):
+            if key.split("/")[-1] in dropped:
+                del o[key]
+            elif key.startswith(shared):
+                if key in variants:
+                    np.testing.assert_array_equal(o[key], variants[key])
+                variants[key] = o.pop(key)
+        variants.update({f"{tag}/{k}": v for k, v in o.items()})
+    assert max(float(variants[f"noclip/it{k}/grad_norm"]) for k in range(2)) < 1e6 and str(variants["adam/optimizer"]) == "Adam"
+    assert min(float(variants[f"noclip/it{k}/grad_norm"]) for k in range(2)) > 0.5  # max_grad_norm = 0.5 would have engaged
+    assert int(variants["adam/it1/optimizer_steps"]) == 2 and float(variants["norm/max_grad_norm"]) == 0.5
+    save("a2c_train_kat_variants.npz", **variants)
+    _, o = _a2c_run(11, n_envs=8, lr=7e-4, ent_coef=0.0, late=((0, 397), (5, 393), (6, 399)), opt_state=False)
+    assert int(o["n_truncations"]) >= 2
+    slim = {}
+    for k, v in o.items():  # slim_weights on the per-iteration keys: big tensors as digests under the key check_weights looks up
+        if "after/" in k and v.size > 4000:
+            slim.update({k + "#sum": np.float64(v.astype(np.float64).sum()), k + "#abs": np.float64(np.abs(v.astype(np.float64)).sum()),
+                         k + "#head": v.reshape(-1)[:64].copy(), k + "#shape": np.array(v.shape, np.int64)})
+        elif k.split("/")[-1] not in ("eps", "last_obs", "logged_keys", "logged_values"):
+            slim[k] = v
+    save("a2c_train_kat_default.npz", **slim)
+
+
+GENS = {"a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint}
 
