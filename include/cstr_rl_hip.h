@@ -869,6 +869,33 @@ int cstr_a2c_loss_f32(const cstr_a2c_loss_t *p, uint64_t *workspace, cstr_stream
 int cstr_rmsprop_f32(float *param, float *grad, float *square_avg, const double *lr, double alpha, double eps, float max_norm,
                      uint64_t *workspace, float *norm_out, int64_t n, cstr_stream_t stream);
 
+/* ---- DQN on the discrete valve face: exploration draw, action selection, target + gather + Huber loss (core/dqn/dqn.py:168-256) -----
+ * Same conventions as the PPO block: f32 data, host-side validation (NULL, non-positive sizes, misaligned or overlapping rows ->
+ * CSTR_E_BADARG), then only enqueues; a deterministic batch reduction; the workspace is a uint64[CSTR_PPO_WS_WORDS] as above.
+ * The face: n_actions = levels * levels indices over two valves with `levels` settings each, 2 <= levels <= CSTR_DQN_MAX_LEVELS
+ * (anything else, or more than CSTR_PPO_MAX_ROWS rows: CSTR_E_UNSUPPORTED). Index a = i * levels + j stands for the normalised valve
+ * pair (v(i), v(j)), v(q) = (float)-1 + (float)(2 q) / (float)(levels - 1); a stored valve value gives its level back as
+ * rint((v + 1) * (levels - 1) / 2), clamped into the face.
+ * cstr_mt19937_rand_flag_f64: one RandomState.random_sample() from the legacy stream image mt_state [CSTR_MT_STATE_WORDS] (two words,
+ * ((a >> 5) * 2^26 + (b >> 6)) / 2^53; the stream advances, twist included): flag_out[0] = draw < threshold[0] in f64, threshold a
+ * DEVICE double; draw_out (optional) keeps the draw. `np.random.rand() < self.exploration_rate` of dqn.py:245.
+ * cstr_dqn_act_f32: q [n][ldq], n_actions columns used. Greedy index = first maximum of the row (torch.argmax; a NaN counts as the
+ * greatest value). mode 0: greedy. mode 1 (the reference): every row takes a uniform random index iff flag[0] != 0 (device int32),
+ * else greedy. mode 2: row r explores iff u[r][0] < eps[0] (device double, compared in f64). The random index is
+ * min(floor(u[r][1] * n_actions), n_actions - 1). Uniforms in modes 1 and 2: exactly one of u_in [n][2] (read) or rng_ctl
+ * [CSTR_RNG_CTL_WORDS] (drawn: Philox4x32-10 on DQN's own stream, (word >> 8) * 2^-24; the last workgroup advances the offset by n in
+ * every such launch). valve_out [n][2] = (v(a / levels), v(a % levels)); index_out int64[n] (optional) = a.
+ * cstr_dqn_loss_f32 (dqn.py:195-212, one launch): target = reward + ((1 - done) * gamma) * max_a next_q[b][a] (a NaN propagates),
+ * cur = q[b][index(valve[b])], loss_out[0] = mean(smooth_l1(cur - target)) with beta 1, loss_sum[0] (optional) += it; g_q [batch][ldq]
+ * = d loss / d q: zero except g_q[b][index] = clamp(cur - target, -1, 1) / batch. cur_q_out / target_out [batch] (optional). */
+#define CSTR_DQN_MAX_LEVELS 16
+int cstr_mt19937_rand_flag_f64(uint32_t *mt_state, const double *threshold, int32_t *flag_out, double *draw_out, cstr_stream_t stream);
+int cstr_dqn_act_f32(const float *q, int64_t ldq, int64_t n, int n_actions, int levels, int mode, const double *eps, const int32_t *flag,
+                     const float *u_in, uint64_t *rng_ctl, float *valve_out, int64_t *index_out, cstr_stream_t stream);
+int cstr_dqn_loss_f32(const float *q, int64_t ldq, const float *next_q, int64_t ldn, const float *valve, const float *reward,
+                      const float *done, float gamma, int64_t batch, int n_actions, int levels, float *g_q, float *loss_out,
+                      float *loss_sum, float *cur_q_out, float *target_out, uint64_t *workspace, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

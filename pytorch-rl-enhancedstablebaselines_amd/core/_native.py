@@ -20,6 +20,7 @@ MAX_ENS_CRITICS = 16
 SDE_MAX_LATENT, SDE_MAX_MATS = 4096, 65537
 BCQ_MAX_LATENT, BCQ_MAX_ACT, BCQ_MAX_SAMPLES, BCQ_MAX_ROWS = 256, 64, 4096, 1 << 24
 ROLLOUT_CTL_WORDS, PPO_WS_WORDS, PPO_MAX_BLOCKS, PPO_MAX_ROWS = 4, 1024, 64, 1 << 30
+DQN_MAX_LEVELS = 16
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -35,6 +36,7 @@ SYMBOLS = (
     "cstr_bcq_perturb_bwd_f32", "cstr_bcq_target_f32", "cstr_bcq_select_f32",
     "cstr_diag_gaussian_act_f32", "cstr_rollout_add_f32", "cstr_gae_f32", "cstr_ppo_gather_f32", "cstr_ppo_loss_f32", "cstr_grad_clip_f32",
     "cstr_a2c_loss_f32", "cstr_rmsprop_f32",
+    "cstr_mt19937_rand_flag_f64", "cstr_dqn_act_f32", "cstr_dqn_loss_f32",
 )
 
 

@@ -11,7 +11,7 @@ import torch as th
 from core.common import distributed as dist_util
 from core.common.callbacks import BaseCallback, MaybeCallback, to_callback
 from core.common.logger import Logger, configure_logger
-from core.common.spaces import Box, as_box
+from core.common.spaces import Box, Discrete, as_box, as_discrete
 from core.common.utils import get_device, get_schedule_fn, set_random_seed, update_learning_rate
 from core.common.vec_env import CSTRVecEnv, VecEnv, unwrap_vec_normalize
 
@@ -57,19 +57,28 @@ class BaseAlgorithm:
         if env is not None:
             env = self._wrap_env(env, self.verbose)
             self.observation_space = as_box(env.observation_space)
-            self.action_space = as_box(env.action_space)
+            self.action_space = self._as_action_space(env.action_space)
             self.n_envs = env.num_envs
             self.env = env
             self._vec_normalize_env = unwrap_vec_normalize(env)  # reference base_class.py:195
-            if supported_action_spaces is not None and not isinstance(self.action_space, Box):
-                raise AssertionError(f"The algorithm only supports {supported_action_spaces} as action spaces")
+            # reference base_class.py:202-208: a class that names Discrete (DQN) takes a Discrete space and nothing else; every other
+            # class takes a Box
+            wants_discrete = supported_action_spaces is not None and Discrete in supported_action_spaces
+            if isinstance(self.action_space, Discrete) != wants_discrete:
+                raise AssertionError(f"The algorithm only supports {supported_action_spaces} as action spaces "
+                                     f"but {self.action_space} was provided")
             if not support_multi_env and self.n_envs > 1:
                 raise ValueError("Error: the model does not support multiple envs; it requires a single vectorized environment.")
-            # reference base_class.py:215-218
-            assert np.all(np.isfinite(np.array([self.action_space.low, self.action_space.high]))), \
-                "Continuous action space must have a finite lower and upper bound"
+            if isinstance(self.action_space, Box):  # reference base_class.py:215-218
+                assert np.all(np.isfinite(np.array([self.action_space.low, self.action_space.high]))), \
+                    "Continuous action space must have a finite lower and upper bound"
 
     # ---- env / policy plumbing --------------------------------------------------------------------------------
+    @staticmethod
+    def _as_action_space(space):
+        d = as_discrete(space)
+        return d if d is not None else as_box(space)
+
     @staticmethod
     def _wrap_env(env, verbose: int = 0) -> VecEnv:
         """reference: base_class.py:220-253. A VecEnv passes through untouched; a bare TwoSeriesCSTREnv becomes a
@@ -146,7 +155,7 @@ class BaseAlgorithm:
         env = self._wrap_env(env, self.verbose)
         if env.num_envs != self.n_envs:
             raise AssertionError("The number of environments to be set is different from the number of environments in the model")
-        if as_box(env.observation_space) != self.observation_space or as_box(env.action_space) != self.action_space:
+        if as_box(env.observation_space) != self.observation_space or self._as_action_space(env.action_space) != self.action_space:
             raise ValueError("Observation/action spaces do not match")
         if force_reset:
             self._last_obs = None
@@ -292,6 +301,9 @@ class BaseAlgorithm:
             data["train_freq"] = [tf.frequency, tf.unit.value]
         data["algo"] = type(self).__name__
         for nm, sp in (("observation_space", self.observation_space), ("action_space", self.action_space)):
+            if isinstance(sp, Discrete):
+                data[nm] = {"n": sp.n, "start": sp.start, "shape": [], "dtype": str(sp.dtype)}
+                continue
             data[nm] = {"low": np.asarray(sp.low).tolist(), "high": np.asarray(sp.high).tolist(), "shape": list(sp.shape), "dtype": str(sp.dtype)}
         data.update(self._extra_save_data())
         for k in (exclude or []):
@@ -309,6 +321,7 @@ class BaseAlgorithm:
         data, params, variables = load_from_zip_file(path, device="cpu")
         if env is None:
             raise ValueError("load(): pass `env` (environments are not stored in the archive)")
+        cls._check_archive(data, env)
         ctor = {k: data[k] for k in cls._ctor_keys() if k in data}
         if "train_freq" in data and isinstance(data["train_freq"], list):
             ctor["train_freq"] = (int(data["train_freq"][0]), str(data["train_freq"][1]))
@@ -322,9 +335,17 @@ class BaseAlgorithm:
         for k in ("num_timesteps", "_n_updates", "_episode_num", "_total_timesteps", "_num_timesteps_at_start"):
             if k in data:
                 setattr(model, k, data[k])
+        model._restore_extra(data)
         if model.use_sde:
             model.policy.reset_noise()  # :823-824
         return model
+
+    @classmethod
+    def _check_archive(cls, data: dict, env) -> None:
+        """Hook of load(): refuse an archive that does not fit `env` before anything is built."""
+
+    def _restore_extra(self, data: dict) -> None:
+        """Hook of load(): the class's own counters out of the archive's `data`."""
 
     @classmethod
     def _ctor_keys(cls) -> tuple:

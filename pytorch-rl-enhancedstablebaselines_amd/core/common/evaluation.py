@@ -106,7 +106,8 @@ def evaluate_policy(model, env, n_eval_episodes: int = 10, deterministic: bool =
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype="int")  # :79-82
     policy = getattr(model, "policy", model)
     on_device = (callback is None and not render and isinstance(getattr(env, "unwrapped", None), CSTRVecEnv)
-                 and hasattr(env, "step_device") and hasattr(policy, "_predict") and hasattr(policy, "squash_output"))
+                 and hasattr(env, "step_device") and hasattr(policy, "_predict") and hasattr(policy, "squash_output")
+                 and hasattr(getattr(policy, "action_space", None), "low"))  # a Discrete face (DQN) steps through env.step(indices)
     if on_device:
         rets, lens = _evaluate_on_device(policy, env, targets, deterministic)
     else:

@@ -85,7 +85,7 @@ class GraphReplay:
             return 1
         if self._grads_need_allreduce() and not self._collectives_in_graph():
             return 1  # data-parallel with the collectives BETWEEN graph segments: one iteration per replay list
-        remaining = (self._total_timesteps - self.num_timesteps) // self.n_envs
+        remaining = (self._total_timesteps - self.num_timesteps) // self._graph_steps_per_iteration()
         while u > 1 and remaining < u:  # the tail of a run: the largest of u, u / 2, u / 4, ... that still fits
             u //= 2
         return max(u, 1)
@@ -102,7 +102,7 @@ class GraphReplay:
             # side-stream warm-up (these are REAL iterations: they advance env, ring, RNG and optimiser state)
             warm = self._graph_warm.get(key, 0)
             if warm < GRAPH_WARMUP_ITERATIONS:
-                self._train_host_pre()
+                self._graph_host_pre()
                 side = th.cuda.Stream(device=self.device)
                 side.wait_stream(th.cuda.current_stream(self.device))
                 with th.cuda.stream(side):
@@ -112,7 +112,7 @@ class GraphReplay:
                 self._eager_iterations += 1
                 self._graph_host_bookkeeping(log_interval)
                 return
-            self._train_host_pre()
+            self._graph_host_pre()
             try:
                 self._graph[key] = self._capture_segments(unroll)
             except Exception as exc:  # something in the iteration is not capturable: run eagerly from now on
@@ -121,7 +121,7 @@ class GraphReplay:
                 self._graph_enabled, self._graph = False, None
                 self._learn_iteration(callback if callback is not None else self._noop_callback(), log_interval)
                 return
-        self._train_host_pre()
+        self._graph_host_pre()
         for item in self._graph[key]:  # hipGraph segments interleaved with the eager collectives that separate them
             item.replay() if isinstance(item, th.cuda.CUDAGraph) else item()
         self._graph_replays += unroll
@@ -248,6 +248,10 @@ class GraphReplay:
         """The host side of one iteration that ran on the device (counters, progress, logger records)."""
         raise NotImplementedError
 
+    def _graph_steps_per_iteration(self) -> int:
+        """Env steps one body advances `num_timesteps` by (the unroll ladder counts the bodies that still fit into the run)."""
+        return self.n_envs
+
     def _graph_phase(self) -> int:
         """Which of the alternating launch sequences the coming iteration is (a delayed policy update: one graph per residue)."""
         return 0
@@ -259,6 +263,10 @@ class GraphReplay:
     def _train_host_pre(self) -> None:
         """The host prologue of train() (learning-rate schedule), run before every warm-up, capture and replay."""
         raise NotImplementedError
+
+    def _graph_host_pre(self) -> None:
+        """What the host does before every warm-up body, capture and replay; by default train()'s own prologue."""
+        self._train_host_pre()
 
     def _drop_recording_debts(self) -> None:
         """Forget host-side promises made by launches that were only recorded, after a recording failed."""

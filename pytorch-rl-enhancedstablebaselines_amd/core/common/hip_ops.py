@@ -1515,3 +1515,57 @@ def rmsprop(param, grad, square_avg, lr_dev, alpha: float = 0.99, eps: float = 1
     check(nv.lib().cstr_rmsprop_f32(ptr(param), ptr(grad), ptr(square_avg), ptr(lr_dev), C.c_double(alpha), C.c_double(eps),
                                     C.c_float(max_norm if clip else 0.0), ptr(workspace if clip else None), ptr(norm_out if clip else None),
                                     C.c_int64(n), stream_ptr()), "cstr_rmsprop_f32")
+
+
+# ---- DQN on the discrete valve face: exploration draw, action selection, target + gather + Huber loss (csrc/cstr_dqn.hip) -----------
+def dqn_supported(n_actions: int, levels: int) -> bool:
+    return 2 <= levels <= nv.DQN_MAX_LEVELS and n_actions == levels * levels
+
+
+def mt19937_rand_flag(mt_state, threshold, flag_out, draw_out=None):
+    """flag_out[0] = (one RandomState.random_sample() from the device legacy stream) < threshold[0]; threshold a device double,
+    flag_out a device int32, draw_out (optional, device double) keeps the draw. `np.random.rand() < exploration_rate`."""
+    _chk(mt_state, "mt_state", (nv.MT_STATE_WORDS,), th.int32), _chk(threshold, "threshold", (1,), th.float64)
+    _chk(flag_out, "flag_out", (1,), th.int32), _opt(draw_out, "draw_out", (1,), th.float64)
+    check(nv.lib().cstr_mt19937_rand_flag_f64(ptr(mt_state), ptr(threshold), ptr(flag_out), ptr(draw_out), stream_ptr()),
+          "cstr_mt19937_rand_flag_f64")
+
+
+DQN_GREEDY, DQN_ALL_OR_NONE, DQN_PER_ROW = 0, 1, 2
+
+
+def dqn_act(q, levels: int, mode: int, valve_out, index_out=None, eps=None, flag=None, u=None, rng_ctl=None):
+    """Action selection over q [n, levels^2] (rows may be strided): mode DQN_GREEDY = first maximum; DQN_ALL_OR_NONE = every row a
+    uniform random index iff flag[0] != 0 (the reference's one draw per vec-step); DQN_PER_ROW = row r explores iff u[r, 0] < eps[0].
+    Uniforms are read from `u` [n, 2] when given, drawn from the Philox stream `rng_ctl` otherwise. valve_out [n, 2] receives the
+    normalised valve pair of the index, index_out (optional, int64 [n]) the index."""
+    n, m = q.shape
+    ldq = _rows(q, "q", n, m)
+    _chk(valve_out, "valve_out", (n, 2), th.float32), _opt(index_out, "index_out", (n,), th.int64)
+    _opt(eps, "eps", (1,), th.float64), _opt(flag, "flag", (1,), th.int32), _opt(u, "u", (n, 2), th.float32)
+    _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    check(nv.lib().cstr_dqn_act_f32(ptr(q), C.c_int64(ldq), C.c_int64(n), C.c_int(m), C.c_int(levels), C.c_int(mode), ptr(eps), ptr(flag),
+                                    ptr(u), ptr(rng_ctl), ptr(valve_out), ptr(index_out), stream_ptr()), "cstr_dqn_act_f32")
+
+
+def dqn_loss(q, next_q, valve, reward, done, gamma: float, levels: int, g_q, loss_out, workspace, loss_sum=None, cur_q_out=None,
+             target_out=None):
+    """dqn.py:195-212 in one launch: target = reward + ((1 - done) * f32(gamma)) * max next_q, cur = q[b, index(valve[b])], loss_out =
+    mean Huber loss (beta 1), g_q = d loss / d q (q's shape and row stride). c_float rounds gamma."""
+    b, m = q.shape
+    ldq = _rows(q, "q", b, m)
+    ldn = _rows(next_q, "next_q", b, m)
+    if _rows(g_q, "g_q", b, m) != ldq:
+        raise ValueError("g_q must have q's row stride")
+    _chk(valve, "valve", (b, 2), th.float32)
+    for t, nm in ((reward, "reward"), (done, "done")):
+        _vec(t, nm, b)
+    _vec(loss_out, "loss_out", 1), _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+    if loss_sum is not None:
+        _vec(loss_sum, "loss_sum", 1)
+    for t, nm in ((cur_q_out, "cur_q_out"), (target_out, "target_out")):
+        if t is not None:
+            _vec(t, nm, b)
+    check(nv.lib().cstr_dqn_loss_f32(ptr(q), C.c_int64(ldq), ptr(next_q), C.c_int64(ldn), ptr(valve), ptr(reward), ptr(done), C.c_float(gamma),
+                                     C.c_int64(b), C.c_int(m), C.c_int(levels), ptr(g_q), ptr(loss_out), ptr(loss_sum), ptr(cur_q_out),
+                                     ptr(target_out), ptr(workspace), stream_ptr()), "cstr_dqn_loss_f32")

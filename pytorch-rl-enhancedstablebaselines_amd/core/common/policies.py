@@ -6,7 +6,7 @@ import numpy as np
 import torch as th
 from torch import nn
 
-from core.common.spaces import as_box, get_action_dim
+from core.common.spaces import as_box, as_discrete, get_action_dim
 from core.common.torch_layers import FlattenExtractor, create_mlp
 
 
@@ -20,7 +20,7 @@ class BaseModel(nn.Module):
                  normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs: Optional[dict] = None):
         super().__init__()
         self.observation_space = as_box(observation_space)
-        self.action_space = as_box(action_space)
+        self.action_space = as_discrete(action_space) or as_box(action_space)  # Discrete: DQN's valve face only
         self.features_extractor = features_extractor
         self.normalize_images = normalize_images
         self.optimizer_class = optimizer_class

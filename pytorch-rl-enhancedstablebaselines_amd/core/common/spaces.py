@@ -1,4 +1,4 @@
-"""Minimal `Box` space (the only space on the CSTR path). gymnasium is not a dependency of this stack:
+"""Minimal `Box` space (the space of the CSTR path) and `Discrete` (DQN's discretised valve face). gymnasium is not a dependency of this stack:
 any object with `low`, `high`, `shape`, `dtype` (e.g. a real gymnasium.spaces.Box) is accepted wherever a
 Box is expected; `as_box` normalises it. Mirrors the attributes the reference reads
 (core/common/preprocessing.py:152-197, core/common/base_class.py:215-218)."""
@@ -66,6 +66,51 @@ class Box(Space):
 
     def __repr__(self):
         return f"Box({self.low.min()}, {self.high.max()}, {self.shape}, {self.dtype})"
+
+
+class Discrete(Space):
+    """`n` indices start, ..., start + n - 1 (gymnasium.spaces.Discrete: dtype int64, shape ()). `sample()` draws from the space's own
+    Generator; gymnasium's own draw order is not available here (UNPINNED, as for Box.sample)."""
+
+    def __init__(self, n: int, seed=None, start: int = 0):
+        if not (isinstance(n, (int, np.integer)) and n > 0):
+            raise ValueError(f"n (counts) have to be positive, got {n!r}")
+        self.n, self.start = int(n), int(start)
+        super().__init__((), np.int64)
+        if seed is not None:
+            self.seed(seed)
+
+    def sample_batch(self, count: int) -> np.ndarray:
+        """`np.array([space.sample() for _ in range(count)])` (dqn.py:251) in one call"""
+        return self.start + self.np_random.integers(0, self.n, size=count, dtype=np.int64)
+
+    def sample(self) -> np.int64:
+        return np.int64(self.sample_batch(1)[0])
+
+    def contains(self, x) -> bool:
+        if isinstance(x, (np.generic, np.ndarray)):
+            if not (np.issubdtype(np.asarray(x).dtype, np.integer) and np.asarray(x).shape == ()):
+                return False
+            x = int(x)
+        elif not isinstance(x, int) or isinstance(x, bool):
+            return False
+        return self.start <= x < self.start + self.n
+
+    def __eq__(self, other):
+        return hasattr(other, "n") and not hasattr(other, "low") and int(other.n) == self.n and int(getattr(other, "start", 0)) == self.start
+
+    def __repr__(self):
+        return f"Discrete({self.n})" if self.start == 0 else f"Discrete({self.n}, start={self.start})"
+
+
+def as_discrete(space) -> Optional[Discrete]:
+    """`space` as a Discrete (itself, or a scalar-shaped object with a count `n` and no bounds, e.g. a gymnasium.spaces.Discrete; a
+    MultiBinary(n) has shape (n,) and is none), else None."""
+    if isinstance(space, Discrete):
+        return space
+    if hasattr(space, "n") and not hasattr(space, "low") and np.isscalar(space.n) and tuple(getattr(space, "shape", None) or ()) == ():
+        return Discrete(int(space.n), start=int(getattr(space, "start", 0)))
+    return None
 
 
 class IndexedBox(Box):

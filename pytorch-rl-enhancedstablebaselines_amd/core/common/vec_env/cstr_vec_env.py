@@ -15,8 +15,32 @@ import torch as th
 
 from core import _native as nv
 from core.common import hip_ops
-from core.common.spaces import Box
+from core.common.spaces import Box, Discrete
 from core.common.vec_env.base_vec_env import VecEnv
+
+MIN_VALVE_LEVELS, MAX_VALVE_LEVELS = 2, 16
+
+
+def valve_levels(levels: int) -> np.ndarray:
+    """v(q) for q = 0 .. levels - 1: f32(-1) + f32(2 q) / f32(levels - 1), evaluated in float32 in that order (what
+    cstr_dqn_act_f32 writes)."""
+    q = np.arange(levels, dtype=np.int64)
+    return np.float32(-1) + (2 * q).astype(np.float32) / np.float32(levels - 1)
+
+
+def decode_valve_index(index, levels: int) -> np.ndarray:
+    """indices a [...] -> normalised valve pairs [..., 2] = (v(a // levels), v(a % levels))"""
+    a = np.asarray(index, dtype=np.int64)
+    v = valve_levels(levels)
+    return np.stack([v[a // levels], v[a % levels]], axis=-1)
+
+
+def encode_valve_pair(valve, levels: int) -> np.ndarray:
+    """valve pairs [..., 2] (as stored in the replay ring) -> indices [...]: q = rint((v + 1) * (levels - 1) / 2) in float32"""
+    v = np.asarray(valve, dtype=np.float32)
+    q = np.rint(((v + np.float32(1)) * np.float32(levels - 1)) / np.float32(2))
+    q = np.clip(q, 0, levels - 1).astype(np.int64)
+    return q[..., 0] * levels + q[..., 1]
 
 
 class CSTRVecEnv(VecEnv):
@@ -31,6 +55,11 @@ class CSTRVecEnv(VecEnv):
     :param integrator: "euler" (reference, parity-pinned) or "rk4" (north_star's ask; not in the reference)
     :param default_target, min_concentration, max_concentration, init_mode: TwoSeriesCSTREnv ctor args
     :param seed_offset: added to env seeds, used by data-parallel shards (rank * num_envs)
+    :param discrete_actions: K in 2..16 (twin=False only): a DISCRETE face over the same two valves, for DQN. `action_space` is
+                    Discrete(K * K); index a stands for the valve levels (i, j) = (a // K, a % K) and the normalised valve action
+                    v(q) = f32(-1) + f32(2 q) / f32(K - 1). `valve_space` = Box(-1, 1, (2,)) is what the env kernels and the replay
+                    ring see: `step()` / `step_async()` take index arrays [N] (or [N, 1]) and decode them, `step_device` keeps
+                    taking [N, 2] valve tensors. A constructed face, like twin=True: the reference's env has the Box face only
     """
 
     metadata = {"render_modes": ["human", "rgb_array"], "render_fps": 4}
@@ -38,7 +67,12 @@ class CSTRVecEnv(VecEnv):
 
     def __init__(self, num_envs: int, obs_dim: int = 4, integrator: str = "euler", device="cuda",
                  default_target: float = 0.20, min_concentration: float = 0.05, max_concentration: float = 0.45,
-                 init_mode: str = "random", seed_offset: int = 0, twin: bool = False):
+                 init_mode: str = "random", seed_offset: int = 0, twin: bool = False, discrete_actions: Optional[int] = None):
+        if discrete_actions is not None:
+            if twin:
+                raise ValueError("discrete_actions needs twin=False (one valve pair per env)")
+            if not (isinstance(discrete_actions, (int, np.integer)) and MIN_VALVE_LEVELS <= discrete_actions <= MAX_VALVE_LEVELS):
+                raise ValueError(f"discrete_actions must be an integer in [{MIN_VALVE_LEVELS}, {MAX_VALVE_LEVELS}], got {discrete_actions!r}")
         if obs_dim not in (4, 8):
             raise ValueError(f"obs_dim must be 4 or 8, got {obs_dim}")
         if twin and obs_dim != 8:
@@ -59,7 +93,10 @@ class CSTRVecEnv(VecEnv):
         else:
             lo, hi = -one, one
         a1 = np.ones(self.act_dim, np.float32)
-        super().__init__(num_envs, Box(lo, hi, dtype=np.float32), Box(-a1, a1, dtype=np.float32))
+        self.valve_space = Box(-a1, a1, dtype=np.float32)
+        self.discrete_actions = None if discrete_actions is None else int(discrete_actions)
+        action_space = self.valve_space if discrete_actions is None else Discrete(self.discrete_actions ** 2)
+        super().__init__(num_envs, Box(lo, hi, dtype=np.float32), action_space)
         self.obs_dim, self.integrator, self.seed_offset = obs_dim, integrator, seed_offset
         self.target_C2, self.min_concentration, self.max_concentration = default_target, min_concentration, max_concentration
         self.init_mode = init_mode
@@ -160,6 +197,14 @@ class CSTRVecEnv(VecEnv):
         return self.obs, self._rew, self._done, self._timeout, self._next_obs
 
     def step_async(self, actions) -> None:
+        if self.discrete_actions is not None:
+            idx = actions.cpu().numpy() if isinstance(actions, th.Tensor) else np.asarray(actions)
+            if not np.issubdtype(idx.dtype, np.integer) or idx.shape not in ((self.num_envs,), (self.num_envs, 1)):
+                raise ValueError(f"discrete actions: expected integer indices of shape {(self.num_envs,)}, got {idx.dtype} {idx.shape}")
+            idx = idx.reshape(self.num_envs)
+            if idx.min() < 0 or idx.max() >= self.action_space.n:
+                raise ValueError(f"discrete actions: indices must lie in [0, {self.action_space.n})")
+            actions = decode_valve_index(idx, self.discrete_actions)
         a = th.as_tensor(np.asarray(actions, dtype=np.float32)) if not isinstance(actions, th.Tensor) else actions
         if tuple(a.shape) != (self.num_envs, self.act_dim):
             raise ValueError(f"actions shape {tuple(a.shape)} != {(self.num_envs, self.act_dim)}")

@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,init,vecenv]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,init,vecenv]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -18,6 +18,7 @@ Reference entry points exercised (file:line in /root/reference):
   core/bcq/bcq.py:129-213                BCQ.train; core/bcq/policies.py:426-435 BCQPolicy._predict
   core/ppo/ppo.py:184-300                PPO.train; core/common/on_policy_algorithm.py:162-268 collect_rollouts
   core/a2c/a2c.py:132-190                A2C.train
+  core/dqn/dqn.py:168-256                DQN._on_step / train / predict
   core/common/utils.py:457-481           polyak_update
 """
 import argparse
@@ -1523,10 +1524,246 @@ def gen_a2c():
             slim[k] = v
     save("a2c_train_kat_default.npz", **slim)
 
+# ------------------------------------------------------------------------------ DQN on the discretised valve face
+def _valve(q, K):
+    """v(q) of the discrete valve face, float32, in exactly this order (core/common/vec_env/cstr_vec_env.py states the same)"""
+    return np.float32(-1) + np.float32(2 * q) / np.float32(K - 1)
+
+
+def _make_discrete_venv(N, K):
+    """Harness code of ours: the reference's TwoSeriesCSTREnv behind a Discrete(K * K) action space; index a = i * K + j opens the
+    two valves to v(i), v(j)."""
+    from gymnasium import spaces
+
+    from core.common.vec_env.dummy_vec_env import DummyVecEnv
+    from twoseriescstr import TwoSeriesCSTREnv
+
+    class DiscreteValveCSTR(TwoSeriesCSTREnv):
+        def __init__(self):
+            super().__init__()
+            self._valve_box, self.action_space = self.action_space, spaces.Discrete(K * K)
+
+        def step(self, action):
+            a = int(action)
+            face, self.action_space = self.action_space, self._valve_box  # the env's own step clips into its Box
+            try:
+                return super().step(np.array([_valve(a // K, K), _valve(a % K, K)], np.float32))
+            finally:
+                self.action_space = face
+
+    return DummyVecEnv([lambda: DiscreteValveCSTR() for _ in range(N)])
+
+
+class _DqnHooks:
+    """Around the UNMODIFIED reference (core/dqn/dqn.py): the (current_q, target_q) arguments of smooth_l1_loss and the gradient norm
+    clip_grad_norm_ returns; np.random.rand / randint calls with their results."""
+
+    def __enter__(self):
+        import torch.nn.functional as F_real
+
+        import core.dqn.dqn as dqnmod
+
+        self.huber, self.norms, self.rands, self.randints = [], [], [], []
+        self._mod, self._F, self._clip, self._rand, self._randint = dqnmod, F_real, th.nn.utils.clip_grad_norm_, np.random.rand, np.random.randint
+        hooks = self
+
+        class FProxy:
+            def __getattr__(self, name):
+                return getattr(F_real, name)
+
+            @staticmethod
+            def smooth_l1_loss(a, b, *args, **kw):
+                hooks.huber.append((a.detach().clone(), b.detach().clone()))
+                return F_real.smooth_l1_loss(a, b, *args, **kw)
+
+        def clip(parameters, max_norm, *a, **kw):
+            norm = self._clip(parameters, max_norm, *a, **kw)
+            self.norms.append(float(norm))
+            return norm
+
+        def rand(*a):
+            r = self._rand(*a)
+            self.rands.append(float(r))
+            return r
+
+        def randint(*a, **kw):
+            r = self._randint(*a, **kw)
+            self.randints.append((a, dict(kw), np.asarray(r).copy()))
+            return r
+
+        dqnmod.F, th.nn.utils.clip_grad_norm_, np.random.rand, np.random.randint = FProxy(), clip, rand, randint
+        return self
+
+    def __exit__(self, *exc):
+        self._mod.F, th.nn.utils.clip_grad_norm_, np.random.rand, np.random.randint = self._F, self._clip, self._rand, self._randint
+
+
+def _gen_dqn_train(tag, K, B, n_steps, update_after, **kw):
+    """Teacher-forced DQN.train (core/dqn/dqn.py:184-226): injected batches, one gradient step per call; `update_after`: the
+    reference's own _on_step performs a target update behind that step."""
+    from core.common.logger import Logger
+    from core.common.type_aliases import ReplayBufferSamples
+    from core.dqn.dqn import DQN
+
+    N, D = 4, 4
+    model = DQN("MlpPolicy", _make_discrete_venv(N, K), seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **kw)
+    model.set_logger(Logger(folder=None, output_formats=[]))
+    out = {}
+    for nm in ("q_net", "q_net_target"):
+        out.update(_flat_sd(f"before/{nm}", getattr(model, nm).state_dict()))
+    assert sorted(model.policy.state_dict()) == sorted(f"{n}.q_net.{i}.{p}" for n in ("q_net", "q_net_target") for i in (0, 2, 4) for p in ("weight", "bias"))
+    rng = np.random.default_rng(2024 + K)
+    batches = []
+    for k in range(n_steps):
+        obs = rng.uniform(-1, 1, (B, D)).astype(np.float32)
+        nobs = np.clip(obs + rng.normal(0, 0.05, (B, D)), -1, 1).astype(np.float32)
+        index = rng.integers(0, K * K, (B, 1)).astype(np.int64)
+        # rewards on both sides of the Huber threshold (the untrained Q values are small)
+        rew = np.where(rng.uniform(size=(B, 1)) < 0.5, rng.uniform(-0.8, 0.8, (B, 1)), rng.uniform(-8, 0, (B, 1))).astype(np.float32)
+        done = (rng.uniform(size=(B, 1)) < 0.25).astype(np.float32)
+        batches.append((obs, index, nobs, done, rew))
+    feed = list(batches)
+    model.replay_buffer.sample = lambda batch_size, env=None: ReplayBufferSamples(*(th.as_tensor(x) for x in feed.pop(0)))
+    logged = []
+    with _DqnHooks() as hk:
+        for k in range(n_steps):
+            model.train(gradient_steps=1, batch_size=B)
+            lv = model.logger.name_to_value
+            logged.append(sorted(lv))
+            out[f"step{k}/loss"] = np.float32(lv["train/loss"])
+            out[f"step{k}/n_updates"] = np.int64(lv["train/n_updates"])
+            out[f"step{k}/learning_rate"] = np.float64(lv["train/learning_rate"])
+            if k == update_after:  # the reference's own _on_step: _n_calls hits the update period
+                model._n_calls = max(model.target_update_interval // model.n_envs, 1) - 1
+                before = [p.detach().clone() for p in model.q_net_target.parameters()]
+                model._on_step()
+                assert any(not th.equal(a, b) for a, b in zip(before, model.q_net_target.parameters()))
+            for nm in ("q_net", "q_net_target"):
+                out.update(_flat_sd(f"after/step{k}/{nm}", getattr(model, nm).state_dict()))
+            st = model.policy.optimizer.state_dict()["state"]
+            out[f"step{k}/optimizer_step"] = np.int64(int(next(iter(st.values()))["step"]))
+    assert len(hk.huber) == n_steps and len(hk.norms) == n_steps
+    for k in range(n_steps):
+        for fi, fname in enumerate(["observations", "index", "next_observations", "dones", "rewards"]):
+            out[f"step{k}/batch_{fname}"] = batches[k][fi]
+        out[f"step{k}/current_q"], out[f"step{k}/target_q"] = hk.huber[k][0].numpy(), hk.huber[k][1].numpy()
+        out[f"step{k}/grad_norm"] = np.float32(hk.norms[k])
+        d = np.abs(out[f"step{k}/current_q"] - out[f"step{k}/target_q"])
+        assert (d < 1).any() and (d > 1).any(), "both Huber branches"
+    out["logged_keys"] = np.array(logged[-1])
+    out["hyper"] = np.array([model.gamma, model.tau, model.max_grad_norm, model.lr_schedule(1), B, n_steps, K, update_after], np.float64)
+    out["clip_engaged"] = np.uint8(any(n > model.max_grad_norm for n in hk.norms))
+    print(f"dqn {tag}: grad norms {hk.norms}, max_grad_norm {model.max_grad_norm}")
+    return out
+
+
+def _gen_dqn_predict():
+    from core.dqn.dqn import DQN
+
+    K = 3
+    model = DQN("MlpPolicy", _make_discrete_venv(1, K), seed=3, device="cpu", policy_kwargs=dict(net_arch=[64, 64]))
+    rng = np.random.default_rng(77)
+    obs = rng.uniform(-1, 1, (96, 4)).astype(np.float32)
+    with th.no_grad():
+        q = model.q_net(th.as_tensor(obs)).numpy()
+    top = np.sort(q, axis=1)
+    keep = (top[:, -1] - top[:, -2]) >= 1e-3 * np.abs(q).mean()  # the generator filters; the test leaves out no row
+    obs, q = obs[keep], q[keep]
+    act, _ = model.predict(obs, deterministic=True)
+    one, _ = model.predict(obs[0], deterministic=True)
+    assert act.shape == (len(obs),) and act.dtype == np.int64 and one.shape == () and int(one) == int(act[0])
+    out = dict(obs=obs, actions=act, q=q, levels=np.int64(K), kept=np.int64(keep.sum()), drawn=np.int64(len(keep)))
+    out.update(_flat_sd("before/q_net", model.q_net.state_dict()))
+    save("dqn_predict_kat.npz", **out)
+
+
+def _gen_dqn_explore():
+    """A short seeded learn(): per post-warm-up vec-step the exploration rate in force and the rand() drawn against it; per gradient
+    step the sampled batch_inds / env_indices. They depend on the streams and the ring position only."""
+    from core.common.logger import Logger
+    from core.dqn.dqn import DQN
+
+    N, K, B, seed, total = 4, 3, 16, 11, 64
+    model = DQN("MlpPolicy", _make_discrete_venv(N, K), seed=seed, device="cpu", batch_size=B, buffer_size=64 * N, learning_starts=8, train_freq=4,
+                target_update_interval=24, exploration_fraction=0.8, policy_kwargs=dict(net_arch=[64, 64]))
+    model.set_logger(Logger(folder=None, output_formats=[]))
+    state0 = {}
+    rates_in_force = []
+    orig_collect, orig_predict = model.collect_rollouts, model.predict
+
+    def collect(*a, **kw):
+        if not state0:
+            st = np.random.get_state()
+            state0.update(key=st[1].copy(), pos=np.int64(st[2]))
+        return orig_collect(*a, **kw)
+
+    def predict(*a, **kw):
+        rates_in_force.append(float(model.exploration_rate))
+        return orig_predict(*a, **kw)
+
+    model.collect_rollouts, model.predict = collect, predict
+    with _DqnHooks() as hk:
+        model.learn(total)
+    st = np.random.get_state()
+    sized = [(a, kw, r) for a, kw, r in hk.randints if np.size(r) == B]
+    assert len(hk.rands) == len(rates_in_force) and len(sized) == 2 * model._n_updates
+    out = dict(n_envs=np.int64(N), levels=np.int64(K), batch_size=np.int64(B), seed=np.int64(seed), total_timesteps=np.int64(total),
+               learning_starts=np.int64(8), train_freq=np.int64(4), target_update_interval=np.int64(24), exploration_fraction=np.float64(0.8),
+               exploration_initial_eps=np.float64(model.exploration_initial_eps), exploration_final_eps=np.float64(model.exploration_final_eps),
+               mt_key0=state0["key"], mt_pos0=state0["pos"], mt_key_final=st[1].copy(), mt_pos_final=np.int64(st[2]),
+               exploration_rate=np.array(rates_in_force, np.float64), rand=np.array(hk.rands, np.float64),
+               explored=np.array([r < e for r, e in zip(hk.rands, rates_in_force)], np.uint8),
+               batch_inds=np.stack([r for _, _, r in sized[0::2]]).astype(np.int64), env_indices=np.stack([r for _, _, r in sized[1::2]]).astype(np.int64),
+               batch_high=np.array([(a[1] if len(a) > 1 else kw.get("high", a[0])) for a, kw, _ in sized[0::2]], np.int64),
+               n_updates=np.int64(model._n_updates), n_calls=np.int64(model._n_calls), num_timesteps=np.int64(model.num_timesteps),
+               final_exploration_rate=np.float64(model.exploration_rate))
+    print("dqn explore: rates", rates_in_force, "explored", out["explored"].tolist(), "highs", out["batch_high"].tolist())
+    save("dqn_explore_kat.npz", **out)
+
+
+def _gen_dqn_wiring():
+    """A synthetic one-step problem (done = 1 everywhere): reward 1 iff the stored index equals a fixed function of the observation's
+    sign pattern. The unmodified reference trains on it for seeds 0, 1, 2; the fixture holds the data, the held-out observations and
+    how often the greedy action is the rewarded one, trained and untrained."""
+    from core.common.logger import Logger
+    from core.dqn.dqn import DQN
+
+    K, N, R, B, steps, lr = 3, 8, 256, 64, 600, 1e-3
+    rng = np.random.default_rng(4242)
+    best = lambda o: ((o[..., 0] > 0).astype(np.int64) + (o[..., 2] > 0)) * K + (o[..., 1] > 0).astype(np.int64) + (o[..., 3] > 0)  # noqa: E731
+    obs = rng.uniform(-1, 1, (R, N, 4)).astype(np.float32)
+    index = rng.integers(0, K * K, (R, N)).astype(np.int64)
+    reward = (index == best(obs)).astype(np.float32)
+    held = rng.uniform(-1, 1, (512, 4)).astype(np.float32)
+    trained, untrained = [], []
+    for seed in (0, 1, 2):
+        model = DQN("MlpPolicy", _make_discrete_venv(N, K), seed=seed, device="cpu", batch_size=B, buffer_size=R * N, learning_rate=lr)
+        model.set_logger(Logger(folder=None, output_formats=[]))
+        for r in range(R):
+            model.replay_buffer.add(obs[r], obs[r], index[r].reshape(N, 1), reward[r], np.ones(N, bool), [{} for _ in range(N)])
+        untrained.append(float((model.predict(held, deterministic=True)[0] == best(held)).mean()))
+        model.train(gradient_steps=steps, batch_size=B)
+        trained.append(float((model.predict(held, deterministic=True)[0] == best(held)).mean()))
+    print(f"dqn wiring: reference accuracy trained {trained}, untrained {untrained}")
+    save("dqn_wiring_kat.npz", obs=obs, index=index, reward=reward, held_obs=held, held_best=best(held), levels=np.int64(K),
+         batch_size=np.int64(B), gradient_steps=np.int64(steps), learning_rate=np.float64(lr), reference_accuracy=np.array(trained),
+         untrained_accuracy=np.array(untrained))
+
+
+def gen_dqn():
+    small = _gen_dqn_train("small", K=3, B=32, n_steps=3, update_after=1, max_grad_norm=0.05, target_update_interval=1000,
+                           policy_kwargs=dict(net_arch=[64, 64]))
+    assert small["clip_engaged"]
+    save("dqn_train_kat_small.npz", **small)
+    save("dqn_train_kat_default.npz", **slim_weights(_gen_dqn_train("default", K=5, B=32, n_steps=2, update_after=0)))
+    _gen_dqn_predict()
+    _gen_dqn_explore()
+    _gen_dqn_wiring()
+
 
 GENS = {"a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
-        "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint}
+        "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()

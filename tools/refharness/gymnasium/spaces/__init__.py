@@ -76,6 +76,19 @@ class Discrete(Space):
         self.n, self.start = int(n), int(start)
         super().__init__((), np.int64, seed)
 
+    def sample(self):
+        # stand-in: real gymnasium's exact draw order is NOT pinned
+        return np.int64(self.start + self.np_random.integers(self.n))
+
+    def contains(self, x):
+        return bool(np.issubdtype(np.asarray(x).dtype, np.integer) and np.shape(x) == () and self.start <= int(x) < self.start + self.n)
+
+    def __eq__(self, other):
+        return isinstance(other, Discrete) and self.n == other.n and self.start == other.start
+
+    def __repr__(self):
+        return f"Discrete({self.n})"
+
 
 class MultiDiscrete(Space):
     def __init__(self, nvec, dtype=np.int64, seed=None):
