@@ -1024,6 +1024,13 @@ def test_td3_ddpg_fused_path_equals_stock_aten_path_across_configurations(algo, 
     for (n1, p1), (_, p2) in zip(a.policy.named_parameters(), b.policy.named_parameters()):
         scale = max(float(p2.detach().abs().max()), 1e-3)
         assert float((p1 - p2).detach().abs().max()) < 2e-5 * scale + 2e-6, n1
+    # the optimiser state as well, as for SAC above (the chain path updates it inside the dW / db launch): weights after a few Adam
+    # steps move by about lr * sign(g) whatever |g| is, the moments do not
+    for nm, oa, ob in (("actor", a.actor.optimizer, b.actor.optimizer), ("critic", a.critic.optimizer, b.critic.optimizer)):
+        assert all(hasattr(o, k) for o in (oa, ob) for k in ("step_count", "exp_avg", "exp_avg_sq")), nm  # both are FlatAdam: nothing is left out
+        assert oa.step_count == ob.step_count == (n_calls if nm == "critic" else n_calls // a.policy_delay), nm
+        assert float((oa.exp_avg - ob.exp_avg).abs().max()) < 1e-5 * max(float(ob.exp_avg.abs().max()), 1e-6) + 1e-9, nm
+        assert float((oa.exp_avg_sq - ob.exp_avg_sq).abs().max()) < 1e-4 * max(float(ob.exp_avg_sq.abs().max()), 1e-12), nm
     assert a._n_updates == b._n_updates == n_calls
 
 
