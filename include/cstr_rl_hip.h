@@ -429,6 +429,36 @@ int cstr_rollout_step_f32(const cstr_policy_mlp_t *net, const float *x, int64_t 
                           double *ep_stats, float *action_out, uint32_t *mt_state, int64_t batch, int32_t *sample_idx,
                           cstr_stream_t stream);
 
+/* Whole evaluation episodes in ONE launch: evaluate_policy's loop (core/common/evaluation.py:84-131) for a device-resident vec-env and
+ * a policy that cstr_policy_mlp_t describes. A workgroup owns 16 envs and walks their vec-steps inside the launch; per step: the policy
+ * network on the 16 observation rows (k0 = obs_dim; the shapes of cstr_policy_rows_fwd_f32, W2 streamed from L2 as rows or, when
+ * net->w2_swizzled is given, from the tile-major copy), the head (head 0: the squashed Gaussian at its mode, tanh(mu), exactly what
+ * eps = 0 gives; head 1: the deterministic actor), predict()'s post-processing (`squashed` 1: low + 0.5 (a + 1)(high - low), 0: clip into
+ * [low, high]; core/common/policies.py:379-386), the env step, the episode accounting and the PCG64 reset draw of an env whose episode
+ * ended. Workgroups exchange nothing; the launch writes no control word.
+ *   env_obs [N][obs_dim] i/o, step_count int32[N] i/o, pcg_state [N][4] i/o, static_init double[N][4 per train] i/o or NULL (as in
+ *   cstr_collect_step_f32); act_low / act_high [act_dim]: HOST pointers
+ *   targets int32[N]: HOST pointer (validated before anything is enqueued, then copied into ep_done on `stream`, which is why this entry
+ *                     point is not graph-capturable from pageable memory): episodes wanted per env, 0 allowed. The copy is asynchronous:
+ *                     the caller keeps the array alive and unmodified until `stream` has passed it (e.g. until it has read ep_done back)
+ *   max_vec_steps: bound of the loop over vec-steps whatever the data does; the caller passes max(targets) * coef->max_steps, which a
+ *                  correct run never reaches (every episode is truncated by max_steps)
+ *   ep_return double[N][ep_stride], ep_len int32[N][ep_stride] with ep_stride = max(targets): episode j of env i in slot [i][j] -- the f64
+ *                  sum of the f32 step rewards and the step count; slots at and beyond targets[i] are not written (both may be NULL
+ *                  when every target is 0)
+ *   ep_done int32[N]: episodes counted; ep_done[i] < targets[i] after the launch means max_vec_steps cut the run short (the caller's error)
+ * For the counted episodes ep_return / ep_len / ep_done and pcg_state are bit-identical to the step-by-step launches:
+ * cstr_policy_rows_fwd_f32 on the same net (head 0: eps = 0), the post-processing, cstr_vec_step_f32 with reset observations from
+ * cstr_reset_draw_f32. An env stops once it has met its target: its state after its last counted episode (the reset draw behind that
+ * episode included) is what the launch leaves -- the host loop keeps stepping finished envs until all are done, this launch does not.
+ * CSTR_E_UNSUPPORTED: (obs_dim, net->act_dim) not a layout, unknown integrator, a network shape cstr_policy_rows_fwd_f32 does not take
+ * or more than 64 KB of LDS; CSTR_E_BADARG: NULL pointers, n_envs <= 0, a negative target, max_vec_steps <= 0, net->k0 != obs_dim,
+ * misaligned rows, outputs overlapping inputs or each other. */
+int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs,
+                           int32_t *step_count, uint64_t *pcg_state, double *static_init, int squashed, const float *act_low,
+                           const float *act_high, const int32_t *targets, int64_t n_envs, int64_t max_vec_steps, double *ep_return,
+                           int32_t *ep_len, int32_t *ep_done, cstr_stream_t stream);
+
 /* TD3 / MADDPG target policy smoothing (core/td3/td3.py:167-173; core/maddpg/maddpg.py:131-142) in one launch:
  * noise = clamp(N(0, sigma), -clip, clip); out = clamp(action + noise, -1, 1). action [B][A] contiguous (the target
  * actor's output); `noise` [B][A] (already scaled by sigma) is read when rng_ctl is NULL, otherwise sigma * N(0,1) is drawn

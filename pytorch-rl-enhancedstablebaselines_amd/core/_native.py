@@ -37,6 +37,7 @@ SYMBOLS = (
     "cstr_diag_gaussian_act_f32", "cstr_rollout_add_f32", "cstr_gae_f32", "cstr_ppo_gather_f32", "cstr_ppo_loss_f32", "cstr_grad_clip_f32",
     "cstr_a2c_loss_f32", "cstr_rmsprop_f32",
     "cstr_mt19937_rand_flag_f64", "cstr_dqn_act_f32", "cstr_dqn_loss_f32",
+    "cstr_eval_episodes_f32",
 )
 
 

@@ -9,13 +9,19 @@ returns = float64 sums of the float32 step rewards, episodes appended in sub-env
   * host loop -- any object with `predict(observations, state=, episode_start=, deterministic=)` (evaluation.py:88-93) and any
     `VecEnv` of this package, NumPy in / NumPy out like the reference; also taken when a `callback` wants `locals()` per
     (step, env) (evaluation.py:104-105).
+
+`evaluate_policy_fused` (specific to this package) runs the same evaluation as ONE launch, cstr_eval_episodes_f32: every env's
+episodes are walked inside the kernel and the host reads three arrays back. It covers deterministic evaluation of a two-hidden-layer
+actor on a bare `CSTRVecEnv`; `supported()` tells whether it applies.
 """
 import warnings
 from typing import Callable, Optional, Tuple, Union
 
 import numpy as np
 import torch as th
+from torch import nn
 
+from core.common import hip_ops
 from core.common.vec_env import CSTRVecEnv
 from core.common.vec_env.base_vec_env import VecEnv
 
@@ -112,6 +118,137 @@ def evaluate_policy(model, env, n_eval_episodes: int = 10, deterministic: bool =
         rets, lens = _evaluate_on_device(policy, env, targets, deterministic)
     else:
         rets, lens = _evaluate_on_host(model, env, targets, deterministic, render, callback)
+    mean_reward, std_reward = np.mean(rets), np.std(rets)
+    if reward_threshold is not None:
+        assert mean_reward > reward_threshold, "Mean reward below threshold: " f"{mean_reward:.2f} < {reward_threshold:.2f}"
+    if return_episode_rewards:
+        return rets, lens
+    return mean_reward, std_reward
+
+
+# ---- the whole evaluation in one launch ---------------------------------------------------------------------------------
+
+# What `EvalCallback(fused=None)` picks where `supported()` holds. Decided by measurement (tools/eval_probe.py, profiles/eval_probe.txt,
+# DESIGN.md 5): the launch is the default because it is faster than the device loop at both probed env counts (4.3 ms against 98.5 ms
+# with 16 evaluation envs, 5.6 ms against 93.4 ms with 256).
+FUSED_BY_DEFAULT = True
+
+_ACTS = {nn.ReLU: 1, nn.Tanh: 2}
+
+
+def _two_layer_mlp(seq):
+    """(l1, l2, act) of nn.Sequential(Linear, act, Linear, act) with one activation class, else None"""
+    mods = list(seq)
+    if len(mods) != 4 or not (isinstance(mods[0], nn.Linear) and isinstance(mods[2], nn.Linear)):
+        return None
+    if type(mods[1]) not in _ACTS or type(mods[1]) is not type(mods[3]):
+        return None
+    return mods[0], mods[2], _ACTS[type(mods[1])]
+
+
+def _fused_operands(policy) -> Optional[dict]:
+    """The policy's deterministic actor as operands of hip_ops.eval_episodes (cstr_policy_mlp_t), or None if that struct cannot
+    describe it: SAC's actor without gSDE (head 0 at its mode), TD3's / DDPG's actor (head 1, tanh), `ActorCriticPolicy` with a
+    two-layer `policy_net` and a linear `action_net` (head 1, no output activation, clipped instead of un-scaled)."""
+    from core.common.policies import ActorCriticPolicy
+    from core.common.torch_layers import FlattenExtractor
+
+    actor = getattr(policy, "actor", None)
+    if isinstance(policy, ActorCriticPolicy):
+        if getattr(policy, "use_sde", False) or not isinstance(policy.features_extractor, FlattenExtractor):
+            return None
+        net = _two_layer_mlp(policy.mlp_extractor.policy_net)
+        if net is None or not isinstance(policy.action_net, nn.Linear):
+            return None
+        l1, l2, act = net
+        return dict(layers=(l1, l2), w3=policy.action_net.weight, b3=policy.action_net.bias, act=act, head=1, out_act=0)
+    if not isinstance(actor, nn.Module) or not isinstance(getattr(actor, "features_extractor", None), FlattenExtractor):
+        return None
+    if isinstance(getattr(actor, "latent_pi", None), nn.Sequential):  # SAC
+        if getattr(actor, "use_sde", False) or not isinstance(actor.mu, nn.Linear) or not isinstance(actor.log_std, nn.Linear):
+            return None
+        net = _two_layer_mlp(actor.latent_pi)
+        if net is None:
+            return None
+        l1, l2, act = net
+        return dict(layers=(l1, l2), w3=th.cat((actor.mu.weight, actor.log_std.weight), dim=0), b3=th.cat((actor.mu.bias, actor.log_std.bias), dim=0),
+                    act=act, head=0, out_act=0)
+    if isinstance(getattr(actor, "mu", None), nn.Sequential):  # TD3 / DDPG: create_mlp(..., squash_output=True)
+        mods = list(actor.mu)
+        if len(mods) != 6 or not isinstance(mods[4], nn.Linear) or not isinstance(mods[5], nn.Tanh):
+            return None
+        net = _two_layer_mlp(nn.Sequential(*mods[:4]))
+        if net is None:
+            return None
+        l1, l2, act = net
+        return dict(layers=(l1, l2), w3=mods[4].weight, b3=mods[4].bias, act=act, head=1, out_act=2)
+    return None
+
+
+def _why_not_fused(model, env, deterministic: bool) -> Optional[str]:
+    if not deterministic:
+        return "stochastic evaluation (deterministic=False)"
+    if not isinstance(env, CSTRVecEnv):
+        return "the evaluation env must be a bare CSTRVecEnv (no VecNormalize or other wrapper)"
+    if env.discrete_actions is not None:
+        return "the Discrete valve face (DQN)"
+    policy = getattr(model, "policy", model)
+    if not isinstance(policy, nn.Module) or not hasattr(policy, "squash_output") or not hasattr(getattr(policy, "action_space", None), "low"):
+        return f"{type(policy).__name__} is not a single-agent policy over a Box action space"
+    ops = _fused_operands(policy)
+    if ops is None:
+        return f"{type(policy).__name__}: the actor is not a two-hidden-layer MLP that cstr_policy_mlp_t describes (gSDE, other depths, BCQ, MADDPG)"
+    l1, l2 = ops["layers"]
+    if not hip_ops.eval_episodes_supported(l1.in_features, l1.out_features, l2.out_features, ops["w3"].shape[0], ops["head"], env.act_dim):
+        return f"network shape ({l1.in_features}, {l1.out_features}, {l2.out_features}, {ops['w3'].shape[0]}) on a ({env.obs_dim}, {env.act_dim}) env"
+    if l1.in_features != env.obs_dim or l1.weight.device != env.device:
+        return "policy and env disagree on the observation width or the device"
+    return None
+
+
+def supported(model, env, deterministic: bool = True) -> bool:
+    """Whether `evaluate_policy_fused` applies to this model / policy, env and mode."""
+    return _why_not_fused(model, env, deterministic) is None
+
+
+def _aligned(t: th.Tensor) -> th.Tensor:
+    t = t.detach().contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def evaluate_policy_fused(model, env, n_eval_episodes: int = 10, deterministic: bool = True, reward_threshold: Optional[float] = None,
+                          return_episode_rewards: bool = False, warn: bool = True) -> Union[Tuple[float, float], Tuple[list, list]]:
+    """`evaluate_policy` as ONE launch (hip_ops.eval_episodes): same arguments minus `render` / `callback`, same return values, the
+    episode lists in the reference's order -- sorted by (vec-step at which the episode ended, env index). Raises ValueError where
+    `supported()` is False."""
+    why = _why_not_fused(model, env, deterministic)
+    if why is not None:
+        raise ValueError(f"evaluate_policy_fused does not cover {why}; use evaluate_policy")
+    if warn:
+        warnings.warn(
+            "Evaluation environment is not wrapped with a ``Monitor`` wrapper. "
+            "This may result in reporting modified episode lengths and rewards, if other wrappers happen to modify these. "
+            "Consider wrapping environment first with ``Monitor`` wrapper.",
+            UserWarning,
+        )
+    n = env.num_envs
+    targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype="int")  # :79-82
+    policy = getattr(model, "policy", model)
+    ops = _fused_operands(policy)
+    l1, l2 = ops["layers"]
+    env.reset_device()
+    with th.no_grad(), th.cuda.device(env.device):
+        w1, w2, w3 = _aligned(l1.weight), _aligned(l2.weight), _aligned(ops["w3"])
+        b1, b2, b3 = l1.bias.detach().contiguous(), l2.bias.detach().contiguous(), ops["b3"].detach().contiguous()
+        ep_ret, ep_len, _ = hip_ops.eval_episodes(
+            w1, b1, w2, b2, w3, b3, ops["act"], ops["head"], ops["out_act"], hip_ops.policy_swizzle(w2), env.coef, env.integrator, env.obs,
+            env.step_count, env.pcg_state, policy.squash_output, np.asarray(policy.action_space.low, np.float32),
+            np.asarray(policy.action_space.high, np.float32), targets, int(targets.max()) * int(env.coef.max_steps), static_init=env.static_init)
+        ret_h, len_h = ep_ret.cpu().numpy(), ep_len.cpu().numpy()  # (the wrapper has read ep_done back and checked it against the targets)
+    # the reference appends an episode at the vec-step it ends, sub-environments in order within a vec-step (evaluation.py:99-126)
+    order = sorted((int(len_h[i, :j + 1].sum()), i, j) for i in range(n) for j in range(int(targets[i])))
+    rets = [float(ret_h[i, j]) for _, i, j in order]
+    lens = [int(len_h[i, j]) for _, i, j in order]
     mean_reward, std_reward = np.mean(rets), np.std(rets)
     if reward_threshold is not None:
         assert mean_reward > reward_threshold, "Mean reward below threshold: " f"{mean_reward:.2f} < {reward_threshold:.2f}"

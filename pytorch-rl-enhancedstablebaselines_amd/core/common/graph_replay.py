@@ -7,6 +7,7 @@ through the hooks declared at the end of the class. The mixin reads `device`, `w
 `num_timesteps`, `_total_timesteps` and `policy` of the algorithm and knows nothing about replay buffers, environments or noise.
 """
 import gc
+import math
 import os
 import sys
 import warnings
@@ -41,13 +42,16 @@ class GraphReplay:
         # one-GPU run the launch structure of a data-parallel one (a boundary where each all-reduce would be)
         self._graph_collectives: Optional[bool] = None
         self._force_segment_boundaries = False
+        self._graph_callback: Optional[BaseCallback] = None  # the callback of the iteration being decided (bounds the unroll)
 
     def enable_graph_capture(self, enabled: bool = True, unroll: Optional[int] = None) -> None:
         """Replay the steady-state iteration (actor forward, fused collect, `gradient_steps` gradient steps) from a
         captured hipGraph: ~250 launches become one host call. Every per-call control word the kernels need (ring
         position, Adam step, MT19937 stream, learning rate, env / RNG state) lives in HBM, so a replay is exact.
-        Falls back to the eager path whenever the iteration is not capturable (warm-up, callbacks, host-side action noise,
-        episodic train_freq).
+        Falls back to the eager path whenever the iteration is not capturable (warm-up, host-side action noise, episodic
+        train_freq, a callback that has to see every step). A callback that knows its next event (`calls_until_event()`: the
+        callbacks of core/common/callbacks.py) lets the iterations in between replay; the iteration that contains the event runs
+        eagerly with the callback, so the hook fires where it always did.
 
         `unroll` (default 1, env CSTR_GRAPH_UNROLL): consecutive iterations recorded into ONE graph -- the ~10 us the GPU
         idles between two graph launches is paid once per `unroll` iterations. Used on one GPU, and data-parallel when the
@@ -73,11 +77,27 @@ class GraphReplay:
     def _learn_iteration(self, callback: BaseCallback, log_interval: Optional[int]) -> bool:
         """One iteration of learn() (False: the callback ends training): replayed from a captured hipGraph when it is eligible (same
         launches, same order, one host call), launched eagerly otherwise."""
+        self._graph_callback = callback
         if self._graph_enabled and self._graph_eligible(callback):
             self._graph_iteration(log_interval, callback)
             return True
         self._eager_iterations += 1
         return self._eager_iteration(callback, log_interval)
+
+    def _graph_calls_per_iteration(self) -> int:
+        """`callback.on_step()` calls one body stands for: its vec-steps."""
+        return max(self._graph_steps_per_iteration() // max(self.n_envs, 1), 1)
+
+    def _graph_skippable_calls(self, callback: Optional[BaseCallback]) -> float:
+        """How many coming `on_step()` calls the callback declares eventless (inf: all of them; 0: it has to see every step)."""
+        if callback is None or getattr(callback, "is_noop", False):
+            return math.inf
+        k = callback.calls_until_event()
+        return 0 if k is None else k - 1
+
+    def _callback_allows_replay(self, callback: BaseCallback) -> bool:
+        """The coming iteration may run without its callback: a no-op callback, or one whose next event lies behind the iteration."""
+        return self._graph_skippable_calls(callback) >= self._graph_calls_per_iteration()
 
     def _graph_unroll_now(self) -> int:
         u = self.graph_unroll
@@ -86,6 +106,10 @@ class GraphReplay:
         if self._grads_need_allreduce() and not self._collectives_in_graph():
             return 1  # data-parallel with the collectives BETWEEN graph segments: one iteration per replay list
         remaining = (self._total_timesteps - self.num_timesteps) // self._graph_steps_per_iteration()
+        # ... and the callback's next event: the bodies of one graph must all lie in front of it
+        skippable = self._graph_skippable_calls(self._graph_callback)
+        if skippable != math.inf:
+            remaining = min(remaining, int(skippable) // self._graph_calls_per_iteration())
         while u > 1 and remaining < u:  # the tail of a run: the largest of u, u / 2, u / 4, ... that still fits
             u //= 2
         return max(u, 1)
@@ -111,6 +135,7 @@ class GraphReplay:
                 self._graph_warm[key] = warm + 1
                 self._eager_iterations += 1
                 self._graph_host_bookkeeping(log_interval)
+                self._skip_callback_calls(callback, 1)
                 return
             self._graph_host_pre()
             try:
@@ -127,6 +152,12 @@ class GraphReplay:
         self._graph_replays += unroll
         for _ in range(unroll):
             self._graph_host_bookkeeping(log_interval)
+        self._skip_callback_calls(callback, unroll)
+
+    def _skip_callback_calls(self, callback: Optional[BaseCallback], bodies: int) -> None:
+        """`bodies` iterations ran on the device without their callback (which had declared them eventless): count them."""
+        if callback is not None and not getattr(callback, "is_noop", False):
+            callback.skip_calls(bodies * self._graph_calls_per_iteration())
 
     def _noop_callback(self) -> BaseCallback:
         cb = to_callback(None)

@@ -523,6 +523,76 @@ def policy_rows_fwd(x, w1, b1, w2, b2, w3, b3, act: int, head: int, out_act: int
     return action
 
 
+EVAL_LDS_BYTES = 64 * 1024
+
+
+def eval_episodes_supported(k0: int, h1: int, h2: int, n_out: int, head: int, act_dim: int) -> bool:
+    """cstr_eval_episodes_f32 takes the network shapes of cstr_policy_rows_fwd_f32 on a CSTR layout's observation rows."""
+    lds = 4 * (16 * (16 * -(-h1 // 16) + 4 + 16 * -(-h2 // 16) + 4) + 8 * 16 * 8 + 2 * 16 * 8)
+    return ((k0, act_dim) in LAYOUTS and n_out == (2 * act_dim if head == 0 else act_dim) and policy_rows_supported(k0, h1, h2, n_out)
+            and lds <= EVAL_LDS_BYTES)
+
+
+def eval_episodes(w1, b1, w2, b2, w3, b3, act: int, head: int, out_act: int, w2_swz, coef, integrator: str, env_obs, step_count, pcg_state,
+                  squashed: bool, act_low, act_high, targets, max_vec_steps: int, static_init=None):
+    """Whole evaluation episodes in ONE launch (cstr_eval_episodes_f32): env i runs `targets[i]` episodes with the policy network's
+    deterministic action (head 0: the squashed Gaussian's mode, head 1: the deterministic actor) from the state in `env_obs` /
+    `step_count` / `pcg_state`, which the launch advances. `targets`: a host sequence of non-negative ints. Returns
+    (ep_return float64 [N, max(targets)], ep_len int32 [N, max(targets)], ep_done int32 [N]) in HBM; slots at and beyond targets[i]
+    keep the value the buffers were allocated with (zero). Raises RuntimeError if `max_vec_steps` ended the launch before every env
+    had met its target (ep_done < targets)."""
+    import numpy as np
+
+    n, d = env_obs.shape
+    h1, h2, n_out = w1.shape[0], w2.shape[0], w3.shape[0]
+    a = n_out // 2 if head == 0 else n_out
+    if (d, a) not in LAYOUTS:
+        raise ValueError(f"(obs_dim, act_dim) = {(d, a)} is not a CSTR layout {LAYOUTS}")
+    _chk(env_obs, "env_obs", (n, d), th.float32), _chk(step_count, "step_count", (n,), th.int32)
+    _chk(pcg_state, "pcg_state", (n, nv.PCG_STATE_WORDS), th.int64)
+    _opt(static_init, "static_init", (n, 8 if a == 4 else 4), th.float64)
+    _chk(w1, "w1", (h1, d), th.float32), _chk(b1, "b1", (h1,), th.float32), _chk(w2, "w2", (h2, h1), th.float32)
+    _chk(b2, "b2", (h2,), th.float32), _chk(w3, "w3", (n_out, h2), th.float32), _chk(b3, "b3", (n_out,), th.float32)
+    if w2_swz is not None:
+        _chk(w2_swz, "w2_swz", (swizzled_numel(h2, h1),), th.float32)
+    if len(act_low) != a or len(act_high) != a:
+        raise ValueError(f"act_low/act_high need {a} entries")
+    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32))
+    if tg.shape != (n,):
+        raise ValueError(f"targets: shape {tg.shape}, expected {(n,)}")
+    if tg.min() < 0:
+        raise ValueError("targets must be non-negative")
+    stride = int(tg.max())
+    ep_return = th.zeros(n, stride, dtype=th.float64, device=env_obs.device)
+    ep_len = th.zeros(n, stride, dtype=th.int32, device=env_obs.device)
+    ep_done = th.zeros(n, dtype=th.int32, device=env_obs.device)
+    eval_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, coef, integrator, env_obs, step_count, pcg_state, squashed,
+                       act_low, act_high, tg, max_vec_steps, ep_return, ep_len, ep_done, static_init)
+    short = (ep_done.cpu().numpy() < tg).nonzero()[0]  # the one read-back this wrapper does: a run cut short must not pass for a result
+    if short.size:
+        raise RuntimeError(f"cstr_eval_episodes_f32: max_vec_steps={int(max_vec_steps)} ended the launch before envs {short.tolist()} had "
+                           f"run their episodes (counted {ep_done.cpu().numpy()[short].tolist()}, wanted {tg[short].tolist()})")
+    return ep_return, ep_len, ep_done
+
+
+def eval_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, coef, integrator, env_obs, step_count, pcg_state, squashed,
+                       act_low, act_high, targets, max_vec_steps, ep_return, ep_len, ep_done, static_init=None):
+    """`eval_episodes` into caller-owned result buffers; nothing is checked beyond what the entry point itself checks. `targets`: a
+    contiguous int32 NumPy array that the CALLER keeps alive and unmodified until the stream has passed the launch (the entry point
+    copies it to the device asynchronously): hold a reference until one of the results has been read back."""
+    n, d = env_obs.shape
+    n_out = w3.shape[0]
+    a = n_out // 2 if head == 0 else n_out
+    lo = (C.c_float * a)(*[float(v) for v in act_low])
+    hi = (C.c_float * a)(*[float(v) for v in act_high])
+    net = nv.PolicyMlp(d, w1.shape[0], w2.shape[0], a, act, head, out_act, 0, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                       w3.data_ptr(), b3.data_ptr(), None if w2_swz is None else w2_swz.data_ptr())
+    check(nv.lib().cstr_eval_episodes_f32(C.byref(net), C.byref(coef), C.c_int(INTEGRATORS[integrator]), C.c_int(d), ptr(env_obs),
+                                          ptr(step_count), ptr(pcg_state), ptr(static_init), C.c_int(1 if squashed else 0), lo, hi,
+                                          targets.ctypes.data_as(C.c_void_p), C.c_int64(n), C.c_int64(int(max_vec_steps)), ptr(ep_return),
+                                          ptr(ep_len), ptr(ep_done), stream_ptr()), "cstr_eval_episodes_f32")
+
+
 def rollout_step_supported(k0: int, h1: int, h2: int, n_out: int, has_swizzled_w2: bool) -> bool:
     """cstr_rollout_step_f32 covers the pipelined policy kernel with a one-chunk first layer (see the header)."""
     return has_swizzled_w2 and k0 <= 16 and k0 % 4 == 0 and h1 <= 512 and h2 <= 512 and policy_rows_supported(k0, h1, h2, n_out)

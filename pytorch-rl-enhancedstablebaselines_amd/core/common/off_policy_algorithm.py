@@ -201,7 +201,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
     def _graph_eligible(self, callback: BaseCallback) -> bool:
         from core.common.noise import DeviceNormalActionNoise, LegacyStreamNormalActionNoise, LegacyStreamOUActionNoise
 
-        return (self._fast_path() and getattr(callback, "is_noop", False)
+        return (self._fast_path() and self._callback_allows_replay(callback)
                 and (self.action_noise is None
                      or isinstance(self.action_noise, (DeviceNormalActionNoise, LegacyStreamNormalActionNoise, LegacyStreamOUActionNoise)))
                 and self.train_freq == TrainFreq(1, TrainFrequencyUnit.STEP)

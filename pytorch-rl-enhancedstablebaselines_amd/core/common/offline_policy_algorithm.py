@@ -170,7 +170,7 @@ class OfflineAlgorithm(OffPolicyAlgorithm):
 
     # ---- hipGraph hooks (core/common/graph_replay.py): one replay = one iteration's gradient steps, no rollout ------------
     def _graph_eligible(self, callback: BaseCallback) -> bool:
-        return (type(self.replay_buffer) is ReplayBuffer and getattr(callback, "is_noop", False) and self.gradient_steps >= 1
+        return (type(self.replay_buffer) is ReplayBuffer and self._callback_allows_replay(callback) and self.gradient_steps >= 1
                 and getattr(self, "fused_learner", False) and not getattr(self, "debug_capture", False))
 
     def _graph_cache_key(self, unroll: int) -> tuple:

@@ -321,7 +321,7 @@ class DQN(OffPolicyAlgorithm):
 
     def _graph_eligible(self, callback) -> bool:
         tf = self.train_freq
-        return (self._fast_path() and getattr(callback, "is_noop", False) and tf.unit == TrainFrequencyUnit.STEP
+        return (self._fast_path() and self._callback_allows_replay(callback) and tf.unit == TrainFrequencyUnit.STEP
                 and self.gradient_steps >= 1 and self.num_timesteps >= self.learning_starts and not self.debug_capture
                 and not self.batch_queue and not self.uniform_queue and tf.frequency * max(self.graph_unroll, 1) <= EPS_SLOTS)
 

@@ -1,0 +1,299 @@
+// cstr_eval.hip -- whole evaluation episodes in ONE launch for gfx950 (cstr_eval_episodes_f32).
+//
+// evaluate_policy (core/common/evaluation.py:11-140) is a host loop: per vec-step the actor's launch, the env step, a few element-wise
+// ops and two flags read back. Here a workgroup owns 16 envs and walks their vec-steps inside the launch:
+//   policy network on the 16 observation rows (policy_layer of cstr_policy_device.h, the stages of cstr_policy_rows_fwd_f32: layer 1
+//   and layer 2 on the f32 matrix cores, W2 streamed from L2 every step -- 256 x 256 f32 is 256 KB and does not fit in LDS -- as rows or
+//   from the tile-major copy when the caller has one), the head in the summation order of the launch it stands for (below), predict()'s
+//   post-processing, the env step (cstr_env_device.h), the episode accounting and the PCG64 reset draw of an env whose episode ended.
+// Observations, activations and the head's partial sums live in LDS for the whole launch; a lane of wave 0 per env carries the
+// running return (f64 sum of the f32 step rewards), the length and the episode count. Workgroups never exchange anything: no ticket, no
+// hand-over, results leave through ordinary stores.
+//
+// Bit-level contract: for the counted episodes, ep_return / ep_len / ep_done and the env's pcg_state equal what the step-by-step
+// launches give: cstr_policy_rows_fwd_f32 (head 0: with eps = 0, i.e. the squashed Gaussian at its mode), predict()'s post-processing,
+// cstr_vec_step_f32 with the reset observations of cstr_reset_draw_f32. cstr_policy_rows_fwd_f32 has two head forms with different
+// summation orders (per-lane partial dots + shuffle tree; split-K matrix-core tile when the tile-major W2 is given and the widths are
+// <= 512): this kernel runs the one that launch would run for the same cstr_policy_mlp_t.
+// An env stops when it has met its target: its state after its last counted episode (the reset draw behind that episode included) is
+// what the launch leaves; the host loop would keep stepping it until every env is done, which is NOT reproduced.
+//
+// Termination: the loop over vec-steps is bounded by max_vec_steps whatever the data does; it ends earlier once the workgroup's 16 envs
+// have met their targets.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdlib.h>
+
+#include "../../include/cstr_rl_hip.h"
+#include "cstr_device.h"
+#include "cstr_env_device.h"
+#include "cstr_policy_device.h"
+
+namespace {
+
+// k chunks of layer 2 whose operands a wave requests at once (the accumulation order does not depend on it): 8 keeps the kernel, which
+// also holds the env lanes' episode state, inside its register budget
+constexpr int EVAL_UNROLL = 8;
+constexpr int EVAL_MAX_WIDTH_V2 = 512;  // widths up to which cstr_policy_rows_fwd_f32 takes its pipelined kernel (split-K head)
+
+struct EvalArgs {
+    const float *w1, *b1, *w2, *b2, *w3, *b3, *w2s;
+    int k0, h1, h2, act_dim, out_act, split_k_head;
+    cstr_coef_t k;
+    float *env_obs; int32_t *step_count; uint64_t *pcg; double *static_init;
+    int squashed, integrator; ActBounds ab;
+    double *ep_return; int32_t *ep_len, *ep_done;  // ep_done: targets on entry, episodes counted on exit
+    int64_t ep_stride, n, max_vec_steps;
+};
+
+template <int ACT, int HEAD, int L>
+__global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const EvalArgs a)
+{
+    constexpr int D = Lay<L>::D, A = Lay<L>::A, XS = 8;  // XS: row stride of the observation image
+    extern __shared__ float eval_lds[];
+    __shared__ int go_s;
+    const int H1 = a.h1, H2 = a.h2, kc1 = (H1 + 15) >> 4, kc2 = (H2 + 15) >> 4, S1 = 16 * kc1 + 4, S2 = 16 * kc2 + 4;
+    float *h1s = eval_lds, *h2s = h1s + POLICY_ROWS * S1, *part = h2s + POLICY_ROWS * S2;  // part [8 waves][16 rows][8]
+    float *ps = part + POLICY_WAVES * POLICY_ROWS * 8, *xs = ps + POLICY_ROWS * 8;         // head outputs [16][8], observations [16][XS]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, h = lane >> 4;
+    const int64_t m0 = (int64_t)blockIdx.x * POLICY_ROWS;
+    const int n_out = HEAD == 0 ? 2 * A : A;
+
+    // the env lanes: lane e < 16 of wave 0 owns env m0 + e for the whole launch
+    const int64_t env = m0 + lane;
+    const bool env_lane = wave == 0 && lane < POLICY_ROWS && env < a.n;
+    int32_t target = 0, count = 0, cur_len = 0, st = 0;
+    double cur_ret = 0.0;
+    if (tid < POLICY_ROWS * XS) xs[tid] = 0.0f;  // rows past n_envs and columns past obs_dim stay zero
+    {   // zero the k padding of both activation images (widths that are not multiples of 16: the split-K head reads whole chunks)
+        const int p1 = 16 * kc1 - H1, p2 = 16 * kc2 - H2;
+        if (p1 > 0 && tid < POLICY_ROWS * p1) h1s[(tid / max(p1, 1)) * S1 + H1 + tid % max(p1, 1)] = 0.0f;
+        if (p2 > 0 && tid < POLICY_ROWS * p2) h2s[(tid / max(p2, 1)) * S2 + H2 + tid % max(p2, 1)] = 0.0f;
+    }
+    __syncthreads();
+    if (env_lane) {
+        float o[2][4];
+        load_obs<L>(a.env_obs, env, o);
+#pragma unroll
+        for (int j = 0; j < D; ++j) xs[lane * XS + j] = o[j >> 2][j & 3];
+        st = a.step_count[env];
+        target = a.ep_done[env];
+    }
+    if (wave == 0) {
+        const unsigned long long any = __ballot(env_lane && count < target);
+        if (lane == 0) go_s = any != 0ull;
+    }
+    __syncthreads();
+
+    for (int64_t it = 0; it < a.max_vec_steps; ++it) {
+        if (!go_s) break;  // workgroup-uniform: written before the barrier that ends the previous trip
+        // ---- the policy network on the 16 observation rows (the stages of cstr_policy_rows_fwd_f32) ----
+        policy_layer<ACT, false, true, false, 1>(xs, XS, true, a.k0, a.w1, a.b1, H1, h1s, S1);  // k0 <= 8: one k chunk
+        __syncthreads();
+        if (a.w2s) policy_layer<ACT, false, true, true, EVAL_UNROLL>(h1s, S1, true, H1, a.w2s, a.b2, H2, h2s, S2);
+        else policy_layer<ACT, false, true, false, EVAL_UNROLL>(h1s, S1, true, H1, a.w2, a.b2, H2, h2s, S2);
+        __syncthreads();
+        if (a.split_k_head) {
+            // ONE 16 x 16 tile (rows x outputs, outputs >= n_out are zero columns), K split over the waves: wave w takes the k chunks
+            // w, w + 8, ...; the partial tiles meet in LDS and are added in wave order
+            f32x4 p0 = {0.0f, 0.0f, 0.0f, 0.0f}, p1 = p0;
+            const float *hr = h2s + r * S2 + 4 * h;
+            const float *w3r = a.w3 + (int64_t)min(r, n_out - 1) * H2;
+            for (int c = wave; c < kc2; c += POLICY_WAVES) {
+                const float4 wv = load_k4_clamped<true>(w3r, 16 * c + 4 * h, H2, r < n_out);
+                const float4 av = *reinterpret_cast<const float4 *>(hr + 16 * c);
+                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, wv.x, p0, 0, 0, 0);
+                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, wv.y, p1, 0, 0, 0);
+                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, wv.z, p0, 0, 0, 0);
+                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, wv.w, p1, 0, 0, 0);
+            }
+            p0 += p1;
+            if (r < 8) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) part[(wave * POLICY_ROWS + 4 * h + e) * 8 + r] = p0[e];
+            }
+            __syncthreads();
+            if (tid < POLICY_ROWS * 8 && (tid & 7) < n_out) {  // thread = 8 * row + output slot
+                float sum = 0.0f;
+#pragma unroll
+                for (int w = 0; w < POLICY_WAVES; ++w) sum += part[(w * POLICY_ROWS + (tid >> 3)) * 8 + (tid & 7)];
+                ps[tid] = sum + a.b3[tid & 7];
+            }
+        } else {
+            // per-lane partial dots over the row's h2 values, two rows per wave, then a shuffle tree
+            constexpr int RPW = POLICY_ROWS / POLICY_WAVES;
+            float p[RPW][2 * CSTR_MAX_HEAD_ACT];
+#pragma unroll
+            for (int q = 0; q < RPW; ++q)
+#pragma unroll
+                for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) p[q][j] = 0.0f;
+            for (int c = lane * 4; c < H2; c += 256) {
+                float4 hv[RPW];
+#pragma unroll
+                for (int q = 0; q < RPW; ++q) hv[q] = *reinterpret_cast<const float4 *>(h2s + (wave + q * POLICY_WAVES) * S2 + c);
+#pragma unroll
+                for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
+                    if (j >= n_out) break;
+                    const float4 wv = *reinterpret_cast<const float4 *>(a.w3 + (int64_t)j * H2 + c);
+#pragma unroll
+                    for (int q = 0; q < RPW; ++q) p[q][j] += (hv[q].x * wv.x + hv[q].y * wv.y) + (hv[q].z * wv.z + hv[q].w * wv.w);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < RPW; ++q) {
+#pragma unroll
+                for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
+                    if (j >= n_out) break;
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) p[q][j] += __shfl_xor(p[q][j], o, 64);
+                    if (lane == 0) ps[(wave + q * POLICY_WAVES) * 8 + j] = p[q][j] + a.b3[j];
+                }
+            }
+        }
+        __syncthreads();
+
+        // ---- predict()'s post-processing, env step, episode accounting, reset draw: a lane per env ----
+        const bool active = env_lane && count < target;
+        if (active) {
+            const float *pr = ps + lane * 8;
+            float ea[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+                float v;
+                if (HEAD == 1) {
+                    v = pr[j];
+                    if (a.out_act == ACT_RELU) v = fmaxf(v, 0.0f);
+                    if (a.out_act == ACT_TANH) v = tanhf(v);
+                } else {  // the squashed Gaussian at its mode: what eps = 0 gives
+                    const float mu = pr[j], raw = pr[A + j];
+                    const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
+                    const float sd = expf(ls);
+                    const float u = mu + sd * 0.0f;
+                    v = tanhf(u);
+                }
+                const float lo = a.ab.lo[j], hi = a.ab.hi[j];
+                if (a.squashed & 1) v = lo + (0.5f * (v + 1.0f) * (hi - lo));  // unscale_action (policies.py:375, :413)
+                else v = (v != v) ? v : fminf(fmaxf(v, lo), hi);                // np.clip (policies.py:386); NaN passes through
+                ea[j] = v;
+            }
+            float o[2][4], on[2][4], rew;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o[j >> 2][j & 3] = xs[lane * XS + j];
+            const bool done = a.integrator == CSTR_INTEGRATOR_EULER ? env_step_lane<L, CSTR_INTEGRATOR_EULER>(a.k, o, ea, st, on, rew)
+                                                                    : env_step_lane<L, CSTR_INTEGRATOR_RK4>(a.k, o, ea, st, on, rew);
+            cur_ret += (double)rew;  // current_rewards: float64 (evaluation.py:84, :97)
+            cur_len += 1;
+            if (done) {
+                a.ep_return[env * a.ep_stride + count] = cur_ret;
+                a.ep_len[env * a.ep_stride + count] = cur_len;
+                count += 1;
+                cur_ret = 0.0;
+                cur_len = 0;
+                uint64_t pst[4];  // auto-reset (dummy_vec_env.py:68-72)
+                load_pcg(a.pcg, env, pst);
+                reset_draw_env<L>(a.k, pst, a.static_init, env, on);
+                *reinterpret_cast<ulonglong2 *>(a.pcg + 4 * env) = make_ulonglong2(pst[0], pst[1]);
+                st = 0;
+            }
+#pragma unroll
+            for (int j = 0; j < D; ++j) xs[lane * XS + j] = on[j >> 2][j & 3];
+        }
+        if (wave == 0) {
+            const unsigned long long any = __ballot(env_lane && count < target);
+            if (lane == 0) go_s = any != 0ull;
+        }
+        __syncthreads();
+    }
+
+    if (env_lane) {
+        float o[2][4];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j >> 2][j & 3] = xs[lane * XS + j];
+        store_obs<L>(a.env_obs, env, o);
+        a.step_count[env] = st;
+        a.ep_done[env] = count;
+    }
+}
+
+struct Span { const char *lo, *hi; };
+
+static inline Span span_of(const void *p, int64_t bytes) { return Span{static_cast<const char *>(p), static_cast<const char *>(p) + bytes}; }
+static inline bool overlaps(const Span &x, const Span &y) { return x.lo && y.lo && x.lo < y.hi && y.lo < x.hi; }
+
+}  // namespace
+
+static size_t eval_lds_bytes(const cstr_policy_mlp_t &n)
+{
+    const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
+    return (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 2 * POLICY_ROWS * 8) * sizeof(float);
+}
+
+extern "C" int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs,
+                                      int32_t *step_count, uint64_t *pcg_state, double *static_init, int squashed, const float *act_low,
+                                      const float *act_high, const int32_t *targets, int64_t n_envs, int64_t max_vec_steps,
+                                      double *ep_return, int32_t *ep_len, int32_t *ep_done, cstr_stream_t stream)
+{
+    if (!net || !coef || !env_obs || !step_count || !pcg_state || !act_low || !act_high || !targets || !ep_done) return CSTR_E_BADARG;
+    if (n_envs <= 0 || max_vec_steps <= 0 || (squashed & ~1)) return CSTR_E_BADARG;
+    const cstr_policy_mlp_t &n = *net;
+    if (!n.w1 || !n.b1 || !n.w2 || !n.b2 || !n.w3 || !n.b3 || n.k0 <= 0 || n.h1 <= 0 || n.h2 <= 0 || n.act_dim <= 0 || n.reserved) return CSTR_E_BADARG;
+    const int lay = layout_of(obs_dim, n.act_dim);
+    if (lay < 0 || (integrator != CSTR_INTEGRATOR_EULER && integrator != CSTR_INTEGRATOR_RK4)) return CSTR_E_UNSUPPORTED;
+    if (n.k0 != obs_dim) return CSTR_E_BADARG;  // the policy reads the env's observation rows
+    // the shapes of cstr_policy_rows_fwd_f32
+    if (n.act < 0 || n.act > 2 || n.out_act < 0 || n.out_act > 2 || n.head < 0 || n.head > 1 || (n.h1 & 3) || (n.h2 & 3) ||
+        (size_t)POLICY_ROWS * (n.h1 + 4 + n.h2 + 4) * sizeof(float) > 64 * 1024 || eval_lds_bytes(n) > 64 * 1024 ||
+        (n_envs + POLICY_ROWS - 1) / POLICY_ROWS > 0x7fffffff)
+        return CSTR_E_UNSUPPORTED;
+    if (!aligned16(env_obs) || !aligned16(pcg_state) || !aligned16(n.w1) || !aligned16(n.w2) || !aligned16(n.w3) ||
+        (n.w2_swizzled && !aligned16(n.w2_swizzled)) || !aligned8(ep_return) || (static_init && !aligned8(static_init)) ||
+        (reinterpret_cast<uintptr_t>(step_count) & 3u) || (reinterpret_cast<uintptr_t>(ep_len) & 3u) || (reinterpret_cast<uintptr_t>(ep_done) & 3u))
+        return CSTR_E_BADARG;
+    const int A = n.act_dim;
+    ActBounds ab;
+    for (int j = 0; j < 4; ++j) {
+        ab.lo[j] = j < A ? act_low[j] : -1.0f;
+        ab.hi[j] = j < A ? act_high[j] : 1.0f;
+        if (!(ab.hi[j] > ab.lo[j])) return CSTR_E_BADARG;
+    }
+    int64_t ep_stride = 0;  // targets is a HOST array (like act_low / act_high): checked here, staged into ep_done below
+    for (int64_t i = 0; i < n_envs; ++i) {
+        if (targets[i] < 0) return CSTR_E_BADARG;
+        if (targets[i] > ep_stride) ep_stride = targets[i];
+    }
+    if (ep_stride > 0 && (!ep_return || !ep_len)) return CSTR_E_BADARG;  // (no slot exists when every target is 0)
+    if (ep_stride > 0 && n_envs > INT64_MAX / (8 * ep_stride)) return CSTR_E_UNSUPPORTED;
+    {   // outputs must not overlap what the launch reads, or each other
+        const int TR = lay == 2 ? 2 : 1, n_out = (n.head == 0 ? 2 : 1) * A, kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
+        const Span outs[3] = {span_of(ep_return, 8 * n_envs * ep_stride), span_of(ep_len, 4 * n_envs * ep_stride), span_of(ep_done, 4 * n_envs)};
+        const Span ins[11] = {span_of(env_obs, 4 * n_envs * obs_dim), span_of(step_count, 4 * n_envs), span_of(pcg_state, 32 * n_envs),
+                              span_of(static_init, 32 * TR * n_envs), span_of(n.w1, 4LL * n.h1 * n.k0), span_of(n.b1, 4LL * n.h1),
+                              span_of(n.w2, 4LL * n.h2 * n.h1), span_of(n.b2, 4LL * n.h2), span_of(n.w3, 4LL * n_out * n.h2),
+                              span_of(n.b3, 4LL * n_out), span_of(n.w2_swizzled, 1024LL * kc1 * kc2)};
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 11; ++j)
+                if (overlaps(outs[i], ins[j])) return CSTR_E_BADARG;
+            for (int j = i + 1; j < 3; ++j)
+                if (overlaps(outs[i], outs[j])) return CSTR_E_BADARG;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t cp = hipMemcpyAsync(ep_done, targets, sizeof(int32_t) * (size_t)n_envs, hipMemcpyHostToDevice, s);
+    if (cp != hipSuccess) return (int)cp;
+    if (ep_stride == 0) return CSTR_OK;  // nothing to run: ep_done = targets = 0
+    static const bool force_v1 = getenv("CSTR_POLICY_V1") != nullptr;  // the development knob of cstr_policy_rows_fwd_f32: same head as that launch
+    const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
+    const size_t v2_lds = (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 4 * POLICY_ROWS * 8) * sizeof(float);
+    const bool split_k = n.w2_swizzled && n.h1 <= EVAL_MAX_WIDTH_V2 && n.h2 <= EVAL_MAX_WIDTH_V2 && v2_lds <= 64 * 1024 && !force_v1;
+    EvalArgs a = {n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, A, n.out_act, split_k ? 1 : 0, *coef,
+                  env_obs, step_count, pcg_state, static_init, squashed, integrator, ab, ep_return, ep_len, ep_done, ep_stride, n_envs, max_vec_steps};
+    const unsigned grid = (unsigned)((n_envs + POLICY_ROWS - 1) / POLICY_ROWS);
+    const size_t lds = eval_lds_bytes(n);
+#define EV3(A_, H_, L_) eval_episodes_kernel<A_, H_, L_><<<grid, 64 * POLICY_WAVES, lds, s>>>(a)
+#define EV2(A_, H_) do { if (lay == 0) EV3(A_, H_, 0); else if (lay == 1) EV3(A_, H_, 1); else EV3(A_, H_, 2); } while (0)
+    if (n.head == 0) { if (n.act == 0) EV2(0, 0); else if (n.act == 1) EV2(1, 0); else EV2(2, 0); }
+    else { if (n.act == 0) EV2(0, 1); else if (n.act == 1) EV2(1, 1); else EV2(2, 1); }
+#undef EV2
+#undef EV3
+    return (int)hipGetLastError();
+}

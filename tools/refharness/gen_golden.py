@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,init,vecenv]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,init,vecenv,callbacks]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -20,6 +20,7 @@ Reference entry points exercised (file:line in /root/reference):
   core/a2c/a2c.py:132-190                A2C.train
   core/dqn/dqn.py:168-256                DQN._on_step / train / predict
   core/common/utils.py:457-481           polyak_update
+  core/common/callbacks.py:146-680       EventCallback ... StopTrainingOnNoModelImprovement (structure only)
 """
 import argparse
 import os
@@ -1761,7 +1762,101 @@ def gen_dqn():
     _gen_dqn_wiring()
 
 
-GENS = {"a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+def gen_callbacks():
+    """The reference's training callbacks (core/common/callbacks.py:146-680) on small CPU runs of SAC over
+    DummyVecEnv([TwoSeriesCSTREnv] * N). Only STRUCTURE is written -- directory listings, evaluations.npz's timesteps / ep_lengths,
+    final counters, the timestep or evaluation count at which a stop callback ends the run -- no learned number."""
+    import contextlib
+    import io
+    import tempfile
+
+    from core.common.callbacks import (BaseCallback, CheckpointCallback, EvalCallback, EveryNTimesteps, StopTrainingOnMaxEpisodes,
+                                       StopTrainingOnNoModelImprovement, StopTrainingOnRewardThreshold)
+    from core.common.vec_env.dummy_vec_env import DummyVecEnv
+    from core.sac.sac import SAC
+    from twoseriescstr import TwoSeriesCSTREnv
+
+    def venv(n, seed):
+        v = DummyVecEnv([lambda: TwoSeriesCSTREnv() for _ in range(n)])
+        v.seed(seed)
+        return v
+
+    def sac(n, **kw):
+        kw = dict(dict(seed=0, device="cpu", batch_size=16, buffer_size=4096, learning_starts=40, policy_kwargs=dict(net_arch=[16, 16])), **kw)
+        return SAC("MlpPolicy", venv(n, 3), **kw)
+
+    def learn(model, steps, cb):
+        with contextlib.redirect_stdout(io.StringIO()):
+            model.learn(steps, callback=cb)
+
+    def names(d):
+        return np.array(sorted(os.listdir(d)))
+
+    out = {}
+    # (a) EvalCallback + CheckpointCallback: 4 envs, eval_freq 50, save_freq 60, 520 steps
+    with tempfile.TemporaryDirectory() as d:
+        ev = EvalCallback(venv(2, 7), n_eval_episodes=3, eval_freq=50, log_path=os.path.join(d, "log"), best_model_save_path=os.path.join(d, "best"),
+                          verbose=0, warn=False)
+        ck = CheckpointCallback(save_freq=60, save_path=os.path.join(d, "ck"), name_prefix="m", save_replay_buffer=True)
+        model = sac(4)
+        learn(model, 520, [ev, ck])
+        e = np.load(os.path.join(d, "log", "evaluations.npz"))
+        out.update({"a/dims": np.array([4, 2, 3, 50, 60, 520], np.int64), "a/ck_files": names(os.path.join(d, "ck")),
+                    "a/log_files": names(os.path.join(d, "log")), "a/best_files": names(os.path.join(d, "best")),
+                    "a/eval_keys": np.array(sorted(e.files)), "a/timesteps": e["timesteps"].astype(np.int64),
+                    "a/ep_lengths": e["ep_lengths"].astype(np.int64), "a/results_shape": np.array(e["results"].shape, np.int64),
+                    "a/counters": np.array([ev.n_calls, ck.n_calls, ev.num_timesteps, model.num_timesteps, model._n_updates], np.int64)})
+    # (b) StopTrainingOnMaxEpisodes(2) on 2 envs: the run ends at the step that closes the 4th episode
+    cb = StopTrainingOnMaxEpisodes(max_episodes=2)
+    model = sac(2, learning_starts=10 ** 6)
+    learn(model, 10 ** 5, cb)
+    out["b/stop"] = np.array([2, 2, cb.n_episodes, cb.n_calls, model.num_timesteps], np.int64)
+    # (c) StopTrainingOnRewardThreshold(-inf) behind an EvalCallback's new best: ends at the first evaluation
+    ev = EvalCallback(venv(2, 7), callback_on_new_best=StopTrainingOnRewardThreshold(-np.inf), n_eval_episodes=2, eval_freq=30, verbose=0, warn=False)
+    model = sac(4, learning_starts=10 ** 6)
+    learn(model, 2000, ev)
+    out["c/stop"] = np.array([4, 30, ev.n_calls, model.num_timesteps], np.int64)
+
+    # (d) StopTrainingOnNoModelImprovement(2, min_evals=1) after every evaluation, predictions from a fixed action tape (the model
+    #     never trains: learning_starts beyond the run), so the evaluation results depend on the env alone
+    class Tape:
+        def __init__(self, actions):
+            self.actions, self.t = actions, 0
+
+        def predict(self, observations, state=None, episode_start=None, deterministic=False):
+            a = self.actions[self.t % len(self.actions)].copy()
+            self.t += 1
+            return a, state
+
+    tape = np.random.default_rng(99).uniform(-1, 1, size=(257, 2, 2)).astype(np.float32)
+    stop = StopTrainingOnNoModelImprovement(max_no_improvement_evals=2, min_evals=1)
+    ev = EvalCallback(venv(2, 7), callback_after_eval=stop, n_eval_episodes=2, eval_freq=20, verbose=0, warn=False)
+    model = sac(4, learning_starts=10 ** 6)
+    tp = Tape(tape)
+    model.predict = tp.predict
+    learn(model, 10 ** 5, ev)
+    out.update({"d/tape": tape, "d/stop": np.array([4, 20, stop.n_calls, ev.n_calls, model.num_timesteps, stop.no_improvement_evals, tp.t], np.int64)})
+
+    # (e) EveryNTimesteps(100) on 4 envs and on 3 envs (100 is no multiple of 3): the timesteps at which the child is called
+    class Rec(BaseCallback):
+        def __init__(self):
+            super().__init__()
+            self.seen = []
+
+        def _on_step(self):
+            self.seen.append(self.num_timesteps)
+            return True
+
+    for n in (4, 3):
+        rec = Rec()
+        model = sac(n, learning_starts=10 ** 6)
+        learn(model, 650, EveryNTimesteps(n_steps=100, callback=rec))
+        out[f"e/fired_{n}"] = np.array(rec.seen, np.int64)
+        out[f"e/final_{n}"] = np.array([model.num_timesteps], np.int64)
+    save("callbacks_kat.npz", **out)
+
+
+GENS = {"callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn}
 
