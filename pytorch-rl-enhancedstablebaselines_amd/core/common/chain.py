@@ -1,24 +1,31 @@
-"""SAC.train's gradient step on the row-chain kernels (csrc/cstr_chain.hip): 10 launches instead of 20.
+"""SAC.train's gradient step on the row-chain kernels (csrc/cstr_chain.hip): 8 launches instead of 20 (10 under data-parallel).
 
     reference statement (core/sac/sac.py)                              launch
     :215 sample (gather) + :222 pi(obs) + :247 pi(next_obs)             cstr_sac_actor_chain_fwd_f32      (head left as partial sums)
     :250 target critics + :258 critics (actor head finalised inside)    cstr_q_chain_fwd_f32, 4 networks  (Q heads left as partial sums)
     :230-261 entropy-coefficient loss, TD target, critic loss, critic
              backward to dz                                             cstr_q_chain_bwd_f32, mode 1
-    :266-267 critic dW / db (6 layers)                                  cstr_linear_bwd_weight_sets_f32
-    :240-243, :268 entropy-coefficient + critic Adam steps              cstr_adam_multi_f32
+    :266-267 critic dW / db (6 layers) + :240-243, :268 entropy-
+             coefficient and critic Adam steps                          cstr_linear_bwd_weight_adam_sets_f32
     :273 critics on (obs, pi(obs))                                      cstr_q_chain_fwd_f32, 2 networks
     :275 actor loss + backward through the frozen critics to the action cstr_q_chain_bwd_f32, mode 2      (action gradient as partial sums)
     :279-280 backward of the squashed-Gaussian head and the actor       cstr_sac_actor_chain_bwd_f32
-    :280 actor dW / db (3 layers)                                       cstr_linear_bwd_weight_sets_f32
-    :281 actor Adam step + :284-287 soft update of the target critics   cstr_adam_multi_f32
+    :280 actor dW / db (3 layers) + :281 actor Adam step + :284-287
+             soft update of the target critics                          cstr_linear_bwd_weight_adam_sets_f32
 
-The data-parallel all-reduces keep their places (between the dW / db launch and the Adam launch of each arena). Shapes the chain
-kernels do not cover (other activations, widths that are not multiples of 4 or above 512, batches that are not multiples of 16, a
-VecNormalize normaliser, n_critics != 2) stay on the per-layer fused path (core/common/fused.py). CSTR_CHAIN=0 turns this path off.
+That is the step on one GPU; with the rollout launch in front of it an iteration is 9 launches. Data-parallel training puts a collective
+between a gradient and its optimiser step, so each cstr_linear_bwd_weight_adam_sets_f32 launch becomes
+
+    cstr_linear_bwd_weight_sets_f32 -> all-reduce of the arena's gradient -> cstr_adam_multi_f32
+
+(10 launches; the soft update rides the actor's Adam launch, the entropy coefficient the critic's, or it all-reduces and steps in a
+launch of its own in front of it). Batches of 32 rows and fewer and CSTR_WGRAD_ADAM=0 take the same form without the collectives.
+TD3's step and MADDPG's critic steps are built on the same twin-critic block (`TwinCriticBlock`); their launches are listed in their
+class docstrings. Shapes the chain kernels do not cover (other activations, widths that are not multiples of 4 or above 512, batches
+that are not multiples of 16, a VecNormalize normaliser, n_critics != 2) stay on the per-layer fused path (core/common/fused.py).
+CSTR_CHAIN=0 turns this path off.
 """
 import os
-from typing import Optional
 
 import torch as th
 from torch import nn
@@ -49,8 +56,131 @@ def _q_layers(qnet: nn.Sequential):
     return tuple((m.weight, m.bias) for m in lin)
 
 
+def _is_q_mlp(qnet) -> bool:
+    """Linear-ReLU-Linear-ReLU-Linear(., 1): the only Q network the chain kernels evaluate."""
+    mods = list(qnet)
+    if len(mods) != 5 or not all(isinstance(mods[i], nn.Linear) for i in (0, 2, 4)):
+        return False
+    return all(isinstance(mods[i], nn.ReLU) for i in (1, 3)) and mods[4].out_features == 1
+
+
+def _q_dims_supported(qnet, d: int, a: int, batch_size: int) -> bool:
+    """The (observation, action) layout and the widths of a Q network (`_is_q_mlp`) are ones the chain kernels cover at this batch size."""
+    c1, c2 = qnet[0], qnet[2]
+    return (d, a) in hip_ops.LAYOUTS and c1.in_features == d + a and hip_ops.chain_supported(c1.out_features, c2.out_features, batch_size)
+
+
+def _pick_tiles(kdim: int, want: int, forward: bool = False) -> int:
+    """The largest tile count <= `want` whose per-wave share of a K = kdim reduction fits in registers."""
+    for t in (4, 2, 1):
+        if t <= want and hip_ops.chain_tiles_ok(kdim, t, forward):
+            return t
+    return 1
+
+
+class TwinCriticBlock:
+    """A twin critic and its target on the row-chain kernels: the buffers and the launches of the critic step (four-network forward,
+    TD root + backward to dz, the six dW / db sets) and of a policy pass through the first `n_pi` critics (forward on x_pi, loss root +
+    backward to the action as partial sums). What differs between SAC, TD3 and MADDPG (roles, root arguments, what follows an unfused
+    dW / db launch) is an argument or stays with the caller."""
+
+    def __init__(self, q_networks, target_q_networks, D: int, A: int, B: int, tiles, dev, n_pi: int = 1, q_out=None):
+        """tiles: wanted (4-network forward, policy-pass forward, backward) tile counts. q_out: where the TD root leaves Q1 / Q2 [2, B]
+        (MADDPG hands in a row of the [n_agents, 2, B] tensor its train() reads)."""
+        self.crit, self.targ = [_q_layers(q) for q in q_networks], [_q_layers(q) for q in target_q_networks]
+        self.D, self.A, self.B, self.W, self.n_pi = D, A, B, D + A, n_pi
+        H1, H2 = self.H1, self.H2 = q_networks[0][0].out_features, q_networks[0][2].out_features
+        hip_ops.chain_check_nets(self.crit + self.targ, self.W, H1, H2)  # chain_net passes raw pointers: checked here, once
+        t_q4, t_qpi, t_qb = tiles  # (a wave's share of the reduction must fit in registers: fewer tiles for wide layers)
+        self.t_q4, self.t_qpi = _pick_tiles(H1, t_q4, True), _pick_tiles(H1, t_qpi, True)
+        self.t_qb = _pick_tiles(H2, t_qb)
+        self.n_q4, self.n_qpi = hip_ops.chain_colgroups(H2, self.t_q4), hip_ops.chain_colgroups(H2, self.t_qpi)
+        self.n_gact = hip_ops.chain_colgroups(H1, self.t_qb)
+        e = lambda *sh: th.empty(*sh, dtype=th.float32, device=dev)  # noqa: E731
+        # per-network views (lists): every step reads them one network at a time, and indexing a tensor costs host time
+        self.c_h1, self.c_h2 = list(e(2, B, H1)), list(e(2, B, H2))
+        self.q_part4, self.q_part_pi = list(e(4, self.n_q4, B)), list(e(n_pi, self.n_qpi, B))
+        self.q_out = e(2, B) if q_out is None else q_out
+        self.gq, self.dz2, self.dz1 = e(2, B), e(2, B, H2), e(2, B, H1)
+        self.qpi_out, self.gact_part = e(n_pi, B), e(n_pi, self.n_gact, B, A)
+        self.b3s = [self.crit[0][2][1], self.crit[1][2][1], self.targ[0][2][1], self.targ[1][2][1]]
+
+    PLAIN = (nv.CHAIN_ROLE_PLAIN, nv.CHAIN_ROLE_PLAIN)
+    NEXT = (nv.CHAIN_ROLE_NEXT_STORE, nv.CHAIN_ROLE_NEXT)  # x_next's action columns are finalised from an actor head inside the launch
+
+    def nets4(self, x_cur, x_next, roles=PLAIN, target_roles=NEXT):
+        """The critics on x_cur (hidden layers kept for the backward) and the targets on x_next."""
+        return [hip_ops.chain_net(self.crit[0], x_cur, self.c_h1[0], self.c_h2[0], self.q_part4[0], roles[0]),
+                hip_ops.chain_net(self.crit[1], x_cur, self.c_h1[1], self.c_h2[1], self.q_part4[1], roles[1]),
+                hip_ops.chain_net(self.targ[0], x_next, None, None, self.q_part4[2], target_roles[0]),
+                hip_ops.chain_net(self.targ[1], x_next, None, None, self.q_part4[3], target_roles[1])]
+
+    def pi_nets(self, x_pi, role: int = 0):
+        return [hip_ops.chain_net(self.crit[g], x_pi, self.c_h1[g], self.c_h2[g], self.q_part_pi[g], role) for g in range(self.n_pi)]
+
+    def back_nets(self, n: int = 2):
+        return [hip_ops.chain_net(self.crit[g], None, self.c_h1[g], self.c_h2[g]) for g in range(n)]
+
+    def forward(self, nets, tiles: int, fin=None) -> None:
+        """One forward launch for `nets` (this block's `nets4` / `pi_nets`, or several same-shaped blocks' lists in a row)."""
+        hip_ops.q_chain_fwd(nets, self.W, self.D, self.H1, self.H2, self.B, tiles, fin)
+
+    def td_root(self, rd, gamma: float, scale: float, target_out, loss_out, loss_sum, **kw):
+        """kw: next_logp, ent_coef, alpha, rng_advance, adam_advance of hip_ops.chain_root."""
+        return hip_ops.chain_root("td", self.B, self.q_part4, self.b3s, self.n_q4, gamma=gamma, scale=scale, rew=rd.rewards, done=rd.dones,
+                                  target_out=target_out, q_out=self.q_out, gq_out=self.gq, loss_out=loss_out, loss_sum=loss_sum, **kw)
+
+    def pi_root(self, mode: str, **kw):
+        """mode "sac_actor" (kw: ent_coef, logp) or "neg_mean"; kw: loss_out, loss_sum, adam_advance."""
+        return hip_ops.chain_root(mode, self.B, self.q_part_pi, self.b3s[:self.n_pi], self.n_qpi, q_out=self.qpi_out, **kw)
+
+    def td_backward(self, back, root) -> None:
+        hip_ops.q_chain_bwd(back, root, self.W, self.D, self.H1, self.H2, self.t_qb, dz2=self.dz2, dz1=self.dz1)
+
+    def pi_backward(self, back, root) -> None:
+        hip_ops.q_chain_bwd(back, root, self.W, self.D, self.H1, self.H2, self.t_qb, gact_part=self.gact_part)
+
+    def policy_pass(self, mode: str, x_pi, back, role: int = 0, fin=None, **root_kw) -> None:
+        """The policy loss through the first `n_pi` (frozen) critics and its gradient w.r.t. the action, left in `gact_part`: 2 launches.
+        back: `back_nets(n_pi)` (a step that ran `td_backward` passes the nets it built for it)."""
+        self.forward(self.pi_nets(x_pi, role), self.t_qpi, fin)
+        self.pi_backward(back, self.pi_root(mode, **root_kw))
+
+    def sets(self, x_cur, fuse_opt: bool, opt_index: int = 0) -> list:
+        """The six dW / db sets of the twin critic, for linear_bwd_weight_adam_sets (optimiser `opt_index` of its list) or
+        linear_bwd_weight_sets."""
+        B, sets = self.B, []
+        for g in range(2):
+            (w1, b1), (w2, b2), (w3, b3) = self.crit[g]
+            if fuse_opt:
+                sets += [(self.dz1[g], x_cur, w1, b1, opt_index, None), (self.dz2[g], self.c_h1[g], w2, b2, opt_index, None),
+                         (self.gq[g].view(B, 1), self.c_h2[g], w3, b3, opt_index, None)]
+            else:
+                sets += [(self.dz1[g], x_cur, w1.grad, b1.grad), (self.dz2[g], self.c_h1[g], w2.grad, b2.grad),
+                         (self.gq[g].view(B, 1), self.c_h2[g], w3.grad, b3.grad)]
+        return sets
+
+    @staticmethod
+    def apply(blocks, x_cur, fuse_opt: bool, opts, flat=()) -> None:
+        """The critic gradients of `blocks` in ONE launch. fuse_opt (`_adam_in_wgrad`): with the Adam steps of `opts` (one optimiser per
+        block, step counters pre-advanced by the TD roots) and the `flat` segments inside. Otherwise gradients only: the caller
+        all-reduces and steps behind it."""
+        if fuse_opt:
+            hip_ops.linear_bwd_weight_adam_sets([st for k, blk in enumerate(blocks) for st in blk.sets(x_cur, True, k)], opts, flat)
+        else:
+            hip_ops.linear_bwd_weight_sets([st for blk in blocks for st in blk.sets(x_cur, False)])
+
+    def captured(self, target_q, critic_loss, actor_loss=None, **more) -> dict:
+        """model.last_train_tensors of a debug_capture step."""
+        B = self.B
+        return dict(target_q=target_q.clone(), current_q=[self.q_out[0].clone().view(B, 1), self.q_out[1].clone().view(B, 1)],
+                    critic_loss=critic_loss.clone(), actor_loss=None if actor_loss is None else actor_loss.clone(), **more)
+
+
 class SacChain:
     """Buffers + launch sequence of one SAC gradient step on the chain kernels. Built once per (model, batch size)."""
+
+    ROLES = (nv.CHAIN_ROLE_STORE_PI, nv.CHAIN_ROLE_PLAIN)  # the first critic's launch also finalises pi(obs): x_pi's action columns, params, logp_pi
 
     @staticmethod
     def supported(model, batch_size: int) -> bool:
@@ -64,18 +194,11 @@ class SacChain:
         layers = fa.latent.layers
         if len(layers) != 2 or any(act != fused.ACT_RELU for _, act in layers) or fa.head is None or not fa._hw.is_contiguous():
             return False
-        for q in list(model.critic.q_networks) + list(model.critic_target.q_networks):
-            mods = list(q)
-            if len(mods) != 5 or not all(isinstance(mods[i], nn.Linear) for i in (0, 2, 4)) or not all(isinstance(mods[i], nn.ReLU) for i in (1, 3)):
-                return False
-            if mods[4].out_features != 1:
-                return False
-        (l1, _), (l2, _) = layers
-        c1, c2 = model.critic.q_networks[0][0], model.critic.q_networks[0][2]
-        d, a = l1.in_features, fa.act_dim
-        if (d, a) not in hip_ops.LAYOUTS or c1.in_features != d + a:
+        if not all(_is_q_mlp(q) for q in list(model.critic.q_networks) + list(model.critic_target.q_networks)):
             return False
-        return (hip_ops.chain_supported(l1.out_features, l2.out_features, batch_size) and hip_ops.chain_supported(c1.out_features, c2.out_features, batch_size)
+        (l1, _), (l2, _) = layers
+        return (_q_dims_supported(model.critic.q_networks[0], l1.in_features, fa.act_dim, batch_size)
+                and hip_ops.chain_supported(l1.out_features, l2.out_features, batch_size)
                 and all(p.grad is not None for p in list(model.actor.parameters()) + list(model.critic.parameters())))
 
     def __init__(self, model, batch_size: int):
@@ -84,27 +207,16 @@ class SacChain:
         self.D, self.A, self.B = l1.in_features, fa.act_dim, B
         self.W = self.D + self.A
         self.aH1, self.aH2 = l1.out_features, l2.out_features
-        c = model.critic.q_networks[0]
-        self.cH1, self.cH2 = c[0].out_features, c[2].out_features
-        t_act, t_q4, t_q2, t_qb, t_ab = TILES  # (a wave's share of the reduction must fit in registers: fewer tiles for wide layers)
-        self.t_act, self.t_q4, self.t_q2 = _pick_tiles(self.aH1, t_act, True), _pick_tiles(self.cH1, t_q4, True), _pick_tiles(self.cH1, t_q2, True)
-        self.t_qb, self.t_ab = _pick_tiles(self.cH2, t_qb), _pick_tiles(self.aH2, t_ab)
+        t_act, t_q4, t_q2, t_qb, t_ab = TILES
+        self.t_act, self.t_ab = _pick_tiles(self.aH1, t_act, True), _pick_tiles(self.aH2, t_ab)
         self.actor = hip_ops.sac_actor_desc(self.D, self.A, l1.weight, l1.bias, l2.weight, l2.bias, fa._hw, fa._hb)
         self.actor_layers = (l1, l2)
-        self.crit = [_q_layers(q) for q in model.critic.q_networks]
-        self.targ = [_q_layers(q) for q in model.critic_target.q_networks]
+        self.block = TwinCriticBlock(model.critic.q_networks, model.critic_target.q_networks, self.D, self.A, B, (t_q4, t_q2, t_qb), dev, n_pi=2)
         e = lambda *sh: th.empty(*sh, dtype=th.float32, device=dev)  # noqa: E731
         A, H1, H2 = self.A, self.aH1, self.aH2
         self.n_head_parts = hip_ops.chain_colgroups(H2, self.t_act)
         self.a_h1, self.a_h2, self.head_part = e(B, H1), e(B, H2), e(self.n_head_parts, 2 * B, 2 * A)
         self.params, self.eps_all, self.logp_pi, self.logp_next = e(B, 2 * A), e(2 * B, A), e(B), e(B)
-        self.c_h1, self.c_h2 = e(2, B, self.cH1), e(2, B, self.cH2)
-        self.n_q4, self.n_q2 = hip_ops.chain_colgroups(self.cH2, self.t_q4), hip_ops.chain_colgroups(self.cH2, self.t_q2)
-        self.q_part4, self.q_part2 = e(4, self.n_q4, B), e(2, self.n_q2, B)
-        self.q_out, self.qpi_out, self.gq = e(2, B), e(2, B), e(2, B)
-        self.dz2c, self.dz1c = e(2, B, self.cH2), e(2, B, self.cH1)
-        self.n_gact = hip_ops.chain_colgroups(self.cH1, self.t_qb)
-        self.gact_part = e(2, self.n_gact, B, A)
         self.g_params, self.dz2a, self.dz1a = e(B, 2 * A), e(B, H2), e(B, H1)
         # the merged (mu | log_std) head as (values, gradient, exp_avg, exp_avg_sq) views for the fused dW + Adam launch
         self._head_params = None
@@ -118,7 +230,7 @@ class SacChain:
                                      (fa._hb, fa._hbg, aopt.exp_avg[ob:ob + nb], aopt.exp_avg_sq[ob:ob + nb]))
 
     def step(self, model, pb, gather, gradient_step: int) -> None:
-        s, pol, B, W, D, A = model._loss_sums, model.policy, self.B, self.W, self.D, self.A
+        s, pol, blk, B, D, A = model._loss_sums, model.policy, self.block, self.B, self.D, self.A
         fa = model._fast_actor
         (c_out, c_sum), (a_out, a_sum) = model._loss_slot("critic"), model._loss_slot("actor")
         rd = pb.samples
@@ -153,11 +265,7 @@ class SacChain:
         fin = nv.SacHeadFin(self.head_part.data_ptr(), fa._hb.data_ptr(), eps.data_ptr(), self.n_head_parts, A, D, nv.CHAIN_HEAD_GAUSSIAN, 2 * B, B, 0.0, 0.0,
                             pb.x_pi.data_ptr(), pb.x_next.data_ptr(), self.params.data_ptr(), self.logp_pi.data_ptr(), self.logp_next.data_ptr())
         self._keep = eps2  # alive until the launches that read it have been issued (and recorded)
-        nets4 = [hip_ops.chain_net(self.crit[0], pb.x_data, self.c_h1[0], self.c_h2[0], self.q_part4[0], nv.CHAIN_ROLE_STORE_PI),
-                 hip_ops.chain_net(self.crit[1], pb.x_data, self.c_h1[1], self.c_h2[1], self.q_part4[1], nv.CHAIN_ROLE_PLAIN),
-                 hip_ops.chain_net(self.targ[0], pb.x_next, None, None, self.q_part4[2], nv.CHAIN_ROLE_NEXT_STORE),
-                 hip_ops.chain_net(self.targ[1], pb.x_next, None, None, self.q_part4[3], nv.CHAIN_ROLE_NEXT)]
-        hip_ops.q_chain_fwd(nets4, W, D, self.cH1, self.cH2, B, self.t_q4, fin)
+        blk.forward(blk.nets4(pb.x_data, pb.x_next, roles=self.ROLES), blk.t_q4, fin)
         # -- entropy-coefficient loss, TD target, critic loss and the critic backward down to dz1
         if model.ent_coef_optimizer is not None:
             (ent_coef, ent_coef_sum), (e_out, e_sum) = model._loss_slot("ent_coef"), model._loss_slot("ent_coef_loss")
@@ -166,52 +274,34 @@ class SacChain:
         else:
             ent_coef, alpha = model.ent_coef_tensor.reshape(1), None
             s["ent_coef"] += ent_coef
-        b3s = [self.crit[0][2][1], self.crit[1][2][1], self.targ[0][2][1], self.targ[1][2][1]]
         # one GPU: no collective between a gradient and its optimiser step -> the dW / db launch applies Adam to its tiles; the step
-        # counters are advanced by the loss workgroup of the launch in front of it
+        # counters are advanced by the loss workgroup of the launch in front of it. The actor's launch also needs the merged head's
+        # moment views: without them its optimiser steps (and advances its own counter) behind an unfused dW / db launch
         fuse_opt = _adam_in_wgrad(model, B)
+        fuse_actor = fuse_opt and self._head_params is not None
         ent_opt = model.ent_coef_optimizer
-        root = hip_ops.chain_root("td", B, [self.q_part4[g] for g in range(4)], b3s, self.n_q4, gamma=model.gamma, scale=0.5,
-                                  next_logp=self.logp_next, rew=rd.rewards, done=rd.dones, ent_coef=ent_coef, target_out=model._target_q,
-                                  q_out=self.q_out, gq_out=self.gq, loss_out=c_out, loss_sum=c_sum,
-                                  alpha=alpha, rng_advance=rng_total,
-                                  adam_advance=([model.critic.optimizer] + ([ent_opt] if ent_opt is not None else [])) if fuse_opt else ())
-        back = [hip_ops.chain_net(self.crit[g], None, self.c_h1[g], self.c_h2[g]) for g in range(2)]
-        hip_ops.q_chain_bwd(back, root, W, D, self.cH1, self.cH2, self.t_qb, dz2=self.dz2c, dz1=self.dz1c)
-        if fuse_opt:
-            sets = []
-            for g in range(2):
-                (w1, b1), (w2, b2), (w3, b3) = self.crit[g]
-                sets += [(self.dz1c[g], pb.x_data, w1, b1, 0, None), (self.dz2c[g], self.c_h1[g], w2, b2, 0, None),
-                         (self.gq[g].view(B, 1), self.c_h2[g], w3, b3, 0, None)]
-            hip_ops.linear_bwd_weight_adam_sets(sets, [model.critic.optimizer], [ent_opt._segment()] if ent_opt is not None else [])
-        else:
-            sets = []
-            for g in range(2):
-                (w1, b1), (w2, b2), (w3, b3) = self.crit[g]
-                sets += [(self.dz1c[g], pb.x_data, w1.grad, b1.grad), (self.dz2c[g], self.c_h1[g], w2.grad, b2.grad),
-                         (self.gq[g].view(B, 1), self.c_h2[g], w3.grad, b3.grad)]
-            hip_ops.linear_bwd_weight_sets(sets)
-            if model.ent_coef_optimizer is not None and not model._ent_rides_critic:
+        back = blk.back_nets()
+        advance = ([model.critic.optimizer] + ([ent_opt] if ent_opt is not None else [])) if fuse_opt else ()
+        blk.td_backward(back, blk.td_root(rd, model.gamma, 0.5, model._target_q, c_out, c_sum, next_logp=self.logp_next, ent_coef=ent_coef,
+                                          alpha=alpha, rng_advance=rng_total, adam_advance=advance))
+        blk.apply([blk], pb.x_data, fuse_opt, [model.critic.optimizer], [ent_opt._segment()] if fuse_opt and ent_opt is not None else [])
+        if not fuse_opt:
+            if ent_opt is not None and not model._ent_rides_critic:
                 model._allreduce_grads(model._ent_arena)
-                model.ent_coef_optimizer.step()
+                ent_opt.step()
             model._allreduce_grads(pol.critic_arena)
-            if model.ent_coef_optimizer is not None and model._ent_rides_critic:
-                model.critic.optimizer.step_with(model.ent_coef_optimizer)
+            if ent_opt is not None and model._ent_rides_critic:
+                model.critic.optimizer.step_with(ent_opt)
             else:
                 model.critic.optimizer.step()
         # -- actor loss through the (updated, frozen) critics
-        nets2 = [hip_ops.chain_net(self.crit[g], pb.x_pi, self.c_h1[g], self.c_h2[g], self.q_part2[g]) for g in range(2)]
-        hip_ops.q_chain_fwd(nets2, W, D, self.cH1, self.cH2, B, self.t_q2)
-        aroot = hip_ops.chain_root("sac_actor", B, [self.q_part2[0], self.q_part2[1]], b3s[:2], self.n_q2, ent_coef=ent_coef, logp=self.logp_pi,
-                                   q_out=self.qpi_out, loss_out=a_out, loss_sum=a_sum,
-                                   adam_advance=[model.actor.optimizer] if fuse_opt else ())
-        hip_ops.q_chain_bwd(back, aroot, W, D, self.cH1, self.cH2, self.t_qb, gact_part=self.gact_part)
-        hip_ops.sac_actor_chain_bwd(self.actor, self.gact_part, 2, self.n_gact, ent_coef, pb.x_pi, self.params, eps, self.a_h1, self.a_h2,
+        blk.policy_pass("sac_actor", pb.x_pi, back, ent_coef=ent_coef, logp=self.logp_pi, loss_out=a_out, loss_sum=a_sum,
+                        adam_advance=[model.actor.optimizer] if fuse_actor else ())
+        hip_ops.sac_actor_chain_bwd(self.actor, blk.gact_part, 2, blk.n_gact, ent_coef, pb.x_pi, self.params, eps, self.a_h1, self.a_h2,
                                     self.g_params, self.dz2a, self.dz1a, B, self.t_ab)
         l1, l2 = self.actor_layers
         soft = gradient_step % model.target_update_interval == 0
-        if fuse_opt and self._head_params is not None:
+        if fuse_actor:
             aopt = model.actor.optimizer
             sh = aopt.shadow
             hw_p, hb_p = self._head_params
@@ -231,17 +321,7 @@ class SacChain:
             else:
                 model.actor.optimizer.step()
         if model.debug_capture:
-            model.last_train_tensors = dict(target_q=model._target_q.clone(), current_q=[self.q_out[0].clone().view(B, 1), self.q_out[1].clone().view(B, 1)],
-                                            critic_loss=c_out.clone(), actor_loss=a_out.clone(),
-                                            ent_coef=ent_coef.detach().clone(), log_prob=self.logp_pi.clone())
-
-
-def _pick_tiles(kdim: int, want: int, forward: bool = False) -> int:
-    """The largest tile count <= `want` whose per-wave share of a K = kdim reduction fits in registers."""
-    for t in (4, 2, 1):
-        if t <= want and hip_ops.chain_tiles_ok(kdim, t, forward):
-            return t
-    return 1
+            model.last_train_tensors = blk.captured(model._target_q, c_out, a_out, ent_coef=ent_coef.detach().clone(), log_prob=self.logp_pi.clone())
 
 
 class Td3Chain:
@@ -260,23 +340,16 @@ class Td3Chain:
             return False
         if len(model.critic.q_networks) != 2:
             return False
-        for q in list(model.critic.q_networks) + list(model.critic_target.q_networks):
-            mods = list(q)
-            if len(mods) != 5 or not all(isinstance(mods[i], nn.Linear) for i in (0, 2, 4)) or not all(isinstance(mods[i], nn.ReLU) for i in (1, 3)):
-                return False
-            if mods[4].out_features != 1:
-                return False
+        if not all(_is_q_mlp(q) for q in list(model.critic.q_networks) + list(model.critic_target.q_networks)):
+            return False
         for actor in (model.actor, model.actor_target):
             mods = list(actor.mu)
             if (len(mods) != 6 or not all(isinstance(mods[i], nn.Linear) for i in (0, 2, 4)) or not all(isinstance(mods[i], nn.ReLU) for i in (1, 3))
                     or not isinstance(mods[5], nn.Tanh)):
                 return False
         a1, a2, a3 = (model.actor.mu[i] for i in (0, 2, 4))
-        c1, c2 = model.critic.q_networks[0][0], model.critic.q_networks[0][2]
-        d, a = a1.in_features, a3.out_features
-        if (d, a) not in hip_ops.LAYOUTS or c1.in_features != d + a:
-            return False
-        return (hip_ops.chain_supported(a1.out_features, a2.out_features, batch_size) and hip_ops.chain_supported(c1.out_features, c2.out_features, batch_size)
+        return (_q_dims_supported(model.critic.q_networks[0], a1.in_features, a3.out_features, batch_size)
+                and hip_ops.chain_supported(a1.out_features, a2.out_features, batch_size)
                 and all(p.grad is not None for p in list(model.actor.parameters()) + list(model.critic.parameters())))
 
     def __init__(self, model, batch_size: int):
@@ -286,33 +359,22 @@ class Td3Chain:
         self.D, self.A, self.B = a1.in_features, a3.out_features, B
         self.W = self.D + self.A
         self.aH1, self.aH2 = a1.out_features, a2.out_features
-        c = model.critic.q_networks[0]
-        self.cH1, self.cH2 = c[0].out_features, c[2].out_features
         t_act, t_q4, t_q2, t_qb, t_ab = TD3_TILES
-        self.t_act, self.t_q4, self.t_q1 = _pick_tiles(self.aH1, t_act, True), _pick_tiles(self.cH1, t_q4, True), _pick_tiles(self.cH1, t_q2, True)
-        self.t_qb, self.t_ab = _pick_tiles(self.cH2, t_qb), _pick_tiles(self.aH2, t_ab)
+        self.t_act, self.t_ab = _pick_tiles(self.aH1, t_act, True), _pick_tiles(self.aH2, t_ab)
         self.actor = hip_ops.sac_actor_desc(self.D, self.A, a1.weight, a1.bias, a2.weight, a2.bias, a3.weight, a3.bias)
         self.tactor = hip_ops.sac_actor_desc(self.D, self.A, t1.weight, t1.bias, t2.weight, t2.bias, t3.weight, t3.bias)
         self.actor_layers, self.tactor_layers = (a1, a2, a3), (t1, t2, t3)
-        self.crit = [_q_layers(q) for q in model.critic.q_networks]
-        self.targ = [_q_layers(q) for q in model.critic_target.q_networks]
+        self.block = TwinCriticBlock(model.critic.q_networks, model.critic_target.q_networks, self.D, self.A, B, (t_q4, t_q2, t_qb), dev)
         e = lambda *sh: th.empty(*sh, dtype=th.float32, device=dev)  # noqa: E731
         A, H1, H2 = self.A, self.aH1, self.aH2
         self.n_head = hip_ops.chain_colgroups(H2, self.t_act)
         self.head_part = e(self.n_head, B, A)
         self.eps = e(B, A)
         self.a_h1, self.a_h2 = e(B, H1), e(B, H2)
-        self.c_h1, self.c_h2 = e(2, B, self.cH1), e(2, B, self.cH2)
-        self.n_q4, self.n_q1 = hip_ops.chain_colgroups(self.cH2, self.t_q4), hip_ops.chain_colgroups(self.cH2, self.t_q1)
-        self.q_part4, self.q_part1 = e(4, self.n_q4, B), e(1, self.n_q1, B)
-        self.q_out, self.qpi_out, self.gq = e(2, B), e(1, B), e(2, B)
-        self.dz2c, self.dz1c = e(2, B, self.cH2), e(2, B, self.cH1)
-        self.n_gact = hip_ops.chain_colgroups(self.cH1, self.t_qb)
-        self.gact_part = e(1, self.n_gact, B, A)
         self.g_params, self.dz2a, self.dz1a = e(B, A), e(B, H2), e(B, H1)
 
     def step(self, model, pb, gather, n_updates: int) -> None:
-        pol, B, W, D, A = model.policy, self.B, self.W, self.D, self.A
+        pol, blk, B, D, A = model.policy, self.block, self.B, self.D, self.A
         rd = pb.samples
         c_out, c_sum = model._loss_slot("critic")
         queued = model.noise_queue.pop(0).to(model.device, th.float32).contiguous() if model.noise_queue else None  # teacher-forced, scaled
@@ -335,33 +397,14 @@ class Td3Chain:
         fin = nv.SacHeadFin(self.head_part.data_ptr(), t3.bias.data_ptr(), eps.data_ptr(), self.n_head, A, D, nv.CHAIN_HEAD_DETERMINISTIC, B, 0,
                             float(sigma), float(model.target_noise_clip), pb.x_pi.data_ptr(), pb.x_next.data_ptr(), None, None, None)
         self._keep = queued
-        nets4 = [hip_ops.chain_net(self.crit[0], pb.x_data, self.c_h1[0], self.c_h2[0], self.q_part4[0], nv.CHAIN_ROLE_PLAIN),
-                 hip_ops.chain_net(self.crit[1], pb.x_data, self.c_h1[1], self.c_h2[1], self.q_part4[1], nv.CHAIN_ROLE_PLAIN),
-                 hip_ops.chain_net(self.targ[0], pb.x_next, None, None, self.q_part4[2], nv.CHAIN_ROLE_NEXT_STORE),
-                 hip_ops.chain_net(self.targ[1], pb.x_next, None, None, self.q_part4[3], nv.CHAIN_ROLE_NEXT)]
-        hip_ops.q_chain_fwd(nets4, W, D, self.cH1, self.cH2, B, self.t_q4, fin)
-        b3s = [self.crit[0][2][1], self.crit[1][2][1], self.targ[0][2][1], self.targ[1][2][1]]
-        root = hip_ops.chain_root("td", B, [self.q_part4[g] for g in range(4)], b3s, self.n_q4, gamma=model.gamma, scale=1.0, rew=rd.rewards,
-                                  done=rd.dones, target_out=model._target_q, q_out=self.q_out, gq_out=self.gq, loss_out=c_out, loss_sum=c_sum,
-                                  rng_advance=None if queued is not None else (rng, B), adam_advance=[model.critic.optimizer] if fuse_opt else ())
-        back = [hip_ops.chain_net(self.crit[g], None, self.c_h1[g], self.c_h2[g]) for g in range(2)]
-        hip_ops.q_chain_bwd(back, root, W, D, self.cH1, self.cH2, self.t_qb, dz2=self.dz2c, dz1=self.dz1c)
-        sets = []
-        for g in range(2):
-            (w1, b1), (w2, b2), (w3, b3) = self.crit[g]
-            if fuse_opt:
-                sets += [(self.dz1c[g], pb.x_data, w1, b1, 0, None), (self.dz2c[g], self.c_h1[g], w2, b2, 0, None),
-                         (self.gq[g].view(B, 1), self.c_h2[g], w3, b3, 0, None)]
-            else:
-                sets += [(self.dz1c[g], pb.x_data, w1.grad, b1.grad), (self.dz2c[g], self.c_h1[g], w2.grad, b2.grad),
-                         (self.gq[g].view(B, 1), self.c_h2[g], w3.grad, b3.grad)]
-        if fuse_opt:
-            hip_ops.linear_bwd_weight_adam_sets(sets, [model.critic.optimizer])
-        else:
-            hip_ops.linear_bwd_weight_sets(sets)
+        blk.forward(blk.nets4(pb.x_data, pb.x_next), blk.t_q4, fin)
+        back = blk.back_nets()
+        blk.td_backward(back, blk.td_root(rd, model.gamma, 1.0, model._target_q, c_out, c_sum, rng_advance=None if queued is not None else (rng, B),
+                                          adam_advance=[model.critic.optimizer] if fuse_opt else ()))
+        blk.apply([blk], pb.x_data, fuse_opt, [model.critic.optimizer])
+        if not fuse_opt:
             model._allreduce_grads(pol.critic_arena)
             model.critic.optimizer.step()
-        actor_done = False
         a_out = None
         if n_updates % model.policy_delay == 0:  # :192-206
             a_out, a_sum = model._loss_slot("actor")
@@ -370,12 +413,9 @@ class Td3Chain:
                                         rows_mode=nv.CHAIN_ROWS_OBS, head_n=A)
             fin2 = nv.SacHeadFin(self.head_part.data_ptr(), a3.bias.data_ptr(), None, self.n_head, A, D, nv.CHAIN_HEAD_DETERMINISTIC, B, 0, 0.0, 0.0,
                                  pb.x_pi.data_ptr(), None, None, None, None)
-            net1 = [hip_ops.chain_net(self.crit[0], pb.x_pi, self.c_h1[0], self.c_h2[0], self.q_part1[0], nv.CHAIN_ROLE_PI)]
-            hip_ops.q_chain_fwd(net1, W, D, self.cH1, self.cH2, B, self.t_q1, fin2)
-            aroot = hip_ops.chain_root("neg_mean", B, [self.q_part1[0]], b3s[:1], self.n_q1, q_out=self.qpi_out, loss_out=a_out, loss_sum=a_sum,
-                                       adam_advance=[model.actor.optimizer] if fuse_opt else ())
-            hip_ops.q_chain_bwd(back[:1], aroot, W, D, self.cH1, self.cH2, self.t_qb, gact_part=self.gact_part)
-            hip_ops.sac_actor_chain_bwd(self.actor, self.gact_part, 1, self.n_gact, None, pb.x_pi, None, None, self.a_h1, self.a_h2, self.g_params,
+            blk.policy_pass("neg_mean", pb.x_pi, back[:1], role=nv.CHAIN_ROLE_PI, fin=fin2, loss_out=a_out, loss_sum=a_sum,
+                            adam_advance=[model.actor.optimizer] if fuse_opt else ())
+            hip_ops.sac_actor_chain_bwd(self.actor, blk.gact_part, 1, blk.n_gact, None, pb.x_pi, None, None, self.a_h1, self.a_h2, self.g_params,
                                         self.dz2a, self.dz1a, B, self.t_ab, kind=nv.CHAIN_HEAD_DETERMINISTIC)
             if not pol.actor_target_arena.same_layout(pol.actor_arena) or not pol.critic_target_arena.same_layout(pol.critic_arena):
                 raise ValueError("Iterables have different lengths")  # zip_strict's error (utils.py:447)
@@ -394,10 +434,8 @@ class Td3Chain:
                 model._allreduce_grads(pol.actor_arena)
                 model.actor.optimizer.step_with(polyak=(pol.critic_arena, pol.critic_target_arena, model.tau),
                                                 own_target=(pol.actor_target_arena.flat, model.tau))
-            actor_done = True
         if model.debug_capture:
-            model.last_train_tensors = dict(target_q=model._target_q.clone(), current_q=[self.q_out[0].clone().view(B, 1), self.q_out[1].clone().view(B, 1)],
-                                            critic_loss=c_out.clone(), actor_loss=a_out.clone() if actor_done else None)
+            model.last_train_tensors = blk.captured(model._target_q, c_out, a_out)
 
 
 class MaddpgCriticChain:
@@ -409,6 +447,8 @@ class MaddpgCriticChain:
         dW / db + Adam launch per two agents.
     Centralised critics only (IDDPG's local critics read per-agent inputs and stay on the per-layer path)."""
 
+    TARGET_ROLES = TwinCriticBlock.PLAIN  # x_next arrives complete: no actor head is finalised inside the launch
+
     @staticmethod
     def supported(model, batch_size: int) -> bool:
         C = model.critic
@@ -418,99 +458,48 @@ class MaddpgCriticChain:
 
         if not all(isinstance(o, FlatAdam) for o in C.optimizer_list):
             return False
-        for nets in list(C.q_networks_list) + list(model.critic_target.q_networks_list):
-            for q in nets:
-                mods = list(q)
-                if len(mods) != 5 or not all(isinstance(mods[i], nn.Linear) for i in (0, 2, 4)) or not all(isinstance(mods[i], nn.ReLU) for i in (1, 3)):
-                    return False
-                if mods[4].out_features != 1:
-                    return False
-        c1, c2 = C.q_networks_list[0][0][0], C.q_networks_list[0][0][2]
-        d, a = model.observation_space.shape[0], model.action_space.shape[0]
-        if (d, a) not in hip_ops.LAYOUTS or c1.in_features != d + a:
+        if not all(_is_q_mlp(q) for nets in list(C.q_networks_list) + list(model.critic_target.q_networks_list) for q in nets):
             return False
-        return hip_ops.chain_supported(c1.out_features, c2.out_features, batch_size) and all(p.grad is not None for p in C.parameters())
+        return (_q_dims_supported(C.q_networks_list[0][0], model.observation_space.shape[0], model.action_space.shape[0], batch_size)
+                and all(p.grad is not None for p in C.parameters()))
 
     def __init__(self, model, batch_size: int):
         dev, B, n = model.device, batch_size, model.n_agents
         self.B, self.n = B, n
         self.D, self.A = model.observation_space.shape[0], model.action_space.shape[0]
         self.W = self.D + self.A
-        c = model.critic.q_networks_list[0][0]
-        self.H1, self.H2 = c[0].out_features, c[2].out_features
         t_act, t_q4, t_q2, t_qb, t_ab = TD3_TILES
-        self.t_q, self.t_qb = _pick_tiles(self.H1, t_q4, True), _pick_tiles(self.H2, t_qb)
-        self.crit = [[_q_layers(q) for q in nets] for nets in model.critic.q_networks_list]
-        self.targ = [[_q_layers(q) for q in nets] for nets in model.critic_target.q_networks_list]
-        e = lambda *sh: th.empty(*sh, dtype=th.float32, device=dev)  # noqa: E731
-        self.n_q = hip_ops.chain_colgroups(self.H2, self.t_q)
-        self.c_h1, self.c_h2 = e(n, 2, B, self.H1), e(n, 2, B, self.H2)
-        self.q_part = e(n, 4, self.n_q, B)
-        self.q_out, self.gq = e(n, 2, B), e(n, 2, B)
-        self.dz2, self.dz1 = e(n, 2, B, self.H2), e(n, 2, B, self.H1)
-        # the policy step's pass through agent i's FIRST critic (:174-177): forward partials, action-gradient partials and the critic-input
-        # gradient the per-layer actor backward reads (observation columns stay zero)
-        self.t_q1 = _pick_tiles(self.H1, t_q2, True)
-        self.n_q1, self.n_gact = hip_ops.chain_colgroups(self.H2, self.t_q1), hip_ops.chain_colgroups(self.H1, self.t_qb)
-        self.q_part1, self.qpi_out = e(1, self.n_q1, B), e(1, B)
-        self.gact_part = e(1, self.n_gact, B, self.A)
+        self.q_out = th.empty(n, 2, B, dtype=th.float32, device=dev)
+        # one block per agent; its policy pass is through agent i's FIRST critic (:174-177)
+        self.blocks = [TwinCriticBlock(model.critic.q_networks_list[i], model.critic_target.q_networks_list[i], self.D, self.A, B, (t_q4, t_q2, t_qb),
+                                       dev, q_out=self.q_out[i]) for i in range(n)]
+        # the critic-input gradient the per-layer actor backward reads (observation columns stay zero)
         self.g_x = th.zeros(B, self.W, dtype=th.float32, device=dev)
 
     def actor_loss_grad(self, model, i: int, x_pi) -> th.Tensor:
         """-mean(Q1_i(obs, pi(obs))) (:177) and its gradient w.r.t. the critic input: Q chain forward (first critic, frozen) -> Q backward
         chain to the action (partials) -> the partials' sum into the action columns of g_x: 3 launches instead of 6."""
-        B, W, D = self.B, self.W, self.D
-        net = [hip_ops.chain_net(self.crit[i][0], x_pi, self.c_h1[i, 0], self.c_h2[i, 0], self.q_part1[0])]
-        hip_ops.q_chain_fwd(net, W, D, self.H1, self.H2, B, self.t_q1)
-        aroot = hip_ops.chain_root("neg_mean", B, [self.q_part1[0]], [self.crit[i][0][2][1]], self.n_q1, q_out=self.qpi_out, loss_out=model._loss_now,
-                                   loss_sum=model._loss_sums[f"actor{i}"])
-        back = [hip_ops.chain_net(self.crit[i][0], None, self.c_h1[i, 0], self.c_h2[i, 0])]
-        hip_ops.q_chain_bwd(back, aroot, W, D, self.H1, self.H2, self.t_qb, gact_part=self.gact_part)
-        hip_ops.chain_sum_parts(self.gact_part, self.g_x[:, D:])
+        blk = self.blocks[i]
+        blk.policy_pass("neg_mean", x_pi, blk.back_nets(1), loss_out=model._loss_now, loss_sum=model._loss_sums[f"actor{i}"])
+        hip_ops.chain_sum_parts(blk.gact_part, self.g_x[:, self.D:])
         return self.g_x
 
-    def _nets4(self, i: int, x_cur, x_next):
-        return [hip_ops.chain_net(self.crit[i][0], x_cur, self.c_h1[i, 0], self.c_h2[i, 0], self.q_part[i, 0]),
-                hip_ops.chain_net(self.crit[i][1], x_cur, self.c_h1[i, 1], self.c_h2[i, 1], self.q_part[i, 1]),
-                hip_ops.chain_net(self.targ[i][0], x_next, None, None, self.q_part[i, 2]),
-                hip_ops.chain_net(self.targ[i][1], x_next, None, None, self.q_part[i, 3])]
-
     def _backward(self, model, i: int, rd, fuse_opt: bool) -> None:
-        B = self.B
-        b3s = [self.crit[i][0][2][1], self.crit[i][1][2][1], self.targ[i][0][2][1], self.targ[i][1][2][1]]
-        root = hip_ops.chain_root("td", B, [self.q_part[i, g] for g in range(4)], b3s, self.n_q, gamma=model.gamma, scale=1.0, rew=rd.rewards,
-                                  done=rd.dones, target_out=model._target_q[i], q_out=self.q_out[i], gq_out=self.gq[i], loss_out=model._loss_now,
-                                  loss_sum=model._loss_sums[f"critic{i}"], adam_advance=[model.critic.optimizer_list[i]] if fuse_opt else ())
-        back = [hip_ops.chain_net(self.crit[i][g], None, self.c_h1[i, g], self.c_h2[i, g]) for g in range(2)]
-        hip_ops.q_chain_bwd(back, root, self.W, self.D, self.H1, self.H2, self.t_qb, dz2=self.dz2[i], dz1=self.dz1[i])
-
-    def _sets(self, i: int, x_cur, fuse_opt: bool, opt_index: int = 0) -> list:
-        B, sets = self.B, []
-        for g in range(2):
-            (w1, b1), (w2, b2), (w3, b3) = self.crit[i][g]
-            if fuse_opt:
-                sets += [(self.dz1[i, g], x_cur, w1, b1, opt_index, None), (self.dz2[i, g], self.c_h1[i, g], w2, b2, opt_index, None),
-                         (self.gq[i, g].view(B, 1), self.c_h2[i, g], w3, b3, opt_index, None)]
-            else:
-                sets += [(self.dz1[i, g], x_cur, w1.grad, b1.grad), (self.dz2[i, g], self.c_h1[i, g], w2.grad, b2.grad),
-                         (self.gq[i, g].view(B, 1), self.c_h2[i, g], w3.grad, b3.grad)]
-        return sets
+        blk = self.blocks[i]
+        blk.td_backward(blk.back_nets(), blk.td_root(rd, model.gamma, 1.0, model._target_q[i], model._loss_now, model._loss_sums[f"critic{i}"],
+                                                     adam_advance=[model.critic.optimizer_list[i]] if fuse_opt else ()))
 
     def captured(self, model, i: int) -> dict:
-        B = self.B
-        return dict(target_q=model._target_q[i].clone(), current_q=[self.q_out[i, 0].clone().view(B, 1), self.q_out[i, 1].clone().view(B, 1)],
-                    critic_loss=model._loss_now.clone(), actor_loss=None)
+        return self.blocks[i].captured(model._target_q[i], model._loss_now)
 
     def critic_step(self, model, i: int, x_cur, x_next, rd) -> None:
         """Agent i's critic step (:146-164): 3 launches."""
-        fuse_opt = _adam_in_wgrad(model, self.B)
-        hip_ops.q_chain_fwd(self._nets4(i, x_cur, x_next), self.W, self.D, self.H1, self.H2, self.B, self.t_q)
+        fuse_opt, blk = _adam_in_wgrad(model, self.B), self.blocks[i]
+        blk.forward(blk.nets4(x_cur, x_next, target_roles=self.TARGET_ROLES), blk.t_q4)
         self._backward(model, i, rd, fuse_opt)
         opt = model.critic.optimizer_list[i]
-        if fuse_opt:
-            hip_ops.linear_bwd_weight_adam_sets(self._sets(i, x_cur, True), [opt])
-        else:
-            hip_ops.linear_bwd_weight_sets(self._sets(i, x_cur, False))
+        blk.apply([blk], x_cur, fuse_opt, [opt])
+        if not fuse_opt:
             model._allreduce_grads(model.policy.critic_slices[i])
             opt.step()
 
@@ -518,23 +507,16 @@ class MaddpgCriticChain:
         """Every agent's critic step of an update WITHOUT a policy step: the agents' steps do not depend on each other (no soft update in
         between), so their 4 x n_agents networks share ONE forward launch; a backward launch per agent; a dW / db + Adam launch per two
         agents. The same kernels on the same operands as `critic_step`: bit-identical."""
-        fuse_opt = _adam_in_wgrad(model, self.B)
-        nets = [net for i in range(self.n) for net in self._nets4(i, x_cur, x_next)]
-        hip_ops.q_chain_fwd(nets, self.W, self.D, self.H1, self.H2, self.B, self.t_q)
+        fuse_opt, blocks = _adam_in_wgrad(model, self.B), self.blocks
+        blocks[0].forward([net for blk in blocks for net in blk.nets4(x_cur, x_next, target_roles=self.TARGET_ROLES)], blocks[0].t_q4)
         for i in range(self.n):
             self._backward(model, i, rd, fuse_opt)
             if capture is not None:
                 capture.append(self.captured(model, i))
         opts = model.critic.optimizer_list
-        if fuse_opt:
-            for i0 in range(0, self.n, 2):
-                group = list(range(i0, min(i0 + 2, self.n)))
-                sets = [st for k, i in enumerate(group) for st in self._sets(i, x_cur, True, opt_index=k)]
-                hip_ops.linear_bwd_weight_adam_sets(sets, [opts[i] for i in group])
-        else:
-            for i0 in range(0, self.n, 2):
-                group = list(range(i0, min(i0 + 2, self.n)))
-                hip_ops.linear_bwd_weight_sets([st for i in group for st in self._sets(i, x_cur, False)])
+        for i0 in range(0, self.n, 2):
+            TwinCriticBlock.apply(blocks[i0:i0 + 2], x_cur, fuse_opt, opts[i0:i0 + 2])
+        if not fuse_opt:
             for i in range(self.n):
                 model._allreduce_grads(model.policy.critic_slices[i])
             opts[0].step_with(*opts[1:])

@@ -1328,6 +1328,14 @@ def chain_net(layers, x=None, h1=None, h2=None, q_part=None, role: int = 0) -> "
                        _dp(q_part), role, 0)
 
 
+def chain_check_nets(nets, w_in: int, h1: int, h2: int) -> None:
+    """Every ((w1, b1), (w2, b2), (w3, b3)) of `nets` is what the chain kernels read behind chain_net's raw pointers: float32, contiguous,
+    on the current device, shaped by W / H1 / H2. For whoever binds the networks, once (chain_net runs every step)."""
+    for i, ((w1, b1), (w2, b2), (w3, b3)) in enumerate(nets):
+        for t, nm, shape in ((w1, "w1", (h1, w_in)), (b1, "b1", (h1,)), (w2, "w2", (h2, h1)), (b2, "b2", (h2,)), (w3, "w3", (1, h2)), (b3, "b3", (1,))):
+            _chk(t, f"Q network {i}: {nm}", shape, th.float32)
+
+
 def q_chain_fwd(nets, w_in: int, obs_dim: int, h1: int, h2: int, batch: int, tiles: int, fin: Optional["nv.SacHeadFin"] = None):
     """cstr_q_chain_fwd_f32: n_nets Q networks (layer 1 recomputed, layer 2 one MFMA column group per workgroup, head as partials)."""
     arr = (nv.ChainNet * len(nets))(*nets)

@@ -154,7 +154,7 @@ class SAC(OffPolicyAlgorithm):
         (c_out, c_sum), (a_out, a_sum) = self._loss_slot("critic"), self._loss_slot("actor")
         pb, gather = None, None
         chain = self._chain_for(batch_size)
-        if chain is not None:  # the row-chain kernels (core/common/chain.py): 10 launches instead of 20
+        if chain is not None:  # the row-chain kernels (core/common/chain.py): 8 launches instead of 20 (10 under data-parallel)
             pb = self._packed_batch(batch_size)
             gather = self.replay_buffer.take_predrawn(pb) if fused.USE_GATHER_IN_FIRST_LAYER else None
             if gather is None:

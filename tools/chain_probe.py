@@ -34,34 +34,29 @@ def chain_launches(model, B: int, tiles=None) -> dict:
     fa = model._fast_actor
     if fa.rng_ctl is None:
         fa.rng_ctl = hip_ops.new_rng_ctl(0, model.device)
-    W, D, A = c.W, c.D, c.A
+    blk, D, A = c.block, c.D, c.A
     fin = nv.SacHeadFin(c.head_part.data_ptr(), fa._hb.data_ptr(), c.eps_all.data_ptr(), c.n_head_parts, A, D, nv.CHAIN_HEAD_GAUSSIAN, 2 * B, B, 0.0, 0.0,
                         pb.x_pi.data_ptr(), pb.x_next.data_ptr(), c.params.data_ptr(), c.logp_pi.data_ptr(), c.logp_next.data_ptr())
-    nets4 = [hip_ops.chain_net(c.crit[0], pb.x_data, c.c_h1[0], c.c_h2[0], c.q_part4[0], nv.CHAIN_ROLE_STORE_PI),
-             hip_ops.chain_net(c.crit[1], pb.x_data, c.c_h1[1], c.c_h2[1], c.q_part4[1], nv.CHAIN_ROLE_PLAIN),
-             hip_ops.chain_net(c.targ[0], pb.x_next, None, None, c.q_part4[2], nv.CHAIN_ROLE_NEXT_STORE),
-             hip_ops.chain_net(c.targ[1], pb.x_next, None, None, c.q_part4[3], nv.CHAIN_ROLE_NEXT)]
-    nets2 = [hip_ops.chain_net(c.crit[g], pb.x_pi, c.c_h1[g], c.c_h2[g], c.q_part2[g]) for g in range(2)]
-    back = [hip_ops.chain_net(c.crit[g], None, c.c_h1[g], c.c_h2[g]) for g in range(2)]
+    # the step's own lists and roots (core/common/chain.py:TwinCriticBlock), without the RNG / Adam advances (idempotent)
+    nets4 = blk.nets4(pb.x_data, pb.x_next, roles=c.ROLES)
+    nets2, back = blk.pi_nets(pb.x_pi), blk.back_nets()
     ent = th.ones(1, device=model.device)
-    b3s = [c.crit[0][2][1], c.crit[1][2][1], c.targ[0][2][1], c.targ[1][2][1]]
     loss = th.zeros(1, device=model.device)
     tq = th.zeros(B, 1, device=model.device)
-    root = hip_ops.chain_root("td", B, [c.q_part4[g] for g in range(4)], b3s, c.n_q4, gamma=0.99, scale=0.5, next_logp=c.logp_next, rew=rd.rewards,
-                              done=rd.dones, ent_coef=ent, target_out=tq, q_out=c.q_out, gq_out=c.gq, loss_out=loss)
-    aroot = hip_ops.chain_root("sac_actor", B, [c.q_part2[0], c.q_part2[1]], b3s[:2], c.n_q2, ent_coef=ent, logp=c.logp_pi, q_out=c.qpi_out, loss_out=loss)
+    root = blk.td_root(rd, 0.99, 0.5, tq, loss, None, next_logp=c.logp_next, ent_coef=ent)
+    aroot = blk.pi_root("sac_actor", ent_coef=ent, logp=c.logp_pi, loss_out=loss)
     actor_f = 2.0 * (D * c.aH1 + c.aH1 * c.aH2 + c.aH2 * 2 * A)
-    q_f = 2.0 * (W * c.cH1 + c.cH1 * c.cH2 + c.cH2)
+    q_f = 2.0 * (blk.W * blk.H1 + blk.H1 * blk.H2 + blk.H2)
     keep = (c, pb, fin, nets4, nets2, back, root, aroot, ent, loss, tq)  # alive as long as the callables
     return dict(
         sac_actor_chain_fwd=(lambda k=keep: hip_ops.sac_actor_chain_fwd(c.actor, B, None, pb.x_pi, pb.x_next, None, None, c.a_h1, c.a_h2, c.head_part, c.t_act,
                                                                         head_rng_ctl=fa.rng_ctl, eps_all=c.eps_all), actor_f * 2 * B),
-        q_chain_fwd_4nets=(lambda k=keep: hip_ops.q_chain_fwd(nets4, W, D, c.cH1, c.cH2, B, c.t_q4, fin), q_f * 4 * B),
-        q_chain_bwd_td=(lambda k=keep: hip_ops.q_chain_bwd(back, root, W, D, c.cH1, c.cH2, c.t_qb, dz2=c.dz2c, dz1=c.dz1c), 2.0 * c.cH1 * c.cH2 * 2 * B),
-        q_chain_fwd_2nets=(lambda k=keep: hip_ops.q_chain_fwd(nets2, W, D, c.cH1, c.cH2, B, c.t_q2), q_f * 2 * B),
-        q_chain_bwd_actor=(lambda k=keep: hip_ops.q_chain_bwd(back, aroot, W, D, c.cH1, c.cH2, c.t_qb, gact_part=c.gact_part), 2.0 * c.cH1 * c.cH2 * 2 * B),
-        sac_actor_chain_bwd=(lambda k=keep: hip_ops.sac_actor_chain_bwd(c.actor, c.gact_part, 2, c.n_gact, ent, pb.x_pi, c.params, c.eps_all, c.a_h1, c.a_h2,
-                                                                        c.g_params, c.dz2a, c.dz1a, B, c.t_ab), 2.0 * (c.aH1 * c.aH2 + 2 * A * c.aH2) * B))
+        q_chain_fwd_4nets=(lambda k=keep: blk.forward(nets4, blk.t_q4, fin), q_f * 4 * B),
+        q_chain_bwd_td=(lambda k=keep: blk.td_backward(back, root), 2.0 * blk.H1 * blk.H2 * 2 * B),
+        q_chain_fwd_2nets=(lambda k=keep: blk.forward(nets2, blk.t_qpi), q_f * 2 * B),
+        q_chain_bwd_actor=(lambda k=keep: blk.pi_backward(back, aroot), 2.0 * blk.H1 * blk.H2 * 2 * B),
+        sac_actor_chain_bwd=(lambda k=keep: hip_ops.sac_actor_chain_bwd(c.actor, blk.gact_part, 2, blk.n_gact, ent, pb.x_pi, c.params, c.eps_all, c.a_h1,
+                                                                        c.a_h2, c.g_params, c.dz2a, c.dz1a, B, c.t_ab), 2.0 * (c.aH1 * c.aH2 + 2 * A * c.aH2) * B))
 
 
 def main():
