@@ -611,6 +611,15 @@ typedef struct cstr_wgrad_adam_set {
 } cstr_wgrad_adam_set_t;
 int cstr_linear_bwd_weight_adam_sets_f32(const cstr_wgrad_adam_set_t *sets, int n_sets, const cstr_adam_opt_t *opts, int n_opts,
                                          const cstr_adam_seg_t *flat, int n_flat, cstr_stream_t stream);
+/* Test hooks of that launch. It has two kernels that write the same bits: a lean one (slice lookup from preloaded registers, one
+ * record per set, every wave a share of the tile's optimiser step, a body chosen per workgroup) and the one it replaced.
+ * cstr_wgrad_adam_lean(on): on = 0 launches the earlier kernel from now on, on > 0 the lean one (the default), on < 0 changes
+ * nothing; returns the setting before the call. A launch of 65535 workgroups or more always takes the earlier kernel.
+ * cstr_wgrad_adam_tile_body: the body the lean kernel runs for tile (tile_n, tile_k) of an [n][k] gradient reduced over m rows:
+ * 0 full (m = 256, tile complete in n and k), 1 k-narrow (k <= 16, complete in n), 2 n-narrow (n <= 16, complete in k),
+ * 3 generic (every other tile: the earlier kernel's tile body). */
+int cstr_wgrad_adam_lean(int on);
+int cstr_wgrad_adam_tile_body(int64_t m, int64_t n, int64_t k, int64_t tile_n, int64_t tile_k);
 
 /* ---- row-chain kernels: a gradient step's forward / backward chains with FEWER launch boundaries ------------------------------
  * A chain of Linear layers is row-local (row r of layer l+1 needs row r of layer l only), but a launch boundary is the cheapest

@@ -152,14 +152,14 @@ __device__ __forceinline__ void polyak_body(const float *__restrict__ param, flo
     for (int64_t i = (nv << 2) + tid; i < n; i += stride) target[i] = polyak1(param[i], target[i], tau, om);
 }
 
-// the step's scalars from (pre-advanced) control words: what thread 0 of adam_body computes
-__device__ __forceinline__ AdamScalars adam_scalars_advanced(const int64_t *adam_ctl, const double *lr, const double beta1, const double beta2,
-                                                             const double eps, const float gscale)
+// the step's scalars from (pre-advanced) control words: what thread 0 of adam_body computes. pow1 / pow2 = beta1^step / beta2^step
+// (adam_ctl[2], adam_ctl[3] as f64), lr = lr[0]: a caller may have read them long before it needs the scalars
+__device__ __forceinline__ AdamScalars adam_scalars_from(const double pow1, const double pow2, const double lr, const double beta1, const double beta2,
+                                                         const double eps, const float gscale)
 {
-    const double *pw = reinterpret_cast<const double *>(adam_ctl + 2);
-    const double bc1 = 1.0 - pw[0], bc2 = 1.0 - pw[1];
+    const double bc1 = 1.0 - pow1, bc2 = 1.0 - pow2;
     AdamScalars a;
-    a.step_size_neg = -(float)(lr[0] / bc1);
+    a.step_size_neg = -(float)(lr / bc1);
     a.bc2_sqrt = (float)sqrt(bc2);
     a.w1 = (float)(1.0 - beta1);
     a.b2 = (float)beta2;
@@ -167,6 +167,13 @@ __device__ __forceinline__ AdamScalars adam_scalars_advanced(const int64_t *adam
     a.eps = (float)eps;
     a.gscale = gscale;
     return a;
+}
+
+__device__ __forceinline__ AdamScalars adam_scalars_advanced(const int64_t *adam_ctl, const double *lr, const double beta1, const double beta2,
+                                                             const double eps, const float gscale)
+{
+    const double *pw = reinterpret_cast<const double *>(adam_ctl + 2);
+    return adam_scalars_from(pw[0], pw[1], lr[0], beta1, beta2, eps, gscale);
 }
 
 }  // namespace

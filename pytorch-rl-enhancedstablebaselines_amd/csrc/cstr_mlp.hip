@@ -710,6 +710,190 @@ __global__ __launch_bounds__(64 * WAVES) void linear_bwd_weight_adam_sets_kernel
                                              local / kt);
 }
 
+// ---- the same launch, lean (what cstr_linear_bwd_weight_adam_sets_f32 launches unless cstr_wgrad_adam_lean(0) asks for the kernel above) ----
+// Three things differ, none of them in the arithmetic of any element:
+//   * no dependent argument reads in front of the first row request: the slice boundaries travel as 16-bit values in the first 16
+//     dwords of the kernarg, which arrive in SGPRs with the wave (-amdgpu-kernarg-preload-count=16), and a set's record (WaSet) holds
+//     everything a tile needs, the optimiser's block included: one scalar read behind the lookup instead of first[] -> set -> opts[];
+//   * every wave takes a share of the tile's optimiser step: wave w owns row-register e = w (row n0 + 4h + w, column k0 + r), requests
+//     that ONE element's parameter / moments / target at entry, and after the split-M combine stores dW and runs Adam on it, instead
+//     of wave 0 waiting for four elements per lane behind its rows and updating them alone;
+//   * the body is chosen per workgroup (wa_tile_body): tiles of a 256-row launch that are complete in N and K run a straight-line
+//     body without predicates, tiles of a narrow matrix (K <= 16 or N <= 16) the same body under ONE lane mask, everything else
+//     (other M, ragged tiles) linear_bwd_weight_tile<.., ADAM = true> as above.
+enum { WA_FULL = 0, WA_KNARROW = 1, WA_NNARROW = 2, WA_GENERIC = 3 };
+constexpr int WA_ROWS = 256;       // the lean bodies' M: one trip of the row loop, every row of every wave's batch exists
+constexpr int WA_BOUNDS = 30;      // 16-bit slice boundaries behind the head word (sets + flat segments <= 20)
+
+__host__ __device__ inline bool wa_set_lean(const int64_t m, const int64_t n, const int64_t k) { return m == WA_ROWS && n * k < (1 << 28); }
+
+__host__ __device__ inline int wa_tile_body(const bool set_lean, const int n, const int k, const int tile_n, const int tile_k)
+{
+    if (!set_lean) return WA_GENERIC;
+    const bool n_full = 16 * tile_n + 16 <= n, k_full = 16 * tile_k + 16 <= k;
+    if (n_full && k_full) return WA_FULL;
+    if (k <= 16 && n_full) return WA_KNARROW;
+    if (n <= 16 && k_full) return WA_NNARROW;
+    return WA_GENERIC;
+}
+
+struct WaSet {  // one Linear: cstr_wgrad_adam_set_t and its cstr_adam_opt_t in one record
+    const float *dz, *x;
+    float *dw, *db, *w, *w_m, *w_v, *b, *b_m, *b_v, *shadow, *w_target, *b_target;
+    const int64_t *adam_ctl; const double *lr;
+    double beta1, beta2, eps;
+    int ldx, m, n, k, kt, lean;
+    float tau, gscale;
+};
+struct WaSets { WaSet s[CSTR_MAX_LINEAR_SETS]; cstr_adam_seg_t f[CSTR_MAX_ADAM_SEGS]; };
+
+#ifdef CSTR_POLICY_STAMPS
+#define WAL_STAMP(i) do { if (lane == 0 && blockIdx.x < 4096) policy_stamps[(blockIdx.x * 16 + wave) * 8 + (i)] = __builtin_amdgcn_s_memtime(); } while (0)
+#else
+#define WAL_STAMP(i) do { } while (0)
+#endif
+
+struct WaLds {
+    float part[4][4][64];  // [wave][row-register e][lane]: read back as [v][own e][lane], no bank conflicts either way
+    float colpart[4][64];
+    AdamScalars sc;
+};
+
+// One 16 x 16 tile of dW (and db) of a 256-row set + its optimiser step, four waves. MASKED: the tile is complete in only one of
+// N / K; lanes outside re-read column 0 of the tile (their products land in outputs that are not stored) and sit out the update.
+template <bool MASKED>
+__device__ __forceinline__ void wgrad_adam_lean_tile(const WaSet &q, const int tile_k, const int tile_n, WaLds &lds)
+{
+    const int lane = threadIdx.x & 63, r = lane & 15, h = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int N = q.n, K = q.k, ldx = q.ldx;
+    const int k0 = tile_k * 16, n0 = tile_n * 16;
+    const int row = n0 + 4 * h + wave, colk = k0 + r;
+    const bool ok = !MASKED || (row < N && colk < K);
+    const bool bias_lane = q.db != nullptr && tile_k == 0 && wave == 0 && lane < 16 && (!MASKED || n0 + lane < N);
+    const int i = row * K + colk;
+    WAL_STAMP(0);
+    // requested in FRONT of the rows (returns are in order, and this is one element per lane): the control words first, so that the
+    // last wave turns them into the step's scalars while its rows are still in flight. A set without a target reads its parameter
+    // twice (no branch, no wait on the way to the row requests).
+    const double *ctl = reinterpret_cast<const double *>(q.adam_ctl + 2);
+    const double pow1 = ctl[0], pow2 = ctl[1], lr = q.lr[0];
+    float pw = 0.0f, pm = 0.0f, pv = 0.0f, pt = 0.0f, bw = 0.0f, bm = 0.0f, bvv = 0.0f, bt = 0.0f;
+    if (ok) {
+        pw = q.w[i]; pm = q.w_m[i]; pv = q.w_v[i];
+        pt = (q.w_target ? q.w_target : q.w)[i];
+    }
+    if (bias_lane) {
+        bw = q.b[n0 + lane]; bm = q.b_m[n0 + lane]; bvv = q.b_v[n0 + lane];
+        bt = (q.b_target ? q.b_target : q.b)[n0 + lane];
+    }
+    WAL_STAMP(1);  // (where linear_bwd_weight_tile has it: in front of the first row request)
+    // rows 16 * wave + 64 * u + 4 * h + j: the lane's part of the address in the VGPR offset, the wave's in the scalar offset
+    const __amdgpu_buffer_rsrc_t rdz = operand_rsrc(q.dz, (int64_t)WA_ROWS * N), rxx = operand_rsrc(q.x, (int64_t)(WA_ROWS - 1) * ldx + K);
+    const int ar = (MASKED && n0 + r >= N) ? 0 : r, br = (MASKED && colk >= K) ? 0 : r;
+    const int va = 4 * (4 * h * N + n0 + ar), vb = 4 * (4 * h * ldx + k0 + br);
+    float4 a[4], b[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int m = 16 * wave + 64 * u;
+        a[u].x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rdz, va, 4 * (m * N), 0));
+        a[u].y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rdz, va, 4 * ((m + 1) * N), 0));
+        a[u].z = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rdz, va, 4 * ((m + 2) * N), 0));
+        a[u].w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rdz, va, 4 * ((m + 3) * N), 0));
+        b[u].x = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rxx, vb, 4 * (m * ldx), 0));
+        b[u].y = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rxx, vb, 4 * ((m + 1) * ldx), 0));
+        b[u].z = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rxx, vb, 4 * ((m + 2) * ldx), 0));
+        b[u].w = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rxx, vb, 4 * ((m + 3) * ldx), 0));
+    }
+    // the step's scalars, beside the reduction: an f64 division and a square root on one lane of the last wave
+    if (threadIdx.x == 192) lds.sc = adam_scalars_from(pow1, pow2, lr, q.beta1, q.beta2, q.eps, q.gscale);
+    f32x4 acc0 = {0.0f, 0.0f, 0.0f, 0.0f}, acc1 = {0.0f, 0.0f, 0.0f, 0.0f};
+    float colsum = 0.0f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {  // linear_bwd_weight_tile's order, operand for operand
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].x, b[u].x, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].y, b[u].y, acc1, 0, 0, 0);
+        acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].z, b[u].z, acc0, 0, 0, 0);
+        acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u].w, b[u].w, acc1, 0, 0, 0);
+        colsum += (a[u].x + a[u].y) + (a[u].z + a[u].w);
+    }
+    const bool want_db = q.db != nullptr && tile_k == 0;
+    if (want_db) lds.colpart[wave][lane] = colsum;
+    const f32x4 acc = acc0 + acc1;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) lds.part[wave][e][lane] = acc[e];
+    WAL_STAMP(2);
+    __syncthreads();  // LDS only: the optimiser's operands stay in flight across it
+    WAL_STAMP(3);
+    // element e = wave of the tile, the waves' partial sums in linear_bwd_weight_tile's order
+    const float g = ((lds.part[0][wave][lane] + lds.part[1][wave][lane]) + lds.part[2][wave][lane]) + lds.part[3][wave][lane];
+    const AdamScalars s = lds.sc;
+    WAL_STAMP(4);
+    if (ok) {
+        q.dw[i] = g;
+        adam1(pw, g, pm, pv, s);
+        q.w[i] = pw; q.w_m[i] = pm; q.w_v[i] = pv;
+        if (q.w_target) q.w_target[i] = polyak1(pw, pt, q.tau, 1.0f - q.tau);
+        if (q.shadow)  // the tile-major copy the rollout kernel reads (cstr_policy_swizzle_f32's layout)
+            q.shadow[((tile_n * q.kt + tile_k) * 64 + 4 * h + wave + 16 * (r >> 2)) * 4 + (r & 3)] = pw;
+    }
+    if (bias_lane) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int v = 0; v < 4; ++v) sum += (lds.colpart[v][lane] + lds.colpart[v][lane + 16]) + (lds.colpart[v][lane + 32] + lds.colpart[v][lane + 48]);
+        q.db[n0 + lane] = sum;
+        adam1(bw, sum, bm, bvv, s);
+        q.b[n0 + lane] = bw; q.b_m[n0 + lane] = bm; q.b_v[n0 + lane] = bvv;
+        if (q.b_target) q.b_target[n0 + lane] = polyak1(bw, bt, q.tau, 1.0f - q.tau);
+    }
+    WAL_STAMP(5);
+}
+
+// h0 = n_sets | n_flat << 16; h1 .. h15: WA_BOUNDS 16-bit values, the first workgroup of slice 1, 2, ... up to the grid size, then 0xffff
+__global__ __launch_bounds__(256) void linear_bwd_weight_adam_sets_lean_kernel(const unsigned h0, const unsigned h1, const unsigned h2, const unsigned h3,
+                                                                               const unsigned h4, const unsigned h5, const unsigned h6, const unsigned h7,
+                                                                               const unsigned h8, const unsigned h9, const unsigned h10, const unsigned h11,
+                                                                               const unsigned h12, const unsigned h13, const unsigned h14, const unsigned h15,
+                                                                               const WaSets sets)
+{
+    const unsigned hw[16] = {h0, h1, h2, h3, h4, h5, h6, h7, h8, h9, h10, h11, h12, h13, h14, h15};
+    const unsigned b = blockIdx.x, n_sets = h0 & 0xffffu;
+    unsigned lo = 0, hi = 0, i = 0;  // slice i = workgroups [lo, hi): compares on registers that came with the wave
+#pragma unroll
+    for (int t = 0; t < WA_BOUNDS; ++t) {
+        hi = (hw[1 + (t >> 1)] >> (16 * (t & 1))) & 0xffffu;
+        if (b < hi) break;
+        lo = hi;
+        ++i;
+    }
+    const unsigned local = (b - lo) & 0xffffu, count = (hi - lo) & 0xffffu;
+    if (__builtin_expect(i < n_sets, 1)) {
+        // the whole record in ONE batch of scalar reads, here: left to itself the compiler reads it field by field where each is first
+        // used, a round trip each time
+        const WaSet q = sets.s[i];
+        asm volatile("" ::"s"(q.dz), "s"(q.x), "s"(q.dw), "s"(q.db), "s"(q.w), "s"(q.w_m), "s"(q.w_v), "s"(q.b), "s"(q.b_m), "s"(q.b_v), "s"(q.shadow),
+                     "s"(q.w_target), "s"(q.b_target), "s"(q.adam_ctl), "s"(q.lr), "s"(q.beta1), "s"(q.beta2), "s"(q.eps), "s"(q.ldx), "s"(q.m),
+                     "s"(q.n), "s"(q.k), "s"(q.kt), "s"(q.lean), "s"(q.tau), "s"(q.gscale));
+        __shared__ WaLds lds;
+        const unsigned kt = (unsigned)q.kt & 0xffffu;
+        const int tile_n = (int)(local / kt), tile_k = (int)(local - (unsigned)tile_n * kt);
+        const int body = wa_tile_body(q.lean != 0, q.n, q.k, tile_n, tile_k);
+        if (__builtin_expect(body == WA_GENERIC, 0)) {  // (a layout hint the compiler does not take: this body still precedes the lean ones)
+            const AdamTile ad = {q.w, q.w_m, q.w_v, q.b, q.b_m, q.b_v, q.shadow, q.adam_ctl, q.lr, q.beta1, q.beta2, q.eps, q.gscale,
+                                 q.w_target, q.b_target, q.tau};
+            linear_bwd_weight_tile<4, true, true>(q.dz, q.x, q.ldx, q.dw, q.db, q.m, q.n, q.k, 0, &ad, tile_k, tile_n);
+            return;
+        }
+        if (__builtin_expect(body == WA_FULL, 1)) { wgrad_adam_lean_tile<false>(q, tile_k, tile_n, lds); return; }
+        wgrad_adam_lean_tile<true>(q, tile_k, tile_n, lds);
+        return;
+    }
+    const cstr_adam_seg_t &f = sets.f[i - n_sets];
+    if (f.polyak_source) { polyak_body(f.polyak_source, f.param, (float)f.tau, (float)(1.0 - f.tau), f.n, local, count); return; }
+    adam_body(f.param, f.grad, f.exp_avg, f.exp_avg_sq, f.adam_ctl, f.lr, f.beta1, f.beta2, f.eps, f.grad_scale, f.n, AdamShadow{nullptr, 0, 0, 4, 1},
+              f.own_target, (float)f.tau, (float)(1.0 - f.tau), true, local, count);
+}
+
 // ---- last hidden layer + scalar head of a Q network ------------------------------------------------------------
 // create_mlp(..., output_dim = 1) ends in  y = act(z + b1);  q = y . w2 + b2  (core/common/torch_layers.py:110-183,
 // ContinuousCritic: core/common/policies.py:960-987). The head is a matrix-VECTOR product (n = 1), which rocBLAS runs
@@ -2841,11 +3025,15 @@ extern "C" int cstr_linear_bwd_weight_sets_f32(const cstr_wgrad_set_t *sets, int
     return (int)hipGetLastError();
 }
 
+static int wa_lean_enabled = 1;  // cstr_wgrad_adam_lean: 0 = launch the parent kernel (the lean one is checked against it, same process)
+
 extern "C" int cstr_linear_bwd_weight_adam_sets_f32(const cstr_wgrad_adam_set_t *sets, int n_sets, const cstr_adam_opt_t *opts, int n_opts,
                                                     const cstr_adam_seg_t *flat, int n_flat, cstr_stream_t stream)
 {
     if (!sets || n_sets <= 0 || !opts || n_opts <= 0 || n_flat < 0 || (n_flat > 0 && !flat)) return CSTR_E_BADARG;
     if (n_sets > CSTR_MAX_LINEAR_SETS || n_opts > CSTR_MAX_ADAM_SEGS || n_flat > CSTR_MAX_ADAM_SEGS) return CSTR_E_UNSUPPORTED;
+    static_assert(CSTR_MAX_LINEAR_SETS + CSTR_MAX_ADAM_SEGS <= WA_BOUNDS, "the slice boundaries must fit the preloaded head");
+    static_assert(sizeof(WaSets) + 64 <= 4096, "kernarg segment");
     WgradAdamSets t;
     t.n_sets = n_sets;
     t.n_flat = n_flat;
@@ -2877,8 +3065,40 @@ extern "C" int cstr_linear_bwd_weight_adam_sets_f32(const cstr_wgrad_adam_set_t 
     }
     t.first[n_sets + n_flat] = (int)total;
     if (total > 0x7fffffff) return CSTR_E_UNSUPPORTED;
-    linear_bwd_weight_adam_sets_kernel<4, true><<<dim3((unsigned)total), 256, 0, (hipStream_t)stream>>>(t);
+    if (!wa_lean_enabled || total >= 0xffff) {  // the parent kernel: asked for (cstr_wgrad_adam_lean), or boundaries beyond 16 bits
+        linear_bwd_weight_adam_sets_kernel<4, true><<<dim3((unsigned)total), 256, 0, (hipStream_t)stream>>>(t);
+        return (int)hipGetLastError();
+    }
+    WaSets l;
+    unsigned hw[16], bound[WA_BOUNDS];
+    for (int j = 0; j < WA_BOUNDS; ++j) bound[j] = j < n_sets + n_flat ? (unsigned)t.first[j + 1] : 0xffffu;
+    hw[0] = (unsigned)n_sets | (unsigned)n_flat << 16;
+    for (int j = 1; j < 16; ++j) hw[j] = bound[2 * j - 2] | bound[2 * j - 1] << 16;
+    for (int i = 0; i < n_sets; ++i) {
+        const cstr_wgrad_adam_set_t &q = sets[i];
+        const cstr_adam_opt_t &o = opts[q.opt];
+        l.s[i] = WaSet{q.g.dz, q.g.x, q.g.dw, q.g.db, q.w, q.w_m, q.w_v, q.b, q.b_m, q.b_v, q.shadow, q.w_target, q.b_target, o.adam_ctl, o.lr,
+                       o.beta1, o.beta2, o.eps, (int)q.g.ldx, (int)q.g.m, (int)q.g.n, (int)q.g.k, (int)((q.g.k + 15) / 16),
+                       wa_set_lean(q.g.m, q.g.n, q.g.k) ? 1 : 0, q.tau, o.grad_scale};
+    }
+    for (int i = 0; i < n_flat; ++i) l.f[i] = flat[i];
+    linear_bwd_weight_adam_sets_lean_kernel<<<dim3((unsigned)total), 256, 0, (hipStream_t)stream>>>(hw[0], hw[1], hw[2], hw[3], hw[4], hw[5], hw[6], hw[7], hw[8],
+                                                                                                   hw[9], hw[10], hw[11], hw[12], hw[13], hw[14], hw[15], l);
     return (int)hipGetLastError();
+}
+
+extern "C" int cstr_wgrad_adam_lean(int on)
+{
+    const int was = wa_lean_enabled;
+    if (on >= 0) wa_lean_enabled = on != 0;
+    return was;
+}
+
+extern "C" int cstr_wgrad_adam_tile_body(int64_t m, int64_t n, int64_t k, int64_t tile_n, int64_t tile_k)
+{
+    if (m <= 0 || n <= 0 || k <= 0 || tile_n < 0 || tile_k < 0 || tile_n * 16 >= n || tile_k * 16 >= k) return CSTR_E_BADARG;
+    if (n > 0x7fffff || k > 0x7fffff) return CSTR_E_UNSUPPORTED;
+    return wa_tile_body(wa_set_lean(m, n, k), (int)n, (int)k, (int)tile_n, (int)tile_k);
 }
 
 extern "C" int cstr_gaussian_head_gemm_fwd_f32(const float *hidden, int64_t ldh, const float *w, const float *bias, float *params,

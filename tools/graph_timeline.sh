@@ -12,7 +12,10 @@ python3 - <<PY
 import csv, collections, json, statistics
 rows = list(csv.DictReader(open("$f")))
 rows.sort(key=lambda r: int(r["Start_Timestamp"]))
-name = lambda r: r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0][:70]
+short = lambda r: r["Kernel_Name"].replace("(anonymous namespace)::", "").replace("void ", "").split("(")[0][:60]
+# two launches of one kernel per iteration (the critics' and the actor's dW + Adam launch) are told apart by their workgroup count
+split = "Grid_Size_X" in rows[0] and "Workgroup_Size_X" in rows[0]
+name = lambda r: short(r) + (f" wg={int(r['Grid_Size_X']) // max(int(r['Workgroup_Size_X']), 1)}" if split and "adam_sets" in r["Kernel_Name"] else "")
 # steady state: the last 60 % of the dispatches
 rows = rows[int(0.4 * len(rows)):]
 dur, itv = collections.defaultdict(list), collections.defaultdict(list)

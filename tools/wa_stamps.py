@@ -2,7 +2,8 @@
 """Phase stamps of the dW / db + Adam launch (diagnostic build, `make -C .../csrc diag`): a short SAC run under hipGraph replay, then the
 stamps the LAST launches left (blocks < 300: the actor's launch, the others: the critic's). Per workgroup, cycles after its first
 stamp: 1 operands and moments requested | 2 rows loaded + MFMAs done (per wave) | 3 past the split-M barrier | 4 Adam scalars read
-(first wave) | 5 stores issued."""
+(first wave) | 5 stores issued. The lean kernel stamps 1 directly in front of its first row request (behind the read of the set's
+record and the optimiser operands' requests) and 4 / 5 on all four waves: each updates one element per lane."""
 import ctypes as C
 import os
 import sys
