@@ -64,6 +64,8 @@ class BCQ(OfflineAlgorithm):
         if self._fused_learner:
             pol.fast = self._fast = fused.FastBcq(pol)
             self._fast.rng_ctl = self._device_rng()  # one Philox stream for train() and predict(); set_random_seed reseeds it in place
+            # the target is computed here (`bcq_target`), so the losses are launches of their own: no loss-root form
+            self._critic_block = fused.PerLayerTwinCritic(self._fast.critic, self._fast.critic_t, loss_roots=False)
 
     @property
     def fused_learner(self) -> bool:
@@ -90,8 +92,7 @@ class BCQ(OfflineAlgorithm):
         if b is None or b["target_q"].shape[0] != batch_size:
             e = lambda *sh: th.empty(*sh, dtype=th.float32, device=self.device)  # noqa: E731
             lat, a = self._fast.latent, self._fast.act_dim
-            b = self._bufs = dict(target_q=e(batch_size, 1), gq=e(2, batch_size, 1), g_recon=e(batch_size, a),
-                                  gkl=(e(batch_size, lat), e(batch_size, lat)))
+            b = self._bufs = dict(target_q=e(batch_size, 1), g_recon=e(batch_size, a), gkl=(e(batch_size, lat), e(batch_size, lat)))
         return b
 
     # ---- train -------------------------------------------------------------------------------------------------------
@@ -178,14 +179,10 @@ class BCQ(OfflineAlgorithm):
 
     def _gradient_step_fused(self, batch_size: int, n_updates: int) -> None:
         """bcq.py:137-207 on the kernel path (core/common/fused.py FastBcq, csrc/cstr_bcq.hip)."""
-        pol, fast = self.policy, self._fast
-        if self._use_packed_batch():
-            pb = self._packed_batch(batch_size)
-            self.replay_buffer.sample_packed_into(pb)  # :140 + cat([obs, act]) for the encoder and the critics
-            rd, x_data = pb.samples, pb.x_data
-        else:  # a VecNormalize'd buffer: the contiguous batch, one cat launch
-            rd = self.replay_buffer.sample_into(self._batch(batch_size))
-            x_data = th.cat([rd.observations, rd.actions], dim=1)
+        pol, fast, blk = self.policy, self._fast, self._critic_block
+        pb, _, rd = self._sample(batch_size)  # :140 (+ cat([obs, act]) for the encoder and the critics)
+        # (a VecNormalize'd buffer: the contiguous batch, one cat launch)
+        x_data = pb.x_data if pb is not None else th.cat([rd.observations, rd.actions], dim=1)
         B = x_data.shape[0]
         bufs = self._step_bufs(B)
         # VAE step (:143-154): encoder, merged head + latent launch, decoder, loss launch, backward, Adam; the copy into the target
@@ -204,28 +201,22 @@ class BCQ(OfflineAlgorithm):
         # critic step (:176-186)
         # both Q networks per layer in one pointer-table launch, as SAC / TD3 evaluate their critics (fused._TwinPairFn)
         qs = fused.twin_chain_forward(fast.critic, x_data) if fused.twin_chain_supported(fast.critic) else fast.critic.forward_input(x_data)
-        gq = bufs["gq"]
         c_out, c_sum = self._loss_slot("critic")
-        hip_ops.twin_q_loss(qs[0], qs[1], bufs["target_q"], 1.0, gq[0], gq[1], c_out, c_sum)
-        fused.backward_q(qs, gq)
+        blk.q_loss_step(qs, bufs["target_q"], 1.0, c_out, c_sum)
         self.critic.optimizer.step()
         actor_done = False
         if n_updates % self.actor_delay == 0:  # :189-207
             x_pi = fast.candidates(rd.observations, 1, self._pop_noise(), target=False, with_grad=True)
-            qs_pi = fast.critic.forward_input(x_pi, train_params=False, only_first=True)
             a_out, a_sum = self._loss_slot("actor")
-            hip_ops.neg_mean_loss(qs_pi[0], gq[0], a_out, a_sum)
-            fused.backward_q(qs_pi, gq)
+            blk.neg_mean_pass(x_pi, a_out, a_sum)
             # the perturbation net's step, its own soft target update and the critics' in ONE launch; the target VAE already equals
             # the VAE (the reference's polyak + copy of it, :201-203, is the identity on it)
             self.actor.perturbation_optimizer.step_with(polyak=(pol.critic_arena, pol.critic_target_arena, self.tau),
                                                         own_target=(pol.pert_target_arena.flat, self.tau))
             actor_done = True
         if self.debug_capture:
-            self.last_train_tensors = dict(target_q=bufs["target_q"].clone(), current_q=[q.detach().clone() for q in qs],
-                                           critic_loss=c_out.clone(), vae_loss=v_out.clone(), recon=recon.detach().clone(),
-                                           next_q_min=th.min(q_t.stacked, dim=0)[0],
-                                           actor_loss=a_out.clone() if actor_done else None)
+            self.last_train_tensors = blk.captured(qs, bufs["target_q"], c_out, a_out if actor_done else None, vae_loss=v_out.clone(),
+                                                   recon=recon.detach().clone(), next_q_min=th.min(q_t.stacked, dim=0)[0])
 
     # ---- reference odds and ends -------------------------------------------------------------------------------------
     def _behavior_cloning_update(self, observations, actions) -> float:

@@ -9,7 +9,10 @@ leaves every GEMM to PyTorch-ROCm (`torch.mm` -> rocBLAS) with the HIP epilogues
     ONE four-network pointer-table chain (`_TwinPairFn`); the actor's mu / log_std heads = one head kernel;
   * SAC's pi(obs) and pi(next_obs) = ONE 2B-row actor pass, backward on the B differentiated rows (`_ActorPairFn`);
   * a Q network's last hidden layer + scalar head (`hidden_head`) = 1 GEMM launch + 1 launch; its backward's first launch can
-    carry the loss that roots it (`set_loss_root`: TD critic loss, SAC actor loss);
+    carry the loss that roots it (TD critic loss, SAC actor loss, -mean(Q1));
+  * the critic step and the policy pass of SAC, TD3 / DDPG, MADDPG / IDDPG and BCQ on these pieces = ONE block
+    (`PerLayerTwinCritic`, the counterpart of chain.TwinCriticBlock): the forward of critic and target, the choice between a loss
+    head of its own and the loss-root form, the backward, the gradient scratch;
   * deterministic actors write their action into the critic input and read its gradient columns in place (`_LinearXbufFn`,
     `_ActorGroupFn`): no torch.cat, no gather copies;
   * `squashed_gaussian([mean | log_std], eps)` = 1 launch forward, 1 launch backward (analytic);
@@ -510,33 +513,25 @@ def stacked_linear(x, weight, bias, wgrad, bgrad, act: int, train_params: bool, 
 _ZERO_BIAS: dict = {}
 
 # A loss whose gradient w.r.t. the twin Q values is a per-row function of the batch (the TD critic loss, SAC's actor loss) can ride
-# in the FIRST launch of the backward it roots (cstr_hidden_head_bwd_root_f32) instead of being a launch of its own:
-# `set_loss_root(root)` right before the backward call; the twin hidden-head backward that runs next consumes it and ignores the
-# values of the gradient tensor it is handed.
+# in the FIRST launch of the backward it roots (cstr_hidden_head_bwd_root_f32) instead of being a launch of its own: the root is
+# pending while the backward call runs (`_loss_root`, opened by `PerLayerTwinCritic` alone); the twin hidden-head backward that runs
+# next consumes it and ignores the values of the gradient tensor it is handed.
 _pending_root: Optional[dict] = None
 
 
-def set_loss_root(root: Optional[dict]) -> None:
-    global _pending_root
-    _pending_root = root
-
-
-def loss_root_pending() -> bool:
-    return _pending_root is not None
-
-
 @contextlib.contextmanager
-def loss_root(root: Optional[dict]):
-    """`set_loss_root(root)` for the backward call inside the block; on leaving, the root must have been consumed by that backward
+def _loss_root(root: Optional[dict]):
+    """`root` is pending for the backward call inside the block; on leaving, the root must have been consumed by that backward
     (else the graph did not start with the twin hidden-head launch: a programming error) and is cleared in any case, so an
     exception inside the block cannot leave a stale root for an unrelated backward."""
-    set_loss_root(root)
+    global _pending_root
+    _pending_root = root
     try:
         yield
         if root is not None and _pending_root is not None:
             raise RuntimeError("loss root not consumed: the backward did not pass through the twin hidden-head launch")
     finally:
-        set_loss_root(None)
+        _pending_root = None
 
 
 LOSS_ROOT_MAX_ROWS = 1024  # cstr_hidden_head_bwd_root_f32 keeps the per-row gradients in LDS
@@ -1309,6 +1304,121 @@ def twin_pair_forward_many(critics, targets, x_data: th.Tensor, x_next: th.Tenso
         out.stacked = q_c
         outs.append((out, (q_t[0], q_t[1])))
     return outs
+
+
+class PerLayerTwinCritic:
+    """A `FastTwinCritic` and, where there is one, its target on the per-layer kernels: the gradient scratch and the launches of the
+    critic step (forward of critic and target, TD target + critic loss, backward) and of a policy pass through the frozen critics
+    (forward on x_pi, policy loss, backward down to the actor), each loss as a launch of its own or inside the first launch of the
+    backward it roots. The counterpart of chain.TwinCriticBlock for every configuration the row-chain kernels do not cover. What
+    differs between SAC, TD3 / DDPG, MADDPG / IDDPG and BCQ (entropy term, scale, what follows a backward: collectives, optimiser
+    steps, soft updates) is an argument or stays with the caller.
+
+    ensemble: the N-critic loss heads (`td_ens_q_loss`, `sac_actor_ens_loss`) instead of the twin ones. SAC asks for them whenever
+    n_critics != 2, TD3 above two; without them one critic is the twin head on (Q1, Q1) at half the scale, its backward one root with
+    both gradients summed. loss_roots=False (BCQ): every loss is a launch of its own."""
+
+    def __init__(self, critic: "FastTwinCritic", target: Optional["FastTwinCritic"] = None, ensemble: bool = False, loss_roots: bool = True):
+        self.critic, self.target, self.ensemble, self.loss_roots = critic, target, ensemble, loss_roots
+        self.gq: Optional[th.Tensor] = None      # [max(G, 2), B, 1]: d(loss)/dQ of the loss heads (a loss root keeps its own in LDS)
+        self.g_logp: Optional[th.Tensor] = None  # [B]: SAC's d(actor loss)/d(log pi)
+
+    def _scratch(self, q: th.Tensor, logp: bool = False):
+        """The gradient buffers for the batch of `q` [B, 1], re-made when B changes (first made by an eager step, never inside a capture)."""
+        B = q.shape[0]
+        if self.gq is None or self.gq.shape[1] != B:
+            self.gq, self.g_logp = th.empty(max(len(self.critic.nets), 2), B, 1, dtype=th.float32, device=q.device), None
+        if logp and self.g_logp is None:
+            self.g_logp = th.empty(B, dtype=th.float32, device=q.device)
+        return self.gq
+
+    def _rides(self, qs: "QOut") -> bool:
+        """The loss rides in the first launch of the backward through `qs` (cstr_hidden_head_bwd_root_f32)."""
+        return self.loss_roots and qs.stacked is not None and qs.stacked.shape[1] <= LOSS_ROOT_MAX_ROWS and loss_root_supported(self.critic)
+
+    def pair_roots(self, rows: int) -> bool:
+        """`forward` is the four-network chain and `td_step` the loss-root form at this batch size (what lets several blocks share
+        launches: `twin_pair_forward_many`, one `deferred_weight_grads` context around their `td_step`s)."""
+        return self.loss_roots and rows <= LOSS_ROOT_MAX_ROWS and twin_pair_supported(self.critic, self.target) and loss_root_supported(self.critic)
+
+    def forward(self, x_data: th.Tensor, x_next: th.Tensor, pair: bool = True):
+        """(Q(x_data) of the critic with gradients, Q(x_next) of the target without): ONE four-network chain where `twin_pair_supported`
+        (and the caller's inputs allow it: `pair`), otherwise the target's pass, then the critic's."""
+        if pair and twin_pair_supported(self.critic, self.target):
+            return twin_pair_forward(self.critic, self.target, x_data, x_next)
+        with th.no_grad():
+            qs_t = self.target.forward_input(x_next, train_params=False)
+        return self.critic.forward_input(x_data), qs_t
+
+    def td_step(self, qs: "QOut", qs_t, rd, gamma: float, scale: float, target_out, loss_out, loss_sum, next_logp=None, ent_coef=None,
+                alpha=None, after_loss=None) -> None:
+        """TD target from `qs_t` (+ the entropy term: next_logp, ent_coef | alpha, see hip_ops.td_twin_q_loss), critic loss and the
+        critic's backward from `qs` (`forward`'s, or any other pass of the critic's). Safe inside an outer `deferred_weight_grads()`.
+        after_loss(): called once the loss launch has been issued -- behind the loss head, or behind the backward that carried it."""
+        gq, n = self._scratch(qs[0]), len(qs)
+        root = None
+        if n == 2 and self._rides(qs):  # the reductions ride in the critic backward's first launch
+            root = dict(mode="td", q1_t=qs_t[0], q2_t=qs_t[1], next_logp=next_logp, rew=rd.rewards, done=rd.dones, ent_coef=ent_coef,
+                        gamma=gamma, scale=scale, q1=qs[0].detach(), q2=qs[1].detach(), target_out=target_out, loss_out=loss_out,
+                        loss_sum=loss_sum, alpha=alpha)
+        elif self.ensemble:  # the min over all N targets, the loss over all N critics
+            hip_ops.td_ens_q_loss(qs_t, next_logp, rd.rewards, rd.dones, ent_coef, gamma, qs, scale, target_out, gq if gq.shape[0] == n else gq[:n],
+                                  loss_out, loss_sum, alpha=alpha)
+        else:  # (one critic: loss = mse(q1, t) is half the doubled term)
+            hip_ops.td_twin_q_loss(qs_t[0], qs_t[-1], next_logp, rd.rewards, rd.dones, ent_coef, gamma, qs[0], qs[-1], scale if n == 2 else 0.5 * scale,
+                                   target_out, gq[0], gq[1], loss_out, loss_sum, alpha=alpha)
+        if root is None and after_loss is not None:
+            after_loss()
+        if n == 2 or self.ensemble:
+            with _loss_root(root):
+                backward_q(qs, gq)
+        else:  # the twin head on (Q1, Q1): both gradients flow into the one critic
+            with deferred_weight_grads():
+                th.autograd.backward([qs[0]], [gq[0] + gq[1]])
+        if root is not None and after_loss is not None:
+            after_loss()
+
+    def q_loss_step(self, qs: "QOut", target_q: th.Tensor, scale: float, loss_out, loss_sum) -> None:
+        """`td_step` for a target computed elsewhere (BCQ's max over perturbed candidates): twin critic loss head, backward."""
+        gq = self._scratch(qs[0])
+        hip_ops.twin_q_loss(qs[0], qs[1], target_q, scale, gq[0], gq[1], loss_out, loss_sum)
+        backward_q(qs, gq)
+
+    def neg_mean_pass(self, x_pi: th.Tensor, loss_out, loss_sum) -> None:
+        """-mean(Q1(x_pi)) through the first (frozen) critic and its backward into whatever produced x_pi's action columns."""
+        qs_pi = self.critic.forward_input(x_pi, train_params=False, only_first=True)
+        gq = self._scratch(qs_pi[0])
+        if self._rides(qs_pi):
+            with _loss_root(dict(mode="neg_mean", q1=qs_pi[0].detach(), loss_out=loss_out, loss_sum=loss_sum)):
+                backward_q(qs_pi, gq)
+        else:
+            hip_ops.neg_mean_loss(qs_pi[0], gq[0], loss_out, loss_sum)
+            backward_q(qs_pi, gq)
+
+    def sac_actor_pass(self, x_pi: th.Tensor, log_prob: th.Tensor, ent_coef: th.Tensor, loss_out, loss_sum) -> None:
+        """mean(ent_coef * log_prob - min_i Q_i(x_pi)) through all (frozen) critics; backward from both roots, the Q values and
+        log_prob, with the actor's dW / db of all layers in one launch."""
+        qs_pi = self.critic.forward_input(x_pi, train_params=False)
+        gq, n = self._scratch(qs_pi[0], logp=True), len(qs_pi)
+        g_lp, root = self.g_logp, None
+        if self._rides(qs_pi):
+            root = dict(mode="sac_actor", logp=log_prob.detach(), q1=qs_pi[0].detach(), q2=qs_pi[1].detach(), ent_coef=ent_coef, g_logp=g_lp,
+                        loss_out=loss_out, loss_sum=loss_sum)
+        elif self.ensemble:  # min over all N critics
+            hip_ops.sac_actor_ens_loss(log_prob, qs_pi, ent_coef, g_lp, gq if gq.shape[0] == n else gq[:n], loss_out, loss_sum)
+        else:
+            hip_ops.sac_actor_loss(log_prob, qs_pi[0], qs_pi[1], ent_coef, g_lp, gq[0], gq[1], loss_out, loss_sum)
+        with _loss_root(root), deferred_weight_grads():
+            if qs_pi.stacked is not None:
+                th.autograd.backward([log_prob, qs_pi.stacked], [g_lp, gq])
+            else:
+                th.autograd.backward([log_prob, *qs_pi], [g_lp, *(gq[i] for i in range(n))])
+
+    @staticmethod
+    def captured(qs, target_q, critic_loss, actor_loss=None, **more) -> dict:
+        """model.last_train_tensors of a debug_capture step."""
+        return dict(target_q=target_q.clone(), current_q=[q.detach().clone() for q in qs], critic_loss=critic_loss.clone(),
+                    actor_loss=None if actor_loss is None else actor_loss.clone(), **more)
 
 
 def twin_groups(q_networks) -> list:

@@ -337,6 +337,20 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
             self._alloc_packed_step_tensors(batch_size)
         return self._packed
 
+    def _sample(self, batch_size: int, gather_ok=False) -> tuple:
+        """The sampling prologue of a gradient step -> (packed batch | None, gather | None, sample views). With `_use_packed_batch()`
+        the rows land in the critic-input buffers; otherwise in the contiguous batch (through the normaliser, if any).
+        gather_ok (True, or a predicate on the packed batch): the step's first layer can fetch the rows itself, so indices the
+        rollout launch has drawn are handed on (`gather` = ReplayBuffer.take_predrawn(pb)) instead of gathered here."""
+        if not self._use_packed_batch():
+            return None, None, self.replay_buffer.sample_into(self._batch(batch_size))
+        pb, gather = self._packed_batch(batch_size), None
+        if gather_ok and fused.USE_GATHER_IN_FIRST_LAYER and (gather_ok is True or gather_ok(pb)):
+            gather = self.replay_buffer.take_predrawn(pb)
+        if gather is None:
+            self.replay_buffer.sample_packed_into(pb)  # the sample + the critics' cat([obs, act])
+        return pb, gather, pb.samples
+
     def _alloc_step_tensors(self, batch_size: int) -> None:
         """Hook of `_batch`: the per-step tensors whose shape follows the batch size."""
         self._target_q = th.empty(batch_size, 1, dtype=th.float32, device=self.device)
@@ -355,7 +369,11 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         return (self._loss_sums[key], None) if self._single_step else (self._loss_now.get(key), self._loss_sums[key])
 
     def _chain_for(self, batch_size: int):
-        """The row-chain form of the gradient step for this batch size (`chain_type`), or None: per-layer fused path."""
+        """The row-chain form of the gradient step for this batch size (`chain_type`), or None: per-layer fused path. What is cached
+        depends on shapes, architecture and the module flags alone; whether batches are packed follows the replay buffer's normaliser,
+        which every learn() sets again, and is asked on every call."""
+        if not self._use_packed_batch():
+            return None
         cache, key = self._chain_cache, (batch_size, chain.USE_CHAIN, fused.USE_FUSED_LINEAR)
         if key not in cache:
             cache[key] = self.chain_type(self, batch_size) if self.chain_type.supported(self, batch_size) else None

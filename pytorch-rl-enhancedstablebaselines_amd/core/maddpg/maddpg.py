@@ -111,6 +111,8 @@ class MADDPG(OffPolicyAlgorithm):
             self._fast_critics = [fused.FastTwinCritic(_Nets(n), st) for n, st in zip(self.critic.q_networks_list, pol.critic_stacks)]
             self._fast_critic_targets = [fused.FastTwinCritic(_Nets(n), st)
                                          for n, st in zip(self.critic_target.q_networks_list, pol.critic_target_stacks)]
+            # (no ensemble form here: whatever n_critics, the twin loss head on the first and the last Q network)
+            self._critic_blocks = [fused.PerLayerTwinCritic(c, t) for c, t in zip(self._fast_critics, self._fast_critic_targets)]
         if self.faithful_quirks:
             widths = {len(s) for s in self.observation_splits}
             if len(widths) != 1:
@@ -259,16 +261,9 @@ class MADDPG(OffPolicyAlgorithm):
         """maddpg.py:127-185 on the fused path (core/common/fused.py): the same statements and quirks, GEMMs in rocBLAS,
         epilogues / loss roots in HIP, gradients written into the arenas, only the updating agent's networks evaluated."""
         pol, A, C = self.policy, self.actor, self.critic
-        pb = None
-        if self._use_packed_batch():
-            pb = self.replay_buffer.sample_packed_into(self._packed_batch(batch_size))
-            rd = pb.samples
-        else:
-            rd = self.replay_buffer.sample_into(self._batch(batch_size))
+        pb, _, rd = self._sample(batch_size)
         B = rd.observations.shape[0]
-        if not hasattr(self, "_g_bufs") or self._g_bufs.shape[1] != B:
-            self._g_bufs = th.empty(2, B, 1, device=self.device)
-        gq = self._g_bufs
+        blocks = self._critic_blocks
         shared_next = shared_cur = None
         if pb is not None and self._actor_target_group is not None:
             with th.no_grad():  # :131-144: every target actor per layer in one launch, ONE smoothing launch for the joint action
@@ -314,9 +309,8 @@ class MADDPG(OffPolicyAlgorithm):
             if self.debug_capture:
                 self.last_train_tensors = dict(agents=captured_many, batched_critic_steps=True)
             return
-        if (BATCH_AGENT_CRITIC_STEPS and n_updates % self.policy_delay != 0 and shared_next is not None and B <= fused.LOSS_ROOT_MAX_ROWS
-                and self.n_agents <= hip_ops.nv.MAX_ADAM_SEGS
-                and all(fused.twin_pair_supported(c, t) and fused.loss_root_supported(c) for c, t in zip(self._fast_critics, self._fast_critic_targets))
+        if (BATCH_AGENT_CRITIC_STEPS and n_updates % self.policy_delay != 0 and shared_next is not None
+                and self.n_agents <= hip_ops.nv.MAX_ADAM_SEGS and all(blk.pair_roots(B) for blk in blocks)
                 and len({c.acts[0] for c in self._fast_critics}) == 1):
             # A step WITHOUT a policy update: the agents' critic steps (:146-164) do not depend on each other (no soft update in
             # between), so their forward chains share pointer-table launches, their weight gradients one deferred launch pass and
@@ -325,14 +319,9 @@ class MADDPG(OffPolicyAlgorithm):
             captured_many = []
             with fused.deferred_weight_grads():
                 for i, (qs, qs_t) in enumerate(outs):
-                    td_root = dict(mode="td", q1_t=qs_t[0], q2_t=qs_t[1], next_logp=None, rew=rd.rewards, done=rd.dones, ent_coef=None,
-                                   gamma=self.gamma, scale=1.0, q1=qs[0].detach(), q2=qs[1].detach(), target_out=self._target_q[i],
-                                   loss_out=self._loss_now, loss_sum=self._loss_sums[f"critic{i}"], alpha=None)
-                    with fused.loss_root(td_root):
-                        fused.backward_q(qs, gq)
+                    blocks[i].td_step(qs, qs_t, rd, self.gamma, 1.0, self._target_q[i], self._loss_now, self._loss_sums[f"critic{i}"])
                     if self.debug_capture:  # the loss-root launch of agent i has run (only the weight gradients are deferred)
-                        captured_many.append(dict(target_q=self._target_q[i].clone(), current_q=[q.detach().clone() for q in qs],
-                                                  critic_loss=self._loss_now.clone(), actor_loss=None))
+                        captured_many.append(blocks[i].captured(qs, self._target_q[i], self._loss_now))
             for i in range(self.n_agents):
                 self._allreduce_grads(pol.critic_slices[i])
             C.optimizer_list[0].step_with(*C.optimizer_list[1:])
@@ -347,29 +336,9 @@ class MADDPG(OffPolicyAlgorithm):
                 cchain.critic_step(self, i, x_cur, x_next, rd)
                 qs = None
             else:
-                if fused.twin_pair_supported(self._fast_critics[i], self._fast_critic_targets[i]):
-                    # :154 and :148-151 as ONE four-network chain (three launches instead of six)
-                    qs, qs_t = fused.twin_pair_forward(self._fast_critics[i], self._fast_critic_targets[i], x_cur, x_next)
-                else:
-                    with th.no_grad():  # :148-151
-                        qs_t = self._fast_critic_targets[i].forward_input(x_next, train_params=False)
-                    qs = self._fast_critics[i].forward_input(x_cur)  # :154
-                scale = 1.0 if len(qs) == 2 else 0.5
-                root = len(qs) == 2 and qs.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critics[i])
-                td_root = None
-                if root:  # TD target (:148-151) + critic loss (:157-159) inside the critic backward's first launch
-                    td_root = dict(mode="td", q1_t=qs_t[0], q2_t=qs_t[-1], next_logp=None, rew=rd.rewards, done=rd.dones, ent_coef=None,
-                                   gamma=self.gamma, scale=scale, q1=qs[0].detach(), q2=qs[-1].detach(), target_out=self._target_q[i],
-                                   loss_out=self._loss_now, loss_sum=self._loss_sums[f"critic{i}"], alpha=None)
-                else:  # TD target + critic loss in one launch
-                    hip_ops.td_twin_q_loss(qs_t[0], qs_t[-1], None, rd.rewards, rd.dones, None, self.gamma, qs[0], qs[-1], scale,
-                                           self._target_q[i], gq[0], gq[1], self._loss_now, self._loss_sums[f"critic{i}"])
-                if len(qs) == 2:
-                    with fused.loss_root(td_root):
-                        fused.backward_q(qs, gq)  # :162-164
-                else:
-                    with fused.deferred_weight_grads():
-                        th.autograd.backward([qs[0]], [gq[0] + gq[1]])
+                # :148-151 and :154 (ONE four-network chain where the critics allow it), TD target + critic loss (:157-159), backward (:162-164)
+                qs, qs_t = blocks[i].forward(x_cur, x_next)
+                blocks[i].td_step(qs, qs_t, rd, self.gamma, 1.0, self._target_q[i], self._loss_now, self._loss_sums[f"critic{i}"])
                 self._allreduce_grads(pol.critic_slices[i])
                 C.optimizer_list[i].step()
             critic_loss_now = self._loss_now.clone() if self.debug_capture else None
@@ -398,19 +367,8 @@ class MADDPG(OffPolicyAlgorithm):
                     g_x = cchain.actor_loss_grad(self, i, x_pi.detach())
                     with fused.deferred_weight_grads():
                         th.autograd.backward([x_pi], [g_x])
-                    qs_pi = None
-                else:
-                    qs_pi = self._fast_critics[i].forward_input(x_pi, train_params=False, only_first=True)
-                if qs_pi is None:
-                    pass
-                elif qs_pi.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critics[i]):
-                    # -mean(Q1) (:177) rides in the first launch of the backward through the (frozen) first Q network
-                    with fused.loss_root(dict(mode="neg_mean", q1=qs_pi[0].detach(), loss_out=self._loss_now,
-                                              loss_sum=self._loss_sums[f"actor{i}"])):
-                        fused.backward_q(qs_pi, gq)
-                else:
-                    hip_ops.neg_mean_loss(qs_pi[0], gq[0], self._loss_now, self._loss_sums[f"actor{i}"])
-                    fused.backward_q(qs_pi, gq)
+                else:  # -mean(Q1) (:177) through the (frozen) first Q network
+                    blocks[i].neg_mean_pass(x_pi, self._loss_now, self._loss_sums[f"actor{i}"])
                 self._allreduce_grads(pol.actor_slices[i])
                 if self.faithful_quirks:
                     # Q3: polyak of BOTH whole arenas inside the agent loop (:183-185), in the launch of agent i's actor step: the
@@ -428,9 +386,8 @@ class MADDPG(OffPolicyAlgorithm):
                 if self.debug_capture:
                     actor_loss_now = self._loss_now.clone()
             if self.debug_capture:
-                current = ([cchain.q_out[i, 0].clone().view(B, 1), cchain.q_out[i, 1].clone().view(B, 1)] if qs is None
-                           else [q.detach().clone() for q in qs])
-                captured.append(dict(target_q=self._target_q[i].clone(), current_q=current, critic_loss=critic_loss_now, actor_loss=actor_loss_now))
+                kept = (self._target_q[i], critic_loss_now, actor_loss_now)
+                captured.append(cchain.blocks[i].captured(*kept) if qs is None else blocks[i].captured(qs, *kept))
         if not self.faithful_quirks and n_updates % self.policy_delay == 0:
             pol.critic_target_arena.polyak_from(pol.critic_arena, self.tau)
             pol.actor_target_arena.polyak_from(pol.actor_arena, self.tau)

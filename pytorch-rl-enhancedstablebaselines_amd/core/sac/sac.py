@@ -85,6 +85,8 @@ class SAC(OffPolicyAlgorithm):
             self._fast_actor = fused.FastSacActor(self.actor, self.policy.actor_head)
             self._fast_critic = fused.FastTwinCritic(self.critic, self.policy.critic_stack)
             self._fast_critic_target = fused.FastTwinCritic(self.critic_target, self.policy.critic_target_stack)
+            # critic ensembles (policy_kwargs n_critics != 2): the N-critic loss heads, per-layer critic passes
+            self._critic_block = fused.PerLayerTwinCritic(self._fast_critic, self._fast_critic_target, ensemble=len(self.critic.q_networks) != 2)
         if self.use_sde:  # the ATen path differentiates the matrices as torch expressions; the fused head reads the draw buffers
             self.actor.action_dist.torch_matrices = not self.fused_learner
 
@@ -152,33 +154,12 @@ class SAC(OffPolicyAlgorithm):
         backward roots whose kernels emit d(loss)/d(inputs) directly; parameter gradients land in the arenas."""
         s, pol = self._loss_sums, self.policy
         (c_out, c_sum), (a_out, a_sum) = self._loss_slot("critic"), self._loss_slot("actor")
-        pb, gather = None, None
         chain = self._chain_for(batch_size)
+        # a gather in the first layer behind the sample: the chain's actor launch, or the 2B-row actor pass below
+        pb, gather, rd = self._sample(batch_size, True if chain is not None else self._fast_actor.pair_supported)  # :215
         if chain is not None:  # the row-chain kernels (core/common/chain.py): 8 launches instead of 20 (10 under data-parallel)
-            pb = self._packed_batch(batch_size)
-            gather = self.replay_buffer.take_predrawn(pb) if fused.USE_GATHER_IN_FIRST_LAYER else None
-            if gather is None:
-                self.replay_buffer.sample_packed_into(pb)  # :215 + the critics' cat([obs, act])
             return chain.step(self, pb, gather, gradient_step)
-        if self._use_packed_batch():
-            pb = self._packed_batch(batch_size)
-            if fused.USE_GATHER_IN_FIRST_LAYER and self._fast_actor.pair_supported(pb):
-                # indices drawn by the rollout launch: the 2B-row actor pass below gathers the rows in its first layer
-                gather = self.replay_buffer.take_predrawn(pb)
-            if gather is None:
-                self.replay_buffer.sample_packed_into(pb)  # :215 + the critics' cat([obs, act])
-            rd = pb.samples
-        else:
-            rd = self.replay_buffer.sample_into(self._batch(batch_size))  # :215
-        B = rd.observations.shape[0]
-        n_q = len(self.critic.q_networks)
-        ens = n_q != 2  # critic ensembles (policy_kwargs n_critics): the N-critic loss heads, per-layer critic passes
-        if not hasattr(self, "_g_bufs") or self._g_bufs[0].shape[0] != B:
-            e = lambda *sh: th.empty(*sh, dtype=th.float32, device=self.device)  # noqa: E731
-            self._g_bufs = (e(n_q, B, 1), e(B))
-        gq, g_lp = self._g_bufs
-        if not ens:
-            gq1, gq2 = gq[0], gq[1]
+        blk = self._critic_block
 
         pair = pb is not None and self._fast_actor.pair_supported(pb)
         assert gather is None or pair
@@ -193,80 +174,34 @@ class SAC(OffPolicyAlgorithm):
         # coefficient's loss (ent_coef = exp(log_ent_coef) BEFORE the update, :230; the updated value is first used by the
         # next gradient step, so its optimiser step may wait for the critic's all-reduce: one collective instead of two),
         # the TD target (:245-254) and the critic loss (:258-261)
-        twin_pair = pb is not None and fused.twin_pair_supported(self._fast_critic, self._fast_critic_target)
         with th.no_grad():
-            if not pair and pb is not None:
-                x_next, next_log_prob = self._fast_actor.action_log_prob(rd.next_observations, train_params=False, xbuf=pb.x_next)
             if pb is None:
                 next_actions, next_log_prob = self._fast_actor.action_log_prob(rd.next_observations, train_params=False)
-                qs_t = self._fast_critic_target(rd.next_observations, next_actions, train_params=False)
-            elif not twin_pair:
-                qs_t = self._fast_critic_target.forward_input(x_next, train_params=False)
-            if not twin_pair and not ens:
-                q1_t, q2_t = qs_t
-        if twin_pair:  # :258 and :250 as ONE four-network chain (three launches instead of six)
-            qs, (q1_t, q2_t) = fused.twin_pair_forward(self._fast_critic, self._fast_critic_target, pb.x_data, x_next)
-        else:
-            qs = self._fast_critic.forward_input(pb.x_data) if pb is not None else self._fast_critic(rd.observations, rd.actions)  # :258
-        if not ens:
-            q1, q2 = qs
-        if self.ent_coef_optimizer is not None:
+                x_next = th.cat([rd.next_observations, next_actions], dim=1)
+            elif not pair:
+                x_next, next_log_prob = self._fast_actor.action_log_prob(rd.next_observations, train_params=False, xbuf=pb.x_next)
+        # :250 and :258: ONE four-network chain on a packed batch (three launches instead of six), else the target's pass, then the critic's
+        qs, qs_t = blk.forward(pb.x_data if pb is not None else th.cat([rd.observations, rd.actions], dim=1), x_next, pair=pb is not None)
+        ent_opt = self.ent_coef_optimizer
+        if ent_opt is not None:
             (ent_coef, ent_coef_sum), (e_out, e_sum) = self._loss_slot("ent_coef"), self._loss_slot("ent_coef_loss")
             alpha = dict(log_alpha=self.log_ent_coef.detach(), logp_pi=log_prob.detach(), target_entropy=self.target_entropy,
                          grad_out=self._ent_arena.grad[0:1], ent_coef_out=ent_coef, loss_out=e_out, loss_sum=e_sum, ent_coef_sum=ent_coef_sum)
         else:
             ent_coef, alpha = self.ent_coef_tensor.reshape(1), None
             s["ent_coef"] += ent_coef
-        root = qs.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critic)
-        td_root = None
-        if root:  # the three reductions ride in the critic backward's first launch (cstr_hidden_head_bwd_root_f32)
-            td_root = dict(mode="td", q1_t=q1_t, q2_t=q2_t, next_logp=next_log_prob, rew=rd.rewards, done=rd.dones,
-                           ent_coef=ent_coef, gamma=self.gamma, scale=0.5, q1=q1.detach(), q2=q2.detach(), target_out=self._target_q,
-                           loss_out=c_out, loss_sum=c_sum, alpha=alpha)
-        else:
-            if ens:  # :249-250 and :261 over all N critics
-                hip_ops.td_ens_q_loss(qs_t, next_log_prob, rd.rewards, rd.dones, ent_coef, self.gamma, qs, 0.5, self._target_q, gq,
-                                      c_out, c_sum, alpha=alpha)
-            else:
-                hip_ops.td_twin_q_loss(q1_t, q2_t, next_log_prob, rd.rewards, rd.dones, ent_coef, self.gamma, q1, q2, 0.5, self._target_q,
-                                       gq1, gq2, c_out, c_sum, alpha=alpha)
-            if self.ent_coef_optimizer is not None and not self._ent_rides_critic:
-                self._allreduce_grads(self._ent_arena)
-                self.ent_coef_optimizer.step()
-        with fused.loss_root(td_root):
-            fused.backward_q(qs, gq)  # :266-268
-        if root:
-            if self.ent_coef_optimizer is not None and not self._ent_rides_critic:
-                self._allreduce_grads(self._ent_arena)
-                self.ent_coef_optimizer.step()
+        # the entropy coefficient's own collective and step (:240-243), as soon as the launch that leaves its gradient has been issued
+        blk.td_step(qs, qs_t, rd, self.gamma, 0.5, self._target_q, c_out, c_sum, next_logp=next_log_prob, ent_coef=ent_coef, alpha=alpha,
+                    after_loss=self._ent_coef_step if ent_opt is not None and not self._ent_rides_critic else None)  # :266-268
         self._allreduce_grads(pol.critic_arena)
-        if self.ent_coef_optimizer is not None and self._ent_rides_critic:
+        if ent_opt is not None and self._ent_rides_critic:
             # :240-243 (gradient averaged by the critic's collective) and :266-268 in one launch
-            self.critic.optimizer.step_with(self.ent_coef_optimizer)
+            self.critic.optimizer.step_with(ent_opt)
         else:
             self.critic.optimizer.step()
 
-        # :273-275 (critic weights frozen)
-        qs_pi = (self._fast_critic.forward_input(x_pi, train_params=False) if pb is not None
-                 else self._fast_critic(rd.observations, actions_pi, train_params=False))
-        if not ens:
-            q1_pi, q2_pi = qs_pi
-        root = qs_pi.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critic)
-        actor_root = None
-        if root:  # the actor loss rides in the first launch of the backward through the (frozen) critic
-            actor_root = dict(mode="sac_actor", logp=log_prob.detach(), q1=q1_pi.detach(), q2=q2_pi.detach(), ent_coef=ent_coef, g_logp=g_lp,
-                              loss_out=a_out, loss_sum=a_sum)
-        elif ens:  # min over all N critics
-            hip_ops.sac_actor_ens_loss(log_prob, qs_pi, ent_coef, g_lp, gq, a_out, a_sum)
-        else:
-            hip_ops.sac_actor_loss(log_prob, q1_pi, q2_pi, ent_coef, g_lp, gq1, gq2, a_out, a_sum)
-        with fused.loss_root(actor_root), fused.deferred_weight_grads():  # :279-281; the actor's dW / db of all layers in one launch
-            if qs_pi.stacked is not None:
-                th.autograd.backward([log_prob, qs_pi.stacked], [g_lp, gq])
-            elif ens:  # one Q network: no stack
-                th.autograd.backward([log_prob, *qs_pi], [g_lp, *gq])
-            else:
-                th.autograd.backward([log_prob, q1_pi, q2_pi], [g_lp, gq1, gq2])
+        # :273-275 (critic weights frozen) and :279-281
+        blk.sac_actor_pass(x_pi if pb is not None else th.cat([rd.observations, actions_pi], dim=1), log_prob, ent_coef, a_out, a_sum)
         self._allreduce_grads(pol.actor_arena)
         if gradient_step % self.target_update_interval == 0:  # :281 and :284-287 (disjoint arenas) in one launch
             self.actor.optimizer.step_with(polyak=(pol.critic_arena, pol.critic_target_arena, self.tau))
@@ -274,9 +209,12 @@ class SAC(OffPolicyAlgorithm):
             self.actor.optimizer.step()
 
         if self.debug_capture:
-            self.last_train_tensors = dict(target_q=self._target_q.clone(), current_q=[q.detach().clone() for q in qs],
-                                           critic_loss=c_out.clone(), actor_loss=a_out.clone(),
-                                           ent_coef=ent_coef.detach().clone(), log_prob=log_prob.detach().clone())
+            self.last_train_tensors = blk.captured(qs, self._target_q, c_out, a_out, ent_coef=ent_coef.detach().clone(),
+                                                   log_prob=log_prob.detach().clone())
+
+    def _ent_coef_step(self) -> None:
+        self._allreduce_grads(self._ent_arena)
+        self.ent_coef_optimizer.step()
 
     def _chain_for(self, batch_size: int):
         step = super()._chain_for(batch_size)

@@ -55,6 +55,9 @@ class TD3(OffPolicyAlgorithm):
         if self.fused_learner:
             self._fast_actor, self._fast_actor_target = fused.FastMLP(self.actor.mu, self.actor.optimizer), fused.FastMLP(self.actor_target.mu)
             self._fast_critic, self._fast_critic_target = fused.FastTwinCritic(self.critic, self.policy.critic_stack), fused.FastTwinCritic(self.critic_target, self.policy.critic_target_stack)
+            # critic ensembles (policy_kwargs n_critics > 2): min over all N targets, the loss and backward through all N critics;
+            # n_critics == 1 (DDPG) stays on the twin loss head
+            self._critic_block = fused.PerLayerTwinCritic(self._fast_critic, self._fast_critic_target, ensemble=len(self.critic.q_networks) > 2)
 
     def _policy_out_device(self, obs: th.Tensor) -> th.Tensor:
         if not self.fused_learner:
@@ -148,31 +151,12 @@ class TD3(OffPolicyAlgorithm):
     def _gradient_step_fused(self, batch_size: int, n_updates: int) -> None:
         """td3.py:161-206 on the fused path (core/common/fused.py)."""
         pol = self.policy
-        pb, gather = None, None
         chain = self._chain_for(batch_size)
+        # a gather in the first layer behind the sample (:161): the chain's target-actor launch, or the target actor's first layer below
+        pb, gather, rd = self._sample(batch_size, True if chain is not None else self._target_actor_gathers)
         if chain is not None:  # the row-chain kernels (core/common/chain.py): 4 launches (9 with the policy step) instead of 13 (22)
-            pb = self._packed_batch(batch_size)
-            gather = self.replay_buffer.take_predrawn(pb) if fused.USE_GATHER_IN_FIRST_LAYER else None
-            if gather is None:
-                self.replay_buffer.sample_packed_into(pb)  # :161 + the critics' cat([obs, act])
             return chain.step(self, pb, gather, n_updates)
-        if self._use_packed_batch():
-            pb = self._packed_batch(batch_size)
-            if fused.USE_GATHER_IN_FIRST_LAYER and self._fast_actor_target.gather_supported(pb.samples.next_observations):
-                # indices drawn by the rollout launch: the target actor's first layer below gathers the rows itself
-                gather = self.replay_buffer.take_predrawn(pb)
-            if gather is None:
-                self.replay_buffer.sample_packed_into(pb)  # :161 + the critics' cat([obs, act])
-            rd = pb.samples
-        else:
-            rd = self.replay_buffer.sample_into(self._batch(batch_size))
-        B = rd.observations.shape[0]
-        n_q = len(self.critic.q_networks)
-        ens = n_q > 2  # critic ensembles (policy_kwargs n_critics): min over all N targets, the loss and backward through all N critics
-        if not hasattr(self, "_g_bufs") or self._g_bufs[0].shape[0] != B:
-            self._g_bufs = th.empty(max(n_q, 2), B, 1, device=self.device)
-        gq = self._g_bufs
-        gq1, gq2 = gq[0], gq[1]
+        blk = self._critic_block
         with th.no_grad():  # :167-176
             if pb is not None:
                 # target smoothing in ONE launch (clone + normal_ + clamp + add + clamp), written into x_next's action columns
@@ -186,42 +170,17 @@ class TD3(OffPolicyAlgorithm):
                 else:
                     a_t = self._fast_actor_target(rd.next_observations, train_params=False, gather=gather)
                     hip_ops.target_smooth(a_t, queued, rng, self.target_policy_noise, self.target_noise_clip, pb.x_next[:, pb.obs_dim:])
-                twin_pair = fused.twin_pair_supported(self._fast_critic, self._fast_critic_target)
-                if not twin_pair:
-                    qs = self._fast_critic_target.forward_input(pb.x_next, train_params=False)
+                x_next = pb.x_next
             else:
                 noise = self.noise_queue.pop(0).to(self.device) if self.noise_queue else rd.actions.clone().normal_(0, self.target_policy_noise)
                 noise = noise.clamp(-self.target_noise_clip, self.target_noise_clip)
                 next_actions = (self._fast_actor_target(rd.next_observations, train_params=False) + noise).clamp(-1, 1)
-                qs = self._fast_critic_target(rd.next_observations, next_actions, train_params=False)
-            if pb is None or not twin_pair:
-                qs_t = qs
-                q1_t, q2_t = qs[0], qs[-1]
-        if pb is not None and twin_pair:  # :179 and :173 as ONE four-network chain (three launches instead of six)
-            qs, (q1_t, q2_t) = fused.twin_pair_forward(self._fast_critic, self._fast_critic_target, pb.x_data, pb.x_next)
-        else:
-            qs = self._fast_critic.forward_input(pb.x_data) if pb is not None else self._fast_critic(rd.observations, rd.actions)  # :179
-        q1, q2 = qs[0], qs[-1]
-        # TD target (:174-176) + critic loss (:182) in one launch; n_critics == 1 (DDPG): loss = mse(q1, t) -> scale 0.5 of
-        # the doubled term. Twin critics: inside the critic backward's first launch (cstr_hidden_head_bwd_root_f32).
+                x_next = th.cat([rd.next_observations, next_actions], dim=1)
+        # :173 and :179: ONE four-network chain on a packed batch (three launches instead of six), else the target's pass, then the critic's
+        qs, qs_t = blk.forward(pb.x_data if pb is not None else th.cat([rd.observations, rd.actions], dim=1), x_next, pair=pb is not None)
+        # TD target (:174-176) + critic loss (:182, no 0.5) + the critic's backward
         c_out, c_sum = self._loss_slot("critic")
-        root = len(qs) == 2 and qs.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critic)
-        td_root = None
-        if root:
-            td_root = dict(mode="td", q1_t=q1_t, q2_t=q2_t, next_logp=None, rew=rd.rewards, done=rd.dones, ent_coef=None,
-                           gamma=self.gamma, scale=1.0, q1=q1.detach(), q2=q2.detach(), target_out=self._target_q,
-                           loss_out=c_out, loss_sum=c_sum, alpha=None)
-        elif ens:
-            hip_ops.td_ens_q_loss(qs_t, None, rd.rewards, rd.dones, None, self.gamma, qs, 1.0, self._target_q, gq, c_out, c_sum)
-        else:
-            hip_ops.td_twin_q_loss(q1_t, q2_t, None, rd.rewards, rd.dones, None, self.gamma, q1, q2, 1.0 if len(qs) == 2 else 0.5,
-                                   self._target_q, gq1, gq2, c_out, c_sum)
-        if len(qs) >= 2:
-            with fused.loss_root(td_root):
-                fused.backward_q(qs, gq)
-        else:
-            with fused.deferred_weight_grads():
-                th.autograd.backward([q1], [gq1 + gq2])
+        blk.td_step(qs, qs_t, rd, self.gamma, 1.0, self._target_q, c_out, c_sum)
         self._allreduce_grads(pol.critic_arena)
         self.critic.optimizer.step()
         actor_done = False
@@ -230,18 +189,10 @@ class TD3(OffPolicyAlgorithm):
                 # the actor's last layer writes into x_pi = (obs | .): no torch.cat, and its backward reads the action columns
                 # of the critic's input gradient in place
                 x_pi = self._fast_actor(rd.observations, xbuf=pb.x_pi.detach())
-                qs_pi = self._fast_critic.forward_input(x_pi, train_params=False, only_first=True)
             else:
-                a = self._fast_actor(rd.observations)
-                qs_pi = self._fast_critic(rd.observations, a, train_params=False, only_first=True)
+                x_pi = th.cat([rd.observations, self._fast_actor(rd.observations)], dim=1)
             a_out, a_sum = self._loss_slot("actor")
-            if qs_pi.stacked is not None and B <= fused.LOSS_ROOT_MAX_ROWS and fused.loss_root_supported(self._fast_critic):
-                # -mean(Q1) (:194) rides in the first launch of the backward through the (frozen) first Q network
-                with fused.loss_root(dict(mode="neg_mean", q1=qs_pi[0].detach(), loss_out=a_out, loss_sum=a_sum)):
-                    fused.backward_q(qs_pi, gq)
-            else:
-                hip_ops.neg_mean_loss(qs_pi[0], gq1, a_out, a_sum)
-                fused.backward_q(qs_pi, gq)
+            blk.neg_mean_pass(x_pi, a_out, a_sum)  # -mean(Q1) (:194) through the (frozen) first Q network
             self._allreduce_grads(pol.actor_arena)
             # the actor's step, the critics' soft update (disjoint arenas) and the actor target's soft update (by the threads that
             # have just computed the new actor weights) in ONE launch (:199, :204, :205)
@@ -251,9 +202,10 @@ class TD3(OffPolicyAlgorithm):
                                            own_target=(pol.actor_target_arena.flat, self.tau))
             actor_done = True
         if self.debug_capture:
-            self.last_train_tensors = dict(target_q=self._target_q.clone(), current_q=[q.detach().clone() for q in qs],
-                                           critic_loss=c_out.clone(),
-                                           actor_loss=a_out.clone() if actor_done else None)
+            self.last_train_tensors = blk.captured(qs, self._target_q, c_out, a_out if actor_done else None)
+
+    def _target_actor_gathers(self, pb) -> bool:
+        return self._fast_actor_target.gather_supported(pb.samples.next_observations)
 
     def _get_torch_save_params(self) -> tuple:
         """reference: td3.py:234-240"""
