@@ -803,7 +803,8 @@ int cstr_bcq_select_f32(const float *q1, const float *cand, int64_t ldc, int64_t
 /* ---- PPO: the arithmetic around the Linear layers of an on-policy rollout step and minibatch step (core/ppo/ppo.py:184-300,
  * core/common/on_policy_algorithm.py:162-268, core/common/buffers.py:343-521) ------------------------------------------------------
  * All f32; obs_dim in {4, 8}, act_dim in {2, 4} (CSTR_E_UNSUPPORTED otherwise, as for more than CSTR_PPO_MAX_ROWS rows); any row
- * count >= 1. Every entry point validates on the host (NULL, non-positive sizes, misaligned rows -- 4 * width bytes for [.][width]
+ * count >= 1. cstr_rollout_add_f32 and cstr_ppo_gather_f32 also take act_dim 1: the Categorical head's action row, the index as one
+ * float (4-byte-aligned rows; see the Categorical block below). Every entry point validates on the host (NULL, non-positive sizes, misaligned rows -- 4 * width bytes for [.][width]
  * matrices, 16 for observations --, overlapping input / output rows -> CSTR_E_BADARG), then only enqueues. Batch reductions are
  * deterministic (per-workgroup f64 partials summed in workgroup order; no float atomics).
  * cstr_rollout_t: the RolloutBuffer's field arrays, [rows][n_envs][.] row-major. rollout ctl: int64[CSTR_ROLLOUT_CTL_WORDS] in HBM
@@ -934,6 +935,57 @@ int cstr_dqn_act_f32(const float *q, int64_t ldq, int64_t n, int n_actions, int 
 int cstr_dqn_loss_f32(const float *q, int64_t ldq, const float *next_q, int64_t ldn, const float *valve, const float *reward,
                       const float *done, float gamma, int64_t batch, int n_actions, int levels, float *g_q, float *loss_out,
                       float *loss_sum, float *cur_q_out, float *target_out, uint64_t *workspace, cstr_stream_t stream);
+
+/* ---- Categorical head of PPO / A2C on the discrete valve face (core/common/distributions.py:263-311, core/ppo/ppo.py:213-264,
+ * core/a2c/a2c.py:150-171) ---------------------------------------------------------------------------------------------------------
+ * Same conventions as the PPO block: f32 data, host-side validation (NULL, non-positive sizes, misaligned or overlapping rows ->
+ * CSTR_E_BADARG), then only enqueues; deterministic batch reductions; the workspace is a uint64[CSTR_PPO_WS_WORDS] as above. The face
+ * is the DQN block's: n_actions = levels * levels, 2 <= levels <= CSTR_DQN_MAX_LEVELS (anything else, or more than CSTR_PPO_MAX_ROWS
+ * rows: CSTR_E_UNSUPPORTED). logits [rows][ldz], ldz >= n_actions, n_actions columns used, rows 4-byte aligned.
+ * Per row: logp_j = (z_j - max z) - log sum_j exp(z_j - max z) (torch's Categorical(logits = z)), p_j = exp(logp_j).
+ * cstr_categorical_act_f32 (one launch): the index a comes from exactly one source (two at once, or none: CSTR_E_BADARG):
+ *   deterministic != 0: the first maximum of the row's logits (a NaN counts as the greatest value). The reference takes argmax(probs);
+ *     the two differ only where two distinct logits round to the same probability;
+ *   action_in int64[n]: teacher-forced indices; values outside the face are the caller's bug and are clamped into it;
+ *   u_in [n]: a given uniform in [0, 1);
+ *   rng_ctl [CSTR_RNG_CTL_WORDS]: the uniform is drawn, Philox4x32-10 on the head's own stream, counter (offset + row, 0, tag), word 0
+ *     as (word >> 8) * 2^-24; the last workgroup advances the offset by n.
+ * With a uniform u, a is the first index whose inclusive cumulative probability (f32, index order) exceeds u, n_actions - 1 if none
+ * does. Outputs: index_f32 [n] = a as a float (what the rollout buffer stores); optional index_out int64[n], valve_out [n][2] =
+ * (v(a / levels), v(a % levels)), log_prob [n] = logp_a, u_out [n] = the uniforms (only with u_in or rng_ctl).
+ * cstr_categorical_loss_f32 (one launch): see cstr_categorical_loss_t. Per row the stored action is a = (long)actions[b] (clamped
+ * into the face), H_b = -sum_j p_j logp_j. objective 0 (PPO): cstr_ppo_loss_f32's statements with logp_a as the log-prob, the same six
+ * scalars in the same order, entropy_loss = -mean_b H_b; objective 1 (A2C): cstr_a2c_loss_f32's four scalars, the advantage
+ * normalisation without a batch > 1 guard (batch 1: NaN). Any other objective: CSTR_E_BADARG.
+ * g_logits[b][j] = g_logp_b * ((j == a) - p_j) + (ent_coef / batch) * p_j * (logp_j + H_b), g_logp_b = d loss / d logp_a (PPO:
+ * -(dmin * ratio) / batch with the closed-interval clamp rule; A2C: -adv_b / batch); columns n_actions .. ldz of g_logits are not
+ * written. g_value [batch] as in the two blocks above. */
+typedef struct {
+    const float *logits;       /* [batch][ldz], n_actions columns used */
+    int64_t ldz;
+    const float *actions;      /* [batch]: the stored index as a float */
+    const float *values;       /* [batch]: the value net's output */
+    const float *old_values;   /* [batch]; may be NULL when clip_range_vf <= 0 or objective 1 */
+    const float *old_log_prob; /* [batch]; may be NULL for objective 1 */
+    const float *adv;          /* [batch] */
+    const float *returns;      /* [batch] */
+    int64_t batch;
+    int32_t n_actions, levels;
+    int32_t objective;           /* 0: PPO, 1: A2C */
+    int32_t normalize_advantage; /* != 0: (adv - mean) / (unbiased std + 1e-8); PPO skips it when batch == 1 */
+    double clip_range;           /* PPO */
+    double clip_range_vf;        /* PPO; <= 0: no value clipping */
+    float ent_coef, vf_coef;
+    float *g_logits;             /* [batch][ldz] */
+    float *g_value;              /* [batch] */
+    float *scalars_out;          /* [6] (PPO) / [4] (A2C) or NULL */
+    float *scalars_sum;          /* same size or NULL: += */
+    float *log_prob_out;         /* [batch] or NULL: logp_a */
+} cstr_categorical_loss_t;
+int cstr_categorical_act_f32(const float *logits, int64_t ldz, int64_t n, int n_actions, int levels, int deterministic,
+                             const int64_t *action_in, const float *u_in, uint64_t *rng_ctl, float *index_f32, int64_t *index_out,
+                             float *valve_out, float *log_prob, float *u_out, cstr_stream_t stream);
+int cstr_categorical_loss_f32(const cstr_categorical_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@ SYMBOLS = (
     "cstr_a2c_loss_f32", "cstr_rmsprop_f32",
     "cstr_mt19937_rand_flag_f64", "cstr_dqn_act_f32", "cstr_dqn_loss_f32",
     "cstr_eval_episodes_f32",
+    "cstr_categorical_act_f32", "cstr_categorical_loss_f32",
 )
 
 
@@ -168,6 +169,15 @@ class A2cLoss(C.Structure):
     _fields_ = [("mean", C.c_void_p), ("ldm", C.c_int64)] + [(n, C.c_void_p) for n in ("log_std", "actions", "values", "adv", "returns")] + [
         ("batch", C.c_int64), ("act_dim", C.c_int32), ("normalize_advantage", C.c_int32), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [
         (n, C.c_void_p) for n in ("g_mean", "g_value", "g_log_std", "scalars_out", "log_prob_out")]
+
+
+class CategoricalLoss(C.Structure):
+    """cstr_categorical_loss_t"""
+    _fields_ = [("logits", C.c_void_p), ("ldz", C.c_int64)] + [(n, C.c_void_p) for n in (
+        "actions", "values", "old_values", "old_log_prob", "adv", "returns")] + [
+        ("batch", C.c_int64), ("n_actions", C.c_int32), ("levels", C.c_int32), ("objective", C.c_int32), ("normalize_advantage", C.c_int32),
+        ("clip_range", C.c_double), ("clip_range_vf", C.c_double), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [(n, C.c_void_p) for n in (
+            "g_logits", "g_value", "scalars_out", "scalars_sum", "log_prob_out")]
 
 
 class NativeError(RuntimeError):

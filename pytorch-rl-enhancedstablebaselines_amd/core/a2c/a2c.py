@@ -14,7 +14,10 @@ NumPy's stream: the reference draws one `permutation(T * N)` per train() from th
 draws from that global stream (a VecEnv that is not device-resident) the in-place path still consumes the draw, so the stream's
 position matches the reference's; with the algorithm's own `RandomState` (a device env) nothing else reads it and the draw is skipped.
 
-Not built: RMSpropTFLike, gSDE, hipGraph replay, data-parallel training, VecNormalize, discrete actions, CNN / dict policies."""
+On a Discrete valve face the policy has a Categorical head and the loss launch is hip_ops.categorical_loss (csrc/cstr_categorical.hip).
+
+Not built: RMSpropTFLike, gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiDiscrete / MultiBinary actions, CNN / dict
+policies."""
 from typing import Optional, Union
 
 import numpy as np
@@ -27,6 +30,7 @@ from core.common.arena import FlatRMSprop
 from core.common.buffers import RolloutBuffer
 from core.common.logger import DeviceMean
 from core.common.on_policy_algorithm import OnPolicyAlgorithm
+from core.common.spaces import Discrete
 
 
 class A2C(OnPolicyAlgorithm):
@@ -44,7 +48,7 @@ class A2C(OnPolicyAlgorithm):
                          vf_coef=vf_coef, max_grad_norm=max_grad_norm, use_sde=use_sde, sde_sample_freq=sde_sample_freq,
                          rollout_buffer_class=rollout_buffer_class, rollout_buffer_kwargs=rollout_buffer_kwargs,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs,
-                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box",))
+                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box", Discrete))
         self.normalize_advantage = normalize_advantage
         self.rms_prop_eps, self.use_rms_prop = rms_prop_eps, use_rms_prop
         self._rewrite_policy_kwargs(self.policy_kwargs, use_rms_prop, rms_prop_eps)
@@ -74,7 +78,7 @@ class A2C(OnPolicyAlgorithm):
         b = self._step_bufs.get(rows)
         if b is None:
             e = lambda *sh: th.empty(*sh, dtype=th.float32, device=self.device)  # noqa: E731
-            b = self._step_bufs[rows] = dict(g_mean=e(rows, self.rollout_buffer.action_dim), g_value=e(rows, 1), log_prob=e(rows))
+            b = self._step_bufs[rows] = dict(g_mean=e(rows, self.policy.action_net.out_features), g_value=e(rows, 1), log_prob=e(rows))
         return b
 
     def _rows_in_place(self, rb: RolloutBuffer):
@@ -101,11 +105,16 @@ class A2C(OnPolicyAlgorithm):
         """evaluate_actions on the per-layer kernels, the loss launch, loss.backward() from its gradients, clip_grad_norm_ and the step"""
         fast, pol = self._fast, self.policy
         b = self._bufs(obs.shape[0])
-        mean = fast.mean(obs, train_params=True)
+        mean = fast.logits(obs, train_params=True) if fast.discrete else fast.mean(obs, train_params=True)
         values = fast.values(obs, train_params=True)
-        hip_ops.a2c_loss(mean.detach(), pol.log_std.detach(), actions, values.detach(), advantages, returns, self.normalize_advantage,
-                         self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], pol.log_std.grad, self._ws, scalars_out=self._scalars,
-                         log_prob_out=b["log_prob"] if self.debug_capture else None)
+        if fast.discrete:  # the Categorical head: g_mean holds d loss / d logits, there is no log_std
+            hip_ops.categorical_loss(hip_ops.CAT_A2C, mean.detach(), fast.levels, actions, values.detach(), advantages, returns,
+                                     self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
+                                     scalars_out=self._scalars, log_prob_out=b["log_prob"] if self.debug_capture else None)
+        else:
+            hip_ops.a2c_loss(mean.detach(), pol.log_std.detach(), actions, values.detach(), advantages, returns, self.normalize_advantage,
+                             self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], pol.log_std.grad, self._ws, scalars_out=self._scalars,
+                             log_prob_out=b["log_prob"] if self.debug_capture else None)
         with fused.deferred_weight_grads():
             th.autograd.backward([mean, values], [b["g_mean"], b["g_value"]])
         opt = pol.optimizer
@@ -156,14 +165,15 @@ class A2C(OnPolicyAlgorithm):
                 y_pred, y_true = rb.values.flatten(), rb.returns.flatten()
                 var_y = y_true.var(unbiased=False)  # explained_variance (utils.py, np.var): NaN where var(y_true) == 0
                 explained_var = th.where(var_y == 0, th.full_like(var_y, float("nan")), 1 - (y_true - y_pred).var(unbiased=False) / var_y)
-                std = th.exp(self.policy.log_std.detach()).mean()
+                std = th.exp(self.policy.log_std.detach()).mean() if hasattr(self.policy, "log_std") else None
         self._n_updates += 1
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         self.logger.record("train/explained_variance", DeviceMean(explained_var, 1))
         self.logger.record("train/entropy_loss", DeviceMean(scalars[2], 1))
         self.logger.record("train/policy_loss", DeviceMean(scalars[0], 1))
         self.logger.record("train/value_loss", DeviceMean(scalars[1], 1))
-        self.logger.record("train/std", DeviceMean(std, 1))
+        if std is not None:  # :187-188: a Categorical head has no log_std
+            self.logger.record("train/std", DeviceMean(std, 1))
 
     def learn(self, total_timesteps: int, callback=None, log_interval: int = 100, tb_log_name: str = "A2C", reset_num_timesteps: bool = True,
               progress_bar: bool = False):

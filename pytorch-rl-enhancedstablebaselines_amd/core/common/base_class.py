@@ -61,10 +61,11 @@ class BaseAlgorithm:
             self.n_envs = env.num_envs
             self.env = env
             self._vec_normalize_env = unwrap_vec_normalize(env)  # reference base_class.py:195
-            # reference base_class.py:202-208: a class that names Discrete (DQN) takes a Discrete space and nothing else; every other
-            # class takes a Box
+            # reference base_class.py:202-208: a class that names Discrete alone (DQN) takes a Discrete space and nothing else, one that
+            # names "Box" and Discrete (PPO, A2C) takes either; every other class takes a Box
             wants_discrete = supported_action_spaces is not None and Discrete in supported_action_spaces
-            if isinstance(self.action_space, Discrete) != wants_discrete:
+            wants_box = not wants_discrete or "Box" in supported_action_spaces
+            if not (wants_discrete if isinstance(self.action_space, Discrete) else wants_box):
                 raise AssertionError(f"The algorithm only supports {supported_action_spaces} as action spaces "
                                      f"but {self.action_space} was provided")
             if not support_multi_env and self.n_envs > 1:

@@ -209,6 +209,50 @@ class StateDependentNoiseDistribution:
         return actions, self.log_prob(actions)
 
 
+class CategoricalDistribution:
+    """reference: core/common/distributions.py:263-311 -- torch's Categorical over the logits of a Discrete action space (torch
+    statements: the API and the torch-statement path; the kernel path evaluates the same expressions in csrc/cstr_categorical.hip).
+    `action_queue`: teacher-forcing hook, each `sample()` pops its indices from here first (tests)."""
+
+    def __init__(self, action_dim: int):
+        self.action_dim = action_dim
+        self.distribution = None
+        self.action_queue: list = []
+
+    def proba_distribution_net(self, latent_dim: int) -> nn.Module:
+        return nn.Linear(latent_dim, self.action_dim)
+
+    def proba_distribution(self, action_logits: th.Tensor) -> "CategoricalDistribution":
+        self.distribution = th.distributions.Categorical(logits=action_logits)
+        return self
+
+    def log_prob(self, actions: th.Tensor) -> th.Tensor:
+        return self.distribution.log_prob(actions)
+
+    def entropy(self) -> th.Tensor:
+        return self.distribution.entropy()
+
+    def sample(self) -> th.Tensor:
+        if self.action_queue:
+            d = self.distribution
+            return self.action_queue.pop(0).to(d.logits.device, th.int64).reshape(d.logits.shape[:-1])
+        return self.distribution.sample()
+
+    def mode(self) -> th.Tensor:
+        return th.argmax(self.distribution.probs, dim=1)
+
+    def get_actions(self, deterministic: bool = False) -> th.Tensor:
+        return self.mode() if deterministic else self.sample()
+
+    def actions_from_params(self, action_logits: th.Tensor, deterministic: bool = False) -> th.Tensor:
+        self.proba_distribution(action_logits)
+        return self.get_actions(deterministic=deterministic)
+
+    def log_prob_from_params(self, action_logits: th.Tensor):
+        actions = self.actions_from_params(action_logits)
+        return actions, self.log_prob(actions)
+
+
 class DiagGaussianDistribution:
     """reference: core/common/distributions.py:125-204 -- the unsquashed diagonal Gaussian of the on-policy algorithms (torch
     statements: the API and the torch-statement path; the kernel path evaluates the same expressions in csrc/cstr_ppo.hip).

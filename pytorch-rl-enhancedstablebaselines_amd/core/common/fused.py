@@ -1450,25 +1450,45 @@ def twin_stack(arena, first_group: int = 0, n_layers: Optional[int] = None):
 class FastActorCritic:
     """The on-policy ActorCriticPolicy (core/common/policies.py) on the kernel path: both trunks and both heads through the per-layer
     Linear kernels (`linear`: forward, and backward with deferred weight gradients), the diagonal Gaussian head in one launch
-    (hip_ops.diag_gaussian_act). Noise: `eps_queue` (teacher-forced [n, A] draws, tests) first, the Philox stream `rng_ctl` otherwise."""
+    (hip_ops.diag_gaussian_act). Noise: `eps_queue` (teacher-forced [n, A] draws, tests) first, the Philox stream `rng_ctl` otherwise.
+    The categorical form (a Discrete valve face of 2 to 16 levels per valve): `logits()` replaces `mean()`, the head is
+    hip_ops.categorical_act, `act()` returns the index as a float [n, 1] and the valve pair the env steps with; `action_queue`
+    (teacher-forced int64 [n] indices, tests) first, the Philox stream otherwise."""
 
     def __init__(self, policy, rng_ctl: Optional[th.Tensor] = None):
         self.policy = policy
         self.pi_layers = FastMLP(policy.mlp_extractor.policy_net).layers + [(policy.action_net, ACT_NONE)]
         self.vf_layers = FastMLP(policy.mlp_extractor.value_net).layers + [(policy.value_net, ACT_NONE)]
-        self.act_dim = policy.action_net.out_features
-        dev = policy.log_std.device
-        self.low = th.as_tensor(policy.action_space.low, dtype=th.float32).reshape(-1).to(dev).contiguous()
-        self.high = th.as_tensor(policy.action_space.high, dtype=th.float32).reshape(-1).to(dev).contiguous()
+        self.discrete = bool(getattr(policy, "discrete", False))
+        dev = policy.action_net.weight.device
+        if self.discrete:
+            self.n_actions = policy.action_net.out_features
+            self.levels = self.face_levels(self.n_actions)
+            self.act_dim = 1  # the buffer's action row: the index as one float
+        else:
+            self.act_dim = policy.action_net.out_features
+            self.low = th.as_tensor(policy.action_space.low, dtype=th.float32).reshape(-1).to(dev).contiguous()
+            self.high = th.as_tensor(policy.action_space.high, dtype=th.float32).reshape(-1).to(dev).contiguous()
         self.rng_ctl = rng_ctl
         self.eps_queue: list = []
+        self.action_queue: list = []
         self._bufs: dict = {}
+
+    @staticmethod
+    def face_levels(n_actions: int) -> int:
+        """levels per valve of a Discrete(levels^2) valve face, 0 if n_actions is no square"""
+        k = int(round(n_actions ** 0.5))
+        return k if k * k == n_actions else 0
 
     @staticmethod
     def supported(policy) -> bool:
         ext = policy.mlp_extractor
-        return (FastMLP.supported(ext.policy_net) and FastMLP.supported(ext.value_net)
-                and hip_ops.ppo_supported(policy.features_dim, policy.action_net.out_features)
+        n_out = policy.action_net.out_features
+        if getattr(policy, "discrete", False):
+            head = hip_ops.categorical_supported(policy.features_dim, n_out, FastActorCritic.face_levels(n_out))
+        else:
+            head = hip_ops.ppo_supported(policy.features_dim, n_out)
+        return (FastMLP.supported(ext.policy_net) and FastMLP.supported(ext.value_net) and head
                 and all(p.grad is not None for p in policy.parameters()))
 
     @staticmethod
@@ -1483,6 +1503,10 @@ class FastActorCritic:
         """the action mean [n, A]"""
         return self._run(self.pi_layers, obs, train_params)
 
+    def logits(self, obs: th.Tensor, train_params: bool = False) -> th.Tensor:
+        """the categorical form's action logits [n, levels^2]"""
+        return self._run(self.pi_layers, obs, train_params)
+
     def values(self, obs: th.Tensor, train_params: bool = False) -> th.Tensor:
         """the value estimate [n, 1]"""
         return self._run(self.vf_layers, obs, train_params)
@@ -1491,13 +1515,30 @@ class FastActorCritic:
         b = self._bufs.get(n)
         if b is None:
             e = lambda *sh: th.empty(*sh, dtype=th.float32, device=device)  # noqa: E731
-            b = self._bufs[n] = dict(action=e(n, self.act_dim), env_action=e(n, self.act_dim), log_prob=e(n))
+            b = self._bufs[n] = dict(action=e(n, self.act_dim), env_action=e(n, 2 if self.discrete else self.act_dim), log_prob=e(n))
         return b
+
+    def _act_categorical(self, obs: th.Tensor, deterministic: bool, want_value: bool):
+        n = obs.shape[0]
+        b = self.bufs(n, obs.device)
+        logits = self.logits(obs)
+        values = self.values(obs) if want_value else None
+        forced = None
+        if not deterministic and self.action_queue:
+            forced = self.action_queue.pop(0).to(obs.device, th.int64).reshape(n).contiguous()
+        rng = None if (deterministic or forced is not None) else self.rng_ctl
+        if not deterministic and forced is None and rng is None:
+            raise RuntimeError("FastActorCritic.act: no index source (neither a queued action nor a Philox stream)")
+        hip_ops.categorical_act(logits, self.levels, b["action"], deterministic=deterministic, action_in=forced, rng_ctl=rng,
+                                valve_out=b["env_action"], log_prob=b["log_prob"])
+        return b["action"], values, b["log_prob"], b["env_action"]
 
     def act(self, obs: th.Tensor, deterministic: bool = False, want_value: bool = True):
         """ActorCriticPolicy.forward without gradients -> (actions [n, A] unclipped, values [n, 1] or None, log_prob [n], env_action =
         clip(actions, low, high)). The outputs are static per row count: valid until the next call with as many rows."""
         with th.no_grad():
+            if self.discrete:  # -> (index as a float [n, 1], values, log_prob, the valve pair [n, 2])
+                return self._act_categorical(obs, deterministic, want_value)
             n = obs.shape[0]
             b = self.bufs(n, obs.device)
             mean = self.mean(obs)

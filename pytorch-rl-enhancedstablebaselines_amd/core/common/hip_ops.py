@@ -1443,6 +1443,11 @@ def ppo_supported(obs_dim: int, act_dim: int) -> bool:
     return obs_dim in (4, 8) and act_dim in (2, 4)
 
 
+def rollout_supported(obs_dim: int, act_dim: int) -> bool:
+    """the device rollout buffer's widths: the Gaussian head's, and act_dim 1 (the Categorical head's index as one float)"""
+    return obs_dim in (4, 8) and act_dim in (1, 2, 4)
+
+
 def new_ppo_workspace(device) -> th.Tensor:
     """uint64[CSTR_PPO_WS_WORDS] (as int64) for cstr_ppo_loss_f32 / cstr_grad_clip_f32: zero before the first use, one per stream"""
     return th.zeros(nv.PPO_WS_WORDS, dtype=th.int64, device=device)
@@ -1455,8 +1460,8 @@ class DeviceRollout:
     FIELDS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
 
     def __init__(self, rows: int, n_envs: int, obs_dim: int, act_dim: int, device):
-        if not ppo_supported(obs_dim, act_dim):
-            raise ValueError(f"DeviceRollout supports obs_dim in (4, 8) and act_dim in (2, 4), got {obs_dim}/{act_dim}")
+        if not rollout_supported(obs_dim, act_dim):
+            raise ValueError(f"DeviceRollout supports obs_dim in (4, 8) and act_dim in (1, 2, 4), got {obs_dim}/{act_dim}")
         if rows <= 0 or n_envs <= 0:
             raise ValueError(f"DeviceRollout needs rows >= 1 and n_envs >= 1, got {rows}/{n_envs}")
         z = lambda *s: th.zeros(*s, dtype=th.float32, device=device)  # noqa: E731
@@ -1647,3 +1652,56 @@ def dqn_loss(q, next_q, valve, reward, done, gamma: float, levels: int, g_q, los
     check(nv.lib().cstr_dqn_loss_f32(ptr(q), C.c_int64(ldq), ptr(next_q), C.c_int64(ldn), ptr(valve), ptr(reward), ptr(done), C.c_float(gamma),
                                      C.c_int64(b), C.c_int(m), C.c_int(levels), ptr(g_q), ptr(loss_out), ptr(loss_sum), ptr(cur_q_out),
                                      ptr(target_out), ptr(workspace), stream_ptr()), "cstr_dqn_loss_f32")
+
+
+# ---- Categorical head of PPO / A2C on the discrete valve face (csrc/cstr_categorical.hip) -------------------------------------------
+def categorical_supported(obs_dim: int, n_actions: int, levels: int) -> bool:
+    return obs_dim in (4, 8) and dqn_supported(n_actions, levels)
+
+
+def categorical_act(logits, levels: int, index_f32, deterministic: bool = False, action_in=None, u=None, rng_ctl=None, index_out=None,
+                    valve_out=None, log_prob=None, u_out=None):
+    """The Categorical(logits) head over logits [n, levels^2] (rows may be strided) in one launch. The index comes from exactly one
+    source: `deterministic` (first maximum of the logits), `action_in` (int64 [n], teacher-forced), `u` ([n] uniforms, inverse CDF) or
+    the Philox stream `rng_ctl` (the uniform is drawn). index_f32 [n] (or [n, 1]) receives the index as a float; optional: index_out
+    int64 [n], valve_out [n, 2] (the env's valve pair), log_prob [n], u_out [n] (the uniforms used)."""
+    n, m = logits.shape
+    ldz = _rows(logits, "logits", n, m)
+    _vec(index_f32, "index_f32", n)
+    _opt(action_in, "action_in", (n,), th.int64), _opt(u, "u", (n,), th.float32), _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    _opt(index_out, "index_out", (n,), th.int64), _opt(valve_out, "valve_out", (n, 2), th.float32)
+    _opt(log_prob, "log_prob", (n,), th.float32), _opt(u_out, "u_out", (n,), th.float32)
+    check(nv.lib().cstr_categorical_act_f32(ptr(logits), C.c_int64(ldz), C.c_int64(n), C.c_int(m), C.c_int(levels),
+                                            C.c_int(int(bool(deterministic))), ptr(action_in), ptr(u), ptr(rng_ctl), ptr(index_f32),
+                                            ptr(index_out), ptr(valve_out), ptr(log_prob), ptr(u_out), stream_ptr()), "cstr_categorical_act_f32")
+
+
+CAT_PPO, CAT_A2C = 0, 1
+
+
+def categorical_loss(objective: int, logits, levels: int, actions, values, adv, returns, normalize_advantage: bool, ent_coef: float,
+                     vf_coef: float, g_logits, g_value, workspace, old_values=None, old_log_prob=None, clip_range: float = 0.0,
+                     clip_range_vf: Optional[float] = None, scalars_out=None, scalars_sum=None, log_prob_out=None):
+    """ppo.py:213-264 (CAT_PPO: the six PPO_SCALARS) or a2c.py:150-171 (CAT_A2C: the four A2C_SCALARS) on a Categorical head in one
+    launch: the scalars and d loss / d (logits, value). actions [b] or [b, 1]: the stored index as a float. g_logits has the logits'
+    shape and row stride."""
+    b, m = logits.shape
+    ldz = _rows(logits, "logits", b, m)
+    if _rows(g_logits, "g_logits", b, m) != ldz:
+        raise ValueError("g_logits must have the logits' row stride")
+    for t, nm in ((actions, "actions"), (values, "values"), (adv, "adv"), (returns, "returns"), (g_value, "g_value")):
+        _vec(t, nm, b)
+    for t, nm in ((old_values, "old_values"), (old_log_prob, "old_log_prob"), (log_prob_out, "log_prob_out")):
+        if t is not None:
+            _vec(t, nm, b)
+    n_scalars = 6 if objective == CAT_PPO else 4
+    for t, nm in ((scalars_out, "scalars_out"), (scalars_sum, "scalars_sum")):
+        if t is not None:
+            _vec(t, nm, n_scalars)
+    _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    p = nv.CategoricalLoss(logits.data_ptr(), ldz, actions.data_ptr(), values.data_ptr(), dp(old_values), dp(old_log_prob), adv.data_ptr(),
+                           returns.data_ptr(), b, m, int(levels), int(objective), int(bool(normalize_advantage)), float(clip_range),
+                           -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef), float(vf_coef), g_logits.data_ptr(),
+                           g_value.data_ptr(), dp(scalars_out), dp(scalars_sum), dp(log_prob_out))
+    check(nv.lib().cstr_categorical_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_categorical_loss_f32")

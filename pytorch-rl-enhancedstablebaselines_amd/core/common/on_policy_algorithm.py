@@ -22,6 +22,7 @@ from core.common import blas, fused
 from core.common.base_class import BaseAlgorithm
 from core.common.buffers import RolloutBuffer
 from core.common.callbacks import BaseCallback, MaybeCallback
+from core.common.spaces import Discrete, as_discrete
 from core.common.vec_env import VecEnv
 
 
@@ -122,7 +123,8 @@ class OnPolicyAlgorithm(BaseAlgorithm):
     def _device_rollout(self) -> bool:
         rb = self.rollout_buffer
         return (self._denv is not None and self._fused_learner and type(rb) is RolloutBuffer and rb.n_envs == self._denv.num_envs
-                and rb.obs_shape[0] == self._denv.obs_dim and rb.action_dim == self._denv.act_dim)
+                and rb.obs_shape[0] == self._denv.obs_dim
+                and rb.action_dim == (1 if self._denv.discrete_actions is not None else self._denv.act_dim))  # Discrete: the index
 
     def collect_rollouts(self, env: VecEnv, callback: BaseCallback, rollout_buffer: RolloutBuffer, n_rollout_steps: int) -> bool:
         """reference :162-268"""
@@ -190,7 +192,11 @@ class OnPolicyAlgorithm(BaseAlgorithm):
             actions, values, log_probs = self.policy(obs_tensor)
             actions, values, log_probs = actions.clone(), values.clone(), log_probs.clone()
         actions_np = actions.cpu().numpy()
-        clipped = np.clip(actions_np, self.action_space.low, self.action_space.high)
+        if isinstance(self.action_space, Discrete):  # :228-232: indices step the env as they are and are stored as [n, 1]
+            clipped = actions_np
+            actions_np = actions_np.reshape(-1, 1)
+        else:
+            clipped = np.clip(actions_np, self.action_space.low, self.action_space.high)
         new_obs, rewards, dones, infos = env.step(clipped)
         rewards = np.array(rewards, dtype=np.float32)
         ret = self._ep_return.cpu().numpy() + rewards
@@ -255,6 +261,20 @@ class OnPolicyAlgorithm(BaseAlgorithm):
             self.train()
         callback.on_training_end()
         return self
+
+    @classmethod
+    def _check_archive(cls, data: dict, env) -> None:
+        """An archive written on a Discrete face fits an env with the same number of indices only (and a Box archive a Box env): the
+        policy's head is built from the env's action space."""
+        saved = data.get("action_space")
+        if not isinstance(saved, dict) or not ({"n", "low"} & set(saved)):
+            return  # an archive of the reference: its spaces are not stored as plain data
+        saved_n = saved.get("n")
+        face = as_discrete(getattr(env, "action_space", None))
+        if saved_n != (None if face is None else int(face.n)):
+            was = "a Box action space" if saved_n is None else f"Discrete({saved_n})"
+            raise ValueError(f"the archive was written for {was}, the env has {getattr(env, 'action_space', None)} "
+                             f"(discrete_actions={getattr(getattr(env, 'unwrapped', env), 'discrete_actions', None)})")
 
     def _get_torch_save_params(self) -> tuple:
         """reference :342-345"""

@@ -152,4 +152,7 @@ def get_obs_shape(space) -> tuple:
 
 
 def get_action_dim(space) -> int:
+    """reference: core/common/preprocessing.py:184-210 -- a Discrete action is a single int"""
+    if as_discrete(space) is not None:
+        return 1
     return int(np.prod(as_box(space).shape))

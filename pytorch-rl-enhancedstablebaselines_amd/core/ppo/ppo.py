@@ -8,7 +8,10 @@ the flat arena (its coefficient stays on the device) and the FlatAdam step. Noth
 set (the early stop needs approx_kl on the host, as in the reference). Another optimiser class, or widths the kernels decline, run
 the reference's own torch statements on the arena parameters (`fused_learner` False); they are also the tests' reference.
 
-Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, discrete actions, CNN / dict policies."""
+On a Discrete valve face (`CSTRVecEnv(discrete_actions=K)`) the policy has a Categorical head: the rollout head and the loss launch
+are csrc/cstr_categorical.hip's (hip_ops.categorical_act / categorical_loss), the buffer's action row is the index as one float.
+
+Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiDiscrete / MultiBinary actions, CNN / dict policies."""
 import warnings
 from typing import Optional, Union
 
@@ -18,6 +21,7 @@ from torch.nn import functional as F
 from core.common import fused, hip_ops
 from core.common.logger import DeviceMean
 from core.common.on_policy_algorithm import OnPolicyAlgorithm
+from core.common.spaces import Discrete
 from core.common.utils import get_schedule_fn
 from core.ppo.policies import MlpPolicy
 
@@ -35,7 +39,7 @@ class PPO(OnPolicyAlgorithm):
                          vf_coef=vf_coef, max_grad_norm=max_grad_norm, use_sde=use_sde, sde_sample_freq=sde_sample_freq,
                          rollout_buffer_class=rollout_buffer_class, rollout_buffer_kwargs=rollout_buffer_kwargs,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs,
-                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box",))
+                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box", Discrete))
         self._check_batch_arguments(batch_size, self.n_steps, None if self.env is None else self.env.num_envs, normalize_advantage)
         self.batch_size = batch_size
         self.n_epochs = n_epochs
@@ -87,13 +91,21 @@ class PPO(OnPolicyAlgorithm):
         b = self._step_bufs.get(rows)
         if b is None:
             e = lambda *sh: th.empty(*sh, dtype=th.float32, device=self.device)  # noqa: E731
-            b = self._step_bufs[rows] = dict(g_mean=e(rows, self.rollout_buffer.action_dim), g_value=e(rows, 1), log_prob=e(rows))
+            b = self._step_bufs[rows] = dict(g_mean=e(rows, self.policy.action_net.out_features), g_value=e(rows, 1), log_prob=e(rows))
         return b
 
     def _minibatch_forward_fused(self, rd, clip_range: float, clip_range_vf: Optional[float], sums: th.Tensor):
         """evaluate_actions on the per-layer kernels and the loss launch; returns what the backward needs"""
         fast, pol = self._fast, self.policy
         b = self._bufs(rd.observations.shape[0])
+        if fast.discrete:  # the Categorical head: g_mean holds d loss / d logits, there is no log_std
+            logits = fast.logits(rd.observations, train_params=True)
+            values = fast.values(rd.observations, train_params=True)
+            hip_ops.categorical_loss(hip_ops.CAT_PPO, logits.detach(), fast.levels, rd.actions, values.detach(), rd.advantages, rd.returns,
+                                     self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
+                                     old_values=rd.old_values, old_log_prob=rd.old_log_prob, clip_range=clip_range, clip_range_vf=clip_range_vf,
+                                     scalars_out=self._scalars, scalars_sum=sums, log_prob_out=b["log_prob"] if self.debug_capture else None)
+            return logits, values, b
         mean = fast.mean(rd.observations, train_params=True)
         values = fast.values(rd.observations, train_params=True)
         hip_ops.ppo_loss(mean.detach(), pol.log_std.detach(), rd.actions, values.detach(), rd.old_values, rd.old_log_prob, rd.advantages,
@@ -192,7 +204,7 @@ class PPO(OnPolicyAlgorithm):
                 y_pred, y_true = rb.values.flatten(), rb.returns.flatten()
                 var_y = y_true.var(unbiased=False)  # explained_variance (utils.py, np.var): NaN where var(y_true) == 0
                 explained_var = th.where(var_y == 0, th.full_like(var_y, float("nan")), 1 - (y_true - y_pred).var(unbiased=False) / var_y)
-                std = th.exp(self.policy.log_std.detach()).mean()
+                std = th.exp(self.policy.log_std.detach()).mean() if hasattr(self.policy, "log_std") else None
         count = max(n_minibatches, 1)
         self.logger.record("train/entropy_loss", DeviceMean(totals[2], count))
         self.logger.record("train/policy_gradient_loss", DeviceMean(totals[0], count))
@@ -201,7 +213,8 @@ class PPO(OnPolicyAlgorithm):
         self.logger.record("train/clip_fraction", DeviceMean(totals[5], count))
         self.logger.record("train/loss", DeviceMean(last_loss, 1))
         self.logger.record("train/explained_variance", DeviceMean(explained_var, 1))
-        self.logger.record("train/std", DeviceMean(std, 1))
+        if std is not None:  # :293-294: a Categorical head has no log_std
+            self.logger.record("train/std", DeviceMean(std, 1))
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         self.logger.record("train/clip_range", clip_range)
         if self.clip_range_vf is not None:

@@ -26,9 +26,6 @@ namespace {
 
 constexpr uint32_t DQN_STREAM_TAG = 0xD09A11C7u;  // counter word 3: never shares counters with the other heads' streams
 
-// v(q) of the discrete valve face (core/common/vec_env/cstr_vec_env.py): f32(-1) + f32(2 q) / f32(K - 1), in that order
-__device__ __forceinline__ float valve_of(const int q, const int K) { return -1.0f + (float)(2 * q) / (float)(K - 1); }
-
 // its inverse on a stored valve value: rint((v + 1) (K - 1) / 2), clamped into [0, K - 1] (a NaN gives 0)
 __device__ __forceinline__ int level_of(const float v, const int K)
 {

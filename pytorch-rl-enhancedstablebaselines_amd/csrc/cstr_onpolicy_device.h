@@ -1,5 +1,5 @@
-// cstr_onpolicy_device.h -- what the on-policy kernels share (cstr_ppo.hip, cstr_a2c.hip; internal, not part of the ABI): row loads
-// and stores, the diagonal Gaussian's log-prob, the fixed-order f64 batch reduction (LDS tree per workgroup, published partials,
+// cstr_onpolicy_device.h -- what the on-policy kernels share (cstr_ppo.hip, cstr_a2c.hip, cstr_dqn.hip, cstr_categorical.hip; internal, not part of the ABI): row loads
+// and stores, the diagonal Gaussian's log-prob, the discrete face's valve values, the fixed-order f64 batch reduction (LDS tree per workgroup, published partials,
 // last-workgroup ticket), the sum-of-squares pass and the coefficient of clip_grad_norm_, and the host-side argument checks.
 // Everything sits in an anonymous namespace: each translation unit gets its own copy, nothing is exported.
 #pragma once
@@ -16,6 +16,7 @@ constexpr float HALF_LOG_2PI_E = 1.418938533204672742f;  // 0.5 + 0.5 * math.log
 constexpr int WS_PART0 = 8;    // workspace word of the first partial (word 0: the ticket; 64-byte offset keeps it on its own line)
 
 template <int W> struct VecOf;
+template <> struct VecOf<1> { typedef float type; };
 template <> struct VecOf<2> { typedef float2 type; };
 template <> struct VecOf<4> { typedef float4 type; };
 
@@ -48,6 +49,9 @@ template <int A> __device__ __forceinline__ float diag_log_prob(const float (&ac
     }
     return lp;
 }
+
+// v(q) of the discrete valve face (core/common/vec_env/cstr_vec_env.py): f32(-1) + f32(2 q) / f32(K - 1), in that order
+__device__ __forceinline__ float valve_of(const int q, const int K) { return -1.0f + (float)(2 * q) / (float)(K - 1); }
 
 // sum of v over the workgroup's 256 threads in a fixed tree; every thread gets the result
 __device__ __forceinline__ double block_sum_f64(double v, double *red)
@@ -101,7 +105,7 @@ inline bool overlap(const void *a, int64_t a_floats, const void *b, int64_t b_fl
 }
 
 inline bool aligned4(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-inline bool row_aligned(const void *p, int width) { return width == 4 ? aligned16(p) : aligned8(p); }
+inline bool row_aligned(const void *p, int width) { return width == 4 ? aligned16(p) : (width == 1 ? aligned4(p) : aligned8(p)); }
 
 inline unsigned lane_grid(int64_t n, int block, int64_t cap)
 {

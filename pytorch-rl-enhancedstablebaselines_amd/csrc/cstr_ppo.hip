@@ -303,7 +303,8 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(float *__restrict__ gra
     if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
 }
 
-inline bool widths_ok(int obs_dim, int act_dim) { return (obs_dim == 4 || obs_dim == 8) && (act_dim == 2 || act_dim == 4); }
+// act_dim 1: the Categorical head's action row, the index as one float (cstr_categorical.hip)
+inline bool widths_ok(int obs_dim, int act_dim) { return (obs_dim == 4 || obs_dim == 8) && (act_dim == 1 || act_dim == 2 || act_dim == 4); }
 
 inline int rollout_check(const cstr_rollout_t *rb)
 {
@@ -384,7 +385,9 @@ extern "C" int cstr_rollout_add_f32(const cstr_rollout_t *rb, int64_t *ctl, cons
 #define ADD_LAUNCH(D, A)                                                                                                              \
     rollout_add_kernel<D, A><<<grid, 64, 0, (hipStream_t)stream>>>(*rb, ctl, obs, act, reward, episode_start, value, log_prob, timeout, \
                                                                   terminal_value, gamma, done, ep_return, ep_len, ep_stats)
-    if (d == 4 && a == 2) ADD_LAUNCH(4, 2);
+    if (d == 4 && a == 1) ADD_LAUNCH(4, 1);
+    else if (a == 1) ADD_LAUNCH(8, 1);
+    else if (d == 4 && a == 2) ADD_LAUNCH(4, 2);
     else if (d == 4) ADD_LAUNCH(4, 4);
     else if (a == 2) ADD_LAUNCH(8, 2);
     else ADD_LAUNCH(8, 4);
@@ -441,7 +444,9 @@ extern "C" int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx,
     const int d = rb->obs_dim, a = rb->act_dim;
 #define GATHER_LAUNCH(D, A) \
     ppo_gather_kernel<D, A><<<grid, 256, 0, (hipStream_t)stream>>>(*rb, idx, batch, obs, act, old_value, old_log_prob, adv, ret)
-    if (d == 4 && a == 2) GATHER_LAUNCH(4, 2);
+    if (d == 4 && a == 1) GATHER_LAUNCH(4, 1);
+    else if (a == 1) GATHER_LAUNCH(8, 1);
+    else if (d == 4 && a == 2) GATHER_LAUNCH(4, 2);
     else if (d == 4) GATHER_LAUNCH(4, 4);
     else if (a == 2) GATHER_LAUNCH(8, 2);
     else GATHER_LAUNCH(8, 4);

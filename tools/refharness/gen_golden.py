@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,init,vecenv,callbacks]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,ppo_discrete,a2c_discrete,init,vecenv,callbacks]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -1273,7 +1273,7 @@ class _PpoHooks:
         self._dummy.step_wait = self._step_wait
 
 
-def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, target_kl=None, **kw):
+def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, target_kl=None, venv=None, **kw):
     """One teacher-forceable PPO iteration of the reference on the CPU: _setup_learn (which resets the envs), THEN the step counters of
     the envs in `late` are set near the time limit (set before learn() they would be undone by the reset), collect_rollouts, train()."""
     from core.common.logger import Logger
@@ -1285,7 +1285,7 @@ def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=()
     pk = {} if net_arch is None else dict(policy_kwargs=dict(net_arch=net_arch))
     with _w.catch_warnings():
         _w.simplefilter("ignore")
-        model = PPO("MlpPolicy", _make_venv(n_envs), seed=seed, device="cpu", n_steps=n_steps, batch_size=batch_size, n_epochs=n_epochs,
+        model = PPO("MlpPolicy", _make_venv(n_envs) if venv is None else venv, seed=seed, device="cpu", n_steps=n_steps, batch_size=batch_size, n_epochs=n_epochs,
                     learning_rate=lr, ent_coef=ent_coef, target_kl=target_kl, **pk, **kw)
     model.set_logger(Logger(folder=None, output_formats=[]))
     out = _flat_sd("before/policy", model.policy.state_dict())
@@ -1300,8 +1300,12 @@ def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=()
         rb = model.rollout_buffer
         for f in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
             out[f"rollout/{f}"] = np.array(getattr(rb, f), np.float32).copy()
-        assert len(hk.draws) == n_steps and len(hk.infos) == n_steps
-        out["eps"] = np.stack([d.numpy() for d in hk.draws])
+        assert len(hk.infos) == n_steps
+        if venv is None:  # a Discrete face samples through multinomial: no Normal draws; the indices are rollout/actions
+            assert len(hk.draws) == n_steps
+            out["eps"] = np.stack([d.numpy() for d in hk.draws])
+        else:
+            assert not hk.draws
         out["timeouts"] = np.array([[bool(i.get("TimeLimit.truncated", False)) and "terminal_observation" in i for i in step] for step in hk.infos],
                                    np.float32)
         with th.no_grad():
@@ -1414,7 +1418,7 @@ class _A2cHooks(_PpoHooks):
                     grad_norm=np.float32(float(norm)))
 
 
-def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, iterations=2, opt_state=True, **kw):
+def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, iterations=2, opt_state=True, venv=None, **kw):
     """`iterations` consecutive teacher-forceable A2C iterations of the reference on the CPU (rollout, train, rollout, train: the
     second step meets a non-zero square_avg): _setup_learn, THEN the step counters of the envs in `late` are set near the time limit."""
     from core.a2c.a2c import A2C
@@ -1422,7 +1426,8 @@ def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=
     from core.common.utils import obs_as_tensor
 
     pk = {} if net_arch is None else dict(policy_kwargs=dict(net_arch=net_arch))
-    model = A2C("MlpPolicy", _make_venv(n_envs), seed=seed, device="cpu", n_steps=n_steps, learning_rate=lr, ent_coef=ent_coef, **pk, **kw)
+    model = A2C("MlpPolicy", _make_venv(n_envs) if venv is None else venv, seed=seed, device="cpu", n_steps=n_steps, learning_rate=lr,
+                ent_coef=ent_coef, **pk, **kw)
     model.set_logger(Logger(folder=None, output_formats=[]))
     out = _flat_sd("before/policy", model.policy.state_dict())
     out["state_dict_keys"] = np.array(list(model.policy.state_dict().keys()))
@@ -1440,8 +1445,12 @@ def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=
             rb = model.rollout_buffer
             for f in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
                 out[f"{pre}rollout/{f}"] = np.array(getattr(rb, f), np.float32).copy()
-            assert len(hk.draws) == n_steps and len(hk.infos) == n_steps
-            out[pre + "eps"] = np.stack([d.numpy() for d in hk.draws])
+            assert len(hk.infos) == n_steps
+            if venv is None:  # a Discrete face samples through multinomial: no Normal draws; the indices are rollout/actions
+                assert len(hk.draws) == n_steps
+                out[pre + "eps"] = np.stack([d.numpy() for d in hk.draws])
+            else:
+                assert not hk.draws
             out[pre + "timeouts"] = np.array([[bool(i.get("TimeLimit.truncated", False)) and "terminal_observation" in i for i in step]
                                               for step in hk.infos], np.float32)
             n_trunc += int(out[pre + "timeouts"].sum())
@@ -1762,6 +1771,71 @@ def gen_dqn():
     _gen_dqn_wiring()
 
 
+# ------------------------------------------------------- PPO / A2C on the discretised valve face (Categorical head)
+def gen_ppo_discrete():
+    """PPO on Discrete(K * K) (core/ppo/ppo.py:127-136, core/common/distributions.py:263-311): ppo_cat_train_kat_small.npz (K = 3, 4
+    envs, n_steps 8, batch 12, 3 epochs, nets [32, 32]), ppo_cat_train_kat_default.npz (K = 5, class-default nets as digests, 8 envs,
+    n_steps 16, batch 64, 2 epochs) and ppo_cat_predict_kat.npz. The sampled indices are rollout/actions [T, N, 1]."""
+    late = ((1, 396), (2, 399), (3, 395))
+    small = dict(n_envs=4, n_steps=8, batch_size=12, n_epochs=3, net_arch=[32, 32], late=late)
+    for seed in range(7, 120):
+        model, out, hk = _ppo_run(seed, venv=_make_discrete_venv(4, 3), **small)
+        clipped = max(float(mb["scalars"][5]) for mb in hk.minibatches)
+        if clipped > 0 and int(out["n_truncations"]) >= 2 and _ppo_margins_ok(hk, 0.2, None):
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the small categorical PPO fixture")
+    out["levels"] = np.int64(3)
+    assert out["rollout/actions"].shape == (8, 4, 1) and "policy/log_std" not in "".join(out["state_dict_keys"].tolist())
+    print(f"ppo cat small: seed {seed}, max clip_fraction {clipped:.3f}, truncations {int(out['n_truncations'])}")
+    save("ppo_cat_train_kat_small.npz", **out)
+    for seed_d in range(11, 120):
+        _, o, hk_d = _ppo_run(seed_d, n_envs=8, n_steps=16, batch_size=64, n_epochs=2, late=((0, 390), (5, 397), (6, 399)),
+                              venv=_make_discrete_venv(8, 5))
+        # the conditions of ppo_train_kat_default.npz: four steps at the class-default head gain of 0.01 move no ratio past the clip range
+        if int(o["n_truncations"]) >= 2 and _ppo_margins_ok(hk_d, 0.2, None):
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the default categorical PPO fixture")
+    o["levels"] = np.int64(5)
+    print(f"ppo cat default: seed {seed_d}")
+    save("ppo_cat_train_kat_default.npz", **slim_weights(o))
+    # predict: the trained small model on 16 seeded observations; every row's top-two logit gap exceeds 1e-4 * max |logit|
+    for pseed in range(99, 200):
+        obs = np.random.default_rng(pseed).uniform(-1, 1, (16, 4)).astype(np.float32)
+        with th.no_grad():
+            logits = model.policy.action_net(model.policy.mlp_extractor.forward_actor(th.as_tensor(obs))).numpy()
+        top = np.sort(logits, axis=1)
+        if ((top[:, -1] - top[:, -2]) > 1e-4 * np.abs(logits).max()).all():
+            break
+    else:
+        raise RuntimeError("no observation seed met the logit-gap condition")
+    p = _flat_sd("policy", model.policy.state_dict())
+    p["obs"], p["net_arch"], p["seed"], p["obs_seed"], p["levels"] = obs, np.array([32, 32], np.int64), out["seed"], np.int64(pseed), np.int64(3)
+    p["deterministic"], _ = model.predict(obs, deterministic=True)
+    assert p["deterministic"].dtype == np.int64 and p["deterministic"].shape == (16,) and np.array_equal(p["deterministic"], logits.argmax(axis=1))
+    p["logits"] = logits
+    with th.no_grad():
+        p["values"] = model.policy.predict_values(th.as_tensor(obs)).numpy()
+    save("ppo_cat_predict_kat.npz", **p)
+
+
+def gen_a2c_discrete():
+    """A2C on Discrete(9), two consecutive iterations: a2c_cat_train_kat_small.npz (K = 3, 4 envs, n_steps 5, nets [32, 32])"""
+    late = ((1, 396), (2, 399), (3, 392))
+    for seed in range(7, 120):
+        _, out = _a2c_run(seed, n_envs=4, net_arch=[32, 32], late=late, venv=_make_discrete_venv(4, 3))
+        trunc = [int(out[f"it{k}/timeouts"].sum()) for k in range(2)]
+        if min(trunc) >= 1:
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the small categorical A2C fixture")
+    assert int(out["n_truncations"]) >= 2 and out["it0/rollout/actions"].shape == (5, 4, 1) and str(out["optimizer"]) == "RMSprop"
+    out["levels"] = np.int64(3)
+    print(f"a2c cat small: seed {seed}, gradient norms {[float(out[f'it{k}/grad_norm']) for k in range(2)]}, truncations {trunc}")
+    save("a2c_cat_train_kat_small.npz", **out)
+
+
 def gen_callbacks():
     """The reference's training callbacks (core/common/callbacks.py:146-680) on small CPU runs of SAC over
     DummyVecEnv([TwoSeriesCSTREnv] * N). Only STRUCTURE is written -- directory listings, evaluations.npz's timesteps / ep_lengths,
@@ -1856,7 +1930,7 @@ def gen_callbacks():
     save("callbacks_kat.npz", **out)
 
 
-GENS = {"callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+GENS = {"ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn}
 
