@@ -987,6 +987,74 @@ int cstr_categorical_act_f32(const float *logits, int64_t ldz, int64_t n, int n_
                              float *valve_out, float *log_prob, float *u_out, cstr_stream_t stream);
 int cstr_categorical_loss_f32(const cstr_categorical_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
 
+/* ---- Hindsight Experience Replay on the goal-conditioned face of the env (core/her/her_replay_buffer.py) ---------------------------
+ * The goal face (constructed here; the reference's env has none): achieved_goal = observation[2] (normalised C2), desired_goal = the
+ * env's own target through the same affine map, g = 2 (target - s_lo[2]) / s_span[2] - 1. A flat row is six floats in key order,
+ * [achieved_goal | desired_goal | observation], rows 8-byte aligned. The reward is the reference's concentration term
+ * (twoseriescstr.py:288-291) on (achieved, desired), in f32 and in this order:
+ *   C2 = s_lo2 + (ag + 1) * s_span2 / 2;  T = s_lo2 + (dg + 1) * s_span2 / 2;  ne = |C2 - T| / conc_span;  r = -5 (ne ne) - 2 ne.
+ * All three entry points validate on the host (NULL, non-positive sizes, a ring that is not (4, 2), misaligned or overlapping rows ->
+ * CSTR_E_BADARG / CSTR_E_UNSUPPORTED) and then only enqueue. */
+#define CSTR_HER_FUTURE 0  /* GoalSelectionStrategy (core/her/goal_selection_strategy.py:12-17) */
+#define CSTR_HER_FINAL 1
+#define CSTR_HER_EPISODE 2
+#define CSTR_HER_MAX_BATCH 1024
+#define CSTR_HER_MAX_ROWS 8192         /* ring rows: the sampler keeps a prefix sum over them in LDS */
+#define CSTR_HER_MAX_ENVS (1 << 24)    /* and rows * n_envs < 2^31: the count of valid transitions is an int32 */
+
+/* Side arrays of the HER ring, beside a cstr_ring_t with (obs_dim, act_dim) = (4, 2). W = ceil(n_envs / 64). */
+typedef struct cstr_her {
+    float *desired_goal;   /* [rows][n_envs]: observations["desired_goal"]; next_observations' is the same within an episode */
+    int32_t *ep_start;     /* [rows][n_envs] (:97) */
+    int32_t *ep_length;    /* [rows][n_envs] (:98); > 0 = the transition can be sampled */
+    int32_t *cur_ep_start; /* [n_envs] (:99) */
+    int32_t *row_valid;    /* [rows]: number of envs with ep_length > 0 in the row; kept current by cstr_her_add_f32 */
+    uint64_t *valid_bits;  /* [rows][W]: bit e of word w set = env 64 w + e of the row has ep_length > 0; likewise */
+} cstr_her_t;
+
+/* VecEnv.step on the goal face, one launch: TwoSeriesCSTREnv.step (the dynamics of cstr_vec_step_f32, bit for bit) with the reward
+ * above on the lane's own target (NaN action or state: old state, -10, truncated, as there), truncation, auto-reset from the env's
+ * own PCG64 stream exactly as cstr_reset_draw_f32 draws it, and the target of the next episode.
+ *   env_obs [N][4] i/o: the env state, replaced by the reset observation where done;  act [N][2];  step_count [N] i/o
+ *   pcg_state [N][4] i/o, static_init double[N][4] or NULL: the reset source
+ *   target [N] i/o: raw setpoint (mol/L) per env
+ *   episode int32[N] i/o or NULL: NULL = targets stay; else an env that finishes redraws target = goal_lo + (goal_hi - goal_lo) * u,
+ *     u = (x >> 8) * 2^-24 with x = word 0 of Philox4x32-10, key = goal_seed, counter = (goal_index_offset + env index [64 bit],
+ *     episode[env], tag 0x90A17A67), and episode[env] += 1: counter-based, no other state
+ *   next_rows [N][6] out: the true next observation (terminal observation where done) with the OLD target
+ *   rows_after [N][6] out: what VecEnv.step returns (reset observation and new target where done)
+ *   reward / done / timeout [N] out. obs_dim must be 4. */
+int cstr_goal_vec_step_f32(const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs, const float *act, int32_t *step_count,
+                           uint64_t *pcg_state, double *static_init, float *target, int32_t *episode, uint64_t goal_seed,
+                           int64_t goal_index_offset, float goal_lo, float goal_hi, float *next_rows, float *rows_after, float *reward,
+                           float *done, float *timeout, int64_t n_envs, cstr_stream_t stream);
+
+/* HerReplayBuffer.add + _compute_episode_length (her_replay_buffer.py:135-184) at the device-resident ring position, a lane per env:
+ * an old episode that the row overwrites is invalidated as a whole (np.arange(pos, ep_start + ep_length) % rows, the reference's
+ * modulo), ep_start[pos] = cur_ep_start, the ring row and the goal are written (obs_rows / next_rows [N][6] flat rows; columns 2..5
+ * go to the ring, column 1 of obs_rows to desired_goal), and where done != 0 the episode's rows get ep_length = end - start with
+ * end = the advanced position (+ rows when it wrapped) and cur_ep_start = the advanced position. row_valid / valid_bits follow every
+ * change. The last workgroup advances ring_ctl like cstr_replay_add_f32. */
+int cstr_her_add_f32(const cstr_ring_t *ring, const cstr_her_t *her, int64_t *ring_ctl, const float *obs_rows, const float *next_rows,
+                     const float *act, const float *rew, const float *done, const float *timeout, cstr_stream_t stream);
+
+/* HerReplayBuffer.sample (her_replay_buffer.py:186-384) in one launch on the legacy MT19937 stream:
+ *   k = randint(0, n_valid, batch) (what np.random.choice(valid_indices, batch) draws) -> the k-th valid (row, env), row-major;
+ *   the first nb_virtual samples are virtual: goal index final = len - 1 (no draw) | future = randint(cur, len) per element,
+ *   cur = (row - ep_start) % rows | episode = randint(0, len) per element (array-form randint: one masked-rejection draw per element
+ *   in order, none where high - low == 1); new goal = next_observations[(index + ep_start) % rows, env][2]; virtual reward = the
+ *   statement above on (next achieved, new goal); real rewards and goals are the stored ones; done = dones * (1 - timeouts).
+ * Outputs hold the real transitions first, then the virtual ones: out_obs / out_next_obs [B][6] flat rows, out_act [B][2], out_done /
+ * out_rew [B]; out_row_idx / out_env_idx / out_goal_row int64[B] or NULL, in output order (goal row -1 for real transitions).
+ * forced_row / forced_env int64[B] (both or neither; draw order, the first nb_virtual are virtual): the index draw is skipped;
+ * forced_goal int64[B] (needs the pair): ring rows of the goals, the goal draw is skipped too. Forced indices are clamped into the ring.
+ * status int32[1] out: 0 = sampled; 1 = no valid transition, nothing else was written and the stream is where it was.
+ * nb_virtual > batch or an unknown strategy: CSTR_E_BADARG; batch > CSTR_HER_MAX_BATCH, rows > CSTR_HER_MAX_ROWS: CSTR_E_UNSUPPORTED. */
+int cstr_her_sample_f32(const cstr_coef_t *coef, const cstr_ring_t *ring, const cstr_her_t *her, uint32_t *mt_state, int64_t batch,
+                        int64_t nb_virtual, int strategy, const int64_t *forced_row, const int64_t *forced_env, const int64_t *forced_goal,
+                        float *out_obs, float *out_act, float *out_next_obs, float *out_done, float *out_rew, int64_t *out_row_idx,
+                        int64_t *out_env_idx, int64_t *out_goal_row, int32_t *status, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ import os
 with open(os.path.join(os.path.dirname(__file__), "version.txt")) as _fh:  # the reference forgot to ship this file
     __version__ = _fh.read().strip()
 
-__all__ = ["SAC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "PPO", "A2C", "DQN", "__version__"]
+__all__ = ["SAC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "PPO", "A2C", "DQN", "HerReplayBuffer", "__version__"]
 
 
 def __getattr__(name):
@@ -34,4 +34,7 @@ def __getattr__(name):
     if name == "DQN":
         from core.dqn import DQN
         return DQN
+    if name == "HerReplayBuffer":
+        from core.her import HerReplayBuffer
+        return HerReplayBuffer
     raise AttributeError(f"module 'core' has no attribute {name!r}")

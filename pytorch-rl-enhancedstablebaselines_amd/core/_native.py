@@ -21,6 +21,8 @@ SDE_MAX_LATENT, SDE_MAX_MATS = 4096, 65537
 BCQ_MAX_LATENT, BCQ_MAX_ACT, BCQ_MAX_SAMPLES, BCQ_MAX_ROWS = 256, 64, 4096, 1 << 24
 ROLLOUT_CTL_WORDS, PPO_WS_WORDS, PPO_MAX_BLOCKS, PPO_MAX_ROWS = 4, 1024, 64, 1 << 30
 DQN_MAX_LEVELS = 16
+HER_STRATEGIES = {"future": 0, "final": 1, "episode": 2}
+HER_MAX_BATCH, HER_MAX_ROWS, HER_MAX_ENVS, HER_GOAL_TAG = 1024, 8192, 1 << 24, 0x90A17A67
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -39,6 +41,7 @@ SYMBOLS = (
     "cstr_mt19937_rand_flag_f64", "cstr_dqn_act_f32", "cstr_dqn_loss_f32",
     "cstr_eval_episodes_f32",
     "cstr_categorical_act_f32", "cstr_categorical_loss_f32",
+    "cstr_goal_vec_step_f32", "cstr_her_add_f32", "cstr_her_sample_f32",
 )
 
 
@@ -56,6 +59,11 @@ class Ring(C.Structure):
     """cstr_ring_t"""
     _fields_ = [(n, C.c_void_p) for n in ("obs", "next_obs", "act", "rew", "done", "timeout")] + [
         ("rows", C.c_int64), ("n_envs", C.c_int64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32)]
+
+
+class Her(C.Structure):
+    """cstr_her_t"""
+    _fields_ = [(n, C.c_void_p) for n in ("desired_goal", "ep_start", "ep_length", "cur_ep_start", "row_valid", "valid_bits")]
 
 
 class AdamSeg(C.Structure):

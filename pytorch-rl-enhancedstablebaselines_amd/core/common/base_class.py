@@ -18,6 +18,29 @@ from core.common.vec_env import CSTRVecEnv, VecEnv, unwrap_vec_normalize
 
 class BaseAlgorithm:
     policy_aliases: dict = {}
+    goal_face_support = False  # SAC, TD3, DDPG: HER on the goal face of CSTRVecEnv (a Dict observation space)
+    goal_space = None          # that Dict space; `observation_space` is then the Box of its flat row, which is what the learner sees
+
+    def _accept_goal_face(self, policy, env) -> None:
+        """The env has a Dict observation space (reference: base_class.py:206-210 and what this stack builds of HER)."""
+        from core.common.policies import MultiInputMixin
+
+        name = type(self).__name__
+        if not self.goal_face_support:
+            raise ValueError(f"{name} does not support a Dict observation space (the goal face of the env): HER is built for SAC, TD3 and DDPG")
+        if not (isinstance(self.policy_class, type) and issubclass(self.policy_class, MultiInputMixin)):
+            raise ValueError(f"You must use `MultiInputPolicy` when working with dict observation space, not {policy}")  # :210
+        inner = getattr(env, "unwrapped", env)
+        if unwrap_vec_normalize(env) is not None or not (isinstance(inner, CSTRVecEnv) and inner is env and inner.goal_conditioned):
+            raise ValueError(f"{name} on a Dict observation space needs a bare CSTRVecEnv(goal_conditioned=True): VecNormalize and other "
+                             "wrappers are not built for the goal face")
+        if self.world_size > 1:
+            raise ValueError(f"{name} on the goal face does not run data-parallel (world_size = {self.world_size})")
+        if self.use_sde:
+            raise ValueError(f"{name} on the goal face does not support gSDE (use_sde=True)")
+        self.goal_space = env.observation_space
+        one = np.ones(self.goal_space.flat_dim(), np.float32)
+        self.observation_space = Box(-one, one, dtype=np.float32)
 
     def __init__(self, policy, env, learning_rate, policy_kwargs: Optional[dict] = None, stats_window_size: int = 100,
                  tensorboard_log: Optional[str] = None, verbose: int = 0, device: Union[th.device, str] = "auto",
@@ -56,7 +79,10 @@ class BaseAlgorithm:
         self.policy = None
         if env is not None:
             env = self._wrap_env(env, self.verbose)
-            self.observation_space = as_box(env.observation_space)
+            if isinstance(getattr(env.observation_space, "spaces", None), dict):
+                self._accept_goal_face(policy, env)
+            else:
+                self.observation_space = as_box(env.observation_space)
             self.action_space = self._as_action_space(env.action_space)
             self.n_envs = env.num_envs
             self.env = env
@@ -156,7 +182,11 @@ class BaseAlgorithm:
         env = self._wrap_env(env, self.verbose)
         if env.num_envs != self.n_envs:
             raise AssertionError("The number of environments to be set is different from the number of environments in the model")
-        if as_box(env.observation_space) != self.observation_space or self._as_action_space(env.action_space) != self.action_space:
+        is_dict = isinstance(getattr(env.observation_space, "spaces", None), dict)
+        if is_dict != (self.goal_space is not None):
+            raise ValueError("Observation spaces do not match: a model of the goal face needs CSTRVecEnv(goal_conditioned=True), and only such a model takes it")
+        same_obs = env.observation_space == self.goal_space if is_dict else as_box(env.observation_space) == self.observation_space
+        if not same_obs or self._as_action_space(env.action_space) != self.action_space:
             raise ValueError("Observation/action spaces do not match")
         if force_reset:
             self._last_obs = None
@@ -306,6 +336,12 @@ class BaseAlgorithm:
                 data[nm] = {"n": sp.n, "start": sp.start, "shape": [], "dtype": str(sp.dtype)}
                 continue
             data[nm] = {"low": np.asarray(sp.low).tolist(), "high": np.asarray(sp.high).tolist(), "shape": list(sp.shape), "dtype": str(sp.dtype)}
+        if self.goal_space is not None:  # the Dict space of the goal face, key by key; HER's own arguments (plain JSON, nothing pickled)
+            data["observation_space"] = {"spaces": {k: {"low": np.asarray(s.low).tolist(), "high": np.asarray(s.high).tolist(),
+                                                        "shape": list(s.shape), "dtype": str(s.dtype)} for k, s in self.goal_space.items()}}
+            rb = getattr(self, "replay_buffer", None)
+            if rb is not None and hasattr(rb, "n_sampled_goal"):
+                data["her_kwargs"] = {"n_sampled_goal": int(rb.n_sampled_goal), "goal_selection_strategy": rb.strategy_key}
         data.update(self._extra_save_data())
         for k in (exclude or []):
             data.pop(k, None)
@@ -324,6 +360,15 @@ class BaseAlgorithm:
             raise ValueError("load(): pass `env` (environments are not stored in the archive)")
         cls._check_archive(data, env)
         ctor = {k: data[k] for k in cls._ctor_keys() if k in data}
+        goal_archive = isinstance(data.get("observation_space"), dict) and "spaces" in data["observation_space"]
+        goal_env = isinstance(getattr(getattr(env, "observation_space", None), "spaces", None), dict)
+        if goal_archive != goal_env:
+            raise ValueError("load(): the archive holds a model of the goal face (a Dict observation space) and the env has none"
+                             if goal_archive else "load(): the env has the goal face (a Dict observation space) and the archive's model has none")
+        if goal_archive and "replay_buffer_class" not in kwargs:
+            from core.her import HerReplayBuffer
+
+            ctor["replay_buffer_class"], ctor["replay_buffer_kwargs"] = HerReplayBuffer, dict(data.get("her_kwargs", {}))
         if "train_freq" in data and isinstance(data["train_freq"], list):
             ctor["train_freq"] = (int(data["train_freq"][0]), str(data["train_freq"][1]))
         ctor.update(kwargs)
@@ -354,4 +399,5 @@ class BaseAlgorithm:
 
     @classmethod
     def _construct_for_load(cls, env, device, ctor: dict):
-        return cls("MlpPolicy", env, device=device, **ctor)
+        goal_env = isinstance(getattr(getattr(env, "observation_space", None), "spaces", None), dict)
+        return cls("MultiInputPolicy" if goal_env else "MlpPolicy", env, device=device, **ctor)

@@ -1705,3 +1705,88 @@ def categorical_loss(objective: int, logits, levels: int, actions, values, adv, 
                            -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef), float(vf_coef), g_logits.data_ptr(),
                            g_value.data_ptr(), dp(scalars_out), dp(scalars_sum), dp(log_prob_out))
     check(nv.lib().cstr_categorical_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_categorical_loss_f32")
+
+
+# ---- HER: the goal face of the env and the device HerReplayBuffer (csrc/cstr_her.hip) ---------------------------------------------
+GOAL_ROW = 6  # flat row [achieved_goal | desired_goal | observation]
+
+
+class DeviceHer:
+    """cstr_her_t over torch tensors (HBM), beside a (4, 2) DeviceRing: desired_goal / ep_start / ep_length [rows, n_envs],
+    cur_ep_start [n_envs] (her_replay_buffer.py:97-99) and the two summaries of `ep_length > 0` the sampler reads."""
+
+    def __init__(self, ring: DeviceRing, device):
+        if (ring.obs_dim, ring.act_dim) != (4, 2):
+            raise ValueError(f"the HER ring is the (4, 2) layout, got {(ring.obs_dim, ring.act_dim)}")
+        if ring.rows > nv.HER_MAX_ROWS or ring.n_envs > nv.HER_MAX_ENVS:
+            raise ValueError(f"the HER ring holds at most {nv.HER_MAX_ROWS} rows of {nv.HER_MAX_ENVS} envs, got {ring.rows} x {ring.n_envs}")
+        rows, n = ring.rows, ring.n_envs
+        zi = lambda *s: th.zeros(*s, dtype=th.int32, device=device)  # noqa: E731
+        self.desired_goal = th.zeros(rows, n, dtype=th.float32, device=device)
+        self.ep_start, self.ep_length, self.cur_ep_start = zi(rows, n), zi(rows, n), zi(n)
+        self.row_valid = zi(rows)
+        self.words = (n + 63) // 64
+        self.valid_bits = th.zeros(rows, self.words, dtype=th.int64, device=device)
+        self.status = zi(1)
+        self.c = nv.Her(self.desired_goal.data_ptr(), self.ep_start.data_ptr(), self.ep_length.data_ptr(), self.cur_ep_start.data_ptr(),
+                        self.row_valid.data_ptr(), self.valid_bits.data_ptr())
+
+    def rebuild_summaries(self) -> None:
+        """row_valid / valid_bits from ep_length (after the host wrote ep_length: unpickling, truncate_last_trajectory)."""
+        valid = self.ep_length > 0
+        self.row_valid.copy_(valid.sum(dim=1).to(th.int32))
+        pad = self.words * 64 - valid.shape[1]
+        v = th.nn.functional.pad(valid, (0, pad)).reshape(valid.shape[0], self.words, 64).to(th.int64)
+        self.valid_bits.copy_((v << th.arange(64, device=v.device, dtype=th.int64)).sum(dim=2))
+
+
+def goal_vec_step(coef, integrator: str, env_obs, act, step_count, pcg_state, target, next_rows, rows_after, reward, done, timeout,
+                  static_init=None, episode=None, goal_seed: int = 0, goal_index_offset: int = 0, goal_lo: float = 0.0, goal_hi: float = 0.0):
+    """VecEnv.step on the goal face (cstr_goal_vec_step_f32); `episode` None = targets stay as they are."""
+    n = env_obs.shape[0]
+    _chk(env_obs, "env_obs", (n, 4), th.float32), _chk(act, "act", (n, 2), th.float32), _chk(step_count, "step_count", (n,), th.int32)
+    _chk(pcg_state, "pcg_state", (n, nv.PCG_STATE_WORDS), th.int64), _opt(static_init, "static_init", (n, 4), th.float64)
+    _chk(target, "target", (n,), th.float32), _opt(episode, "episode", (n,), th.int32)
+    _chk(next_rows, "next_rows", (n, GOAL_ROW), th.float32), _chk(rows_after, "rows_after", (n, GOAL_ROW), th.float32)
+    for t, nm in ((reward, "reward"), (done, "done"), (timeout, "timeout")):
+        _chk(t, nm, (n,), th.float32)
+    check(nv.lib().cstr_goal_vec_step_f32(C.byref(coef), C.c_int(INTEGRATORS[integrator]), C.c_int(4), ptr(env_obs), ptr(act), ptr(step_count),
+                                          ptr(pcg_state), ptr(static_init), ptr(target), ptr(episode), C.c_uint64(int(goal_seed) & (2**64 - 1)),
+                                          C.c_int64(int(goal_index_offset)), C.c_float(goal_lo), C.c_float(goal_hi), ptr(next_rows),
+                                          ptr(rows_after), ptr(reward), ptr(done), ptr(timeout), C.c_int64(n), stream_ptr()),
+          "cstr_goal_vec_step_f32")
+
+
+def her_add(ring: DeviceRing, her: DeviceHer, obs_rows, next_rows, act, rew, done, timeout):
+    """HerReplayBuffer.add at the device-resident ring position (cstr_her_add_f32)."""
+    n = ring.n_envs
+    _chk(obs_rows, "obs_rows", (n, GOAL_ROW), th.float32), _chk(next_rows, "next_rows", (n, GOAL_ROW), th.float32)
+    _chk(act, "act", (n, 2), th.float32)
+    for t, nm in ((rew, "rew"), (done, "done"), (timeout, "timeout")):
+        _chk(t, nm, (n,), th.float32)
+    check(nv.lib().cstr_her_add_f32(C.byref(ring.c), C.byref(her.c), ptr(ring.ctl), ptr(obs_rows), ptr(next_rows), ptr(act), ptr(rew), ptr(done),
+                                    ptr(timeout), stream_ptr()), "cstr_her_add_f32")
+
+
+def her_sample(coef, ring: DeviceRing, her: DeviceHer, mt_state, batch: int, nb_virtual: int, strategy: str, out_obs, out_act, out_next_obs,
+               out_done, out_rew, out_row_idx=None, out_env_idx=None, out_goal_row=None, forced_row=None, forced_env=None, forced_goal=None):
+    """HerReplayBuffer.sample in one launch (cstr_her_sample_f32); her.status[0] tells afterwards whether anything was valid."""
+    if strategy not in nv.HER_STRATEGIES:
+        raise ValueError(f"strategy must be one of {list(nv.HER_STRATEGIES)}, got {strategy!r}")
+    if not 0 < batch <= nv.HER_MAX_BATCH:
+        raise ValueError(f"batch_size must be in [1, {nv.HER_MAX_BATCH}], got {batch}")
+    if not 0 <= nb_virtual <= batch:
+        raise ValueError(f"nb_virtual must be in [0, {batch}], got {nb_virtual}")
+    _chk(mt_state, "mt_state", (nv.MT_STATE_WORDS,), th.int32)
+    _chk(out_obs, "out_obs", (batch, GOAL_ROW), th.float32), _chk(out_next_obs, "out_next_obs", (batch, GOAL_ROW), th.float32)
+    _chk(out_act, "out_act", (batch, 2), th.float32)
+    _chk(out_done, "out_done", (batch, 1), th.float32), _chk(out_rew, "out_rew", (batch, 1), th.float32)
+    for t, nm in ((out_row_idx, "out_row_idx"), (out_env_idx, "out_env_idx"), (out_goal_row, "out_goal_row"), (forced_row, "forced_row"),
+                  (forced_env, "forced_env"), (forced_goal, "forced_goal")):
+        _opt(t, nm, (batch,), th.int64)
+    if (forced_row is None) != (forced_env is None) or (forced_goal is not None and forced_row is None):
+        raise ValueError("forced_row and forced_env go together; forced_goal needs them")
+    check(nv.lib().cstr_her_sample_f32(C.byref(coef), C.byref(ring.c), C.byref(her.c), ptr(mt_state), C.c_int64(batch), C.c_int64(nb_virtual),
+                                       C.c_int(nv.HER_STRATEGIES[strategy]), ptr(forced_row), ptr(forced_env), ptr(forced_goal), ptr(out_obs),
+                                       ptr(out_act), ptr(out_next_obs), ptr(out_done), ptr(out_rew), ptr(out_row_idx), ptr(out_env_idx),
+                                       ptr(out_goal_row), ptr(her.status), stream_ptr()), "cstr_her_sample_f32")

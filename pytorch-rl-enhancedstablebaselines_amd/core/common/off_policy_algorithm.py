@@ -97,11 +97,20 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         self.set_random_seed(self.seed)
         if self.replay_buffer_class is None:
             self.replay_buffer_class = ReplayBuffer
+        from core.her import HerReplayBuffer
+
+        is_her = isinstance(self.replay_buffer_class, type) and issubclass(self.replay_buffer_class, HerReplayBuffer)
+        if is_her != (self.goal_space is not None):
+            raise ValueError("HerReplayBuffer needs the goal face of the env (CSTRVecEnv(goal_conditioned=True)) and a MultiInputPolicy" if is_her
+                             else "the goal face of the env needs replay_buffer_class=HerReplayBuffer (a plain DictReplayBuffer is not built)")
         if self.replay_buffer is None:
             kw = dict(self.replay_buffer_kwargs)
-            self.replay_buffer = self.replay_buffer_class(self.buffer_size, self.observation_space, self.action_space,
-                                                          device=self.device, n_envs=self.n_envs,
+            if is_her:  # reference :184-196: the buffer computes the rewards of relabelled transitions with the env
+                kw["env"] = self.env
+            self.replay_buffer = self.replay_buffer_class(self.buffer_size, self.goal_space if is_her else self.observation_space,
+                                                          self.action_space, device=self.device, n_envs=self.n_envs,
                                                           optimize_memory_usage=self.optimize_memory_usage, **kw)
+        self._her_checked = False
         # built on the CPU generator in the reference's construction order (same seed -> same initial weights),
         # then moved into the HBM arenas by the policy itself
         self.policy = self._make_policy()
@@ -118,7 +127,8 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         self._ep_stats = th.zeros(4, dtype=th.float64, device=self.device)
 
     def _make_policy(self):
-        return self.policy_class(self.observation_space, self.action_space, self.lr_schedule, **self.policy_kwargs)
+        space = self.goal_space if self.goal_space is not None else self.observation_space  # a MultiInputPolicy takes the Dict space
+        return self.policy_class(space, self.action_space, self.lr_schedule, **self.policy_kwargs)
 
     def save_replay_buffer(self, path) -> None:
         """reference: off_policy_algorithm.py:214-222"""
@@ -128,14 +138,33 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         save_to_pkl(path, self.replay_buffer, self.verbose)
 
     def load_replay_buffer(self, path, truncate_last_traj: bool = True) -> None:
-        """reference: off_policy_algorithm.py:224-254 (HerReplayBuffer is out of scope)"""
+        """reference: off_policy_algorithm.py:224-254"""
         from core.common.save_util import load_from_pkl
+        from core.her import HerReplayBuffer
 
         self.replay_buffer = load_from_pkl(path, self.verbose)
         assert isinstance(self.replay_buffer, ReplayBuffer), "The replay buffer must inherit from ReplayBuffer class"
+        if isinstance(self.replay_buffer, HerReplayBuffer) != (self.goal_space is not None):
+            raise ValueError("load_replay_buffer: a HerReplayBuffer belongs to a model of the goal face, and only to such a model")
         self.replay_buffer.to(self.device)  # :252-253
+        if isinstance(self.replay_buffer, HerReplayBuffer):  # :243-250
+            assert self.env is not None, "You must pass an environment at load time when using `HerReplayBuffer`"
+            self.replay_buffer.set_env(self.env)
+            if truncate_last_traj:
+                self.replay_buffer.truncate_last_trajectory()
         self.replay_buffer.normalizer = self._vec_normalize_env
+        self._her_checked = False
         self._graph = None  # captured graphs hold the old ring's pointers
+
+    def _her_path(self) -> bool:
+        """The device rollout on the goal face: policy forward on the flat rows, cstr_goal_vec_step_f32, cstr_her_add_f32."""
+        from core.her import HerReplayBuffer
+
+        env, rb = self._denv, self.replay_buffer
+        return env is not None and env.goal_conditioned and isinstance(rb, HerReplayBuffer) and rb.n_envs == env.num_envs
+
+    def _device_rollout(self) -> bool:
+        return self._fast_path() or self._her_path()
 
     def _fast_path(self) -> bool:
         rb = self.replay_buffer
@@ -155,12 +184,12 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         base = self.action_noise
         if isinstance(base, VectorizedActionNoise) and base.n_envs == self.env.num_envs:
             base = base.base_noise
-        if isinstance(base, NormalActionNoise) and self._fast_path() and np.size(base._mu) <= 8:
+        if isinstance(base, NormalActionNoise) and self._device_rollout() and np.size(base._mu) <= 8:
             # the reference's n_envs sequential np.random.normal draws per vec-step (noise.py:44-45, :141-142) as one
             # kernel on the HBM image of the same legacy stream the replay sampler uses: bit-faithful interleaving
             self.action_noise = LegacyStreamNormalActionNoise(base._mu, base._sigma, self.env.num_envs, self.device,
                                                               lambda: self.replay_buffer.sampler_stream)
-        elif isinstance(base, OrnsteinUhlenbeckActionNoise) and self._fast_path() and np.size(base._mu) <= 8:
+        elif isinstance(base, OrnsteinUhlenbeckActionNoise) and self._device_rollout() and np.size(base._mu) <= 8:
             # noise.py:84-89 per env on the same stream, float64 state in HBM
             self.action_noise = LegacyStreamOUActionNoise(base._mu, base._sigma, base._theta, base._dt, base.initial_noise,
                                                           self.env.num_envs, self.device, lambda: self.replay_buffer.sampler_stream)
@@ -179,7 +208,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         while self.num_timesteps < total_timesteps:
             if not self._learn_iteration(callback, log_interval):
                 break
-        if self._fast_path():
+        if self._device_rollout():
             self._sync_episode_stats(log_interval, force=True)
         callback.on_training_end()
         return self
@@ -193,6 +222,13 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
             return False
         if self.num_timesteps > 0 and self.num_timesteps > self.learning_starts:
             gradient_steps = self.gradient_steps if self.gradient_steps >= 0 else rollout.episode_timesteps
+            if gradient_steps > 0 and not self._her_checked and self._her_path():
+                # HerReplayBuffer.sample's check (her_replay_buffer.py:197-201), once, when training starts: one host read
+                self._her_checked = True
+                if not self.replay_buffer.has_valid_transition():
+                    from core.her.her_replay_buffer import NO_EPISODE_MSG
+
+                    raise RuntimeError(NO_EPISODE_MSG)
             if gradient_steps > 0:
                 self.train(batch_size=self.batch_size, gradient_steps=gradient_steps)
         return True
@@ -438,13 +474,21 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         assert train_freq.frequency > 0, "Should at least collect one step or episode."
         if env.num_envs > 1:
             assert train_freq.unit == TrainFrequencyUnit.STEP, "You must use only one env when doing episodic training."
-        fast = self._fast_path() and train_freq.unit == TrainFrequencyUnit.STEP
+        her = self._her_path()
+        if self.goal_space is not None and not (her and train_freq.unit == TrainFrequencyUnit.STEP):
+            raise ValueError("the goal face is collected on the device only: CSTRVecEnv(goal_conditioned=True), a HerReplayBuffer with the "
+                             "env's n_envs, and a train_freq in steps")
+        fast = (her or self._fast_path()) and train_freq.unit == TrainFrequencyUnit.STEP
         noop_cb = getattr(callback, "is_noop", False)
         callback.on_rollout_start()
         continue_training = True
         while should_collect_more_steps(train_freq, num_collected_steps, num_collected_episodes):
             self._sde_rollout_resets(num_collected_steps)
-            if fast:
+            if her:
+                self._collect_one_her(env.unwrapped, replay_buffer, action_noise, learning_starts)
+                new_obs, rewards, dones = self._last_obs, env._rew, env._done  # device tensors (for callbacks)
+                infos = None
+            elif fast:
                 self._collect_one_fused(env.unwrapped, replay_buffer, action_noise, learning_starts)
                 new_obs, rewards, dones = self._last_obs, env._rew, env._done  # device tensors (for callbacks)
                 infos: Any = None
@@ -499,9 +543,51 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         rb.note_fused_add()
         self._last_obs = self._rollout_obs()
 
+    def _collect_one_her(self, env: CSTRVecEnv, rb, action_noise, learning_starts: int) -> None:
+        """One vec-step on the goal face, entirely in HBM and without a host synchronisation: reference statements :561 (_sample_action,
+        :364-411: the same float32 expressions as the fused collect step, here as element-wise device ops), :564 (env.step =
+        cstr_goal_vec_step_f32) and :580 (_store_transition -> HerReplayBuffer.add = cstr_her_add_f32), then Monitor's episode statistics."""
+        n, dev = env.num_envs, self.device
+        if not hasattr(self, "_act_lo"):
+            self._act_lo = th.as_tensor(np.asarray(self.action_space.low, np.float32), device=dev)
+            self._act_hi = th.as_tensor(np.asarray(self.action_space.high, np.float32), device=dev)
+        lo, hi = self._act_lo, self._act_hi
+        if self._warmup(learning_starts):
+            v = th.as_tensor(self.action_space.sample_batch(n)).to(dev)  # :386-388, drawn on the host like the Box face's warm-up
+        else:
+            pol = self._policy_out_device(env.flat)
+            adv = self._take_rng_advance()  # SAC's rollout head leaves its Philox offset to the launch behind it
+            if adv is not None:
+                adv[0][1] += adv[1]
+            v = lo + (0.5 * (pol + 1.0) * (hi - lo))  # predict(): unscale_action (policies.py:375, :413)
+        sc = 2.0 * ((v - lo) / (hi - lo)) - 1.0  # scale_action (policies.py:402)
+        if action_noise is not None:
+            z = action_noise()
+            z = z if isinstance(z, th.Tensor) else th.as_tensor(np.asarray(z, np.float32))
+            sc = th.clamp(sc + z.to(dev, th.float32).reshape(n, -1), -1.0, 1.0)  # :401-402
+        sc = sc.contiguous()                                 # buffer_action (:405)
+        ea = (lo + (0.5 * (sc + 1.0) * (hi - lo))).contiguous()  # unscale_action (:406)
+        if getattr(self, "_her_rows", None) is None or self._her_rows.shape != env.flat.shape:
+            self._her_rows = th.empty_like(env.flat)
+            self._ep_len = th.zeros(n, dtype=th.float32, device=dev)
+        self._her_rows.copy_(env.flat)  # _last_obs: the step overwrites the env's rows
+        _, rew, done, tout, nxt = env.step_device(ea)
+        rb.add_device(self._her_rows, nxt, sc, rew, done, tout)
+        # Monitor semantics: return / length of the episodes that end here (core/common/monitor.py:96-109), accumulated in HBM
+        ret, length = self._ep_return + rew, self._ep_len + 1.0
+        self._ep_stats[0] += done.sum().double()
+        self._ep_stats[1] += (ret * done).sum().double()
+        self._ep_stats[2] += (length * done).sum().double()
+        self._ep_return.copy_(ret * (1.0 - done))
+        self._ep_len.copy_(length * (1.0 - done))
+        self._after_device_step(action_noise)
+        self._last_obs = env.flat
+
     def _rollout_obs(self) -> th.Tensor:
         """What the rollout policy sees: the env's observation, through VecNormalize when the env is wrapped in one."""
         vn = self._vec_normalize_env
+        if self.goal_space is not None:
+            return self._denv.flat
         return self._denv.obs if vn is None else vn.norm_obs_dev
 
     def _device_collect_step(self, pol: th.Tensor, squashed: int, noise: Optional[th.Tensor], action_noise) -> None:

@@ -7,7 +7,35 @@ import torch as th
 from torch import nn
 
 from core.common.spaces import Discrete, as_box, as_discrete, get_action_dim
-from core.common.torch_layers import FlattenExtractor, create_mlp
+from core.common.torch_layers import CombinedExtractor, FlattenExtractor, create_mlp
+
+
+class MultiInputMixin:
+    """`MultiInputPolicy` of an algorithm = its own policy class on a Dict observation space with a CombinedExtractor (reference:
+    core/sac/policies.py:MultiInputPolicy, core/td3/policies.py:MultiInputPolicy). The extractor concatenates in key order and has no
+    parameters, so the networks are the class's own on the flat row: `observation_space` is that row's Box, `goal_space` the Dict.
+    `predict()` takes a dict of arrays or flat rows."""
+
+    def __init__(self, observation_space, action_space, lr_schedule, *args, features_extractor_class=CombinedExtractor, **kwargs):
+        from core.common.spaces import Box
+
+        if not isinstance(getattr(observation_space, "spaces", None), dict):
+            raise ValueError(f"MultiInputPolicy needs a Dict observation space, got {observation_space!r}")
+        object.__setattr__(self, "goal_space", observation_space)
+        low = np.concatenate([np.asarray(s.low, np.float32).reshape(-1) for s in observation_space.spaces.values()])
+        high = np.concatenate([np.asarray(s.high, np.float32).reshape(-1) for s in observation_space.spaces.values()])
+        super().__init__(Box(low, high, dtype=np.float32), action_space, lr_schedule, *args, features_extractor_class=features_extractor_class,
+                         **kwargs)
+
+    def obs_to_tensor(self, observation) -> tuple:
+        """reference: policies.py:240-277, Dict branch: the sub-arrays become one flat row per observation, in key order"""
+        if isinstance(observation, dict):
+            keys = list(self.goal_space.spaces.keys())
+            vectorized = np.ndim(observation[keys[-1]]) == len(self.goal_space.spaces[keys[-1]].shape) + 1
+            parts = [np.asarray(observation[k].cpu() if isinstance(observation[k], th.Tensor) else observation[k], dtype=np.float32) for k in keys]
+            parts = [p.reshape(-1, int(np.prod(self.goal_space.spaces[k].shape))) for p, k in zip(parts, keys)]
+            return th.as_tensor(np.concatenate(parts, axis=1), device=self.device), vectorized
+        return super().obs_to_tensor(observation)
 
 
 class BaseModel(nn.Module):
@@ -28,12 +56,18 @@ class BaseModel(nn.Module):
         self.features_extractor_class = features_extractor_class
         self.features_extractor_kwargs = features_extractor_kwargs or {}
 
+    goal_space = None  # the Dict space of a MultiInputPolicy (MultiInputMixin); `observation_space` is then its flat row
+
     def make_features_extractor(self) -> nn.Module:
+        if self.features_extractor_class is CombinedExtractor and self.goal_space is not None:
+            return CombinedExtractor(self.goal_space)
         if self.features_extractor_class is not FlattenExtractor:
-            raise NotImplementedError("Only FlattenExtractor is built (CNN / dict extractors are out of scope, SURVEY 2)")
+            raise NotImplementedError("Only FlattenExtractor and, on a Dict space, CombinedExtractor are built (CNN extractors are out of scope, SURVEY 2)")
         return FlattenExtractor(int(np.prod(self.observation_space.shape)))
 
-    def extract_features(self, obs: th.Tensor, features_extractor: nn.Module) -> th.Tensor:
+    def extract_features(self, obs, features_extractor: nn.Module) -> th.Tensor:
+        if isinstance(obs, dict):  # preprocess_obs, Dict branch (preprocessing.py:140-146)
+            return features_extractor({k: v.float() for k, v in obs.items()})
         return features_extractor(obs.float())  # preprocess_obs, Box branch (preprocessing.py:118-121)
 
     @property

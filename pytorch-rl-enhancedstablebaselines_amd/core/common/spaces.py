@@ -103,6 +103,59 @@ class Discrete(Space):
         return f"Discrete({self.n})" if self.start == 0 else f"Discrete({self.n}, start={self.start})"
 
 
+class Dict(Space):
+    """A dictionary of spaces with SORTED keys, as gymnasium.spaces.Dict orders a plain dict (the goal face of the env: achieved_goal,
+    desired_goal, observation). The device-side observation is the flat row of the sub-spaces in key order."""
+
+    def __init__(self, spaces=None, seed=None, **kwargs):
+        given = dict(spaces or {}, **kwargs)
+        self.spaces = {k: given[k] for k in sorted(given)}
+        for k, s in self.spaces.items():
+            if not isinstance(s, Space):
+                raise ValueError(f"Dict space element is not an instance of Space: key={k!r}, space={s!r}")
+        self._shape, self.dtype, self._np_random = None, None, None
+        if seed is not None:
+            self.seed(seed)
+
+    @property
+    def shape(self):
+        return None
+
+    def seed(self, seed: Optional[int] = None):
+        ss = np.random.SeedSequence(seed)
+        for sub, child in zip(self.spaces.values(), ss.spawn(len(self.spaces))):
+            sub._np_random = np.random.Generator(np.random.PCG64(child))
+        return [ss.entropy]
+
+    def keys(self):
+        return self.spaces.keys()
+
+    def items(self):
+        return self.spaces.items()
+
+    def values(self):
+        return self.spaces.values()
+
+    def __getitem__(self, key):
+        return self.spaces[key]
+
+    def sample(self) -> dict:
+        return {k: s.sample() for k, s in self.spaces.items()}
+
+    def contains(self, x) -> bool:
+        return isinstance(x, dict) and x.keys() == self.spaces.keys() and all(s.contains(x[k]) for k, s in self.spaces.items())
+
+    def flat_dim(self) -> int:
+        return int(sum(np.prod(s.shape) for s in self.spaces.values()))
+
+    def __eq__(self, other):
+        return isinstance(getattr(other, "spaces", None), dict) and list(other.spaces.keys()) == list(self.spaces.keys()) and all(
+            self.spaces[k] == other.spaces[k] for k in self.spaces)
+
+    def __repr__(self):
+        return "Dict(" + ", ".join(f"{k!r}: {s}" for k, s in self.spaces.items()) + ")"
+
+
 def as_discrete(space) -> Optional[Discrete]:
     """`space` as a Discrete (itself, or a scalar-shaped object with a count `n` and no bounds, e.g. a gymnasium.spaces.Discrete; a
     MultiBinary(n) has shape (n,) and is none), else None."""

@@ -16,6 +16,24 @@ class FlattenExtractor(nn.Module):
         return self.flatten(observations)
 
 
+class CombinedExtractor(nn.Module):
+    """reference: core/common/torch_layers.py:266-316 for a Dict of vector sub-spaces: every key is flattened and the results are
+    concatenated in key order. No parameters, so a policy built on it has the state-dict keys and seeded initial weights of the
+    reference's MultiInputPolicy. The device-side observation of the goal face already is that concatenation (one flat row per env):
+    a tensor passes through unchanged."""
+
+    def __init__(self, observation_space):
+        super().__init__()
+        self.keys = list(observation_space.spaces.keys())
+        self.extractors = nn.ModuleDict({k: nn.Flatten() for k in self.keys})
+        self.features_dim = int(observation_space.flat_dim())
+
+    def forward(self, observations) -> th.Tensor:
+        if isinstance(observations, dict):
+            return th.cat([self.extractors[k](observations[k]) for k in self.keys], dim=1)  # :311-316
+        return observations.reshape(observations.shape[0], -1)
+
+
 def create_mlp(input_dim: int, output_dim: int, net_arch: list, activation_fn=nn.ReLU, squash_output: bool = False,
                with_bias: bool = True) -> list:
     modules: list = []

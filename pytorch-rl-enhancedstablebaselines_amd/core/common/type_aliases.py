@@ -13,6 +13,15 @@ class ReplayBufferSamples(NamedTuple):
     rewards: th.Tensor
 
 
+class DictReplayBufferSamples(NamedTuple):
+    """reference: core/common/type_aliases.py (DictReplayBufferSamples); observations / next_observations: {key: tensor}"""
+    observations: dict
+    actions: th.Tensor
+    next_observations: dict
+    dones: th.Tensor
+    rewards: th.Tensor
+
+
 class RolloutBufferSamples(NamedTuple):
     observations: th.Tensor
     actions: th.Tensor

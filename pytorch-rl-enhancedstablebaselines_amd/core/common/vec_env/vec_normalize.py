@@ -57,6 +57,8 @@ class VecNormalize(VecEnv):
                  norm_obs_keys=None):
         if not isinstance(venv, CSTRVecEnv):
             raise ValueError("VecNormalize wraps the device-resident CSTRVecEnv (or DummyVecEnv of TwoSeriesCSTREnv) in this stack")
+        if getattr(venv, "goal_conditioned", False):
+            raise ValueError("VecNormalize is not built for the goal face of the env (a Dict observation space, goal_conditioned=True)")
         if norm_obs_keys is not None:
             raise ValueError("`norm_obs_keys` param is applicable only with `gym.spaces.Dict` observation spaces")  # :118-120
         super().__init__(venv.num_envs, venv.observation_space, venv.action_space)

@@ -20,7 +20,7 @@ the values into a slot array; each recorded launch reads its own slot. Target up
 in-body positions at which `_n_calls` hits the update period.
 
 Not built (each raises where reachable): CnnPolicy / MultiInputPolicy, a VecNormalize-wrapped env, data-parallel training
-(world_size > 1), optimize_memory_usage, HER."""
+(world_size > 1), optimize_memory_usage, HER (core/her and the env's goal face serve SAC, TD3 and DDPG)."""
 import warnings
 from typing import List, Optional, Union
 

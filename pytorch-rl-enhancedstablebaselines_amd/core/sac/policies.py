@@ -9,7 +9,7 @@ from torch import nn
 from core.common import distributed as dist_util
 from core.common.arena import FlatAdam, ParamArena, make_optimizer
 from core.common.distributions import SquashedDiagGaussianDistribution, StateDependentNoiseDistribution
-from core.common.policies import BasePolicy, ContinuousCritic
+from core.common.policies import BasePolicy, ContinuousCritic, MultiInputMixin
 from core.common.spaces import get_action_dim
 from core.common.torch_layers import FlattenExtractor, create_mlp, get_actor_critic_arch
 
@@ -169,3 +169,7 @@ class SACPolicy(BasePolicy):
 
 
 MlpPolicy = SACPolicy
+
+
+class MultiInputPolicy(MultiInputMixin, SACPolicy):
+    """reference: sac/policies.py MultiInputPolicy -- SACPolicy with a CombinedExtractor on a Dict observation space"""

@@ -17,11 +17,12 @@ from core.common.arena import FlatAdam, ParamArena
 from core.common.chain import SacChain
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
-from core.sac.policies import MlpPolicy
+from core.sac.policies import MlpPolicy, MultiInputPolicy
 
 
 class SAC(OffPolicyAlgorithm):
-    policy_aliases = {"MlpPolicy": MlpPolicy}
+    policy_aliases = {"MlpPolicy": MlpPolicy, "MultiInputPolicy": MultiInputPolicy}
+    goal_face_support = True  # HER on the goal face of the env
     train_batch_size = 64
     chain_type = SacChain
 

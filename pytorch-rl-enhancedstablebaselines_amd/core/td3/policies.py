@@ -6,7 +6,7 @@ from torch import nn
 
 from core.common import distributed as dist_util
 from core.common.arena import FlatAdam, ParamArena, make_optimizer
-from core.common.policies import BasePolicy, ContinuousCritic
+from core.common.policies import BasePolicy, ContinuousCritic, MultiInputMixin
 from core.common.spaces import get_action_dim
 from core.common.torch_layers import FlattenExtractor, create_mlp, get_actor_critic_arch
 
@@ -106,3 +106,7 @@ class TD3Policy(BasePolicy):
 
 
 MlpPolicy = TD3Policy
+
+
+class MultiInputPolicy(MultiInputMixin, TD3Policy):
+    """reference: td3/policies.py MultiInputPolicy -- TD3Policy with a CombinedExtractor on a Dict observation space"""

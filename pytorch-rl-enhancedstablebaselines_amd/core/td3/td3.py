@@ -9,11 +9,12 @@ from core.common import fused, hip_ops
 from core.common.chain import Td3Chain
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
-from core.td3.policies import MlpPolicy
+from core.td3.policies import MlpPolicy, MultiInputPolicy
 
 
 class TD3(OffPolicyAlgorithm):
-    policy_aliases = {"MlpPolicy": MlpPolicy}
+    policy_aliases = {"MlpPolicy": MlpPolicy, "MultiInputPolicy": MultiInputPolicy}
+    goal_face_support = True  # HER on the goal face of the env (DDPG inherits it)
     train_batch_size = 100
     chain_type = Td3Chain
 

@@ -1,0 +1,416 @@
+// cstr_her.hip -- Hindsight Experience Replay on the goal-conditioned face of the CSTR env, for gfx950 (MI355X):
+//   cstr_goal_vec_step_f32  VecEnv.step on the goal face: the env step of cstr_env_device.h, the goal reward with the lane's own
+//                           target, auto-reset from the env's PCG64 stream, the Philox target redraw, flat [ag | dg | obs] rows;
+//   cstr_her_add_f32        HerReplayBuffer.add + _compute_episode_length (core/her/her_replay_buffer.py:135-184), a lane per env;
+//   cstr_her_sample_f32     HerReplayBuffer.sample (:186-384) in one launch on NumPy's legacy MT19937 stream.
+// The goal has one dimension: achieved_goal = observation[2] (normalised C2), so the ring stores no achieved goals.
+//
+// The sampler is ONE workgroup. Wave 0 owns the MT19937 stream (one-wave twist and index draw of cstr_mt_device.h); the goal
+// draw of `future` / `episode` is NumPy's array-form randint, i.e. one scalar masked-rejection draw per element in order, each
+// with its own mask: wave 0 walks it with wave-uniform control flow (every lane reads the same LDS word). Selecting the k-th valid
+// transition and the gather are a lane per sample. Valid transitions are found through two summaries that cstr_her_add_f32 keeps
+// current: row_valid[r] (valid envs of ring row r) and valid_bits[r][w] (bit e of word w: env 64 w + e is valid).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/cstr_rl_hip.h"
+#include "cstr_device.h"
+
+#include "cstr_env_device.h"
+#include "cstr_mt_device.h"
+#include "cstr_rng_device.h"
+
+namespace {
+
+constexpr int HER_TPB = 256;
+constexpr uint32_t HER_GOAL_TAG = 0x90A17A67u;  // counter word 3 of the target redraw: shares no counters with the other streams
+
+// desired_goal of a raw target: the observation's own affine map of C2 (twoseriescstr.py:131), f32
+__device__ __forceinline__ float goal_of_target(const cstr_coef_t &k, const float target) { return 2.0f * (target - k.s_lo[2]) / k.s_span[2] - 1.0f; }
+
+// GoalEnv reward = the reference's concentration term (twoseriescstr.py:288-291) on (achieved, desired), both normalised
+__device__ __forceinline__ float goal_reward(const float s_lo2, const float s_span2, const float conc_span, const float ag, const float dg)
+{
+    const float C2 = s_lo2 + (ag + 1.0f) * s_span2 / 2.0f;
+    const float T = s_lo2 + (dg + 1.0f) * s_span2 / 2.0f;
+    const float ne = fabsf(C2 - T) / conc_span;
+    return -5.0f * (ne * ne) - 2.0f * ne;
+}
+
+// flat row [achieved_goal | desired_goal | observation]: six floats, 8-byte aligned
+__device__ __forceinline__ void store_row6(float *p, const int64_t i, const float dg, const float o[4])
+{
+    float2 *q = reinterpret_cast<float2 *>(p + 6 * i);
+    q[0] = make_float2(o[2], dg);
+    q[1] = make_float2(o[0], o[1]);
+    q[2] = make_float2(o[2], o[3]);
+}
+
+struct GoalDraw { uint64_t seed; int64_t index_offset; float lo, hi; int32_t *episode; };
+
+// ---- VecEnv.step on the goal face (dummy_vec_env.py:56-73 over TwoSeriesCSTREnv.step) ------------------------------------------
+template <int INTEG>
+__global__ void goal_step_kernel(const cstr_coef_t k, float *__restrict__ env_obs, const float *__restrict__ act, int32_t *__restrict__ step_count,
+                                 uint64_t *__restrict__ pcg, double *__restrict__ static_init, float *__restrict__ target, const GoalDraw gd,
+                                 float *__restrict__ next_rows, float *__restrict__ rows_after, float *__restrict__ reward,
+                                 float *__restrict__ done, float *__restrict__ timeout, const int64_t n)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float o[2][4], on[4], raw[4], a[4], r;
+        load_obs<0>(env_obs, i, o);
+        load_act<2>(act, i, a);
+        int32_t st = step_count[i];
+        float tg = target[i];
+        bool bad = (a[0] != a[0]) || (a[1] != a[1]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bad |= (o[0][j] != o[0][j]);
+        const bool trunc = cstr_step_lane<INTEG>(k, o[0], a[0], a[1], st, on, raw, r);
+        const float dg = goal_of_target(k, tg);
+        if (!bad) r = goal_reward(k.s_lo[2], k.s_span[2], k.conc_span, on[2], dg);  // NaN path: old state, -10, truncated
+        const bool d = trunc;
+        store_row6(next_rows, i, dg, on);
+        reward[i] = r;
+        done[i] = d ? 1.0f : 0.0f;
+        timeout[i] = trunc ? 1.0f : 0.0f;
+        if (d) {  // dummy_vec_env.py:68-72: the env's own reset stream, as cstr_reset_draw_f32 consumes it
+            uint64_t pst[4];
+            load_pcg(pcg, i, pst);
+            float ro[2][4];
+            reset_draw_env<0>(k, pst, static_init, i, ro);
+            *reinterpret_cast<ulonglong2 *>(pcg + 4 * i) = make_ulonglong2(pst[0], pst[1]);
+            store_obs<0>(env_obs, i, ro);
+            float dg2 = dg;
+            if (gd.episode) {  // target of the episode that starts now: counter (env index, episode ordinal, tag), key = goal seed
+                const int32_t e = gd.episode[i];
+                const uint64_t idx = (uint64_t)(gd.index_offset + i);
+                uint32_t x[4];
+                philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)e, HER_GOAL_TAG, (uint32_t)gd.seed, (uint32_t)(gd.seed >> 32), x);
+                const float u = (float)(x[0] >> 8) * (1.0f / 16777216.0f);
+                tg = gd.lo + (gd.hi - gd.lo) * u;
+                target[i] = tg;
+                gd.episode[i] = e + 1;
+                dg2 = goal_of_target(k, tg);
+            }
+            store_row6(rows_after, i, dg2, ro[0]);
+            st = 0;
+        } else {
+            float oo[2][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) oo[0][j] = on[j];
+            store_obs<0>(env_obs, i, oo);
+            store_row6(rows_after, i, dg, on);
+        }
+        step_count[i] = st;
+    }
+}
+
+// ---- HerReplayBuffer.add -----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void her_set_valid(const cstr_her_t &h, const int64_t words, const int64_t r, const int64_t i, const bool valid)
+{
+    unsigned long long *w = reinterpret_cast<unsigned long long *>(h.valid_bits) + r * words + (i >> 6);
+    const unsigned long long bit = 1ULL << (i & 63);
+    if (valid) {
+        if (!(atomicOr(w, bit) & bit)) atomicAdd(h.row_valid + r, 1);
+    } else {
+        if (atomicAnd(w, ~bit) & bit) atomicSub(h.row_valid + r, 1);
+    }
+}
+
+__global__ void her_add_kernel(const cstr_ring_t ring, const cstr_her_t h, int64_t *__restrict__ ring_ctl, const float *__restrict__ obs_rows,
+                               const float *__restrict__ next_rows, const float *__restrict__ act, const float *__restrict__ rew,
+                               const float *__restrict__ done, const float *__restrict__ timeout)
+{
+    const int64_t n = ring.n_envs, rows = ring.rows, pos = ring_ctl[0], words = (n + 63) >> 6;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t o = pos * n + i;
+        // her_replay_buffer.py:148-154: writing onto an old episode deletes the whole of it
+        const int32_t len0 = h.ep_length[o];
+        if (len0 > 0) {
+            const int64_t end = (int64_t)h.ep_start[o] + len0;
+            for (int64_t j = pos; j < end; ++j) {  // np.arange(pos, episode_end) % buffer_size
+                const int64_t r = j % rows;
+                if (h.ep_length[r * n + i] > 0) her_set_valid(h, words, r, i, false);
+                h.ep_length[r * n + i] = 0;
+            }
+        }
+        const int32_t cs = h.cur_ep_start[i];
+        h.ep_start[o] = cs;  // :157
+        // :162, DictReplayBuffer.add: the row; achieved_goal is column 2 of the observation and is not stored
+        const float2 g = *reinterpret_cast<const float2 *>(obs_rows + 6 * i);
+        const float2 x01 = *reinterpret_cast<const float2 *>(obs_rows + 6 * i + 2), x23 = *reinterpret_cast<const float2 *>(obs_rows + 6 * i + 4);
+        const float2 y01 = *reinterpret_cast<const float2 *>(next_rows + 6 * i + 2), y23 = *reinterpret_cast<const float2 *>(next_rows + 6 * i + 4);
+        *reinterpret_cast<float4 *>(ring.obs + o * 4) = make_float4(x01.x, x01.y, x23.x, x23.y);
+        *reinterpret_cast<float4 *>(ring.next_obs + o * 4) = make_float4(y01.x, y01.y, y23.x, y23.y);
+        *reinterpret_cast<float2 *>(ring.act + o * 2) = *reinterpret_cast<const float2 *>(act + 2 * i);
+        h.desired_goal[o] = g.y;
+        ring.rew[o] = rew[i];
+        const float dn = done[i];
+        ring.done[o] = dn;
+        ring.timeout[o] = timeout[i];
+        if (dn != 0.0f) {  // :165-184, _compute_episode_length with self.pos already advanced by the add
+            const int64_t new_pos = (pos + 1 == rows) ? 0 : pos + 1;
+            int64_t end = new_pos;
+            if (end < cs) end += rows;
+            const int32_t len = (int32_t)(end - cs);
+            for (int64_t j = cs; j < end; ++j) {  // np.arange(episode_start, episode_end) % buffer_size
+                const int64_t r = j % rows;
+                h.ep_length[r * n + i] = len;
+                her_set_valid(h, words, r, i, true);
+            }
+            h.cur_ep_start[i] = (int32_t)new_pos;
+        }
+    }
+    ring_advance_last_block(ring_ctl, rows);
+}
+
+// ---- HerReplayBuffer.sample --------------------------------------------------------------------------------------------------
+struct HerSampleArgs {
+    cstr_ring_t ring;
+    cstr_her_t her;
+    uint32_t *mt_state;
+    int batch, nb_virtual, strategy;
+    float s_lo2, s_span2, conc_span;
+    const int64_t *forced_row, *forced_env, *forced_goal;
+    float *out_obs, *out_act, *out_next_obs, *out_done, *out_rew;
+    int64_t *out_row_idx, *out_env_idx, *out_goal_row;
+    int32_t *status;
+};
+
+__device__ __forceinline__ int64_t clamp_index(const int64_t v, const int64_t n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+
+__global__ __launch_bounds__(HER_TPB) void her_sample_kernel(const HerSampleArgs a)
+{
+    __shared__ uint32_t mt[MT_N];
+    __shared__ int part[HER_TPB];
+    extern __shared__ __align__(16) int32_t dyn[];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, B = a.batch, nbv = a.nb_virtual;
+    const int64_t rows = a.ring.rows, n = a.ring.n_envs, words = (n + 63) >> 6;
+    int32_t *pre = dyn;                    // [rows] inclusive prefix sum of row_valid
+    int32_t *s_row = dyn + rows;           // [B] per sample, in draw order
+    int32_t *s_env = s_row + B, *s_lo = s_env + B, *s_hi = s_lo + B, *s_start = s_hi + B;
+    const bool forced = a.forced_row != nullptr;
+
+    for (int i = t; i < MT_N; i += HER_TPB) mt[i] = a.mt_state[i];
+    int pos = (int)min(a.mt_state[MT_N], (uint32_t)MT_N);  // used by wave 0 only; never past the LDS image
+    // inclusive prefix sum of the valid counts: a contiguous chunk of rows per lane, then the 256 chunk totals
+    const int64_t chunk = (rows + HER_TPB - 1) / HER_TPB, r0 = (int64_t)t * chunk, r1 = (r0 + chunk < rows) ? r0 + chunk : rows;
+    int acc = 0;
+    for (int64_t r = r0; r < r1; ++r) { acc += a.her.row_valid[r]; pre[r] = acc; }
+    part[t] = acc;
+    __syncthreads();
+    int before = 0, n_valid = 0;
+    for (int i = 0; i < HER_TPB; ++i) { const int c = part[i]; if (i < t) before += c; n_valid += c; }
+    for (int64_t r = r0; r < r1; ++r) pre[r] += before;
+    if (!forced && n_valid <= 0) {  // her_replay_buffer.py:197-201; workgroup-uniform: nothing has been written
+        if (t == 0) a.status[0] = 1;
+        return;
+    }
+    if (t == 0) a.status[0] = 0;
+    __syncthreads();
+    // :210-212: np.random.choice(valid_indices, B, replace=True) draws randint(0, n_valid, B); s_row holds k for now
+    if (!forced && wave == 0) pos = mt_randint_fill_wave(mt, pos, (uint32_t)(n_valid - 1), B, s_row, lane);
+    __syncthreads();
+    for (int s = t; s < B; s += HER_TPB) {
+        int64_t row, env;
+        if (forced) {
+            row = clamp_index(a.forced_row[s], rows);
+            env = clamp_index(a.forced_env[s], n);
+        } else {  // :215, the k-th valid (row, env) in row-major order
+            int k = s_row[s];
+            int64_t lo = 0, hi = rows - 1;
+            while (lo < hi) {  // smallest row whose inclusive prefix exceeds k
+                const int64_t mid = (lo + hi) >> 1;
+                if (pre[mid] > k) hi = mid; else lo = mid + 1;
+            }
+            row = lo;
+            if (row > 0) k -= pre[row - 1];
+            env = 0;
+            const unsigned long long *bits = reinterpret_cast<const unsigned long long *>(a.her.valid_bits) + row * words;
+            bool found = false;
+            for (int64_t w0 = 0; w0 < words && !found; w0 += 8) {  // eight independent word loads in flight, then the in-order count
+                unsigned long long v8[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v8[j] = (w0 + j < words) ? bits[w0 + j] : 0ULL;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    unsigned long long v = v8[j];
+                    const int c = __popcll(v);
+                    if (!found && k < c) {
+                        for (; k > 0; --k) v &= v - 1;  // drop the k lowest set bits
+                        env = (w0 + j) * 64 + (int64_t)__builtin_ctzll(v);
+                        found = true;
+                    }
+                    if (!found) k -= c;
+                }
+            }
+            env = clamp_index(env, n);
+        }
+        const int64_t o = row * n + env;
+        const int32_t es = a.her.ep_start[o], el = a.her.ep_length[o];
+        s_row[s] = (int32_t)row;
+        s_env[s] = (int32_t)env;
+        s_start[s] = es;
+        int32_t lo = el - 1, hi = el;  // final: batch_ep_length - 1, no draw (:366-368)
+        if (a.strategy == CSTR_HER_FUTURE) lo = (int32_t)((((row - es) % rows) + rows) % rows);  // :373-374
+        else if (a.strategy == CSTR_HER_EPISODE) lo = 0;                                            // :378
+        s_lo[s] = lo;
+        s_hi[s] = hi;
+    }
+    __syncthreads();
+    if (wave == 0) {
+        if (nbv > 0 && a.strategy != CSTR_HER_FINAL && !a.forced_goal) {
+            // np.random.randint(low[], high[]): one masked-rejection draw per element, in order, none where high - low == 1
+            for (int s = 0; s < nbv; ++s) {  // wave-uniform
+                const int32_t lo = s_lo[s], span = s_hi[s] - lo;
+                uint32_t v = 0;
+                if (span > 1) {
+                    const uint32_t rng = (uint32_t)(span - 1);
+                    uint32_t mask = rng;
+                    mask |= mask >> 1; mask |= mask >> 2; mask |= mask >> 4; mask |= mask >> 8; mask |= mask >> 16;
+                    do {
+                        if (pos == MT_N) { mt_twist_wave(mt, lane); pos = 0; }
+                        v = mt_temper(mt[pos]) & mask;
+                        pos += 1;
+                    } while (v > rng);
+                }
+                if (lane == 0) s_lo[s] = lo + (int32_t)v;
+            }
+        }
+        if (!forced || (nbv > 0 && a.strategy != CSTR_HER_FINAL && !a.forced_goal)) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            for (int i = lane; i < MT_N; i += 64) a.mt_state[i] = mt[i];
+            if (lane == 0) a.mt_state[MT_N] = (uint32_t)pos;
+        }
+    }
+    __syncthreads();
+    // the five outputs: real transitions first, then the virtual ones (:228-238)
+    for (int s = t; s < B; s += HER_TPB) {
+        const bool virt = s < nbv;
+        const int64_t b = virt ? (int64_t)(B - nbv) + s : (int64_t)s - nbv;
+        const int64_t row = s_row[s], env = s_env[s], o = row * n + env;
+        const float4 x = *reinterpret_cast<const float4 *>(a.ring.obs + o * 4), y = *reinterpret_cast<const float4 *>(a.ring.next_obs + o * 4);
+        float dg = a.her.desired_goal[o], rw = a.ring.rew[o];
+        int64_t grow = -1;
+        if (virt) {
+            if (a.forced_goal) grow = clamp_index(a.forced_goal[s], rows);
+            else grow = ((((int64_t)s_lo[s] + s_start[s]) % rows) + rows) % rows;  // :383
+            dg = a.ring.next_obs[(grow * n + env) * 4 + 2];                        // :384, next achieved goal of that transition
+            rw = goal_reward(a.s_lo2, a.s_span2, a.conc_span, y.z, dg);           // :320-335
+        }
+        float2 *po = reinterpret_cast<float2 *>(a.out_obs + 6 * b), *pn = reinterpret_cast<float2 *>(a.out_next_obs + 6 * b);
+        po[0] = make_float2(x.z, dg); po[1] = make_float2(x.x, x.y); po[2] = make_float2(x.z, x.w);
+        pn[0] = make_float2(y.z, dg); pn[1] = make_float2(y.x, y.y); pn[2] = make_float2(y.z, y.w);
+        *reinterpret_cast<float2 *>(a.out_act + 2 * b) = *reinterpret_cast<const float2 *>(a.ring.act + o * 2);
+        a.out_done[b] = a.ring.done[o] * (1.0f - a.ring.timeout[o]);  // :281-283
+        a.out_rew[b] = rw;
+        if (a.out_row_idx) a.out_row_idx[b] = row;
+        if (a.out_env_idx) a.out_env_idx[b] = env;
+        if (a.out_goal_row) a.out_goal_row[b] = grow;
+    }
+}
+
+inline bool spans_overlap(const void *p, int64_t p_bytes, const void *q, int64_t q_bytes)
+{
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(p), b0 = reinterpret_cast<uintptr_t>(q);
+    return a0 < b0 + (uintptr_t)q_bytes && b0 < a0 + (uintptr_t)p_bytes;
+}
+
+inline bool aligned4p(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+
+int check_her(const cstr_ring_t *ring, const cstr_her_t *her)
+{
+    if (!ring || !her) return CSTR_E_BADARG;
+    if (!ring->obs || !ring->next_obs || !ring->act || !ring->rew || !ring->done || !ring->timeout || ring->rows <= 0 || ring->n_envs <= 0)
+        return CSTR_E_BADARG;
+    if (!her->desired_goal || !her->ep_start || !her->ep_length || !her->cur_ep_start || !her->row_valid || !her->valid_bits) return CSTR_E_BADARG;
+    if (ring->obs_dim != 4 || ring->act_dim != 2) return CSTR_E_UNSUPPORTED;
+    if (ring->rows > CSTR_HER_MAX_ROWS || ring->n_envs > CSTR_HER_MAX_ENVS) return CSTR_E_UNSUPPORTED;
+    if (ring->rows * ring->n_envs >= (1LL << 31)) return CSTR_E_UNSUPPORTED;  // the count of valid transitions is an int32
+    if (!aligned16(ring->obs) || !aligned16(ring->next_obs) || !aligned8(ring->act) || !aligned8(her->valid_bits)) return CSTR_E_BADARG;
+    if (!aligned4p(her->desired_goal) || !aligned4p(her->ep_start) || !aligned4p(her->ep_length) || !aligned4p(her->cur_ep_start) ||
+        !aligned4p(her->row_valid))
+        return CSTR_E_BADARG;
+    return CSTR_OK;
+}
+
+}  // namespace
+
+extern "C" int cstr_goal_vec_step_f32(const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs, const float *act,
+                                      int32_t *step_count, uint64_t *pcg_state, double *static_init, float *target, int32_t *episode,
+                                      uint64_t goal_seed, int64_t goal_index_offset, float goal_lo, float goal_hi, float *next_rows,
+                                      float *rows_after, float *reward, float *done, float *timeout, int64_t n_envs, cstr_stream_t stream)
+{
+    if (!coef || !env_obs || !act || !step_count || !pcg_state || !target || !next_rows || !rows_after || !reward || !done || !timeout ||
+        n_envs <= 0)
+        return CSTR_E_BADARG;
+    if (obs_dim != 4 || (integrator != CSTR_INTEGRATOR_EULER && integrator != CSTR_INTEGRATOR_RK4)) return CSTR_E_UNSUPPORTED;
+    if (!aligned16(env_obs) || !aligned8(act) || !aligned16(pcg_state) || !aligned8(next_rows) || !aligned8(rows_after) || !aligned4p(target) ||
+        !aligned4p(step_count) || (episode && !aligned4p(episode)))
+        return CSTR_E_BADARG;
+    if (episode && !(goal_lo <= goal_hi)) return CSTR_E_BADARG;
+    const int64_t row_bytes = 24 * n_envs;
+    if (spans_overlap(next_rows, row_bytes, rows_after, row_bytes) || spans_overlap(next_rows, row_bytes, env_obs, 16 * n_envs) ||
+        spans_overlap(rows_after, row_bytes, env_obs, 16 * n_envs))
+        return CSTR_E_BADARG;
+    const GoalDraw gd{goal_seed, goal_index_offset, goal_lo, goal_hi, episode};
+    int block, grid;
+    env_launch_shape(n_envs, block, grid);
+    hipStream_t s = (hipStream_t)stream;
+    if (integrator == CSTR_INTEGRATOR_EULER)
+        goal_step_kernel<CSTR_INTEGRATOR_EULER><<<grid, block, 0, s>>>(*coef, env_obs, act, step_count, pcg_state, static_init, target, gd, next_rows,
+                                                                        rows_after, reward, done, timeout, n_envs);
+    else
+        goal_step_kernel<CSTR_INTEGRATOR_RK4><<<grid, block, 0, s>>>(*coef, env_obs, act, step_count, pcg_state, static_init, target, gd, next_rows,
+                                                                      rows_after, reward, done, timeout, n_envs);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_her_add_f32(const cstr_ring_t *ring, const cstr_her_t *her, int64_t *ring_ctl, const float *obs_rows, const float *next_rows,
+                                const float *act, const float *rew, const float *done, const float *timeout, cstr_stream_t stream)
+{
+    const int rc = check_her(ring, her);
+    if (rc) return rc;
+    if (!ring_ctl || !obs_rows || !next_rows || !act || !rew || !done || !timeout) return CSTR_E_BADARG;
+    if (!aligned8(obs_rows) || !aligned8(next_rows) || !aligned8(act) || !aligned4p(rew) || !aligned4p(done) || !aligned4p(timeout)) return CSTR_E_BADARG;
+    const int64_t cells = ring->rows * ring->n_envs, n = ring->n_envs;
+    if (spans_overlap(ring->obs, 16 * cells, obs_rows, 24 * n) || spans_overlap(ring->next_obs, 16 * cells, obs_rows, 24 * n) ||
+        spans_overlap(ring->obs, 16 * cells, next_rows, 24 * n) || spans_overlap(ring->next_obs, 16 * cells, next_rows, 24 * n))
+        return CSTR_E_BADARG;
+    int block, grid;
+    env_launch_shape(n, block, grid);
+    her_add_kernel<<<grid, block, 0, (hipStream_t)stream>>>(*ring, *her, ring_ctl, obs_rows, next_rows, act, rew, done, timeout);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_her_sample_f32(const cstr_coef_t *coef, const cstr_ring_t *ring, const cstr_her_t *her, uint32_t *mt_state, int64_t batch,
+                                   int64_t nb_virtual, int strategy, const int64_t *forced_row, const int64_t *forced_env,
+                                   const int64_t *forced_goal, float *out_obs, float *out_act, float *out_next_obs, float *out_done,
+                                   float *out_rew, int64_t *out_row_idx, int64_t *out_env_idx, int64_t *out_goal_row, int32_t *status,
+                                   cstr_stream_t stream)
+{
+    const int rc = check_her(ring, her);
+    if (rc) return rc;
+    if (!coef || !mt_state || !out_obs || !out_act || !out_next_obs || !out_done || !out_rew || !status || batch <= 0) return CSTR_E_BADARG;
+    if (nb_virtual < 0 || nb_virtual > batch) return CSTR_E_BADARG;
+    if (strategy != CSTR_HER_FUTURE && strategy != CSTR_HER_FINAL && strategy != CSTR_HER_EPISODE) return CSTR_E_BADARG;
+    if ((forced_row == nullptr) != (forced_env == nullptr) || (forced_goal && !forced_row)) return CSTR_E_BADARG;
+    if (batch > CSTR_HER_MAX_BATCH) return CSTR_E_UNSUPPORTED;
+    if (!aligned8(out_obs) || !aligned8(out_next_obs) || !aligned8(out_act) || !aligned4p(out_done) || !aligned4p(out_rew) || !aligned4p(mt_state) ||
+        !aligned4p(status))
+        return CSTR_E_BADARG;
+    const void *outs[5] = {out_obs, out_next_obs, out_act, out_done, out_rew};
+    const int64_t out_bytes[5] = {24 * batch, 24 * batch, 8 * batch, 4 * batch, 4 * batch};
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (spans_overlap(outs[i], out_bytes[i], outs[j], out_bytes[j])) return CSTR_E_BADARG;
+    HerSampleArgs a;
+    a.ring = *ring; a.her = *her; a.mt_state = mt_state;
+    a.batch = (int)batch; a.nb_virtual = (int)nb_virtual; a.strategy = strategy;
+    a.s_lo2 = coef->s_lo[2]; a.s_span2 = coef->s_span[2]; a.conc_span = coef->conc_span;
+    a.forced_row = forced_row; a.forced_env = forced_env; a.forced_goal = forced_goal;
+    a.out_obs = out_obs; a.out_act = out_act; a.out_next_obs = out_next_obs; a.out_done = out_done; a.out_rew = out_rew;
+    a.out_row_idx = out_row_idx; a.out_env_idx = out_env_idx; a.out_goal_row = out_goal_row; a.status = status;
+    const size_t dyn = sizeof(int32_t) * ((size_t)ring->rows + 5 * (size_t)batch);
+    her_sample_kernel<<<1, HER_TPB, dyn, (hipStream_t)stream>>>(a);
+    return (int)hipGetLastError();
+}

@@ -19,6 +19,7 @@ Reference entry points exercised (file:line in /root/reference):
   core/ppo/ppo.py:184-300                PPO.train; core/common/on_policy_algorithm.py:162-268 collect_rollouts
   core/a2c/a2c.py:132-190                A2C.train
   core/dqn/dqn.py:168-256                DQN._on_step / train / predict
+  core/her/her_replay_buffer.py:135-408  HerReplayBuffer.add / sample / truncate_last_trajectory (--only her)
   core/common/utils.py:457-481           polyak_update
   core/common/callbacks.py:146-680       EventCallback ... StopTrainingOnNoModelImprovement (structure only)
 """
@@ -375,7 +376,53 @@ def _gen_sac_sde_predict():
     save("sac_sde_predict_kat.npz", **out)
 
 
-def _gen_sac(tag, net_arch, B, n_steps, n_critics=2, sde=None):
+_HER_STEPS, _HER_TARGETS = (7, 9, 12, 15), (0.12, 0.20, 0.33, 0.40)  # per-env episode lengths / setpoints of the HER learner fixtures
+
+
+def _her_kwargs():
+    from core.her.her_replay_buffer import HerReplayBuffer
+
+    return dict(replay_buffer_class=HerReplayBuffer)
+
+
+def _fill_her(model, venv, rng, steps):
+    """Scripted steps of the goal-face envs into the model's HerReplayBuffer; returns the add inputs as flat rows (`adds_*`), from
+    which a test rebuilds the ring and its episode bookkeeping."""
+    N = venv.num_envs
+    flat = lambda d: np.concatenate([d["achieved_goal"], d["desired_goal"], d["observation"]], axis=1).astype(np.float32)  # noqa: E731
+    rec = {k: [] for k in ("obs", "next", "act", "rew", "done", "timeout")}
+    venv.seed(11)
+    obs = venv.reset()
+    for _ in range(steps):
+        a = rng.uniform(-1, 1, (N, 2)).astype(np.float32)
+        nobs, r, d, infos = venv.step(a)
+        nxt = {k: v.copy() for k, v in nobs.items()}
+        for i in range(N):
+            if d[i]:
+                for k in nxt:
+                    nxt[k][i] = infos[i]["terminal_observation"][k]
+        model.replay_buffer.add(obs, nxt, a, r, d, infos)
+        for k, v in (("obs", flat(obs)), ("next", flat(nxt)), ("act", a), ("rew", np.asarray(r, np.float32)), ("done", d.astype(np.float32)),
+                     ("timeout", np.array([i.get("TimeLimit.truncated", False) for i in infos], np.float32))):
+            rec[k].append(v)
+        obs = nobs
+    return {f"adds_{k}": np.stack(v) for k, v in rec.items()}
+
+
+def _flat_batch(s):
+    """a DictReplayBufferSamples as the five arrays of a flat batch: observations in key order"""
+    cat = lambda d: np.concatenate([d[k].numpy() for k in ("achieved_goal", "desired_goal", "observation")], axis=1)  # noqa: E731
+    return [cat(s.observations), s.actions.numpy().copy(), cat(s.next_observations), s.dones.numpy().copy(), s.rewards.numpy().copy()]
+
+
+def gen_her_learners():
+    """sac_her_train_kat_small.npz / td3_her_train_kat_small.npz: the reference's MultiInputPolicy + HerReplayBuffer (future, 4 goals),
+    seeded initial weights, then teacher-forced train() steps on recorded batches, as the *_train_kat_small fixtures."""
+    _gen_sac("small", [64, 64], 64, 3, her=True)
+    _gen_td3("small", her=True)
+
+
+def _gen_sac(tag, net_arch, B, n_steps, n_critics=2, sde=None, her=False):
     import torch.distributions.normal as tdn
     import torch.nn.functional as F_real
 
@@ -401,8 +448,10 @@ def _gen_sac(tag, net_arch, B, n_steps, n_critics=2, sde=None):
             return F_real.mse_loss(a, b, *args, **kw)
 
     N, D, A = 4, 4, 2
-    venv = _make_venv(N)
+    venv = _make_goal_venv(_HER_STEPS, _HER_TARGETS) if her else _make_venv(N)
     pk = {} if net_arch is None else {"policy_kwargs": dict(net_arch=net_arch)}
+    if her:
+        pk.update(_her_kwargs())
     if n_critics != 2:
         pk.setdefault("policy_kwargs", {})["n_critics"] = n_critics
     if sde is not None:  # gSDE: the construction draws are recorded too
@@ -429,20 +478,24 @@ def _gen_sac(tag, net_arch, B, n_steps, n_critics=2, sde=None):
         assert len(rec.eps) == 2
         init_draws, rec.eps = rec.eps, []
     else:
-        model = SAC("MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
+        model = SAC("MultiInputPolicy" if her else "MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
     assert len(model.critic.q_networks) == n_critics
     model.set_logger(Logger(folder=None, output_formats=[]))
     rng = np.random.default_rng(99)
-    _fill_buffer(model, rng, 40, N, D, A)
     out = {}
+    if her:
+        out.update(_fill_her(model, venv, rng, 40))
+    else:
+        _fill_buffer(model, rng, 40, N, D, A)
     out.update(_flat_sd("before/actor", model.actor.state_dict()))
     out.update(_flat_sd("before/critic", model.critic.state_dict()))
     out.update(_flat_sd("before/critic_target", model.critic_target.state_dict()))
     out["before/log_ent_coef"] = model.log_ent_coef.detach().numpy().copy()
     rb = model.replay_buffer
-    out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
-               ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
-               ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
+    if not her:
+        out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
+                   ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
+                   ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
     np.random.seed(2024)
     th.manual_seed(77)
     orig_sample = rb.sample
@@ -450,7 +503,7 @@ def _gen_sac(tag, net_arch, B, n_steps, n_critics=2, sde=None):
 
     def rec_sample(batch_size, env=None):
         s = orig_sample(batch_size, env=env)
-        batches.append([x.numpy().copy() for x in s])
+        batches.append(_flat_batch(s) if her else [x.numpy().copy() for x in s])
         return s
 
     rb.sample = rec_sample
@@ -493,6 +546,8 @@ def _gen_sac(tag, net_arch, B, n_steps, n_critics=2, sde=None):
         # keep the committed fixture small: weights are reproducible from seed 0 (checked by the
         # init KAT), so store only digests of the big tensors for the default-size nets
         out = slim_weights(out, with_shape=False)
+    if her:
+        return save(f"sac_her_train_kat_{tag}.npz", **out)
     save(f"sac_sde_train_kat_{tag[len('sde_'):]}.npz" if sde is not None else f"sac_train_kat_{tag}.npz", **out)
 
 
@@ -511,7 +566,7 @@ def gen_td3_ncrit():
     _gen_td3("small", n_critics=3)
 
 
-def _gen_td3(tag, algo="td3", n_critics=None):
+def _gen_td3(tag, algo="td3", n_critics=None, her=False):
     """tag "small": net_arch [48, 32], batch 64; "default": the class default [400, 300] (td3/policies.py:141-145), batch 256.
     algo "ddpg": core/ddpg/ddpg.py:14-130 -- TD3.train with policy_delay 1, ONE critic (one mse_loss per step) and a
     target-smoothing draw clamped to [-0, 0] (target_policy_noise 0.1, target_noise_clip 0.0).
@@ -539,28 +594,34 @@ def _gen_td3(tag, algo="td3", n_critics=None):
 
     N, D, A, n_steps = 4, 4, 2, 4
     B = 64 if tag == "small" else 256
-    venv = _make_venv(N)
+    venv = _make_goal_venv(_HER_STEPS, _HER_TARGETS) if her else _make_venv(N)
     pk = dict(policy_kwargs=dict(net_arch=[48, 32])) if tag == "small" else {}
+    if her:
+        pk.update(_her_kwargs())
     if n_critics is not None:
         pk.setdefault("policy_kwargs", {})["n_critics"] = n_critics
-    model = TD3("MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
+    model = TD3("MultiInputPolicy" if her else "MlpPolicy", venv, seed=0, device="cpu", batch_size=B, buffer_size=64 * N, **pk)
     model.set_logger(Logger(folder=None, output_formats=[]))
     rng = np.random.default_rng(314)
-    _fill_buffer(model, rng, 40, N, D, A)
     out = {}
+    if her:
+        out.update(_fill_her(model, venv, rng, 40))
+    else:
+        _fill_buffer(model, rng, 40, N, D, A)
     for nm in ("actor", "actor_target", "critic", "critic_target"):
         out.update(_flat_sd(f"before/{nm}", getattr(model, nm).state_dict()))
     rb = model.replay_buffer
-    out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
-               ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
-               ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
+    if not her:
+        out.update(ring_obs=rb.observations.copy(), ring_next_obs=rb.next_observations.copy(), ring_act=rb.actions.copy(),
+                   ring_rew=rb.rewards.copy(), ring_done=rb.dones.copy(), ring_timeout=rb.timeouts.copy(),
+                   ring_pos=np.int64(rb.pos), ring_full=np.uint8(rb.full))
     np.random.seed(555)
     orig_sample = rb.sample
     batches = []
 
     def rec_sample(batch_size, env=None):
         s = orig_sample(batch_size, env=env)
-        batches.append([x.numpy().copy() for x in s])
+        batches.append(_flat_batch(s) if her else [x.numpy().copy() for x in s])
         return s
 
     rb.sample = rec_sample
@@ -591,7 +652,9 @@ def _gen_td3(tag, algo="td3", n_critics=None):
     out["hyper"] = np.array([model.gamma, model.tau, model.target_policy_noise, model.target_noise_clip,
                              model.policy_delay, model.lr_schedule(1), B, n_steps], np.float64)
     out["np_seed"] = np.int64(555)
-    if n_critics is not None:
+    if her:
+        save(f"{algo}_her_train_kat_{tag}.npz", **out)
+    elif n_critics is not None:
         save(f"{algo}_train_kat_ncrit{n_critics}.npz", **out)
     elif tag == "default":
         assert model.actor.mu[0].out_features == 400 and model.actor.mu[2].out_features == 300
@@ -1930,7 +1993,135 @@ def gen_callbacks():
     save("callbacks_kat.npz", **out)
 
 
-GENS = {"ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+def _goal_reward(ag, dg):
+    """The goal face's float32 reward statement (core/common/vec_env/cstr_vec_env.py states the same): the reference's concentration
+    term (twoseriescstr.py:288-291) on (achieved, desired), both normalised."""
+    lo2, span2, cs = np.float32(0.0), np.float32(0.7) - np.float32(0.0), np.float32(0.45 - 0.05)
+    ag, dg = np.asarray(ag, np.float32).reshape(-1), np.asarray(dg, np.float32).reshape(-1)
+    c2 = lo2 + (ag + np.float32(1)) * span2 / np.float32(2)
+    t = lo2 + (dg + np.float32(1)) * span2 / np.float32(2)
+    ne = np.abs(c2 - t) / cs
+    return (np.float32(-5) * (ne * ne) - np.float32(2) * ne).astype(np.float32)
+
+
+def _make_goal_venv(max_steps, targets):
+    """Harness code of ours: a wrapper AROUND the unmodified TwoSeriesCSTREnv (not a subclass: the env's own compute_reward(state,
+    action) has another signature) that exposes the Dict face and the reward statement above."""
+    import gymnasium
+    from gymnasium import spaces
+
+    from core.common.vec_env.dummy_vec_env import DummyVecEnv
+    from twoseriescstr import TwoSeriesCSTREnv
+
+    class GoalCSTR(gymnasium.Env):
+        def __init__(self, steps, target):
+            self.inner = TwoSeriesCSTREnv()
+            self.inner.max_steps = steps
+            box = lambda n: spaces.Box(-np.ones(n, np.float32), np.ones(n, np.float32), dtype=np.float32)  # noqa: E731
+            self.observation_space = spaces.Dict({"observation": box(4), "achieved_goal": box(1), "desired_goal": box(1)})
+            self.action_space = self.inner.action_space
+            self.goal = np.float32(2) * (np.float32(target) - np.float32(0.0)) / np.float32(0.7) - np.float32(1)
+
+        def _face(self, o):
+            o = np.asarray(o, np.float32)
+            return {"achieved_goal": o[2:3].copy(), "desired_goal": np.array([self.goal], np.float32), "observation": o}
+
+        def reset(self, *, seed=None, options=None):
+            o, info = self.inner.reset(seed=seed, options=options)
+            return self._face(o), info
+
+        def step(self, action):
+            o, _, terminated, truncated, info = self.inner.step(action)
+            d = self._face(o)
+            return d, float(self.compute_reward(d["achieved_goal"][None], d["desired_goal"][None], [info])[0]), terminated, truncated, info
+
+        def compute_reward(self, achieved_goal, desired_goal, infos):
+            return _goal_reward(achieved_goal, desired_goal)
+
+    return DummyVecEnv([lambda s=s, t=t: GoalCSTR(s, t) for s, t in zip(max_steps, targets)])
+
+
+def gen_her():
+    """her_buffer_kat.npz: the unmodified HerReplayBuffer (core/her/her_replay_buffer.py) fed by scripted steps of three goal-face envs
+    with per-env episode lengths, into rings of 4 and 12 rows through three wraps: the add inputs, the episode bookkeeping after every
+    add, seeded sample(10) / sample(256) for the three strategies and n_sampled_goal 0 / 4 (drawn indices, goal indices, the five
+    outputs, the MT19937 state afterwards), and a pickle + truncate_last_trajectory case."""
+    import pickle
+    import warnings
+
+    from core.her.her_replay_buffer import HerReplayBuffer
+    from core.her.goal_selection_strategy import KEY_TO_GOAL_STRATEGY
+
+    N, out = 3, {}
+    targets = (0.12, 0.20, 0.33)
+    for R, tag, steps in ((4, "r4a", (1, 2, 4)), (4, "r4b", (2, 4, 7)), (12, "r12a", (1, 2, 12)), (12, "r12b", (2, 12, 15))):
+        venv = _make_goal_venv(steps, targets)
+        venv.seed(40 + R)
+        obs = venv.reset()
+        buf = HerReplayBuffer(R * N, venv.observation_space, venv.action_space, venv, device="cpu", n_envs=N)
+        rng = np.random.default_rng(R)
+        T = 3 * R + 2
+        rec = {k: [] for k in ("obs", "next", "act", "rew", "done", "timeout", "ep_start", "ep_length", "cur")}
+        flat = lambda d: np.concatenate([d["achieved_goal"], d["desired_goal"], d["observation"]], axis=1).astype(np.float32)  # noqa: E731
+        for _ in range(T):
+            a = rng.uniform(-1, 1, (N, 2)).astype(np.float32)
+            nobs, r, d, infos = venv.step(a)
+            nxt = {k: v.copy() for k, v in nobs.items()}
+            for i in range(N):
+                if d[i]:
+                    for k in nxt:
+                        nxt[k][i] = infos[i]["terminal_observation"][k]
+            buf.add(obs, nxt, a, r, d, infos)
+            for k, v in (("obs", flat(obs)), ("next", flat(nxt)), ("act", a), ("rew", np.asarray(r, np.float32)), ("done", d.astype(np.float32)),
+                         ("timeout", np.array([i.get("TimeLimit.truncated", False) for i in infos], np.float32)),
+                         ("ep_start", buf.ep_start.copy()), ("ep_length", buf.ep_length.copy()), ("cur", buf._current_ep_start.copy())):
+                rec[k].append(v)
+            obs = nobs
+        out.update({f"{tag}/{k}": np.stack(v) for k, v in rec.items()})
+        out[f"{tag}/meta"] = np.array([R, N, T, buf.pos, int(buf.full)], np.int64)
+        # seeded samples; np.random.choice / randint are recorded by hooks around the unmodified sample()
+        choice, randint = np.random.choice, np.random.randint
+        for strategy in ("future", "final", "episode"):
+            for nsg in (0, 4):
+                for B in ((10, 256) if tag in ("r4a", "r12b") else (10,)):
+                    buf.goal_selection_strategy, buf.n_sampled_goal, buf.her_ratio = KEY_TO_GOAL_STRATEGY[strategy], nsg, 1 - (1.0 / (nsg + 1))
+                    drawn = {}
+
+                    def rec_choice(a, **kw):
+                        drawn["flat"] = choice(a, **kw)
+                        return drawn["flat"]
+
+                    def rec_randint(*a, **kw):
+                        drawn["goal"] = randint(*a, **kw)
+                        return drawn["goal"]
+
+                    np.random.seed(1000 + B + nsg)
+                    np.random.choice, np.random.randint = rec_choice, rec_randint
+                    try:
+                        s = buf.sample(B)
+                    finally:
+                        np.random.choice, np.random.randint = choice, randint
+                    st = np.random.get_state()
+                    key = f"{tag}/{strategy}/{nsg}/{B}"
+                    out[key + "/flat_idx"] = np.asarray(drawn["flat"], np.int64)
+                    out[key + "/goal_idx"] = np.asarray(drawn.get("goal", np.zeros(0)), np.int64)
+                    out[key + "/obs"] = np.concatenate([s.observations[k].numpy() for k in ("achieved_goal", "desired_goal", "observation")], axis=1)
+                    out[key + "/next"] = np.concatenate([s.next_observations[k].numpy() for k in ("achieved_goal", "desired_goal", "observation")], axis=1)
+                    out[key + "/act"], out[key + "/done"], out[key + "/rew"] = s.actions.numpy(), s.dones.numpy(), s.rewards.numpy()
+                    out[key + "/mt_key"], out[key + "/mt_pos"] = st[1].astype(np.uint32), np.array([st[2], st[3]], np.int64)
+        # save / load / truncate_last_trajectory (:386-408)
+        clone = pickle.loads(pickle.dumps(buf))
+        clone.set_env(venv)
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            clone.truncate_last_trajectory()
+        out[f"{tag}/trunc/warned"] = np.array([len(w)], np.int64)
+        out[f"{tag}/trunc/ep_length"], out[f"{tag}/trunc/cur"] = clone.ep_length.copy(), clone._current_ep_start.copy()
+        out[f"{tag}/trunc/dones"], out[f"{tag}/trunc/timeouts"] = clone.dones.astype(np.float32), clone.timeouts.astype(np.float32)
+    save("her_buffer_kat.npz", **out)
+
+
+GENS = {"her": gen_her, "her_learners": gen_her_learners,"ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn}
 

@@ -104,8 +104,12 @@ class MultiBinary(Space):
 
 class Dict(Space):
     def __init__(self, spaces=None, seed=None):
-        self.spaces = dict(spaces or {})
+        given = dict(spaces or {})
+        self.spaces = {k: given[k] for k in sorted(given)}  # gymnasium sorts the keys of a plain dict
         super().__init__(None, None, seed)
+
+    def __getitem__(self, key):
+        return self.spaces[key]
 
     def items(self):
         return self.spaces.items()
