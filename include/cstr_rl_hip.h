@@ -736,6 +736,16 @@ typedef struct cstr_chain_root {
 } cstr_chain_root_t;
 int cstr_q_chain_bwd_f32(const cstr_chain_net_t *nets, int n_nets, const cstr_chain_root_t *root, int w_in, int obs_dim, int h1, int h2,
                          float *dz2, float *dz1, float *gact_part, int tiles, cstr_stream_t stream);
+/* Test hook of the two Q launches above. Each has two kernels that write the same bits: the generic one (run-time widths, loss mode,
+ * head kind and partial-sum count) and a lean one for 256 x 256 networks on the (4, 2) and (8, 2) layouts whose partial-sum requests
+ * run on arguments that arrive with the wave, whose remaining arguments are one batch of scalar reads, and whose loss mode, head kind,
+ * store set and partial-sum bucket are fixed at compile time. Lean instantiations exist for what the learners dispatch -- forward:
+ * no pending head, Gaussian, deterministic; backward: mode 1 with the alpha part and next_logp, with next_logp and ent_coef, with
+ * neither (each storing dz1 and dz2), modes 2 and 3 (storing gact_part) -- with at most 16 partial sums; every other launch runs the
+ * generic kernel whatever the switch says.
+ * cstr_chain_lean(on): on = 0 launches the generic kernels from now on, on > 0 the lean ones where they exist (the default), on < 0
+ * changes nothing; returns the setting before the call. */
+int cstr_chain_lean(int on);
 
 /* out[row * out_stride + col] = sum over p < n_parts of part[p][row][col] (p ascending): the finalisation of a chain launch's partial
  * sums for a consumer that is not a chain kernel -- MADDPG's per-layer actor backward (core/maddpg/maddpg.py:174-179) reads

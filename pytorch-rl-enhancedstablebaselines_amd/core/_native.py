@@ -32,7 +32,7 @@ SYMBOLS = (
     "cstr_squashed_gaussian_fwd_f32", "cstr_squashed_gaussian_bwd_f32", "cstr_sac_alpha_f32", "cstr_twin_q_loss_f32",
     "cstr_sac_actor_loss_f32", "cstr_neg_mean_loss_f32", "cstr_td_ens_q_loss_f32", "cstr_sac_actor_ens_loss_f32",
     "cstr_sac_actor_chain_fwd_f32", "cstr_q_chain_fwd_f32", "cstr_q_chain_bwd_f32", "cstr_sac_actor_chain_bwd_f32",
-    "cstr_linear_bwd_weight_adam_sets_f32", "cstr_wgrad_adam_lean", "cstr_wgrad_adam_tile_body", "cstr_chain_sum_parts_f32",
+    "cstr_linear_bwd_weight_adam_sets_f32", "cstr_wgrad_adam_lean", "cstr_wgrad_adam_tile_body", "cstr_chain_lean", "cstr_chain_sum_parts_f32",
     "cstr_sde_draw_f32", "cstr_sde_head_fwd_f32", "cstr_sde_head_bwd_f32", "cstr_sde_param_grad_f32",
     "cstr_bcq_latent_fwd_f32", "cstr_bcq_vae_loss_f32", "cstr_bcq_latent_bwd_f32", "cstr_bcq_expand_f32", "cstr_bcq_perturb_fwd_f32",
     "cstr_bcq_perturb_bwd_f32", "cstr_bcq_target_f32", "cstr_bcq_select_f32",

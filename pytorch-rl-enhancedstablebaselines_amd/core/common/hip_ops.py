@@ -1410,6 +1410,12 @@ def q_chain_bwd(nets, root: "nv.ChainRoot", w_in: int, obs_dim: int, h1: int, h2
                                         ptr(dz1), ptr(gact_part), C.c_int(tiles), stream_ptr()), "cstr_q_chain_bwd_f32")
 
 
+def chain_lean(on: int = -1) -> int:
+    """cstr_chain_lean: 0 = the generic Q chain kernels from now on, > 0 = the lean ones where they exist (the default), < 0 = query;
+    returns the setting before the call (both kernels write the same bits: tests/test_qchain_lean_bodies.py)."""
+    return int(nv.lib().cstr_chain_lean(C.c_int(on)))
+
+
 def sac_actor_chain_bwd(actor: "nv.SacActorNet", gact_part, n_nets: int, n_parts: int, ent_coef, x_pi, params, eps, a_h1, a_h2, g_params, dz2, dz1,
                         batch: int, tiles: int, kind: int = 0):
     """cstr_sac_actor_chain_bwd_f32: action gradient from the critic's partials, head backward (kind: CHAIN_HEAD_GAUSSIAN / _DETERMINISTIC),

@@ -915,6 +915,437 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_kernel(const QBwdArgs 
     CH_STAMP(2, 7);
 }
 
+// ---- the two Q launches, lean (what cstr_q_chain_fwd_f32 / cstr_q_chain_bwd_f32 launch at 256 x 256 unless cstr_chain_lean(0)) -----
+// The kernels above read their arguments where each is first used: kernarg -> the record nets[blockIdx.z] -> root / fin fields ->
+// values behind pointers (b3[0], ent_coef[0]), a scalar round trip each time, three of them in front of the request for the previous
+// launch's partial sums -- and carry every loss mode, every partial-sum bucket and every optional output as run-time branches (4,541
+// instructions in the backward kernel). The lean kernels change none of the arithmetic:
+//   * what the partial-sum requests need (batch, n_parts, the partials' pointers) are the kernel's first 16 argument dwords, which
+//     arrive in SGPRs with the wave (-amdgpu-kernarg-preload-count=16): the requests go out in front of every wait;
+//   * the workgroup's net record and the pointers of its mode are ONE batch of scalar reads (pinned by an empty asm use, as
+//     linear_bwd_weight_adam_sets_lean_kernel does); uniform values behind pointers (b3, ent_coef / log_alpha) ride in the vector
+//     queue behind the partials instead of a dependent scalar round;
+//   * loss mode, alpha / next_logp, the head's kind, the store set and the partial-sum bucket are template parameters chosen by the
+//     host, which instantiates what SAC, TD3, MADDPG and BCQ dispatch and sends everything else to the kernels above.
+// Partial sums keep the generic bucket of every n (PartBatch: n <= 8 the 8-register form, 9 .. 16 sum_parts_n<16>; the loss
+// workgroup: sum_parts' 4 / 8 / 16), i.e. the same adds in the same order over the same zero padding.
+template <int NP>
+struct PartBatchN {
+    float v[NP];
+    // `on` = false: the lane requests nothing (out of range: zeros, no memory access) -- a predicate instead of a branch keeps the
+    // requests in the kernel's entry block, in front of the wait for the batched argument read
+    __device__ __forceinline__ void request(const float *part, const int n, const int64_t stride, const int64_t at, const int64_t total, const bool on = true)
+    {
+        const __amdgpu_buffer_rsrc_t rs = rsrc_of(part, total);
+        const unsigned st = (unsigned)stride, at0 = (unsigned)at;  // the byte offset's low 32 bits, as PartBatch truncates them
+#pragma unroll
+        for (int p = 0; p < NP; ++p) v[p] = ld32(rs, (on && p < n) ? (int)(4u * (p * st + at0)) : BUF_OOB);
+    }
+    __device__ __forceinline__ float sum() const
+    {
+        float s = v[0];
+#pragma unroll
+        for (int p = 1; p < NP; ++p) s += v[p];
+        return s;
+    }
+};
+// a launch-uniform value behind a pointer as a VECTOR load (every lane the same address): it returns in order behind the requests
+// in front of it, where a scalar read would be one more dependent round trip with its own wait
+__device__ __forceinline__ float ld_uniform(const float *p) { return ld32(rsrc_of(p, 1), 0); }
+
+constexpr int part_bucket_row(const int n) { return n <= 8 ? 8 : 16; }                // PartBatch's forms
+constexpr int part_bucket_loss(const int n) { return n <= 4 ? 4 : n <= 8 ? 8 : 16; }  // sum_parts' forms
+
+enum { QF_PLAIN = 0, QF_GAUSSIAN = 1, QF_DETERMINISTIC = 2 };
+struct QFwdLeanArgs {
+    cstr_chain_net_t nets[CSTR_CHAIN_MAX_NETS];
+    float *x_pi, *x_next, *params, *logp_pi, *logp_next;
+};
+
+// q_chain_fwd_kernel<D, A, NQ, 1> with the pending head's kind (FIN: QF_*) and the bucket of its partial sums (PB) fixed
+template <int D, int A, int NQ, int FIN, int PB>
+__global__ __launch_bounds__(CH_THREADS) void q_chain_fwd_lean_kernel(const int batch, const int fin_parts, const float *fin_head_part, const float *fin_hb,
+                                                                      const float *fin_eps, const int fin_part_rows, const int fin_next_offset,
+                                                                      const float fin_sigma, const float fin_clip, const unsigned long long roles,
+                                                                      const QFwdLeanArgs a)
+{
+    extern __shared__ __align__(16) float smem[];
+    constexpr int W = D + A, WX = 1;
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 15, h = lane >> 4;
+    constexpr int T = exact_tiles<NQ, WX>(), S = CH_WAVES / T;
+    const int tile = wave % T, ks = wave / T;
+    const cstr_chain_net_t net = a.nets[blockIdx.z];
+    float *const o_x_pi = a.x_pi, *const o_x_next = a.x_next, *const o_params = a.params, *const o_logp_pi = a.logp_pi, *const o_logp_next = a.logp_next;
+    __builtin_amdgcn_sched_barrier(0);  // the scalar reads are issued here, in front of the address arithmetic of the requests below
+    constexpr int H1 = exact_h1<WX>(), H2 = exact_h2<WX>();
+    const int B = batch;
+    const int n0 = (blockIdx.x * T + tile) * 16, m0 = blockIdx.y * 16;
+    float *xs = smem + SM_XS, *red = smem + SM_RED, *panel = smem + SM_PANEL;
+    constexpr int ld = H1 + 4;
+    float *w1s = panel + 16 * ld;
+    const bool col_ok = n0 + r < H2;
+    CH_STAMP(1, 0);
+    // the pending actor head's partial sums first: their operands, this network's role included (4 bits per network), came with the wave
+    const int role = FIN != QF_PLAIN ? (int)((roles >> (4 * blockIdx.z)) & 15u) : CSTR_CHAIN_ROLE_PLAIN;
+    const bool nxt = role == CSTR_CHAIN_ROLE_NEXT || role == CSTR_CHAIN_ROLE_NEXT_STORE;
+    const bool own = nxt || role == CSTR_CHAIN_ROLE_PI;
+    const bool fin_rows = own || (role == CSTR_CHAIN_ROLE_STORE_PI && blockIdx.x == 0);
+    const bool fin_lane = FIN != QF_PLAIN && fin_rows && t < 16 * A;
+    const int f_row = t / A, f_j = t % A;
+    constexpr bool f_det = FIN == QF_DETERMINISTIC;
+    PartBatchN<PB> p_mu, p_raw;
+    float f_ev = 0.0f, f_hb_mu = 0.0f, f_hb_raw = 0.0f;
+    constexpr int HN = f_det ? A : 2 * A;
+    const int64_t f_i = (nxt ? fin_next_offset : 0) + m0 + f_row;  // row of the actor pass
+    if (FIN != QF_PLAIN) {
+        const int64_t pstride = (int64_t)fin_part_rows * HN, ptotal = pstride * fin_parts;
+        p_mu.request(fin_head_part, fin_parts, pstride, f_i * HN + f_j, ptotal, fin_lane);
+        if (!f_det) p_raw.request(fin_head_part, fin_parts, pstride, f_i * HN + A + f_j, ptotal, fin_lane);
+    }
+    // the whole record and the store pointers in one batch of scalar reads, here
+    asm volatile("" ::"s"(net.w1), "s"(net.b1), "s"(net.w2), "s"(net.b2), "s"(net.w3), "s"(net.x), "s"(net.h1), "s"(net.h2), "s"(net.q_part));
+    if (FIN != QF_PLAIN) asm volatile("" ::"s"(o_x_pi), "s"(o_x_next), "s"(o_params), "s"(o_logp_pi), "s"(o_logp_next));
+    if (fin_lane) {
+        f_ev = (!f_det || fin_eps) ? fin_eps[f_i * A + f_j] : 0.0f;
+        f_hb_mu = fin_hb[f_j];
+        f_hb_raw = f_det ? 0.0f : fin_hb[A + f_j];
+    }
+    // (a) requests that depend on nothing
+    float4 bq[NQ];
+    load_b_fwd<NQ>(bq, net.w2, H2, H1, n0, ks, S);
+    const int col = min(n0 + r, H2 - 1);
+    const float bv = net.b2[col];
+    const float w3v = col_ok ? net.w3[col] : 0.0f;
+    stage_w1<W>(w1s, net.w1, net.b1, H1);
+    L1Direct<W> l1d;
+    if (l1_pad<W>() == 0) l1d.request(net.w1, net.b1, H1);
+    // (b) input rows; the pending head's action columns finalised here (q_chain_fwd_kernel's roles)
+    {
+        const int row = t >> 4, k = t & 15;
+        float xv = k == W ? 1.0f : 0.0f;
+        if (k < W && !(own && k >= D)) xv = net.x[(int64_t)(m0 + row) * W + k];
+        if (!(own && k >= D && k < W)) xs[row * 16 + k] = xv;
+    }
+    float f_mu = 0.0f, f_raw = 0.0f, f_a = 0.0f, f_lp = 0.0f;
+    if (fin_lane) {
+        const float ev = f_ev;
+        f_mu = p_mu.sum() + f_hb_mu;
+        if (f_det) {
+            f_a = tanhf(f_mu);
+            if (nxt) f_a = fminf(fmaxf(f_a + fminf(fmaxf(ev * fin_sigma, -fin_clip), fin_clip), -1.0f), 1.0f);
+        } else {
+            f_raw = p_raw.sum() + f_hb_raw;
+            float term;
+            sample_action(f_mu, f_raw, ev, f_a, term);
+            f_lp = term;
+            if (A >= 2) f_lp += __shfl_xor(f_lp, 1, 64);
+            if (A == 4) f_lp += __shfl_xor(f_lp, 2, 64);
+        }
+        if (own) xs[f_row * 16 + D + f_j] = f_a;
+    }
+    CH_STAMP(1, 1);
+    lds_barrier();
+    CH_STAMP(1, 2);
+    // (c) layer 1 recomputed on the matrix cores
+    layer1_mfma<l1_pad<W>(), W>(xs, w1s, panel, ld, H1, &l1d, net.w1, net.b1);
+    lds_barrier();
+    CH_STAMP(1, 3);
+    f32x4 acc = tile_mma<NQ>(panel, ld, H1, bq, ks, S);
+    CH_STAMP(1, 4);
+    acc = combine_split_k(acc, smem, T, S);
+    CH_STAMP(1, 5);
+    float hv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (wave < T) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
+#ifdef CSTR_HEAD_F64
+            double sd = (double)hv[e] * (double)w3v;
+            sd += __shfl_xor(sd, 8, 64); sd += __shfl_xor(sd, 4, 64); sd += __shfl_xor(sd, 2, 64); sd += __shfl_xor(sd, 1, 64);
+            const float s = (float)sd;
+#else
+            const float s = rowsum16(hv[e] * w3v);
+#endif
+            if (r == 0) red[(tile * 16 + 4 * h + e) * 8] = s;
+        }
+    }
+    lds_barrier();
+    CH_STAMP(1, 6);
+    if (t < 16) {
+        float s = red[t * 8];
+#pragma unroll
+        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + t) * 8];
+        net.q_part[(int64_t)blockIdx.x * B + m0 + t] = s;
+    }
+    // ---- global stores, all behind the last barrier ----
+    if (wave < T && col_ok && net.h2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) net.h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
+    }
+    if (blockIdx.x == 0 && net.h1) store_panel(panel, ld, net.h1, H1, m0);
+    if (fin_lane && blockIdx.x == 0 && role != CSTR_CHAIN_ROLE_NEXT) {
+        const int bb = m0 + f_row;
+        (nxt ? o_x_next : o_x_pi)[(int64_t)bb * W + D + f_j] = f_a;
+        if (!nxt && !f_det) {
+            o_params[(int64_t)bb * 2 * A + f_j] = f_mu;
+            o_params[(int64_t)bb * 2 * A + A + f_j] = f_raw;
+        }
+        if (f_j == 0 && !f_det) (nxt ? o_logp_next : o_logp_pi)[bb] = f_lp;
+    }
+    CH_STAMP(1, 7);
+}
+
+template <int LB>
+__device__ __forceinline__ float q_from_parts_n(const float *part, const float *b3, const int n_parts, const int batch, const int row)
+{
+    const float b = b3[0];
+    return sum_parts_n<LB>(rsrc_of(part, (int64_t)n_parts * batch), n_parts, batch, row) + b;
+}
+
+// chain_loss_workgroup with the mode, the alpha part, next_logp and sum_parts' bucket (LB) fixed: the same expressions, tree and side
+// effects, small enough to sit inline behind the lean kernel's one uniform branch
+template <int MODE, bool ALPHA, bool NLOGP, int LB>
+__device__ __forceinline__ void chain_loss_lean(const cstr_chain_root_t &rt, float *sm)
+{
+    const int tid = threadIdx.x, B = rt.batch, P = rt.n_parts;
+    constexpr bool with_alpha = MODE == 1 && ALPHA;
+    const float la = with_alpha ? rt.alpha.log_alpha[0] : 0.0f;
+    const float ec = with_alpha ? expf(la) : (rt.ent_coef ? rt.ent_coef[0] : 0.0f);
+    const float inv = 1.0f / (float)B;
+    if (MODE == 1) {
+        float a1 = 0.0f, a2 = 0.0f, aa = 0.0f;
+        for (int b = tid; b < B; b += 256) {
+            float q = fminf(q_from_parts_n<LB>(rt.q_part[2], rt.b3[2], P, B, b), q_from_parts_n<LB>(rt.q_part[3], rt.b3[3], P, B, b));
+            if (NLOGP) q = q - ec * rt.next_logp[b];
+            const float tq = rt.rew[b] + (1.0f - rt.done[b]) * rt.gamma * q;
+            const float d1 = q_from_parts_n<LB>(rt.q_part[0], rt.b3[0], P, B, b) - tq, d2 = q_from_parts_n<LB>(rt.q_part[1], rt.b3[1], P, B, b) - tq;
+            a1 += d1 * d1;
+            a2 += d2 * d2;
+            if (with_alpha) aa += rt.alpha.logp_pi[b] + rt.alpha.target_entropy;
+        }
+        const float s1 = block_sum_256(a1, sm), s2 = block_sum_256(a2, sm);
+        const float mean = with_alpha ? block_sum_256(aa, sm) / (float)B : 0.0f;
+        if (tid == 0) {
+            const float loss = rt.scale * (s1 / (float)B + s2 / (float)B);
+            if (rt.loss_out) rt.loss_out[0] = loss;
+            if (rt.loss_sum) rt.loss_sum[0] += loss;
+            if (with_alpha) {
+                rt.alpha.grad_out[0] = -mean;
+                rt.alpha.ent_coef_out[0] = ec;
+                if (rt.alpha.loss_out) rt.alpha.loss_out[0] = -(la * mean);
+                if (rt.alpha.loss_sum) rt.alpha.loss_sum[0] += -(la * mean);
+                if (rt.alpha.ent_coef_sum) rt.alpha.ent_coef_sum[0] += ec;
+            }
+        }
+    } else if (MODE == 3) {
+        float acc = 0.0f;
+        for (int b = tid; b < B; b += 256) acc += q_from_parts_n<LB>(rt.q_part[0], rt.b3[0], P, B, b);
+        const float sum = block_sum_256(acc, sm);
+        if (tid == 0) {
+            const float loss = -(sum * inv);
+            if (rt.loss_out) rt.loss_out[0] = loss;
+            if (rt.loss_sum) rt.loss_sum[0] += loss;
+        }
+    } else {
+        float acc = 0.0f;
+        for (int b = tid; b < B; b += 256) {
+            const float x = q_from_parts_n<LB>(rt.q_part[0], rt.b3[0], P, B, b), c = q_from_parts_n<LB>(rt.q_part[1], rt.b3[1], P, B, b);
+            acc += ec * rt.logp[b] - (x <= c ? x : c);
+        }
+        const float sum = block_sum_256(acc, sm);
+        if (tid == 0) {
+            const float loss = sum * inv;
+            if (rt.loss_out) rt.loss_out[0] = loss;
+            if (rt.loss_sum) rt.loss_sum[0] += loss;
+        }
+    }
+    if (tid == 0 && rt.rng_ctl) rt.rng_ctl[1] += rt.rng_advance;
+    if (tid < 2 && rt.adam_advance[tid]) {
+        int64_t *ctl = rt.adam_advance[tid];
+        double *pw = reinterpret_cast<double *>(ctl + 2);
+        ctl[0] += 1;
+        pw[0] *= rt.adam_beta1[tid];
+        pw[1] *= rt.adam_beta2[tid];
+    }
+}
+
+struct QBwdLeanNet { const float *w1, *w2, *w3, *h1, *h2; };
+struct QBwdLeanArgs {
+    QBwdLeanNet nets[2];
+    const float *b3[4];
+    const float *ec_src;  // MODE 1 with next_logp: log_alpha (ALPHA) or ent_coef
+    const float *rew, *done, *next_logp;
+    float *dz2, *dz1, *gact_part, *q_out, *gq_out, *target_out;
+    float gamma, scale;
+    cstr_chain_root_t root;  // the loss workgroup's
+};
+
+// q_chain_bwd_kernel<D, A, NQ, 1> with the root's mode and sum_parts' bucket of the Q partials (LB: 4, 8 or 16) fixed: MODE 1 stores
+// dz1 / dz2, MODES 2 and 3 the action-gradient partials
+template <int D, int A, int NQ, int MODE, bool ALPHA, bool NLOGP, int LB>
+__global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_lean_kernel(const int batch, const int n_parts, const float *qp0, const float *qp1, const float *qp2,
+                                                                      const float *qp3, const QBwdLeanArgs a)
+{
+    extern __shared__ __align__(16) float smem[];
+    constexpr int W = D + A, WX = 1;
+    constexpr bool GACT = MODE != 1;
+    constexpr int NEED = MODE == 1 ? 4 : MODE == 3 ? 1 : 2;
+    constexpr int PB = part_bucket_row(LB);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 15, h = lane >> 4;
+    const int B = batch;
+    constexpr int H1 = exact_h1<WX>(), H2 = exact_h2<WX>();
+    const int g = blockIdx.z;
+    if (__builtin_expect((int)blockIdx.y == B / 16, 0)) {  // the loss workgroup
+        if (g == 0 && blockIdx.x == 0) chain_loss_lean<MODE, ALPHA, NLOGP, LB>(a.root, smem + SM_RED);
+        return;
+    }
+    constexpr int T = exact_tiles<NQ, WX>(), S = CH_WAVES / T;
+    const int tile = wave % T, ks = wave / T;
+    const QBwdLeanNet net = a.nets[g];
+    const float *const b3p[4] = {a.b3[0], a.b3[1], a.b3[2], a.b3[3]};
+    const float *const ec_src = a.ec_src, *const rew = a.rew, *const done = a.done, *const next_logp = a.next_logp;
+    float *const o_dz2 = a.dz2, *const o_dz1 = a.dz1, *const o_gact = a.gact_part, *const o_q = a.q_out, *const o_gqp = a.gq_out, *const o_tqp = a.target_out;
+    const float gamma = a.gamma, scale = a.scale;
+    const int k0 = (blockIdx.x * T + tile) * 16, m0 = blockIdx.y * 16;
+    const bool col_ok = k0 + r < H1;
+    const int col = min(k0 + r, H1 - 1);
+    float *red = smem + SM_RED, *gs = smem + SM_GS, *panel = smem + SM_PANEL;
+    constexpr int ld = H2 + 4;
+    CH_STAMP(2, 0);
+    // the row group's Q partials first: their operands came with the wave
+    const float *const qp[4] = {qp0, qp1, qp2, qp3};
+    PartBatchN<PB> pq[NEED];
+    if (t < 16) {
+#pragma unroll
+        for (int q = 0; q < NEED; ++q) pq[q].request(qp[q], n_parts, B, m0 + t, (int64_t)n_parts * B);
+    }
+    // the net record and the pointers of this mode in one batch of scalar reads, here
+    asm volatile("" ::"s"(net.w1), "s"(net.w2), "s"(net.w3), "s"(net.h1), "s"(net.h2), "s"(b3p[0]), "s"(o_q), "s"(o_gqp), "s"(scale));
+    if (NEED > 1) asm volatile("" ::"s"(b3p[1]));
+    if (MODE == 1) asm volatile("" ::"s"(b3p[2]), "s"(b3p[3]), "s"(o_dz2), "s"(o_dz1), "s"(o_tqp), "s"(gamma), "s"(rew), "s"(done));
+    if (MODE == 1 && NLOGP) asm volatile("" ::"s"(ec_src), "s"(next_logp));
+    if (GACT) asm volatile("" ::"s"(o_gact));
+    float r_nl = 0.0f, r_rw = 0.0f, r_dn = 0.0f, r_b3[4] = {0.0f, 0.0f, 0.0f, 0.0f}, r_ec = 0.0f;
+    if (t < 16) {
+        const int row = m0 + t;
+#pragma unroll
+        for (int q = 0; q < NEED; ++q) r_b3[q] = ld_uniform(b3p[q]);
+        if (MODE == 1) {
+            if (NLOGP) {
+                r_nl = next_logp[row];
+                r_ec = ld_uniform(ec_src);
+            }
+            r_rw = rew[row];
+            r_dn = done[row];
+        }
+    }
+    // (a) operands that depend on nothing
+    float4 bq[NQ];
+    load_b_bwd<NQ>(bq, net.w2, H2, H1, k0, ks, S);
+    float ty[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ty[e] = net.h1[(int64_t)(m0 + 4 * h + e) * H1 + col];
+    float w1a[A];
+#pragma unroll
+    for (int j = 0; j < A; ++j) w1a[j] = GACT ? net.w1[(int64_t)col * W + D + j] : 0.0f;
+    float y[16];  // H2 == 256: one column per thread
+    const float w3c = net.w3[t];
+#pragma unroll
+    for (int row = 0; row < 16; ++row) y[row] = net.h2[(int64_t)(m0 + row) * H2 + t];
+    // (b) d(loss)/dq of this network for the row group's 16 rows (cstr_head_root_t's expressions)
+    float o_qv = 0.0f, o_gq = 0.0f, o_tq = 0.0f;
+    if (t < 16) {
+        const float kq = scale * 2.0f / (float)B, inv = 1.0f / (float)B;
+        if constexpr (MODE == 1) {
+            const float ec = ALPHA ? expf(r_ec) : r_ec;
+            const float qa = pq[2].sum() + r_b3[2], qb = pq[3].sum() + r_b3[3];
+            o_qv = (g == 0 ? pq[0].sum() + r_b3[0] : pq[1].sum() + r_b3[1]);
+            float q = fminf(qa, qb);
+            if (NLOGP) q = q - ec * r_nl;
+            o_tq = r_rw + (1.0f - r_dn) * gamma * q;
+            o_gq = kq * (o_qv - o_tq);
+        } else if constexpr (MODE == 3) {
+            o_qv = pq[0].sum() + r_b3[0];
+            o_gq = -inv;
+        } else {
+            const float q1 = pq[0].sum() + r_b3[0], q2 = pq[1].sum() + r_b3[1];
+            const bool first = q1 <= q2;
+            o_qv = g == 0 ? q1 : q2;
+            o_gq = (first == (g == 0)) ? -inv : 0.0f;
+        }
+        gs[t] = o_gq;
+    }
+    CH_STAMP(2, 1);
+    lds_barrier();
+    CH_STAMP(2, 2);
+    // (c) dz2 = dq * w3 * relu'(h2) into the panel (values kept for the store at the end)
+    {
+        float gq[16];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 g4 = *reinterpret_cast<const float4 *>(gs + 4 * q);
+            gq[4 * q] = g4.x; gq[4 * q + 1] = g4.y; gq[4 * q + 2] = g4.z; gq[4 * q + 3] = g4.w;
+        }
+#pragma unroll
+        for (int row = 0; row < 16; ++row) {
+            y[row] = y[row] > 0.0f ? gq[row] * w3c : 0.0f;
+            panel[row * ld + t] = y[row];
+        }
+    }
+    lds_barrier();
+    CH_STAMP(2, 3);
+    // (d) dz1 tile, (e) split-K combine, (f) * relu'(h1); partial action gradient
+    f32x4 acc = tile_mma<NQ>(panel, ld, H2, bq, ks, S);
+    CH_STAMP(2, 4);
+    acc = combine_split_k(acc, smem, T, S);
+    CH_STAMP(2, 5);
+    float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (wave < T) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = (col_ok && ty[e] > 0.0f) ? acc[e] : 0.0f;
+        if (GACT) {
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float s = rowsum16(d[e] * w1a[j]);
+                    if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
+                }
+            }
+        }
+    }
+    if (GACT) {
+        lds_barrier();
+        if (t < 16 * A) {
+            const int row = t / A, j = t % A;
+            float s = red[row * 8 + j];
+#pragma unroll
+            for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + row) * 8 + j];
+            o_gact[(((int64_t)g * gridDim.x + blockIdx.x) * B + m0 + row) * A + j] = s;
+        }
+    }
+    CH_STAMP(2, 6);
+    // ---- global stores, all behind the last barrier ----
+    if (!GACT) {
+        if (wave < T && col_ok) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o_dz1[((int64_t)g * B + m0 + 4 * h + e) * H1 + k0 + r] = d[e];
+        }
+        const int cpg = (H2 + gridDim.x - 1) / gridDim.x;  // each workgroup of the row group stores its share of the columns
+        if (t / cpg == (int)blockIdx.x) {
+#pragma unroll
+            for (int row = 0; row < 16; ++row) o_dz2[((int64_t)g * B + m0 + row) * H2 + t] = y[row];
+        }
+    }
+    if (t < 16 && blockIdx.x == 0) {
+        const int row = m0 + t;
+        if (o_q) o_q[(int64_t)g * B + row] = o_qv;
+        if (o_gqp) o_gqp[(int64_t)g * B + row] = o_gq;
+        if (MODE == 1 && g == 0 && o_tqp) o_tqp[row] = o_tq;
+    }
+    CH_STAMP(2, 7);
+}
+
 // ---- SAC actor, backward chain -------------------------------------------------------------------------------------------------
 struct ActorBwdArgs {
     cstr_sac_actor_t net;
@@ -1100,6 +1531,123 @@ static int chain_wx(int h1, int h2, int tiles, int nq)
 
 constexpr size_t CHAIN_LDS_LIMIT = 64 * 1024;
 
+// ---- the lean Q launches' dispatch: false = not covered, the caller launches the generic kernel ------------------------------------
+int chain_lean_enabled = 1;  // cstr_chain_lean
+
+struct QFwdLeanScalars { int batch, parts; const float *head_part, *hb, *eps; int part_rows, next_offset; float sigma, clip; unsigned long long roles; };
+
+template <int D, int A, int NQ, int FIN, int PB>
+void q_fwd_lean_go(const dim3 grid, const size_t lds, hipStream_t s, const QFwdLeanScalars &c, const QFwdLeanArgs &a)
+{
+    q_chain_fwd_lean_kernel<D, A, NQ, FIN, PB><<<grid, CH_THREADS, lds, s>>>(c.batch, c.parts, c.head_part, c.hb, c.eps, c.part_rows, c.next_offset, c.sigma,
+                                                                             c.clip, c.roles, a);
+}
+template <int D, int A, int NQ>
+void q_fwd_lean_variant(const int finv, const int pb, const dim3 grid, const size_t lds, hipStream_t s, const QFwdLeanScalars &c, const QFwdLeanArgs &a)
+{
+    if (finv == QF_PLAIN) q_fwd_lean_go<D, A, NQ, QF_PLAIN, 8>(grid, lds, s, c, a);
+    else if (finv == QF_GAUSSIAN && pb == 8) q_fwd_lean_go<D, A, NQ, QF_GAUSSIAN, 8>(grid, lds, s, c, a);
+    else if (finv == QF_GAUSSIAN) q_fwd_lean_go<D, A, NQ, QF_GAUSSIAN, 16>(grid, lds, s, c, a);
+    else if (pb == 8) q_fwd_lean_go<D, A, NQ, QF_DETERMINISTIC, 8>(grid, lds, s, c, a);
+    else q_fwd_lean_go<D, A, NQ, QF_DETERMINISTIC, 16>(grid, lds, s, c, a);
+}
+template <int D, int A, typename... Rest>
+void q_fwd_lean_nq(const int nq, Rest &&...rest)
+{
+    if (nq == 4) q_fwd_lean_variant<D, A, 4>(rest...);
+    else if (nq == 8) q_fwd_lean_variant<D, A, 8>(rest...);
+    else q_fwd_lean_variant<D, A, 16>(rest...);
+}
+
+// the variants of the backward launch that a learner dispatches: TD root with the entropy coefficient's own loss (SAC, ent_coef
+// "auto"), with a fixed coefficient (SAC), without log-probs (TD3, MADDPG, BCQ); SAC's and the deterministic actors' loss roots
+enum { QB_TD_ALPHA = 0, QB_TD_LOGP = 1, QB_TD_PLAIN = 2, QB_ACTOR_SAC = 3, QB_ACTOR_NEG_MEAN = 4 };
+struct QBwdLeanScalars { int batch, parts; const float *qp[4]; };
+
+template <int D, int A, int NQ, int MODE, bool ALPHA, bool NLOGP, int LB>
+void q_bwd_lean_go(const dim3 grid, const size_t lds, hipStream_t s, const QBwdLeanScalars &c, const QBwdLeanArgs &a)
+{
+    q_chain_bwd_lean_kernel<D, A, NQ, MODE, ALPHA, NLOGP, LB><<<grid, CH_THREADS, lds, s>>>(c.batch, c.parts, c.qp[0], c.qp[1], c.qp[2], c.qp[3], a);
+}
+template <int D, int A, int NQ, int LB>
+void q_bwd_lean_variant(const int variant, const dim3 grid, const size_t lds, hipStream_t s, const QBwdLeanScalars &c, const QBwdLeanArgs &a)
+{
+    if (variant == QB_TD_ALPHA) q_bwd_lean_go<D, A, NQ, 1, true, true, LB>(grid, lds, s, c, a);
+    else if (variant == QB_TD_LOGP) q_bwd_lean_go<D, A, NQ, 1, false, true, LB>(grid, lds, s, c, a);
+    else if (variant == QB_TD_PLAIN) q_bwd_lean_go<D, A, NQ, 1, false, false, LB>(grid, lds, s, c, a);
+    else if (variant == QB_ACTOR_SAC) q_bwd_lean_go<D, A, NQ, 2, false, false, LB>(grid, lds, s, c, a);
+    else q_bwd_lean_go<D, A, NQ, 3, false, false, LB>(grid, lds, s, c, a);
+}
+template <int D, int A, int NQ, typename... Rest>
+void q_bwd_lean_lb(const int lb, Rest &&...rest)
+{
+    if (lb == 4) q_bwd_lean_variant<D, A, NQ, 4>(rest...);
+    else if (lb == 8) q_bwd_lean_variant<D, A, NQ, 8>(rest...);
+    else q_bwd_lean_variant<D, A, NQ, 16>(rest...);
+}
+template <int D, int A, typename... Rest>
+void q_bwd_lean_nq(const int nq, Rest &&...rest)
+{
+    if (nq == 4) q_bwd_lean_lb<D, A, 4>(rest...);
+    else if (nq == 8) q_bwd_lean_lb<D, A, 8>(rest...);
+    else q_bwd_lean_lb<D, A, 16>(rest...);
+}
+
+bool q_fwd_lean_launch(const QFwdArgs &g, const int lay, const int wx, const int nq, const dim3 grid, const size_t lds, hipStream_t s)
+{
+    if (!chain_lean_enabled || wx != 1 || (lay != 0 && lay != 1)) return false;
+    if (g.has_fin && g.fin.n_parts > MAX_PARTS) return false;
+    QFwdLeanArgs a = {};
+    QFwdLeanScalars c = {};
+    c.batch = g.batch;
+    for (int i = 0; i < g.n_nets; ++i) {
+        a.nets[i] = g.nets[i];
+        c.roles |= (unsigned long long)(g.nets[i].role & 15) << (4 * i);
+    }
+    int finv = QF_PLAIN, pb = 8;
+    if (g.has_fin) {
+        const cstr_sac_head_fin_t &f = g.fin;
+        finv = f.kind == CSTR_CHAIN_HEAD_DETERMINISTIC ? QF_DETERMINISTIC : QF_GAUSSIAN;
+        pb = part_bucket_row(f.n_parts);
+        c.parts = f.n_parts; c.head_part = f.head_part; c.hb = f.hb; c.eps = f.eps; c.part_rows = f.part_rows; c.next_offset = f.next_offset;
+        c.sigma = f.sigma; c.clip = f.clip;
+        a.x_pi = f.x_pi; a.x_next = f.x_next; a.params = f.params; a.logp_pi = f.logp_pi; a.logp_next = f.logp_next;
+    }
+    if (lay == 0) q_fwd_lean_nq<4, 2>(nq, finv, pb, grid, lds, s, c, a);
+    else q_fwd_lean_nq<8, 2>(nq, finv, pb, grid, lds, s, c, a);
+    return true;
+}
+
+bool q_bwd_lean_launch(const QBwdArgs &g, const int lay, const int wx, const int nq, const dim3 grid, const size_t lds, hipStream_t s)
+{
+    const cstr_chain_root_t &rt = g.root;
+    if (!chain_lean_enabled || wx != 1 || (lay != 0 && lay != 1) || rt.n_parts > MAX_PARTS) return false;
+    const bool stores_dz = g.dz1 && g.dz2 && !g.gact_part, stores_gact = g.gact_part && !g.dz1 && !g.dz2;
+    const bool alpha = rt.alpha.log_alpha != nullptr, nlogp = rt.next_logp != nullptr;
+    int variant;
+    if (rt.mode == 1) {
+        if (!stores_dz || (alpha && !nlogp) || (!alpha && nlogp && !rt.ent_coef)) return false;
+        variant = alpha ? QB_TD_ALPHA : nlogp ? QB_TD_LOGP : QB_TD_PLAIN;
+    } else {
+        if (!stores_gact) return false;
+        variant = rt.mode == 2 ? QB_ACTOR_SAC : QB_ACTOR_NEG_MEAN;
+    }
+    QBwdLeanArgs a = {};
+    QBwdLeanScalars c = {};
+    for (int i = 0; i < g.n_nets; ++i) a.nets[i] = QBwdLeanNet{g.nets[i].w1, g.nets[i].w2, g.nets[i].w3, g.nets[i].h1, g.nets[i].h2};
+    for (int q = 0; q < 4; ++q) { a.b3[q] = rt.b3[q]; c.qp[q] = rt.q_part[q]; }
+    a.ec_src = alpha ? rt.alpha.log_alpha : rt.ent_coef;
+    a.dz2 = g.dz2; a.dz1 = g.dz1; a.gact_part = g.gact_part; a.q_out = rt.q_out; a.gq_out = rt.gq_out; a.target_out = rt.target_out;
+    a.gamma = rt.gamma; a.scale = rt.scale;
+    a.root = rt;
+    a.rew = rt.rew; a.done = rt.done; a.next_logp = rt.next_logp;
+    c.batch = rt.batch; c.parts = rt.n_parts;
+    const int lb = part_bucket_loss(rt.n_parts);
+    if (lay == 0) q_bwd_lean_nq<4, 2>(nq, lb, variant, grid, lds, s, c, a);
+    else q_bwd_lean_nq<8, 2>(nq, lb, variant, grid, lds, s, c, a);
+    return true;
+}
+
 }  // namespace
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------
@@ -1189,7 +1737,8 @@ extern "C" int cstr_q_chain_fwd_f32(const cstr_chain_net_t *nets, int n_nets, in
     const int nq = nq_for(h1, tiles, 32), lay = chain_layout(obs_dim, w_in - obs_dim);
     if (!nq || lay < 0 || lds > CHAIN_LDS_LIMIT) return CSTR_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    CHAIN_DISPATCH(q_chain_fwd_kernel, lay, chain_wx(h1, h2, tiles, nq), nq, grid, lds, s, a);
+    const int wx = chain_wx(h1, h2, tiles, nq);
+    if (!q_fwd_lean_launch(a, lay, wx, nq, grid, lds, s)) CHAIN_DISPATCH(q_chain_fwd_kernel, lay, wx, nq, grid, lds, s, a);
     return (int)hipGetLastError();
 }
 
@@ -1220,8 +1769,16 @@ extern "C" int cstr_q_chain_bwd_f32(const cstr_chain_net_t *nets, int n_nets, co
     const int nq = nq_for(h2, tiles), lay = chain_layout(obs_dim, w_in - obs_dim);
     if (!nq || lay < 0 || lds > CHAIN_LDS_LIMIT) return CSTR_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    CHAIN_DISPATCH(q_chain_bwd_kernel, lay, chain_wx(h1, h2, tiles, nq), nq, grid, lds, s, a);
+    const int wx = chain_wx(h1, h2, tiles, nq);
+    if (!q_bwd_lean_launch(a, lay, wx, nq, grid, lds, s)) CHAIN_DISPATCH(q_chain_bwd_kernel, lay, wx, nq, grid, lds, s, a);
     return (int)hipGetLastError();
+}
+
+extern "C" int cstr_chain_lean(int on)
+{
+    const int was = chain_lean_enabled;
+    if (on >= 0) chain_lean_enabled = on != 0;
+    return was;
 }
 
 extern "C" int cstr_chain_sum_parts_f32(const float *part, int n_parts, int64_t rows, int cols, float *out, int64_t out_stride, cstr_stream_t stream)
