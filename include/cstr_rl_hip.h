@@ -997,6 +997,58 @@ int cstr_categorical_act_f32(const float *logits, int64_t ldz, int64_t n, int n_
                              float *valve_out, float *log_prob, float *u_out, cstr_stream_t stream);
 int cstr_categorical_loss_f32(const cstr_categorical_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
 
+/* ---- MultiCategorical head of PPO / A2C on the MultiDiscrete valve face (core/common/distributions.py:314-368, core/ppo/ppo.py:213-264,
+ * core/a2c/a2c.py:150-171) ---------------------------------------------------------------------------------------------------------
+ * Same conventions as the Categorical block: f32 data, host-side validation (NULL, non-positive sizes, ldz < levels0 + levels1,
+ * misaligned or overlapping rows -> CSTR_E_BADARG), then only enqueues; deterministic batch reductions; the workspace is a
+ * uint64[CSTR_PPO_WS_WORDS] as above. The face: one categorical per valve, 2 <= levels_g <= CSTR_MCAT_MAX_LEVELS (anything else, or
+ * more than CSTR_PPO_MAX_ROWS rows: CSTR_E_UNSUPPORTED). logits [rows][ldz], ldz >= levels0 + levels1, rows 4-byte aligned: columns
+ * 0 .. levels0 - 1 are valve 0's, levels0 .. levels0 + levels1 - 1 valve 1's (th.split order). Level q of valve g stands for the
+ * normalised valve action v_g(q) = f32(-1) + f32(2 q) / f32(levels_g - 1). Rows of pairs ([.][2]) are 8-byte aligned.
+ * Per valve g: logp_j = (z_j - m_g) - log sum_j exp(z_j - m_g), p_j = exp(logp_j), H_g = -sum_j p_j max(logp_j, -FLT_MAX).
+ * Per row: logp = logp_0[a_0] + logp_1[a_1], H = H_0 + H_1 (f32).
+ * cstr_multicategorical_act_f32 (one launch): the pair (a_0, a_1) comes from exactly one source (two at once, or none: CSTR_E_BADARG):
+ *   deterministic != 0: the first maximum of each valve's logits (a NaN counts as the greatest value, the first one wins);
+ *   action_in int64[n][2]: teacher-forced pairs; levels outside the face are the caller's bug and are clamped per valve;
+ *   u_in [n][2]: given uniforms in [0, 1);
+ *   rng_ctl [CSTR_RNG_CTL_WORDS]: the uniforms are drawn, Philox4x32-10 on the head's own stream, counter (offset + row, 0, tag), words
+ *     0 and 1 of the one block as (word >> 8) * 2^-24 for valves 0 and 1; the last workgroup advances the offset by n.
+ * With uniforms, a_g is the first level of valve g whose inclusive cumulative probability (f32, index order) exceeds u_g, levels_g - 1
+ * if none does. Outputs: action_f32 [n][2] = the pair as floats (what the rollout buffer stores); optional action_out int64[n][2],
+ * valve_out [n][2] = (v_0(a_0), v_1(a_1)), log_prob [n], u_out [n][2] = the uniforms (only with u_in or rng_ctl).
+ * cstr_multicategorical_loss_f32 (one launch): cstr_categorical_loss_f32's objectives, scalars and order on the row's logp and H; the
+ * stored pair is (long)actions[b][g], clamped per valve. For a column j of valve g:
+ *   g_logits[b][j] = g_logp_b * ((j == a_g) - p_j) + (ent_coef / batch) * p_j * (logp_j + H_g)      (the valve's own H_g);
+ * columns levels0 + levels1 .. ldz of g_logits are not written. g_value, scalars_out, scalars_sum, log_prob_out, the value clip, the
+ * advantage normalisation and the NaN behaviour are the Categorical loss's. */
+#define CSTR_MCAT_MAX_LEVELS 32
+typedef struct {
+    const float *logits;       /* [batch][ldz], levels0 + levels1 columns used */
+    int64_t ldz;
+    const float *actions;      /* [batch][2]: the stored level pair as floats */
+    const float *values;       /* [batch]: the value net's output */
+    const float *old_values;   /* [batch]; may be NULL when clip_range_vf <= 0 or objective 1 */
+    const float *old_log_prob; /* [batch]; may be NULL for objective 1 */
+    const float *adv;          /* [batch] */
+    const float *returns;      /* [batch] */
+    int64_t batch;
+    int32_t levels0, levels1;
+    int32_t objective;           /* 0: PPO, 1: A2C */
+    int32_t normalize_advantage; /* != 0: (adv - mean) / (unbiased std + 1e-8); PPO skips it when batch == 1 */
+    double clip_range;           /* PPO */
+    double clip_range_vf;        /* PPO; <= 0: no value clipping */
+    float ent_coef, vf_coef;
+    float *g_logits;             /* [batch][ldz] */
+    float *g_value;              /* [batch] */
+    float *scalars_out;          /* [6] (PPO) / [4] (A2C) or NULL */
+    float *scalars_sum;          /* same size or NULL: += */
+    float *log_prob_out;         /* [batch] or NULL: the pair's log-prob */
+} cstr_multicategorical_loss_t;
+int cstr_multicategorical_act_f32(const float *logits, int64_t ldz, int64_t n, int levels0, int levels1, int deterministic,
+                                  const int64_t *action_in, const float *u_in, uint64_t *rng_ctl, float *action_f32, int64_t *action_out,
+                                  float *valve_out, float *log_prob, float *u_out, cstr_stream_t stream);
+int cstr_multicategorical_loss_f32(const cstr_multicategorical_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
+
 /* ---- Hindsight Experience Replay on the goal-conditioned face of the env (core/her/her_replay_buffer.py) ---------------------------
  * The goal face (constructed here; the reference's env has none): achieved_goal = observation[2] (normalised C2), desired_goal = the
  * env's own target through the same affine map, g = 2 (target - s_lo[2]) / s_span[2] - 1. A flat row is six floats in key order,

@@ -21,6 +21,7 @@ SDE_MAX_LATENT, SDE_MAX_MATS = 4096, 65537
 BCQ_MAX_LATENT, BCQ_MAX_ACT, BCQ_MAX_SAMPLES, BCQ_MAX_ROWS = 256, 64, 4096, 1 << 24
 ROLLOUT_CTL_WORDS, PPO_WS_WORDS, PPO_MAX_BLOCKS, PPO_MAX_ROWS = 4, 1024, 64, 1 << 30
 DQN_MAX_LEVELS = 16
+MCAT_MAX_LEVELS = 32
 HER_STRATEGIES = {"future": 0, "final": 1, "episode": 2}
 HER_MAX_BATCH, HER_MAX_ROWS, HER_MAX_ENVS, HER_GOAL_TAG = 1024, 8192, 1 << 24, 0x90A17A67
 
@@ -41,6 +42,7 @@ SYMBOLS = (
     "cstr_mt19937_rand_flag_f64", "cstr_dqn_act_f32", "cstr_dqn_loss_f32",
     "cstr_eval_episodes_f32",
     "cstr_categorical_act_f32", "cstr_categorical_loss_f32",
+    "cstr_multicategorical_act_f32", "cstr_multicategorical_loss_f32",
     "cstr_goal_vec_step_f32", "cstr_her_add_f32", "cstr_her_sample_f32",
 )
 
@@ -184,6 +186,15 @@ class CategoricalLoss(C.Structure):
     _fields_ = [("logits", C.c_void_p), ("ldz", C.c_int64)] + [(n, C.c_void_p) for n in (
         "actions", "values", "old_values", "old_log_prob", "adv", "returns")] + [
         ("batch", C.c_int64), ("n_actions", C.c_int32), ("levels", C.c_int32), ("objective", C.c_int32), ("normalize_advantage", C.c_int32),
+        ("clip_range", C.c_double), ("clip_range_vf", C.c_double), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [(n, C.c_void_p) for n in (
+            "g_logits", "g_value", "scalars_out", "scalars_sum", "log_prob_out")]
+
+
+class MultiCategoricalLoss(C.Structure):
+    """cstr_multicategorical_loss_t"""
+    _fields_ = [("logits", C.c_void_p), ("ldz", C.c_int64)] + [(n, C.c_void_p) for n in (
+        "actions", "values", "old_values", "old_log_prob", "adv", "returns")] + [
+        ("batch", C.c_int64), ("levels0", C.c_int32), ("levels1", C.c_int32), ("objective", C.c_int32), ("normalize_advantage", C.c_int32),
         ("clip_range", C.c_double), ("clip_range_vf", C.c_double), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [(n, C.c_void_p) for n in (
             "g_logits", "g_value", "scalars_out", "scalars_sum", "log_prob_out")]
 

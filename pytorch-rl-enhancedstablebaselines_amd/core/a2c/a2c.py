@@ -14,10 +14,11 @@ NumPy's stream: the reference draws one `permutation(T * N)` per train() from th
 draws from that global stream (a VecEnv that is not device-resident) the in-place path still consumes the draw, so the stream's
 position matches the reference's; with the algorithm's own `RandomState` (a device env) nothing else reads it and the draw is skipped.
 
-On a Discrete valve face the policy has a Categorical head and the loss launch is hip_ops.categorical_loss (csrc/cstr_categorical.hip).
+On a Discrete valve face the policy has a Categorical head and the loss launch is hip_ops.categorical_loss (csrc/cstr_categorical.hip);
+on a MultiDiscrete one (`CSTRVecEnv(multi_discrete_actions=(K0, K1))`) a MultiCategorical head, one categorical per valve, and the loss
+launch is hip_ops.multicategorical_loss (csrc/cstr_multicategorical.hip).
 
-Not built: RMSpropTFLike, gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiDiscrete / MultiBinary actions, CNN / dict
-policies."""
+Not built: RMSpropTFLike, gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN / dict policies."""
 from typing import Optional, Union
 
 import numpy as np
@@ -30,7 +31,7 @@ from core.common.arena import FlatRMSprop
 from core.common.buffers import RolloutBuffer
 from core.common.logger import DeviceMean
 from core.common.on_policy_algorithm import OnPolicyAlgorithm
-from core.common.spaces import Discrete
+from core.common.spaces import Discrete, MultiDiscrete
 
 
 class A2C(OnPolicyAlgorithm):
@@ -48,7 +49,7 @@ class A2C(OnPolicyAlgorithm):
                          vf_coef=vf_coef, max_grad_norm=max_grad_norm, use_sde=use_sde, sde_sample_freq=sde_sample_freq,
                          rollout_buffer_class=rollout_buffer_class, rollout_buffer_kwargs=rollout_buffer_kwargs,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs,
-                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box", Discrete))
+                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box", Discrete, MultiDiscrete))
         self.normalize_advantage = normalize_advantage
         self.rms_prop_eps, self.use_rms_prop = rms_prop_eps, use_rms_prop
         self._rewrite_policy_kwargs(self.policy_kwargs, use_rms_prop, rms_prop_eps)
@@ -105,12 +106,16 @@ class A2C(OnPolicyAlgorithm):
         """evaluate_actions on the per-layer kernels, the loss launch, loss.backward() from its gradients, clip_grad_norm_ and the step"""
         fast, pol = self._fast, self.policy
         b = self._bufs(obs.shape[0])
-        mean = fast.logits(obs, train_params=True) if fast.discrete else fast.mean(obs, train_params=True)
+        mean = fast.logits(obs, train_params=True) if (fast.discrete or fast.multi_discrete) else fast.mean(obs, train_params=True)
         values = fast.values(obs, train_params=True)
         if fast.discrete:  # the Categorical head: g_mean holds d loss / d logits, there is no log_std
             hip_ops.categorical_loss(hip_ops.CAT_A2C, mean.detach(), fast.levels, actions, values.detach(), advantages, returns,
                                      self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
                                      scalars_out=self._scalars, log_prob_out=b["log_prob"] if self.debug_capture else None)
+        elif fast.multi_discrete:  # the MultiCategorical head: one categorical per valve
+            hip_ops.multicategorical_loss(hip_ops.CAT_A2C, mean.detach(), fast.nvec, actions, values.detach(), advantages, returns,
+                                          self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
+                                          scalars_out=self._scalars, log_prob_out=b["log_prob"] if self.debug_capture else None)
         else:
             hip_ops.a2c_loss(mean.detach(), pol.log_std.detach(), actions, values.detach(), advantages, returns, self.normalize_advantage,
                              self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], pol.log_std.grad, self._ws, scalars_out=self._scalars,

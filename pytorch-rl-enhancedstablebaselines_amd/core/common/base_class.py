@@ -11,7 +11,7 @@ import torch as th
 from core.common import distributed as dist_util
 from core.common.callbacks import BaseCallback, MaybeCallback, to_callback
 from core.common.logger import Logger, configure_logger
-from core.common.spaces import Box, Discrete, as_box, as_discrete
+from core.common.spaces import Box, Discrete, MultiDiscrete, as_box, as_discrete, as_multi_discrete
 from core.common.utils import get_device, get_schedule_fn, set_random_seed, update_learning_rate
 from core.common.vec_env import CSTRVecEnv, VecEnv, unwrap_vec_normalize
 
@@ -91,7 +91,12 @@ class BaseAlgorithm:
             # names "Box" and Discrete (PPO, A2C) takes either; every other class takes a Box
             wants_discrete = supported_action_spaces is not None and Discrete in supported_action_spaces
             wants_box = not wants_discrete or "Box" in supported_action_spaces
-            if not (wants_discrete if isinstance(self.action_space, Discrete) else wants_box):
+            if isinstance(self.action_space, MultiDiscrete):  # PPO and A2C name it; nobody else takes the factored face
+                admitted = supported_action_spaces is not None and MultiDiscrete in supported_action_spaces
+                supported_action_spaces = supported_action_spaces or ("Box",)
+            else:
+                admitted = wants_discrete if isinstance(self.action_space, Discrete) else wants_box
+            if not admitted:
                 raise AssertionError(f"The algorithm only supports {supported_action_spaces} as action spaces "
                                      f"but {self.action_space} was provided")
             if not support_multi_env and self.n_envs > 1:
@@ -104,6 +109,8 @@ class BaseAlgorithm:
     @staticmethod
     def _as_action_space(space):
         d = as_discrete(space)
+        if d is None:
+            d = as_multi_discrete(space)
         return d if d is not None else as_box(space)
 
     @staticmethod
@@ -334,6 +341,9 @@ class BaseAlgorithm:
         for nm, sp in (("observation_space", self.observation_space), ("action_space", self.action_space)):
             if isinstance(sp, Discrete):
                 data[nm] = {"n": sp.n, "start": sp.start, "shape": [], "dtype": str(sp.dtype)}
+                continue
+            if isinstance(sp, MultiDiscrete):
+                data[nm] = {"nvec": sp.nvec.tolist(), "shape": list(sp.shape), "dtype": str(sp.dtype)}
                 continue
             data[nm] = {"low": np.asarray(sp.low).tolist(), "high": np.asarray(sp.high).tolist(), "shape": list(sp.shape), "dtype": str(sp.dtype)}
         if self.goal_space is not None:  # the Dict space of the goal face, key by key; HER's own arguments (plain JSON, nothing pickled)

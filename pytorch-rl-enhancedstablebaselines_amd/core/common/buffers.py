@@ -18,7 +18,7 @@ import numpy as np
 import torch as th
 
 from core.common import hip_ops, legacy_rng
-from core.common.spaces import as_box, as_discrete, get_action_dim, get_obs_shape
+from core.common.spaces import as_box, as_discrete, as_multi_discrete, get_action_dim, get_obs_shape
 from core.common.type_aliases import ReplayBufferSamples, RolloutBufferSamples
 from core.common.utils import get_device
 
@@ -30,7 +30,8 @@ class BaseBuffer:
                  n_envs: int = 1):
         self.buffer_size = buffer_size
         self.observation_space = as_box(observation_space)
-        self.action_space = as_discrete(action_space) or as_box(action_space)  # Discrete: the on-policy buffers' [T, N, 1] index
+        # Discrete: the on-policy buffers' [T, N, 1] index; MultiDiscrete: their [T, N, len(nvec)] levels
+        self.action_space = as_discrete(action_space) or as_multi_discrete(action_space) or as_box(action_space)
         self.obs_shape = get_obs_shape(self.observation_space)
         self.action_dim = get_action_dim(self.action_space)
         self.device = get_device(device)

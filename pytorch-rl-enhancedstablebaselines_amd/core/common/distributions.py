@@ -253,6 +253,52 @@ class CategoricalDistribution:
         return actions, self.log_prob(actions)
 
 
+class MultiCategoricalDistribution:
+    """reference: core/common/distributions.py:314-368 -- one torch Categorical per component of a MultiDiscrete action space, over
+    the th.split of the flat logits (torch statements: the API and the torch-statement path; the kernel path evaluates the same
+    expressions in csrc/cstr_multicategorical.hip). Log-probs and entropies are summed over the components.
+    `action_queue`: teacher-forcing hook, each `sample()` pops its [n, len(action_dims)] levels from here first (tests)."""
+
+    def __init__(self, action_dims):
+        self.action_dims = [int(k) for k in action_dims]
+        self.distribution = None
+        self.action_queue: list = []
+
+    def proba_distribution_net(self, latent_dim: int) -> nn.Module:
+        return nn.Linear(latent_dim, sum(self.action_dims))
+
+    def proba_distribution(self, action_logits: th.Tensor) -> "MultiCategoricalDistribution":
+        self.distribution = [th.distributions.Categorical(logits=z) for z in th.split(action_logits, self.action_dims, dim=1)]
+        return self
+
+    def log_prob(self, actions: th.Tensor) -> th.Tensor:
+        per_valve = [d.log_prob(a) for d, a in zip(self.distribution, th.unbind(actions, dim=1))]
+        return th.stack(per_valve, dim=1).sum(dim=1)
+
+    def entropy(self) -> th.Tensor:
+        return th.stack([d.entropy() for d in self.distribution], dim=1).sum(dim=1)
+
+    def sample(self) -> th.Tensor:
+        if self.action_queue:
+            z = self.distribution[0].logits
+            return self.action_queue.pop(0).to(z.device, th.int64).reshape(z.shape[0], len(self.action_dims))
+        return th.stack([d.sample() for d in self.distribution], dim=1)
+
+    def mode(self) -> th.Tensor:
+        return th.stack([th.argmax(d.probs, dim=1) for d in self.distribution], dim=1)
+
+    def get_actions(self, deterministic: bool = False) -> th.Tensor:
+        return self.mode() if deterministic else self.sample()
+
+    def actions_from_params(self, action_logits: th.Tensor, deterministic: bool = False) -> th.Tensor:
+        self.proba_distribution(action_logits)
+        return self.get_actions(deterministic=deterministic)
+
+    def log_prob_from_params(self, action_logits: th.Tensor):
+        actions = self.actions_from_params(action_logits)
+        return actions, self.log_prob(actions)
+
+
 class DiagGaussianDistribution:
     """reference: core/common/distributions.py:125-204 -- the unsquashed diagonal Gaussian of the on-policy algorithms (torch
     statements: the API and the torch-statement path; the kernel path evaluates the same expressions in csrc/cstr_ppo.hip).

@@ -192,6 +192,8 @@ def _why_not_fused(model, env, deterministic: bool) -> Optional[str]:
         return "the evaluation env must be a bare CSTRVecEnv (no VecNormalize or other wrapper)"
     if env.discrete_actions is not None:
         return "the Discrete valve face (DQN)"
+    if getattr(env, "multi_discrete_actions", None) is not None:
+        return "the MultiDiscrete valve face (one categorical per valve: the launch has no MultiCategorical head)"
     policy = getattr(model, "policy", model)
     if not isinstance(policy, nn.Module) or not hasattr(policy, "squash_output") or not hasattr(getattr(policy, "action_space", None), "low"):
         return f"{type(policy).__name__} is not a single-agent policy over a Box action space"

@@ -1453,7 +1453,10 @@ class FastActorCritic:
     (hip_ops.diag_gaussian_act). Noise: `eps_queue` (teacher-forced [n, A] draws, tests) first, the Philox stream `rng_ctl` otherwise.
     The categorical form (a Discrete valve face of 2 to 16 levels per valve): `logits()` replaces `mean()`, the head is
     hip_ops.categorical_act, `act()` returns the index as a float [n, 1] and the valve pair the env steps with; `action_queue`
-    (teacher-forced int64 [n] indices, tests) first, the Philox stream otherwise."""
+    (teacher-forced int64 [n] indices, tests) first, the Philox stream otherwise.
+    The multi-categorical form (a MultiDiscrete valve face, 2 to 32 levels per valve; chosen from the policy's SPACE, never from the
+    width of `action_net`: MultiDiscrete([2, 2]) and Discrete(4) both have four logits): the head is hip_ops.multicategorical_act,
+    `act()` returns the level pair as floats [n, 2] and the valve pair; `action_queue` holds int64 [n, 2] pairs."""
 
     def __init__(self, policy, rng_ctl: Optional[th.Tensor] = None):
         self.policy = policy
@@ -1461,10 +1464,14 @@ class FastActorCritic:
         self.vf_layers = FastMLP(policy.mlp_extractor.value_net).layers + [(policy.value_net, ACT_NONE)]
         self.discrete = bool(getattr(policy, "discrete", False))
         dev = policy.action_net.weight.device
+        self.multi_discrete = bool(getattr(policy, "multi_discrete", False))
         if self.discrete:
             self.n_actions = policy.action_net.out_features
             self.levels = self.face_levels(self.n_actions)
             self.act_dim = 1  # the buffer's action row: the index as one float
+        elif self.multi_discrete:
+            self.nvec = tuple(int(k) for k in policy.action_space.nvec)
+            self.act_dim = len(self.nvec)  # the buffer's action row: the level pair as floats
         else:
             self.act_dim = policy.action_net.out_features
             self.low = th.as_tensor(policy.action_space.low, dtype=th.float32).reshape(-1).to(dev).contiguous()
@@ -1486,6 +1493,8 @@ class FastActorCritic:
         n_out = policy.action_net.out_features
         if getattr(policy, "discrete", False):
             head = hip_ops.categorical_supported(policy.features_dim, n_out, FastActorCritic.face_levels(n_out))
+        elif getattr(policy, "multi_discrete", False):
+            head = hip_ops.multicategorical_supported(policy.features_dim, tuple(int(k) for k in policy.action_space.nvec))
         else:
             head = hip_ops.ppo_supported(policy.features_dim, n_out)
         return (FastMLP.supported(ext.policy_net) and FastMLP.supported(ext.value_net) and head
@@ -1504,7 +1513,7 @@ class FastActorCritic:
         return self._run(self.pi_layers, obs, train_params)
 
     def logits(self, obs: th.Tensor, train_params: bool = False) -> th.Tensor:
-        """the categorical form's action logits [n, levels^2]"""
+        """the categorical form's action logits [n, levels^2]; the multi-categorical form's [n, K0 + K1] in th.split order"""
         return self._run(self.pi_layers, obs, train_params)
 
     def values(self, obs: th.Tensor, train_params: bool = False) -> th.Tensor:
@@ -1533,12 +1542,29 @@ class FastActorCritic:
                                 valve_out=b["env_action"], log_prob=b["log_prob"])
         return b["action"], values, b["log_prob"], b["env_action"]
 
+    def _act_multicategorical(self, obs: th.Tensor, deterministic: bool, want_value: bool):
+        n = obs.shape[0]
+        b = self.bufs(n, obs.device)
+        logits = self.logits(obs)
+        values = self.values(obs) if want_value else None
+        forced = None
+        if not deterministic and self.action_queue:
+            forced = self.action_queue.pop(0).to(obs.device, th.int64).reshape(n, 2).contiguous()
+        rng = None if (deterministic or forced is not None) else self.rng_ctl
+        if not deterministic and forced is None and rng is None:
+            raise RuntimeError("FastActorCritic.act: no action source (neither a queued pair nor a Philox stream)")
+        hip_ops.multicategorical_act(logits, self.nvec, b["action"], deterministic=deterministic, action_in=forced, rng_ctl=rng,
+                                     valve_out=b["env_action"], log_prob=b["log_prob"])
+        return b["action"], values, b["log_prob"], b["env_action"]
+
     def act(self, obs: th.Tensor, deterministic: bool = False, want_value: bool = True):
         """ActorCriticPolicy.forward without gradients -> (actions [n, A] unclipped, values [n, 1] or None, log_prob [n], env_action =
         clip(actions, low, high)). The outputs are static per row count: valid until the next call with as many rows."""
         with th.no_grad():
             if self.discrete:  # -> (index as a float [n, 1], values, log_prob, the valve pair [n, 2])
                 return self._act_categorical(obs, deterministic, want_value)
+            if self.multi_discrete:  # -> (level pair as floats [n, 2], values, log_prob, the valve pair [n, 2])
+                return self._act_multicategorical(obs, deterministic, want_value)
             n = obs.shape[0]
             b = self.bufs(n, obs.device)
             mean = self.mean(obs)

@@ -1713,6 +1713,68 @@ def categorical_loss(objective: int, logits, levels: int, actions, values, adv, 
     check(nv.lib().cstr_categorical_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_categorical_loss_f32")
 
 
+# ---- MultiCategorical head of PPO / A2C on the MultiDiscrete valve face (csrc/cstr_multicategorical.hip) ---------------------------
+def multicategorical_supported(obs_dim: int, nvec) -> bool:
+    """two valves, 2 .. MCAT_MAX_LEVELS levels each"""
+    return obs_dim in (4, 8) and len(nvec) == 2 and all(2 <= int(k) <= nv.MCAT_MAX_LEVELS for k in nvec)
+
+
+def _levels_pair(nvec, m: int):
+    if len(nvec) != 2 or int(nvec[0]) + int(nvec[1]) != m:
+        raise ValueError(f"logits: {m} columns do not fit the level counts {tuple(nvec)} (two valves, K0 + K1 columns)")
+    return int(nvec[0]), int(nvec[1])
+
+
+def multicategorical_act(logits, nvec, action_f32, deterministic: bool = False, action_in=None, u=None, rng_ctl=None, action_out=None,
+                         valve_out=None, log_prob=None, u_out=None):
+    """The MultiCategorical head over logits [n, K0 + K1] (th.split order; rows may be strided) in one launch. The level pair comes
+    from exactly one source: `deterministic` (first maximum of each valve's logits), `action_in` (int64 [n, 2], teacher-forced), `u`
+    ([n, 2] uniforms, inverse CDF per valve) or the Philox stream `rng_ctl` (the uniforms are drawn). action_f32 [n, 2] receives the
+    pair as floats; optional: action_out int64 [n, 2], valve_out [n, 2] (the env's valve pair), log_prob [n] (summed over the valves),
+    u_out [n, 2] (the uniforms used)."""
+    n, m = logits.shape
+    k0, k1 = _levels_pair(nvec, m)
+    ldz = _rows(logits, "logits", n, m)
+    _chk(action_f32, "action_f32", (n, 2), th.float32)
+    _opt(action_in, "action_in", (n, 2), th.int64), _opt(u, "u", (n, 2), th.float32), _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    _opt(action_out, "action_out", (n, 2), th.int64), _opt(valve_out, "valve_out", (n, 2), th.float32)
+    _opt(log_prob, "log_prob", (n,), th.float32), _opt(u_out, "u_out", (n, 2), th.float32)
+    check(nv.lib().cstr_multicategorical_act_f32(ptr(logits), C.c_int64(ldz), C.c_int64(n), C.c_int(k0), C.c_int(k1),
+                                                 C.c_int(int(bool(deterministic))), ptr(action_in), ptr(u), ptr(rng_ctl), ptr(action_f32),
+                                                 ptr(action_out), ptr(valve_out), ptr(log_prob), ptr(u_out), stream_ptr()),
+          "cstr_multicategorical_act_f32")
+
+
+def multicategorical_loss(objective: int, logits, nvec, actions, values, adv, returns, normalize_advantage: bool, ent_coef: float,
+                          vf_coef: float, g_logits, g_value, workspace, old_values=None, old_log_prob=None, clip_range: float = 0.0,
+                          clip_range_vf: Optional[float] = None, scalars_out=None, scalars_sum=None, log_prob_out=None):
+    """categorical_loss on a MultiCategorical head (CAT_PPO: the six PPO_SCALARS, CAT_A2C: the four A2C_SCALARS) in one launch: the
+    scalars and d loss / d (logits, value). actions [b, 2]: the stored level pair as floats. g_logits has the logits' shape and row
+    stride."""
+    b, m = logits.shape
+    k0, k1 = _levels_pair(nvec, m)
+    ldz = _rows(logits, "logits", b, m)
+    if _rows(g_logits, "g_logits", b, m) != ldz:
+        raise ValueError("g_logits must have the logits' row stride")
+    _chk(actions, "actions", (b, 2), th.float32)
+    for t, nm in ((values, "values"), (adv, "adv"), (returns, "returns"), (g_value, "g_value")):
+        _vec(t, nm, b)
+    for t, nm in ((old_values, "old_values"), (old_log_prob, "old_log_prob"), (log_prob_out, "log_prob_out")):
+        if t is not None:
+            _vec(t, nm, b)
+    n_scalars = 6 if objective == CAT_PPO else 4
+    for t, nm in ((scalars_out, "scalars_out"), (scalars_sum, "scalars_sum")):
+        if t is not None:
+            _vec(t, nm, n_scalars)
+    _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    p = nv.MultiCategoricalLoss(logits.data_ptr(), ldz, actions.data_ptr(), values.data_ptr(), dp(old_values), dp(old_log_prob),
+                                adv.data_ptr(), returns.data_ptr(), b, k0, k1, int(objective), int(bool(normalize_advantage)),
+                                float(clip_range), -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef), float(vf_coef),
+                                g_logits.data_ptr(), g_value.data_ptr(), dp(scalars_out), dp(scalars_sum), dp(log_prob_out))
+    check(nv.lib().cstr_multicategorical_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_multicategorical_loss_f32")
+
+
 # ---- HER: the goal face of the env and the device HerReplayBuffer (csrc/cstr_her.hip) ---------------------------------------------
 GOAL_ROW = 6  # flat row [achieved_goal | desired_goal | observation]
 

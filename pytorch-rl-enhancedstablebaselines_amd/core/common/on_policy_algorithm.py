@@ -22,7 +22,7 @@ from core.common import blas, fused
 from core.common.base_class import BaseAlgorithm
 from core.common.buffers import RolloutBuffer
 from core.common.callbacks import BaseCallback, MaybeCallback
-from core.common.spaces import Discrete, as_discrete
+from core.common.spaces import Discrete, MultiDiscrete, as_discrete, as_multi_discrete
 from core.common.vec_env import VecEnv
 
 
@@ -124,7 +124,7 @@ class OnPolicyAlgorithm(BaseAlgorithm):
         rb = self.rollout_buffer
         return (self._denv is not None and self._fused_learner and type(rb) is RolloutBuffer and rb.n_envs == self._denv.num_envs
                 and rb.obs_shape[0] == self._denv.obs_dim
-                and rb.action_dim == (1 if self._denv.discrete_actions is not None else self._denv.act_dim))  # Discrete: the index
+                and rb.action_dim == (1 if self._denv.discrete_actions is not None else self._denv.act_dim))  # Discrete: the index; MultiDiscrete: the level pair, act_dim floats
 
     def collect_rollouts(self, env: VecEnv, callback: BaseCallback, rollout_buffer: RolloutBuffer, n_rollout_steps: int) -> bool:
         """reference :162-268"""
@@ -195,6 +195,8 @@ class OnPolicyAlgorithm(BaseAlgorithm):
         if isinstance(self.action_space, Discrete):  # :228-232: indices step the env as they are and are stored as [n, 1]
             clipped = actions_np
             actions_np = actions_np.reshape(-1, 1)
+        elif isinstance(self.action_space, MultiDiscrete):  # the integer level pairs [n, 2] step the env unclipped and are stored as they are
+            clipped = actions_np
         else:
             clipped = np.clip(actions_np, self.action_space.low, self.action_space.high)
         new_obs, rewards, dones, infos = env.step(clipped)
@@ -264,15 +266,17 @@ class OnPolicyAlgorithm(BaseAlgorithm):
 
     @classmethod
     def _check_archive(cls, data: dict, env) -> None:
-        """An archive written on a Discrete face fits an env with the same number of indices only (and a Box archive a Box env): the
-        policy's head is built from the env's action space."""
+        """An archive written on a Discrete face fits an env with the same number of indices only (and a Box archive a Box env, a MultiDiscrete
+        archive an env with the same `nvec`): the policy's head is built from the env's action space."""
         saved = data.get("action_space")
-        if not isinstance(saved, dict) or not ({"n", "low"} & set(saved)):
+        if not isinstance(saved, dict) or not ({"n", "low", "nvec"} & set(saved)):
             return  # an archive of the reference: its spaces are not stored as plain data
         saved_n = saved.get("n")
+        saved_nvec = None if saved.get("nvec") is None else [int(k) for k in saved["nvec"]]
         face = as_discrete(getattr(env, "action_space", None))
-        if saved_n != (None if face is None else int(face.n)):
-            was = "a Box action space" if saved_n is None else f"Discrete({saved_n})"
+        multi = None if face is not None else as_multi_discrete(getattr(env, "action_space", None))
+        if saved_n != (None if face is None else int(face.n)) or saved_nvec != (None if multi is None else [int(k) for k in multi.nvec]):
+            was = f"MultiDiscrete({saved_nvec})" if saved_nvec is not None else ("a Box action space" if saved_n is None else f"Discrete({saved_n})")
             raise ValueError(f"the archive was written for {was}, the env has {getattr(env, 'action_space', None)} "
                              f"(discrete_actions={getattr(getattr(env, 'unwrapped', env), 'discrete_actions', None)})")
 

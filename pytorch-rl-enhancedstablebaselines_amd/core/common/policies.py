@@ -6,7 +6,7 @@ import numpy as np
 import torch as th
 from torch import nn
 
-from core.common.spaces import Discrete, as_box, as_discrete, get_action_dim
+from core.common.spaces import Discrete, MultiDiscrete, as_box, as_discrete, as_multi_discrete, get_action_dim
 from core.common.torch_layers import CombinedExtractor, FlattenExtractor, create_mlp
 
 
@@ -48,7 +48,7 @@ class BaseModel(nn.Module):
                  normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs: Optional[dict] = None):
         super().__init__()
         self.observation_space = as_box(observation_space)
-        self.action_space = as_discrete(action_space) or as_box(action_space)  # Discrete: DQN's valve face only
+        self.action_space = as_discrete(action_space) or as_multi_discrete(action_space) or as_box(action_space)  # the valve faces
         self.features_extractor = features_extractor
         self.normalize_images = normalize_images
         self.optimizer_class = optimizer_class
@@ -116,7 +116,7 @@ class BasePolicy(BaseModel):
         with th.no_grad():
             actions = self._predict(obs_tensor, deterministic=deterministic)
         actions = actions.cpu().numpy().reshape((-1, *self.action_space.shape))
-        if as_discrete(self.action_space) is not None:
+        if as_discrete(self.action_space) is not None or isinstance(self.action_space, MultiDiscrete):
             pass  # indices: neither unscaled nor clipped (:373-381 are the Box branch)
         elif self.squash_output:
             actions = self.unscale_action(actions)
@@ -166,7 +166,8 @@ class ContinuousCritic(BaseModel):
 
 class ActorCriticPolicy(BasePolicy):
     """reference: core/common/policies.py:416-771 -- policy and value networks of the on-policy algorithms, Box actions (a diagonal
-    Gaussian head with a `log_std` parameter) or Discrete ones (a Categorical head: `action_net` gives the logits, no `log_std`) and a
+    Gaussian head with a `log_std` parameter), Discrete ones (a Categorical head: `action_net` gives the logits, no `log_std`) or
+    MultiDiscrete ones (`multi_discrete`: a MultiCategorical head, `action_net` gives sum(nvec) logits in th.split order) and a
     FlattenExtractor only. Built on the CPU generator in the reference's order (same seed -> the same default initial weights; the
     orthogonal initialisation goes through LAPACK's QR), then `to_device_arenas` moves EVERY parameter, `log_std` included, into one
     flat arena under one optimiser (Adam: eps = 1e-5, :468-472). `fast` (core/common/fused.py FastActorCritic): the kernel form of
@@ -177,7 +178,7 @@ class ActorCriticPolicy(BasePolicy):
                  squash_output: bool = False, features_extractor_class=FlattenExtractor, features_extractor_kwargs: Optional[dict] = None,
                  share_features_extractor: bool = True, normalize_images: bool = True, optimizer_class=th.optim.Adam,
                  optimizer_kwargs: Optional[dict] = None):
-        from core.common.distributions import CategoricalDistribution, DiagGaussianDistribution
+        from core.common.distributions import CategoricalDistribution, DiagGaussianDistribution, MultiCategoricalDistribution
         from core.common.torch_layers import MlpExtractor
 
         if optimizer_kwargs is None:
@@ -203,15 +204,18 @@ class ActorCriticPolicy(BasePolicy):
         self.pi_features_extractor = self.vf_features_extractor = self.features_extractor  # a FlattenExtractor has no parameters
         self.log_std_init, self.use_sde, self.dist_kwargs = log_std_init, False, None
         self.discrete = isinstance(self.action_space, Discrete)  # make_proba_distribution (distributions.py:659-688)
+        self.multi_discrete = isinstance(self.action_space, MultiDiscrete)  # `discrete` keeps meaning Discrete only
         if self.discrete:
             self.action_dist = CategoricalDistribution(int(self.action_space.n))
+        elif self.multi_discrete:
+            self.action_dist = MultiCategoricalDistribution([int(k) for k in self.action_space.nvec])
         else:
             self.action_dist = DiagGaussianDistribution(get_action_dim(self.action_space))
         self._lr_schedule = lr_schedule
         self.fast = None
         # :585-631
         self.mlp_extractor = MlpExtractor(self.features_dim, net_arch=self.net_arch, activation_fn=self.activation_fn)
-        if self.discrete:  # the logits layer; a Categorical head has no log_std (neither parameter nor attribute)
+        if self.discrete or self.multi_discrete:  # the logits layer; a (Multi)Categorical head has no log_std (neither parameter nor attribute)
             self.action_net = self.action_dist.proba_distribution_net(latent_dim=self.mlp_extractor.latent_dim_pi)
         else:
             self.action_net, self.log_std = self.action_dist.proba_distribution_net(latent_dim=self.mlp_extractor.latent_dim_pi,
@@ -244,7 +248,7 @@ class ActorCriticPolicy(BasePolicy):
 
     # ---- the reference's statements on the arena parameters ----------------------------------------------------------
     def _get_action_dist_from_latent(self, latent_pi: th.Tensor):
-        if self.discrete:
+        if self.discrete or self.multi_discrete:
             return self.action_dist.proba_distribution(action_logits=self.action_net(latent_pi))
         return self.action_dist.proba_distribution(self.action_net(latent_pi), self.log_std)
 
@@ -253,11 +257,18 @@ class ActorCriticPolicy(BasePolicy):
         index_f32, values, log_prob, _ = self.fast.act(obs.float().contiguous(), deterministic, want_value=want_value)
         return index_f32.reshape(-1).long(), values, log_prob
 
+    def _fast_pairs(self, obs: th.Tensor, deterministic: bool, want_value: bool):
+        """the kernel head on the MultiDiscrete face -> (int64 level pairs [n, 2], values [n, 1] or None, log_prob [n])"""
+        pair_f32, values, log_prob, _ = self.fast.act(obs.float().contiguous(), deterministic, want_value=want_value)
+        return pair_f32.long(), values, log_prob
+
     def forward(self, obs: th.Tensor, deterministic: bool = False) -> tuple:
         """:636-658 -> (actions, values [n, 1], log_prob [n])"""
         if self.fast is not None and obs.is_cuda and not th.is_grad_enabled():
             if self.discrete:
                 return self._fast_index(obs, deterministic, True)
+            if self.multi_discrete:
+                return self._fast_pairs(obs, deterministic, True)
             return self.fast.act(obs.float().contiguous(), deterministic)[:3]
         features = self.extract_features(obs, self.features_extractor)
         latent_pi, latent_vf = self.mlp_extractor(features)
@@ -274,6 +285,8 @@ class ActorCriticPolicy(BasePolicy):
         distribution = self._get_action_dist_from_latent(latent_pi)
         if self.discrete:
             actions = actions.long().flatten()  # ppo.py:208-210 / a2c.py:146-148
+        elif self.multi_discrete:
+            actions = actions.long().reshape(-1, len(self.action_dist.action_dims))  # Categorical.log_prob takes value.long() itself
         log_prob = distribution.log_prob(actions)
         values = self.value_net(latent_vf)
         return values, log_prob, distribution.entropy()
@@ -295,5 +308,7 @@ class ActorCriticPolicy(BasePolicy):
         if self.fast is not None and observation.is_cuda and not th.is_grad_enabled():
             if self.discrete:
                 return self._fast_index(observation, deterministic, False)[0]
+            if self.multi_discrete:
+                return self._fast_pairs(observation, deterministic, False)[0]
             return self.fast.act(observation.float().contiguous(), deterministic, want_value=False)[0]
         return self.get_distribution(observation).get_actions(deterministic=deterministic)

@@ -1,4 +1,5 @@
-"""Minimal `Box` space (the space of the CSTR path) and `Discrete` (DQN's discretised valve face). gymnasium is not a dependency of this stack:
+"""Minimal `Box` space (the space of the CSTR path), `Discrete` (DQN's discretised valve face) and `MultiDiscrete` (the factored valve
+face of PPO / A2C). gymnasium is not a dependency of this stack:
 any object with `low`, `high`, `shape`, `dtype` (e.g. a real gymnasium.spaces.Box) is accepted wherever a
 Box is expected; `as_box` normalises it. Mirrors the attributes the reference reads
 (core/common/preprocessing.py:152-197, core/common/base_class.py:215-218)."""
@@ -103,6 +104,39 @@ class Discrete(Space):
         return f"Discrete({self.n})" if self.start == 0 else f"Discrete({self.n}, start={self.start})"
 
 
+class MultiDiscrete(Space):
+    """One Discrete per component: component g takes 0 .. nvec[g] - 1 (gymnasium.spaces.MultiDiscrete with a 1-D `nvec`: dtype int64,
+    shape (len(nvec),)). `sample()` draws from the space's own Generator (UNPINNED, as for Discrete.sample)."""
+
+    def __init__(self, nvec, seed=None):
+        nvec = np.array(nvec, dtype=np.int64, copy=True)
+        if nvec.ndim != 1 or nvec.size == 0 or not (nvec > 0).all():
+            raise ValueError(f"nvec (counts) have to be a non-empty 1-D array of positive counts, got {nvec!r}")
+        self.nvec = nvec
+        super().__init__(nvec.shape, np.int64)
+        if seed is not None:
+            self.seed(seed)
+
+    def sample_batch(self, count: int) -> np.ndarray:
+        return self.np_random.integers(0, self.nvec, size=(count, len(self.nvec)), dtype=np.int64)
+
+    def sample(self) -> np.ndarray:
+        return self.sample_batch(1)[0]
+
+    def contains(self, x) -> bool:
+        if isinstance(x, (list, tuple)):
+            x = np.array(x)
+        return bool(isinstance(x, np.ndarray) and x.shape == self.shape and x.dtype != bool and np.issubdtype(x.dtype, np.integer)
+                    and (x >= 0).all() and (x < self.nvec).all())
+
+    def __eq__(self, other):
+        nvec = getattr(other, "nvec", None)
+        return nvec is not None and not hasattr(other, "low") and np.ndim(nvec) == 1 and np.array_equal(np.asarray(nvec), self.nvec)
+
+    def __repr__(self):
+        return f"MultiDiscrete({self.nvec})"
+
+
 class Dict(Space):
     """A dictionary of spaces with SORTED keys, as gymnasium.spaces.Dict orders a plain dict (the goal face of the env: achieved_goal,
     desired_goal, observation). The device-side observation is the flat row of the sub-spaces in key order."""
@@ -166,6 +200,16 @@ def as_discrete(space) -> Optional[Discrete]:
     return None
 
 
+def as_multi_discrete(space) -> Optional[MultiDiscrete]:
+    """`space` as a MultiDiscrete (itself, or any object with a 1-D `nvec`, e.g. a gymnasium.spaces.MultiDiscrete), else None."""
+    if isinstance(space, MultiDiscrete):
+        return space
+    nvec = getattr(space, "nvec", None)
+    if nvec is not None and np.ndim(nvec) == 1 and np.size(nvec) > 0:
+        return MultiDiscrete(np.asarray(nvec))
+    return None
+
+
 class IndexedBox(Box):
     """Box that remembers which indices of the global vector it covers
     (reference: core/common/envs/multi_agent_envs.py:7-29)."""
@@ -205,7 +249,10 @@ def get_obs_shape(space) -> tuple:
 
 
 def get_action_dim(space) -> int:
-    """reference: core/common/preprocessing.py:184-210 -- a Discrete action is a single int"""
+    """reference: core/common/preprocessing.py:184-210 -- a Discrete action is a single int, a MultiDiscrete one an int per component"""
     if as_discrete(space) is not None:
         return 1
+    multi = as_multi_discrete(space)
+    if multi is not None:
+        return int(len(multi.nvec))
     return int(np.prod(as_box(space).shape))

@@ -15,10 +15,11 @@ import torch as th
 
 from core import _native as nv
 from core.common import hip_ops
-from core.common.spaces import Box, Dict, Discrete
+from core.common.spaces import Box, Dict, Discrete, MultiDiscrete
 from core.common.vec_env.base_vec_env import VecEnv
 
 MIN_VALVE_LEVELS, MAX_VALVE_LEVELS = 2, 16
+MAX_MULTI_VALVE_LEVELS = 32  # the MultiDiscrete face: one categorical per valve (csrc/cstr_multicategorical.hip)
 
 
 def valve_levels(levels: int) -> np.ndarray:
@@ -41,6 +42,12 @@ def encode_valve_pair(valve, levels: int) -> np.ndarray:
     q = np.rint(((v + np.float32(1)) * np.float32(levels - 1)) / np.float32(2))
     q = np.clip(q, 0, levels - 1).astype(np.int64)
     return q[..., 0] * levels + q[..., 1]
+
+
+def decode_valve_levels(pairs, nvec) -> np.ndarray:
+    """level pairs [..., 2] of the MultiDiscrete face -> normalised valve pairs [..., 2] = (v_0(a_0), v_1(a_1))"""
+    a = np.asarray(pairs, dtype=np.int64)
+    return np.stack([valve_levels(int(nvec[0]))[a[..., 0]], valve_levels(int(nvec[1]))[a[..., 1]]], axis=-1)
 
 
 GOAL_KEYS = ("achieved_goal", "desired_goal", "observation")  # sorted: the column order of the flat row
@@ -111,6 +118,11 @@ class CSTRVecEnv(VecEnv):
                     v(q) = f32(-1) + f32(2 q) / f32(K - 1). `valve_space` = Box(-1, 1, (2,)) is what the env kernels and the replay
                     ring see: `step()` / `step_async()` take index arrays [N] (or [N, 1]) and decode them, `step_device` keeps
                     taking [N, 2] valve tensors. A constructed face, like twin=True: the reference's env has the Box face only
+    :param multi_discrete_actions: K or (K0, K1), each in 2..32 (twin=False, no discrete_actions, no goal face): a FACTORED discrete
+                    face, one categorical per valve, for PPO / A2C. `action_space` is MultiDiscrete([K0, K1]); level q of valve g is
+                    the normalised valve action v_g(q) = f32(-1) + f32(2 q) / f32(K_g - 1) (`valve_levels(K_g)`). `step()` /
+                    `step_async()` take integer arrays [N, 2]; `step_device`, `valve_space` and the env kernels keep seeing the
+                    valve pair. `discrete_actions` stays None on this face: it names the joint-index face alone
     :param goal_conditioned: the GOAL face (obs_dim=4, twin=False, continuous valves only), for HER. `observation_space` is
                     Dict(achieved_goal: Box(-1, 1, (1,)), desired_goal: Box(-1, 1, (1,)), observation: Box(-1, 1, (4,))):
                     achieved_goal = observation[2] (normalised C2), desired_goal = the env's OWN target through the same affine
@@ -131,7 +143,20 @@ class CSTRVecEnv(VecEnv):
     def __init__(self, num_envs: int, obs_dim: int = 4, integrator: str = "euler", device="cuda",
                  default_target: float = 0.20, min_concentration: float = 0.05, max_concentration: float = 0.45,
                  init_mode: str = "random", seed_offset: int = 0, twin: bool = False, discrete_actions: Optional[int] = None,
-                 goal_conditioned: bool = False, goal_range=None, goal_seed: int = 0):
+                 goal_conditioned: bool = False, goal_range=None, goal_seed: int = 0, multi_discrete_actions=None):
+        if multi_discrete_actions is not None:
+            if twin:
+                raise ValueError("multi_discrete_actions needs twin=False (one valve pair per env)")
+            if discrete_actions is not None:
+                raise ValueError("multi_discrete_actions and discrete_actions are two faces over the same valves: choose one")
+            if goal_conditioned:
+                raise ValueError("multi_discrete_actions needs goal_conditioned=False (the goal face has continuous valves only)")
+            pair = (multi_discrete_actions,) * 2 if isinstance(multi_discrete_actions, (int, np.integer)) else tuple(multi_discrete_actions)
+            if len(pair) != 2 or not all(isinstance(k, (int, np.integer)) and not isinstance(k, bool)
+                                         and MIN_VALVE_LEVELS <= k <= MAX_MULTI_VALVE_LEVELS for k in pair):
+                raise ValueError(f"multi_discrete_actions must be an integer or a pair of integers in [{MIN_VALVE_LEVELS}, "
+                                 f"{MAX_MULTI_VALVE_LEVELS}], got {multi_discrete_actions!r}")
+            multi_discrete_actions = (int(pair[0]), int(pair[1]))
         if goal_conditioned and (twin or obs_dim != 4 or discrete_actions is not None):
             raise ValueError("goal_conditioned=True needs obs_dim=4, twin=False and continuous valves (discrete_actions=None)")
         if goal_range is not None:
@@ -167,7 +192,11 @@ class CSTRVecEnv(VecEnv):
         a1 = np.ones(self.act_dim, np.float32)
         self.valve_space = Box(-a1, a1, dtype=np.float32)
         self.discrete_actions = None if discrete_actions is None else int(discrete_actions)
-        action_space = self.valve_space if discrete_actions is None else Discrete(self.discrete_actions ** 2)
+        self.multi_discrete_actions = multi_discrete_actions
+        if multi_discrete_actions is not None:
+            action_space = MultiDiscrete(list(multi_discrete_actions))
+        else:
+            action_space = self.valve_space if discrete_actions is None else Discrete(self.discrete_actions ** 2)
         self.goal_conditioned = bool(goal_conditioned)
         self.goal_range = None if goal_range is None else (float(goal_range[0]), float(goal_range[1]))
         self.goal_seed = int(goal_seed)
@@ -346,6 +375,14 @@ class CSTRVecEnv(VecEnv):
             if idx.min() < 0 or idx.max() >= self.action_space.n:
                 raise ValueError(f"discrete actions: indices must lie in [0, {self.action_space.n})")
             actions = decode_valve_index(idx, self.discrete_actions)
+        elif self.multi_discrete_actions is not None:
+            pairs = actions.cpu().numpy() if isinstance(actions, th.Tensor) else np.asarray(actions)
+            if not np.issubdtype(pairs.dtype, np.integer) or pairs.shape != (self.num_envs, 2):
+                raise ValueError(f"multi-discrete actions: expected integer level pairs of shape {(self.num_envs, 2)}, got {pairs.dtype} {pairs.shape}")
+            nvec = self.action_space.nvec
+            if pairs.min() < 0 or (pairs >= nvec).any():
+                raise ValueError(f"multi-discrete actions: levels must lie in [0, {nvec[0]}) x [0, {nvec[1]})")
+            actions = decode_valve_levels(pairs, nvec)
         a = th.as_tensor(np.asarray(actions, dtype=np.float32)) if not isinstance(actions, th.Tensor) else actions
         if tuple(a.shape) != (self.num_envs, self.act_dim):
             raise ValueError(f"actions shape {tuple(a.shape)} != {(self.num_envs, self.act_dim)}")

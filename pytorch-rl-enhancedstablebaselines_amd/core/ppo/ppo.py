@@ -11,7 +11,11 @@ the reference's own torch statements on the arena parameters (`fused_learner` Fa
 On a Discrete valve face (`CSTRVecEnv(discrete_actions=K)`) the policy has a Categorical head: the rollout head and the loss launch
 are csrc/cstr_categorical.hip's (hip_ops.categorical_act / categorical_loss), the buffer's action row is the index as one float.
 
-Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiDiscrete / MultiBinary actions, CNN / dict policies."""
+On a MultiDiscrete valve face (`CSTRVecEnv(multi_discrete_actions=(K0, K1))`) it has a MultiCategorical head, one categorical per
+valve over K0 + K1 logits: csrc/cstr_multicategorical.hip (hip_ops.multicategorical_act / multicategorical_loss), the buffer's action
+row is the level pair as two floats.
+
+Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN / dict policies."""
 import warnings
 from typing import Optional, Union
 
@@ -21,7 +25,7 @@ from torch.nn import functional as F
 from core.common import fused, hip_ops
 from core.common.logger import DeviceMean
 from core.common.on_policy_algorithm import OnPolicyAlgorithm
-from core.common.spaces import Discrete
+from core.common.spaces import Discrete, MultiDiscrete
 from core.common.utils import get_schedule_fn
 from core.ppo.policies import MlpPolicy
 
@@ -39,7 +43,7 @@ class PPO(OnPolicyAlgorithm):
                          vf_coef=vf_coef, max_grad_norm=max_grad_norm, use_sde=use_sde, sde_sample_freq=sde_sample_freq,
                          rollout_buffer_class=rollout_buffer_class, rollout_buffer_kwargs=rollout_buffer_kwargs,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs,
-                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box", Discrete))
+                         verbose=verbose, device=device, seed=seed, _init_setup_model=False, supported_action_spaces=("Box", Discrete, MultiDiscrete))
         self._check_batch_arguments(batch_size, self.n_steps, None if self.env is None else self.env.num_envs, normalize_advantage)
         self.batch_size = batch_size
         self.n_epochs = n_epochs
@@ -105,6 +109,15 @@ class PPO(OnPolicyAlgorithm):
                                      self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
                                      old_values=rd.old_values, old_log_prob=rd.old_log_prob, clip_range=clip_range, clip_range_vf=clip_range_vf,
                                      scalars_out=self._scalars, scalars_sum=sums, log_prob_out=b["log_prob"] if self.debug_capture else None)
+            return logits, values, b
+        if fast.multi_discrete:  # the MultiCategorical head: one categorical per valve, the entropy gradient per valve
+            logits = fast.logits(rd.observations, train_params=True)
+            values = fast.values(rd.observations, train_params=True)
+            hip_ops.multicategorical_loss(hip_ops.CAT_PPO, logits.detach(), fast.nvec, rd.actions, values.detach(), rd.advantages, rd.returns,
+                                          self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
+                                          old_values=rd.old_values, old_log_prob=rd.old_log_prob, clip_range=clip_range,
+                                          clip_range_vf=clip_range_vf, scalars_out=self._scalars, scalars_sum=sums,
+                                          log_prob_out=b["log_prob"] if self.debug_capture else None)
             return logits, values, b
         mean = fast.mean(rd.observations, train_params=True)
         values = fast.values(rd.observations, train_params=True)

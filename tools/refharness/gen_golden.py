@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,ppo_discrete,a2c_discrete,init,vecenv,callbacks]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,ppo_discrete,a2c_discrete,ppo_multidiscrete,a2c_multidiscrete,init,vecenv,callbacks]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -1899,6 +1899,148 @@ def gen_a2c_discrete():
     save("a2c_cat_train_kat_small.npz", **out)
 
 
+# ------------------------------------------------------- PPO / A2C on the MultiDiscrete valve face (MultiCategorical head)
+def _make_multidiscrete_venv(N, K0, K1):
+    """Harness code of ours: the reference's TwoSeriesCSTREnv behind a MultiDiscrete([K0, K1]) action space; the pair (a0, a1) opens
+    the two valves to v_0(a0), v_1(a1)."""
+    from gymnasium import spaces
+
+    from core.common.vec_env.dummy_vec_env import DummyVecEnv
+    from twoseriescstr import TwoSeriesCSTREnv
+
+    class MultiDiscreteValveCSTR(TwoSeriesCSTREnv):
+        def __init__(self):
+            super().__init__()
+            self._valve_box, self.action_space = self.action_space, spaces.MultiDiscrete([K0, K1])
+
+        def step(self, action):
+            a0, a1 = (int(q) for q in np.asarray(action).reshape(2))
+            face, self.action_space = self.action_space, self._valve_box  # the env's own step clips into its Box
+            try:
+                return super().step(np.array([_valve(a0, K0), _valve(a1, K1)], np.float32))
+            finally:
+                self.action_space = face
+
+    return DummyVecEnv([lambda: MultiDiscreteValveCSTR() for _ in range(N)])
+
+
+def gen_ppo_multidiscrete():
+    """PPO on MultiDiscrete([K0, K1]) (core/ppo/ppo.py:127-136, core/common/distributions.py:314-368): ppo_mcat_train_kat_small.npz
+    (nvec [3, 5], 4 envs, n_steps 8, batch 12, 3 epochs, nets [32, 32]), ppo_mcat_train_kat_default.npz (nvec [5, 5], class-default
+    nets as digests, 8 envs, n_steps 16, batch 64, 2 epochs) and ppo_mcat_predict_kat.npz. The sampled pairs are rollout/actions
+    [T, N, 2]."""
+    late = ((1, 396), (2, 399), (3, 395))
+    small = dict(n_envs=4, n_steps=8, batch_size=12, n_epochs=3, net_arch=[32, 32], late=late)
+    for seed in range(7, 120):
+        model, out, hk = _ppo_run(seed, venv=_make_multidiscrete_venv(4, 3, 5), **small)
+        clipped = max(float(mb["scalars"][5]) for mb in hk.minibatches)
+        if clipped > 0 and int(out["n_truncations"]) >= 2 and _ppo_margins_ok(hk, 0.2, None):
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the small multi-categorical PPO fixture")
+    out["nvec"] = np.array([3, 5], np.int64)
+    keys = "".join(out["state_dict_keys"].tolist())
+    assert out["rollout/actions"].shape == (8, 4, 2) and "log_std" not in keys and out["before/policy/action_net.weight"].shape == (8, 32)
+    print(f"ppo mcat small: seed {seed}, max clip_fraction {clipped:.3f}, truncations {int(out['n_truncations'])}")
+    save("ppo_mcat_train_kat_small.npz", **out)
+    for seed_d in range(11, 120):
+        _, o, hk_d = _ppo_run(seed_d, n_envs=8, n_steps=16, batch_size=64, n_epochs=2, late=((0, 390), (5, 397), (6, 399)),
+                              venv=_make_multidiscrete_venv(8, 5, 5))
+        # the conditions of ppo_train_kat_default.npz: four steps at the class-default head gain of 0.01 move no ratio past the clip range
+        if int(o["n_truncations"]) >= 2 and _ppo_margins_ok(hk_d, 0.2, None):
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the default multi-categorical PPO fixture")
+    o["nvec"] = np.array([5, 5], np.int64)
+    print(f"ppo mcat default: seed {seed_d}")
+    save("ppo_mcat_train_kat_default.npz", **slim_weights(o))
+    # predict: the trained small model on 16 seeded observations; per valve, every row's top-two logit gap exceeds 1e-4 * max |logit|
+    for pseed in range(99, 400):
+        obs = np.random.default_rng(pseed).uniform(-1, 1, (16, 4)).astype(np.float32)
+        with th.no_grad():
+            logits = model.policy.action_net(model.policy.mlp_extractor.forward_actor(th.as_tensor(obs))).numpy()
+        tops = [np.sort(z, axis=1) for z in (logits[:, :3], logits[:, 3:])]
+        if all(((t[:, -1] - t[:, -2]) > 1e-4 * np.abs(logits).max()).all() for t in tops):
+            break
+    else:
+        raise RuntimeError("no observation seed met the logit-gap condition")
+    p = _flat_sd("policy", model.policy.state_dict())
+    p["obs"], p["net_arch"], p["seed"], p["obs_seed"], p["nvec"] = obs, np.array([32, 32], np.int64), out["seed"], np.int64(pseed), np.array([3, 5], np.int64)
+    p["deterministic"], _ = model.predict(obs, deterministic=True)
+    expect = np.stack([logits[:, :3].argmax(axis=1), logits[:, 3:].argmax(axis=1)], axis=1)
+    assert p["deterministic"].dtype == np.int64 and p["deterministic"].shape == (16, 2) and np.array_equal(p["deterministic"], expect)
+    one, _ = model.predict(obs[0], deterministic=True)
+    assert one.shape == (2,) and one.dtype == np.int64
+    p["logits"] = logits
+    with th.no_grad():
+        p["values"] = model.policy.predict_values(th.as_tensor(obs)).numpy()
+    save("ppo_mcat_predict_kat.npz", **p)
+
+
+def _a2c_reference_own_error(out, nvec):
+    """Harness code of ours: how far the reference's float32 weights after each train() are from the same step taken in float64 (same
+    rollout rows, same weights before, same square_avg before), per element in the units the tests hold an implementation to
+    (tests/_parity_helpers.check_weights: |got - want| / (2e-5 max|want| + 1e-4 |want|)); the worst over both iterations. RMSprop
+    divides by sqrt(square_avg) + eps, so where a gradient element is a cancelling sum near eps its float32 rounding error reaches the
+    weight almost undamped: a rollout with such an element measures the summation order, not the statements."""
+    keys = [str(k) for k in out["state_dict_keys"]]
+    lr, eps, alpha = float(out["learning_rate"]), float(out["rms_prop_eps"]), 0.99
+    T, N = int(out["n_steps"]), int(out["n_envs"])
+    flat = lambda a: (a if a.ndim > 2 else a[..., None]).swapaxes(0, 1).reshape(T * N, -1)  # noqa: E731  swap_and_flatten
+    worst = 0.0
+    for it in range(int(out["iterations"])):
+        pre, before = f"it{it}/", ("before" if it == 0 else f"it{it - 1}/after")
+        P = {k: th.tensor(out[f"{before}/policy/{k}"].astype(np.float64), requires_grad=True) for k in keys}
+        f = lambda name: th.tensor(flat(out[f"{pre}rollout/{name}"]).astype(np.float64))  # noqa: E731
+        obs = f("observations")
+
+        def mlp(net, head):
+            h = obs
+            for i in (0, 2):
+                h = th.tanh(h @ P[f"mlp_extractor.{net}.{i}.weight"].T + P[f"mlp_extractor.{net}.{i}.bias"])
+            return h @ P[f"{head}.weight"].T + P[f"{head}.bias"]
+
+        dists = [th.distributions.Categorical(logits=z) for z in th.split(mlp("policy_net", "action_net"), list(nvec), dim=1)]
+        log_prob = sum(d.log_prob(a.long()) for d, a in zip(dists, th.unbind(f("actions"), dim=1)))
+        entropy = sum(d.entropy() for d in dists)
+        values = mlp("value_net", "value_net").flatten()
+        loss = (-(f("advantages").flatten() * log_prob).mean() + float(out["ent_coef"]) * -entropy.mean()
+                + float(out["vf_coef"]) * th.nn.functional.mse_loss(f("returns").flatten(), values))
+        loss.backward()
+        norm = float(th.sqrt(sum((p.grad ** 2).sum() for p in P.values())))
+        coef = min(1.0, float(out["max_grad_norm"]) / (norm + 1e-6))
+        for k in keys:
+            g = P[k].grad.numpy() * coef
+            prev = np.zeros_like(g) if it == 0 else out[f"it{it - 1}/opt/square_avg/{k}"].astype(np.float64)
+            stepped = P[k].detach().numpy() - lr * g / (np.sqrt(alpha * prev + (1 - alpha) * g * g) + eps)
+            ref = out[f"{pre}after/policy/{k}"].astype(np.float64)
+            worst = max(worst, float((np.abs(ref - stepped) / (2e-5 * max(np.abs(ref).max(), 1e-3) + 1e-4 * np.abs(ref))).max()))
+    return worst
+
+
+def gen_a2c_multidiscrete():
+    """A2C on MultiDiscrete([3, 5]), two consecutive iterations: a2c_mcat_train_kat_small.npz (4 envs, n_steps 5, nets [32, 32]).
+    Seed conditions: a truncation in each iteration, as for the Categorical fixture, and a rollout whose step the reference itself
+    takes well: its own float32 error (_a2c_reference_own_error) at most a quarter of the bar the tests hold an implementation to, so
+    that three quarters of the bar remain for the implementation's own float32 rounding, which is of the same kind and size. (Seed 7
+    has a gradient element of 8e-5 in action_net.weight whose float32 value is 2.5e-4 off in the reference itself; its step through
+    RMSprop's eps = 1e-5 puts the reference's own weight at 0.6 of the bar.)"""
+    late = ((1, 396), (2, 399), (3, 392))
+    for seed in range(7, 120):
+        _, out = _a2c_run(seed, n_envs=4, net_arch=[32, 32], late=late, venv=_make_multidiscrete_venv(4, 3, 5))
+        trunc = [int(out[f"it{k}/timeouts"].sum()) for k in range(2)]
+        own = _a2c_reference_own_error(out, (3, 5)) if min(trunc) >= 1 else float("inf")
+        print(f"a2c mcat small: seed {seed}: truncations {trunc}, the reference's own float32 error {own:.3f} of the bar")
+        if min(trunc) >= 1 and own <= 0.25:
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the small multi-categorical A2C fixture")
+    assert int(out["n_truncations"]) >= 2 and out["it0/rollout/actions"].shape == (5, 4, 2) and str(out["optimizer"]) == "RMSprop"
+    out["nvec"] = np.array([3, 5], np.int64)
+    print(f"a2c mcat small: seed {seed}, gradient norms {[float(out[f'it{k}/grad_norm']) for k in range(2)]}, truncations {trunc}")
+    save("a2c_mcat_train_kat_small.npz", **out)
+
+
 def gen_callbacks():
     """The reference's training callbacks (core/common/callbacks.py:146-680) on small CPU runs of SAC over
     DummyVecEnv([TwoSeriesCSTREnv] * N). Only STRUCTURE is written -- directory listings, evaluations.npz's timesteps / ep_lengths,
@@ -2121,7 +2263,7 @@ def gen_her():
     save("her_buffer_kat.npz", **out)
 
 
-GENS = {"her": gen_her, "her_learners": gen_her_learners,"ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+GENS = {"her": gen_her, "her_learners": gen_her_learners, "ppo_multidiscrete": gen_ppo_multidiscrete, "a2c_multidiscrete": gen_a2c_multidiscrete, "ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn}
 
