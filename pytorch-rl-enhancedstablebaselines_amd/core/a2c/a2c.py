@@ -108,14 +108,10 @@ class A2C(OnPolicyAlgorithm):
         b = self._bufs(obs.shape[0])
         mean = fast.logits(obs, train_params=True) if (fast.discrete or fast.multi_discrete) else fast.mean(obs, train_params=True)
         values = fast.values(obs, train_params=True)
-        if fast.discrete:  # the Categorical head: g_mean holds d loss / d logits, there is no log_std
-            hip_ops.categorical_loss(hip_ops.CAT_A2C, mean.detach(), fast.levels, actions, values.detach(), advantages, returns,
-                                     self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
-                                     scalars_out=self._scalars, log_prob_out=b["log_prob"] if self.debug_capture else None)
-        elif fast.multi_discrete:  # the MultiCategorical head: one categorical per valve
-            hip_ops.multicategorical_loss(hip_ops.CAT_A2C, mean.detach(), fast.nvec, actions, values.detach(), advantages, returns,
-                                          self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
-                                          scalars_out=self._scalars, log_prob_out=b["log_prob"] if self.debug_capture else None)
+        if fast.discrete or fast.multi_discrete:  # a (Multi)Categorical head: g_mean holds d loss / d logits, there is no log_std
+            fast.discrete_loss(hip_ops.CAT_A2C, mean.detach(), actions, values.detach(), advantages, returns, self.normalize_advantage,
+                               self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws, scalars_out=self._scalars,
+                               log_prob_out=b["log_prob"] if self.debug_capture else None)
         else:
             hip_ops.a2c_loss(mean.detach(), pol.log_std.detach(), actions, values.detach(), advantages, returns, self.normalize_advantage,
                              self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], pol.log_std.grad, self._ws, scalars_out=self._scalars,

@@ -1527,44 +1527,38 @@ class FastActorCritic:
             b = self._bufs[n] = dict(action=e(n, self.act_dim), env_action=e(n, 2 if self.discrete else self.act_dim), log_prob=e(n))
         return b
 
-    def _act_categorical(self, obs: th.Tensor, deterministic: bool, want_value: bool):
+    def _act_discrete(self, head, face, forced_shape, obs: th.Tensor, deterministic: bool, want_value: bool):
+        """the rollout head of a discrete form: `head` is hip_ops.categorical_act (face = levels, queued actions int64 [n]) or
+        hip_ops.multicategorical_act (face = nvec, queued actions int64 [n, 2])"""
         n = obs.shape[0]
         b = self.bufs(n, obs.device)
         logits = self.logits(obs)
         values = self.values(obs) if want_value else None
         forced = None
         if not deterministic and self.action_queue:
-            forced = self.action_queue.pop(0).to(obs.device, th.int64).reshape(n).contiguous()
+            forced = self.action_queue.pop(0).to(obs.device, th.int64).reshape(n, *forced_shape).contiguous()
         rng = None if (deterministic or forced is not None) else self.rng_ctl
         if not deterministic and forced is None and rng is None:
-            raise RuntimeError("FastActorCritic.act: no index source (neither a queued action nor a Philox stream)")
-        hip_ops.categorical_act(logits, self.levels, b["action"], deterministic=deterministic, action_in=forced, rng_ctl=rng,
-                                valve_out=b["env_action"], log_prob=b["log_prob"])
+            raise RuntimeError("FastActorCritic.act: no action source (neither a queued action nor a Philox stream)")
+        head(logits, face, b["action"], deterministic=deterministic, action_in=forced, rng_ctl=rng, valve_out=b["env_action"],
+             log_prob=b["log_prob"])
         return b["action"], values, b["log_prob"], b["env_action"]
 
-    def _act_multicategorical(self, obs: th.Tensor, deterministic: bool, want_value: bool):
-        n = obs.shape[0]
-        b = self.bufs(n, obs.device)
-        logits = self.logits(obs)
-        values = self.values(obs) if want_value else None
-        forced = None
-        if not deterministic and self.action_queue:
-            forced = self.action_queue.pop(0).to(obs.device, th.int64).reshape(n, 2).contiguous()
-        rng = None if (deterministic or forced is not None) else self.rng_ctl
-        if not deterministic and forced is None and rng is None:
-            raise RuntimeError("FastActorCritic.act: no action source (neither a queued pair nor a Philox stream)")
-        hip_ops.multicategorical_act(logits, self.nvec, b["action"], deterministic=deterministic, action_in=forced, rng_ctl=rng,
-                                     valve_out=b["env_action"], log_prob=b["log_prob"])
-        return b["action"], values, b["log_prob"], b["env_action"]
+    def discrete_loss(self, objective: int, logits, actions, *args, **kwargs) -> None:
+        """hip_ops.categorical_loss or multicategorical_loss, whichever the form's head is, on its face"""
+        if self.discrete:  # the Categorical head
+            hip_ops.categorical_loss(objective, logits, self.levels, actions, *args, **kwargs)
+        else:  # the MultiCategorical head: one categorical per valve, the entropy gradient per valve
+            hip_ops.multicategorical_loss(objective, logits, self.nvec, actions, *args, **kwargs)
 
     def act(self, obs: th.Tensor, deterministic: bool = False, want_value: bool = True):
         """ActorCriticPolicy.forward without gradients -> (actions [n, A] unclipped, values [n, 1] or None, log_prob [n], env_action =
         clip(actions, low, high)). The outputs are static per row count: valid until the next call with as many rows."""
         with th.no_grad():
             if self.discrete:  # -> (index as a float [n, 1], values, log_prob, the valve pair [n, 2])
-                return self._act_categorical(obs, deterministic, want_value)
+                return self._act_discrete(hip_ops.categorical_act, self.levels, (), obs, deterministic, want_value)
             if self.multi_discrete:  # -> (level pair as floats [n, 2], values, log_prob, the valve pair [n, 2])
-                return self._act_multicategorical(obs, deterministic, want_value)
+                return self._act_discrete(hip_ops.multicategorical_act, self.nvec, (2,), obs, deterministic, want_value)
             n = obs.shape[0]
             b = self.bufs(n, obs.device)
             mean = self.mean(obs)

@@ -1685,17 +1685,15 @@ def categorical_act(logits, levels: int, index_f32, deterministic: bool = False,
 CAT_PPO, CAT_A2C = 0, 1
 
 
-def categorical_loss(objective: int, logits, levels: int, actions, values, adv, returns, normalize_advantage: bool, ent_coef: float,
-                     vf_coef: float, g_logits, g_value, workspace, old_values=None, old_log_prob=None, clip_range: float = 0.0,
-                     clip_range_vf: Optional[float] = None, scalars_out=None, scalars_sum=None, log_prob_out=None):
-    """ppo.py:213-264 (CAT_PPO: the six PPO_SCALARS) or a2c.py:150-171 (CAT_A2C: the four A2C_SCALARS) on a Categorical head in one
-    launch: the scalars and d loss / d (logits, value). actions [b] or [b, 1]: the stored index as a float. g_logits has the logits'
-    shape and row stride."""
+def _discrete_loss(struct, symbol: str, face, objective: int, logits, actions, values, adv, returns, normalize_advantage, ent_coef, vf_coef,
+                   g_logits, g_value, workspace, old_values, old_log_prob, clip_range, clip_range_vf, scalars_out, scalars_sum, log_prob_out):
+    """What categorical_loss and multicategorical_loss share: the two structs differ only in the face's two int32 fields (`face`) and
+    in the shape of `actions`, which the caller has checked."""
     b, m = logits.shape
     ldz = _rows(logits, "logits", b, m)
     if _rows(g_logits, "g_logits", b, m) != ldz:
         raise ValueError("g_logits must have the logits' row stride")
-    for t, nm in ((actions, "actions"), (values, "values"), (adv, "adv"), (returns, "returns"), (g_value, "g_value")):
+    for t, nm in ((values, "values"), (adv, "adv"), (returns, "returns"), (g_value, "g_value")):
         _vec(t, nm, b)
     for t, nm in ((old_values, "old_values"), (old_log_prob, "old_log_prob"), (log_prob_out, "log_prob_out")):
         if t is not None:
@@ -1706,11 +1704,24 @@ def categorical_loss(objective: int, logits, levels: int, actions, values, adv, 
             _vec(t, nm, n_scalars)
     _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
     dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    p = nv.CategoricalLoss(logits.data_ptr(), ldz, actions.data_ptr(), values.data_ptr(), dp(old_values), dp(old_log_prob), adv.data_ptr(),
-                           returns.data_ptr(), b, m, int(levels), int(objective), int(bool(normalize_advantage)), float(clip_range),
-                           -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef), float(vf_coef), g_logits.data_ptr(),
-                           g_value.data_ptr(), dp(scalars_out), dp(scalars_sum), dp(log_prob_out))
-    check(nv.lib().cstr_categorical_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_categorical_loss_f32")
+    p = struct(logits.data_ptr(), ldz, actions.data_ptr(), values.data_ptr(), dp(old_values), dp(old_log_prob), adv.data_ptr(),
+               returns.data_ptr(), b, face[0], face[1], int(objective), int(bool(normalize_advantage)), float(clip_range),
+               -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef), float(vf_coef), g_logits.data_ptr(),
+               g_value.data_ptr(), dp(scalars_out), dp(scalars_sum), dp(log_prob_out))
+    check(getattr(nv.lib(), symbol)(C.byref(p), ptr(workspace), stream_ptr()), symbol)
+
+
+def categorical_loss(objective: int, logits, levels: int, actions, values, adv, returns, normalize_advantage: bool, ent_coef: float,
+                     vf_coef: float, g_logits, g_value, workspace, old_values=None, old_log_prob=None, clip_range: float = 0.0,
+                     clip_range_vf: Optional[float] = None, scalars_out=None, scalars_sum=None, log_prob_out=None):
+    """ppo.py:213-264 (CAT_PPO: the six PPO_SCALARS) or a2c.py:150-171 (CAT_A2C: the four A2C_SCALARS) on a Categorical head in one
+    launch: the scalars and d loss / d (logits, value). actions [b] or [b, 1]: the stored index as a float. g_logits has the logits'
+    shape and row stride."""
+    b, m = logits.shape
+    _vec(actions, "actions", b)
+    _discrete_loss(nv.CategoricalLoss, "cstr_categorical_loss_f32", (m, int(levels)), objective, logits, actions, values, adv,
+                   returns, normalize_advantage, ent_coef, vf_coef, g_logits, g_value, workspace, old_values, old_log_prob, clip_range,
+                   clip_range_vf, scalars_out, scalars_sum, log_prob_out)
 
 
 # ---- MultiCategorical head of PPO / A2C on the MultiDiscrete valve face (csrc/cstr_multicategorical.hip) ---------------------------
@@ -1752,27 +1763,11 @@ def multicategorical_loss(objective: int, logits, nvec, actions, values, adv, re
     scalars and d loss / d (logits, value). actions [b, 2]: the stored level pair as floats. g_logits has the logits' shape and row
     stride."""
     b, m = logits.shape
-    k0, k1 = _levels_pair(nvec, m)
-    ldz = _rows(logits, "logits", b, m)
-    if _rows(g_logits, "g_logits", b, m) != ldz:
-        raise ValueError("g_logits must have the logits' row stride")
+    face = _levels_pair(nvec, m)
     _chk(actions, "actions", (b, 2), th.float32)
-    for t, nm in ((values, "values"), (adv, "adv"), (returns, "returns"), (g_value, "g_value")):
-        _vec(t, nm, b)
-    for t, nm in ((old_values, "old_values"), (old_log_prob, "old_log_prob"), (log_prob_out, "log_prob_out")):
-        if t is not None:
-            _vec(t, nm, b)
-    n_scalars = 6 if objective == CAT_PPO else 4
-    for t, nm in ((scalars_out, "scalars_out"), (scalars_sum, "scalars_sum")):
-        if t is not None:
-            _vec(t, nm, n_scalars)
-    _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
-    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    p = nv.MultiCategoricalLoss(logits.data_ptr(), ldz, actions.data_ptr(), values.data_ptr(), dp(old_values), dp(old_log_prob),
-                                adv.data_ptr(), returns.data_ptr(), b, k0, k1, int(objective), int(bool(normalize_advantage)),
-                                float(clip_range), -1.0 if clip_range_vf is None else float(clip_range_vf), float(ent_coef), float(vf_coef),
-                                g_logits.data_ptr(), g_value.data_ptr(), dp(scalars_out), dp(scalars_sum), dp(log_prob_out))
-    check(nv.lib().cstr_multicategorical_loss_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_multicategorical_loss_f32")
+    _discrete_loss(nv.MultiCategoricalLoss, "cstr_multicategorical_loss_f32", face, objective, logits, actions, values, adv, returns,
+                   normalize_advantage, ent_coef, vf_coef, g_logits, g_value, workspace, old_values, old_log_prob, clip_range, clip_range_vf,
+                   scalars_out, scalars_sum, log_prob_out)
 
 
 # ---- HER: the goal face of the env and the device HerReplayBuffer (csrc/cstr_her.hip) ---------------------------------------------

@@ -102,22 +102,13 @@ class PPO(OnPolicyAlgorithm):
         """evaluate_actions on the per-layer kernels and the loss launch; returns what the backward needs"""
         fast, pol = self._fast, self.policy
         b = self._bufs(rd.observations.shape[0])
-        if fast.discrete:  # the Categorical head: g_mean holds d loss / d logits, there is no log_std
+        if fast.discrete or fast.multi_discrete:  # a (Multi)Categorical head: g_mean holds d loss / d logits, there is no log_std
             logits = fast.logits(rd.observations, train_params=True)
             values = fast.values(rd.observations, train_params=True)
-            hip_ops.categorical_loss(hip_ops.CAT_PPO, logits.detach(), fast.levels, rd.actions, values.detach(), rd.advantages, rd.returns,
-                                     self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
-                                     old_values=rd.old_values, old_log_prob=rd.old_log_prob, clip_range=clip_range, clip_range_vf=clip_range_vf,
-                                     scalars_out=self._scalars, scalars_sum=sums, log_prob_out=b["log_prob"] if self.debug_capture else None)
-            return logits, values, b
-        if fast.multi_discrete:  # the MultiCategorical head: one categorical per valve, the entropy gradient per valve
-            logits = fast.logits(rd.observations, train_params=True)
-            values = fast.values(rd.observations, train_params=True)
-            hip_ops.multicategorical_loss(hip_ops.CAT_PPO, logits.detach(), fast.nvec, rd.actions, values.detach(), rd.advantages, rd.returns,
-                                          self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
-                                          old_values=rd.old_values, old_log_prob=rd.old_log_prob, clip_range=clip_range,
-                                          clip_range_vf=clip_range_vf, scalars_out=self._scalars, scalars_sum=sums,
-                                          log_prob_out=b["log_prob"] if self.debug_capture else None)
+            fast.discrete_loss(hip_ops.CAT_PPO, logits.detach(), rd.actions, values.detach(), rd.advantages, rd.returns,
+                               self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
+                               old_values=rd.old_values, old_log_prob=rd.old_log_prob, clip_range=clip_range, clip_range_vf=clip_range_vf,
+                               scalars_out=self._scalars, scalars_sum=sums, log_prob_out=b["log_prob"] if self.debug_capture else None)
             return logits, values, b
         mean = fast.mean(rd.observations, train_params=True)
         values = fast.values(rd.observations, train_params=True)

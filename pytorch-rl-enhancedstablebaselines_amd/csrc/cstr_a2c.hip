@@ -1,9 +1,8 @@
 // cstr_a2c.hip -- A2C's own arithmetic and its optimiser (reference core/a2c/a2c.py:132-190), f32, gfx950:
 //   * everything between evaluate_actions' outputs and loss.backward() (a2c.py:150-171) in ONE launch: advantage normalisation, the
 //     diagonal Gaussian's log-prob and entropy, the policy-gradient and value losses, the four scalars and the gradients w.r.t. the
-//     action mean, the value and log_std. The structure is ppo_loss_kernel's: every thread sums its rows in f64, a fixed LDS tree per
-//     workgroup, the partials are published and the workgroup that draws the last ticket sums them in workgroup order. No float atomics;
-//     the grid is a function of the row count alone.
+//     action mean, the value and log_std. The kernel is PPO's with the other objective (diag_gaussian_loss_kernel<A, false> of
+//     cstr_onpolicy_device.h, where the reduction convention is stated); cstr_a2c_loss_f32 fills its arguments.
 //   * torch.optim.RMSprop (momentum 0, not centred, no weight decay) over one flat arena with clip_grad_norm_ folded in: launch 1 is
 //     the sum-of-squares pass of cstr_grad_clip_f32 (same grid, same partials), launch 2 forms the coefficient from the partials as
 //     grad_scale_kernel does, scales each gradient in register, writes it back and takes the step. Without clipping: one launch and
@@ -19,96 +18,6 @@
 #include "cstr_onpolicy_device.h"
 
 namespace {
-
-constexpr int A2C_PARTS = 8;  // policy sum, value sum, -, -, d log_std[0..3]: the stride of cstr_ppo_loss_f32's partials
-
-// a2c.py:150-171
-template <int A>
-__global__ __launch_bounds__(256) void a2c_loss_kernel(const cstr_a2c_loss_t p, unsigned long long *__restrict__ ws)
-{
-    __shared__ double red[256];
-    __shared__ double tot[A2C_PARTS];
-    const int64_t B = p.batch;
-    // advantage statistics over the whole buffer: every workgroup computes them itself, in the same order
-    const bool norm = p.normalize_advantage != 0;
-    float a_mean = 0.0f, a_den = 1.0f;
-    if (norm) {
-        double s = 0.0;
-        for (int64_t i = threadIdx.x; i < B; i += 256) s += (double)p.adv[i];
-        a_mean = (float)(block_sum_f64(s, red) / (double)B);
-        double q = 0.0;
-        for (int64_t i = threadIdx.x; i < B; i += 256) {
-            const float d = p.adv[i] - a_mean;
-            q += (double)(d * d);
-        }
-        a_den = (float)sqrt(block_sum_f64(q, red) / (double)(B - 1)) + 1e-8f;  // unbiased std, a2c.py:156; B == 1: 0 / 0 = NaN
-    }
-    float sig[A], var[A];
-#pragma unroll
-    for (int k = 0; k < A; ++k) {
-        sig[k] = expf(p.log_std[k]);
-        var[k] = sig[k] * sig[k];
-    }
-    const float inv_b = 1.0f / (float)B;
-    double acc[2 + A];
-#pragma unroll
-    for (int k = 0; k < 2 + A; ++k) acc[k] = 0.0;
-    for (int64_t b = blockIdx.x * 256ll + threadIdx.x; b < B; b += (int64_t)gridDim.x * 256ll) {
-        float mu[A], act[A];
-        load_row<A>(p.mean + b * p.ldm, mu);
-        load_row<A>(p.actions + b * A, act);
-        const float logp = diag_log_prob<A>(act, mu, sig);
-        if (p.log_prob_out) p.log_prob_out[b] = logp;
-        const float advn = norm ? (p.adv[b] - a_mean) / a_den : p.adv[b];
-        acc[0] += (double)(advn * logp);
-        const float g_logp = -(inv_b * advn);  // d(-mean(adv * log_prob)) / d log_prob
-        float gm[A];
-#pragma unroll
-        for (int k = 0; k < A; ++k) {
-            const float d = act[k] - mu[k];
-            gm[k] = g_logp * (d / var[k]);
-            acc[2 + k] += (double)(g_logp * ((d * d) / var[k] - 1.0f));
-        }
-        store_row<A>(p.g_mean + b * A, gm);
-        const float v = p.values[b], ret = p.returns[b];
-        const float dr = ret - v;
-        acc[1] += (double)(dr * dr);
-        p.g_value[b] = p.vf_coef * ((2.0f * inv_b) * (v - ret));
-    }
-#pragma unroll
-    for (int k = 0; k < 2 + A; ++k) {
-        const double s = block_sum_f64(acc[k], red);
-        const int slot = k < 2 ? k : k + 2;
-        if (threadIdx.x == 0) publish_f64(ws + WS_PART0 + (int64_t)blockIdx.x * A2C_PARTS + slot, s);
-    }
-    __threadfence();  // release: the partials are visible chip-wide before this workgroup's ticket is
-    if (!last_block_ticket(ws)) return;
-    __threadfence();  // acquire: behind the last ticket every workgroup's partials are read from memory
-    if (threadIdx.x < A2C_PARTS) {
-        double s = 0.0;
-        const bool used = threadIdx.x < 2 || (threadIdx.x >= 4 && threadIdx.x < 4 + A);
-        if (used)
-            for (unsigned j = 0; j < gridDim.x; ++j) s += consume_f64(ws + WS_PART0 + (int64_t)j * A2C_PARTS + threadIdx.x);
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ent = 0.0f;
-#pragma unroll
-        for (int k = 0; k < A; ++k) ent += HALF_LOG_2PI_E + logf(sig[k]);
-        float out[4];
-        out[0] = -(float)(tot[0] / (double)B);  // policy_loss
-        out[1] = (float)(tot[1] / (double)B);   // value_loss
-        out[2] = -ent;                          // entropy_loss = -mean(entropy); the entropy does not depend on the row
-        out[3] = (out[0] + p.ent_coef * out[2]) + p.vf_coef * out[1];  // loss
-        if (p.scalars_out) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) p.scalars_out[k] = out[k];
-        }
-#pragma unroll
-        for (int k = 0; k < A; ++k) p.g_log_std[k] = (float)tot[4 + k] - p.ent_coef;  // d(ent_coef * entropy_loss) / d log_std = -ent_coef
-    }
-}
 
 // torch.optim.RMSprop's single-tensor step, every operation rounded to f32 in ATen's order (mul_ / addcmul_ / sqrt / add_ / addcdiv_)
 __device__ __forceinline__ void rmsprop1(float &w, float &g, float &sq, const float coef, const float alpha, const float oma,
@@ -159,36 +68,13 @@ __global__ __launch_bounds__(512) void rmsprop_kernel(float *__restrict__ param,
 
 extern "C" int cstr_a2c_loss_f32(const cstr_a2c_loss_t *p, uint64_t *workspace, cstr_stream_t stream)
 {
-    if (!p || !workspace || !p->mean || !p->log_std || !p->actions || !p->values || !p->adv || !p->returns || !p->g_mean || !p->g_value ||
-        !p->g_log_std || p->batch <= 0 || p->act_dim <= 0)
-        return CSTR_E_BADARG;
-    if (p->act_dim != 2 && p->act_dim != 4) return CSTR_E_UNSUPPORTED;
-    if (p->batch > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
-    const int A = p->act_dim;
-    if (p->ldm < A || (p->ldm * 4) % (A == 4 ? 16 : 8)) return CSTR_E_BADARG;
-    if (!aligned8(workspace) || !row_aligned(p->mean, A) || !row_aligned(p->actions, A) || !row_aligned(p->g_mean, A) ||
-        !aligned4(p->log_std) || !aligned4(p->values) || !aligned4(p->adv) || !aligned4(p->returns) || !aligned4(p->g_value) ||
-        !aligned4(p->g_log_std) || (p->scalars_out && !aligned4(p->scalars_out)) || (p->log_prob_out && !aligned4(p->log_prob_out)))
-        return CSTR_E_BADARG;
-    {
-        const int64_t B = p->batch;
-        const void *ins[6] = {p->mean, p->log_std, p->actions, p->values, p->adv, p->returns};
-        const int64_t in_n[6] = {(B - 1) * p->ldm + A, A, B * A, B, B, B};
-        const void *outs[6] = {p->g_mean, p->g_value, p->g_log_std, p->scalars_out, p->log_prob_out, workspace};
-        const int64_t out_n[6] = {B * A, B, A, 4, B, 2 * CSTR_PPO_WS_WORDS};
-        for (int o = 0; o < 6; ++o) {
-            if (!outs[o]) continue;
-            for (int i = 0; i < 6; ++i)
-                if (overlap(outs[o], out_n[o], ins[i], in_n[i])) return CSTR_E_BADARG;
-            for (int q = o + 1; q < 6; ++q)
-                if (outs[q] && overlap(outs[o], out_n[o], outs[q], out_n[q])) return CSTR_E_BADARG;
-        }
-    }
-    const unsigned grid = lane_grid(p->batch, 256, CSTR_PPO_MAX_BLOCKS);
-    unsigned long long *ws = reinterpret_cast<unsigned long long *>(workspace);
-    if (A == 2) a2c_loss_kernel<2><<<grid, 256, 0, (hipStream_t)stream>>>(*p, ws);
-    else a2c_loss_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(*p, ws);
-    return (int)hipGetLastError();
+    if (!p) return CSTR_E_BADARG;
+    cstr_ppo_loss_t k = {};  // no old_values, old_log_prob, clip ranges or scalars_sum: the A2C objective reads none of them
+    k.mean = p->mean, k.ldm = p->ldm, k.log_std = p->log_std, k.actions = p->actions, k.values = p->values;
+    k.adv = p->adv, k.returns = p->returns, k.batch = p->batch, k.act_dim = p->act_dim, k.normalize_advantage = p->normalize_advantage;
+    k.ent_coef = p->ent_coef, k.vf_coef = p->vf_coef, k.g_mean = p->g_mean, k.g_value = p->g_value, k.g_log_std = p->g_log_std;
+    k.scalars_out = p->scalars_out, k.log_prob_out = p->log_prob_out;
+    return diag_gaussian_loss_launch<false>(&k, workspace, stream);
 }
 
 extern "C" int cstr_rmsprop_f32(float *param, float *grad, float *square_avg, const double *lr, double alpha, double eps, float max_norm,

@@ -9,8 +9,8 @@
 // Uniforms are READ when given and DRAWN otherwise: Philox4x32-10 keyed by rng_ctl[0], counter (rng_ctl[1] + row, 0, DQN tag); words
 // 0 and 1 give u[row][0] and u[row][1] as (word >> 8) * 2^-24 in [0, 1). The last workgroup advances rng_ctl[1] by the row count,
 // in every launch that draws (mode 1 also when the flag is 0: the launch sequence, not the data, decides the stream position).
-// The batch reduction has a fixed order and no float atomics (the convention of cstr_ppo.hip): every thread sums its rows in f64, a
-// fixed LDS tree per workgroup, published partials, and the workgroup that draws the last ticket sums them in workgroup order.
+// The batch reduction follows the convention at the top of cstr_onpolicy_device.h (fixed order, no float atomics), with one slot and
+// one workspace word per workgroup.
 // One lane per row: a row of at most 256 Q values is scanned by its lane. The launches are latency-bound at the batch sizes DQN
 // uses (32 rows by default); nothing here is tuned for bandwidth.
 #include <hip/hip_runtime.h>
@@ -128,8 +128,9 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float *__restrict__
                                                        float *__restrict__ target_out, unsigned long long *__restrict__ ws)
 {
     __shared__ double red[256];
+    __shared__ double tot[1];
     const float fB = (float)B;
-    double acc = 0.0;
+    double acc[1] = {0.0};
     for (int64_t b = blockIdx.x * 256ll + threadIdx.x; b < B; b += (int64_t)gridDim.x * 256ll) {
         float best;
         row_argmax(next_q + b * ldn, M, best);                      // next_q_values.max(dim=1)
@@ -138,22 +139,16 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float *__restrict__
         const int a = level_of(v.x, K) * K + level_of(v.y, K);     // in [0, M) by construction
         const float cur = q[b * ldq + a];                           // th.gather(current_q_values, 1, actions)
         const float d = cur - target, z = fabsf(d);
-        acc += (double)(z < 1.0f ? (0.5f * z) * z : z - 0.5f);      // smooth_l1_loss, beta = 1 (a NaN takes the second branch)
+        acc[0] += (double)(z < 1.0f ? (0.5f * z) * z : z - 0.5f);      // smooth_l1_loss, beta = 1 (a NaN takes the second branch)
         float *g = g_q + b * ldq;
         for (int c = 0; c < M; ++c) g[c] = 0.0f;
         g[a] = d != d ? d : fminf(fmaxf(d, -1.0f), 1.0f) / fB;      // d smooth_l1 / d cur = clamp(d, -1, 1), mean over B; a NaN stays one
         if (cur_q_out) cur_q_out[b] = cur;
         if (target_out) target_out[b] = target;
     }
-    const double s = block_sum_f64(acc, red);
-    if (threadIdx.x == 0) publish_f64(ws + WS_PART0 + blockIdx.x, s);
-    __threadfence();  // release: the partial is visible chip-wide before this workgroup's ticket is
-    if (!last_block_ticket(ws)) return;
-    __threadfence();  // acquire: behind the last ticket every workgroup's partial is read from memory
+    if (!reduce_partials<1, 1u, 1>(acc, red, ws, tot)) return;
     if (threadIdx.x == 0) {
-        double tot = 0.0;
-        for (unsigned j = 0; j < gridDim.x; ++j) tot += consume_f64(ws + WS_PART0 + j);
-        const float loss = (float)(tot / (double)B);
+        const float loss = (float)(tot[0] / (double)B);
         loss_out[0] = loss;
         if (loss_sum) loss_sum[0] += loss;
     }
@@ -163,9 +158,6 @@ inline int face_check(int n_actions, int levels)
 {
     return (levels < 2 || levels > CSTR_DQN_MAX_LEVELS || n_actions != levels * levels) ? CSTR_E_UNSUPPORTED : 0;
 }
-
-// floats spanned by `rows` rows of `width` floats with row stride ld
-inline int64_t span(int64_t rows, int64_t ld, int64_t width) { return (rows - 1) * ld + width; }
 
 }  // namespace
 
@@ -201,19 +193,9 @@ extern "C" int cstr_dqn_act_f32(const float *q, int64_t ldq, int64_t n, int n_ac
         (u_in && !aligned8(u_in)) || (rng_ctl && !aligned8(rng_ctl)))
         return CSTR_E_BADARG;
     {
-        const void *ins[5] = {q, eps, flag, u_in, rng_ctl};
-        const int64_t in_n[5] = {span(n, ldq, n_actions), 2, 1, 2 * n, 2 * CSTR_RNG_CTL_WORDS};
-        const void *outs[2] = {valve_out, index_out};
-        const int64_t out_n[2] = {2 * n, 2 * n};
-        for (int o = 0; o < 2; ++o) {
-            if (!outs[o]) continue;
-            for (int i = 0; i < 5; ++i)
-                if (ins[i] && overlap(outs[o], out_n[o], ins[i], in_n[i])) return CSTR_E_BADARG;
-        }
-        if (index_out && overlap(valve_out, 2 * n, index_out, 2 * n)) return CSTR_E_BADARG;
-        if (rng_ctl)
-            for (int i = 0; i < 4; ++i)
-                if (ins[i] && overlap(rng_ctl, 2 * CSTR_RNG_CTL_WORDS, ins[i], in_n[i])) return CSTR_E_BADARG;
+        const Buf ins[4] = {{q, span(n, ldq, n_actions)}, {eps, 2}, {flag, 1}, {u_in, 2 * n}};
+        const Buf outs[3] = {{valve_out, 2 * n}, {index_out, 2 * n}, {rng_ctl, 2 * CSTR_RNG_CTL_WORDS}};
+        if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
     }
     dqn_act_kernel<<<lane_grid(n, 64, 4096), 64, 0, (hipStream_t)stream>>>(q, ldq, n, n_actions, levels, mode, eps, flag, u_in, rng_ctl,
                                                                           valve_out, index_out);
@@ -236,17 +218,10 @@ extern "C" int cstr_dqn_loss_f32(const float *q, int64_t ldq, const float *next_
         return CSTR_E_BADARG;
     {
         const int64_t B = batch;
-        const void *ins[5] = {q, next_q, valve, reward, done};
-        const int64_t in_n[5] = {span(B, ldq, n_actions), span(B, ldn, n_actions), 2 * B, B, B};
-        const void *outs[6] = {g_q, loss_out, loss_sum, cur_q_out, target_out, workspace};
-        const int64_t out_n[6] = {span(B, ldq, n_actions), 1, 1, B, B, 2 * CSTR_PPO_WS_WORDS};
-        for (int o = 0; o < 6; ++o) {
-            if (!outs[o]) continue;
-            for (int i = 0; i < 5; ++i)
-                if (overlap(outs[o], out_n[o], ins[i], in_n[i])) return CSTR_E_BADARG;
-            for (int p = o + 1; p < 6; ++p)
-                if (outs[p] && overlap(outs[o], out_n[o], outs[p], out_n[p])) return CSTR_E_BADARG;
-        }
+        const Buf ins[5] = {{q, span(B, ldq, n_actions)}, {next_q, span(B, ldn, n_actions)}, {valve, 2 * B}, {reward, B}, {done, B}};
+        const Buf outs[6] = {{g_q, span(B, ldq, n_actions)}, {loss_out, 1}, {loss_sum, 1}, {cur_q_out, B}, {target_out, B},
+                             {workspace, 2 * CSTR_PPO_WS_WORDS}};
+        if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
     }
     const unsigned grid = lane_grid(batch, 256, CSTR_PPO_MAX_BLOCKS);
     dqn_loss_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(q, ldq, next_q, ldn, valve, reward, done, gamma, batch, n_actions, levels, g_q,

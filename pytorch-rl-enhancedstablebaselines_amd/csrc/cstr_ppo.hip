@@ -7,15 +7,13 @@
 //   * the minibatch gather by flat swap_and_flatten indices (index i = env i / T, step i % T);
 //   * everything between evaluate_actions' outputs and loss.backward() (ppo.py:213-264): advantage normalisation, the diagonal
 //     Gaussian's log-prob and entropy, ratio and clipped surrogate, the (clipped) value loss, the six logged scalars and the
-//     gradients w.r.t. the action mean, the value and log_std;
+//     gradients w.r.t. the action mean, the value and log_std (diag_gaussian_loss_kernel<A, true> of cstr_onpolicy_device.h);
 //   * clip_grad_norm_ over the flat gradient arena (the coefficient stays on the device).
 // Noise is READ when given and DRAWN otherwise: Philox4x32-10 keyed by rng_ctl[0], counter (rng_ctl[1] + row, 0, PPO tag) -> two
 // Box-Muller pairs = the row's (up to four) draws; the last workgroup advances rng_ctl[1] by the row count.
-// Batch reductions have a fixed order and no float atomics: every thread sums its rows in f64, a fixed LDS tree per workgroup, the
-// per-workgroup partials are published (agent-scope stores, release fence, ticket) and the workgroup that draws the last ticket sums
-// them in workgroup order behind an acquire fence. The grid is a function of the row count alone, so a given batch always reduces
-// the same way. The gradient clip is two launches (partials, then every workgroup sums the partials in the same order and scales
-// its share), so no workgroup waits for another inside a launch.
+// Batch reductions follow the convention at the top of cstr_onpolicy_device.h (fixed order, no float atomics). The gradient clip is
+// two launches (partials, then every workgroup sums the partials in the same order and scales its share), so no workgroup waits for
+// another inside a launch.
 // NOT a batch reduction, and not order-deterministic: the Monitor-style episode statistics of the add launch (ep_stats: f64
 // atomicAdd per finished episode, the convention of cstr_collect_step_f32). The count and the sum of lengths are integers in f64 and
 // so exact in any order; the sum of returns, which only feeds the logged rollout/ep_rew_mean, may differ in its last f64 bits.
@@ -32,7 +30,6 @@
 namespace {
 
 constexpr uint32_t PPO_STREAM_TAG = 0x990A11C7u;  // counter word 3: never shares counters with the other heads' streams
-constexpr int LOSS_PARTS = 8;  // policy sum, value sum, kl sum, clipped count, d log_std[0..3]
 
 // on_policy_algorithm.py:199-216: one lane per env
 template <int A>
@@ -186,112 +183,6 @@ __global__ __launch_bounds__(256) void ppo_gather_kernel(const cstr_rollout_t rb
     }
 }
 
-// ppo.py:213-264
-template <int A>
-__global__ __launch_bounds__(256) void ppo_loss_kernel(const cstr_ppo_loss_t p, unsigned long long *__restrict__ ws)
-{
-    __shared__ double red[256];
-    __shared__ double tot[LOSS_PARTS];
-    const int64_t B = p.batch;
-    // advantage statistics over the whole minibatch: every workgroup computes them itself, in the same order
-    const bool norm = p.normalize_advantage && B > 1;
-    float a_mean = 0.0f, a_den = 1.0f;
-    if (norm) {
-        double s = 0.0;
-        for (int64_t i = threadIdx.x; i < B; i += 256) s += (double)p.adv[i];
-        a_mean = (float)(block_sum_f64(s, red) / (double)B);
-        double q = 0.0;
-        for (int64_t i = threadIdx.x; i < B; i += 256) {
-            const float d = p.adv[i] - a_mean;
-            q += (double)(d * d);
-        }
-        a_den = (float)sqrt(block_sum_f64(q, red) / (double)(B - 1)) + 1e-8f;  // unbiased std, ppo.py:219
-    }
-    float sig[A], var[A];
-#pragma unroll
-    for (int k = 0; k < A; ++k) {
-        sig[k] = expf(p.log_std[k]);
-        var[k] = sig[k] * sig[k];
-    }
-    const float lo = (float)(1.0 - p.clip_range), hi = (float)(1.0 + p.clip_range), cr = (float)p.clip_range;
-    const bool vclip = p.clip_range_vf > 0.0;
-    const float cv = (float)p.clip_range_vf;
-    const float inv_b = 1.0f / (float)B;
-    double acc[LOSS_PARTS];
-#pragma unroll
-    for (int k = 0; k < LOSS_PARTS; ++k) acc[k] = 0.0;
-    for (int64_t b = blockIdx.x * 256ll + threadIdx.x; b < B; b += (int64_t)gridDim.x * 256ll) {
-        float mu[A], act[A];
-        load_row<A>(p.mean + b * p.ldm, mu);
-        load_row<A>(p.actions + b * A, act);
-        const float logp = diag_log_prob<A>(act, mu, sig);
-        if (p.log_prob_out) p.log_prob_out[b] = logp;
-        const float lr = logp - p.old_log_prob[b];
-        const float ratio = expf(lr);
-        const float advn = norm ? (p.adv[b] - a_mean) / a_den : p.adv[b];
-        const float pl1 = advn * ratio, pl2 = advn * fminf(fmaxf(ratio, lo), hi);
-        acc[0] += (double)fminf(pl1, pl2);
-        acc[2] += (double)((ratio - 1.0f) - lr);
-        acc[3] += fabsf(ratio - 1.0f) > cr ? 1.0 : 0.0;
-        // d min(pl1, pl2) / d ratio: the clamp passes the gradient on the closed interval (there pl1 == pl2, torch splits the
-        // gradient between the two equal operands and both halves arrive); outside it only pl1 carries one
-        const float dmin = ((ratio >= lo && ratio <= hi) || pl1 < pl2) ? advn : 0.0f;
-        const float g_logp = -(inv_b * dmin) * ratio;
-        float gm[A];
-#pragma unroll
-        for (int k = 0; k < A; ++k) {
-            const float d = act[k] - mu[k];
-            gm[k] = g_logp * (d / var[k]);
-            acc[4 + k] += (double)(g_logp * ((d * d) / var[k] - 1.0f));
-        }
-        store_row<A>(p.g_mean + b * A, gm);
-        const float v = p.values[b], ret = p.returns[b];
-        float vp = v;
-        bool pass = true;
-        if (vclip) {
-            const float vo = p.old_values[b], dv = v - vo;
-            vp = vo + fminf(fmaxf(dv, -cv), cv);
-            pass = dv >= -cv && dv <= cv;
-        }
-        const float dr = ret - vp;
-        acc[1] += (double)(dr * dr);
-        p.g_value[b] = pass ? p.vf_coef * ((2.0f * inv_b) * (vp - ret)) : 0.0f;
-    }
-#pragma unroll
-    for (int k = 0; k < LOSS_PARTS; ++k) {
-        const double s = (k < 4 + A) ? block_sum_f64(acc[k], red) : 0.0;
-        if (threadIdx.x == 0) publish_f64(ws + WS_PART0 + (int64_t)blockIdx.x * LOSS_PARTS + k, s);
-    }
-    __threadfence();  // release: the partials are visible chip-wide before this workgroup's ticket is
-    if (!last_block_ticket(ws)) return;
-    __threadfence();  // acquire: behind the last ticket every workgroup's partials are read from memory
-    if (threadIdx.x < LOSS_PARTS) {
-        double s = 0.0;
-        for (unsigned j = 0; j < gridDim.x; ++j) s += consume_f64(ws + WS_PART0 + (int64_t)j * LOSS_PARTS + threadIdx.x);
-        tot[threadIdx.x] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float ent = 0.0f;
-#pragma unroll
-        for (int k = 0; k < A; ++k) ent += HALF_LOG_2PI_E + logf(sig[k]);
-        float out[6];
-        out[0] = -(float)(tot[0] / (double)B);          // policy_gradient_loss
-        out[1] = (float)(tot[1] / (double)B);           // value_loss
-        out[2] = -ent;                                  // entropy_loss = -mean(entropy); the entropy does not depend on the row
-        out[3] = (out[0] + p.ent_coef * out[2]) + p.vf_coef * out[1];  // loss
-        out[4] = (float)(tot[2] / (double)B);           // approx_kl
-        out[5] = (float)(tot[3] / (double)B);           // clip_fraction
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            if (p.scalars_out) p.scalars_out[k] = out[k];
-            if (p.scalars_sum) p.scalars_sum[k] += out[k];
-        }
-#pragma unroll
-        for (int k = 0; k < A; ++k) p.g_log_std[k] = (float)tot[4 + k] - p.ent_coef;  // d(ent_coef * entropy_loss) / d log_std = -ent_coef
-    }
-}
-
 // clip_grad_norm_ (torch.nn.utils), launch 2 behind grad_sumsq_kernel: coef = min(1, max_norm / (norm + 1e-6)); grad *= coef (torch
 // multiplies also when the coefficient is 1)
 __global__ __launch_bounds__(256) void grad_scale_kernel(float *__restrict__ grad, const int64_t n, const double *__restrict__ part,
@@ -336,17 +227,9 @@ extern "C" int cstr_diag_gaussian_act_f32(const float *mean, const float *log_st
         return CSTR_E_BADARG;
     {
         const int64_t na = n * act_dim;
-        const void *ins[2] = {mean, deterministic ? nullptr : eps_in};
-        const void *outs[4] = {action, env_action, log_prob, eps_out};
-        const int64_t out_n[4] = {na, na, n, na};
-        for (int o = 0; o < 4; ++o) {
-            if (!outs[o]) continue;
-            for (int i = 0; i < 2; ++i)
-                if (ins[i] && overlap(outs[o], out_n[o], ins[i], na)) return CSTR_E_BADARG;
-            if (overlap(outs[o], out_n[o], log_std, act_dim)) return CSTR_E_BADARG;
-            for (int q = o + 1; q < 4; ++q)
-                if (outs[q] && overlap(outs[o], out_n[o], outs[q], out_n[q])) return CSTR_E_BADARG;
-        }
+        const Buf ins[3] = {{mean, na}, {deterministic ? nullptr : eps_in, na}, {log_std, act_dim}};
+        const Buf outs[4] = {{action, na}, {env_action, na}, {log_prob, n}, {eps_out, na}};
+        if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
     }
     const unsigned grid = lane_grid(n, 64, 4096);
     if (act_dim == 2)
@@ -406,11 +289,9 @@ extern "C" int cstr_gae_f32(const float *rewards, const float *values, const flo
     for (int i = 0; i < 7; ++i)
         if (!aligned4(all[i])) return CSTR_E_BADARG;
     const int64_t cells = n_steps * n_envs;
-    const void *ins[5] = {rewards, values, episode_starts, last_values, dones};
-    const int64_t in_n[5] = {cells, cells, cells, n_envs, n_envs};
-    for (int i = 0; i < 5; ++i)
-        if (overlap(advantages, cells, ins[i], in_n[i]) || overlap(returns, cells, ins[i], in_n[i])) return CSTR_E_BADARG;
-    if (overlap(advantages, cells, returns, cells)) return CSTR_E_BADARG;
+    const Buf ins[5] = {{rewards, cells}, {values, cells}, {episode_starts, cells}, {last_values, n_envs}, {dones, n_envs}};
+    const Buf outs[2] = {{advantages, cells}, {returns, cells}};
+    if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
     // NEP 50: a Python float times a float32 array rounds the float to float32; gamma * gae_lambda is a product of two Python floats
     gae_kernel<<<lane_grid(n_envs, 64, 4096), 64, 0, (hipStream_t)stream>>>(rewards, values, episode_starts, last_values, dones, (float)gamma,
                                                                            (float)(gamma * gae_lambda), advantages, returns, n_steps,
@@ -429,17 +310,11 @@ extern "C" int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx,
         !aligned4(adv) || !aligned4(ret))
         return CSTR_E_BADARG;
     const int64_t cells = rb->rows * rb->n_envs;
-    const void *outs[6] = {obs, act, old_value, old_log_prob, adv, ret};
-    const int64_t out_n[6] = {batch * rb->obs_dim, batch * rb->act_dim, batch, batch, batch, batch};
-    const void *ins[6] = {rb->obs, rb->act, rb->values, rb->log_probs, rb->advantages, rb->returns};
-    const int64_t in_n[6] = {cells * rb->obs_dim, cells * rb->act_dim, cells, cells, cells, cells};
-    for (int o = 0; o < 6; ++o) {
-        for (int i = 0; i < 6; ++i)
-            if (overlap(outs[o], out_n[o], ins[i], in_n[i])) return CSTR_E_BADARG;
-        if (overlap(outs[o], out_n[o], idx, 2 * batch)) return CSTR_E_BADARG;
-        for (int q = o + 1; q < 6; ++q)
-            if (overlap(outs[o], out_n[o], outs[q], out_n[q])) return CSTR_E_BADARG;
-    }
+    const Buf outs[6] = {{obs, batch * rb->obs_dim}, {act, batch * rb->act_dim}, {old_value, batch}, {old_log_prob, batch}, {adv, batch},
+                         {ret, batch}};
+    const Buf ins[7] = {{rb->obs, cells * rb->obs_dim}, {rb->act, cells * rb->act_dim}, {rb->values, cells}, {rb->log_probs, cells},
+                        {rb->advantages, cells}, {rb->returns, cells}, {idx, 2 * batch}};
+    if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
     const unsigned grid = lane_grid(batch, 256, 2048);
     const int d = rb->obs_dim, a = rb->act_dim;
 #define GATHER_LAUNCH(D, A) \
@@ -456,39 +331,7 @@ extern "C" int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx,
 
 extern "C" int cstr_ppo_loss_f32(const cstr_ppo_loss_t *p, uint64_t *workspace, cstr_stream_t stream)
 {
-    if (!p || !workspace || !p->mean || !p->log_std || !p->actions || !p->values || !p->old_log_prob || !p->adv || !p->returns ||
-        !p->g_mean || !p->g_value || !p->g_log_std || p->batch <= 0 || p->act_dim <= 0)
-        return CSTR_E_BADARG;
-    if (!(p->clip_range >= 0.0) || (p->clip_range_vf > 0.0 && !p->old_values)) return CSTR_E_BADARG;
-    if (p->act_dim != 2 && p->act_dim != 4) return CSTR_E_UNSUPPORTED;
-    if (p->batch > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
-    const int A = p->act_dim;
-    if (p->ldm < A || (p->ldm * 4) % (A == 4 ? 16 : 8)) return CSTR_E_BADARG;
-    if (!aligned8(workspace) || !row_aligned(p->mean, A) || !row_aligned(p->actions, A) || !row_aligned(p->g_mean, A) ||
-        !aligned4(p->log_std) || !aligned4(p->values) || !aligned4(p->old_log_prob) || !aligned4(p->adv) || !aligned4(p->returns) ||
-        !aligned4(p->g_value) || !aligned4(p->g_log_std) || (p->old_values && !aligned4(p->old_values)) ||
-        (p->scalars_out && !aligned4(p->scalars_out)) || (p->scalars_sum && !aligned4(p->scalars_sum)) ||
-        (p->log_prob_out && !aligned4(p->log_prob_out)))
-        return CSTR_E_BADARG;
-    {
-        const int64_t B = p->batch;
-        const void *ins[8] = {p->mean, p->log_std, p->actions, p->values, p->old_values, p->old_log_prob, p->adv, p->returns};
-        const int64_t in_n[8] = {(B - 1) * p->ldm + A, A, B * A, B, B, B, B, B};
-        const void *outs[7] = {p->g_mean, p->g_value, p->g_log_std, p->scalars_out, p->scalars_sum, p->log_prob_out, workspace};
-        const int64_t out_n[7] = {B * A, B, A, 6, 6, B, 2 * CSTR_PPO_WS_WORDS};
-        for (int o = 0; o < 7; ++o) {
-            if (!outs[o]) continue;
-            for (int i = 0; i < 8; ++i)
-                if (ins[i] && overlap(outs[o], out_n[o], ins[i], in_n[i])) return CSTR_E_BADARG;
-            for (int q = o + 1; q < 7; ++q)
-                if (outs[q] && overlap(outs[o], out_n[o], outs[q], out_n[q])) return CSTR_E_BADARG;
-        }
-    }
-    const unsigned grid = lane_grid(p->batch, 256, CSTR_PPO_MAX_BLOCKS);
-    unsigned long long *ws = reinterpret_cast<unsigned long long *>(workspace);
-    if (A == 2) ppo_loss_kernel<2><<<grid, 256, 0, (hipStream_t)stream>>>(*p, ws);
-    else ppo_loss_kernel<4><<<grid, 256, 0, (hipStream_t)stream>>>(*p, ws);
-    return (int)hipGetLastError();
+    return p ? diag_gaussian_loss_launch<true>(p, workspace, stream) : CSTR_E_BADARG;
 }
 
 extern "C" int cstr_grad_clip_f32(float *grad, int64_t n, float max_norm, uint64_t *workspace, float *norm_out, cstr_stream_t stream)

@@ -324,3 +324,44 @@ def test_predict_fixture_is_consistent(golden):
         assert np.array_equal(z64.argmax(axis=1), g["deterministic"][:, v])
         top = np.sort(z32, axis=1)
         assert ((top[:, -1] - top[:, -2]) > 1e-4 * np.abs(g["logits"]).max()).all()  # every row, per valve: the tests leave out none
+
+
+# ---- the arguments the four loss structs share: one table of bad values through all four entry points ------------------------------
+SHARED = dict(values=P(2), adv=P(4), returns=P(5), g_value=P(7), scalars_out=P(8), log_prob_out=null, batch=12, normalize_advantage=1,
+              ent_coef=0.0, vf_coef=0.5)
+PPO_ONLY = dict(old_values=null, old_log_prob=P(3), clip_range=0.2, clip_range_vf=-1.0, scalars_sum=null)
+GAUSSIAN = dict(mean=P(0), ldm=2, log_std=P(10), actions=P(1), act_dim=2, g_mean=P(6), g_log_std=P(11))
+LOSS_ENTRY_POINTS = {
+    "ppo": ("cstr_ppo_loss_f32", nv.PpoLoss, dict(SHARED, **PPO_ONLY, **GAUSSIAN)),
+    "a2c": ("cstr_a2c_loss_f32", nv.A2cLoss, dict(SHARED, **GAUSSIAN)),
+    "categorical": ("cstr_categorical_loss_f32", nv.CategoricalLoss,
+                    dict(SHARED, **PPO_ONLY, logits=P(0), ldz=16, actions=P(1), n_actions=9, levels=3, objective=0, g_logits=P(6))),
+    "multicategorical": ("cstr_multicategorical_loss_f32", nv.MultiCategoricalLoss,
+                         dict(SHARED, **PPO_ONLY, logits=P(0), ldz=8, actions=P(1), levels0=3, levels1=5, objective=0, g_logits=P(6))),
+}
+
+
+@pytest.mark.parametrize("entry", list(LOSS_ENTRY_POINTS))
+def test_loss_entry_points_agree_on_bad_shared_arguments(entry):
+    """every call fails a host-side check: none reaches a launch (the pointers are fake)"""
+    symbol, struct, base = LOSS_ENTRY_POINTS[entry]
+    fn = getattr(nv.lib(), symbol)
+
+    def loss(ws=P(9), **kw):
+        p = struct()
+        for k, v in dict(base, **kw).items():
+            setattr(p, k, v.value if isinstance(v, C.c_void_p) else v)
+        return fn(C.byref(p), ws, null)
+
+    assert loss(ws=null) == BAD
+    for name in ("values", "adv", "returns", "g_value"):  # each shared required pointer
+        assert loss(**{name: null}) == BAD, name
+    assert loss(ws=off(P(9), 4)) == BAD                   # the workspace holds 8-byte words
+    assert loss(g_value=P(2)) == BAD                      # g_value over values
+    assert loss(scalars_out=P(4)) == BAD                  # scalars_out over adv
+    assert loss(log_prob_out=P(7)) == BAD                 # log_prob_out over g_value
+    assert loss(ws=P(7)) == BAD and loss(ws=P(8)) == BAD  # the workspace over an output
+    assert loss(batch=(1 << 30) + 1) == UNSUP
+    if "scalars_sum" in base:
+        assert loss(scalars_sum=P(8)) == BAD              # scalars_sum over scalars_out
+        assert loss(old_log_prob=null) == BAD             # the PPO objective reads it
