@@ -1411,8 +1411,9 @@ def q_chain_bwd(nets, root: "nv.ChainRoot", w_in: int, obs_dim: int, h1: int, h2
 
 
 def chain_lean(on: int = -1) -> int:
-    """cstr_chain_lean: 0 = the generic Q chain kernels from now on, > 0 = the lean ones where they exist (the default), < 0 = query;
-    returns the setting before the call (both kernels write the same bits: tests/test_qchain_lean_bodies.py)."""
+    """cstr_chain_lean: 0 = the generic Q chain and actor forward chain kernels from now on, > 0 = the lean ones where they exist (the
+    default), < 0 = query; returns the setting before the call (both kernels write the same bits: tests/test_qchain_lean_bodies.py,
+    tests/test_actor_chain_lean_bodies.py)."""
     return int(nv.lib().cstr_chain_lean(C.c_int(on)))
 
 

@@ -293,6 +293,20 @@ struct L1Direct {
 #pragma unroll
         for (int i = 0; i < 4; ++i) wb[i] = l1_direct_quad<KIN>(w1, b1, min(16 * (wave + CH_WAVES * i) + r, h1 - 1), h, bias[i]);
     }
+    // the same values for whole-quad rows (KIN % 4 == 0) without a branch per lane: the quads beyond the row are the zeros of the
+    // descriptor's range check, so the requests stay in the caller's entry block
+    __device__ __forceinline__ void request_flat(const float *w1, const float *b1, const int h1)
+    {
+        static_assert(KIN % 4 == 0, "whole-quad rows only");
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, h = lane >> 4;
+        const __amdgpu_buffer_rsrc_t rw = rsrc_of(w1, (int64_t)h1 * KIN);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int n = min(16 * (wave + CH_WAVES * i) + r, h1 - 1);
+            bias[i] = b1[n];
+            wb[i] = ld128(rw, 4 * h < KIN ? 4 * (n * KIN + 4 * h) : BUF_OOB);
+        }
+    }
 };
 
 template <int KP, int KIN>
@@ -1463,6 +1477,198 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_bwd_kernel(const A
     CH_STAMP(3, 7);
 }
 
+// ---- the actor forward launch, lean (what cstr_sac_actor_chain_fwd_f32 launches at 256 x 256 unless cstr_chain_lean(0)) -----------
+// The same treatment as the lean Q launches above, for the kernel whose dependent chain starts at data the launch in front has just
+// written: the gather (idx[b], idx[B + b] -> the ring row -> LDS -> barrier 1). In the generic kernel those requests stand behind every
+// weight request and four scalar rounds (the 264-byte argument struct is read field by field), and a vmcnt(0) ties the ring row to
+// the weight loads. Here
+//   * what the first requests need are the leading 16 argument dwords (preloaded): they leave in front of every wait;
+//   * everything else is one struct, read as one batch of scalar loads;
+//   * the requests of the entry block are predicated (range-checked descriptors, clamped addresses), not branched around, so the
+//     compiler counts them: the ring row waits for the two indices only, its LDS store for the row only;
+//   * rows mode (PAIR), head width (2A), gather / packed input and noise drawn or not are compile-time.
+// No expression, MFMA operand, accumulator or summation order differs from the generic kernel. The actor BACKWARD launch got the same
+// treatment as an experiment (partials requested first, Gaussian head and bucket compile-time); its own launch was not shorter in the
+// graph, so it stays generic (profiles/actor_chain_lean_ab.txt, section 6).
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+
+struct ActorFwdLeanArgs {
+    const float *w1, *b1, *w2, *b2, *hw;
+    const float *ring_act, *ring_rew, *ring_done, *ring_timeout;
+    int64_t ring_rows; int64_t *ring_ctl; int advance_ring;
+    float *x_data, *out_done, *out_rew, *a_h1, *a_h2, *head_part, *eps_all;
+};
+
+// sac_actor_chain_fwd_kernel<D, A, NQ, 1> at CSTR_CHAIN_ROWS_PAIR with 2A head outputs and both kept activations; GATHER: the rows
+// come from the ring through idx (and column group 0 materialises the packed batch), else from x_pi / x_next; NOISE: eps_all is drawn
+template <int D, int A, int NQ, bool GATHER, bool NOISE>
+__global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_fwd_lean_kernel(const int batch, const unsigned n_envs, const int32_t *idx, const float *ring_obs,
+                                                                              const float *ring_next, float *x_pi, float *x_next, const uint64_t *rng_ctl,
+                                                                              const uint64_t rng_offset, const ActorFwdLeanArgs a)
+{
+    extern __shared__ __align__(16) float smem[];
+    constexpr int W = D + A, QPR = D / 4, WX = 1, HN = 2 * A;
+    static_assert(l1_pad<D>() == 0 && D % 4 == 0, "whole-quad observation rows");
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 15, h = lane >> 4;
+    constexpr int T = exact_tiles<NQ, WX>(), S = CH_WAVES / T;
+    const int tile = wave % T, ks = wave / T;
+    constexpr int H1 = exact_h1<WX>(), H2 = exact_h2<WX>();
+    const int B = batch, M = 2 * B;
+    const int n0 = (blockIdx.x * T + tile) * 16, m0 = blockIdx.y * 16;
+    float *xs = smem + SM_XS, *red = smem + SM_RED, *panel = smem + SM_PANEL;
+    constexpr int ld = H1 + 4;
+    float *w1s = panel + 16 * ld;
+    const bool col_ok = n0 + r < H2;
+    CH_STAMP(0, 0);
+    // (b) first: the row group's 16 input rows. Lane t < 16 QPR owns quad t % QPR of row t / QPR; 16 | B, so the row group lies on one
+    // side of the obs | next_obs boundary (next is uniform)
+    const bool gl = t < 16 * QPR, next = m0 >= B;
+    const int row = gl ? t / QPR : 0, qd = t % QPR;
+    const int b = (next ? m0 - B : m0) + row;
+    const bool mat = GATHER && blockIdx.x == 0;  // this workgroup also materialises the packed batch (stores at the end)
+    unsigned ir = 0, ie = 0;
+    u32x2 plo = {0u, 0u}, phi = plo;
+    if (GATHER) {
+        const __amdgpu_buffer_rsrc_t ri = rsrc_of(reinterpret_cast<const float *>(idx), 2 * (int64_t)B);
+        ir = __builtin_amdgcn_raw_buffer_load_b32(ri, gl ? 4 * b : BUF_OOB, 0, 0);
+        ie = __builtin_amdgcn_raw_buffer_load_b32(ri, gl ? 4 * (B + b) : BUF_OOB, 0, 0);
+    } else {
+        const __amdgpu_buffer_rsrc_t rx = rsrc_of(next ? x_next : x_pi, (int64_t)B * W);
+        plo = __builtin_amdgcn_raw_buffer_load_b64(rx, gl ? 4 * (b * W + 4 * qd) : BUF_OOB, 0, 0);
+        phi = __builtin_amdgcn_raw_buffer_load_b64(rx, gl ? 4 * (b * W + 4 * qd) + 8 : BUF_OOB, 0, 0);
+    }
+    // the Philox control words of the noise lanes (an otherwise idle wave): vector requests behind the indices, no scalar round
+    constexpr int PAIRS = (A + 1) / 2;
+    const bool noise = NOISE && blockIdx.x == 0 && wave == 3 && lane < 16 * PAIRS;
+    u32x2 c_seed = {0u, 0u}, c_ctr = c_seed;
+    if (NOISE) {
+        const __amdgpu_buffer_rsrc_t rc = rsrc_of(reinterpret_cast<const float *>(rng_ctl), 4);
+        c_seed = __builtin_amdgcn_raw_buffer_load_b64(rc, noise ? 0 : BUF_OOB, 0, 0);
+        c_ctr = __builtin_amdgcn_raw_buffer_load_b64(rc, noise ? 8 : BUF_OOB, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // everything else in one batch of scalar reads, here
+    const float *const w1 = a.w1, *const b1 = a.b1, *const w2 = a.w2, *const b2 = a.b2, *const hw = a.hw;
+    const float *const r_act = a.ring_act, *const r_rew = a.ring_rew, *const r_done = a.ring_done, *const r_timeout = a.ring_timeout;
+    const int64_t ring_rows = a.ring_rows;
+    int64_t *const ring_ctl = a.ring_ctl;
+    const int advance_ring = a.advance_ring;
+    float *const o_x_data = a.x_data, *const o_done = a.out_done, *const o_rew = a.out_rew, *const o_a_h1 = a.a_h1, *const o_a_h2 = a.a_h2;
+    float *const o_head_part = a.head_part, *const o_eps = a.eps_all;
+    asm volatile("" ::"s"(w1), "s"(b1), "s"(w2), "s"(b2), "s"(hw), "s"(o_a_h1), "s"(o_a_h2), "s"(o_head_part));
+    if (GATHER) asm volatile("" ::"s"(r_act), "s"(r_rew), "s"(r_done), "s"(r_timeout), "s"(ring_rows), "s"(ring_ctl), "s"(advance_ring), "s"(o_x_data), "s"(o_done), "s"(o_rew));
+    if (NOISE) asm volatile("" ::"s"(o_eps));
+    // (a) what depends on nothing: the wide layer's B operand, the epilogue's bias and head weights, W1
+    float4 bq[NQ];
+    load_b_fwd<NQ>(bq, w2, H2, H1, n0, ks, S);
+    const int col = min(n0 + r, H2 - 1);
+    const float bv = b2[col];
+    float hwv[HN];
+#pragma unroll
+    for (int j = 0; j < HN; ++j) hwv[j] = hw[(int64_t)j * H2 + col];
+    L1Direct<D> l1d;
+    l1d.request_flat(w1, b1, H1);
+    if (t >= 64 && t < 64 + 16 * (4 - QPR)) {  // the padding quads of xs: 1.0 in column D (the bias input), zeros behind it
+        const int i = t - 64, prow = i / (4 - QPR), pq = QPR + i % (4 - QPR);
+        *reinterpret_cast<float4 *>(xs + prow * 16 + 4 * pq) = make_float4(pq == QPR ? 1.0f : 0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    // the ring row behind the two indices (lanes without a row: ring row 0, a clamped address), then what only the stores at the end need
+    float4 v = make_float4(__uint_as_float(plo.x), __uint_as_float(plo.y), __uint_as_float(phi.x), __uint_as_float(phi.y));
+    float actv[A], dn = 0.0f, to = 0.0f, rw = 0.0f;
+#pragma unroll
+    for (int j = 0; j < A; ++j) actv[j] = 0.0f;
+    if (GATHER) {
+        const int64_t o = (int64_t)(int)ir * (int64_t)n_envs + (int)ie;
+        v = *reinterpret_cast<const float4 *>((next ? ring_next : ring_obs) + o * D + 4 * qd);
+        const int64_t od = (gl && mat && !next && qd == 0) ? o : 0;
+#pragma unroll
+        for (int j = 0; j < A; ++j) actv[j] = r_act[od * A + j];
+        dn = r_done[od]; to = r_timeout[od]; rw = r_rew[od];
+    }
+    if (gl) *reinterpret_cast<float4 *>(xs + row * 16 + 4 * qd) = v;
+    // the noise of the row group's sampling head: counter-based, independent of the network -- drawn while the gather is in flight,
+    // consumed by the Q chain launch that finalises the head (counter = offset + row of the 2B-row pass)
+    float e0 = 0.0f, e1 = 0.0f;
+    if (noise) {
+        const int nrow = lane / PAIRS, pr = lane % PAIRS;
+        const uint64_t seed = ((uint64_t)c_seed.y << 32) | c_seed.x, ctr = (((uint64_t)c_ctr.y << 32) | c_ctr.x) + rng_offset + (uint64_t)(m0 + nrow);
+        uint32_t rr[4];
+        philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)pr, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rr);
+        box_muller(rr[0], rr[1], e0, e1);
+    }
+    CH_STAMP(0, 1);
+    lds_barrier();
+    CH_STAMP(0, 2);
+    // (c) layer 1, recomputed by every workgroup of the row group -> panel
+    layer1_mfma<0, D>(xs, w1s, panel, ld, H1, &l1d, w1, b1);
+    lds_barrier();
+    CH_STAMP(0, 3);
+    // (d) layer 2: this wave's 16 x 16 tile (its share of K), (e) split-K combine
+    f32x4 acc = tile_mma<NQ>(panel, ld, H1, bq, ks, S);
+    CH_STAMP(0, 4);
+    acc = combine_split_k(acc, smem, T, S);
+    CH_STAMP(0, 5);
+    // (f) epilogue of the tile's first wave: bias + ReLU, head partials over these 16 columns
+    float hv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (wave < T) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
+#pragma unroll
+        for (int j = 0; j < HN; ++j) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float s = rowsum16(hv[e] * hwv[j]);
+                if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
+            }
+        }
+    }
+    lds_barrier();
+    CH_STAMP(0, 6);
+    if (t < 16 * HN) {
+        const int prow = t / HN, j = t % HN;
+        float s = red[prow * 8 + j];
+#pragma unroll
+        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + prow) * 8 + j];
+        o_head_part[((int64_t)blockIdx.x * M + m0 + prow) * HN + j] = s;
+    }
+    // ---- global stores, all behind the last barrier ----
+    const bool keep_rows = !next;  // the rows a backward follows
+    if (wave < T && col_ok && keep_rows) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o_a_h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
+    }
+    if (blockIdx.x == 0 && keep_rows) store_panel(panel, ld, o_a_h1, H1, m0);
+    if (noise) {
+        const int nrow = lane / PAIRS, pr = lane % PAIRS;
+        float *eo = o_eps + (int64_t)(m0 + nrow) * A + 2 * pr;
+        eo[0] = e0;
+        if (2 * pr + 1 < A) eo[1] = e1;
+    }
+    if (mat && gl) {  // the packed batch for the launches behind this one (cstr_linear_act_fwd_gather_f32's contract)
+        float *xo = (next ? x_next : x_pi) + (int64_t)b * W + 4 * qd;
+        reinterpret_cast<float2 *>(xo)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xo)[1] = make_float2(v.z, v.w);
+        if (!next) {
+            float *xd = o_x_data + (int64_t)b * W;
+            reinterpret_cast<float2 *>(xd + 4 * qd)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xd + 4 * qd)[1] = make_float2(v.z, v.w);
+            if (qd == 0) {
+#pragma unroll
+                for (int j = 0; j < A; ++j) xd[D + j] = actv[j];
+                o_done[b] = dn * (1.0f - to);  // buffers.py:322
+                o_rew[b] = rw;
+            }
+        }
+    }
+    if (GATHER && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {  // nobody reads these words in this launch
+        if (advance_ring) {  // ReplayBuffer.add's epilogue (buffers.py:280-283), left over by the rollout launch
+            int64_t pos = ring_ctl[0] + 1;
+            if (pos == ring_rows) { ring_ctl[1] = 1; pos = 0; }
+            ring_ctl[0] = pos;
+            ring_ctl[3] += 1;
+        }
+    }
+    CH_STAMP(0, 7);
+}
+
 // out[row][col] = sum over parts of part[p][row][col]: the consumer-side finalisation of a chain launch's partial sums for a consumer that
 // is NOT a chain kernel (MADDPG's per-layer actor backward reads d(loss)/d(action) from the action columns of a critic-input gradient)
 __global__ __launch_bounds__(256) void chain_sum_parts_kernel(const float *__restrict__ part, const int n_parts, const int64_t rows, const int cols,
@@ -1648,6 +1854,44 @@ bool q_bwd_lean_launch(const QBwdArgs &g, const int lay, const int wx, const int
     return true;
 }
 
+// ---- the lean actor forward launch's dispatch: SAC's 256 x 256 pass (2B rows, 2A head outputs); everything else runs the generic kernel ----
+template <int D, int A, int NQ, bool GATHER, bool NOISE>
+void actor_fwd_lean_go(const dim3 grid, const size_t lds, hipStream_t s, const ActorFwdArgs &g, const ActorFwdLeanArgs &a)
+{
+    sac_actor_chain_fwd_lean_kernel<D, A, NQ, GATHER, NOISE><<<grid, CH_THREADS, lds, s>>>(g.batch, (unsigned)g.ring.n_envs, g.idx, g.ring.obs, g.ring.next_obs, g.x_pi,
+                                                                                          g.x_next, g.head_rng_ctl, g.head_rng_offset, a);
+}
+template <int D, int A, int NQ, typename... Rest>
+void actor_fwd_lean_variant(const bool gather, const bool noise, Rest &&...rest)
+{
+    if (gather && noise) actor_fwd_lean_go<D, A, NQ, true, true>(rest...);
+    else if (gather) actor_fwd_lean_go<D, A, NQ, true, false>(rest...);
+    else if (noise) actor_fwd_lean_go<D, A, NQ, false, true>(rest...);
+    else actor_fwd_lean_go<D, A, NQ, false, false>(rest...);
+}
+template <int D, int A, typename... Rest>
+void actor_fwd_lean_nq(const int nq, Rest &&...rest)
+{
+    if (nq == 4) actor_fwd_lean_variant<D, A, 4>(rest...);
+    else if (nq == 8) actor_fwd_lean_variant<D, A, 8>(rest...);
+    else actor_fwd_lean_variant<D, A, 16>(rest...);
+}
+
+bool actor_fwd_lean_launch(const ActorFwdArgs &g, const int lay, const int wx, const int nq, const dim3 grid, const size_t lds, hipStream_t s)
+{
+    if (!chain_lean_enabled || wx != 1 || (lay != 0 && lay != 1)) return false;
+    if (g.rows_mode != CSTR_CHAIN_ROWS_PAIR || g.head_n != 2 * g.net.act_dim || !g.a_h1 || !g.a_h2) return false;
+    ActorFwdLeanArgs a = {};
+    a.w1 = g.net.w1; a.b1 = g.net.b1; a.w2 = g.net.w2; a.b2 = g.net.b2; a.hw = g.net.hw;
+    a.ring_act = g.ring.act; a.ring_rew = g.ring.rew; a.ring_done = g.ring.done; a.ring_timeout = g.ring.timeout;
+    a.ring_rows = g.ring.rows; a.ring_ctl = g.ring_ctl; a.advance_ring = g.advance_ring;
+    a.x_data = g.x_data; a.out_done = g.out_done; a.out_rew = g.out_rew; a.a_h1 = g.a_h1; a.a_h2 = g.a_h2; a.head_part = g.head_part; a.eps_all = g.eps_all;
+    const bool gather = g.idx != nullptr, noise = g.eps_all != nullptr;
+    if (lay == 0) actor_fwd_lean_nq<4, 2>(nq, gather, noise, grid, lds, s, g, a);
+    else actor_fwd_lean_nq<8, 2>(nq, gather, noise, grid, lds, s, g, a);
+    return true;
+}
+
 }  // namespace
 
 // ---- C ABI --------------------------------------------------------------------------------------------------------------------
@@ -1700,7 +1944,8 @@ extern "C" int cstr_sac_actor_chain_fwd_f32(const cstr_sac_actor_t *actor, const
     const int nq = nq_for(actor->h1, tiles, 32), lay = chain_layout(actor->obs_dim, actor->act_dim);
     if (!nq || lds > CHAIN_LDS_LIMIT) return CSTR_E_UNSUPPORTED;
     hipStream_t s = (hipStream_t)stream;
-    CHAIN_DISPATCH(sac_actor_chain_fwd_kernel, lay, chain_wx(actor->h1, actor->h2, tiles, nq), nq, grid, lds, s, a);
+    const int wx = chain_wx(actor->h1, actor->h2, tiles, nq);
+    if (!actor_fwd_lean_launch(a, lay, wx, nq, grid, lds, s)) CHAIN_DISPATCH(sac_actor_chain_fwd_kernel, lay, wx, nq, grid, lds, s, a);
     return (int)hipGetLastError();
 }
 
