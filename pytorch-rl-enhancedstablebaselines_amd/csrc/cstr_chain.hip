@@ -48,6 +48,13 @@ __device__ __forceinline__ float4 ld128(const __amdgpu_buffer_rsrc_t rs, const i
     return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
 }
 
+__device__ __forceinline__ float2 ld64(const __amdgpu_buffer_rsrc_t rs, const int byte_off)
+{
+    typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, byte_off, 0, 0);
+    return make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
+}
+
 __device__ __forceinline__ float ld32(const __amdgpu_buffer_rsrc_t rs, const int byte_off)
 {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(rs, byte_off, 0, 0));
@@ -69,6 +76,16 @@ __device__ unsigned long long chain_stamps[4 * 1024 * 4 * 8];  // [kernel][workg
         if ((threadIdx.x & 63) == 0 && wg_ < 1024) chain_stamps[(((K) * 1024 + wg_) * 4 + (threadIdx.x >> 6)) * 8 + (I)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define CH_STAMP(K, I) do { } while (0)
+#endif
+// -DCSTR_QFWD_FIN_STAMPS on top (diagnostic build): the lean Q forward with a pending head stamps its head finalisation INSTEAD of
+// its middle phases -- 3 the head's partial sums arrived | 4 the action is in xs | 5 the log-prob is done (tools/chain_stamps.py
+// FIN=1); V, a vector register the phase ends with, pins the stamp behind the wait for it
+#if defined(CSTR_CHAIN_STAMPS) && defined(CSTR_QFWD_FIN_STAMPS)
+#define CH_FIN_STAMPS true
+#define CH_STAMP_FIN(I, V) do { asm volatile("" ::"v"(V)); CH_STAMP(1, I); } while (0)
+#else
+#define CH_FIN_STAMPS false
+#define CH_STAMP_FIN(I, V) do { } while (0)
 #endif
 
 // LDS-only workgroup barrier: waits for this wave's LDS traffic (lgkmcnt), NOT for its outstanding global loads / stores -- the
@@ -221,15 +238,28 @@ __device__ __forceinline__ float PartBatch::sum() const
 
 // The SAC head's sampling arithmetic for ONE (row, action) (gaussian_head_gemm_fwd_kernel's expressions): mean, raw log_std, eps ->
 // action and this action's log-prob term (Normal log-pdf minus the tanh correction)
-__device__ __forceinline__ void sample_action(const float mu, const float raw, const float e, float &a, float &lp_term)
+// in two halves, so that a kernel whose critical path needs only the action can evaluate the log-prob term later (or not at all): the
+// action half hands sd and u on, the log-prob half is the rest of the expression, operand for operand
+__device__ __forceinline__ void sample_action_act(const float mu, const float raw, const float e, float &a, float &sd, float &u)
+{
+    const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
+    sd = expf(ls);
+    u = mu + sd * e;
+    a = tanhf(u);
+}
+
+__device__ __forceinline__ float sample_action_logp(const float mu, const float sd, const float u, const float a)
 {
     const float half_log_2pi = 0.91893853320467274178f;
-    const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
-    const float sd = expf(ls);
-    const float u = mu + sd * e;
-    a = tanhf(u);
     const float d = u - mu, var = sd * sd;
-    lp_term = (-(d * d) / (2.0f * var) - logf(sd) - half_log_2pi) - logf(1.0f - a * a + 1e-6f);
+    return (-(d * d) / (2.0f * var) - logf(sd) - half_log_2pi) - logf(1.0f - a * a + 1e-6f);
+}
+
+__device__ __forceinline__ void sample_action(const float mu, const float raw, const float e, float &a, float &lp_term)
+{
+    float sd, u;
+    sample_action_act(mu, raw, e, a, sd, u);
+    lp_term = sample_action_logp(mu, sd, u, a);
 }
 
 // ---- first layer of a chain on the matrix cores -----------------------------------------------------------------------------------
@@ -305,6 +335,24 @@ struct L1Direct {
             const int n = min(16 * (wave + CH_WAVES * i) + r, h1 - 1);
             bias[i] = b1[n];
             wb[i] = ld128(rw, 4 * h < KIN ? 4 * (n * KIN + 4 * h) : BUF_OOB);
+        }
+    }
+    // the same values for rows of 4 j + 2 inputs (obs 4 + act 2 = 6, 10: every critic), where request() branches per lane between a
+    // pair of W1, the bias behind the last input and zeros -- and the merge of those branches waits for EVERY request in flight,
+    // in the middle of the entry block: here a pair beyond the row or a bias slot of another lane is a range-checked zero
+    __device__ __forceinline__ void request_pairs(const float *w1, const float *b1, const int h1)
+    {
+        static_assert(KIN % 4 == 2, "rows of 4 j + 2 inputs only");
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r = lane & 15, h = lane >> 4;
+        const __amdgpu_buffer_rsrc_t rw = rsrc_of(w1, (int64_t)h1 * KIN), rb = rsrc_of(b1, h1);
+        const int k0 = 4 * h;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int n = min(16 * (wave + CH_WAVES * i) + r, h1 - 1);
+            const float2 lo = ld64(rw, k0 + 1 < KIN ? 4 * (n * KIN + k0) : BUF_OOB), hi = ld64(rw, k0 + 3 < KIN ? 4 * (n * KIN + k0 + 2) : BUF_OOB);
+            const float bk = ld32(rb, k0 + 2 == KIN ? 4 * n : BUF_OOB);
+            bias[i] = 0.0f;
+            wb[i] = make_float4(lo.x, lo.y, k0 + 2 == KIN ? bk : hi.x, hi.y);
         }
     }
 };
@@ -940,7 +988,10 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_kernel(const QBwdArgs 
 //     linear_bwd_weight_adam_sets_lean_kernel does); uniform values behind pointers (b3, ent_coef / log_alpha) ride in the vector
 //     queue behind the partials instead of a dependent scalar round;
 //   * loss mode, alpha / next_logp, the head's kind, the store set and the partial-sum bucket are template parameters chosen by the
-//     host, which instantiates what SAC, TD3, MADDPG and BCQ dispatch and sends everything else to the kernels above.
+//     host, which instantiates what SAC, TD3, MADDPG and BCQ dispatch and sends everything else to the kernels above;
+//   * the forward kernel requests everything in its entry block through range-checked descriptors, in the order of first use, so no
+//     wait in front of barrier 1 is a vmcnt(0); of a pending head it finalises only the action there, the log-probs and side stores
+//     behind the barriers (profiles/qfwd_fin_defer_ab.txt).
 // Partial sums keep the generic bucket of every n (PartBatch: n <= 8 the 8-register form, 9 .. 16 sum_parts_n<16>; the loss
 // workgroup: sum_parts' 4 / 8 / 16), i.e. the same adds in the same order over the same zero padding.
 template <int NP>
@@ -985,6 +1036,7 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_fwd_lean_kernel(const int 
 {
     extern __shared__ __align__(16) float smem[];
     constexpr int W = D + A, WX = 1;
+    constexpr bool FIN_STAMPS = CH_FIN_STAMPS && FIN != QF_PLAIN;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 15, h = lane >> 4;
     constexpr int T = exact_tiles<NQ, WX>(), S = CH_WAVES / T;
     const int tile = wave % T, ks = wave / T;
@@ -1003,59 +1055,85 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_fwd_lean_kernel(const int 
     const int role = FIN != QF_PLAIN ? (int)((roles >> (4 * blockIdx.z)) & 15u) : CSTR_CHAIN_ROLE_PLAIN;
     const bool nxt = role == CSTR_CHAIN_ROLE_NEXT || role == CSTR_CHAIN_ROLE_NEXT_STORE;
     const bool own = nxt || role == CSTR_CHAIN_ROLE_PI;
-    const bool fin_rows = own || (role == CSTR_CHAIN_ROLE_STORE_PI && blockIdx.x == 0);
-    const bool fin_lane = FIN != QF_PLAIN && fin_rows && t < 16 * A;
-    const int f_row = t / A, f_j = t % A;
+    // The head is finalised by 16 A lanes (one per (row, action)) of ONE wave -- FW: a wave that the head stage behind the split-K
+    // combine leaves idle where there is one (T < 4), so that what only later launches read (log-probs, params, the stored action
+    // columns) is worked out there, beside the head stage of the waves < T, from values the wave kept in registers. In front of
+    // barrier 1 stands only what the layer-1 input needs: the action, and only in the workgroups whose network reads it (`own`);
+    // the log-prob half exists only in the workgroups that store it (column group 0, not NEXT).
+    constexpr int FW = T < CH_WAVES ? CH_WAVES - 1 : 0;
+    const bool fin_store = FIN != QF_PLAIN && blockIdx.x == 0 && (role == CSTR_CHAIN_ROLE_STORE_PI || role == CSTR_CHAIN_ROLE_PI || role == CSTR_CHAIN_ROLE_NEXT_STORE);
+    const bool fin_lane = FIN != QF_PLAIN && (own || fin_store) && wave == FW && lane < 16 * A;
+    const int f_row = lane / A, f_j = lane % A;
     constexpr bool f_det = FIN == QF_DETERMINISTIC;
     PartBatchN<PB> p_mu, p_raw;
     float f_ev = 0.0f, f_hb_mu = 0.0f, f_hb_raw = 0.0f;
     constexpr int HN = f_det ? A : 2 * A;
     const int64_t f_i = (nxt ? fin_next_offset : 0) + m0 + f_row;  // row of the actor pass
     if (FIN != QF_PLAIN) {
+        // every request predicated, none branched around: they stay in the entry block, in front of the wait for the record below
         const int64_t pstride = (int64_t)fin_part_rows * HN, ptotal = pstride * fin_parts;
         p_mu.request(fin_head_part, fin_parts, pstride, f_i * HN + f_j, ptotal, fin_lane);
         if (!f_det) p_raw.request(fin_head_part, fin_parts, pstride, f_i * HN + A + f_j, ptotal, fin_lane);
+        const __amdgpu_buffer_rsrc_t re = rsrc_of(fin_eps, (int64_t)fin_part_rows * A), rh = rsrc_of(fin_hb, HN);
+        f_ev = ld32(re, (fin_lane && (!f_det || fin_eps)) ? (int)(4u * (unsigned)(f_i * A + f_j)) : BUF_OOB);
+        f_hb_mu = ld32(rh, fin_lane ? 4 * f_j : BUF_OOB);
+        if (!f_det) f_hb_raw = ld32(rh, fin_lane ? 4 * (A + f_j) : BUF_OOB);
     }
     // the whole record and the store pointers in one batch of scalar reads, here
     asm volatile("" ::"s"(net.w1), "s"(net.b1), "s"(net.w2), "s"(net.b2), "s"(net.w3), "s"(net.x), "s"(net.h1), "s"(net.h2), "s"(net.q_part));
     if (FIN != QF_PLAIN) asm volatile("" ::"s"(o_x_pi), "s"(o_x_next), "s"(o_params), "s"(o_logp_pi), "s"(o_logp_next));
-    if (fin_lane) {
-        f_ev = (!f_det || fin_eps) ? fin_eps[f_i * A + f_j] : 0.0f;
-        f_hb_mu = fin_hb[f_j];
-        f_hb_raw = f_det ? 0.0f : fin_hb[A + f_j];
-    }
-    // (a) requests that depend on nothing
+    // (a) requests that depend on nothing, in the order of their use: the input rows (barrier 1 waits for them) and W1 (layer 1), as
+    //     range-checked loads that need no branch, THEN the wide layer's operands, which stay in flight across barrier 1 and layer 1
+    const int x_row = t >> 4, x_k = t & 15;  // 256 threads = 16 x 16
+    const bool x_ld = x_k < W && !(own && x_k >= D);
+    const float x_in = ld32(rsrc_of(net.x, (int64_t)B * W), x_ld ? 4 * ((m0 + x_row) * W + x_k) : BUF_OOB);
+    stage_w1<W>(w1s, net.w1, net.b1, H1);
+    L1Direct<W> l1d;
+    if constexpr (W % 4 == 2) l1d.request_pairs(net.w1, net.b1, H1);  // (every lean instantiation: obs 4 or 8 + act 2)
+    else if (l1_pad<W>() == 0) l1d.request(net.w1, net.b1, H1);
     float4 bq[NQ];
     load_b_fwd<NQ>(bq, net.w2, H2, H1, n0, ks, S);
     const int col = min(n0 + r, H2 - 1);
     const float bv = net.b2[col];
     const float w3v = col_ok ? net.w3[col] : 0.0f;
-    stage_w1<W>(w1s, net.w1, net.b1, H1);
-    L1Direct<W> l1d;
-    if (l1_pad<W>() == 0) l1d.request(net.w1, net.b1, H1);
-    // (b) input rows; the pending head's action columns finalised here (q_chain_fwd_kernel's roles)
-    {
-        const int row = t >> 4, k = t & 15;
-        float xv = k == W ? 1.0f : 0.0f;
-        if (k < W && !(own && k >= D)) xv = net.x[(int64_t)(m0 + row) * W + k];
-        if (!(own && k >= D && k < W)) xs[row * 16 + k] = xv;
-    }
-    float f_mu = 0.0f, f_raw = 0.0f, f_a = 0.0f, f_lp = 0.0f;
-    if (fin_lane) {
-        const float ev = f_ev;
+    // (b) input rows (the inputs, 1.0 = the bias input, zeros); the pending head's action columns of an `own` network are finalised
+    //     here (q_chain_fwd_kernel's roles)
+    if (!(own && x_k >= D && x_k < W)) xs[x_row * 16 + x_k] = x_ld ? x_in : (x_k == W ? 1.0f : 0.0f);
+    float f_mu = 0.0f, f_raw = 0.0f, f_a = 0.0f, f_sd = 0.0f, f_u = 0.0f;
+    const auto fin_action = [&]() {  // sums of the partials and the action half
         f_mu = p_mu.sum() + f_hb_mu;
+        CH_STAMP_FIN(3, f_mu);
         if (f_det) {
             f_a = tanhf(f_mu);
-            if (nxt) f_a = fminf(fmaxf(f_a + fminf(fmaxf(ev * fin_sigma, -fin_clip), fin_clip), -1.0f), 1.0f);
+            if (nxt) f_a = fminf(fmaxf(f_a + fminf(fmaxf(f_ev * fin_sigma, -fin_clip), fin_clip), -1.0f), 1.0f);
         } else {
             f_raw = p_raw.sum() + f_hb_raw;
-            float term;
-            sample_action(f_mu, f_raw, ev, f_a, term);
-            f_lp = term;
-            if (A >= 2) f_lp += __shfl_xor(f_lp, 1, 64);
-            if (A == 4) f_lp += __shfl_xor(f_lp, 2, 64);
+            sample_action_act(f_mu, f_raw, f_ev, f_a, f_sd, f_u);
         }
-        if (own) xs[f_row * 16 + D + f_j] = f_a;
+    };
+    // what later launches read, by the workgroups that store it: the log-prob half, the row's sum over its (adjacent) lanes, the stores
+    const auto fin_deferred = [&]() {
+        if (fin_lane && fin_store) {
+            if (!own) fin_action();  // STORE_PI: a side job, nothing of it is read in this launch
+            const int bb = m0 + f_row;
+            (nxt ? o_x_next : o_x_pi)[(int64_t)bb * W + D + f_j] = f_a;
+            if (!f_det) {
+                if (!nxt) {
+                    o_params[(int64_t)bb * 2 * A + f_j] = f_mu;
+                    o_params[(int64_t)bb * 2 * A + A + f_j] = f_raw;
+                }
+                float f_lp = sample_action_logp(f_mu, f_sd, f_u, f_a);
+                if (A >= 2) f_lp += __shfl_xor(f_lp, 1, 64);
+                if (A == 4) f_lp += __shfl_xor(f_lp, 2, 64);
+                CH_STAMP_FIN(5, f_lp);
+                if (f_j == 0) (nxt ? o_logp_next : o_logp_pi)[bb] = f_lp;
+            }
+        }
+    };
+    if (fin_lane && own) {
+        fin_action();
+        xs[f_row * 16 + D + f_j] = f_a;
+        CH_STAMP_FIN(4, f_a);
     }
     CH_STAMP(1, 1);
     lds_barrier();
@@ -1063,12 +1141,13 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_fwd_lean_kernel(const int 
     // (c) layer 1 recomputed on the matrix cores
     layer1_mfma<l1_pad<W>(), W>(xs, w1s, panel, ld, H1, &l1d, net.w1, net.b1);
     lds_barrier();
-    CH_STAMP(1, 3);
+    if (!FIN_STAMPS) CH_STAMP(1, 3);
     f32x4 acc = tile_mma<NQ>(panel, ld, H1, bq, ks, S);
-    CH_STAMP(1, 4);
+    if (!FIN_STAMPS) CH_STAMP(1, 4);
     acc = combine_split_k(acc, smem, T, S);
-    CH_STAMP(1, 5);
+    if (!FIN_STAMPS) CH_STAMP(1, 5);
     float hv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (FW != 0 && wave == FW) fin_deferred();  // beside the head stage of the waves < T
     if (wave < T) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -1097,15 +1176,7 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_fwd_lean_kernel(const int 
         for (int e = 0; e < 4; ++e) net.h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
     }
     if (blockIdx.x == 0 && net.h1) store_panel(panel, ld, net.h1, H1, m0);
-    if (fin_lane && blockIdx.x == 0 && role != CSTR_CHAIN_ROLE_NEXT) {
-        const int bb = m0 + f_row;
-        (nxt ? o_x_next : o_x_pi)[(int64_t)bb * W + D + f_j] = f_a;
-        if (!nxt && !f_det) {
-            o_params[(int64_t)bb * 2 * A + f_j] = f_mu;
-            o_params[(int64_t)bb * 2 * A + A + f_j] = f_raw;
-        }
-        if (f_j == 0 && !f_det) (nxt ? o_logp_next : o_logp_pi)[bb] = f_lp;
-    }
+    if (FW == 0) fin_deferred();  // no idle wave (T == 4): behind the head stage and the stores above
     CH_STAMP(1, 7);
 }
 
