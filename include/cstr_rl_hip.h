@@ -898,7 +898,20 @@ int cstr_grad_clip_f32(float *grad, int64_t n, float max_norm, uint64_t *workspa
  * lr is a DEVICE scalar (f64), as for cstr_adam_f32. max_norm > 0: two launches -- the sum-of-squares pass of cstr_grad_clip_f32
  * (same grid, same partials), then coef = min(1, max_norm / (norm + 1e-6)), the clipped gradient written back to grad and the step;
  * the result is bit-identical to cstr_grad_clip_f32 followed by the unclipped call. workspace is required, norm_out (optional)
- * receives the norm before clipping. max_norm <= 0: coef = 1, one launch, grad is not written, workspace and norm_out may be NULL. */
+ * receives the norm before clipping. max_norm <= 0: coef = 1, one launch, grad is not written, workspace and norm_out may be NULL.
+ * cstr_rmsprop_tf_f32: RMSpropTFLike (core/common/sb2_compat/rmsprop_tf_like.py:90-135; square_avg is initialised to ONES by the
+ * caller, epsilon is added inside the square root) over one flat arena, same launch shape, same folded clip, same lr / workspace /
+ * norm_out conventions as cstr_rmsprop_f32. momentum_buf is given iff momentum > 0, grad_avg iff the centred form is wanted; the up
+ * to five arenas are 16-byte-aligned and disjoint; alpha, eps, weight_decay, momentum >= 0. The form (weight decay != 0, centred,
+ * momentum > 0) selects one of eight kernel bodies, each touching only the arenas it has. Per element, every operation rounded to
+ * f32, the scalars converted once ((float)alpha, (float)(1 - alpha), (float)eps, (float)weight_decay, (float)momentum, (float)(-lr)):
+ *   g' = g * coef                                  (written back to grad when max_norm > 0, before weight decay)
+ *   weight decay:  g' = g' + wd * param
+ *                  sq = sq * alpha + ((1 - alpha) * g') * g'
+ *   centred:       ga = ga * alpha + (1 - alpha) * g';  avg = sqrtf((sq - ga * ga) + eps)     (NaN where that sum is negative)
+ *   otherwise:     avg = sqrtf(sq + eps)
+ *   momentum:      buf = buf * momentum + g' / avg;     param = param + (-lr) * buf
+ *   otherwise:     param = param + ((-lr) * g') / avg */
 typedef struct {
     const float *mean;         /* [batch][ldm], act_dim columns used */
     int64_t ldm;
@@ -918,6 +931,9 @@ typedef struct {
 int cstr_a2c_loss_f32(const cstr_a2c_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
 int cstr_rmsprop_f32(float *param, float *grad, float *square_avg, const double *lr, double alpha, double eps, float max_norm,
                      uint64_t *workspace, float *norm_out, int64_t n, cstr_stream_t stream);
+int cstr_rmsprop_tf_f32(float *param, float *grad, float *square_avg, float *momentum_buf /* NULL iff momentum == 0 */,
+                        float *grad_avg /* NULL iff !centered */, const double *lr, double alpha, double eps, double weight_decay,
+                        double momentum, float max_norm, uint64_t *workspace, float *norm_out, int64_t n, cstr_stream_t stream);
 
 /* ---- DQN on the discrete valve face: exploration draw, action selection, target + gather + Huber loss (core/dqn/dqn.py:168-256) -----
  * Same conventions as the PPO block: f32 data, host-side validation (NULL, non-positive sizes, misaligned or overlapping rows ->

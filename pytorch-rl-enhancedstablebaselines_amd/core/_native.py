@@ -38,7 +38,7 @@ SYMBOLS = (
     "cstr_bcq_latent_fwd_f32", "cstr_bcq_vae_loss_f32", "cstr_bcq_latent_bwd_f32", "cstr_bcq_expand_f32", "cstr_bcq_perturb_fwd_f32",
     "cstr_bcq_perturb_bwd_f32", "cstr_bcq_target_f32", "cstr_bcq_select_f32",
     "cstr_diag_gaussian_act_f32", "cstr_rollout_add_f32", "cstr_gae_f32", "cstr_ppo_gather_f32", "cstr_ppo_loss_f32", "cstr_grad_clip_f32",
-    "cstr_a2c_loss_f32", "cstr_rmsprop_f32",
+    "cstr_a2c_loss_f32", "cstr_rmsprop_f32", "cstr_rmsprop_tf_f32",
     "cstr_mt19937_rand_flag_f64", "cstr_dqn_act_f32", "cstr_dqn_loss_f32",
     "cstr_eval_episodes_f32",
     "cstr_categorical_act_f32", "cstr_categorical_loss_f32",

@@ -7,6 +7,9 @@ weight-gradient sums. The launches of a step: policy forward, value forward, ONE
 `loss.backward()` (:150-171, hip_ops.a2c_loss: the four scalars and d loss / d (action mean, value, log_std)), the backward with one
 deferred weight-gradient launch, and `FlatRMSprop.step(max_norm=...)`, which folds clip_grad_norm_ into the optimiser's two launches.
 `use_rms_prop=False` runs the same path with FlatAdam (eps 1e-5) behind hip_ops.grad_clip. Nothing synchronises with the host.
+`policy_kwargs=dict(optimizer_class=RMSpropTFLike, optimizer_kwargs=dict(eps=1e-5))` (core.common.sb2_compat.rmsprop_tf_like, the
+original A2C's optimiser) takes the same path and the same number of launches through `FlatRMSpropTFLike.step(max_norm=...)`, in all
+its forms (weight decay, momentum, centred).
 Another optimiser class, or widths the kernels decline, run the reference's own torch statements on the arena parameters
 (`fused_learner` False, `rollout_buffer.get(None)` included); they are also the tests' reference.
 
@@ -18,7 +21,7 @@ On a Discrete valve face the policy has a Categorical head and the loss launch i
 on a MultiDiscrete one (`CSTRVecEnv(multi_discrete_actions=(K0, K1))`) a MultiCategorical head, one categorical per valve, and the loss
 launch is hip_ops.multicategorical_loss (csrc/cstr_multicategorical.hip).
 
-Not built: RMSpropTFLike, gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN / dict policies."""
+Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN / dict policies."""
 from typing import Optional, Union
 
 import numpy as np
@@ -27,7 +30,7 @@ from torch.nn import functional as F
 
 from core.a2c.policies import MlpPolicy
 from core.common import fused, hip_ops
-from core.common.arena import FlatRMSprop
+from core.common.arena import FlatRMSprop, FlatRMSpropTFLike
 from core.common.buffers import RolloutBuffer
 from core.common.logger import DeviceMean
 from core.common.on_policy_algorithm import OnPolicyAlgorithm
@@ -36,7 +39,7 @@ from core.common.spaces import Discrete, MultiDiscrete
 
 class A2C(OnPolicyAlgorithm):
     policy_aliases = {"MlpPolicy": MlpPolicy}
-    flat_rmsprop = True  # torch.optim.RMSprop in the form below becomes arena.FlatRMSprop
+    flat_rmsprop = True  # torch.optim.RMSprop in the form below becomes arena.FlatRMSprop, RMSpropTFLike arena.FlatRMSpropTFLike
 
     def __init__(self, policy, env, learning_rate=7e-4, n_steps: int = 5, gamma: float = 0.99, gae_lambda: float = 1.0,
                  ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5, rms_prop_eps: float = 1e-5,
@@ -119,7 +122,7 @@ class A2C(OnPolicyAlgorithm):
         with fused.deferred_weight_grads():
             th.autograd.backward([mean, values], [b["g_mean"], b["g_value"]])
         opt = pol.optimizer
-        if isinstance(opt, FlatRMSprop):
+        if isinstance(opt, (FlatRMSprop, FlatRMSpropTFLike)):
             opt.step(max_norm=self.max_grad_norm, workspace=self._ws, norm_out=self._grad_norm)
         else:
             hip_ops.grad_clip(pol.arena.grad, self.max_grad_norm, self._ws, self._grad_norm)

@@ -1,7 +1,7 @@
 """Flat parameter arenas: the learner-side HBM layout.
 
 Each optimiser group (actor, critic, ...) owns ONE contiguous fp32 buffer for its parameters, one for its
-gradients and two for the Adam moments (one for RMSprop's square average); a target network owns a buffer with the identical layout. The
+gradients and two for the Adam moments (one to three for the RMSprop forms' averages); a target network owns a buffer with the identical layout. The
 nn.Module parameters are views into the arena, `.grad`s are views into the gradient buffer, so:
 
   * `polyak_update` over a whole network is one HIP launch on two flat buffers
@@ -19,6 +19,7 @@ import torch as th
 from torch import nn
 
 from core.common import hip_ops
+from core.common.sb2_compat.rmsprop_tf_like import RMSpropTFLike
 
 _ALIGN = 64  # floats (256 B)
 
@@ -350,11 +351,102 @@ class FlatRMSprop:
         self.sync_lr()
 
 
+class FlatRMSpropTFLike:
+    """`sb2_compat.RMSpropTFLike` (square_avg starts at ones, epsilon inside the square root; weight decay, momentum and centred forms)
+    over one `ParamArena`, learning rate resident in HBM: hip_ops.rmsprop_tf. `momentum_buf` / `grad_avg` exist only in the forms that
+    use them. `step(max_norm=...)` folds clip_grad_norm_ in, as FlatRMSprop's does. The state_dict is the class's own layout (`step` a
+    Python int, `momentum_buffer` / `grad_avg` where the form has them), which is what the reference's `policy.optimizer.pth` holds."""
+
+    def __init__(self, arena: ParamArena, lr: float = 1e-2, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0,
+                 momentum: float = 0, centered: bool = False):
+        RMSpropTFLike([th.zeros(1)], lr, alpha, eps, weight_decay, momentum, centered)  # the class's own ValueErrors
+        self.arena = arena
+        self.defaults = dict(lr=lr, momentum=momentum, alpha=alpha, eps=eps, centered=centered, weight_decay=weight_decay)
+        self.param_groups = [dict(params=arena.params, **self.defaults)]
+        self.square_avg = th.ones_like(arena.flat)
+        self.momentum_buf = th.zeros_like(arena.flat) if momentum > 0 else None
+        self.grad_avg = th.zeros_like(arena.flat) if centered else None
+        self.lr_dev = th.tensor([lr], dtype=th.float64, device=arena.device)
+        self._lr_on_device = float(lr)
+        self._steps = 0
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        self.arena.zero_grad()
+
+    def sync_lr(self) -> None:
+        """Push `param_groups[0]["lr"]` (set by update_learning_rate) to HBM; a constant schedule never copies."""
+        lr = float(self.param_groups[0]["lr"])
+        if lr != self._lr_on_device:
+            self.lr_dev.fill_(lr)
+            self._lr_on_device = lr
+
+    def step(self, closure=None, max_norm: Optional[float] = None, workspace: Optional[th.Tensor] = None,
+             norm_out: Optional[th.Tensor] = None) -> None:
+        """max_norm > 0: th.nn.utils.clip_grad_norm_(parameters, max_norm) first, in the same two launches (FlatRMSprop.step)"""
+        g = self.param_groups[0]  # the form is fixed at construction: hip_ops refuses a momentum that has no buffer
+        with th.cuda.device(self.arena.device):
+            hip_ops.rmsprop_tf(self.arena.flat, self.arena.grad, self.square_avg, self.lr_dev, g["alpha"], g["eps"], g["weight_decay"],
+                               g["momentum"], self.momentum_buf, self.grad_avg, max_norm, workspace, norm_out)
+        self._steps += 1
+
+    @property
+    def step_count(self) -> int:
+        return self._steps
+
+    def _buffers(self) -> list:
+        return [(k, b) for k, b in (("square_avg", self.square_avg), ("momentum_buffer", self.momentum_buf), ("grad_avg", self.grad_avg))
+                if b is not None]
+
+    def state_dict(self) -> dict:
+        state = {}
+        for i, p in enumerate(self.arena.input_params):  # torch.optim indexes parameters in the order they were given
+            o = self.arena.offset_of[id(p)]
+            state[i] = {"step": self._steps, **{k: b[o:o + p.numel()].view(p.shape).clone() for k, b in self._buffers()}}
+        g = self.param_groups[0]
+        group = {"lr": float(g["lr"]), "momentum": g["momentum"], "alpha": g["alpha"], "eps": g["eps"], "centered": g["centered"],
+                 "weight_decay": g["weight_decay"], "params": list(range(len(self.arena.input_params)))}
+        return {"state": state if self._steps > 0 else {}, "param_groups": [group]}
+
+    def load_state_dict(self, sd: dict) -> None:
+        state = sd.get("state", {})
+        names = {k for k, _ in self._buffers()}
+        entries, steps = [], set()
+        for i, p in enumerate(self.arena.input_params):  # validated before anything is written
+            st = state.get(i, state.get(str(i)))
+            if st is None:
+                continue
+            have = {k for k in ("square_avg", "momentum_buffer", "grad_avg") if k in st}
+            if names - have:
+                raise ValueError(f"FlatRMSpropTFLike (momentum {self.defaults['momentum']}, centered {self.defaults['centered']}): "
+                                 f"the checkpoint has no {sorted(names - have)} for parameter {i}")
+            if have - names:
+                raise ValueError(f"FlatRMSpropTFLike (momentum {self.defaults['momentum']}, centered {self.defaults['centered']}): "
+                                 f"the checkpoint holds {sorted(have - names)}, which this form does not keep")
+            entries.append((p, st))
+            steps.add(int(float(st["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"FlatRMSpropTFLike needs one common step count, checkpoint has {sorted(steps)}")
+        self.square_avg.fill_(1.0)
+        for b in (self.momentum_buf, self.grad_avg):
+            if b is not None:
+                b.zero_()
+        for p, st in entries:
+            o = self.arena.offset_of[id(p)]
+            for k, b in self._buffers():
+                b[o:o + p.numel()].view(p.shape).copy_(st[k])
+        self._steps = steps.pop() if steps else 0
+        groups = sd.get("param_groups") or [{}]
+        if "lr" in groups[0]:
+            self.param_groups[0]["lr"] = float(groups[0]["lr"])
+        self.sync_lr()
+
+
 def make_optimizer(module_params: Iterable[nn.Parameter], device, lr: float, optimizer_class=None,
                    optimizer_kwargs: Optional[dict] = None, groups: Optional[list] = None, extra_grad: int = 0, flat_rmsprop: bool = False):
     """Default (optimizer_class None or torch.optim.Adam with default kwargs) -> arena + FlatAdam. flat_rmsprop (only A2C asks):
-    torch.optim.RMSprop with kwargs within {alpha, eps, weight_decay=0, momentum=0, centered=False} -> arena + FlatRMSprop. Any other
-    optimiser class is honoured with the stock torch implementation on the arena's parameter views."""
+    torch.optim.RMSprop with kwargs within {alpha, eps, weight_decay=0, momentum=0, centered=False} -> arena + FlatRMSprop, and
+    sb2_compat.RMSpropTFLike with kwargs within {alpha, eps, weight_decay, momentum, centered} -> arena + FlatRMSpropTFLike. Any other
+    optimiser class is honoured with its own implementation on the arena's parameter views."""
     optimizer_kwargs = dict(optimizer_kwargs or {})
     arena = ParamArena(module_params, device, groups=groups, extra_grad=extra_grad)
     if optimizer_class in (None, th.optim.Adam) and set(optimizer_kwargs) <= {"betas", "eps"}:
@@ -362,4 +454,6 @@ def make_optimizer(module_params: Iterable[nn.Parameter], device, lr: float, opt
     if flat_rmsprop and optimizer_class is th.optim.RMSprop and set(optimizer_kwargs) <= {"alpha", "eps", "weight_decay", "momentum", "centered"} \
             and not optimizer_kwargs.get("weight_decay") and not optimizer_kwargs.get("momentum") and not optimizer_kwargs.get("centered"):
         return arena, FlatRMSprop(arena, lr=lr, **optimizer_kwargs)
+    if flat_rmsprop and optimizer_class is RMSpropTFLike and set(optimizer_kwargs) <= {"alpha", "eps", "weight_decay", "momentum", "centered"}:
+        return arena, FlatRMSpropTFLike(arena, lr=lr, **optimizer_kwargs)
     return arena, optimizer_class(arena.params, lr=lr, **optimizer_kwargs)

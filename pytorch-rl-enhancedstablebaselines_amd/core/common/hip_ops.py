@@ -1607,6 +1607,29 @@ def rmsprop(param, grad, square_avg, lr_dev, alpha: float = 0.99, eps: float = 1
                                     C.c_int64(n), stream_ptr()), "cstr_rmsprop_f32")
 
 
+def rmsprop_tf(param, grad, square_avg, lr_dev, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0.0, momentum: float = 0.0,
+               momentum_buf=None, grad_avg=None, max_norm: Optional[float] = None, workspace=None, norm_out=None):
+    """RMSpropTFLike (square_avg starts at ones, epsilon inside the square root) over one flat arena. momentum_buf iff momentum > 0,
+    grad_avg iff the centred form. The clip is hip_ops.rmsprop's: max_norm > 0 folds clip_grad_norm_ in (two launches, the clipped
+    gradient is written back); None or <= 0: one launch, the gradient is only read."""
+    n = param.numel()
+    for t, nm in ((param, "param"), (grad, "grad"), (square_avg, "square_avg")):
+        _chk(t, nm, (n,), th.float32)
+    _opt(momentum_buf, "momentum_buf", (n,), th.float32), _opt(grad_avg, "grad_avg", (n,), th.float32)
+    if (momentum_buf is not None) != (momentum > 0):
+        raise ValueError("rmsprop_tf: momentum_buf goes with momentum > 0")
+    _chk(lr_dev, "lr", (1,), th.float64)
+    clip = max_norm is not None and max_norm > 0
+    if clip:
+        _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+        if norm_out is not None:
+            _vec(norm_out, "norm_out", 1)
+    check(nv.lib().cstr_rmsprop_tf_f32(ptr(param), ptr(grad), ptr(square_avg), ptr(momentum_buf), ptr(grad_avg), ptr(lr_dev), C.c_double(alpha),
+                                       C.c_double(eps), C.c_double(weight_decay), C.c_double(momentum), C.c_float(max_norm if clip else 0.0),
+                                       ptr(workspace if clip else None), ptr(norm_out if clip else None), C.c_int64(n), stream_ptr()),
+          "cstr_rmsprop_tf_f32")
+
+
 # ---- DQN on the discrete valve face: exploration draw, action selection, target + gather + Huber loss (csrc/cstr_dqn.hip) -----------
 def dqn_supported(n_actions: int, levels: int) -> bool:
     return 2 <= levels <= nv.DQN_MAX_LEVELS and n_actions == levels * levels

@@ -242,9 +242,9 @@ class ActorCriticPolicy(BasePolicy):
                                                     flat_rmsprop=flat_rmsprop)
 
     def flat_optimizers(self) -> list:
-        from core.common.arena import FlatAdam, FlatRMSprop
+        from core.common.arena import FlatAdam, FlatRMSprop, FlatRMSpropTFLike
 
-        return [self.optimizer] if isinstance(self.optimizer, (FlatAdam, FlatRMSprop)) else []
+        return [self.optimizer] if isinstance(self.optimizer, (FlatAdam, FlatRMSprop, FlatRMSpropTFLike)) else []
 
     # ---- the reference's statements on the arena parameters ----------------------------------------------------------
     def _get_action_dist_from_latent(self, latent_pi: th.Tensor):

@@ -4,7 +4,12 @@ core/common/base_class.py:666-888): `data` (JSON), `<name>.pth` per state dict (
 
 Safe by construction: tensors are read with `torch.load(weights_only=True)`, `data` with `json`; entries the
 reference serialised with cloudpickle (`":serialized:"`) are never unpickled -- they are skipped (gymnasium spaces,
-schedules and policy classes are rebuilt from the constructor arguments instead)."""
+schedules and policy classes are rebuilt from the constructor arguments instead). A class inside a stored argument is written by
+name, `{":class:": "module.QualName"}`, and only for the classes of `_NAMED_CLASSES`; reading resolves a name through that table
+alone, never through an import of what the file says.
+
+A reference archive whose `policy_kwargs` holds a class keeps the whole dict under `":serialized:"`, which is skipped: pass
+`policy_kwargs=` to `load()` for such a file."""
 import io
 import json
 import os
@@ -15,9 +20,19 @@ import numpy as np
 import torch as th
 
 
+def _named_classes() -> dict:
+    """{"module.QualName": class} of the classes that may appear inside stored constructor arguments"""
+    from core.common.sb2_compat.rmsprop_tf_like import RMSpropTFLike
+
+    return {f"{c.__module__}.{c.__qualname__}": c for c in (RMSpropTFLike,)}
+
+
 def _jsonable(v: Any):
     if isinstance(v, (bool, int, float, str)) or v is None:
         return v
+    if isinstance(v, type):
+        name = f"{v.__module__}.{v.__qualname__}"
+        return {":class:": name} if _named_classes().get(name) is v else _SKIP
     if isinstance(v, (np.integer, np.floating)):
         return v.item()
     if isinstance(v, (list, tuple)):
@@ -41,9 +56,21 @@ def data_to_json(data: dict) -> str:
     return json.dumps(out, indent=4)
 
 
+def _with_classes(v: Any):
+    """`{":class:": name}` -> the class of that name in `_named_classes()` (an unknown name is an error, not an import)"""
+    if isinstance(v, dict):
+        if set(v) == {":class:"}:
+            known = _named_classes()
+            if v[":class:"] not in known:
+                raise ValueError(f"the archive names the class {v[':class:']!r}, which is not one of {sorted(known)}")
+            return known[v[":class:"]]
+        return {k: _with_classes(x) for k, x in v.items()}
+    return [_with_classes(x) for x in v] if isinstance(v, list) else v
+
+
 def json_to_data(text: str) -> dict:
     raw = json.loads(text)
-    return {k: v for k, v in raw.items() if not (isinstance(v, dict) and ":serialized:" in v)}
+    return {k: _with_classes(v) for k, v in raw.items() if not (isinstance(v, dict) and ":serialized:" in v)}
 
 
 def save_to_zip_file(path, data: Optional[dict], params: Optional[dict], pytorch_variables: Optional[dict], version: str) -> None:

@@ -15,6 +15,8 @@ On a MultiDiscrete valve face (`CSTRVecEnv(multi_discrete_actions=(K0, K1))`) it
 valve over K0 + K1 logits: csrc/cstr_multicategorical.hip (hip_ops.multicategorical_act / multicategorical_loss), the buffer's action
 row is the level pair as two floats.
 
+Another optimiser class (`RMSpropTFLike` included: its flat kernel form is A2C's alone) runs as itself on the arena's parameter views.
+
 Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN / dict policies."""
 import warnings
 from typing import Optional, Union

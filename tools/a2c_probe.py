@@ -2,9 +2,11 @@
 """A2C on the MI355X, class defaults (n_steps 5, RMSprop, nets [64, 64]): ABI calls and milliseconds per iteration (eager launches;
 A2C has no hipGraph replay), the gradient step with the buffer evaluated in place next to what `get(None)` alone would add to it
 (host permutation, its H2D copy, the gather launch), and the fused clip + RMSprop step against cstr_grad_clip_f32 followed by the
-unclipped step on the policy's own arena.
+unclipped step on the policy's own arena. Then train() under three optimisers: FlatRMSprop (the default), FlatRMSpropTFLike
+(optimizer_class=RMSpropTFLike, eps 1e-5) and RMSpropTFLike itself on the arena's parameter views (a subclass of it, which
+make_optimizer treats as any foreign class: the torch-statement path, get(None) included, one ATen launch per tensor and operation).
 
-An ABI call is one kernel launch, except the clipped RMSprop step and the gradient clip, which are two each.
+An ABI call is one kernel launch, except the clipped RMSprop steps and the gradient clip, which are two each.
 
 usage:
   a2c_probe.py [--envs 4096] [--iterations 200]
@@ -93,3 +95,30 @@ if __name__ == "__main__":
     print(f"  train()        : {ms_train:.4f} ms in place ({c2 - c1} ABI calls); get(None) alone, which it does not call: {ms_get:.4f} ms "
           "(host permutation, H2D copy, 1 gather launch)")
     print(f"  clip + RMSprop : fused {ms_fused * 1e3:.2f} us (2 launches), cstr_grad_clip_f32 + unclipped step {ms_sep * 1e3:.2f} us (3 launches)")
+    # train() under the three optimisers, each model warmed up by three iterations of its own, alternating inside this process
+    from core.common.sb2_compat.rmsprop_tf_like import RMSpropTFLike
+
+    class ForeignRMSpropTFLike(RMSpropTFLike):
+        """not `RMSpropTFLike` itself, so it runs as any optimiser class a caller passes does"""
+
+    def build(pk):
+        m = A2C("MlpPolicy", CSTRVecEnv(args.envs), seed=0, policy_kwargs=pk)
+        _, c = m._setup_learn(10 ** 9, None)
+        for _ in range(3):
+            m.collect_rollouts(m.env, c, m.rollout_buffer, m.n_steps)
+            m.train()
+        return m
+
+    tf_kw = dict(optimizer_kwargs=dict(eps=1e-5))
+    models = [("FlatRMSprop (default)", model), ("FlatRMSpropTFLike", build(dict(optimizer_class=RMSpropTFLike, **tf_kw))),
+              ("RMSpropTFLike on the arena views", build(dict(optimizer_class=ForeignRMSpropTFLike, **tf_kw)))]
+    times = {name: [] for name, _ in models}
+    for _ in range(5):
+        for name, m in models:
+            times[name].append(timed(m.train, reps))
+    print("  train() by optimiser             optimizer class                fused_learner  ABI calls  ms per train()")
+    for name, m in models:
+        c0 = nv.ABI_CALLS[0]
+        m.train()
+        calls = nv.ABI_CALLS[0] - c0
+        print(f"  {name:<32s} {type(m.policy.optimizer).__name__:<30s} {str(m.fused_learner):<14s} {calls:<10d} {med(times[name]):.4f}")

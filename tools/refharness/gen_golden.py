@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,ppo_discrete,a2c_discrete,ppo_multidiscrete,a2c_multidiscrete,init,vecenv,callbacks]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,ppo_discrete,a2c_discrete,ppo_multidiscrete,a2c_multidiscrete,init,vecenv,callbacks,rmsprop_tf]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -18,6 +18,7 @@ Reference entry points exercised (file:line in /root/reference):
   core/bcq/bcq.py:129-213                BCQ.train; core/bcq/policies.py:426-435 BCQPolicy._predict
   core/ppo/ppo.py:184-300                PPO.train; core/common/on_policy_algorithm.py:162-268 collect_rollouts
   core/a2c/a2c.py:132-190                A2C.train
+  core/common/sb2_compat/rmsprop_tf_like.py:78-137  RMSpropTFLike.step (--only rmsprop_tf)
   core/dqn/dqn.py:168-256                DQN._on_step / train / predict
   core/her/her_replay_buffer.py:135-408  HerReplayBuffer.add / sample / truncate_last_trajectory (--only her)
   core/common/utils.py:457-481           polyak_update
@@ -1481,7 +1482,8 @@ class _A2cHooks(_PpoHooks):
                     grad_norm=np.float32(float(norm)))
 
 
-def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, iterations=2, opt_state=True, venv=None, **kw):
+def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, iterations=2, opt_state=True, venv=None,
+             policy_kwargs=None, **kw):
     """`iterations` consecutive teacher-forceable A2C iterations of the reference on the CPU (rollout, train, rollout, train: the
     second step meets a non-zero square_avg): _setup_learn, THEN the step counters of the envs in `late` are set near the time limit."""
     from core.a2c.a2c import A2C
@@ -1489,6 +1491,8 @@ def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=
     from core.common.utils import obs_as_tensor
 
     pk = {} if net_arch is None else dict(policy_kwargs=dict(net_arch=net_arch))
+    if policy_kwargs:  # e.g. the optimiser class and its kwargs (gen_rmsprop_tf)
+        pk = dict(policy_kwargs=dict(pk.get("policy_kwargs", {}), **policy_kwargs))
     model = A2C("MlpPolicy", _make_venv(n_envs) if venv is None else venv, seed=seed, device="cpu", n_steps=n_steps, learning_rate=lr,
                 ent_coef=ent_coef, **pk, **kw)
     model.set_logger(Logger(folder=None, output_formats=[]))
@@ -1537,6 +1541,11 @@ def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=
         if opt_state and isinstance(model.policy.optimizer, th.optim.RMSprop):
             for name, p_ in zip(names, model.policy.optimizer.param_groups[0]["params"]):
                 out[f"{pre}opt/square_avg/{name}"] = st[p_]["square_avg"].numpy().copy()
+        elif opt_state and type(model.policy.optimizer).__name__ == "RMSpropTFLike":
+            for name, p_ in zip(names, model.policy.optimizer.param_groups[0]["params"]):
+                for key in ("square_avg", "momentum_buffer", "grad_avg"):
+                    if key in st[p_]:
+                        out[f"{pre}opt/{key}/{name}"] = st[p_][key].numpy().copy()
     arch = net_arch if net_arch is not None else [64, 64]
     out.update(seed=np.int64(seed), n_envs=np.int64(n_envs), n_steps=np.int64(n_steps), iterations=np.int64(iterations),
                net_arch=np.array(arch, np.int64), gamma=np.float64(model.gamma), gae_lambda=np.float64(model.gae_lambda),
@@ -1596,6 +1605,69 @@ def gen_a2c():
         elif k.split("/")[-1] not in ("eps", "last_obs", "logged_keys", "logged_values"):
             slim[k] = v
     save("a2c_train_kat_default.npz", **slim)
+
+
+# ------------------------------------------------------------------------------ RMSpropTFLike
+RMSPROP_TF_FORMS = (("plain", {}), ("a2c", dict(eps=1e-5)), ("momentum", dict(momentum=0.9)), ("centered", dict(centered=True)),
+                    ("centered_momentum", dict(centered=True, momentum=0.9)), ("weight_decay", dict(weight_decay=1e-2)))
+
+
+def gen_rmsprop_tf():
+    """rmsprop_tf_kat.npz: three steps of the reference's RMSpropTFLike (core/common/sb2_compat/rmsprop_tf_like.py:78-137) in six forms
+    on two tensors of 257 and 1024 elements (shared initial values and gradients, magnitudes 1e-6 .. 1), every state tensor after
+    each step. a2c_tflike_train_kat_small.npz / a2c_tflike_train_kat_variants.npz: two consecutive teacher-forceable A2C iterations
+    (as gen_a2c's small fixture) with optimizer_class=RMSpropTFLike, optimizer_kwargs eps=1e-5, and with momentum=0.9, centered=True
+    on [16, 16] nets."""
+    from core.common.sb2_compat.rmsprop_tf_like import RMSpropTFLike
+
+    rng = np.random.default_rng(20260417)
+    sizes = (257, 1024)
+    out = {"sizes": np.array(sizes, np.int64), "forms": np.array([f for f, _ in RMSPROP_TF_FORMS]), "steps": np.int64(3)}
+    for i, n in enumerate(sizes):
+        out[f"param0/w{i}"] = rng.uniform(-1.5, 1.5, n).astype(np.float32)
+        for k in range(3):
+            out[f"grad{k}/w{i}"] = (10.0 ** rng.uniform(-6, 0, n) * rng.choice([-1.0, 1.0], n)).astype(np.float32)
+    for form, kw in RMSPROP_TF_FORMS:
+        ps = [th.nn.Parameter(th.tensor(out[f"param0/w{i}"])) for i in range(len(sizes))]
+        opt = RMSpropTFLike(ps, **kw)
+        g0 = opt.param_groups[0]
+        for key in ("lr", "alpha", "eps", "weight_decay", "momentum"):
+            out[f"{form}/{key}"] = np.float64(g0[key])
+        out[f"{form}/centered"] = np.bool_(g0["centered"])
+        for k in range(3):
+            for i, p in enumerate(ps):
+                p.grad = th.tensor(out[f"grad{k}/w{i}"])
+            opt.step()
+            for i, p in enumerate(ps):
+                st = opt.state[p]
+                assert isinstance(st["step"], int) and st["step"] == k + 1
+                assert set(st) == {"step", "square_avg"} | ({"momentum_buffer"} if g0["momentum"] > 0 else set()) | \
+                    ({"grad_avg"} if g0["centered"] else set())
+                out[f"{form}/step{k}/param/w{i}"] = p.detach().numpy().copy()
+                for key in st:
+                    if key != "step":
+                        out[f"{form}/step{k}/{key}/w{i}"] = st[key].numpy().copy()
+        assert all(np.isfinite(out[f"{form}/step2/param/w{i}"]).all() for i in range(len(sizes)))
+    save("rmsprop_tf_kat.npz", **out)
+    late = ((1, 396), (2, 399), (3, 392))
+    for name, net_arch, okw in (("small", [32, 32], dict(eps=1e-5)), ("variants", [16, 16], dict(eps=1e-5, momentum=0.9, centered=True))):
+        pk = dict(optimizer_class=RMSpropTFLike, optimizer_kwargs=okw)
+        for seed in range(7, 60):
+            model, o = _a2c_run(seed, n_envs=4, net_arch=net_arch, late=late, policy_kwargs=pk)
+            norms = [float(o[f"it{k}/grad_norm"]) for k in range(2)]
+            trunc = [int(o[f"it{k}/timeouts"].sum()) for k in range(2)]
+            if min(norms) > 1.05 * 0.5 and min(trunc) >= 1:
+                break
+        else:
+            raise RuntimeError(f"no seed met the conditions of the {name} RMSpropTFLike A2C fixture")
+        assert str(o["optimizer"]) == "RMSpropTFLike" and int(o["it1/optimizer_steps"]) == 2
+        assert float(np.abs(o["it0/opt/square_avg/log_std"] - 1).max()) > 0  # the second step meets a square_avg that has moved off ones
+        assert ("it1/opt/momentum_buffer/log_std" in o) == ("momentum" in okw) and ("it1/opt/grad_avg/log_std" in o) == ("centered" in okw)
+        for key, v in okw.items():
+            o[f"optimizer_kwargs/{key}"] = np.float64(v)
+        print(f"a2c tflike {name}: seed {seed}, gradient norms {norms}, truncations {trunc}")
+        save(f"a2c_tflike_train_kat_{name}.npz", **o)
+
 
 # ------------------------------------------------------------------------------ DQN on the discretised valve face
 def _valve(q, K):
@@ -2265,7 +2337,8 @@ def gen_her():
 
 GENS = {"her": gen_her, "her_learners": gen_her_learners, "ppo_multidiscrete": gen_ppo_multidiscrete, "a2c_multidiscrete": gen_a2c_multidiscrete, "ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
-        "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn}
+        "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn,
+        "rmsprop_tf": gen_rmsprop_tf}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
