@@ -1133,6 +1133,36 @@ int cstr_her_sample_f32(const cstr_coef_t *coef, const cstr_ring_t *ring, const 
                         float *out_obs, float *out_act, float *out_next_obs, float *out_done, float *out_rew, int64_t *out_row_idx,
                         int64_t *out_env_idx, int64_t *out_goal_row, int32_t *status, cstr_stream_t stream);
 
+/* Whole evaluation episodes on the GOAL face in ONE launch: cstr_eval_episodes_f32's structure (a workgroup owns 16 envs and walks
+ * their vec-steps inside the launch, a lane of wave 0 per env carries the episode state, workgroups exchange nothing) with, per vec-step:
+ *   network input: the flat row [achieved_goal | desired_goal | observation] (6 floats, net->k0 = 6) that cstr_goal_vec_step_f32 writes:
+ *     achieved_goal = observation[2], desired_goal = 2 (target - s_lo[2]) / s_span[2] - 1, constant within an episode; network stages,
+ *     both head forms and predict()'s post-processing as in cstr_eval_episodes_f32;
+ *   env step: the dynamics of cstr_vec_step_f32 on the (4, 2) layout, reward = the goal reward on (achieved goal of the next state, the
+ *     OLD desired goal); NaN action or state: old state, -10, truncated, as in cstr_goal_vec_step_f32;
+ *   episode end, in this order: the accounting slot, the PCG64 reset draw, and -- if episode != NULL -- the target redraw of
+ *     cstr_goal_vec_step_f32 (Philox4x32-10 word 0, key goal_seed, counter (goal_index_offset + env index [64 bit], episode[env], tag
+ *     0x90A17A67), u = (x >> 8) * 2^-24, target = goal_lo + (goal_hi - goal_lo) * u) followed by episode[env] += 1.
+ * Arguments as in cstr_eval_episodes_f32 (obs_dim = 4 implied: env_obs [N][4]) plus
+ *   target float[N] i/o: raw setpoint per env;  episode int32[N] i/o or NULL (NULL: targets stay)
+ *   three OPTIONAL per-episode outputs laid out like ep_return ([N][ep_stride], slots at and beyond targets[i] not written):
+ *     ep_goal float: the episode's desired_goal (normalised)
+ *     ep_gap float: achieved_goal - desired_goal of the episode's TERMINAL row (columns 0 and 1 of the next_rows row that
+ *                   cstr_goal_vec_step_f32 would have written on the last step), one f32 subtraction
+ *     ep_abs_gap double: the f64 sum, in step order, of (double)fabsf(achieved - desired) over the next_rows of all the episode's steps
+ * For the counted episodes every output, pcg_state, env_obs, step_count, target and episode are bit-identical to the step-by-step
+ * launches: cstr_policy_rows_fwd_f32 on the flat rows (head 0: eps = 0), the post-processing, cstr_goal_vec_step_f32. An env stops once
+ * it has met its target: its state after its last counted episode (the reset draw and the target redraw behind that episode included)
+ * is what the launch leaves.
+ * CSTR_E_BADARG: NULL required pointers, n_envs <= 0, a negative target, max_vec_steps <= 0, net->k0 != 6, goal_lo > goal_hi when
+ * episode is given, misaligned rows, outputs overlapping inputs or each other; CSTR_E_UNSUPPORTED: net->act_dim != 2, unknown
+ * integrator, a network shape cstr_policy_rows_fwd_f32 does not take or more than 64 KB of LDS. All checked before anything is enqueued. */
+int cstr_eval_goal_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, float *env_obs, int32_t *step_count,
+                                uint64_t *pcg_state, double *static_init, float *target, int32_t *episode, uint64_t goal_seed,
+                                int64_t goal_index_offset, float goal_lo, float goal_hi, int squashed, const float *act_low,
+                                const float *act_high, const int32_t *targets, int64_t n_envs, int64_t max_vec_steps, double *ep_return,
+                                int32_t *ep_len, int32_t *ep_done, float *ep_goal, float *ep_gap, double *ep_abs_gap, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

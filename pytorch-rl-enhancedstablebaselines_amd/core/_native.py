@@ -44,6 +44,7 @@ SYMBOLS = (
     "cstr_categorical_act_f32", "cstr_categorical_loss_f32",
     "cstr_multicategorical_act_f32", "cstr_multicategorical_loss_f32",
     "cstr_goal_vec_step_f32", "cstr_her_add_f32", "cstr_her_sample_f32",
+    "cstr_eval_goal_episodes_f32",
 )
 
 

@@ -276,8 +276,8 @@ class EvalCallback(EventCallback):
     training (reference: callbacks.py:341-540).
 
     `fused` (specific to this package): None = `evaluate_policy_fused` (the whole evaluation in one launch) where
-    `core.common.evaluation.supported` says it applies, else `evaluate_policy`; False = always `evaluate_policy`; True = raise if
-    unsupported."""
+    `core.common.evaluation.supported` says it applies (the Box faces, and HER models on the goal face), else `evaluate_policy`;
+    False = always `evaluate_policy`; True = raise if unsupported."""
 
     def __init__(self, eval_env, callback_on_new_best: Optional[BaseCallback] = None, callback_after_eval: Optional[BaseCallback] = None,
                  n_eval_episodes: int = 5, eval_freq: int = 10000, log_path: Optional[str] = None,

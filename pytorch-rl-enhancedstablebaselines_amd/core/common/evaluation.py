@@ -12,7 +12,9 @@ returns = float64 sums of the float32 step rewards, episodes appended in sub-env
 
 `evaluate_policy_fused` (specific to this package) runs the same evaluation as ONE launch, cstr_eval_episodes_f32: every env's
 episodes are walked inside the kernel and the host reads three arrays back. It covers deterministic evaluation of a two-hidden-layer
-actor on a bare `CSTRVecEnv`; `supported()` tells whether it applies.
+actor on a bare `CSTRVecEnv`; `supported()` tells whether it applies. On the goal face (`goal_conditioned=True`, SAC / TD3 / DDPG on
+"MultiInputPolicy") the launch is cstr_eval_goal_episodes_f32, and `evaluate_goal_tracking` returns what it knows per episode beyond the
+return: the setpoint that was drawn, how far C2 ended from it and the mean absolute gap on the way.
 """
 import warnings
 from typing import Callable, Optional, Tuple, Union
@@ -24,6 +26,11 @@ from torch import nn
 from core.common import hip_ops
 from core.common.vec_env import CSTRVecEnv
 from core.common.vec_env.base_vec_env import VecEnv
+
+
+_MONITOR_WARNING = ("Evaluation environment is not wrapped with a ``Monitor`` wrapper. "
+                    "This may result in reporting modified episode lengths and rewards, if other wrappers happen to modify these. "
+                    "Consider wrapping environment first with ``Monitor`` wrapper.")
 
 
 def _device_post(policy, dev):
@@ -102,12 +109,7 @@ def evaluate_policy(model, env, n_eval_episodes: int = 10, deterministic: bool =
     if not isinstance(env, VecEnv) and not isinstance(getattr(env, "unwrapped", None), CSTRVecEnv):
         raise ValueError("evaluate_policy: pass a VecEnv of this package (CSTRVecEnv, optionally wrapped in VecNormalize)")
     if warn:  # no Monitor / VecMonitor wrapper exists in this stack: the reference's warning always applies (evaluation.py:64-70)
-        warnings.warn(
-            "Evaluation environment is not wrapped with a ``Monitor`` wrapper. "
-            "This may result in reporting modified episode lengths and rewards, if other wrappers happen to modify these. "
-            "Consider wrapping environment first with ``Monitor`` wrapper.",
-            UserWarning,
-        )
+        warnings.warn(_MONITOR_WARNING, UserWarning)
     n = env.num_envs
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype="int")  # :79-82
     policy = getattr(model, "policy", model)
@@ -130,7 +132,8 @@ def evaluate_policy(model, env, n_eval_episodes: int = 10, deterministic: bool =
 
 # What `EvalCallback(fused=None)` picks where `supported()` holds. Decided by measurement (tools/eval_probe.py, profiles/eval_probe.txt,
 # DESIGN.md 5): the launch is the default because it is faster than the device loop at both probed env counts (4.3 ms against 98.5 ms
-# with 16 evaluation envs, 5.6 ms against 93.4 ms with 256).
+# with 16 evaluation envs, 5.6 ms against 93.4 ms with 256; on the goal face, tools/goal_eval_probe.py, profiles/goal_eval_probe.txt: 4.7 ms
+# against 87.2 ms and 6.0 ms against 87.5 ms).
 FUSED_BY_DEFAULT = True
 
 _ACTS = {nn.ReLU: 1, nn.Tanh: 2}
@@ -147,11 +150,12 @@ def _two_layer_mlp(seq):
 
 
 def _fused_operands(policy) -> Optional[dict]:
-    """The policy's deterministic actor as operands of hip_ops.eval_episodes (cstr_policy_mlp_t), or None if that struct cannot
-    describe it: SAC's actor without gSDE (head 0 at its mode), TD3's / DDPG's actor (head 1, tanh), `ActorCriticPolicy` with a
-    two-layer `policy_net` and a linear `action_net` (head 1, no output activation, clipped instead of un-scaled)."""
+    """The policy's deterministic actor as operands of hip_ops.eval_episodes / goal_eval_episodes (cstr_policy_mlp_t), or None if that
+    struct cannot describe it: SAC's actor without gSDE (head 0 at its mode), TD3's / DDPG's actor (head 1, tanh), `ActorCriticPolicy`
+    with a two-layer `policy_net` and a linear `action_net` (head 1, no output activation, clipped instead of un-scaled). `goal`: the
+    actor sits behind a `CombinedExtractor` (MultiInputPolicy of SAC / TD3 / DDPG), i.e. its rows are the goal face's flat rows."""
     from core.common.policies import ActorCriticPolicy
-    from core.common.torch_layers import FlattenExtractor
+    from core.common.torch_layers import CombinedExtractor, FlattenExtractor
 
     actor = getattr(policy, "actor", None)
     if isinstance(policy, ActorCriticPolicy):
@@ -161,9 +165,10 @@ def _fused_operands(policy) -> Optional[dict]:
         if net is None or not isinstance(policy.action_net, nn.Linear):
             return None
         l1, l2, act = net
-        return dict(layers=(l1, l2), w3=policy.action_net.weight, b3=policy.action_net.bias, act=act, head=1, out_act=0)
-    if not isinstance(actor, nn.Module) or not isinstance(getattr(actor, "features_extractor", None), FlattenExtractor):
+        return dict(layers=(l1, l2), w3=policy.action_net.weight, b3=policy.action_net.bias, act=act, head=1, out_act=0, goal=False)
+    if not isinstance(actor, nn.Module) or not isinstance(getattr(actor, "features_extractor", None), (FlattenExtractor, CombinedExtractor)):
         return None
+    goal = isinstance(actor.features_extractor, CombinedExtractor)
     if isinstance(getattr(actor, "latent_pi", None), nn.Sequential):  # SAC
         if getattr(actor, "use_sde", False) or not isinstance(actor.mu, nn.Linear) or not isinstance(actor.log_std, nn.Linear):
             return None
@@ -172,7 +177,7 @@ def _fused_operands(policy) -> Optional[dict]:
             return None
         l1, l2, act = net
         return dict(layers=(l1, l2), w3=th.cat((actor.mu.weight, actor.log_std.weight), dim=0), b3=th.cat((actor.mu.bias, actor.log_std.bias), dim=0),
-                    act=act, head=0, out_act=0)
+                    act=act, head=0, out_act=0, goal=goal)
     if isinstance(getattr(actor, "mu", None), nn.Sequential):  # TD3 / DDPG: create_mlp(..., squash_output=True)
         mods = list(actor.mu)
         if len(mods) != 6 or not isinstance(mods[4], nn.Linear) or not isinstance(mods[5], nn.Tanh):
@@ -181,7 +186,7 @@ def _fused_operands(policy) -> Optional[dict]:
         if net is None:
             return None
         l1, l2, act = net
-        return dict(layers=(l1, l2), w3=mods[4].weight, b3=mods[4].bias, act=act, head=1, out_act=2)
+        return dict(layers=(l1, l2), w3=mods[4].weight, b3=mods[4].bias, act=act, head=1, out_act=2, goal=goal)
     return None
 
 
@@ -200,10 +205,16 @@ def _why_not_fused(model, env, deterministic: bool) -> Optional[str]:
     ops = _fused_operands(policy)
     if ops is None:
         return f"{type(policy).__name__}: the actor is not a two-hidden-layer MLP that cstr_policy_mlp_t describes (gSDE, other depths, BCQ, MADDPG)"
+    if ops["goal"] != env.goal_conditioned:
+        return ("a goal-face model (MultiInputPolicy) on an env without goal_conditioned=True" if ops["goal"]
+                else "a Box-face model on the goal face (goal_conditioned=True needs a MultiInputPolicy)")
     l1, l2 = ops["layers"]
-    if not hip_ops.eval_episodes_supported(l1.in_features, l1.out_features, l2.out_features, ops["w3"].shape[0], ops["head"], env.act_dim):
+    k0 = hip_ops.GOAL_ROW if ops["goal"] else env.obs_dim  # the goal face's flat row [achieved | desired | observation]
+    shape_ok = (hip_ops.goal_eval_episodes_supported(l1.out_features, l2.out_features, ops["w3"].shape[0], ops["head"]) if ops["goal"] else
+                hip_ops.eval_episodes_supported(l1.in_features, l1.out_features, l2.out_features, ops["w3"].shape[0], ops["head"], env.act_dim))
+    if not shape_ok:
         return f"network shape ({l1.in_features}, {l1.out_features}, {l2.out_features}, {ops['w3'].shape[0]}) on a ({env.obs_dim}, {env.act_dim}) env"
-    if l1.in_features != env.obs_dim or l1.weight.device != env.device:
+    if l1.in_features != k0 or l1.weight.device != env.device:
         return "policy and env disagree on the observation width or the device"
     return None
 
@@ -218,21 +229,11 @@ def _aligned(t: th.Tensor) -> th.Tensor:
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
-def evaluate_policy_fused(model, env, n_eval_episodes: int = 10, deterministic: bool = True, reward_threshold: Optional[float] = None,
-                          return_episode_rewards: bool = False, warn: bool = True) -> Union[Tuple[float, float], Tuple[list, list]]:
-    """`evaluate_policy` as ONE launch (hip_ops.eval_episodes): same arguments minus `render` / `callback`, same return values, the
-    episode lists in the reference's order -- sorted by (vec-step at which the episode ended, env index). Raises ValueError where
-    `supported()` is False."""
-    why = _why_not_fused(model, env, deterministic)
-    if why is not None:
-        raise ValueError(f"evaluate_policy_fused does not cover {why}; use evaluate_policy")
-    if warn:
-        warnings.warn(
-            "Evaluation environment is not wrapped with a ``Monitor`` wrapper. "
-            "This may result in reporting modified episode lengths and rewards, if other wrappers happen to modify these. "
-            "Consider wrapping environment first with ``Monitor`` wrapper.",
-            UserWarning,
-        )
+def _launch(model, env, n_eval_episodes: int, tracking: bool = False):
+    """The one launch behind `evaluate_policy_fused` / `evaluate_goal_tracking` on a supported (model, env): resets the env, runs every
+    env's episodes and returns (order, arrays) -- the reference's episode order as (env, slot) pairs
+    (an episode is appended at the vec-step it ends, sub-environments in order within a vec-step: evaluation.py:99-126) and the launch's
+    per-episode arrays on the host: (ep_return, ep_len) and, with `tracking` on the goal face, (ep_goal, ep_gap, ep_abs_gap) behind them."""
     n = env.num_envs
     targets = np.array([(n_eval_episodes + i) // n for i in range(n)], dtype="int")  # :79-82
     policy = getattr(model, "policy", model)
@@ -242,18 +243,64 @@ def evaluate_policy_fused(model, env, n_eval_episodes: int = 10, deterministic: 
     with th.no_grad(), th.cuda.device(env.device):
         w1, w2, w3 = _aligned(l1.weight), _aligned(l2.weight), _aligned(ops["w3"])
         b1, b2, b3 = l1.bias.detach().contiguous(), l2.bias.detach().contiguous(), ops["b3"].detach().contiguous()
-        ep_ret, ep_len, _ = hip_ops.eval_episodes(
-            w1, b1, w2, b2, w3, b3, ops["act"], ops["head"], ops["out_act"], hip_ops.policy_swizzle(w2), env.coef, env.integrator, env.obs,
-            env.step_count, env.pcg_state, policy.squash_output, np.asarray(policy.action_space.low, np.float32),
-            np.asarray(policy.action_space.high, np.float32), targets, int(targets.max()) * int(env.coef.max_steps), static_init=env.static_init)
-        ret_h, len_h = ep_ret.cpu().numpy(), ep_len.cpu().numpy()  # (the wrapper has read ep_done back and checked it against the targets)
-    # the reference appends an episode at the vec-step it ends, sub-environments in order within a vec-step (evaluation.py:99-126)
-    order = sorted((int(len_h[i, :j + 1].sum()), i, j) for i in range(n) for j in range(int(targets[i])))
-    rets = [float(ret_h[i, j]) for _, i, j in order]
-    lens = [int(len_h[i, j]) for _, i, j in order]
+        net = (w1, b1, w2, b2, w3, b3, ops["act"], ops["head"], ops["out_act"], hip_ops.policy_swizzle(w2), env.coef, env.integrator)
+        low, high = np.asarray(policy.action_space.low, np.float32), np.asarray(policy.action_space.high, np.float32)
+        max_vec_steps = int(targets.max()) * int(env.coef.max_steps)
+        if ops["goal"]:  # the launch advances obs / step_count / pcg_state / targets / episode in place, as step_device does
+            lo_g, hi_g = env.goal_range if env.goal_range is not None else (0.0, 0.0)
+            out = hip_ops.goal_eval_episodes(*net, env.obs, env.step_count, env.pcg_state, env.targets, policy.squash_output, low, high, targets,
+                                             max_vec_steps, static_init=env.static_init, episode=env.episode, goal_seed=env.goal_seed,
+                                             goal_index_offset=env.seed_offset, goal_lo=lo_g, goal_hi=hi_g, tracking=tracking)
+            env._refresh_flat(redraw=False)  # the flat rows of the state the launch left
+        else:
+            out = hip_ops.eval_episodes(*net, env.obs, env.step_count, env.pcg_state, policy.squash_output, low, high, targets, max_vec_steps,
+                                        static_init=env.static_init)
+        arrays = [t.cpu().numpy() for t in out[:2] + out[3:]]  # (the wrapper has read ep_done back and checked it against the targets)
+    len_h = arrays[1]
+    order = [(i, j) for _, i, j in sorted((int(len_h[i, :j + 1].sum()), i, j) for i in range(n) for j in range(int(targets[i])))]
+    return order, arrays
+
+
+def evaluate_policy_fused(model, env, n_eval_episodes: int = 10, deterministic: bool = True, reward_threshold: Optional[float] = None,
+                          return_episode_rewards: bool = False, warn: bool = True) -> Union[Tuple[float, float], Tuple[list, list]]:
+    """`evaluate_policy` as ONE launch (hip_ops.eval_episodes; on the goal face hip_ops.goal_eval_episodes): same arguments minus `render` /
+    `callback`, same return values, the episode lists in the reference's order -- sorted by (vec-step at which the episode ended, env
+    index). Raises ValueError where `supported()` is False."""
+    why = _why_not_fused(model, env, deterministic)
+    if why is not None:
+        raise ValueError(f"evaluate_policy_fused does not cover {why}; use evaluate_policy")
+    if warn:
+        warnings.warn(_MONITOR_WARNING, UserWarning)
+    order, (ret_h, len_h) = _launch(model, env, n_eval_episodes)
+    rets = [float(ret_h[i, j]) for i, j in order]
+    lens = [int(len_h[i, j]) for i, j in order]
     mean_reward, std_reward = np.mean(rets), np.std(rets)
     if reward_threshold is not None:
         assert mean_reward > reward_threshold, "Mean reward below threshold: " f"{mean_reward:.2f} < {reward_threshold:.2f}"
     if return_episode_rewards:
         return rets, lens
     return mean_reward, std_reward
+
+
+def evaluate_goal_tracking(model, env, n_eval_episodes: int = 10, warn: bool = True) -> dict:
+    """Setpoint tracking of a goal-face model, from the same launch as `evaluate_policy_fused` (deterministic actions) with its three
+    per-episode tracking outputs. Returns float64 / int arrays with one entry per episode, in the reference's episode order:
+      episode_rewards, episode_lengths -- what `evaluate_policy_fused(..., return_episode_rewards=True)` returns;
+      target          -- the episode's setpoint in mol/L: the launch's normalised desired goal g through the inverse of the env's affine
+                         map in float64, s_lo[2] + (g + 1) s_span[2] / 2;
+      final_error     -- C2 - setpoint in mol/L at the episode's terminal observation (signed): the launch's float32 gap times s_span[2] / 2;
+      mean_abs_error  -- mean over the episode's steps of |C2 - setpoint| in mol/L, each step's next observation against the episode's setpoint.
+    Raises ValueError where `supported(model, env)` is False or the env is not the goal face."""
+    why = _why_not_fused(model, env, True)
+    if why is None and not env.goal_conditioned:
+        why = "an env without the goal face (goal_conditioned=True)"
+    if why is not None:
+        raise ValueError(f"evaluate_goal_tracking does not cover {why}")
+    if warn:
+        warnings.warn(_MONITOR_WARNING, UserWarning)
+    order, (ret_h, len_h, goal_h, gap_h, abs_h) = _launch(model, env, n_eval_episodes, tracking=True)
+    pick = lambda x: np.array([x[i, j] for i, j in order], dtype=np.float64)  # noqa: E731
+    lo2, half_span = float(env.coef.s_lo[2]), float(env.coef.s_span[2]) / 2.0
+    lens = np.array([int(len_h[i, j]) for i, j in order], dtype=np.int64)
+    return dict(episode_rewards=pick(ret_h), episode_lengths=lens, target=lo2 + (pick(goal_h) + 1.0) * half_span,
+                final_error=pick(gap_h) * half_span, mean_abs_error=pick(abs_h) / lens * half_span)

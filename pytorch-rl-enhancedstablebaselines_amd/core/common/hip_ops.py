@@ -1877,3 +1877,74 @@ def her_sample(coef, ring: DeviceRing, her: DeviceHer, mt_state, batch: int, nb_
                                        C.c_int(nv.HER_STRATEGIES[strategy]), ptr(forced_row), ptr(forced_env), ptr(forced_goal), ptr(out_obs),
                                        ptr(out_act), ptr(out_next_obs), ptr(out_done), ptr(out_rew), ptr(out_row_idx), ptr(out_env_idx),
                                        ptr(out_goal_row), ptr(her.status), stream_ptr()), "cstr_her_sample_f32")
+
+
+def goal_eval_episodes_supported(h1: int, h2: int, n_out: int, head: int) -> bool:
+    """cstr_eval_goal_episodes_f32 takes the network shapes of cstr_policy_rows_fwd_f32 on the goal face's flat rows (k0 = 6, two valves)."""
+    lds = 4 * (16 * (16 * -(-h1 // 16) + 4 + 16 * -(-h2 // 16) + 4) + 8 * 16 * 8 + 2 * 16 * 8)
+    return head in (0, 1) and n_out == (4 if head == 0 else 2) and policy_rows_supported(GOAL_ROW, h1, h2, n_out) and lds <= EVAL_LDS_BYTES
+
+
+def goal_eval_episodes(w1, b1, w2, b2, w3, b3, act: int, head: int, out_act: int, w2_swz, coef, integrator: str, env_obs, step_count, pcg_state,
+                       target, squashed: bool, act_low, act_high, targets, max_vec_steps: int, static_init=None, episode=None, goal_seed: int = 0,
+                       goal_index_offset: int = 0, goal_lo: float = 0.0, goal_hi: float = 0.0, tracking: bool = False):
+    """Whole evaluation episodes on the goal face in ONE launch (cstr_eval_goal_episodes_f32): `eval_episodes` with the network on the
+    flat rows [achieved | desired | observation] (w1 [h1, 6]), the goal reward on the env's own setpoint `target` [N] and, when `episode`
+    [N] int32 is given, the setpoint redraw of `goal_vec_step` at every episode end. The launch advances env_obs / step_count / pcg_state /
+    target / episode. Returns (ep_return, ep_len, ep_done) like `eval_episodes`; with `tracking` also (ep_goal float32, ep_gap float32,
+    ep_abs_gap float64), each [N, max(targets)]: the episode's desired goal, achieved - desired of its terminal row and the f64 sum of
+    |achieved - desired| over its steps. Raises RuntimeError if `max_vec_steps` ended the launch before every env had met its target."""
+    import numpy as np
+
+    n = env_obs.shape[0]
+    h1, h2, n_out = w1.shape[0], w2.shape[0], w3.shape[0]
+    if n_out != (4 if head == 0 else 2):
+        raise ValueError(f"the goal face has two valves: w3 needs {4 if head == 0 else 2} rows for head {head}, got {n_out}")
+    _chk(env_obs, "env_obs", (n, 4), th.float32), _chk(step_count, "step_count", (n,), th.int32)
+    _chk(pcg_state, "pcg_state", (n, nv.PCG_STATE_WORDS), th.int64), _opt(static_init, "static_init", (n, 4), th.float64)
+    _chk(target, "target", (n,), th.float32), _opt(episode, "episode", (n,), th.int32)
+    _chk(w1, "w1", (h1, GOAL_ROW), th.float32), _chk(b1, "b1", (h1,), th.float32), _chk(w2, "w2", (h2, h1), th.float32)
+    _chk(b2, "b2", (h2,), th.float32), _chk(w3, "w3", (n_out, h2), th.float32), _chk(b3, "b3", (n_out,), th.float32)
+    if w2_swz is not None:
+        _chk(w2_swz, "w2_swz", (swizzled_numel(h2, h1),), th.float32)
+    if len(act_low) != 2 or len(act_high) != 2:
+        raise ValueError("act_low/act_high need 2 entries")
+    tg = np.ascontiguousarray(np.asarray(targets, dtype=np.int32))
+    if tg.shape != (n,):
+        raise ValueError(f"targets: shape {tg.shape}, expected {(n,)}")
+    if tg.min() < 0:
+        raise ValueError("targets must be non-negative")
+    stride, dev = int(tg.max()), env_obs.device
+    ep_return = th.zeros(n, stride, dtype=th.float64, device=dev)
+    ep_len = th.zeros(n, stride, dtype=th.int32, device=dev)
+    ep_done = th.zeros(n, dtype=th.int32, device=dev)
+    track = (th.zeros(n, stride, dtype=th.float32, device=dev), th.zeros(n, stride, dtype=th.float32, device=dev),
+             th.zeros(n, stride, dtype=th.float64, device=dev)) if tracking else (None, None, None)
+    goal_eval_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, coef, integrator, env_obs, step_count, pcg_state, target, squashed,
+                            act_low, act_high, tg, max_vec_steps, ep_return, ep_len, ep_done, *track, static_init=static_init, episode=episode,
+                            goal_seed=goal_seed, goal_index_offset=goal_index_offset, goal_lo=goal_lo, goal_hi=goal_hi)
+    short = (ep_done.cpu().numpy() < tg).nonzero()[0]  # the one read-back this wrapper does: a run cut short must not pass for a result
+    if short.size:
+        raise RuntimeError(f"cstr_eval_goal_episodes_f32: max_vec_steps={int(max_vec_steps)} ended the launch before envs {short.tolist()} had "
+                           f"run their episodes (counted {ep_done.cpu().numpy()[short].tolist()}, wanted {tg[short].tolist()})")
+    return (ep_return, ep_len, ep_done) + (track if tracking else ())
+
+
+def goal_eval_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, coef, integrator, env_obs, step_count, pcg_state, target, squashed,
+                            act_low, act_high, targets, max_vec_steps, ep_return, ep_len, ep_done, ep_goal=None, ep_gap=None, ep_abs_gap=None,
+                            static_init=None, episode=None, goal_seed: int = 0, goal_index_offset: int = 0, goal_lo: float = 0.0,
+                            goal_hi: float = 0.0):
+    """`goal_eval_episodes` into caller-owned result buffers; nothing is checked beyond what the entry point itself checks. `targets`: a
+    contiguous int32 NumPy array that the CALLER keeps alive and unmodified until the stream has passed the launch (see
+    `eval_episodes_into`)."""
+    n = env_obs.shape[0]
+    lo = (C.c_float * 2)(*[float(v) for v in act_low])
+    hi = (C.c_float * 2)(*[float(v) for v in act_high])
+    net = nv.PolicyMlp(GOAL_ROW, w1.shape[0], w2.shape[0], 2, act, head, out_act, 0, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                       w3.data_ptr(), b3.data_ptr(), None if w2_swz is None else w2_swz.data_ptr())
+    check(nv.lib().cstr_eval_goal_episodes_f32(C.byref(net), C.byref(coef), C.c_int(INTEGRATORS[integrator]), ptr(env_obs), ptr(step_count),
+                                               ptr(pcg_state), ptr(static_init), ptr(target), ptr(episode),
+                                               C.c_uint64(int(goal_seed) & (2**64 - 1)), C.c_int64(int(goal_index_offset)), C.c_float(goal_lo),
+                                               C.c_float(goal_hi), C.c_int(1 if squashed else 0), lo, hi, targets.ctypes.data_as(C.c_void_p),
+                                               C.c_int64(n), C.c_int64(int(max_vec_steps)), ptr(ep_return), ptr(ep_len), ptr(ep_done),
+                                               ptr(ep_goal), ptr(ep_gap), ptr(ep_abs_gap), stream_ptr()), "cstr_eval_goal_episodes_f32")

@@ -1,4 +1,4 @@
-// cstr_eval.hip -- whole evaluation episodes in ONE launch for gfx950 (cstr_eval_episodes_f32).
+// cstr_eval.hip -- whole evaluation episodes in ONE launch for gfx950 (cstr_eval_episodes_f32, cstr_eval_goal_episodes_f32).
 //
 // evaluate_policy (core/common/evaluation.py:11-140) is a host loop: per vec-step the actor's launch, the env step, a few element-wise
 // ops and two flags read back. Here a workgroup owns 16 envs and walks their vec-steps inside the launch:
@@ -18,6 +18,12 @@
 // An env stops when it has met its target: its state after its last counted episode (the reset draw behind that episode included) is
 // what the launch leaves; the host loop would keep stepping it until every env is done, which is NOT reproduced.
 //
+// cstr_eval_goal_episodes_f32 is the same kernel on the goal-conditioned face (GOAL instantiations): the network reads the flat row
+// [achieved_goal | desired_goal | observation] (k0 = 6), the reward is goal_reward on the env's own setpoint, an episode's end redraws the
+// setpoint from Philox exactly as cstr_goal_vec_step_f32 does, and three optional per-episode outputs carry the setpoint, the terminal
+// gap and the f64 sum of |achieved - desired| -- the numbers a lane has in registers when its episode ends. Its contract is bit-level
+// against cstr_policy_rows_fwd_f32 on the flat rows, predict()'s post-processing and cstr_goal_vec_step_f32.
+//
 // Termination: the loop over vec-steps is bounded by max_vec_steps whatever the data does; it ends earlier once the workgroup's 16 envs
 // have met their targets.
 #include <hip/hip_runtime.h>
@@ -27,12 +33,14 @@
 #include "../../include/cstr_rl_hip.h"
 #include "cstr_device.h"
 #include "cstr_env_device.h"
+#include "cstr_goal_device.h"
 #include "cstr_policy_device.h"
 
 namespace {
 
 // k chunks of layer 2 whose operands a wave requests at once (the accumulation order does not depend on it): 8 keeps the kernel, which
-// also holds the env lanes' episode state, inside its register budget
+// also holds the env lanes' episode state, inside its register budget (200 VGPRs; the goal instantiations, whose env lanes also hold the
+// setpoint, the episode ordinal and the gap sum, 216; no scratch in either: profiles/goal_eval_kernel_resources.txt)
 constexpr int EVAL_UNROLL = 8;
 constexpr int EVAL_MAX_WIDTH_V2 = 512;  // widths up to which cstr_policy_rows_fwd_f32 takes its pipelined kernel (split-K head)
 
@@ -46,10 +54,24 @@ struct EvalArgs {
     int64_t ep_stride, n, max_vec_steps;
 };
 
-template <int ACT, int HEAD, int L>
-__global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const EvalArgs a)
+// the goal face (cstr_eval_goal_episodes_f32): the Box arguments, then the per-env setpoints, their redraw and the tracking outputs
+struct GoalEvalArgs : EvalArgs {
+    float *target; GoalDraw gd;
+    float *ep_goal, *ep_gap; double *ep_abs_gap;  // each optional
+};
+
+template <bool GOAL> struct EvalArgsOf { using type = EvalArgs; };
+template <> struct EvalArgsOf<true> { using type = GoalEvalArgs; };
+
+// GOAL = false: the Box faces, L = the env layout. GOAL = true (L = 0): the network reads the flat row [achieved | desired | observation]
+// (k0 = 6; the env state is columns 2..5 of the LDS row), the reward is goal_reward on the lane's own setpoint, and an episode's end
+// redraws the setpoint as cstr_goal_vec_step_f32 does.
+template <int ACT, int HEAD, int L, bool GOAL = false>
+__global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const typename EvalArgsOf<GOAL>::type a)
 {
+    static_assert(!GOAL || L == 0, "the goal face is the (4, 2) layout");
     constexpr int D = Lay<L>::D, A = Lay<L>::A, XS = 8;  // XS: row stride of the observation image
+    constexpr int X0 = GOAL ? 2 : 0;                     // column of the env state in a row of the image
     extern __shared__ float eval_lds[];
     __shared__ int go_s;
     const int H1 = a.h1, H2 = a.h2, kc1 = (H1 + 15) >> 4, kc2 = (H2 + 15) >> 4, S1 = 16 * kc1 + 4, S2 = 16 * kc2 + 4;
@@ -64,6 +86,9 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
     const bool env_lane = wave == 0 && lane < POLICY_ROWS && env < a.n;
     int32_t target = 0, count = 0, cur_len = 0, st = 0;
     double cur_ret = 0.0;
+    float tg = 0.0f, dg = 0.0f;  // GOAL: the env's raw setpoint and its desired_goal, constant within an episode
+    int32_t ordinal = 0;         // GOAL: ordinal of the env's next episode (the redraw's counter word)
+    double abs_gap = 0.0;        // GOAL: f64 sum of |achieved - desired| over the episode's next rows
     if (tid < POLICY_ROWS * XS) xs[tid] = 0.0f;  // rows past n_envs and columns past obs_dim stay zero
     {   // zero the k padding of both activation images (widths that are not multiples of 16: the split-K head reads whole chunks)
         const int p1 = 16 * kc1 - H1, p2 = 16 * kc2 - H2;
@@ -75,9 +100,16 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
         float o[2][4];
         load_obs<L>(a.env_obs, env, o);
 #pragma unroll
-        for (int j = 0; j < D; ++j) xs[lane * XS + j] = o[j >> 2][j & 3];
+        for (int j = 0; j < D; ++j) xs[lane * XS + X0 + j] = o[j >> 2][j & 3];
         st = a.step_count[env];
         target = a.ep_done[env];
+        if constexpr (GOAL) {
+            tg = a.target[env];
+            dg = goal_of_target(a.k, tg);
+            if (a.gd.episode) ordinal = a.gd.episode[env];
+            xs[lane * XS + 0] = o[0][2];  // achieved_goal = observation[2]
+            xs[lane * XS + 1] = dg;
+        }
     }
     if (wave == 0) {
         const unsigned long long any = __ballot(env_lane && count < target);
@@ -88,7 +120,9 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
     for (int64_t it = 0; it < a.max_vec_steps; ++it) {
         if (!go_s) break;  // workgroup-uniform: written before the barrier that ends the previous trip
         // ---- the policy network on the 16 observation rows (the stages of cstr_policy_rows_fwd_f32) ----
-        policy_layer<ACT, false, true, false, 1>(xs, XS, true, a.k0, a.w1, a.b1, H1, h1s, S1);  // k0 <= 8: one k chunk
+        // k0 <= 8: one k chunk. GOAL: W1's rows are 6 floats (24 bytes), so its operand loads are per element, bounded by k0 -- the
+        // first-layer staging cstr_policy_rows_fwd_f32 takes for k0 = 6 (no 16-byte loads); columns 6, 7 of the image are zero
+        policy_layer<ACT, false, !GOAL, false, 1>(xs, XS, true, a.k0, a.w1, a.b1, H1, h1s, S1);
         __syncthreads();
         if (a.w2s) policy_layer<ACT, false, true, true, EVAL_UNROLL>(h1s, S1, true, H1, a.w2s, a.b2, H2, h2s, S2);
         else policy_layer<ACT, false, true, false, EVAL_UNROLL>(h1s, S1, true, H1, a.w2, a.b2, H2, h2s, S2);
@@ -178,14 +212,32 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
             }
             float o[2][4], on[2][4], rew;
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j >> 2][j & 3] = xs[lane * XS + j];
+            for (int j = 0; j < (GOAL ? 4 : 8); ++j) o[j >> 2][j & 3] = xs[lane * XS + X0 + j];
+            bool bad = false;
+            if constexpr (GOAL) {  // goal_step_kernel's own NaN test: the goal reward does not replace the NaN path's -10
+                bad = (ea[0] != ea[0]) || (ea[1] != ea[1]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) bad |= (o[0][j] != o[0][j]);
+            }
             const bool done = a.integrator == CSTR_INTEGRATOR_EULER ? env_step_lane<L, CSTR_INTEGRATOR_EULER>(a.k, o, ea, st, on, rew)
                                                                     : env_step_lane<L, CSTR_INTEGRATOR_RK4>(a.k, o, ea, st, on, rew);
+            float gap = 0.0f;
+            if constexpr (GOAL) {  // the next row's columns 0, 1: achieved goal of the next state, the OLD desired goal
+                if (!bad) rew = goal_reward(a.k.s_lo[2], a.k.s_span[2], a.k.conc_span, on[0][2], dg);
+                gap = on[0][2] - dg;
+                abs_gap += (double)fabsf(gap);
+            }
             cur_ret += (double)rew;  // current_rewards: float64 (evaluation.py:84, :97)
             cur_len += 1;
             if (done) {
                 a.ep_return[env * a.ep_stride + count] = cur_ret;
                 a.ep_len[env * a.ep_stride + count] = cur_len;
+                if constexpr (GOAL) {
+                    if (a.ep_goal) a.ep_goal[env * a.ep_stride + count] = dg;
+                    if (a.ep_gap) a.ep_gap[env * a.ep_stride + count] = gap;
+                    if (a.ep_abs_gap) a.ep_abs_gap[env * a.ep_stride + count] = abs_gap;
+                    abs_gap = 0.0;
+                }
                 count += 1;
                 cur_ret = 0.0;
                 cur_len = 0;
@@ -194,9 +246,20 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
                 reset_draw_env<L>(a.k, pst, a.static_init, env, on);
                 *reinterpret_cast<ulonglong2 *>(a.pcg + 4 * env) = make_ulonglong2(pst[0], pst[1]);
                 st = 0;
+                if constexpr (GOAL) {
+                    if (a.gd.episode) {  // the setpoint of the episode that starts now
+                        tg = goal_draw_target(a.gd, env, ordinal);
+                        ordinal += 1;
+                        dg = goal_of_target(a.k, tg);
+                    }
+                }
             }
 #pragma unroll
-            for (int j = 0; j < D; ++j) xs[lane * XS + j] = on[j >> 2][j & 3];
+            for (int j = 0; j < D; ++j) xs[lane * XS + X0 + j] = on[j >> 2][j & 3];
+            if constexpr (GOAL) {
+                xs[lane * XS + 0] = on[0][2];
+                xs[lane * XS + 1] = dg;
+            }
         }
         if (wave == 0) {
             const unsigned long long any = __ballot(env_lane && count < target);
@@ -208,10 +271,14 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
     if (env_lane) {
         float o[2][4];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) o[j >> 2][j & 3] = xs[lane * XS + j];
+        for (int j = 0; j < (GOAL ? 4 : 8); ++j) o[j >> 2][j & 3] = xs[lane * XS + X0 + j];
         store_obs<L>(a.env_obs, env, o);
         a.step_count[env] = st;
         a.ep_done[env] = count;
+        if constexpr (GOAL) {
+            a.target[env] = tg;
+            if (a.gd.episode) a.gd.episode[env] = ordinal;
+        }
     }
 }
 
@@ -226,6 +293,15 @@ static size_t eval_lds_bytes(const cstr_policy_mlp_t &n)
 {
     const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
     return (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 2 * POLICY_ROWS * 8) * sizeof(float);
+}
+
+// whether cstr_policy_rows_fwd_f32 runs its split-K head for this network (its pipelined kernel): the launches here run the same one
+static bool eval_split_k_head(const cstr_policy_mlp_t &n)
+{
+    static const bool force_v1 = getenv("CSTR_POLICY_V1") != nullptr;  // the development knob of cstr_policy_rows_fwd_f32: same head as that launch
+    const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
+    const size_t v2_lds = (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 4 * POLICY_ROWS * 8) * sizeof(float);
+    return n.w2_swizzled && n.h1 <= EVAL_MAX_WIDTH_V2 && n.h2 <= EVAL_MAX_WIDTH_V2 && v2_lds <= 64 * 1024 && !force_v1;
 }
 
 extern "C" int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs,
@@ -281,10 +357,7 @@ extern "C" int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_c
     const hipError_t cp = hipMemcpyAsync(ep_done, targets, sizeof(int32_t) * (size_t)n_envs, hipMemcpyHostToDevice, s);
     if (cp != hipSuccess) return (int)cp;
     if (ep_stride == 0) return CSTR_OK;  // nothing to run: ep_done = targets = 0
-    static const bool force_v1 = getenv("CSTR_POLICY_V1") != nullptr;  // the development knob of cstr_policy_rows_fwd_f32: same head as that launch
-    const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
-    const size_t v2_lds = (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 4 * POLICY_ROWS * 8) * sizeof(float);
-    const bool split_k = n.w2_swizzled && n.h1 <= EVAL_MAX_WIDTH_V2 && n.h2 <= EVAL_MAX_WIDTH_V2 && v2_lds <= 64 * 1024 && !force_v1;
+    const bool split_k = eval_split_k_head(n);
     EvalArgs a = {n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, A, n.out_act, split_k ? 1 : 0, *coef,
                   env_obs, step_count, pcg_state, static_init, squashed, integrator, ab, ep_return, ep_len, ep_done, ep_stride, n_envs, max_vec_steps};
     const unsigned grid = (unsigned)((n_envs + POLICY_ROWS - 1) / POLICY_ROWS);
@@ -295,5 +368,81 @@ extern "C" int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_c
     else { if (n.act == 0) EV2(0, 1); else if (n.act == 1) EV2(1, 1); else EV2(2, 1); }
 #undef EV2
 #undef EV3
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_eval_goal_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, float *env_obs,
+                                           int32_t *step_count, uint64_t *pcg_state, double *static_init, float *target, int32_t *episode,
+                                           uint64_t goal_seed, int64_t goal_index_offset, float goal_lo, float goal_hi, int squashed,
+                                           const float *act_low, const float *act_high, const int32_t *targets, int64_t n_envs,
+                                           int64_t max_vec_steps, double *ep_return, int32_t *ep_len, int32_t *ep_done, float *ep_goal,
+                                           float *ep_gap, double *ep_abs_gap, cstr_stream_t stream)
+{
+    constexpr int K0 = 6;  // the flat row [achieved_goal | desired_goal | observation]
+    if (!net || !coef || !env_obs || !step_count || !pcg_state || !target || !act_low || !act_high || !targets || !ep_done) return CSTR_E_BADARG;
+    if (n_envs <= 0 || max_vec_steps <= 0 || (squashed & ~1)) return CSTR_E_BADARG;
+    const cstr_policy_mlp_t &n = *net;
+    if (!n.w1 || !n.b1 || !n.w2 || !n.b2 || !n.w3 || !n.b3 || n.k0 <= 0 || n.h1 <= 0 || n.h2 <= 0 || n.act_dim <= 0 || n.reserved) return CSTR_E_BADARG;
+    if (n.act_dim != 2 || (integrator != CSTR_INTEGRATOR_EULER && integrator != CSTR_INTEGRATOR_RK4)) return CSTR_E_UNSUPPORTED;
+    if (n.k0 != K0) return CSTR_E_BADARG;  // the policy reads the goal face's flat rows
+    if (episode && !(goal_lo <= goal_hi)) return CSTR_E_BADARG;
+    // the shapes of cstr_policy_rows_fwd_f32
+    if (n.act < 0 || n.act > 2 || n.out_act < 0 || n.out_act > 2 || n.head < 0 || n.head > 1 || (n.h1 & 3) || (n.h2 & 3) ||
+        (size_t)POLICY_ROWS * (n.h1 + 4 + n.h2 + 4) * sizeof(float) > 64 * 1024 || eval_lds_bytes(n) > 64 * 1024 ||
+        (n_envs + POLICY_ROWS - 1) / POLICY_ROWS > 0x7fffffff)
+        return CSTR_E_UNSUPPORTED;
+    const auto aligned4 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
+    if (!aligned16(env_obs) || !aligned16(pcg_state) || !aligned4(n.w1) || !aligned16(n.w2) || !aligned16(n.w3) ||
+        (n.w2_swizzled && !aligned16(n.w2_swizzled)) || !aligned8(ep_return) || !aligned8(ep_abs_gap) || (static_init && !aligned8(static_init)) ||
+        !aligned4(step_count) || !aligned4(target) || !aligned4(episode) || !aligned4(ep_len) || !aligned4(ep_done) || !aligned4(ep_goal) ||
+        !aligned4(ep_gap))
+        return CSTR_E_BADARG;
+    ActBounds ab;
+    for (int j = 0; j < 4; ++j) {
+        ab.lo[j] = j < 2 ? act_low[j] : -1.0f;
+        ab.hi[j] = j < 2 ? act_high[j] : 1.0f;
+        if (!(ab.hi[j] > ab.lo[j])) return CSTR_E_BADARG;
+    }
+    int64_t ep_stride = 0;  // targets is a HOST array (like act_low / act_high): checked here, staged into ep_done below
+    for (int64_t i = 0; i < n_envs; ++i) {
+        if (targets[i] < 0) return CSTR_E_BADARG;
+        if (targets[i] > ep_stride) ep_stride = targets[i];
+    }
+    if (ep_stride > 0 && (!ep_return || !ep_len)) return CSTR_E_BADARG;  // (no slot exists when every target is 0)
+    if (ep_stride > 0 && n_envs > INT64_MAX / (8 * ep_stride)) return CSTR_E_UNSUPPORTED;
+    {   // outputs must not overlap what the launch reads, or each other
+        const int n_out = (n.head == 0 ? 2 : 1) * 2, kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
+        const int64_t slots = n_envs * ep_stride;
+        const Span outs[6] = {span_of(ep_return, 8 * slots), span_of(ep_len, 4 * slots), span_of(ep_done, 4 * n_envs),
+                              span_of(ep_goal, 4 * slots), span_of(ep_gap, 4 * slots), span_of(ep_abs_gap, 8 * slots)};
+        const Span ins[13] = {span_of(env_obs, 16 * n_envs), span_of(step_count, 4 * n_envs), span_of(pcg_state, 32 * n_envs),
+                              span_of(static_init, 32 * n_envs), span_of(target, 4 * n_envs), span_of(episode, 4 * n_envs),
+                              span_of(n.w1, 4LL * n.h1 * K0), span_of(n.b1, 4LL * n.h1), span_of(n.w2, 4LL * n.h2 * n.h1),
+                              span_of(n.b2, 4LL * n.h2), span_of(n.w3, 4LL * n_out * n.h2), span_of(n.b3, 4LL * n_out),
+                              span_of(n.w2_swizzled, 1024LL * kc1 * kc2)};
+        for (int i = 0; i < 6; ++i) {
+            for (int j = 0; j < 13; ++j)
+                if (overlaps(outs[i], ins[j])) return CSTR_E_BADARG;
+            for (int j = i + 1; j < 6; ++j)
+                if (overlaps(outs[i], outs[j])) return CSTR_E_BADARG;
+        }
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t cp = hipMemcpyAsync(ep_done, targets, sizeof(int32_t) * (size_t)n_envs, hipMemcpyHostToDevice, s);
+    if (cp != hipSuccess) return (int)cp;
+    if (ep_stride == 0) return CSTR_OK;  // nothing to run: ep_done = targets = 0
+    GoalEvalArgs a;
+    static_cast<EvalArgs &>(a) = EvalArgs{n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, 2, n.out_act, eval_split_k_head(n) ? 1 : 0,
+                                          *coef, env_obs, step_count, pcg_state, static_init, squashed, integrator, ab, ep_return, ep_len, ep_done,
+                                          ep_stride, n_envs, max_vec_steps};
+    a.target = target;
+    a.gd = GoalDraw{goal_seed, goal_index_offset, goal_lo, goal_hi, episode};
+    a.ep_goal = ep_goal; a.ep_gap = ep_gap; a.ep_abs_gap = ep_abs_gap;
+    const unsigned grid = (unsigned)((n_envs + POLICY_ROWS - 1) / POLICY_ROWS);
+    const size_t lds = eval_lds_bytes(n);
+#define EVG(A_, H_) eval_episodes_kernel<A_, H_, 0, true><<<grid, 64 * POLICY_WAVES, lds, s>>>(a)
+    if (n.head == 0) { if (n.act == 0) EVG(0, 0); else if (n.act == 1) EVG(1, 0); else EVG(2, 0); }
+    else { if (n.act == 0) EVG(0, 1); else if (n.act == 1) EVG(1, 1); else EVG(2, 1); }
+#undef EVG
     return (int)hipGetLastError();
 }

@@ -17,37 +17,13 @@
 #include "cstr_device.h"
 
 #include "cstr_env_device.h"
+#include "cstr_goal_device.h"
 #include "cstr_mt_device.h"
 #include "cstr_rng_device.h"
 
 namespace {
 
 constexpr int HER_TPB = 256;
-constexpr uint32_t HER_GOAL_TAG = 0x90A17A67u;  // counter word 3 of the target redraw: shares no counters with the other streams
-
-// desired_goal of a raw target: the observation's own affine map of C2 (twoseriescstr.py:131), f32
-__device__ __forceinline__ float goal_of_target(const cstr_coef_t &k, const float target) { return 2.0f * (target - k.s_lo[2]) / k.s_span[2] - 1.0f; }
-
-// GoalEnv reward = the reference's concentration term (twoseriescstr.py:288-291) on (achieved, desired), both normalised
-__device__ __forceinline__ float goal_reward(const float s_lo2, const float s_span2, const float conc_span, const float ag, const float dg)
-{
-    const float C2 = s_lo2 + (ag + 1.0f) * s_span2 / 2.0f;
-    const float T = s_lo2 + (dg + 1.0f) * s_span2 / 2.0f;
-    const float ne = fabsf(C2 - T) / conc_span;
-    return -5.0f * (ne * ne) - 2.0f * ne;
-}
-
-// flat row [achieved_goal | desired_goal | observation]: six floats, 8-byte aligned
-__device__ __forceinline__ void store_row6(float *p, const int64_t i, const float dg, const float o[4])
-{
-    float2 *q = reinterpret_cast<float2 *>(p + 6 * i);
-    q[0] = make_float2(o[2], dg);
-    q[1] = make_float2(o[0], o[1]);
-    q[2] = make_float2(o[2], o[3]);
-}
-
-struct GoalDraw { uint64_t seed; int64_t index_offset; float lo, hi; int32_t *episode; };
-
 // ---- VecEnv.step on the goal face (dummy_vec_env.py:56-73 over TwoSeriesCSTREnv.step) ------------------------------------------
 template <int INTEG>
 __global__ void goal_step_kernel(const cstr_coef_t k, float *__restrict__ env_obs, const float *__restrict__ act, int32_t *__restrict__ step_count,
@@ -82,11 +58,7 @@ __global__ void goal_step_kernel(const cstr_coef_t k, float *__restrict__ env_ob
             float dg2 = dg;
             if (gd.episode) {  // target of the episode that starts now: counter (env index, episode ordinal, tag), key = goal seed
                 const int32_t e = gd.episode[i];
-                const uint64_t idx = (uint64_t)(gd.index_offset + i);
-                uint32_t x[4];
-                philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), (uint32_t)e, HER_GOAL_TAG, (uint32_t)gd.seed, (uint32_t)(gd.seed >> 32), x);
-                const float u = (float)(x[0] >> 8) * (1.0f / 16777216.0f);
-                tg = gd.lo + (gd.hi - gd.lo) * u;
+                tg = goal_draw_target(gd, i, e);
                 target[i] = tg;
                 gd.episode[i] = e + 1;
                 dg2 = goal_of_target(k, tg);
