@@ -15,6 +15,7 @@
 // chain (to the action), actor backward chain, [dW/db sets], [Adam + polyak]: 10 launches (6 of them here) instead of 20.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/cstr_rl_hip.h"
 #include "cstr_device.h"
@@ -413,6 +414,152 @@ __device__ __forceinline__ void store_panel(const float *panel, const int ld, fl
     }
 }
 
+// ---- the stages behind barrier 1, shared by a generic kernel and its lean form -----------------------------------------------------
+// A lean kernel (further down) differs from its generic kernel in the PROLOGUE only: where the arguments come from, the order of the
+// requests, which variant is compiled in. Everything behind barrier 1 is written once, here and in front of the backward kernels, and
+// called by both, so the two compute the same bits by construction. The caller hands over the lane indices and the scalars it already
+// holds (nothing is re-derived from threadIdx or re-read from the arguments); widths, tile count and leading dimension are plain ints:
+// run-time values from a generic kernel, constants that fold after inlining from a lean one, as do the generic conditions (rows mode,
+// head width, optional outputs) a lean call site fixes.
+
+// Q forward, head stage of a tile's first wave: hv = relu(acc + b2), the head's partial dot product over these 16 columns -> red
+__device__ __forceinline__ void q_fwd_head(float (&hv)[4], const f32x4 acc, const float bv, const float w3v, const bool col_ok, float *red, const int tile,
+                                           const int r, const int h)
+{
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
+#ifdef CSTR_HEAD_F64  // experiment (VERDICT r2 next-6c): the head's dot product over the workgroup's columns accumulated in f64
+        double sd = (double)hv[e] * (double)w3v;
+        sd += __shfl_xor(sd, 8, 64); sd += __shfl_xor(sd, 4, 64); sd += __shfl_xor(sd, 2, 64); sd += __shfl_xor(sd, 1, 64);
+        const float s = (float)sd;
+#else
+        const float s = rowsum16(hv[e] * w3v);
+#endif
+        if (r == 0) red[(tile * 16 + 4 * h + e) * 8] = s;
+    }
+}
+
+// Q forward, tail (behind the last barrier): the sum over the workgroup's tiles -> q_part, then the kept activations h2 and h1
+__device__ __forceinline__ void q_fwd_tail(const float (&hv)[4], const float *red, const float *panel, const int ld, const int T, const int H1, const int H2,
+                                           const int B, const int n0, const int m0, const int t, const int wave, const int r, const int h, const bool col_ok,
+                                           float *q_part, float *h2, float *h1)
+{
+    if (t < 16) {
+        float s = red[t * 8];
+        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + t) * 8];
+        q_part[(int64_t)blockIdx.x * B + m0 + t] = s;
+    }
+    // ---- global stores, all behind the last barrier ----
+    if (wave < T && col_ok && h2) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
+    }
+    if (blockIdx.x == 0 && h1) store_panel(panel, ld, h1, H1, m0);
+}
+
+// actor forward: the noise of the row group's sampling head, counter-based and independent of the network (counter = ctr0 + row of
+// the pass, ctr0 = the control word + the launch's offset); lane = (row, pair of actions)
+template <int A>
+__device__ __forceinline__ void actor_fwd_noise(const uint64_t seed, const uint64_t ctr0, const int m0, const int lane, float &e0, float &e1)
+{
+    constexpr int PAIRS = (A + 1) / 2;
+    const int row = lane / PAIRS, pr = lane % PAIRS;
+    const uint64_t ctr = ctr0 + (uint64_t)(m0 + row);
+    uint32_t rr[4];
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)pr, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rr);
+    box_muller(rr[0], rr[1], e0, e1);
+}
+
+// actor forward, (f) epilogue of the tile's first wave: bias + ReLU, head partials over these 16 columns for the HN head outputs in
+// use; then (behind one barrier) their sum over the workgroup's tiles -> head_part [column group][M rows][HN]
+template <int A>
+__device__ __forceinline__ void actor_fwd_epilogue(float (&hv)[4], const f32x4 acc, const float bv, const float (&hwv)[2 * A], const int HN, const bool col_ok,
+                                                   float *red, const int T, const int tile, const int t, const int wave, const int r, const int h,
+                                                   float *head_part, const int M, const int m0)
+{
+    if (wave < T) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 2 * A; ++j) {
+            if (j < HN) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float s = rowsum16(hv[e] * hwv[j]);
+                    if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
+                }
+            }
+        }
+    }
+    lds_barrier();
+    CH_STAMP(0, 6);
+    if (t < 16 * HN) {
+        const int row = t / HN, j = t % HN;
+        float s = red[row * 8 + j];
+        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + row) * 8 + j];
+        head_part[((int64_t)blockIdx.x * M + m0 + row) * HN + j] = s;
+    }
+}
+
+// actor forward, global stores (all behind the last barrier): the kept activations of the rows a backward follows, the noise, the
+// packed batch of a gathering launch (column group 0: `mat`; lane t < 16 D / 4 holds quad t % (D / 4) of transition b in v, of its
+// observation in vo where a next_obs-only pass needs it, and lane qd == 0 its action / reward / done words), the ring's advance
+template <int D, int A>
+__device__ __forceinline__ void actor_fwd_stores(const float (&hv)[4], const float *panel, const int ld, const int T, const int H1, const int H2, const int B,
+                                                 const int mode, const int n0, const int m0, const int t, const int lane, const int wave, const int r,
+                                                 const int h, const bool col_ok, const bool keep_h2, float *a_h2, const bool keep_h1, float *a_h1,
+                                                 const bool noise, const float e0, const float e1, float *eps_all, const bool mat, const bool next,
+                                                 const int b, float4 v, const float4 vo, const float (&actv)[A], const float dn, const float to,
+                                                 const float rw, float *x_pi, float *x_next, float *x_data, float *out_done, float *out_rew,
+                                                 const bool gather, const int advance_ring, int64_t *ring_ctl, const int64_t ring_rows)
+{
+    constexpr int W = D + A, QPR = D / 4, PAIRS = (A + 1) / 2;
+    const bool data_row = mode != CSTR_CHAIN_ROWS_PAIR;  // (with a gather) every row also writes its transition's x_data / reward / done
+    const bool keep_rows = mode == CSTR_CHAIN_ROWS_OBS || (mode == CSTR_CHAIN_ROWS_PAIR && m0 < B);  // the rows a backward follows
+    if (wave < T && col_ok && keep_h2 && keep_rows) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) a_h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
+    }
+    if (blockIdx.x == 0 && keep_h1 && keep_rows) store_panel(panel, ld, a_h1, H1, m0);
+    if (noise) {
+        const int row = lane / PAIRS, pr = lane % PAIRS;
+        float *eo = eps_all + (int64_t)(m0 + row) * A + 2 * pr;
+        eo[0] = e0;
+        if (2 * pr + 1 < A) eo[1] = e1;
+    }
+    if (mat && t < 16 * QPR) {  // the packed batch for the launches behind this one (cstr_linear_act_fwd_gather_f32's contract)
+        const int qd = t % QPR;
+        float *xo = (next ? x_next : x_pi) + (int64_t)b * W + 4 * qd;
+        reinterpret_cast<float2 *>(xo)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xo)[1] = make_float2(v.z, v.w);
+        if (data_row && next) {  // a next_obs-only pass: this row's observation goes to x_data and x_pi as well
+            if (x_pi) {
+                float *xp = x_pi + (int64_t)b * W + 4 * qd;
+                reinterpret_cast<float2 *>(xp)[0] = make_float2(vo.x, vo.y); reinterpret_cast<float2 *>(xp)[1] = make_float2(vo.z, vo.w);
+            }
+            v = vo;
+        }
+        if (!next || data_row) {
+            float *xd = x_data + (int64_t)b * W;
+            reinterpret_cast<float2 *>(xd + 4 * qd)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xd + 4 * qd)[1] = make_float2(v.z, v.w);
+            if (qd == 0) {
+#pragma unroll
+                for (int j = 0; j < A; ++j) xd[D + j] = actv[j];
+                out_done[b] = dn * (1.0f - to);  // buffers.py:322
+                out_rew[b] = rw;
+            }
+        }
+    }
+    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0 && gather) {  // nobody reads these words in this launch
+        if (advance_ring) {  // ReplayBuffer.add's epilogue (buffers.py:280-283), left over by the rollout launch
+            int64_t pos = ring_ctl[0] + 1;
+            if (pos == ring_rows) { ring_ctl[1] = 1; pos = 0; }
+            ring_ctl[0] = pos;
+            ring_ctl[3] += 1;
+        }
+    }
+}
+
 // ---- SAC actor, forward chain -------------------------------------------------------------------------------------------------
 struct ActorFwdArgs {
     cstr_sac_actor_t net;
@@ -487,13 +634,7 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_fwd_kernel(const A
     constexpr int PAIRS = (A + 1) / 2;
     float e0 = 0.0f, e1 = 0.0f;
     const bool noise = a.eps_all != nullptr && blockIdx.x == 0 && wave == 3 && lane < 16 * PAIRS;
-    if (noise) {
-        const int row = lane / PAIRS, pr = lane % PAIRS;
-        const uint64_t seed = a.head_rng_ctl[0], ctr = a.head_rng_ctl[1] + a.head_rng_offset + (uint64_t)(m0 + row);
-        uint32_t rr[4];
-        philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)pr, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rr);
-        box_muller(rr[0], rr[1], e0, e1);
-    }
+    if (noise) actor_fwd_noise<A>(a.head_rng_ctl[0], a.head_rng_ctl[1] + a.head_rng_offset, m0, lane, e0, e1);
     CH_STAMP(0, 1);
     lds_barrier();
     CH_STAMP(0, 2);
@@ -506,73 +647,12 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_fwd_kernel(const A
     CH_STAMP(0, 4);
     acc = combine_split_k(acc, smem, T, S);
     CH_STAMP(0, 5);
-    // (f) epilogue of the tile's first wave: bias + ReLU, head partials over these 16 columns
+    // (f) epilogue, head partials -> head_part, the global stores (all behind the last barrier)
     float hv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (wave < T) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
-#pragma unroll
-        for (int j = 0; j < 2 * A; ++j) {
-            if (j < HN) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float s = rowsum16(hv[e] * hwv[j]);
-                    if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
-                }
-            }
-        }
-    }
-    lds_barrier();
-    CH_STAMP(0, 6);
-    if (t < 16 * HN) {
-        const int row = t / HN, j = t % HN;
-        float s = red[row * 8 + j];
-        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + row) * 8 + j];
-        a.head_part[((int64_t)blockIdx.x * M + m0 + row) * HN + j] = s;
-    }
-    // ---- global stores, all behind the last barrier ----
-    const bool keep_rows = mode == CSTR_CHAIN_ROWS_OBS || (mode == CSTR_CHAIN_ROWS_PAIR && m0 < B);  // the rows a backward follows
-    if (wave < T && col_ok && a.a_h2 && keep_rows) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a.a_h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
-    }
-    if (blockIdx.x == 0 && a.a_h1 && keep_rows) store_panel(panel, ld, a.a_h1, H1, m0);
-    if (noise) {
-        const int row = lane / PAIRS, pr = lane % PAIRS;
-        float *eo = a.eps_all + (int64_t)(m0 + row) * A + 2 * pr;
-        eo[0] = e0;
-        if (2 * pr + 1 < A) eo[1] = e1;
-    }
-    if (mat && t < 16 * QPR) {  // the packed batch for the launches behind this one (cstr_linear_act_fwd_gather_f32's contract)
-        const int qd = t % QPR;
-        float *xo = (next ? a.x_next : a.x_pi) + (int64_t)b * W + 4 * qd;
-        reinterpret_cast<float2 *>(xo)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xo)[1] = make_float2(v.z, v.w);
-        if (data_row && next) {  // a next_obs-only pass: this row's observation goes to x_data and x_pi as well
-            if (a.x_pi) {
-                float *xp = a.x_pi + (int64_t)b * W + 4 * qd;
-                reinterpret_cast<float2 *>(xp)[0] = make_float2(vo.x, vo.y); reinterpret_cast<float2 *>(xp)[1] = make_float2(vo.z, vo.w);
-            }
-            v = vo;
-        }
-        if (!next || data_row) {
-            float *xd = a.x_data + (int64_t)b * W;
-            reinterpret_cast<float2 *>(xd + 4 * qd)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xd + 4 * qd)[1] = make_float2(v.z, v.w);
-            if (qd == 0) {
-#pragma unroll
-                for (int j = 0; j < A; ++j) xd[D + j] = actv[j];
-                a.out_done[b] = dn * (1.0f - to);  // buffers.py:322
-                a.out_rew[b] = rw;
-            }
-        }
-    }
-    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0 && a.idx) {  // nobody reads these words in this launch
-        if (a.advance_ring) {  // ReplayBuffer.add's epilogue (buffers.py:280-283), left over by the rollout launch
-            int64_t pos = a.ring_ctl[0] + 1;
-            if (pos == a.ring.rows) { a.ring_ctl[1] = 1; pos = 0; }
-            a.ring_ctl[0] = pos;
-            a.ring_ctl[3] += 1;
-        }
-    }
+    actor_fwd_epilogue<A>(hv, acc, bv, hwv, HN, col_ok, red, T, tile, t, wave, r, h, a.head_part, M, m0);
+    actor_fwd_stores<D, A>(hv, panel, ld, T, H1, H2, B, mode, n0, m0, t, lane, wave, r, h, col_ok, a.a_h2 != nullptr, a.a_h2, a.a_h1 != nullptr, a.a_h1, noise,
+                           e0, e1, a.eps_all, mat, next, b, v, vo, actv, dn, to, rw, a.x_pi, a.x_next, a.x_data, a.out_done, a.out_rew, a.idx != nullptr,
+                           a.advance_ring, a.ring_ctl, a.ring.rows);
     CH_STAMP(0, 7);
 }
 
@@ -673,33 +753,10 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_fwd_kernel(const QFwdArgs 
     acc = combine_split_k(acc, smem, T, S);
     CH_STAMP(1, 5);
     float hv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (wave < T) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
-#ifdef CSTR_HEAD_F64  // experiment (VERDICT r2 next-6c): the head's dot product over the workgroup's columns accumulated in f64
-            double sd = (double)hv[e] * (double)w3v;
-            sd += __shfl_xor(sd, 8, 64); sd += __shfl_xor(sd, 4, 64); sd += __shfl_xor(sd, 2, 64); sd += __shfl_xor(sd, 1, 64);
-            const float s = (float)sd;
-#else
-            const float s = rowsum16(hv[e] * w3v);
-#endif
-            if (r == 0) red[(tile * 16 + 4 * h + e) * 8] = s;
-        }
-    }
+    if (wave < T) q_fwd_head(hv, acc, bv, w3v, col_ok, red, tile, r, h);
     lds_barrier();
     CH_STAMP(1, 6);
-    if (t < 16) {
-        float s = red[t * 8];
-        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + t) * 8];
-        net.q_part[(int64_t)blockIdx.x * B + m0 + t] = s;
-    }
-    // ---- global stores, all behind the last barrier ----
-    if (wave < T && col_ok && net.h2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) net.h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
-    }
-    if (blockIdx.x == 0 && net.h1) store_panel(panel, ld, net.h1, H1, m0);
+    q_fwd_tail(hv, red, panel, ld, T, H1, H2, B, n0, m0, t, wave, r, h, col_ok, net.q_part, net.h2, net.h1);
     if (fin_lane && blockIdx.x == 0 && role != CSTR_CHAIN_ROLE_NEXT) {
         const int bb = m0 + f_row;
         const bool det = a.fin.kind == CSTR_CHAIN_HEAD_DETERMINISTIC;
@@ -721,12 +778,6 @@ struct QBwdArgs {
     float *dz2, *dz1, *gact_part;
 };
 
-__device__ __forceinline__ float q_from_parts(const float *part, const float *b3, const int n_parts, const int batch, const int row)
-{
-    const float b = b3[0];
-    return sum_parts(part, n_parts, batch, row, (int64_t)n_parts * batch) + b;
-}
-
 __device__ __forceinline__ float wave_sum64(float v)
 {
 #pragma unroll
@@ -745,21 +796,46 @@ __device__ __forceinline__ float block_sum_256(float v, float *sm)
     return r;
 }
 
-// the batch reductions of the loss (td_twin_q_loss_kernel / sac_actor_loss_kernel / neg_mean_loss_kernel's expressions and tree)
-__device__ void chain_loss_workgroup(const cstr_chain_root_t &rt, float *sm)
+// The root's variant -- loss mode, entropy coefficient's own loss (alpha), log-probs in the target (nlogp), bucket of the Q partial
+// sums (LB) -- as the shared stages below see it: read from the record at run time by the generic kernel (LB 0: sum_parts picks the
+// bucket by n) or fixed by the lean kernel's instantiation (LB 4, 8 or 16: that bucket of sum_parts)
+struct RootRt {
+    static constexpr int LB = 0;
+    int mode; bool alpha, nlogp;
+    __device__ __forceinline__ explicit RootRt(const cstr_chain_root_t &rt) : mode(rt.mode), alpha(rt.alpha.log_alpha != nullptr), nlogp(rt.next_logp != nullptr) {}
+};
+template <int MODE, bool ALPHA, bool NLOGP, int LB_>
+struct RootFixed {
+    static constexpr int LB = LB_, mode = MODE;
+    static constexpr bool alpha = ALPHA, nlogp = NLOGP;
+};
+
+template <int LB>
+__device__ __forceinline__ float q_from_parts(const float *part, const float *b3, const int n_parts, const int batch, const int row)
 {
+    const float b = b3[0];
+    if constexpr (LB == 0) return sum_parts(part, n_parts, batch, row, (int64_t)n_parts * batch) + b;
+    else return sum_parts_n<LB>(rsrc_of(part, (int64_t)n_parts * batch), n_parts, batch, row) + b;
+}
+
+// the batch reductions of the loss (td_twin_q_loss_kernel / sac_actor_loss_kernel / neg_mean_loss_kernel's expressions and tree) and
+// the launch's side effects, by the loss workgroup
+template <typename V>
+__device__ __forceinline__ void chain_loss(const V v, const cstr_chain_root_t &rt, float *sm)
+{
+    constexpr int LB = V::LB;
     const int tid = threadIdx.x, B = rt.batch, P = rt.n_parts;
-    const bool with_alpha = rt.mode == 1 && rt.alpha.log_alpha != nullptr;
+    const bool with_alpha = v.mode == 1 && v.alpha;
     const float la = with_alpha ? rt.alpha.log_alpha[0] : 0.0f;
     const float ec = with_alpha ? expf(la) : (rt.ent_coef ? rt.ent_coef[0] : 0.0f);
     const float inv = 1.0f / (float)B;
-    if (rt.mode == 1) {
+    if (v.mode == 1) {
         float a1 = 0.0f, a2 = 0.0f, aa = 0.0f;
         for (int b = tid; b < B; b += 256) {
-            float q = fminf(q_from_parts(rt.q_part[2], rt.b3[2], P, B, b), q_from_parts(rt.q_part[3], rt.b3[3], P, B, b));
-            if (rt.next_logp) q = q - ec * rt.next_logp[b];
+            float q = fminf(q_from_parts<LB>(rt.q_part[2], rt.b3[2], P, B, b), q_from_parts<LB>(rt.q_part[3], rt.b3[3], P, B, b));
+            if (v.nlogp) q = q - ec * rt.next_logp[b];
             const float tq = rt.rew[b] + (1.0f - rt.done[b]) * rt.gamma * q;
-            const float d1 = q_from_parts(rt.q_part[0], rt.b3[0], P, B, b) - tq, d2 = q_from_parts(rt.q_part[1], rt.b3[1], P, B, b) - tq;
+            const float d1 = q_from_parts<LB>(rt.q_part[0], rt.b3[0], P, B, b) - tq, d2 = q_from_parts<LB>(rt.q_part[1], rt.b3[1], P, B, b) - tq;
             a1 += d1 * d1;
             a2 += d2 * d2;
             if (with_alpha) aa += rt.alpha.logp_pi[b] + rt.alpha.target_entropy;
@@ -778,9 +854,9 @@ __device__ void chain_loss_workgroup(const cstr_chain_root_t &rt, float *sm)
                 if (rt.alpha.ent_coef_sum) rt.alpha.ent_coef_sum[0] += ec;
             }
         }
-    } else if (rt.mode == 3) {
+    } else if (v.mode == 3) {
         float acc = 0.0f;
-        for (int b = tid; b < B; b += 256) acc += q_from_parts(rt.q_part[0], rt.b3[0], P, B, b);
+        for (int b = tid; b < B; b += 256) acc += q_from_parts<LB>(rt.q_part[0], rt.b3[0], P, B, b);
         const float sum = block_sum_256(acc, sm);
         if (tid == 0) {
             const float loss = -(sum * inv);
@@ -790,7 +866,7 @@ __device__ void chain_loss_workgroup(const cstr_chain_root_t &rt, float *sm)
     } else {
         float acc = 0.0f;
         for (int b = tid; b < B; b += 256) {
-            const float x = q_from_parts(rt.q_part[0], rt.b3[0], P, B, b), c = q_from_parts(rt.q_part[1], rt.b3[1], P, B, b);
+            const float x = q_from_parts<LB>(rt.q_part[0], rt.b3[0], P, B, b), c = q_from_parts<LB>(rt.q_part[1], rt.b3[1], P, B, b);
             acc += ec * rt.logp[b] - (x <= c ? x : c);
         }
         const float sum = block_sum_256(acc, sm);
@@ -807,6 +883,120 @@ __device__ void chain_loss_workgroup(const cstr_chain_root_t &rt, float *sm)
         ctl[0] += 1;
         pw[0] *= rt.adam_beta1[tid];
         pw[1] *= rt.adam_beta2[tid];
+    }
+}
+// the generic kernels' (every variant a branch): one out-of-line copy for all their instantiations
+__device__ void chain_loss_workgroup(const cstr_chain_root_t &rt, float *sm) { chain_loss(RootRt(rt), rt, sm); }
+
+// (b) d(loss)/dq of network g for ONE row of the row group (cstr_head_root_t's expressions): Q values from the row's partial sums
+// pq[0 .. 3] (requested in the prologue) + b3, the TD target, this network's Q / gradient / target
+template <typename V, typename PQ>
+__device__ __forceinline__ void q_bwd_root(const V v, const int g, const PQ *pq, const float (&b3)[4], const float ec, const float nl, const float rw, const float dn,
+                                           const float gamma, const float scale, const int B, float &o_q, float &o_gq, float &o_tq)
+{
+    const float kq = scale * 2.0f / (float)B, inv = 1.0f / (float)B;
+    if (v.mode == 1) {
+        const float qa = pq[2].sum() + b3[2], qb = pq[3].sum() + b3[3];
+        o_q = (g == 0 ? pq[0].sum() + b3[0] : pq[1].sum() + b3[1]);
+        float q = fminf(qa, qb);
+        if (v.nlogp) q = q - ec * nl;
+        o_tq = rw + (1.0f - dn) * gamma * q;
+        o_gq = kq * (o_q - o_tq);
+    } else if (v.mode == 3) {
+        o_q = pq[0].sum() + b3[0];
+        o_gq = -inv;
+    } else {
+        const float q1 = pq[0].sum() + b3[0], q2 = pq[1].sum() + b3[1];
+        const bool first = q1 <= q2;
+        o_q = g == 0 ? q1 : q2;
+        o_gq = (first == (g == 0)) ? -inv : 0.0f;
+    }
+}
+
+// (c) dz2 = dq * w3 * relu'(h2), recomputed by every workgroup of the row group into the panel: thread t owns the columns t + 256 i,
+// i < NC, whose h2 values sit in y (replaced by dz2: kept for the store at the end); gs = the 16 rows' dq
+template <int NC>
+__device__ __forceinline__ void q_bwd_dz2(float (&y)[NC][16], const float (&w3c)[NC], const float *gs, float *panel, const int ld, const int H2, const int t)
+{
+    __builtin_assume(t < CH_THREADS);  // (a workgroup is CH_THREADS threads: at H2 = 256 and NC = 1 the column guard below folds away)
+    float gq[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float4 g4 = *reinterpret_cast<const float4 *>(gs + 4 * q);
+        gq[4 * q] = g4.x; gq[4 * q + 1] = g4.y; gq[4 * q + 2] = g4.z; gq[4 * q + 3] = g4.w;
+    }
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        const int c = t + CH_THREADS * i;
+        if (c < H2) {
+#pragma unroll
+            for (int row = 0; row < 16; ++row) {
+                y[i][row] = y[i][row] > 0.0f ? gq[row] * w3c[i] : 0.0f;
+                panel[row * ld + c] = y[i][row];
+            }
+        }
+    }
+}
+
+// (f) epilogue of the dz1 tile: * relu'(h1); with `gact` the partial action gradient over these 16 columns through red -> gact_part
+template <int A>
+__device__ __forceinline__ void q_bwd_epilogue(float (&d)[4], const f32x4 acc, const float (&ty)[4], const float (&w1a)[A], const bool col_ok, const bool gact,
+                                               float *gact_part, float *red, const int T, const int tile, const int t, const int wave, const int r, const int h,
+                                               const int g, const int B, const int m0)
+{
+    if (wave < T) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) d[e] = (col_ok && ty[e] > 0.0f) ? acc[e] : 0.0f;
+        if (gact) {
+#pragma unroll
+            for (int j = 0; j < A; ++j) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float s = rowsum16(d[e] * w1a[j]);
+                    if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
+                }
+            }
+        }
+    }
+    if (gact) {
+        lds_barrier();
+        if (t < 16 * A) {
+            const int row = t / A, j = t % A;
+            float s = red[row * 8 + j];
+            for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + row) * 8 + j];
+            gact_part[(((int64_t)g * gridDim.x + blockIdx.x) * B + m0 + row) * A + j] = s;
+        }
+    }
+}
+
+// global stores, all behind the last barrier: the dz1 tile, this workgroup's share of the dz2 columns, the rows' Q / dq / target
+template <int NC>
+__device__ __forceinline__ void q_bwd_stores(const float (&d)[4], const float (&y)[NC][16], const int T, const int H1, const int H2, const int B, const int g,
+                                             const int k0, const int m0, const int t, const int wave, const int r, const int h, const bool col_ok,
+                                             const bool st_dz1, float *dz1, const bool st_dz2, float *dz2, const bool td, const float o_q, const float o_gq,
+                                             const float o_tq, float *q_out, float *gq_out, float *target_out)
+{
+    if (st_dz1 && wave < T && col_ok) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) dz1[((int64_t)g * B + m0 + 4 * h + e) * H1 + k0 + r] = d[e];
+    }
+    __builtin_assume(t < CH_THREADS);
+    if (st_dz2) {  // each workgroup of the row group stores its share of the columns
+        const int cpg = (H2 + gridDim.x - 1) / gridDim.x;
+#pragma unroll
+        for (int i = 0; i < NC; ++i) {
+            const int c = t + CH_THREADS * i;
+            if (c < H2 && c / cpg == (int)blockIdx.x) {
+#pragma unroll
+                for (int row = 0; row < 16; ++row) dz2[((int64_t)g * B + m0 + row) * H2 + c] = y[i][row];
+            }
+        }
+    }
+    if (t < 16 && blockIdx.x == 0) {
+        const int row = m0 + t;
+        if (q_out) q_out[(int64_t)g * B + row] = o_q;
+        if (gq_out) gq_out[(int64_t)g * B + row] = o_gq;
+        if (td && g == 0 && target_out) target_out[row] = o_tq;
     }
 }
 
@@ -878,48 +1068,14 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_kernel(const QBwdArgs 
     if (t < 16) {
         const bool with_alpha = rt.mode == 1 && rt.alpha.log_alpha != nullptr;
         const float ec = with_alpha ? expf(rt.alpha.log_alpha[0]) : (rt.ent_coef ? rt.ent_coef[0] : 0.0f);
-        const float kq = rt.scale * 2.0f / (float)B, inv = 1.0f / (float)B;
-        if (rt.mode == 1) {
-            const float qa = pq[2].sum() + r_b3[2], qb = pq[3].sum() + r_b3[3];
-            o_q = (g == 0 ? pq[0].sum() + r_b3[0] : pq[1].sum() + r_b3[1]);
-            float q = fminf(qa, qb);
-            if (rt.next_logp) q = q - ec * r_nl;
-            o_tq = r_rw + (1.0f - r_dn) * rt.gamma * q;
-            o_gq = kq * (o_q - o_tq);
-        } else if (rt.mode == 3) {
-            o_q = pq[0].sum() + r_b3[0];
-            o_gq = -inv;
-        } else {
-            const float q1 = pq[0].sum() + r_b3[0], q2 = pq[1].sum() + r_b3[1];
-            const bool first = q1 <= q2;
-            o_q = g == 0 ? q1 : q2;
-            o_gq = (first == (g == 0)) ? -inv : 0.0f;
-        }
+        q_bwd_root(RootRt(rt), g, pq, r_b3, ec, r_nl, r_rw, r_dn, rt.gamma, rt.scale, B, o_q, o_gq, o_tq);
         gs[t] = o_gq;
     }
     CH_STAMP(2, 1);
     lds_barrier();
     CH_STAMP(2, 2);
     // (c) dz2 = dq * w3 * relu'(h2), recomputed by every workgroup of the row group into the panel (values kept for the store at the end)
-    {
-        float gq[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 g4 = *reinterpret_cast<const float4 *>(gs + 4 * q);
-            gq[4 * q] = g4.x; gq[4 * q + 1] = g4.y; gq[4 * q + 2] = g4.z; gq[4 * q + 3] = g4.w;
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = t + CH_THREADS * i;
-            if (c < H2) {
-#pragma unroll
-                for (int row = 0; row < 16; ++row) {
-                    y[i][row] = y[i][row] > 0.0f ? gq[row] * w3c[i] : 0.0f;
-                    panel[row * ld + c] = y[i][row];
-                }
-            }
-        }
-    }
+    q_bwd_dz2<2>(y, w3c, gs, panel, ld, H2, t);
     lds_barrier();
     CH_STAMP(2, 3);
     // (d) dz1 tile = (dz2 W2)[rows][k0 .. k0 + 15], (e) split-K combine, (f) * relu'(h1); partial action gradient
@@ -928,52 +1084,10 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_kernel(const QBwdArgs 
     acc = combine_split_k(acc, smem, T, S);
     CH_STAMP(2, 5);
     float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (wave < T) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = (col_ok && ty[e] > 0.0f) ? acc[e] : 0.0f;
-        if (a.gact_part) {
-#pragma unroll
-            for (int j = 0; j < A; ++j) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float s = rowsum16(d[e] * w1a[j]);
-                    if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
-                }
-            }
-        }
-    }
-    if (a.gact_part) {
-        lds_barrier();
-        if (t < 16 * A) {
-            const int row = t / A, j = t % A;
-            float s = red[row * 8 + j];
-            for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + row) * 8 + j];
-            a.gact_part[(((int64_t)g * gridDim.x + blockIdx.x) * B + m0 + row) * A + j] = s;
-        }
-    }
+    q_bwd_epilogue<A>(d, acc, ty, w1a, col_ok, a.gact_part != nullptr, a.gact_part, red, T, tile, t, wave, r, h, g, B, m0);
     CH_STAMP(2, 6);
-    // ---- global stores, all behind the last barrier ----
-    if (a.dz1 && wave < T && col_ok) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) a.dz1[((int64_t)g * B + m0 + 4 * h + e) * H1 + k0 + r] = d[e];
-    }
-    if (a.dz2) {  // each workgroup of the row group stores its share of the columns
-        const int cpg = (H2 + gridDim.x - 1) / gridDim.x;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int c = t + CH_THREADS * i;
-            if (c < H2 && c / cpg == (int)blockIdx.x) {
-#pragma unroll
-                for (int row = 0; row < 16; ++row) a.dz2[((int64_t)g * B + m0 + row) * H2 + c] = y[i][row];
-            }
-        }
-    }
-    if (t < 16 && blockIdx.x == 0) {
-        const int row = m0 + t;
-        if (rt.q_out) rt.q_out[(int64_t)g * B + row] = o_q;
-        if (rt.gq_out) rt.gq_out[(int64_t)g * B + row] = o_gq;
-        if (rt.mode == 1 && g == 0 && rt.target_out) rt.target_out[row] = o_tq;
-    }
+    q_bwd_stores<2>(d, y, T, H1, H2, B, g, k0, m0, t, wave, r, h, col_ok, a.dz1 != nullptr, a.dz1, a.dz2 != nullptr, a.dz2, rt.mode == 1, o_q, o_gq, o_tq, rt.q_out,
+                    rt.gq_out, rt.target_out);
     CH_STAMP(2, 7);
 }
 
@@ -994,6 +1108,9 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_kernel(const QBwdArgs 
 //     behind the barriers (profiles/qfwd_fin_defer_ab.txt).
 // Partial sums keep the generic bucket of every n (PartBatch: n <= 8 the 8-register form, 9 .. 16 sum_parts_n<16>; the loss
 // workgroup: sum_parts' 4 / 8 / 16), i.e. the same adds in the same order over the same zero padding.
+// The lean kernels hold a PROLOGUE only (everything in front of barrier 1). Behind it they call the stages the generic kernels call,
+// with their constants: q_fwd_head / q_fwd_tail; q_bwd_root / q_bwd_dz2<1> / q_bwd_epilogue / q_bwd_stores and chain_loss with a
+// RootFixed variant (the generic kernel: RootRt). A change to a stage is made once, in those functions.
 template <int NP>
 struct PartBatchN {
     float v[NP];
@@ -1148,110 +1265,12 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_fwd_lean_kernel(const int 
     if (!FIN_STAMPS) CH_STAMP(1, 5);
     float hv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (FW != 0 && wave == FW) fin_deferred();  // beside the head stage of the waves < T
-    if (wave < T) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
-#ifdef CSTR_HEAD_F64
-            double sd = (double)hv[e] * (double)w3v;
-            sd += __shfl_xor(sd, 8, 64); sd += __shfl_xor(sd, 4, 64); sd += __shfl_xor(sd, 2, 64); sd += __shfl_xor(sd, 1, 64);
-            const float s = (float)sd;
-#else
-            const float s = rowsum16(hv[e] * w3v);
-#endif
-            if (r == 0) red[(tile * 16 + 4 * h + e) * 8] = s;
-        }
-    }
+    if (wave < T) q_fwd_head(hv, acc, bv, w3v, col_ok, red, tile, r, h);
     lds_barrier();
     CH_STAMP(1, 6);
-    if (t < 16) {
-        float s = red[t * 8];
-#pragma unroll
-        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + t) * 8];
-        net.q_part[(int64_t)blockIdx.x * B + m0 + t] = s;
-    }
-    // ---- global stores, all behind the last barrier ----
-    if (wave < T && col_ok && net.h2) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) net.h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
-    }
-    if (blockIdx.x == 0 && net.h1) store_panel(panel, ld, net.h1, H1, m0);
+    q_fwd_tail(hv, red, panel, ld, T, H1, H2, B, n0, m0, t, wave, r, h, col_ok, net.q_part, net.h2, net.h1);
     if (FW == 0) fin_deferred();  // no idle wave (T == 4): behind the head stage and the stores above
     CH_STAMP(1, 7);
-}
-
-template <int LB>
-__device__ __forceinline__ float q_from_parts_n(const float *part, const float *b3, const int n_parts, const int batch, const int row)
-{
-    const float b = b3[0];
-    return sum_parts_n<LB>(rsrc_of(part, (int64_t)n_parts * batch), n_parts, batch, row) + b;
-}
-
-// chain_loss_workgroup with the mode, the alpha part, next_logp and sum_parts' bucket (LB) fixed: the same expressions, tree and side
-// effects, small enough to sit inline behind the lean kernel's one uniform branch
-template <int MODE, bool ALPHA, bool NLOGP, int LB>
-__device__ __forceinline__ void chain_loss_lean(const cstr_chain_root_t &rt, float *sm)
-{
-    const int tid = threadIdx.x, B = rt.batch, P = rt.n_parts;
-    constexpr bool with_alpha = MODE == 1 && ALPHA;
-    const float la = with_alpha ? rt.alpha.log_alpha[0] : 0.0f;
-    const float ec = with_alpha ? expf(la) : (rt.ent_coef ? rt.ent_coef[0] : 0.0f);
-    const float inv = 1.0f / (float)B;
-    if (MODE == 1) {
-        float a1 = 0.0f, a2 = 0.0f, aa = 0.0f;
-        for (int b = tid; b < B; b += 256) {
-            float q = fminf(q_from_parts_n<LB>(rt.q_part[2], rt.b3[2], P, B, b), q_from_parts_n<LB>(rt.q_part[3], rt.b3[3], P, B, b));
-            if (NLOGP) q = q - ec * rt.next_logp[b];
-            const float tq = rt.rew[b] + (1.0f - rt.done[b]) * rt.gamma * q;
-            const float d1 = q_from_parts_n<LB>(rt.q_part[0], rt.b3[0], P, B, b) - tq, d2 = q_from_parts_n<LB>(rt.q_part[1], rt.b3[1], P, B, b) - tq;
-            a1 += d1 * d1;
-            a2 += d2 * d2;
-            if (with_alpha) aa += rt.alpha.logp_pi[b] + rt.alpha.target_entropy;
-        }
-        const float s1 = block_sum_256(a1, sm), s2 = block_sum_256(a2, sm);
-        const float mean = with_alpha ? block_sum_256(aa, sm) / (float)B : 0.0f;
-        if (tid == 0) {
-            const float loss = rt.scale * (s1 / (float)B + s2 / (float)B);
-            if (rt.loss_out) rt.loss_out[0] = loss;
-            if (rt.loss_sum) rt.loss_sum[0] += loss;
-            if (with_alpha) {
-                rt.alpha.grad_out[0] = -mean;
-                rt.alpha.ent_coef_out[0] = ec;
-                if (rt.alpha.loss_out) rt.alpha.loss_out[0] = -(la * mean);
-                if (rt.alpha.loss_sum) rt.alpha.loss_sum[0] += -(la * mean);
-                if (rt.alpha.ent_coef_sum) rt.alpha.ent_coef_sum[0] += ec;
-            }
-        }
-    } else if (MODE == 3) {
-        float acc = 0.0f;
-        for (int b = tid; b < B; b += 256) acc += q_from_parts_n<LB>(rt.q_part[0], rt.b3[0], P, B, b);
-        const float sum = block_sum_256(acc, sm);
-        if (tid == 0) {
-            const float loss = -(sum * inv);
-            if (rt.loss_out) rt.loss_out[0] = loss;
-            if (rt.loss_sum) rt.loss_sum[0] += loss;
-        }
-    } else {
-        float acc = 0.0f;
-        for (int b = tid; b < B; b += 256) {
-            const float x = q_from_parts_n<LB>(rt.q_part[0], rt.b3[0], P, B, b), c = q_from_parts_n<LB>(rt.q_part[1], rt.b3[1], P, B, b);
-            acc += ec * rt.logp[b] - (x <= c ? x : c);
-        }
-        const float sum = block_sum_256(acc, sm);
-        if (tid == 0) {
-            const float loss = sum * inv;
-            if (rt.loss_out) rt.loss_out[0] = loss;
-            if (rt.loss_sum) rt.loss_sum[0] += loss;
-        }
-    }
-    if (tid == 0 && rt.rng_ctl) rt.rng_ctl[1] += rt.rng_advance;
-    if (tid < 2 && rt.adam_advance[tid]) {
-        int64_t *ctl = rt.adam_advance[tid];
-        double *pw = reinterpret_cast<double *>(ctl + 2);
-        ctl[0] += 1;
-        pw[0] *= rt.adam_beta1[tid];
-        pw[1] *= rt.adam_beta2[tid];
-    }
 }
 
 struct QBwdLeanNet { const float *w1, *w2, *w3, *h1, *h2; };
@@ -1281,7 +1300,7 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_lean_kernel(const int 
     constexpr int H1 = exact_h1<WX>(), H2 = exact_h2<WX>();
     const int g = blockIdx.z;
     if (__builtin_expect((int)blockIdx.y == B / 16, 0)) {  // the loss workgroup
-        if (g == 0 && blockIdx.x == 0) chain_loss_lean<MODE, ALPHA, NLOGP, LB>(a.root, smem + SM_RED);
+        if (g == 0 && blockIdx.x == 0) chain_loss(RootFixed<MODE, ALPHA, NLOGP, LB>(), a.root, smem + SM_RED);
         return;
     }
     constexpr int T = exact_tiles<NQ, WX>(), S = CH_WAVES / T;
@@ -1333,50 +1352,21 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_lean_kernel(const int 
     float w1a[A];
 #pragma unroll
     for (int j = 0; j < A; ++j) w1a[j] = GACT ? net.w1[(int64_t)col * W + D + j] : 0.0f;
-    float y[16];  // H2 == 256: one column per thread
-    const float w3c = net.w3[t];
+    float y[1][16];  // H2 == 256: one column per thread
+    const float w3c[1] = {net.w3[t]};
 #pragma unroll
-    for (int row = 0; row < 16; ++row) y[row] = net.h2[(int64_t)(m0 + row) * H2 + t];
+    for (int row = 0; row < 16; ++row) y[0][row] = net.h2[(int64_t)(m0 + row) * H2 + t];
     // (b) d(loss)/dq of this network for the row group's 16 rows (cstr_head_root_t's expressions)
     float o_qv = 0.0f, o_gq = 0.0f, o_tq = 0.0f;
     if (t < 16) {
-        const float kq = scale * 2.0f / (float)B, inv = 1.0f / (float)B;
-        if constexpr (MODE == 1) {
-            const float ec = ALPHA ? expf(r_ec) : r_ec;
-            const float qa = pq[2].sum() + r_b3[2], qb = pq[3].sum() + r_b3[3];
-            o_qv = (g == 0 ? pq[0].sum() + r_b3[0] : pq[1].sum() + r_b3[1]);
-            float q = fminf(qa, qb);
-            if (NLOGP) q = q - ec * r_nl;
-            o_tq = r_rw + (1.0f - r_dn) * gamma * q;
-            o_gq = kq * (o_qv - o_tq);
-        } else if constexpr (MODE == 3) {
-            o_qv = pq[0].sum() + r_b3[0];
-            o_gq = -inv;
-        } else {
-            const float q1 = pq[0].sum() + r_b3[0], q2 = pq[1].sum() + r_b3[1];
-            const bool first = q1 <= q2;
-            o_qv = g == 0 ? q1 : q2;
-            o_gq = (first == (g == 0)) ? -inv : 0.0f;
-        }
+        q_bwd_root(RootFixed<MODE, ALPHA, NLOGP, LB>(), g, pq, r_b3, ALPHA ? expf(r_ec) : r_ec, r_nl, r_rw, r_dn, gamma, scale, B, o_qv, o_gq, o_tq);
         gs[t] = o_gq;
     }
     CH_STAMP(2, 1);
     lds_barrier();
     CH_STAMP(2, 2);
     // (c) dz2 = dq * w3 * relu'(h2) into the panel (values kept for the store at the end)
-    {
-        float gq[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float4 g4 = *reinterpret_cast<const float4 *>(gs + 4 * q);
-            gq[4 * q] = g4.x; gq[4 * q + 1] = g4.y; gq[4 * q + 2] = g4.z; gq[4 * q + 3] = g4.w;
-        }
-#pragma unroll
-        for (int row = 0; row < 16; ++row) {
-            y[row] = y[row] > 0.0f ? gq[row] * w3c : 0.0f;
-            panel[row * ld + t] = y[row];
-        }
-    }
+    q_bwd_dz2<1>(y, w3c, gs, panel, ld, H2, t);
     lds_barrier();
     CH_STAMP(2, 3);
     // (d) dz1 tile, (e) split-K combine, (f) * relu'(h1); partial action gradient
@@ -1385,49 +1375,9 @@ __global__ __launch_bounds__(CH_THREADS) void q_chain_bwd_lean_kernel(const int 
     acc = combine_split_k(acc, smem, T, S);
     CH_STAMP(2, 5);
     float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (wave < T) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) d[e] = (col_ok && ty[e] > 0.0f) ? acc[e] : 0.0f;
-        if (GACT) {
-#pragma unroll
-            for (int j = 0; j < A; ++j) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float s = rowsum16(d[e] * w1a[j]);
-                    if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
-                }
-            }
-        }
-    }
-    if (GACT) {
-        lds_barrier();
-        if (t < 16 * A) {
-            const int row = t / A, j = t % A;
-            float s = red[row * 8 + j];
-#pragma unroll
-            for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + row) * 8 + j];
-            o_gact[(((int64_t)g * gridDim.x + blockIdx.x) * B + m0 + row) * A + j] = s;
-        }
-    }
+    q_bwd_epilogue<A>(d, acc, ty, w1a, col_ok, GACT, o_gact, red, T, tile, t, wave, r, h, g, B, m0);
     CH_STAMP(2, 6);
-    // ---- global stores, all behind the last barrier ----
-    if (!GACT) {
-        if (wave < T && col_ok) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o_dz1[((int64_t)g * B + m0 + 4 * h + e) * H1 + k0 + r] = d[e];
-        }
-        const int cpg = (H2 + gridDim.x - 1) / gridDim.x;  // each workgroup of the row group stores its share of the columns
-        if (t / cpg == (int)blockIdx.x) {
-#pragma unroll
-            for (int row = 0; row < 16; ++row) o_dz2[((int64_t)g * B + m0 + row) * H2 + t] = y[row];
-        }
-    }
-    if (t < 16 && blockIdx.x == 0) {
-        const int row = m0 + t;
-        if (o_q) o_q[(int64_t)g * B + row] = o_qv;
-        if (o_gqp) o_gqp[(int64_t)g * B + row] = o_gq;
-        if (MODE == 1 && g == 0 && o_tqp) o_tqp[row] = o_tq;
-    }
+    q_bwd_stores<1>(d, y, T, H1, H2, B, g, k0, m0, t, wave, r, h, col_ok, !GACT, o_dz1, !GACT, o_dz2, MODE == 1, o_qv, o_gq, o_tq, o_q, o_gqp, o_tqp);
     CH_STAMP(2, 7);
 }
 
@@ -1558,7 +1508,9 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_bwd_kernel(const A
 //   * the requests of the entry block are predicated (range-checked descriptors, clamped addresses), not branched around, so the
 //     compiler counts them: the ring row waits for the two indices only, its LDS store for the row only;
 //   * rows mode (PAIR), head width (2A), gather / packed input and noise drawn or not are compile-time.
-// No expression, MFMA operand, accumulator or summation order differs from the generic kernel. The actor BACKWARD launch got the same
+// No expression, MFMA operand, accumulator or summation order differs from the generic kernel: behind barrier 1 both call the same
+// stages (actor_fwd_epilogue, actor_fwd_stores; the noise lanes' actor_fwd_noise), the lean kernel with PAIR rows, HN = 2A and both kept
+// activations as constants that fold the generic kernel's other cases away. The actor BACKWARD launch got the same
 // treatment as an experiment (partials requested first, Gaussian head and bucket compile-time); its own launch was not shorter in the
 // graph, so it stays generic (profiles/actor_chain_lean_ab.txt, section 6).
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
@@ -1660,13 +1612,7 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_fwd_lean_kernel(co
     // the noise of the row group's sampling head: counter-based, independent of the network -- drawn while the gather is in flight,
     // consumed by the Q chain launch that finalises the head (counter = offset + row of the 2B-row pass)
     float e0 = 0.0f, e1 = 0.0f;
-    if (noise) {
-        const int nrow = lane / PAIRS, pr = lane % PAIRS;
-        const uint64_t seed = ((uint64_t)c_seed.y << 32) | c_seed.x, ctr = (((uint64_t)c_ctr.y << 32) | c_ctr.x) + rng_offset + (uint64_t)(m0 + nrow);
-        uint32_t rr[4];
-        philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)pr, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rr);
-        box_muller(rr[0], rr[1], e0, e1);
-    }
+    if (noise) actor_fwd_noise<A>(((uint64_t)c_seed.y << 32) | c_seed.x, (((uint64_t)c_ctr.y << 32) | c_ctr.x) + rng_offset, m0, lane, e0, e1);
     CH_STAMP(0, 1);
     lds_barrier();
     CH_STAMP(0, 2);
@@ -1679,64 +1625,12 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_fwd_lean_kernel(co
     CH_STAMP(0, 4);
     acc = combine_split_k(acc, smem, T, S);
     CH_STAMP(0, 5);
-    // (f) epilogue of the tile's first wave: bias + ReLU, head partials over these 16 columns
+    // (f) epilogue, head partials -> head_part, the global stores (all behind the last barrier): the generic kernel's at PAIR rows,
+    // 2A head outputs, both activations kept -- constants that fold its other cases away (no next_obs-only row: vo is never read)
     float hv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (wave < T) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hv[e] = col_ok ? fmaxf(acc[e] + bv, 0.0f) : 0.0f;
-#pragma unroll
-        for (int j = 0; j < HN; ++j) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float s = rowsum16(hv[e] * hwv[j]);
-                if (r == 0) red[(tile * 16 + 4 * h + e) * 8 + j] = s;
-            }
-        }
-    }
-    lds_barrier();
-    CH_STAMP(0, 6);
-    if (t < 16 * HN) {
-        const int prow = t / HN, j = t % HN;
-        float s = red[prow * 8 + j];
-#pragma unroll
-        for (int tl = 1; tl < T; ++tl) s += red[(tl * 16 + prow) * 8 + j];
-        o_head_part[((int64_t)blockIdx.x * M + m0 + prow) * HN + j] = s;
-    }
-    // ---- global stores, all behind the last barrier ----
-    const bool keep_rows = !next;  // the rows a backward follows
-    if (wave < T && col_ok && keep_rows) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) o_a_h2[(int64_t)(m0 + 4 * h + e) * H2 + n0 + r] = hv[e];
-    }
-    if (blockIdx.x == 0 && keep_rows) store_panel(panel, ld, o_a_h1, H1, m0);
-    if (noise) {
-        const int nrow = lane / PAIRS, pr = lane % PAIRS;
-        float *eo = o_eps + (int64_t)(m0 + nrow) * A + 2 * pr;
-        eo[0] = e0;
-        if (2 * pr + 1 < A) eo[1] = e1;
-    }
-    if (mat && gl) {  // the packed batch for the launches behind this one (cstr_linear_act_fwd_gather_f32's contract)
-        float *xo = (next ? x_next : x_pi) + (int64_t)b * W + 4 * qd;
-        reinterpret_cast<float2 *>(xo)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xo)[1] = make_float2(v.z, v.w);
-        if (!next) {
-            float *xd = o_x_data + (int64_t)b * W;
-            reinterpret_cast<float2 *>(xd + 4 * qd)[0] = make_float2(v.x, v.y); reinterpret_cast<float2 *>(xd + 4 * qd)[1] = make_float2(v.z, v.w);
-            if (qd == 0) {
-#pragma unroll
-                for (int j = 0; j < A; ++j) xd[D + j] = actv[j];
-                o_done[b] = dn * (1.0f - to);  // buffers.py:322
-                o_rew[b] = rw;
-            }
-        }
-    }
-    if (GATHER && blockIdx.x == 0 && blockIdx.y == 0 && t == 0) {  // nobody reads these words in this launch
-        if (advance_ring) {  // ReplayBuffer.add's epilogue (buffers.py:280-283), left over by the rollout launch
-            int64_t pos = ring_ctl[0] + 1;
-            if (pos == ring_rows) { ring_ctl[1] = 1; pos = 0; }
-            ring_ctl[0] = pos;
-            ring_ctl[3] += 1;
-        }
-    }
+    actor_fwd_epilogue<A>(hv, acc, bv, hwv, HN, col_ok, red, T, tile, t, wave, r, h, o_head_part, M, m0);
+    actor_fwd_stores<D, A>(hv, panel, ld, T, H1, H2, B, CSTR_CHAIN_ROWS_PAIR, n0, m0, t, lane, wave, r, h, col_ok, true, o_a_h2, true, o_a_h1, noise, e0, e1, o_eps,
+                           mat, next, b, v, v, actv, dn, to, rw, x_pi, x_next, o_x_data, o_done, o_rew, GATHER, advance_ring, ring_ctl, ring_rows);
     CH_STAMP(0, 7);
 }
 
@@ -1811,6 +1705,15 @@ constexpr size_t CHAIN_LDS_LIMIT = 64 * 1024;
 // ---- the lean Q launches' dispatch: false = not covered, the caller launches the generic kernel ------------------------------------
 int chain_lean_enabled = 1;  // cstr_chain_lean
 
+// the per-wave share as a compile-time constant for the lean launches: f(std::integral_constant<int, NQ>), nq = 4, 8 or 16 (chain_wx == 1)
+template <typename F>
+void lean_nq(const int nq, F &&f)
+{
+    if (nq == 4) f(std::integral_constant<int, 4>());
+    else if (nq == 8) f(std::integral_constant<int, 8>());
+    else f(std::integral_constant<int, 16>());
+}
+
 struct QFwdLeanScalars { int batch, parts; const float *head_part, *hb, *eps; int part_rows, next_offset; float sigma, clip; unsigned long long roles; };
 
 template <int D, int A, int NQ, int FIN, int PB>
@@ -1827,13 +1730,6 @@ void q_fwd_lean_variant(const int finv, const int pb, const dim3 grid, const siz
     else if (finv == QF_GAUSSIAN) q_fwd_lean_go<D, A, NQ, QF_GAUSSIAN, 16>(grid, lds, s, c, a);
     else if (pb == 8) q_fwd_lean_go<D, A, NQ, QF_DETERMINISTIC, 8>(grid, lds, s, c, a);
     else q_fwd_lean_go<D, A, NQ, QF_DETERMINISTIC, 16>(grid, lds, s, c, a);
-}
-template <int D, int A, typename... Rest>
-void q_fwd_lean_nq(const int nq, Rest &&...rest)
-{
-    if (nq == 4) q_fwd_lean_variant<D, A, 4>(rest...);
-    else if (nq == 8) q_fwd_lean_variant<D, A, 8>(rest...);
-    else q_fwd_lean_variant<D, A, 16>(rest...);
 }
 
 // the variants of the backward launch that a learner dispatches: TD root with the entropy coefficient's own loss (SAC, ent_coef
@@ -1862,13 +1758,6 @@ void q_bwd_lean_lb(const int lb, Rest &&...rest)
     else if (lb == 8) q_bwd_lean_variant<D, A, NQ, 8>(rest...);
     else q_bwd_lean_variant<D, A, NQ, 16>(rest...);
 }
-template <int D, int A, typename... Rest>
-void q_bwd_lean_nq(const int nq, Rest &&...rest)
-{
-    if (nq == 4) q_bwd_lean_lb<D, A, 4>(rest...);
-    else if (nq == 8) q_bwd_lean_lb<D, A, 8>(rest...);
-    else q_bwd_lean_lb<D, A, 16>(rest...);
-}
 
 bool q_fwd_lean_launch(const QFwdArgs &g, const int lay, const int wx, const int nq, const dim3 grid, const size_t lds, hipStream_t s)
 {
@@ -1890,8 +1779,10 @@ bool q_fwd_lean_launch(const QFwdArgs &g, const int lay, const int wx, const int
         c.sigma = f.sigma; c.clip = f.clip;
         a.x_pi = f.x_pi; a.x_next = f.x_next; a.params = f.params; a.logp_pi = f.logp_pi; a.logp_next = f.logp_next;
     }
-    if (lay == 0) q_fwd_lean_nq<4, 2>(nq, finv, pb, grid, lds, s, c, a);
-    else q_fwd_lean_nq<8, 2>(nq, finv, pb, grid, lds, s, c, a);
+    lean_nq(nq, [&](auto n) {
+        if (lay == 0) q_fwd_lean_variant<4, 2, decltype(n)::value>(finv, pb, grid, lds, s, c, a);
+        else q_fwd_lean_variant<8, 2, decltype(n)::value>(finv, pb, grid, lds, s, c, a);
+    });
     return true;
 }
 
@@ -1920,8 +1811,10 @@ bool q_bwd_lean_launch(const QBwdArgs &g, const int lay, const int wx, const int
     a.rew = rt.rew; a.done = rt.done; a.next_logp = rt.next_logp;
     c.batch = rt.batch; c.parts = rt.n_parts;
     const int lb = part_bucket_loss(rt.n_parts);
-    if (lay == 0) q_bwd_lean_nq<4, 2>(nq, lb, variant, grid, lds, s, c, a);
-    else q_bwd_lean_nq<8, 2>(nq, lb, variant, grid, lds, s, c, a);
+    lean_nq(nq, [&](auto n) {
+        if (lay == 0) q_bwd_lean_lb<4, 2, decltype(n)::value>(lb, variant, grid, lds, s, c, a);
+        else q_bwd_lean_lb<8, 2, decltype(n)::value>(lb, variant, grid, lds, s, c, a);
+    });
     return true;
 }
 
@@ -1940,14 +1833,6 @@ void actor_fwd_lean_variant(const bool gather, const bool noise, Rest &&...rest)
     else if (noise) actor_fwd_lean_go<D, A, NQ, false, true>(rest...);
     else actor_fwd_lean_go<D, A, NQ, false, false>(rest...);
 }
-template <int D, int A, typename... Rest>
-void actor_fwd_lean_nq(const int nq, Rest &&...rest)
-{
-    if (nq == 4) actor_fwd_lean_variant<D, A, 4>(rest...);
-    else if (nq == 8) actor_fwd_lean_variant<D, A, 8>(rest...);
-    else actor_fwd_lean_variant<D, A, 16>(rest...);
-}
-
 bool actor_fwd_lean_launch(const ActorFwdArgs &g, const int lay, const int wx, const int nq, const dim3 grid, const size_t lds, hipStream_t s)
 {
     if (!chain_lean_enabled || wx != 1 || (lay != 0 && lay != 1)) return false;
@@ -1958,8 +1843,10 @@ bool actor_fwd_lean_launch(const ActorFwdArgs &g, const int lay, const int wx, c
     a.ring_rows = g.ring.rows; a.ring_ctl = g.ring_ctl; a.advance_ring = g.advance_ring;
     a.x_data = g.x_data; a.out_done = g.out_done; a.out_rew = g.out_rew; a.a_h1 = g.a_h1; a.a_h2 = g.a_h2; a.head_part = g.head_part; a.eps_all = g.eps_all;
     const bool gather = g.idx != nullptr, noise = g.eps_all != nullptr;
-    if (lay == 0) actor_fwd_lean_nq<4, 2>(nq, gather, noise, grid, lds, s, g, a);
-    else actor_fwd_lean_nq<8, 2>(nq, gather, noise, grid, lds, s, g, a);
+    lean_nq(nq, [&](auto n) {
+        if (lay == 0) actor_fwd_lean_variant<4, 2, decltype(n)::value>(gather, noise, grid, lds, s, g, a);
+        else actor_fwd_lean_variant<8, 2, decltype(n)::value>(gather, noise, grid, lds, s, g, a);
+    });
     return true;
 }
 
@@ -2065,7 +1952,7 @@ extern "C" int cstr_q_chain_bwd_f32(const cstr_chain_net_t *nets, int n_nets, co
     if (root->mode < 1 || root->mode > 3 || root->n_parts < 1) return CSTR_E_BADARG;
     if ((root->mode == 3) != (n_nets == 1)) return CSTR_E_BADARG;
     if (!chain_dims_ok(h1, h2, root->batch, tiles)) return CSTR_E_UNSUPPORTED;
-        QBwdArgs a = {};
+    QBwdArgs a = {};
     for (int g = 0; g < n_nets; ++g) {
         const cstr_chain_net_t &n = nets[g];
         if (!n.w1 || !n.w2 || !n.w3 || !n.h1 || !n.h2) return CSTR_E_BADARG;
