@@ -19,6 +19,7 @@
 
 #include "../../include/cstr_rl_hip.h"
 #include "cstr_device.h"
+#include "cstr_gaussian_device.h"
 #include "cstr_rng_device.h"
 
 namespace {
@@ -27,7 +28,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 constexpr int BUF_OOB = 0x40000000;
 constexpr int CH_THREADS = 256, CH_WAVES = 4;
-constexpr float LOG_STD_MIN = -20.0f, LOG_STD_MAX = 2.0f;  // core/sac/policies.py:20-22
 constexpr int MAX_A = CSTR_MAX_HEAD_ACT;                   // 4
 
 // dynamic LDS layout (floats): part | red | xs | gs | panel
@@ -237,23 +237,12 @@ __device__ __forceinline__ float PartBatch::sum() const
     return s;
 }
 
-// The SAC head's sampling arithmetic for ONE (row, action) (gaussian_head_gemm_fwd_kernel's expressions): mean, raw log_std, eps ->
-// action and this action's log-prob term (Normal log-pdf minus the tanh correction)
-// in two halves, so that a kernel whose critical path needs only the action can evaluate the log-prob term later (or not at all): the
-// action half hands sd and u on, the log-prob half is the rest of the expression, operand for operand
-__device__ __forceinline__ void sample_action_act(const float mu, const float raw, const float e, float &a, float &sd, float &u)
-{
-    const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
-    sd = expf(ls);
-    u = mu + sd * e;
-    a = tanhf(u);
-}
-
+// The SAC head's sampling arithmetic for ONE (row, action) is cstr_gaussian_device.h's: sample_action_act (mean, raw log_std, eps ->
+// action, handing sd and u on) and, here, this action's log-prob term: Normal log-pdf minus the tanh correction, subtracted PER ELEMENT
+// (the head and policy launches sum the two terms separately and subtract once per row)
 __device__ __forceinline__ float sample_action_logp(const float mu, const float sd, const float u, const float a)
 {
-    const float half_log_2pi = 0.91893853320467274178f;
-    const float d = u - mu, var = sd * sd;
-    return (-(d * d) / (2.0f * var) - logf(sd) - half_log_2pi) - logf(1.0f - a * a + 1e-6f);
+    return gaussian_logp_term(mu, sd, u) - tanh_correction_term(a);
 }
 
 __device__ __forceinline__ void sample_action(const float mu, const float raw, const float e, float &a, float &lp_term)
@@ -465,10 +454,7 @@ __device__ __forceinline__ void actor_fwd_noise(const uint64_t seed, const uint6
 {
     constexpr int PAIRS = (A + 1) / 2;
     const int row = lane / PAIRS, pr = lane % PAIRS;
-    const uint64_t ctr = ctr0 + (uint64_t)(m0 + row);
-    uint32_t rr[4];
-    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)pr, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rr);
-    box_muller(rr[0], rr[1], e0, e1);
+    philox_normal_pair(seed, ctr0 + (uint64_t)(m0 + row), (uint32_t)pr, e0, e1);
 }
 
 // actor forward, (f) epilogue of the tile's first wave: bias + ReLU, head partials over these 16 columns for the HN head outputs in
@@ -1421,8 +1407,8 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_bwd_kernel(const A
 #pragma unroll
         for (int e = 0; e < 4; ++e) zm[i][e] = a.a_h2[(int64_t)(m0 + 4 * h + e) * H2 + cc];
     }
-    // (b) d(loss)/d(action) from the critic's partial sums, then the squashed-Gaussian head's backward (gaussian_head_bwd_kernel's
-    //     expressions): g_params[row] = (d/d mean | d/d log_std) -> gs[16][8] (zero-padded: the k chunk of the dz2 MFMA)
+    // (b) d(loss)/d(action) from the critic's partial sums, then the squashed-Gaussian head's backward (squashed_gaussian_grad,
+    //     as gaussian_head_bwd_kernel): g_params[row] = (d/d mean | d/d log_std) -> gs[16][8] (zero-padded: the k chunk of the dz2 MFMA)
     float o_gu = 0.0f, o_gls = 0.0f;
     if (t < 16 * A) {
         const int row = t / A, j = t % A, b = m0 + row;
@@ -1432,14 +1418,11 @@ __global__ __launch_bounds__(CH_THREADS) void sac_actor_chain_bwd_kernel(const A
         // networks x column groups are ONE run of partials (stride B * A): summed in (network, group) order
         const int np = a.n_nets * a.n_parts;
         const float ga = sum_parts(a.gact_part, np, (int64_t)B * A, (int64_t)b * A + j, (int64_t)np * B * A);
-        const float one_m = 1.0f - av * av;
         if (det) {  // a = tanh(z): d/dz = d/da * (1 - a^2)   (bias_act_bwd's tanh expression)
-            o_gu = ga * one_m;
+            o_gu = ga * (1.0f - av * av);
         } else {
             const float gl = ecv * (1.0f / (float)B);  // d(loss)/d(logp) (sac_actor_loss_kernel)
-            const float s = expf(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
-            o_gu = ga * one_m + gl * (2.0f * av * one_m / (one_m + 1e-6f));
-            o_gls = (raw >= LOG_STD_MIN && raw <= LOG_STD_MAX) ? o_gu * epv * s - gl : 0.0f;
+            squashed_gaussian_grad(av, raw, epv, ga, gl, o_gu, o_gls);
         }
         gs[row * 8 + j] = o_gu;
         gs[row * 8 + A + j] = o_gls;  // (deterministic head: zero -- the k chunk of the dz2 MFMA is 4 wide)

@@ -326,6 +326,32 @@ __device__ __forceinline__ void store_act(float *p, int64_t i, const float a[4])
 
 struct ActBounds { float lo[4], hi[4]; };
 
+// ---- one action component between the policy and the env -----------------------------------------------------------------------------
+// unscale_action (policies.py:375, :406, :413): [-1, 1] -> [lo, hi]
+__device__ __forceinline__ float unscale_action(const float v, const float lo, const float hi) { return lo + (0.5f * (v + 1.0f) * (hi - lo)); }
+
+// predict()'s np.clip for an unsquashed policy (policies.py:386): NaN passes through (fminf / fmaxf would drop it)
+__device__ __forceinline__ float clip_keep_nan(const float v, const float lo, const float hi) { return (v != v) ? v : fminf(fmaxf(v, lo), hi); }
+
+// The collect step's action scaling chain (off_policy_algorithm.py:364-411) on the policy output u: sa = buffer_action, ea = the env's
+// action. `squashed` bit 0: predict() unscales; bit 1: multi-agent algorithms -- `isinstance(any(...), spaces.Box)` is always False in
+// the reference, so neither scaling nor action noise is applied and buffer_action = action = predict() output
+// (core/common/multiagent_policy_algorithm.py:369, :391-392). z: the action noise, applied when `noisy`.
+__device__ __forceinline__ void action_scale_chain(const int squashed, const float lo, const float hi, const float u, const bool noisy, const float z,
+                                                   float &sa, float &ea)
+{
+    float v = u;
+    if (squashed & 1) v = unscale_action(v, lo, hi);  // predict()
+    if (squashed & 2) {
+        sa = ea = v;
+    } else {
+        float sc = 2.0f * ((v - lo) / (hi - lo)) - 1.0f;       // scale_action (policies.py:402)
+        if (noisy) sc = fminf(fmaxf(sc + z, -1.0f), 1.0f);     // off_policy_algorithm.py:401-402
+        sa = sc;                                               // buffer_action (:405)
+        ea = unscale_action(sc, lo, hi);                       // (:406)
+    }
+}
+
 // What one env of the fused collect step needs besides its own action (cstr_collect_step_f32): everything is wave-uniform.
 struct CollectArgs {
     cstr_ring_t ring;
@@ -360,22 +386,8 @@ __device__ __forceinline__ void collect_env_lane(const cstr_coef_t &k, const Col
     const cstr_ring_t &ring = c.ring;
     float on[2][4], sa[4], ea[4], r;
 #pragma unroll
-    for (int j = 0; j < A; ++j) {
-        const float lo = c.ab.lo[j], hi = c.ab.hi[j];
-        float v = u[j];
-        if (c.squashed & 1) v = lo + (0.5f * (v + 1.0f) * (hi - lo));  // predict(): unscale_action (policies.py:375, :413)
-        if (c.squashed & 2) {
-            // multi-agent algorithms: `isinstance(any(...), spaces.Box)` is always False in the reference, so neither
-            // scaling nor action noise is applied and buffer_action = action = predict() output
-            // (core/common/multiagent_policy_algorithm.py:369, :391-392)
-            sa[j] = ea[j] = v;
-        } else {
-            float sc = 2.0f * ((v - lo) / (hi - lo)) - 1.0f;            // scale_action (policies.py:402)
-            if (c.noise) sc = fminf(fmaxf(sc + in.z[j], -1.0f), 1.0f);  // off_policy_algorithm.py:401-402
-            sa[j] = sc;                                                  // buffer_action (:405)
-            ea[j] = lo + (0.5f * (sc + 1.0f) * (hi - lo));               // unscale_action (:406)
-        }
-    }
+    for (int j = 0; j < A; ++j)
+        action_scale_chain(c.squashed, c.ab.lo[j], c.ab.hi[j], u[j], c.noise != nullptr, c.noise ? in.z[j] : 0.0f, sa[j], ea[j]);
     int32_t st = in.st;
     const bool trunc = env_step_lane<L, INTEG>(k, in.o, ea, st, on, r);
     const bool d = trunc;
@@ -472,16 +484,8 @@ __device__ __forceinline__ void collect_env_quad(const cstr_coef_t &k, const Col
     const bool own = live && j < 4, lane0 = live && j == 0;
     // action scaling chain of component ja (lanes 0, 1)
     const float lo = ja ? c.ab.lo[1] : c.ab.lo[0], hi = ja ? c.ab.hi[1] : c.ab.hi[0];
-    float v = u, sa, ea;
-    if (c.squashed & 1) v = lo + (0.5f * (v + 1.0f) * (hi - lo));  // predict(): unscale_action (policies.py:375, :413)
-    if (c.squashed & 2) {
-        sa = ea = v;
-    } else {
-        float sc = 2.0f * ((v - lo) / (hi - lo)) - 1.0f;         // scale_action (policies.py:402)
-        if (c.noise) sc = fminf(fmaxf(sc + in.z, -1.0f), 1.0f);  // off_policy_algorithm.py:401-402
-        sa = sc;                                                  // buffer_action (:405)
-        ea = lo + (0.5f * (sc + 1.0f) * (hi - lo));               // unscale_action (:406)
-    }
+    float sa, ea;
+    action_scale_chain(c.squashed, lo, hi, u, c.noise != nullptr, in.z, sa, ea);
     // cstr_step_lane, component jj
     const float s_lo = sel4(jj, k.s_lo), s_hi = sel4(jj, k.s_hi), s_span = sel4(jj, k.s_span);
     const float an = fminf(fmaxf(ea, -1.0f), 1.0f);                                      // :399

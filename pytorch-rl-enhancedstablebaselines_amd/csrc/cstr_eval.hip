@@ -14,7 +14,10 @@
 // launches give: cstr_policy_rows_fwd_f32 (head 0: with eps = 0, i.e. the squashed Gaussian at its mode), predict()'s post-processing,
 // cstr_vec_step_f32 with the reset observations of cstr_reset_draw_f32. cstr_policy_rows_fwd_f32 has two head forms with different
 // summation orders (per-lane partial dots + shuffle tree; split-K matrix-core tile when the tile-major W2 is given and the widths are
-// <= 512): this kernel runs the one that launch would run for the same cstr_policy_mlp_t.
+// <= 512): this kernel runs the one that launch would run for the same cstr_policy_mlp_t. Both sides of the contract are the same code:
+// the layers (policy_layer), the two heads (policy_head_tree; split_k_head_chunk / _store / _out) and the host's choice between them
+// (policy_runs_split_k_head) live in cstr_policy_device.h, the element arithmetic (sample_action_act at eps = 0, head_out_act) in
+// cstr_gaussian_device.h, predict()'s unscale / clip (unscale_action, clip_keep_nan) in cstr_env_device.h.
 // An env stops when it has met its target: its state after its last counted episode (the reset draw behind that episode included) is
 // what the launch leaves; the host loop would keep stepping it until every env is done, which is NOT reproduced.
 //
@@ -28,7 +31,6 @@
 // have met their targets.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include "../../include/cstr_rl_hip.h"
 #include "cstr_device.h"
@@ -42,7 +44,6 @@ namespace {
 // also holds the env lanes' episode state, inside its register budget (200 VGPRs; the goal instantiations, whose env lanes also hold the
 // setpoint, the episode ordinal and the gap sum, 216; no scratch in either: profiles/goal_eval_kernel_resources.txt)
 constexpr int EVAL_UNROLL = 8;
-constexpr int EVAL_MAX_WIDTH_V2 = 512;  // widths up to which cstr_policy_rows_fwd_f32 takes its pipelined kernel (split-K head)
 
 struct EvalArgs {
     const float *w1, *b1, *w2, *b2, *w3, *b3, *w2s;
@@ -128,61 +129,18 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
         else policy_layer<ACT, false, true, false, EVAL_UNROLL>(h1s, S1, true, H1, a.w2, a.b2, H2, h2s, S2);
         __syncthreads();
         if (a.split_k_head) {
-            // ONE 16 x 16 tile (rows x outputs, outputs >= n_out are zero columns), K split over the waves: wave w takes the k chunks
-            // w, w + 8, ...; the partial tiles meet in LDS and are added in wave order
+            // the split-K tile of the pipelined policy kernel (cstr_policy_device.h); here the w3 quads are loaded in the loop
             f32x4 p0 = {0.0f, 0.0f, 0.0f, 0.0f}, p1 = p0;
             const float *hr = h2s + r * S2 + 4 * h;
             const float *w3r = a.w3 + (int64_t)min(r, n_out - 1) * H2;
-            for (int c = wave; c < kc2; c += POLICY_WAVES) {
-                const float4 wv = load_k4_clamped<true>(w3r, 16 * c + 4 * h, H2, r < n_out);
-                const float4 av = *reinterpret_cast<const float4 *>(hr + 16 * c);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, wv.x, p0, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, wv.y, p1, 0, 0, 0);
-                p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, wv.z, p0, 0, 0, 0);
-                p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, wv.w, p1, 0, 0, 0);
-            }
-            p0 += p1;
-            if (r < 8) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) part[(wave * POLICY_ROWS + 4 * h + e) * 8 + r] = p0[e];
-            }
+            for (int c = wave; c < kc2; c += POLICY_WAVES)
+                split_k_head_chunk(hr + 16 * c, load_k4_clamped<true>(w3r, 16 * c + 4 * h, H2, r < n_out), p0, p1);
+            split_k_head_store(part, p0 + p1);
             __syncthreads();
-            if (tid < POLICY_ROWS * 8 && (tid & 7) < n_out) {  // thread = 8 * row + output slot
-                float sum = 0.0f;
-#pragma unroll
-                for (int w = 0; w < POLICY_WAVES; ++w) sum += part[(w * POLICY_ROWS + (tid >> 3)) * 8 + (tid & 7)];
-                ps[tid] = sum + a.b3[tid & 7];
-            }
+            if (tid < POLICY_ROWS * 8 && (tid & 7) < n_out)  // thread = 8 * row + output slot
+                ps[tid] = split_k_head_out(part, tid >> 3, tid & 7, a.b3[tid & 7]);
         } else {
-            // per-lane partial dots over the row's h2 values, two rows per wave, then a shuffle tree
-            constexpr int RPW = POLICY_ROWS / POLICY_WAVES;
-            float p[RPW][2 * CSTR_MAX_HEAD_ACT];
-#pragma unroll
-            for (int q = 0; q < RPW; ++q)
-#pragma unroll
-                for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) p[q][j] = 0.0f;
-            for (int c = lane * 4; c < H2; c += 256) {
-                float4 hv[RPW];
-#pragma unroll
-                for (int q = 0; q < RPW; ++q) hv[q] = *reinterpret_cast<const float4 *>(h2s + (wave + q * POLICY_WAVES) * S2 + c);
-#pragma unroll
-                for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
-                    if (j >= n_out) break;
-                    const float4 wv = *reinterpret_cast<const float4 *>(a.w3 + (int64_t)j * H2 + c);
-#pragma unroll
-                    for (int q = 0; q < RPW; ++q) p[q][j] += (hv[q].x * wv.x + hv[q].y * wv.y) + (hv[q].z * wv.z + hv[q].w * wv.w);
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < RPW; ++q) {
-#pragma unroll
-                for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
-                    if (j >= n_out) break;
-#pragma unroll
-                    for (int o = 32; o > 0; o >>= 1) p[q][j] += __shfl_xor(p[q][j], o, 64);
-                    if (lane == 0) ps[(wave + q * POLICY_WAVES) * 8 + j] = p[q][j] + a.b3[j];
-                }
-            }
+            policy_head_tree<POLICY_ROWS / POLICY_WAVES>(h2s, S2, H2, a.w3, a.b3, n_out, ps, wave, lane);  // the first policy kernel's head
         }
         __syncthreads();
 
@@ -193,22 +151,11 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
             float ea[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int j = 0; j < A; ++j) {
-                float v;
-                if (HEAD == 1) {
-                    v = pr[j];
-                    if (a.out_act == ACT_RELU) v = fmaxf(v, 0.0f);
-                    if (a.out_act == ACT_TANH) v = tanhf(v);
-                } else {  // the squashed Gaussian at its mode: what eps = 0 gives
-                    const float mu = pr[j], raw = pr[A + j];
-                    const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
-                    const float sd = expf(ls);
-                    const float u = mu + sd * 0.0f;
-                    v = tanhf(u);
-                }
+                float v, sd, u;
+                if (HEAD == 1) v = head_out_act(pr[j], a.out_act);
+                else sample_action_act(pr[j], pr[A + j], 0.0f, v, sd, u);  // the squashed Gaussian at its mode: what eps = 0 gives
                 const float lo = a.ab.lo[j], hi = a.ab.hi[j];
-                if (a.squashed & 1) v = lo + (0.5f * (v + 1.0f) * (hi - lo));  // unscale_action (policies.py:375, :413)
-                else v = (v != v) ? v : fminf(fmaxf(v, lo), hi);                // np.clip (policies.py:386); NaN passes through
-                ea[j] = v;
+                ea[j] = (a.squashed & 1) ? unscale_action(v, lo, hi) : clip_keep_nan(v, lo, hi);  // policies.py:375, :413 | :386
             }
             float o[2][4], on[2][4], rew;
 #pragma unroll
@@ -295,15 +242,6 @@ static size_t eval_lds_bytes(const cstr_policy_mlp_t &n)
     return (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 2 * POLICY_ROWS * 8) * sizeof(float);
 }
 
-// whether cstr_policy_rows_fwd_f32 runs its split-K head for this network (its pipelined kernel): the launches here run the same one
-static bool eval_split_k_head(const cstr_policy_mlp_t &n)
-{
-    static const bool force_v1 = getenv("CSTR_POLICY_V1") != nullptr;  // the development knob of cstr_policy_rows_fwd_f32: same head as that launch
-    const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
-    const size_t v2_lds = (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 4 * POLICY_ROWS * 8) * sizeof(float);
-    return n.w2_swizzled && n.h1 <= EVAL_MAX_WIDTH_V2 && n.h2 <= EVAL_MAX_WIDTH_V2 && v2_lds <= 64 * 1024 && !force_v1;
-}
-
 extern "C" int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs,
                                       int32_t *step_count, uint64_t *pcg_state, double *static_init, int squashed, const float *act_low,
                                       const float *act_high, const int32_t *targets, int64_t n_envs, int64_t max_vec_steps,
@@ -357,8 +295,7 @@ extern "C" int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_c
     const hipError_t cp = hipMemcpyAsync(ep_done, targets, sizeof(int32_t) * (size_t)n_envs, hipMemcpyHostToDevice, s);
     if (cp != hipSuccess) return (int)cp;
     if (ep_stride == 0) return CSTR_OK;  // nothing to run: ep_done = targets = 0
-    const bool split_k = eval_split_k_head(n);
-    EvalArgs a = {n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, A, n.out_act, split_k ? 1 : 0, *coef,
+    EvalArgs a = {n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, A, n.out_act, policy_runs_split_k_head(n) ? 1 : 0, *coef,
                   env_obs, step_count, pcg_state, static_init, squashed, integrator, ab, ep_return, ep_len, ep_done, ep_stride, n_envs, max_vec_steps};
     const unsigned grid = (unsigned)((n_envs + POLICY_ROWS - 1) / POLICY_ROWS);
     const size_t lds = eval_lds_bytes(n);
@@ -432,7 +369,7 @@ extern "C" int cstr_eval_goal_episodes_f32(const cstr_policy_mlp_t *net, const c
     if (cp != hipSuccess) return (int)cp;
     if (ep_stride == 0) return CSTR_OK;  // nothing to run: ep_done = targets = 0
     GoalEvalArgs a;
-    static_cast<EvalArgs &>(a) = EvalArgs{n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, 2, n.out_act, eval_split_k_head(n) ? 1 : 0,
+    static_cast<EvalArgs &>(a) = EvalArgs{n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, 2, n.out_act, policy_runs_split_k_head(n) ? 1 : 0,
                                           *coef, env_obs, step_count, pcg_state, static_init, squashed, integrator, ab, ep_return, ep_len, ep_done,
                                           ep_stride, n_envs, max_vec_steps};
     a.target = target;

@@ -1003,29 +1003,22 @@ __global__ void squashed_gaussian_fwd_kernel(const float *__restrict__ mean, con
                                              const float *__restrict__ eps, float *__restrict__ action,
                                              float *__restrict__ logp, const int64_t batch, const int act_dim, const int in_stride)
 {
-    const float half_log_2pi = 0.91893853320467274178f;  // math.log(math.sqrt(2 * math.pi))
     for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < batch; b += (int64_t)gridDim.x * blockDim.x) {
         float lp = 0.0f, corr = 0.0f;
         for (int j = 0; j < act_dim; ++j) {
             const int64_t i = b * act_dim + j, k = b * in_stride + j;
             const float mu = mean[k];
-            const float ls = fminf(fmaxf(log_std_raw[k], LOG_STD_MIN), LOG_STD_MAX);
-            const float s = expf(ls);
-            const float u = mu + s * eps[i];  // Normal.rsample
-            const float a = tanhf(u);
+            float a, s, u;
+            sample_action_act(mu, log_std_raw[k], eps[i], a, s, u);
             action[i] = a;
-            const float d = u - mu, var = s * s;
-            lp += -(d * d) / (2.0f * var) - logf(s) - half_log_2pi;  // torch Normal.log_prob
-            corr += logf(1.0f - a * a + 1e-6f);                      // distributions.py:232
+            lp += gaussian_logp_term(mu, s, u);
+            corr += tanh_correction_term(a);
         }
         if (logp) logp[b] = lp - corr;
     }
 }
 
-// Analytic backward. With d = s*eps the Gaussian term is -eps^2/2 - ls - c, so
-//   dlogp/du_j = 2 a (1 - a^2) / (1 - a^2 + 1e-6),  da/du = 1 - a^2
-//   g_mean = G_u,  g_ls = G_u * eps * s - g_logp,  g_raw = g_ls inside the clamp range, 0 outside
-// (autograd through the reference's expression adds terms that cancel to rounding noise, ~1e-7 relative).
+// Analytic backward (squashed_gaussian_grad of cstr_gaussian_device.h): g_mean = gu, g_log_std_raw = gls.
 __global__ void squashed_gaussian_bwd_kernel(const float *__restrict__ g_action, const float *__restrict__ g_logp,
                                              const float *__restrict__ action, const float *__restrict__ log_std_raw,
                                              const float *__restrict__ eps, float *__restrict__ g_mean,
@@ -1034,16 +1027,12 @@ __global__ void squashed_gaussian_bwd_kernel(const float *__restrict__ g_action,
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < batch * act_dim; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t b = i / act_dim, j = i % act_dim, k = b * in_stride + j;
-        const float a = action[i], raw = log_std_raw[k];
-        const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
-        const float s = expf(ls);
-        const float one_m = 1.0f - a * a;
         const float gl = g_logp ? g_logp[b] : 0.0f;
         const float ga = g_action ? g_action[b * ga_stride + j] : 0.0f;  // may be a column slice of a wider gradient
-        const float gu = ga * one_m + gl * (2.0f * a * one_m / (one_m + 1e-6f));
+        float gu, gls;
+        squashed_gaussian_grad(action[i], log_std_raw[k], eps[i], ga, gl, gu, gls);
         g_mean[k] = gu;
-        const float gls = gu * eps[i] * s - gl;
-        g_log_std_raw[k] = (raw >= LOG_STD_MIN && raw <= LOG_STD_MAX) ? gls : 0.0f;
+        g_log_std_raw[k] = gls;
     }
 }
 
@@ -1058,33 +1047,24 @@ __global__ __launch_bounds__(64) void gaussian_head_fwd_kernel(float *__restrict
                                                                float *__restrict__ action, const int64_t action_stride,
                                                                float *__restrict__ logp, const int64_t batch, const int act_dim)
 {
-    const float half_log_2pi = 0.91893853320467274178f;
     const uint64_t seed = rng_ctl ? rng_ctl[0] : 0ull, base = rng_ctl ? rng_ctl[1] : 0ull;
     for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < batch; b += (int64_t)gridDim.x * blockDim.x) {
         float *pr = params + b * 2 * act_dim;
         float lp = 0.0f, corr = 0.0f;
         for (int j0 = 0; j0 < act_dim; j0 += 2) {
             float e[2];
-            if (rng_ctl) {
-                const uint64_t ctr = base + (uint64_t)b;
-                uint32_t r[4];
-                philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)(j0 >> 1), 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-                box_muller(r[0], r[1], e[0], e[1]);
-            }
+            if (rng_ctl) philox_normal_pair(seed, base + (uint64_t)b, (uint32_t)(j0 >> 1), e[0], e[1]);
             for (int jj = 0; jj < 2 && j0 + jj < act_dim; ++jj) {
                 const int j = j0 + jj;
                 if (rng_ctl) eps[b * act_dim + j] = e[jj];
                 else e[jj] = eps[b * act_dim + j];
                 float mu = pr[j], raw = pr[act_dim + j];
                 if (bias) { mu += bias[j]; raw += bias[act_dim + j]; pr[j] = mu; pr[act_dim + j] = raw; }
-                const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);  // core/sac/policies.py:173
-                const float s = expf(ls);
-                const float u = mu + s * e[jj];  // Normal.rsample (distributions.py:183)
-                const float a = tanhf(u);
+                float a, s, u;
+                sample_action_act(mu, raw, e[jj], a, s, u);
                 action[b * action_stride + j] = a;
-                const float d = u - mu, var = s * s;
-                lp += -(d * d) / (2.0f * var) - logf(s) - half_log_2pi;
-                corr += logf(1.0f - a * a + 1e-6f);  // distributions.py:232
+                lp += gaussian_logp_term(mu, s, u);
+                corr += tanh_correction_term(a);
             }
         }
         if (logp) logp[b] = lp - corr;
@@ -1107,10 +1087,7 @@ __global__ __launch_bounds__(64) void target_smooth_kernel(const float *__restri
         for (int j0 = 0; j0 < act_dim; j0 += 2) {
             float e[2] = {0.0f, 0.0f};
             if (rng_ctl) {
-                const uint64_t ctr = base + (uint64_t)b;
-                uint32_t r[4];
-                philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)(j0 >> 1), 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-                box_muller(r[0], r[1], e[0], e[1]);
+                philox_normal_pair(seed, base + (uint64_t)b, (uint32_t)(j0 >> 1), e[0], e[1]);
                 e[0] *= sigma;
                 e[1] *= sigma;
             }
@@ -1166,11 +1143,8 @@ __global__ __launch_bounds__(256) void linear_smooth_fwd_kernel(const float *__r
             const int64_t row = m0 + 4 * h + e;
             float z = 0.0f;
             if (rng_ctl) {
-                const uint64_t ctr = base + (uint64_t)row;
-                uint32_t rr[4];
                 float e0, e1;
-                philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)(r >> 1), 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rr);
-                box_muller(rr[0], rr[1], e0, e1);
+                philox_normal_pair(seed, base + (uint64_t)row, (uint32_t)(r >> 1), e0, e1);
                 e0 *= sigma;
                 e1 *= sigma;
                 z = (r & 1) ? e1 : e0;
@@ -1223,8 +1197,8 @@ __global__ __launch_bounds__(256) void linear_smooth_fwd_kernel(const float *__r
 
 // The same head INCLUDING its GEMM: the merged (mu | log_std) Linear has 2A <= 8 outputs, i.e. it is 2A dot products per
 // row, not a matrix-matrix product. One wave per row: 16-byte loads of the latent row and of the 2A weight rows, xor-shuffle
-// reductions, then the sampling arithmetic of gaussian_head_fwd_kernel on the reduced values (computed redundantly by every
-// lane, stored by lane 0). params [B][2A] is written for the backward.
+// reductions (head_tree_dots, the policy kernel's shuffle-tree head for one row), then the sampling arithmetic of
+// cstr_gaussian_device.h, as in gaussian_head_fwd_kernel, on the reduced values (computed redundantly by every lane, stored by lane 0). params [B][2A] is written for the backward.
 __global__ __launch_bounds__(1024) void gaussian_head_gemm_fwd_kernel(const float *__restrict__ hid, const float *__restrict__ w,
                                                                      const int ldh, const int K, const int64_t batch, const int act_dim,
                                                                      const float *__restrict__ bias, uint64_t *__restrict__ rng_ctl,
@@ -1232,56 +1206,34 @@ __global__ __launch_bounds__(1024) void gaussian_head_gemm_fwd_kernel(const floa
                                                                      float *__restrict__ action, const int64_t action_stride,
                                                                      float *__restrict__ logp)
 {   // (argument order: the dot products' operands first -- see linear_act_fwd_kernel)
-    const float half_log_2pi = 0.91893853320467274178f;
     const uint64_t seed = rng_ctl ? rng_ctl[0] : 0ull, base = rng_ctl ? rng_ctl[1] : 0ull;
     const int lane = threadIdx.x & 63;
     const int64_t b = blockIdx.x * (int64_t)(blockDim.x >> 6) + (threadIdx.x >> 6);
     if (b < batch) {  // (no early return: every wave reaches the ticket barrier below)
-        const float *hr = hid + b * ldh;
-        float p[2 * CSTR_MAX_HEAD_ACT];
-#pragma unroll
-        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) p[j] = 0.0f;
-        for (int c = lane * 4; c < K; c += 256) {
-            const float4 hv = *reinterpret_cast<const float4 *>(hr + c);
-#pragma unroll
-            for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
-                if (j >= 2 * act_dim) break;
-                const float4 wv = *reinterpret_cast<const float4 *>(w + (int64_t)j * K + c);
-                p[j] += (hv.x * wv.x + hv.y * wv.y) + (hv.z * wv.z + hv.w * wv.w);
-            }
-        }
+        float p[1][2 * CSTR_MAX_HEAD_ACT];
+        head_tree_dots<1>(hid + b * ldh, 0, K, w, 2 * act_dim, lane, p);  // the one-row form: the row in global memory
 #pragma unroll
         for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
             if (j >= 2 * act_dim) break;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) p[j] += __shfl_xor(p[j], o, 64);
-            p[j] += bias[j];
+            p[0][j] += bias[j];
         }
         float lp = 0.0f, corr = 0.0f;
         for (int j0 = 0; j0 < act_dim; j0 += 2) {
             float e[2] = {0.0f, 0.0f};
-            if (rng_ctl) {
-                const uint64_t ctr = base + (uint64_t)b;
-                uint32_t r[4];
-                philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)(j0 >> 1), 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
-                box_muller(r[0], r[1], e[0], e[1]);
-            }
+            if (rng_ctl) philox_normal_pair(seed, base + (uint64_t)b, (uint32_t)(j0 >> 1), e[0], e[1]);
             for (int jj = 0; jj < 2 && j0 + jj < act_dim; ++jj) {
                 const int j = j0 + jj;
                 if (!rng_ctl) e[jj] = eps[b * act_dim + j];
                 float mu = 0.0f, raw = 0.0f;
 #pragma unroll
                 for (int q = 0; q < 2 * CSTR_MAX_HEAD_ACT; ++q) {  // selects with static register indices
-                    if (q == j) mu = p[q];
-                    if (q == act_dim + j) raw = p[q];
+                    if (q == j) mu = p[0][q];
+                    if (q == act_dim + j) raw = p[0][q];
                 }
-                const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
-                const float sd = expf(ls);
-                const float u = mu + sd * e[jj];
-                const float a = tanhf(u);
-                const float d = u - mu, var = sd * sd;
-                lp += -(d * d) / (2.0f * var) - logf(sd) - half_log_2pi;
-                corr += logf(1.0f - a * a + 1e-6f);
+                float a, sd, u;
+                sample_action_act(mu, raw, e[jj], a, sd, u);
+                lp += gaussian_logp_term(mu, sd, u);
+                corr += tanh_correction_term(a);
                 if (lane == 0) {
                     if (rng_ctl) eps[b * act_dim + j] = e[jj];
                     params[b * 2 * act_dim + j] = mu;
@@ -1296,7 +1248,7 @@ __global__ __launch_bounds__(1024) void gaussian_head_gemm_fwd_kernel(const floa
         rng_ctl[1] = base + (uint64_t)batch;
 }
 
-// Backward (same algebra as squashed_gaussian_bwd_kernel) + the merged head's bias gradient (column sums over the batch).
+// Backward (squashed_gaussian_grad, as squashed_gaussian_bwd_kernel) + the merged head's bias gradient (column sums over the batch).
 // One workgroup: the batch is a few hundred rows.
 __global__ __launch_bounds__(256) void gaussian_head_bwd_kernel(const float *__restrict__ g_action, const int64_t ga_stride,
                                                                 const float *__restrict__ g_logp, const float *__restrict__ action,
@@ -1313,12 +1265,9 @@ __global__ __launch_bounds__(256) void gaussian_head_bwd_kernel(const float *__r
 #pragma unroll
         for (int j = 0; j < CSTR_MAX_HEAD_ACT; ++j) {
             if (j >= act_dim) break;
-            const float a = action[b * action_stride + j], raw = params[b * 2 * act_dim + act_dim + j];
-            const float s = expf(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
-            const float one_m = 1.0f - a * a;
             const float ga = g_action ? g_action[b * ga_stride + j] : 0.0f;
-            const float gu = ga * one_m + gl * (2.0f * a * one_m / (one_m + 1e-6f));
-            const float gls = (raw >= LOG_STD_MIN && raw <= LOG_STD_MAX) ? gu * eps[b * act_dim + j] * s - gl : 0.0f;
+            float gu, gls;
+            squashed_gaussian_grad(action[b * action_stride + j], params[b * 2 * act_dim + act_dim + j], eps[b * act_dim + j], ga, gl, gu, gls);
             g_params[b * 2 * act_dim + j] = gu;
             g_params[b * 2 * act_dim + act_dim + j] = gls;
             col[j] += gu;
@@ -1373,12 +1322,9 @@ __global__ __launch_bounds__(256) void gaussian_head_bwd_input_kernel(const floa
         const int64_t b = row0 + r;
         if (b < batch && j < act_dim) {
             const float gl = g_logp ? g_logp[b] : 0.0f;
-            const float a = action[b * action_stride + j], raw = params[b * 2 * act_dim + act_dim + j];
-            const float s = expf(fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX));
-            const float one_m = 1.0f - a * a;
             const float ga = g_action ? g_action[b * ga_stride + j] : 0.0f;
-            const float gu = ga * one_m + gl * (2.0f * a * one_m / (one_m + 1e-6f));
-            const float gls = (raw >= LOG_STD_MIN && raw <= LOG_STD_MAX) ? gu * eps[b * act_dim + j] * s - gl : 0.0f;
+            float gu, gls;
+            squashed_gaussian_grad(action[b * action_stride + j], params[b * 2 * act_dim + act_dim + j], eps[b * act_dim + j], ga, gl, gu, gls);
             g_params[b * 2 * act_dim + j] = gu;
             g_params[b * 2 * act_dim + act_dim + j] = gls;
             gp[r][j] = gu;
@@ -1510,71 +1456,30 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void policy_rows_fwd_kernel(cons
     else policy_layer<ACT, false, true>(h1s, S1, true, H1, a.w2, a.b2, H2, h2s, S2);
     __syncthreads();
 
-    // head: POLICY_ROWS / POLICY_WAVES = 2 rows per wave, evaluated together (one pass over the head's weights)
-    constexpr int RPW = POLICY_ROWS / POLICY_WAVES;
-    float p[RPW][2 * CSTR_MAX_HEAD_ACT];
-#pragma unroll
-    for (int q = 0; q < RPW; ++q)
-#pragma unroll
-        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) p[q][j] = 0.0f;
-    for (int c = lane * 4; c < H2; c += 256) {
-        float4 hv[RPW];
-#pragma unroll
-        for (int q = 0; q < RPW; ++q) hv[q] = *reinterpret_cast<const float4 *>(h2s + (wave + q * POLICY_WAVES) * S2 + c);
-#pragma unroll
-        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
-            if (j >= n_out) break;
-            const float4 wv = *reinterpret_cast<const float4 *>(a.w3 + (int64_t)j * H2 + c);
-#pragma unroll
-            for (int q = 0; q < RPW; ++q) p[q][j] += (hv[q].x * wv.x + hv[q].y * wv.y) + (hv[q].z * wv.z + hv[q].w * wv.w);
-        }
-    }
-    // the reduced head outputs meet in LDS (h1s is free again); then ONE wave samples all 16 rows, a lane per row: the
+    // head (policy_head_tree): POLICY_ROWS / POLICY_WAVES = 2 rows per wave, evaluated together (one pass over the head's weights).
+    // The reduced head outputs meet in LDS (h1s is free again); then ONE wave samples all 16 rows, a lane per row: the
     // Philox / Box-Muller / tanh / log chain is ~1.5 k instructions, run once instead of once per row
-    float *ps = h1s;  // [POLICY_ROWS][2 * CSTR_MAX_HEAD_ACT]
-#pragma unroll
-    for (int q = 0; q < RPW; ++q) {
-#pragma unroll
-        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
-            if (j >= n_out) break;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) p[q][j] += __shfl_xor(p[q][j], o, 64);
-            if (lane == 0) ps[(wave + q * POLICY_WAVES) * 2 * CSTR_MAX_HEAD_ACT + j] = p[q][j] + a.b3[j];
-        }
-    }
+    float *ps = h1s;  // [POLICY_ROWS][8]
+    policy_head_tree<POLICY_ROWS / POLICY_WAVES>(h2s, S2, H2, a.w3, a.b3, n_out, ps, wave, lane);
     __syncthreads();
     const int64_t row = m0 + lane;
     if (wave == 0 && lane < POLICY_ROWS && row < a.m) {
-        const float *pr = ps + lane * 2 * CSTR_MAX_HEAD_ACT;
+        const float *pr = ps + lane * 8;
         if (HEAD == 1) {
-            for (int j = 0; j < n_out; ++j) {
-                float v = pr[j];
-                if (a.out_act == ACT_RELU) v = fmaxf(v, 0.0f);
-                if (a.out_act == ACT_TANH) v = tanhf(v);
-                a.action[row * a.action_stride + j] = v;
-            }
+            for (int j = 0; j < n_out; ++j) a.action[row * a.action_stride + j] = head_out_act(pr[j], a.out_act);
         } else {
-            const float half_log_2pi = 0.91893853320467274178f;
             float lp = 0.0f, corr = 0.0f;
             for (int j0 = 0; j0 < a.act_dim; j0 += 2) {
                 float e[2] = {0.0f, 0.0f};
-                if (!a.eps_in) {
-                    const uint64_t ctr = base + (uint64_t)row;
-                    uint32_t rnd[4];
-                    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), (uint32_t)(j0 >> 1), 0u, (uint32_t)seed, (uint32_t)(seed >> 32), rnd);
-                    box_muller(rnd[0], rnd[1], e[0], e[1]);
-                }
+                if (!a.eps_in) philox_normal_pair(seed, base + (uint64_t)row, (uint32_t)(j0 >> 1), e[0], e[1]);
                 for (int jj = 0; jj < 2 && j0 + jj < a.act_dim; ++jj) {
                     const int j = j0 + jj;
                     if (a.eps_in) e[jj] = a.eps_in[row * a.act_dim + j];
-                    const float mu = pr[j], raw = pr[a.act_dim + j];
-                    const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
-                    const float sd = expf(ls);
-                    const float u = mu + sd * e[jj];
-                    const float act = tanhf(u);
-                    const float d = u - mu, var = sd * sd;
-                    lp += -(d * d) / (2.0f * var) - logf(sd) - half_log_2pi;
-                    corr += logf(1.0f - act * act + 1e-6f);
+                    const float mu = pr[j];
+                    float act, sd, u;
+                    sample_action_act(mu, pr[a.act_dim + j], e[jj], act, sd, u);
+                    lp += gaussian_logp_term(mu, sd, u);
+                    corr += tanh_correction_term(act);
                     a.action[row * a.action_stride + j] = act;
                 }
             }
@@ -1602,7 +1507,7 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void policy_rows_fwd_kernel(cons
 //     last-workgroup epilogue), no 256-workgroup ticket at the end of this launch.
 // Layer 1 / layer 2 values are bit-identical to the first version (same k order, same accumulator assignment); the head's
 // summation order differs (split-K MFMA instead of per-lane partial dots + shuffle tree).
-constexpr int V2_CH = 4, V2_MAX_WIDTH = 512;
+constexpr int V2_CH = 4;  // (V2_MAX_WIDTH and the choice between the two kernels: policy_runs_split_k_head, cstr_policy_device.h)
 
 // 1 KB piece `piece` of the tile-major weight copy: lane's 16 bytes through a buffer load whose per-lane offset (16 * lane) is ONE
 // register for every request and whose piece offset is scalar -- no 64-bit vector address arithmetic between the MFMAs
@@ -1947,17 +1852,9 @@ __device__ __forceinline__ void policy_rows_v2_body(const PolicyArgs &a, const R
         for (int q = 0; q < V2_HEAD_Q; ++q) {
             const int c = wave + WAVES * q;
             if (c >= kc2) break;  // wave-uniform
-            const float4 av = *reinterpret_cast<const float4 *>(hr + 16 * c);
-            p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, w3q[q].x, p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, w3q[q].y, p1, 0, 0, 0);
-            p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, w3q[q].z, p0, 0, 0, 0);
-            p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, w3q[q].w, p1, 0, 0, 0);
+            split_k_head_chunk(hr + 16 * c, w3q[q], p0, p1);  // (the w3 quads are in registers, requested before layer 1)
         }
-        p0 += p1;
-        if (r < 8) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) part[(wave * POLICY_ROWS + 4 * h + e) * 8 + r] = p0[e];
-        }
+        split_k_head_store(part, p0 + p1);
     }
     POLICY_BARRIER();
     V2_STAMP(5);
@@ -1966,36 +1863,25 @@ __device__ __forceinline__ void policy_rows_v2_body(const PolicyArgs &a, const R
     const int trow = tid >> 3, j = tid & 7;
     const int64_t row = m0 + trow;
     const bool live = tid < POLICY_ROWS * 8 && row < a.m;
-    auto head_out = [&](const int jj, const float bias) {
-        float sum = 0.0f;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) sum += part[(w * POLICY_ROWS + trow) * 8 + jj];
-        return sum + bias;
-    };
     float act_out = 0.0f;  // this lane's action component (FUSE: handed to the row's collect lane)
     if (HEAD == 1) {
         if (live && j < n_out) {
-            float v = head_out(j, b3v0);
-            if (a.out_act == ACT_RELU) v = fmaxf(v, 0.0f);
-            if (a.out_act == ACT_TANH) v = tanhf(v);
+            const float v = head_out_act(split_k_head_out(part, trow, j, b3v0), a.out_act);
             if (!FUSE || a.action) a.action[row * a.action_stride + j] = v;
             act_out = v;
         }
     } else {
         if (live && j < a.act_dim) {
-            const float half_log_2pi = 0.91893853320467274178f;
-            const float mu = head_out(j, b3v0), raw = head_out(a.act_dim + j, b3v1);
+            const float mu = split_k_head_out(part, trow, j, b3v0), raw = split_k_head_out(part, trow, a.act_dim + j, b3v1);
+            // (the draw's two halves come from two waves: no whole philox_normal_pair on one lane here)
             const float e = a.eps_in ? a.eps_in[row * a.act_dim + j] : eps_s[trow * 8 + j] * csn_s[trow * 8 + j];
-            const float ls = fminf(fmaxf(raw, LOG_STD_MIN), LOG_STD_MAX);
-            const float sd = expf(ls);
-            const float u = mu + sd * e;
-            const float act = tanhf(u);
-            const float d = u - mu, var = sd * sd;
+            float act, sd, u;
+            sample_action_act(mu, raw, e, act, sd, u);
             if (!FUSE || a.action) a.action[row * a.action_stride + j] = act;
             act_out = act;
             if (a.logp) {
-                term[trow * 8 + j] = -(d * d) / (2.0f * var) - logf(sd) - half_log_2pi;
-                term[POLICY_ROWS * 8 + trow * 8 + j] = logf(1.0f - act * act + 1e-6f);
+                term[trow * 8 + j] = gaussian_logp_term(mu, sd, u);
+                term[POLICY_ROWS * 8 + trow * 8 + j] = tanh_correction_term(act);
             }
         }
         if (a.logp) {  // kernel-uniform
@@ -2787,12 +2673,6 @@ static int check_policy_net(const cstr_policy_mlp_t *net, const float *x, int64_
     return CSTR_OK;
 }
 
-static size_t policy_v2_lds(const cstr_policy_mlp_t &n)
-{
-    const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
-    return (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 4 * POLICY_ROWS * 8) * sizeof(float);
-}
-
 extern "C" int cstr_policy_rows_fwd_f32(const cstr_policy_mlp_t *net, const float *x, int64_t ldx, const float *eps, uint64_t *rng_ctl,
                                        float *action, int64_t action_stride, float *logp, int64_t m, cstr_stream_t stream)
 {
@@ -2806,8 +2686,7 @@ extern "C" int cstr_policy_rows_fwd_f32(const cstr_policy_mlp_t *net, const floa
     const unsigned grid = (unsigned)((m + POLICY_ROWS - 1) / POLICY_ROWS);
     const bool vec0 = (n.k0 & 3) == 0 && (ldx & 3) == 0 && aligned16(x) && aligned16(n.w1);
     hipStream_t s = (hipStream_t)stream;
-    static const bool force_v1 = getenv("CSTR_POLICY_V1") != nullptr;  // development A/B knob (tools/policy_ab.py)
-    if (n.w2_swizzled && n.h1 <= V2_MAX_WIDTH && n.h2 <= V2_MAX_WIDTH && policy_v2_lds(n) <= 64 * 1024 && !force_v1) {
+    if (policy_runs_split_k_head(n)) {
         // the software-pipelined kernel (tile-major W2 required)
         const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
         const size_t lds2 = policy_v2_lds(n);
@@ -2853,7 +2732,7 @@ extern "C" int cstr_rollout_step_f32(const cstr_policy_mlp_t *net, const float *
     if (mt_state && (ring->rows >= 0xFFFFFFFFLL || ring->n_envs >= 0xFFFFFFFFLL)) return CSTR_E_UNSUPPORTED;
     // the software-pipelined kernel with a one-chunk first layer: tile-major W2, widths <= 512, k0 <= 16 in 16-byte rows
     const bool vec0 = (n.k0 & 3) == 0 && (ldx & 3) == 0 && aligned16(x) && aligned16(n.w1);
-    if (!n.w2_swizzled || n.h1 > V2_MAX_WIDTH || n.h2 > V2_MAX_WIDTH || n.k0 > 16 || !vec0 || policy_v2_lds(n) > 64 * 1024) return CSTR_E_UNSUPPORTED;
+    if (!policy_v2_fits(n) || n.k0 > 16 || !vec0) return CSTR_E_UNSUPPORTED;
     ro.k = *coef;
     ro.ring_ctl = ring_ctl;
     ro.layout = layout_of(ring->obs_dim, ring->act_dim);

@@ -1,15 +1,16 @@
 // cstr_policy_device.h -- device functions of the rollout policy network shared by its kernels (internal, included by cstr_mlp.hip
-// and cstr_eval.hip): the 16-row hidden layer on the f32 matrix cores and its operand loads. Every TU that includes this is built
-// with -ffp-contract=off.
+// and cstr_eval.hip): the 16-row hidden layer on the f32 matrix cores and its operand loads, the two head forms of
+// cstr_policy_rows_fwd_f32 (shuffle tree, split-K tile) and the host-side choice between that launch's two kernels. Every TU that
+// includes this is built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+
+#include "../../include/cstr_rl_hip.h"
+#include "cstr_gaussian_device.h"
 
 namespace {
-
-constexpr int ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2;
-
-constexpr float LOG_STD_MIN = -20.0f, LOG_STD_MAX = 2.0f;  // core/sac/policies.py:20-22
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
@@ -113,6 +114,120 @@ __device__ __forceinline__ void policy_layer(const float *__restrict__ in, const
             }
         }
     }
+}
+
+// ---- the head (n_out <= 8 outputs per row) in the two summation orders of cstr_policy_rows_fwd_f32 ----------------------------------
+// Both leave (or read) the head outputs as an image [16 rows][8 slots] in LDS.
+static_assert(2 * CSTR_MAX_HEAD_ACT == 8, "the head images are 8 slots wide");
+
+// Shuffle-tree form, the dots: RPW rows per wave (row q at row0 + q * row_step, LDS or global memory, 16-byte aligned), per-lane partial
+// dots over the row's K values against the n_out rows of w3 [n_out][K], then a 64-lane xor tree: every lane ends with the sums in p.
+template <int RPW>
+__device__ __forceinline__ void head_tree_dots(const float *row0, const int row_step, const int K, const float *w3,
+                                               const int n_out, const int lane, float (&p)[RPW][2 * CSTR_MAX_HEAD_ACT])
+{
+#pragma unroll
+    for (int q = 0; q < RPW; ++q)
+#pragma unroll
+        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) p[q][j] = 0.0f;
+    for (int c = lane * 4; c < K; c += 256) {
+        float4 hv[RPW];
+#pragma unroll
+        for (int q = 0; q < RPW; ++q) hv[q] = *reinterpret_cast<const float4 *>(row0 + q * row_step + c);
+#pragma unroll
+        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
+            if (j >= n_out) break;
+            const float4 wv = *reinterpret_cast<const float4 *>(w3 + (int64_t)j * K + c);
+#pragma unroll
+            for (int q = 0; q < RPW; ++q) p[q][j] += (hv[q].x * wv.x + hv[q].y * wv.y) + (hv[q].z * wv.z + hv[q].w * wv.w);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < RPW; ++q) {
+#pragma unroll
+        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
+            if (j >= n_out) break;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) p[q][j] += __shfl_xor(p[q][j], o, 64);
+        }
+    }
+}
+
+// Shuffle-tree head of the workgroup's 16 rows of h2s (LDS, row stride S2): wave w takes rows w, w + 8, ...; ps[row][slot] = dot + b3
+template <int RPW>
+__device__ __forceinline__ void policy_head_tree(const float *h2s, const int S2, const int H2, const float *w3,
+                                                 const float *b3, const int n_out, float *ps, const int wave, const int lane)
+{
+    float p[RPW][2 * CSTR_MAX_HEAD_ACT];
+    head_tree_dots<RPW>(h2s + wave * S2, POLICY_WAVES * S2, H2, w3, n_out, lane, p);
+#pragma unroll
+    for (int q = 0; q < RPW; ++q) {
+#pragma unroll
+        for (int j = 0; j < 2 * CSTR_MAX_HEAD_ACT; ++j) {
+            if (j >= n_out) break;
+            if (lane == 0) ps[(wave + q * POLICY_WAVES) * 8 + j] = p[q][j] + b3[j];
+        }
+    }
+}
+
+// Split-K form: ONE 16 x 16 tile (rows x outputs, outputs >= n_out are zero columns), K split over the waves: wave w takes the k chunks
+// w, w + 8, ...; the partial tiles meet in LDS (part [8 waves][16 rows][8]) and are added in wave order.
+// One k chunk: hr = this lane's four h2 values of the chunk (LDS), wv = its four w3 values (zeros for r >= n_out). The LOOP over the
+// chunks stays with its kernel: the pipelined kernel holds its w3 quads in registers, requested before layer 1, and walks them fully
+// unrolled; the evaluation kernel, which runs the network once per vec-step, loads them in the loop.
+__device__ __forceinline__ void split_k_head_chunk(const float *hr, const float4 wv, f32x4 &p0, f32x4 &p1)
+{
+    const float4 av = *reinterpret_cast<const float4 *>(hr);
+    p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, wv.x, p0, 0, 0, 0);
+    p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, wv.y, p1, 0, 0, 0);
+    p0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, wv.z, p0, 0, 0, 0);
+    p1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, wv.w, p1, 0, 0, 0);
+}
+
+// the wave's partial tile p (column = r, row = 4 * h + register) into its slice of part. The lane's coordinates are derived HERE, not
+// passed in: handed the pipelined kernel's own `wave`, `r`, `h`, two rollout instantiations came out with a vmcnt(0) behind their first
+// ring requests (profiles/actor_head_shared_ab.txt)
+__device__ __forceinline__ void split_k_head_store(float *part, const f32x4 p)
+{
+    const int wave = threadIdx.x >> 6, r = threadIdx.x & 15, h = (threadIdx.x & 63) >> 4;
+    if (r < 8) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) part[(wave * POLICY_ROWS + 4 * h + e) * 8 + r] = p[e];
+    }
+}
+
+// (behind a workgroup barrier) head output `slot` of row `row`: the partial tiles in wave order, then the bias
+__device__ __forceinline__ float split_k_head_out(const float *part, const int row, const int slot, const float bias)
+{
+    float sum = 0.0f;
+#pragma unroll
+    for (int w = 0; w < POLICY_WAVES; ++w) sum += part[(w * POLICY_ROWS + row) * 8 + slot];
+    return sum + bias;
+}
+
+// ---- which kernel cstr_policy_rows_fwd_f32 runs (host) -------------------------------------------------------------------------------
+constexpr int V2_MAX_WIDTH = 512;  // widths up to which the pipelined kernel is instantiated
+
+// dynamic LDS of the pipelined kernel: h1 | h2 images (k padded to 16, + 4 floats per row), part, then eps, 2 x term, cos | sin [16][8] each
+static inline size_t policy_v2_lds(const cstr_policy_mlp_t &n)
+{
+    const int kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
+    return (size_t)(POLICY_ROWS * (16 * kc1 + 4 + 16 * kc2 + 4) + POLICY_WAVES * POLICY_ROWS * 8 + 4 * POLICY_ROWS * 8) * sizeof(float);
+}
+
+// the pipelined kernel can run this network: tile-major W2 given, widths and LDS inside its instantiations (cstr_rollout_step_f32 needs it)
+static inline bool policy_v2_fits(const cstr_policy_mlp_t &n)
+{
+    return n.w2_swizzled && n.h1 <= V2_MAX_WIDTH && n.h2 <= V2_MAX_WIDTH && policy_v2_lds(n) <= 64 * 1024;
+}
+
+// cstr_policy_rows_fwd_f32 runs its pipelined kernel, i.e. the split-K head, for this network (else the first kernel and its shuffle-tree
+// head). The evaluation launches ask the same question and run the same head. CSTR_POLICY_V1: development A/B knob (tools/policy_ab.py),
+// read once per translation unit.
+static inline bool policy_runs_split_k_head(const cstr_policy_mlp_t &n)
+{
+    static const bool force_v1 = getenv("CSTR_POLICY_V1") != nullptr;
+    return policy_v2_fits(n) && !force_v1;
 }
 
 }  // namespace

@@ -43,4 +43,13 @@ __device__ __forceinline__ void box_muller(uint32_t a, uint32_t b, float &z0, fl
     z1 = r * sn;
 }
 
+// The sampling heads' draw: two N(0, 1) values for (row counter `ctr`, pair of actions `pair`) of the stream keyed by `seed`.
+// (A kernel that gives the two halves of Box-Muller to different lanes calls philox4x32_10 with the same words itself.)
+__device__ __forceinline__ void philox_normal_pair(const uint64_t seed, const uint64_t ctr, const uint32_t pair, float &e0, float &e1)
+{
+    uint32_t r[4];
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), pair, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    box_muller(r[0], r[1], e0, e1);
+}
+
 }  // namespace
