@@ -881,6 +881,20 @@ int cstr_gae_f32(const float *rewards, const float *values, const float *episode
 int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx, int64_t batch, float *obs, float *act, float *old_value,
                         float *old_log_prob, float *adv, float *ret, cstr_stream_t stream);
 int cstr_ppo_loss_f32(const cstr_ppo_loss_t *p, uint64_t *workspace, cstr_stream_t stream);
+/* The rollout buffer of the GOAL face (PPO / A2C on a Dict observation space; reference core/common/buffers.py:696-840
+ * DictRolloutBuffer): rb->obs is [rows][n_envs][6], the flat row [achieved_goal | desired_goal | observation] that
+ * cstr_goal_vec_step_f32 writes. rb->obs_dim must be 6 and rb->act_dim 2, the goal face's (4, 2) layout (anything else:
+ * CSTR_E_UNSUPPORTED). Observation rows (rb->obs, rows) are 8-byte aligned and move as three float2. Everything else is the statement
+ * of cstr_rollout_add_f32 / cstr_ppo_gather_f32 above -- the same kernel bodies, instantiated on the row width: the timeout bootstrap,
+ * episode_start overwritten with done after it was stored, the episode statistics, ctl, the swap-and-flatten index order and the
+ * clamped indices, and the host-side validation (CSTR_E_BADARG) before anything is enqueued. The Box-face entry points keep refusing
+ * obs_dim 6. */
+int cstr_goal_rollout_add_f32(const cstr_rollout_t *rb, int64_t *ctl, const float *rows, const float *act, const float *reward,
+                              float *episode_start, const float *value, const float *log_prob, const float *timeout,
+                              const float *terminal_value, float gamma, const float *done, float *ep_return, int32_t *ep_len,
+                              double *ep_stats, cstr_stream_t stream);
+int cstr_goal_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx, int64_t batch, float *rows, float *act, float *old_value,
+                             float *old_log_prob, float *adv, float *ret, cstr_stream_t stream);
 int cstr_grad_clip_f32(float *grad, int64_t n, float max_norm, uint64_t *workspace, float *norm_out, cstr_stream_t stream);
 
 /* ---- A2C: the loss launch and the optimiser of core/a2c/a2c.py:132-190 ---------------------------------------------------------------

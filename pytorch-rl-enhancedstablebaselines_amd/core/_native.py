@@ -45,6 +45,7 @@ SYMBOLS = (
     "cstr_multicategorical_act_f32", "cstr_multicategorical_loss_f32",
     "cstr_goal_vec_step_f32", "cstr_her_add_f32", "cstr_her_sample_f32",
     "cstr_eval_goal_episodes_f32",
+    "cstr_goal_rollout_add_f32", "cstr_goal_ppo_gather_f32",
 )
 
 

@@ -1,4 +1,4 @@
 from core.a2c.a2c import A2C
-from core.a2c.policies import MlpPolicy
+from core.a2c.policies import MlpPolicy, MultiInputPolicy
 
-__all__ = ["A2C", "MlpPolicy"]
+__all__ = ["A2C", "MlpPolicy", "MultiInputPolicy"]

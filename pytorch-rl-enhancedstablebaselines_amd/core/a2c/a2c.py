@@ -21,14 +21,19 @@ On a Discrete valve face the policy has a Categorical head and the loss launch i
 on a MultiDiscrete one (`CSTRVecEnv(multi_discrete_actions=(K0, K1))`) a MultiCategorical head, one categorical per valve, and the loss
 launch is hip_ops.multicategorical_loss (csrc/cstr_multicategorical.hip).
 
-Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN / dict policies."""
+On the goal face (`CSTRVecEnv(goal_conditioned=True)`, "MultiInputPolicy") the observation is the env's flat row [achieved_goal |
+desired_goal | observation]: a MultiInputActorCriticPolicy (first layers at K = 6) and a DictRolloutBuffer, whose add and gather launches
+are the Box face's kernels instantiated on the 6-float row; the head, GAE, loss, clip and optimiser launches are the Box face's own.
+
+Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN policies, Dict observation spaces other
+than the goal face, the goal face combined with a discrete valve face."""
 from typing import Optional, Union
 
 import numpy as np
 import torch as th
 from torch.nn import functional as F
 
-from core.a2c.policies import MlpPolicy
+from core.a2c.policies import MlpPolicy, MultiInputPolicy
 from core.common import fused, hip_ops
 from core.common.arena import FlatRMSprop, FlatRMSpropTFLike
 from core.common.buffers import RolloutBuffer
@@ -38,7 +43,7 @@ from core.common.spaces import Discrete, MultiDiscrete
 
 
 class A2C(OnPolicyAlgorithm):
-    policy_aliases = {"MlpPolicy": MlpPolicy}
+    policy_aliases = {"MlpPolicy": MlpPolicy, "MultiInputPolicy": MultiInputPolicy}
     flat_rmsprop = True  # torch.optim.RMSprop in the form below becomes arena.FlatRMSprop, RMSpropTFLike arena.FlatRMSpropTFLike
 
     def __init__(self, policy, env, learning_rate=7e-4, n_steps: int = 5, gamma: float = 0.99, gae_lambda: float = 1.0,
@@ -86,14 +91,15 @@ class A2C(OnPolicyAlgorithm):
         return b
 
     def _rows_in_place(self, rb: RolloutBuffer):
-        """The buffer's own storage as B = T * N rows (row t * N + n) -> (observations, actions, advantages, returns, order None)."""
+        """The buffer's own storage as B = T * N rows (row t * N + n) -> (observations, actions, advantages, returns, order None). On the
+        goal face the observations are the DictRolloutBuffer's flat rows, B contiguous 6-float rows."""
         assert rb.full, ""
         total = rb.buffer_size * rb.n_envs
         if rb.forced_permutations:
             rb.forced_permutations.pop(0)  # the teacher-forcing hook stays in step with get()
         elif rb.permutation_rng is None:
             np.random.permutation(total)  # the global stream moves as in the reference (buffers.py:483)
-        return (rb.observations.view(total, -1), rb.actions.view(total, -1), rb.advantages.view(total), rb.returns.view(total), None)
+        return (rb.rb.observations.view(total, -1), rb.actions.view(total, -1), rb.advantages.view(total), rb.returns.view(total), None)
 
     @staticmethod
     def _rows_get(rb: RolloutBuffer):

@@ -18,7 +18,7 @@ from core.common.vec_env import CSTRVecEnv, VecEnv, unwrap_vec_normalize
 
 class BaseAlgorithm:
     policy_aliases: dict = {}
-    goal_face_support = False  # SAC, TD3, DDPG: HER on the goal face of CSTRVecEnv (a Dict observation space)
+    goal_face_support = False  # SAC, TD3, DDPG (HER), PPO, A2C: the goal face of CSTRVecEnv (a Dict observation space)
     goal_space = None          # that Dict space; `observation_space` is then the Box of its flat row, which is what the learner sees
 
     def _accept_goal_face(self, policy, env) -> None:
@@ -27,9 +27,10 @@ class BaseAlgorithm:
 
         name = type(self).__name__
         if not self.goal_face_support:
-            raise ValueError(f"{name} does not support a Dict observation space (the goal face of the env): HER is built for SAC, TD3 and DDPG")
+            raise ValueError(f"{name} does not support a Dict observation space (the goal face of the env): HER is built for SAC, TD3 and DDPG, "
+                             "and PPO and A2C take the face with `MultiInputPolicy`")
         if not (isinstance(self.policy_class, type) and issubclass(self.policy_class, MultiInputMixin)):
-            raise ValueError(f"You must use `MultiInputPolicy` when working with dict observation space, not {policy}")  # :210
+            raise ValueError(self._goal_face_policy_message(policy))
         inner = getattr(env, "unwrapped", env)
         if unwrap_vec_normalize(env) is not None or not (isinstance(inner, CSTRVecEnv) and inner is env and inner.goal_conditioned):
             raise ValueError(f"{name} on a Dict observation space needs a bare CSTRVecEnv(goal_conditioned=True): VecNormalize and other "
@@ -41,6 +42,10 @@ class BaseAlgorithm:
         self.goal_space = env.observation_space
         one = np.ones(self.goal_space.flat_dim(), np.float32)
         self.observation_space = Box(-one, one, dtype=np.float32)
+
+    def _goal_face_policy_message(self, policy) -> str:
+        """what a policy without the CombinedExtractor is told on a Dict observation space (reference: base_class.py:210)"""
+        return f"You must use `MultiInputPolicy` when working with dict observation space, not {policy}"
 
     def __init__(self, policy, env, learning_rate, policy_kwargs: Optional[dict] = None, stats_window_size: int = 100,
                  tensorboard_log: Optional[str] = None, verbose: int = 0, device: Union[th.device, str] = "auto",
@@ -375,7 +380,7 @@ class BaseAlgorithm:
         if goal_archive != goal_env:
             raise ValueError("load(): the archive holds a model of the goal face (a Dict observation space) and the env has none"
                              if goal_archive else "load(): the env has the goal face (a Dict observation space) and the archive's model has none")
-        if goal_archive and "replay_buffer_class" not in kwargs:
+        if goal_archive and "replay_buffer_class" not in kwargs and "buffer_size" in cls._ctor_keys():  # the off-policy classes: HER
             from core.her import HerReplayBuffer
 
             ctor["replay_buffer_class"], ctor["replay_buffer_kwargs"] = HerReplayBuffer, dict(data.get("her_kwargs", {}))

@@ -11,6 +11,10 @@
 `RolloutBuffer` (reference: core/common/buffers.py:343-521) is the on-policy counterpart: SoA in HBM with the reference's array names
 and `[T, N, ...]` shapes, `add` one launch at a device-resident position, GAE one launch, minibatches gathered by the host-drawn
 permutation (the reference's `np.random.permutation` stream), copied to the device once per epoch.
+
+`DictRolloutBuffer` (reference: core/common/buffers.py:696-840) is that buffer on the goal face of `CSTRVecEnv`: the observations are
+stored as the env's flat rows `[T, N, 6]`, `observations` is the reference's dict as column views of them, and the add and gather
+launches are the same kernels instantiated on the 6-float row (hip_ops.goal_rollout_add / goal_ppo_gather).
 """
 from typing import Any, Generator, Optional, Union
 
@@ -19,7 +23,7 @@ import torch as th
 
 from core.common import hip_ops, legacy_rng
 from core.common.spaces import as_box, as_discrete, as_multi_discrete, get_action_dim, get_obs_shape
-from core.common.type_aliases import ReplayBufferSamples, RolloutBufferSamples
+from core.common.type_aliases import GoalRolloutBufferSamples, ReplayBufferSamples, RolloutBufferSamples
 from core.common.utils import get_device
 
 
@@ -328,7 +332,7 @@ class RolloutBuffer(BaseBuffer):
     def reset(self) -> None:
         """:391-401"""
         for name in self._FIELDS:
-            getattr(self, name).zero_()
+            getattr(self.rb, name).zero_()
         self.rb.ctl.zero_()
         self._adds = 0
 
@@ -418,6 +422,108 @@ class RolloutBuffer(BaseBuffer):
             part = idx[start:start + batch_size]
             mb = self._minibatch(part.shape[0])
             with th.cuda.device(self.device):
-                hip_ops.ppo_gather(self.rb, part, *mb)
+                self._gather(part, mb)
             yield mb
             start += batch_size
+
+    def _gather(self, part: th.Tensor, mb) -> None:
+        hip_ops.ppo_gather(self.rb, part, *mb)
+
+
+class DictRolloutBuffer(RolloutBuffer):
+    """reference: core/common/buffers.py:696-840, for the goal face of `CSTRVecEnv` (a Dict of achieved_goal (1,), desired_goal (1,),
+    observation (4,)).
+
+    The storage is ONE array of flat rows, `rows` [T, N, 6] = [achieved_goal | desired_goal | observation] -- what the env's
+    `step_device` hands over and what the policy's first layer reads. `observations` is the reference's dict {key: [T, N, dim]}, in
+    sorted key order, as column views of that array. `add` takes dict observations (NumPy or tensors) like the reference's, `add_device`
+    the flat rows. `get()` yields GoalRolloutBufferSamples: `observations` is the dict of the minibatch (views of `rows` [batch, 6])."""
+
+    def __init__(self, buffer_size: int, observation_space, action_space, device: Union[th.device, str] = "auto",
+                 gae_lambda: float = 1, gamma: float = 0.99, n_envs: int = 1, permutation_rng=None):
+        from core.common.vec_env.cstr_vec_env import GOAL_KEYS
+
+        spaces = getattr(observation_space, "spaces", None)
+        assert isinstance(spaces, dict), "DictRolloutBuffer must be used with Dict obs space only"  # :735
+        self.buffer_size, self.n_envs, self._adds = buffer_size, n_envs, 0
+        self.observation_space = observation_space
+        self.action_space = as_box(action_space)
+        self.obs_shape = {k: tuple(sp.shape) for k, sp in spaces.items()}
+        if tuple(self.obs_shape.keys()) != GOAL_KEYS or tuple(self.obs_shape.values()) != ((1,), (1,), (4,)):
+            raise ValueError(f"DictRolloutBuffer supports the CSTR goal face (goals (1,), observation (4,)), got {self.obs_shape}")
+        self.action_dim = get_action_dim(self.action_space)
+        self.device = get_device(device)
+        self.gae_lambda, self.gamma = gae_lambda, gamma
+        with th.cuda.device(self.device):
+            self.rb = hip_ops.DeviceRollout(buffer_size, n_envs, hip_ops.GOAL_ROW, self.action_dim, self.device, goal=True)
+        for name in self._FIELDS[1:]:
+            setattr(self, name, getattr(self.rb, name))
+        self.rows = self.rb.observations
+        self.observations = self.split(self.rows)
+        self.permutation_rng = permutation_rng
+        self.forced_permutations: list = []
+        self.last_indices: Optional[np.ndarray] = None
+        self._mb: dict = {}
+
+    @staticmethod
+    def split(rows: th.Tensor) -> dict:
+        """flat rows [..., 6] -> the dict of column views, in key order"""
+        return {"achieved_goal": rows[..., 0:1], "desired_goal": rows[..., 1:2], "observation": rows[..., 2:6]}
+
+    @classmethod
+    def from_arrays(cls, observation_space, action_space, device, observations, actions, rewards, episode_starts, values, log_probs,
+                    advantages=None, returns=None, gae_lambda: float = 1, gamma: float = 0.99) -> "DictRolloutBuffer":
+        """A FULL buffer holding the given host arrays; `observations` is the reference's dict {key: [T, N, dim]} or the flat rows
+        [T, N, 6], the others as for RolloutBuffer.from_arrays."""
+        from core.common.vec_env.cstr_vec_env import goal_dict_to_rows
+
+        rows, n_envs = np.shape(rewards)
+        buf = cls(rows, observation_space, action_space, device=device, gae_lambda=gae_lambda, gamma=gamma, n_envs=n_envs)
+        flat = goal_dict_to_rows(observations) if isinstance(observations, dict) else observations
+        given = dict(observations=flat, actions=actions, rewards=rewards, episode_starts=episode_starts, values=values,
+                     log_probs=log_probs, advantages=advantages, returns=returns)
+        for name, arr in given.items():
+            if arr is not None:
+                field = getattr(buf.rb, name)
+                field.copy_(th.from_numpy(np.ascontiguousarray(arr, dtype=np.float32)).reshape(field.shape))
+        buf._adds = rows
+        buf.rb.ctl.copy_(th.tensor([rows, 1, 0, rows], dtype=th.int64))
+        return buf
+
+    def _flat(self, obs) -> th.Tensor:
+        """dict observations (NumPy arrays or tensors) or flat rows -> device rows [N, 6]"""
+        n = self.n_envs
+        if isinstance(obs, dict):
+            obs = th.cat([self._dev(obs[k], (n, -1)) for k in self.obs_shape], dim=1)
+        return self._dev(obs, (n, hip_ops.GOAL_ROW))
+
+    def add(self, obs, action, reward, episode_start, value, log_prob) -> None:
+        """:763-803. `obs`: the dict of observations (or the flat rows)."""
+        n = self.n_envs
+        if self.full:
+            raise IndexError(f"index {self.buffer_size} is out of bounds for axis 0 with size {self.buffer_size}")
+        with th.cuda.device(self.device):
+            hip_ops.goal_rollout_add(self.rb, self._flat(obs), self._dev(action, (n, self.action_dim)), self._dev(reward, (n,)),
+                                     self._dev(episode_start, (n,)).clone(), self._dev(value, (n,)), self._dev(log_prob, (n,)))
+        self._adds += 1
+
+    def add_device(self, rows, action, reward, episode_start, value, log_prob, timeout=None, terminal_value=None, done=None,
+                   ep_return=None, ep_len=None, ep_stats=None) -> None:
+        """RolloutBuffer.add_device with the env's flat rows [N, 6] as the observation operand"""
+        if self.full:
+            raise IndexError(f"index {self.buffer_size} is out of bounds for axis 0 with size {self.buffer_size}")
+        hip_ops.goal_rollout_add(self.rb, rows, action, reward, episode_start, value, log_prob, timeout, terminal_value, self.gamma, done,
+                                 ep_return, ep_len, ep_stats)
+        self._adds += 1
+
+    def _minibatch(self, rows: int) -> GoalRolloutBufferSamples:
+        mb = self._mb.get(rows)
+        if mb is None:
+            e = lambda *s: th.empty(*s, dtype=th.float32, device=self.device)  # noqa: E731
+            flat = e(rows, hip_ops.GOAL_ROW)
+            mb = self._mb[rows] = GoalRolloutBufferSamples(self.split(flat), e(rows, self.action_dim), e(rows), e(rows), e(rows), e(rows))
+            mb.rows = flat
+        return mb
+
+    def _gather(self, part: th.Tensor, mb) -> None:
+        hip_ops.goal_ppo_gather(self.rb, part, mb.rows, *mb[1:])

@@ -12,7 +12,7 @@ returns = float64 sums of the float32 step rewards, episodes appended in sub-env
 
 `evaluate_policy_fused` (specific to this package) runs the same evaluation as ONE launch, cstr_eval_episodes_f32: every env's
 episodes are walked inside the kernel and the host reads three arrays back. It covers deterministic evaluation of a two-hidden-layer
-actor on a bare `CSTRVecEnv`; `supported()` tells whether it applies. On the goal face (`goal_conditioned=True`, SAC / TD3 / DDPG on
+actor on a bare `CSTRVecEnv`; `supported()` tells whether it applies. On the goal face (`goal_conditioned=True`, SAC / TD3 / DDPG / PPO / A2C on
 "MultiInputPolicy") the launch is cstr_eval_goal_episodes_f32, and `evaluate_goal_tracking` returns what it knows per episode beyond the
 return: the setpoint that was drawn, how far C2 ended from it and the mean absolute gap on the way.
 """
@@ -153,19 +153,20 @@ def _fused_operands(policy) -> Optional[dict]:
     """The policy's deterministic actor as operands of hip_ops.eval_episodes / goal_eval_episodes (cstr_policy_mlp_t), or None if that
     struct cannot describe it: SAC's actor without gSDE (head 0 at its mode), TD3's / DDPG's actor (head 1, tanh), `ActorCriticPolicy`
     with a two-layer `policy_net` and a linear `action_net` (head 1, no output activation, clipped instead of un-scaled). `goal`: the
-    actor sits behind a `CombinedExtractor` (MultiInputPolicy of SAC / TD3 / DDPG), i.e. its rows are the goal face's flat rows."""
+    actor sits behind a `CombinedExtractor` (MultiInputPolicy of SAC / TD3 / DDPG / PPO / A2C), i.e. its rows are the goal face's flat rows."""
     from core.common.policies import ActorCriticPolicy
     from core.common.torch_layers import CombinedExtractor, FlattenExtractor
 
     actor = getattr(policy, "actor", None)
     if isinstance(policy, ActorCriticPolicy):
-        if getattr(policy, "use_sde", False) or not isinstance(policy.features_extractor, FlattenExtractor):
+        if getattr(policy, "use_sde", False) or not isinstance(policy.features_extractor, (FlattenExtractor, CombinedExtractor)):
             return None
         net = _two_layer_mlp(policy.mlp_extractor.policy_net)
         if net is None or not isinstance(policy.action_net, nn.Linear):
             return None
         l1, l2, act = net
-        return dict(layers=(l1, l2), w3=policy.action_net.weight, b3=policy.action_net.bias, act=act, head=1, out_act=0, goal=False)
+        return dict(layers=(l1, l2), w3=policy.action_net.weight, b3=policy.action_net.bias, act=act, head=1, out_act=0,
+                    goal=isinstance(policy.features_extractor, CombinedExtractor))
     if not isinstance(actor, nn.Module) or not isinstance(getattr(actor, "features_extractor", None), (FlattenExtractor, CombinedExtractor)):
         return None
     goal = isinstance(actor.features_extractor, CombinedExtractor)

@@ -1496,7 +1496,7 @@ class FastActorCritic:
         elif getattr(policy, "multi_discrete", False):
             head = hip_ops.multicategorical_supported(policy.features_dim, tuple(int(k) for k in policy.action_space.nvec))
         else:
-            head = hip_ops.ppo_supported(policy.features_dim, n_out)
+            head = hip_ops.ppo_supported(policy.features_dim, n_out) or hip_ops.goal_onpolicy_supported(policy.features_dim, n_out)
         return (FastMLP.supported(ext.policy_net) and FastMLP.supported(ext.value_net) and head
                 and all(p.grad is not None for p in policy.parameters()))
 
@@ -1520,18 +1520,20 @@ class FastActorCritic:
         """the value estimate [n, 1]"""
         return self._run(self.vf_layers, obs, train_params)
 
-    def bufs(self, n: int, device) -> dict:
-        b = self._bufs.get(n)
+    def bufs(self, n: int, device, want_value: bool = True) -> dict:
+        """the head's static outputs, one set per (row count, want_value): a rollout step (want_value) hands its set to the buffer's add
+        launch AFTER the callbacks ran, and a callback's predict() (no value) on as many rows must not write into it"""
+        b = self._bufs.get((n, want_value))
         if b is None:
             e = lambda *sh: th.empty(*sh, dtype=th.float32, device=device)  # noqa: E731
-            b = self._bufs[n] = dict(action=e(n, self.act_dim), env_action=e(n, 2 if self.discrete else self.act_dim), log_prob=e(n))
+            b = self._bufs[(n, want_value)] = dict(action=e(n, self.act_dim), env_action=e(n, 2 if self.discrete else self.act_dim), log_prob=e(n))
         return b
 
     def _act_discrete(self, head, face, forced_shape, obs: th.Tensor, deterministic: bool, want_value: bool):
         """the rollout head of a discrete form: `head` is hip_ops.categorical_act (face = levels, queued actions int64 [n]) or
         hip_ops.multicategorical_act (face = nvec, queued actions int64 [n, 2])"""
         n = obs.shape[0]
-        b = self.bufs(n, obs.device)
+        b = self.bufs(n, obs.device, want_value)
         logits = self.logits(obs)
         values = self.values(obs) if want_value else None
         forced = None
@@ -1560,7 +1562,7 @@ class FastActorCritic:
             if self.multi_discrete:  # -> (level pair as floats [n, 2], values, log_prob, the valve pair [n, 2])
                 return self._act_discrete(hip_ops.multicategorical_act, self.nvec, (2,), obs, deterministic, want_value)
             n = obs.shape[0]
-            b = self.bufs(n, obs.device)
+            b = self.bufs(n, obs.device, want_value)
             mean = self.mean(obs)
             values = self.values(obs) if want_value else None
             eps = None

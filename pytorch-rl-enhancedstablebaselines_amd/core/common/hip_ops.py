@@ -1455,6 +1455,11 @@ def rollout_supported(obs_dim: int, act_dim: int) -> bool:
     return obs_dim in (4, 8) and act_dim in (1, 2, 4)
 
 
+def goal_onpolicy_supported(features_dim: int, act_dim: int) -> bool:
+    """PPO / A2C on the goal face: the flat row [achieved_goal | desired_goal | observation] in front of the Gaussian head's valve pair"""
+    return features_dim == GOAL_ROW and act_dim == 2
+
+
 def new_ppo_workspace(device) -> th.Tensor:
     """uint64[CSTR_PPO_WS_WORDS] (as int64) for cstr_ppo_loss_f32 / cstr_grad_clip_f32: zero before the first use, one per stream"""
     return th.zeros(nv.PPO_WS_WORDS, dtype=th.int64, device=device)
@@ -1466,9 +1471,13 @@ class DeviceRollout:
 
     FIELDS = ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns")
 
-    def __init__(self, rows: int, n_envs: int, obs_dim: int, act_dim: int, device):
-        if not rollout_supported(obs_dim, act_dim):
+    def __init__(self, rows: int, n_envs: int, obs_dim: int, act_dim: int, device, goal: bool = False):
+        """goal: the goal face's buffer, observations [T, N, GOAL_ROW] flat rows (goal_rollout_add / goal_ppo_gather serve it)"""
+        if goal and not goal_onpolicy_supported(obs_dim, act_dim):
+            raise ValueError(f"DeviceRollout on the goal face needs obs_dim {GOAL_ROW} and act_dim 2, got {obs_dim}/{act_dim}")
+        if not goal and not rollout_supported(obs_dim, act_dim):
             raise ValueError(f"DeviceRollout supports obs_dim in (4, 8) and act_dim in (1, 2, 4), got {obs_dim}/{act_dim}")
+        self.goal = bool(goal)
         if rows <= 0 or n_envs <= 0:
             raise ValueError(f"DeviceRollout needs rows >= 1 and n_envs >= 1, got {rows}/{n_envs}")
         z = lambda *s: th.zeros(*s, dtype=th.float32, device=device)  # noqa: E731
@@ -1496,6 +1505,21 @@ def rollout_add(rb: DeviceRollout, obs, act, reward, episode_start, value, log_p
                 done=None, ep_return=None, ep_len=None, ep_stats=None):
     """RolloutBuffer.add at the device position (+ reward += f32(gamma) * terminal_value where timeout: c_float rounds gamma). With `done`, `episode_start`
     becomes `done` for the next call; with ep_return / ep_len / ep_stats the episode statistics accumulate in the same launch."""
+    _rollout_add("cstr_rollout_add_f32", rb, obs, act, reward, episode_start, value, log_prob, timeout, terminal_value, gamma, done, ep_return,
+                 ep_len, ep_stats)
+
+
+def goal_rollout_add(rb: DeviceRollout, rows, act, reward, episode_start, value, log_prob, timeout=None, terminal_value=None,
+                     gamma: float = 0.99, done=None, ep_return=None, ep_len=None, ep_stats=None):
+    """`rollout_add` on the goal face's buffer: `rows` [n, GOAL_ROW] are the env's flat rows (DictRolloutBuffer.add)"""
+    if not rb.goal:
+        raise ValueError("goal_rollout_add needs a DeviceRollout of the goal face (goal=True)")
+    _rollout_add("cstr_goal_rollout_add_f32", rb, rows, act, reward, episode_start, value, log_prob, timeout, terminal_value, gamma, done,
+                 ep_return, ep_len, ep_stats)
+
+
+def _rollout_add(entry: str, rb, obs, act, reward, episode_start, value, log_prob, timeout, terminal_value, gamma, done, ep_return, ep_len,
+                 ep_stats):
     n, d, a = rb.n_envs, rb.obs_dim, rb.act_dim
     _chk(obs, "obs", (n, d), th.float32), _chk(act, "act", (n, a), th.float32)
     for t, nm in ((reward, "reward"), (episode_start, "episode_start"), (value, "value"), (log_prob, "log_prob")):
@@ -1503,9 +1527,9 @@ def rollout_add(rb: DeviceRollout, obs, act, reward, episode_start, value, log_p
     for t, nm in ((timeout, "timeout"), (terminal_value, "terminal_value"), (done, "done"), (ep_return, "ep_return")):
         _opt(t, nm, (n,), th.float32)
     _opt(ep_len, "ep_len", (n,), th.int32), _opt(ep_stats, "ep_stats", (4,), th.float64)
-    check(nv.lib().cstr_rollout_add_f32(C.byref(rb.c), ptr(rb.ctl), ptr(obs), ptr(act), ptr(reward), ptr(episode_start), ptr(value),
-                                        ptr(log_prob), ptr(timeout), ptr(terminal_value), C.c_float(gamma), ptr(done), ptr(ep_return),
-                                        ptr(ep_len), ptr(ep_stats), stream_ptr()), "cstr_rollout_add_f32")
+    check(getattr(nv.lib(), entry)(C.byref(rb.c), ptr(rb.ctl), ptr(obs), ptr(act), ptr(reward), ptr(episode_start), ptr(value), ptr(log_prob),
+                                   ptr(timeout), ptr(terminal_value), C.c_float(gamma), ptr(done), ptr(ep_return), ptr(ep_len), ptr(ep_stats),
+                                   stream_ptr()), entry)
 
 
 def gae(rb: DeviceRollout, last_values, dones, gamma: float, gae_lambda: float):
@@ -1519,12 +1543,23 @@ def gae(rb: DeviceRollout, last_values, dones, gamma: float, gae_lambda: float):
 
 def ppo_gather(rb: DeviceRollout, idx, obs, act, old_value, old_log_prob, adv, ret):
     """rows idx (flat swap_and_flatten order: env idx // T, step idx % T) of the six minibatch fields into contiguous tensors"""
+    _ppo_gather("cstr_ppo_gather_f32", rb, idx, obs, act, old_value, old_log_prob, adv, ret)
+
+
+def goal_ppo_gather(rb: DeviceRollout, idx, rows, act, old_value, old_log_prob, adv, ret):
+    """`ppo_gather` on the goal face's buffer: `rows` [b, GOAL_ROW] receives the flat observation rows (DictRolloutBuffer.get)"""
+    if not rb.goal:
+        raise ValueError("goal_ppo_gather needs a DeviceRollout of the goal face (goal=True)")
+    _ppo_gather("cstr_goal_ppo_gather_f32", rb, idx, rows, act, old_value, old_log_prob, adv, ret)
+
+
+def _ppo_gather(entry: str, rb, idx, obs, act, old_value, old_log_prob, adv, ret):
     b = idx.shape[0]
     _chk(idx, "idx", (b,), th.int64), _chk(obs, "obs", (b, rb.obs_dim), th.float32), _chk(act, "act", (b, rb.act_dim), th.float32)
     for t, nm in ((old_value, "old_value"), (old_log_prob, "old_log_prob"), (adv, "adv"), (ret, "ret")):
         _chk(t, nm, (b,), th.float32)
-    check(nv.lib().cstr_ppo_gather_f32(C.byref(rb.c), ptr(idx), C.c_int64(b), ptr(obs), ptr(act), ptr(old_value), ptr(old_log_prob), ptr(adv),
-                                       ptr(ret), stream_ptr()), "cstr_ppo_gather_f32")
+    check(getattr(nv.lib(), entry)(C.byref(rb.c), ptr(idx), C.c_int64(b), ptr(obs), ptr(act), ptr(old_value), ptr(old_log_prob), ptr(adv), ptr(ret),
+                                   stream_ptr()), entry)
 
 
 def ppo_loss(mean, log_std, actions, values, old_values, old_log_prob, adv, returns, clip_range: float, clip_range_vf: Optional[float],

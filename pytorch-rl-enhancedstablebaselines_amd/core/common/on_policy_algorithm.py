@@ -6,6 +6,11 @@ with the host: policy and value forward, the Gaussian head launch, the env step,
 only where an episode was truncated), the buffer's add launch (timeout bootstrap, next step's episode starts and the episode
 statistics included). Any other VecEnv takes the reference's NumPy loop.
 
+On the goal face (`CSTRVecEnv(goal_conditioned=True)`, "MultiInputPolicy", a `DictRolloutBuffer`) the same step runs on the env's flat
+rows [achieved_goal | desired_goal | observation]: a copy of `env.flat`, the policy at K = 6, the goal face's one-launch env step, the
+value net on the terminal rows, the add launch of the 6-float row. The NumPy loop handles dict observations through
+`policy.obs_to_tensor`, a dict `terminal_observation` included.
+
 Minibatch order: the reference draws `np.random.permutation(T * N)` per epoch from the process-global legacy stream, which the
 last seeded env reset left seeded with seed + n_envs - 1. With a device env the same sequence comes from a `RandomState` of the
 algorithm's own: it is (re)created when this model's own envs perform a seeded reset (`_numpy_reseeded`) and runs on across later
@@ -20,13 +25,15 @@ import torch as th
 
 from core.common import blas, fused
 from core.common.base_class import BaseAlgorithm
-from core.common.buffers import RolloutBuffer
+from core.common.buffers import DictRolloutBuffer, RolloutBuffer
 from core.common.callbacks import BaseCallback, MaybeCallback
 from core.common.spaces import Discrete, MultiDiscrete, as_discrete, as_multi_discrete
 from core.common.vec_env import VecEnv
+from core.common.vec_env.cstr_vec_env import goal_rows_to_dict
 
 
 class OnPolicyAlgorithm(BaseAlgorithm):
+    goal_face_support = True  # with "MultiInputPolicy": a MultiInputActorCriticPolicy and a DictRolloutBuffer
     flat_rmsprop = False  # True (A2C): torch.optim.RMSprop in the policy's kwargs becomes the flat kernel form (arena.FlatRMSprop)
 
     def __init__(self, policy, env, learning_rate, n_steps: int, gamma: float, gae_lambda: float, ent_coef: float, vf_coef: float,
@@ -59,6 +66,10 @@ class OnPolicyAlgorithm(BaseAlgorithm):
         if _init_setup_model:
             self._setup_model()
 
+    def _goal_face_policy_message(self, policy) -> str:
+        return (f"{type(self).__name__} with {policy} does not support a Dict observation space (the goal face of the env): "
+                "use `MultiInputPolicy`")
+
     def enable_graph_capture(self, enabled: bool = True) -> None:
         if enabled:
             raise NotImplementedError(f"{type(self).__name__} has no hipGraph replay: learn() launches eagerly")
@@ -69,14 +80,14 @@ class OnPolicyAlgorithm(BaseAlgorithm):
         self._setup_lr_schedule()
         blas.configure()
         self.set_random_seed(self.seed)
-        if self.rollout_buffer_class is None:
-            self.rollout_buffer_class = RolloutBuffer
-        self.rollout_buffer = self.rollout_buffer_class(self.n_steps, self.observation_space, self.action_space, device=self.device,
+        space = self.goal_space if self.goal_space is not None else self.observation_space  # the goal face: the Dict space
+        if self.rollout_buffer_class is None:  # :121-125
+            self.rollout_buffer_class = DictRolloutBuffer if self.goal_space is not None else RolloutBuffer
+        self.rollout_buffer = self.rollout_buffer_class(self.n_steps, space, self.action_space, device=self.device,
                                                         gamma=self.gamma, gae_lambda=self.gae_lambda, n_envs=self.n_envs,
                                                         **self.rollout_buffer_kwargs)
         # built on the CPU generator in the reference's construction order, then moved into ONE flat arena by the policy itself
-        self.policy = self.policy_class(self.observation_space, self.action_space, self.lr_schedule, use_sde=self.use_sde,
-                                        **self.policy_kwargs)
+        self.policy = self.policy_class(space, self.action_space, self.lr_schedule, use_sde=self.use_sde, **self.policy_kwargs)
         self.policy.to_device_arenas(self.device, flat_rmsprop=self.flat_rmsprop)
         n, dev = self.n_envs, self.device
         self._fast = None
@@ -122,6 +133,8 @@ class OnPolicyAlgorithm(BaseAlgorithm):
     # ---- rollouts -------------------------------------------------------------------------------------------------
     def _device_rollout(self) -> bool:
         rb = self.rollout_buffer
+        if self._denv is not None and self._denv.goal_conditioned:  # the flat rows of the goal face into a DictRolloutBuffer
+            return self._fused_learner and type(rb) is DictRolloutBuffer and rb.n_envs == self._denv.num_envs and rb.action_dim == self._denv.act_dim
         return (self._denv is not None and self._fused_learner and type(rb) is RolloutBuffer and rb.n_envs == self._denv.num_envs
                 and rb.obs_shape[0] == self._denv.obs_dim
                 and rb.action_dim == (1 if self._denv.discrete_actions is not None else self._denv.act_dim))  # Discrete: the index; MultiDiscrete: the level pair, act_dim floats
@@ -171,7 +184,7 @@ class OnPolicyAlgorithm(BaseAlgorithm):
         if self._starts_on == "host":  # the NumPy loop ran last (fused_learner was switched): its episode starts come over
             self._episode_starts_dev.copy_(th.as_tensor(np.asarray(self._last_episode_starts, np.float32)))
         self._starts_on = "device"
-        self._obs_prev.copy_(env.obs)
+        self._obs_prev.copy_(env.flat if env.goal_conditioned else env.obs)
         actions, values, log_probs, env_actions = fast.act(self._obs_prev)
         new_obs, rewards, dones, timeouts, terminal_obs = env.step_device(env_actions)
         with th.no_grad():
@@ -184,6 +197,8 @@ class OnPolicyAlgorithm(BaseAlgorithm):
         """The reference's NumPy statements (:199-245) for a VecEnv that is not device-resident."""
         if isinstance(self._last_obs, th.Tensor):  # the device env's own observation tensor: the step below overwrites it
             self._last_obs = self._last_obs.cpu().numpy()
+            if self.goal_space is not None:  # the goal face's flat rows: the host loop keeps the dict, as env.step returns it
+                self._last_obs = goal_rows_to_dict(self._last_obs)
         if self._starts_on == "device":  # the device rollout ran last: its episode starts come over
             self._last_episode_starts = self._episode_starts_dev.cpu().numpy() > 0
         self._starts_on = "host"

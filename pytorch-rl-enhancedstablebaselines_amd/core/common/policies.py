@@ -312,3 +312,10 @@ class ActorCriticPolicy(BasePolicy):
                 return self._fast_pairs(observation, deterministic, False)[0]
             return self.fast.act(observation.float().contiguous(), deterministic, want_value=False)[0]
         return self.get_distribution(observation).get_actions(deterministic=deterministic)
+
+
+class MultiInputActorCriticPolicy(MultiInputMixin, ActorCriticPolicy):
+    """reference: core/common/policies.py:839-910 -- ActorCriticPolicy behind a CombinedExtractor on a Dict observation space (the goal
+    face of the env). The extractor has no parameters: state-dict keys, construction order and seeded initial weights are
+    ActorCriticPolicy's on a features_dim = 6 input. On the device the observation already is the flat row, which passes through the
+    extractor unchanged; `predict()` takes a dict of arrays or flat rows."""

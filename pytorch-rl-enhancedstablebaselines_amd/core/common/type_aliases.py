@@ -31,6 +31,22 @@ class RolloutBufferSamples(NamedTuple):
     returns: th.Tensor
 
 
+class DictRolloutBufferSamples(NamedTuple):
+    """reference: core/common/type_aliases.py (DictRolloutBufferSamples); observations: {key: tensor}"""
+    observations: dict
+    actions: th.Tensor
+    old_values: th.Tensor
+    old_log_prob: th.Tensor
+    advantages: th.Tensor
+    returns: th.Tensor
+
+
+class GoalRolloutBufferSamples(DictRolloutBufferSamples):
+    """What DictRolloutBuffer.get() yields: the reference's six fields, and beside them `rows` [batch, 6], the flat rows the dict's
+    tensors are column views of (what the kernels read)."""
+    rows: th.Tensor = None
+
+
 class RolloutReturn(NamedTuple):
     episode_timesteps: int
     n_episodes: int

@@ -1,4 +1,4 @@
-from core.ppo.policies import MlpPolicy
+from core.ppo.policies import MlpPolicy, MultiInputPolicy
 from core.ppo.ppo import PPO
 
-__all__ = ["PPO", "MlpPolicy"]
+__all__ = ["PPO", "MlpPolicy", "MultiInputPolicy"]

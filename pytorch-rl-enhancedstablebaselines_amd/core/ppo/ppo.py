@@ -17,7 +17,12 @@ row is the level pair as two floats.
 
 Another optimiser class (`RMSpropTFLike` included: its flat kernel form is A2C's alone) runs as itself on the arena's parameter views.
 
-Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN / dict policies."""
+On the goal face (`CSTRVecEnv(goal_conditioned=True)`, "MultiInputPolicy") the observation is the env's flat row [achieved_goal |
+desired_goal | observation]: a MultiInputActorCriticPolicy (first layers at K = 6) and a DictRolloutBuffer, whose add and gather launches
+are the Box face's kernels instantiated on the 6-float row; the head, GAE, loss, clip and optimiser launches are the Box face's own.
+
+Not built: gSDE, hipGraph replay, data-parallel training, VecNormalize, MultiBinary actions, CNN policies, Dict observation spaces other
+than the goal face, the goal face combined with a discrete valve face."""
 import warnings
 from typing import Optional, Union
 
@@ -29,11 +34,11 @@ from core.common.logger import DeviceMean
 from core.common.on_policy_algorithm import OnPolicyAlgorithm
 from core.common.spaces import Discrete, MultiDiscrete
 from core.common.utils import get_schedule_fn
-from core.ppo.policies import MlpPolicy
+from core.ppo.policies import MlpPolicy, MultiInputPolicy
 
 
 class PPO(OnPolicyAlgorithm):
-    policy_aliases = {"MlpPolicy": MlpPolicy}
+    policy_aliases = {"MlpPolicy": MlpPolicy, "MultiInputPolicy": MultiInputPolicy}
 
     def __init__(self, policy, env, learning_rate=3e-4, n_steps: int = 2048, batch_size: int = 64, n_epochs: int = 10, gamma: float = 0.99,
                  gae_lambda: float = 0.95, clip_range=0.2, clip_range_vf=None, normalize_advantage: bool = True, ent_coef: float = 0.0,
@@ -103,17 +108,20 @@ class PPO(OnPolicyAlgorithm):
     def _minibatch_forward_fused(self, rd, clip_range: float, clip_range_vf: Optional[float], sums: th.Tensor):
         """evaluate_actions on the per-layer kernels and the loss launch; returns what the backward needs"""
         fast, pol = self._fast, self.policy
-        b = self._bufs(rd.observations.shape[0])
+        obs = getattr(rd, "rows", None)  # the goal face: the flat rows behind the sample's dict (DictRolloutBuffer.get)
+        if obs is None:
+            obs = rd.observations
+        b = self._bufs(obs.shape[0])
         if fast.discrete or fast.multi_discrete:  # a (Multi)Categorical head: g_mean holds d loss / d logits, there is no log_std
-            logits = fast.logits(rd.observations, train_params=True)
-            values = fast.values(rd.observations, train_params=True)
+            logits = fast.logits(obs, train_params=True)
+            values = fast.values(obs, train_params=True)
             fast.discrete_loss(hip_ops.CAT_PPO, logits.detach(), rd.actions, values.detach(), rd.advantages, rd.returns,
                                self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"], b["g_value"], self._ws,
                                old_values=rd.old_values, old_log_prob=rd.old_log_prob, clip_range=clip_range, clip_range_vf=clip_range_vf,
                                scalars_out=self._scalars, scalars_sum=sums, log_prob_out=b["log_prob"] if self.debug_capture else None)
             return logits, values, b
-        mean = fast.mean(rd.observations, train_params=True)
-        values = fast.values(rd.observations, train_params=True)
+        mean = fast.mean(obs, train_params=True)
+        values = fast.values(obs, train_params=True)
         hip_ops.ppo_loss(mean.detach(), pol.log_std.detach(), rd.actions, values.detach(), rd.old_values, rd.old_log_prob, rd.advantages,
                          rd.returns, clip_range, clip_range_vf, self.normalize_advantage, self.ent_coef, self.vf_coef, b["g_mean"],
                          b["g_value"], pol.log_std.grad, self._ws, scalars_out=self._scalars, scalars_sum=sums,

@@ -5,6 +5,8 @@
 //   * RolloutBuffer.add at the device-resident position, with the timeout bootstrap reward += gamma * V(terminal observation);
 //   * compute_returns_and_advantage (GAE), one lane per env, NumPy's expression order and rounding points (bit-identical);
 //   * the minibatch gather by flat swap_and_flatten indices (index i = env i / T, step i % T);
+//   * the same add and gather on the goal face's buffer (cstr_goal_rollout_add_f32 / cstr_goal_ppo_gather_f32): the kernels are
+//     templated on the row width, a 6-float row [achieved_goal | desired_goal | observation] moves as three float2;
 //   * everything between evaluate_actions' outputs and loss.backward() (ppo.py:213-264): advantage normalisation, the diagonal
 //     Gaussian's log-prob and entropy, ratio and clipped surrogate, the (clipped) value loss, the six logged scalars and the
 //     gradients w.r.t. the action mean, the value and log_std (diag_gaussian_loss_kernel<A, true> of cstr_onpolicy_device.h);
@@ -30,6 +32,7 @@
 namespace {
 
 constexpr uint32_t PPO_STREAM_TAG = 0x990A11C7u;  // counter word 3: never shares counters with the other heads' streams
+constexpr int GOAL_ROW = 6;  // the goal face's flat row [achieved_goal | desired_goal | observation] (cstr_goal_vec_step_f32)
 
 // on_policy_algorithm.py:199-216: one lane per env
 template <int A>
@@ -79,6 +82,20 @@ __global__ __launch_bounds__(64) void diag_gaussian_act_kernel(const float *__re
         rng_ctl[1] = base + (uint64_t)n;
 }
 
+// One observation row: float4 pieces where the width is a multiple of four (16-byte-aligned rows), float2 pieces otherwise (the goal
+// face's 6-float rows, 8-byte aligned)
+template <int D> __device__ __forceinline__ void copy_obs_row(const float *src, float *dst)
+{
+    constexpr int V = D % 4 == 0 ? 4 : 2;
+    static_assert(D % V == 0, "an observation row is a whole number of vector pieces");
+#pragma unroll
+    for (int c = 0; c < D; c += V) {
+        float v[V];
+        load_row<V>(src + c, v);
+        store_row<V>(dst + c, v);
+    }
+}
+
 // buffers.py:440-479 + on_policy_algorithm.py:236-245. ctl = { pos, full, ticket, adds }; a full buffer takes no row.
 template <int D, int A>
 __global__ __launch_bounds__(64) void rollout_add_kernel(const cstr_rollout_t rb, int64_t *__restrict__ ctl, const float *__restrict__ obs,
@@ -94,12 +111,7 @@ __global__ __launch_bounds__(64) void rollout_add_kernel(const cstr_rollout_t rb
     if (room) {
         for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
             const int64_t r = pos * n + i;
-#pragma unroll
-            for (int c = 0; c < D; c += 4) {
-                float v[4];
-                load_row<4>(obs + i * D + c, v);
-                store_row<4>(rb.obs + r * D + c, v);
-            }
+            copy_obs_row<D>(obs + i * D, rb.obs + r * D);
             float a[A];
             load_row<A>(act + i * A, a);
             store_row<A>(rb.act + r * A, a);
@@ -167,12 +179,7 @@ __global__ __launch_bounds__(256) void ppo_gather_kernel(const cstr_rollout_t rb
         int64_t i = idx[b];
         i = i < 0 ? 0 : (i >= total ? total - 1 : i);
         const int64_t env = i / T, step = i - env * T, r = step * N + env;
-#pragma unroll
-        for (int c = 0; c < D; c += 4) {
-            float v[4];
-            load_row<4>(rb.obs + r * D + c, v);
-            store_row<4>(obs + b * D + c, v);
-        }
+        copy_obs_row<D>(rb.obs + r * D, obs + b * D);
         float a[A];
         load_row<A>(rb.act + r * A, a);
         store_row<A>(act + b * A, a);
@@ -194,20 +201,101 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(float *__restrict__ gra
     if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
 }
 
-// act_dim 1: the Categorical head's action row, the index as one float (cstr_categorical.hip)
-inline bool widths_ok(int obs_dim, int act_dim) { return (obs_dim == 4 || obs_dim == 8) && (act_dim == 1 || act_dim == 2 || act_dim == 4); }
+// The two faces of the rollout buffer's entry points: which widths they take and how an observation row must be aligned.
+// BoxFace: act_dim 1 is the Categorical head's action row, the index as one float (cstr_categorical.hip).
+struct BoxFace {
+    static bool widths_ok(int obs_dim, int act_dim) { return (obs_dim == 4 || obs_dim == 8) && (act_dim == 1 || act_dim == 2 || act_dim == 4); }
+    static bool obs_aligned(const void *p) { return aligned16(p); }
+};
+// GoalFace: the flat row of cstr_goal_vec_step_f32, GOAL_ROW floats, and the valve pair
+struct GoalFace {
+    static bool widths_ok(int obs_dim, int act_dim) { return obs_dim == GOAL_ROW && act_dim == 2; }
+    static bool obs_aligned(const void *p) { return aligned8(p); }
+};
 
-inline int rollout_check(const cstr_rollout_t *rb)
+template <class Face> inline int rollout_check(const cstr_rollout_t *rb)
 {
     if (!rb || !rb->obs || !rb->act || !rb->rew || !rb->episode_start || !rb->values || !rb->log_probs || !rb->advantages ||
         !rb->returns || rb->rows <= 0 || rb->n_envs <= 0 || rb->obs_dim <= 0 || rb->act_dim <= 0)
         return CSTR_E_BADARG;
-    if (!widths_ok(rb->obs_dim, rb->act_dim)) return CSTR_E_UNSUPPORTED;
+    if (!Face::widths_ok(rb->obs_dim, rb->act_dim)) return CSTR_E_UNSUPPORTED;
     if (rb->rows > CSTR_PPO_MAX_ROWS / rb->n_envs) return CSTR_E_UNSUPPORTED;
-    if (!aligned16(rb->obs) || !row_aligned(rb->act, rb->act_dim) || !aligned4(rb->rew) || !aligned4(rb->episode_start) ||
+    if (!Face::obs_aligned(rb->obs) || !row_aligned(rb->act, rb->act_dim) || !aligned4(rb->rew) || !aligned4(rb->episode_start) ||
         !aligned4(rb->values) || !aligned4(rb->log_probs) || !aligned4(rb->advantages) || !aligned4(rb->returns))
         return CSTR_E_BADARG;
     return 0;
+}
+
+// validation of both add entry points, then the launch of the face's instantiation
+template <class Face>
+inline int rollout_add(const cstr_rollout_t *rb, int64_t *ctl, const float *obs, const float *act, const float *reward, float *episode_start,
+                       const float *value, const float *log_prob, const float *timeout, const float *terminal_value, float gamma,
+                       const float *done, float *ep_return, int32_t *ep_len, double *ep_stats, cstr_stream_t stream)
+{
+    const int rc = rollout_check<Face>(rb);
+    if (rc) return rc;
+    if (!ctl || !obs || !act || !reward || !episode_start || !value || !log_prob) return CSTR_E_BADARG;
+    if ((timeout == nullptr) != (terminal_value == nullptr)) return CSTR_E_BADARG;
+    if ((ep_stats == nullptr) != (ep_return == nullptr) || (ep_stats == nullptr) != (ep_len == nullptr) || (ep_stats && !done))
+        return CSTR_E_BADARG;  // the episode statistics: all three or none, and they need `done`
+    if ((done && (!aligned4(done) || overlap(done, rb->n_envs, episode_start, rb->n_envs))) ||
+        (ep_stats && (!aligned8(ep_stats) || !aligned4(ep_return) || !aligned4(ep_len))))
+        return CSTR_E_BADARG;
+    if (!aligned8(ctl) || !Face::obs_aligned(obs) || !row_aligned(act, rb->act_dim) || !aligned4(reward) || !aligned4(episode_start) ||
+        !aligned4(value) || !aligned4(log_prob) || (timeout && (!aligned4(timeout) || !aligned4(terminal_value))))
+        return CSTR_E_BADARG;
+    const int64_t n = rb->n_envs, cells = rb->rows * n;
+    if (overlap(rb->obs, cells * rb->obs_dim, obs, n * rb->obs_dim) || overlap(rb->act, cells * rb->act_dim, act, n * rb->act_dim) ||
+        overlap(rb->rew, cells, reward, n) || overlap(rb->episode_start, cells, episode_start, n) || overlap(rb->values, cells, value, n) ||
+        overlap(rb->log_probs, cells, log_prob, n))
+        return CSTR_E_BADARG;
+    const unsigned grid = lane_grid(n, 64, 4096);
+    const int d = rb->obs_dim, a = rb->act_dim;
+#define ADD_LAUNCH(D, A)                                                                                                              \
+    rollout_add_kernel<D, A><<<grid, 64, 0, (hipStream_t)stream>>>(*rb, ctl, obs, act, reward, episode_start, value, log_prob, timeout, \
+                                                                  terminal_value, gamma, done, ep_return, ep_len, ep_stats)
+    if (d == GOAL_ROW) ADD_LAUNCH(GOAL_ROW, 2);  // GoalFace alone gets here: BoxFace::widths_ok has refused the width
+    else if (d == 4 && a == 1) ADD_LAUNCH(4, 1);
+    else if (a == 1) ADD_LAUNCH(8, 1);
+    else if (d == 4 && a == 2) ADD_LAUNCH(4, 2);
+    else if (d == 4) ADD_LAUNCH(4, 4);
+    else if (a == 2) ADD_LAUNCH(8, 2);
+    else ADD_LAUNCH(8, 4);
+#undef ADD_LAUNCH
+    return (int)hipGetLastError();
+}
+
+// validation of both gather entry points, then the launch of the face's instantiation
+template <class Face>
+inline int ppo_gather(const cstr_rollout_t *rb, const int64_t *idx, int64_t batch, float *obs, float *act, float *old_value,
+                      float *old_log_prob, float *adv, float *ret, cstr_stream_t stream)
+{
+    const int rc = rollout_check<Face>(rb);
+    if (rc) return rc;
+    if (!idx || !obs || !act || !old_value || !old_log_prob || !adv || !ret || batch <= 0) return CSTR_E_BADARG;
+    if (batch > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
+    if (!aligned8(idx) || !Face::obs_aligned(obs) || !row_aligned(act, rb->act_dim) || !aligned4(old_value) || !aligned4(old_log_prob) ||
+        !aligned4(adv) || !aligned4(ret))
+        return CSTR_E_BADARG;
+    const int64_t cells = rb->rows * rb->n_envs;
+    const Buf outs[6] = {{obs, batch * rb->obs_dim}, {act, batch * rb->act_dim}, {old_value, batch}, {old_log_prob, batch}, {adv, batch},
+                         {ret, batch}};
+    const Buf ins[7] = {{rb->obs, cells * rb->obs_dim}, {rb->act, cells * rb->act_dim}, {rb->values, cells}, {rb->log_probs, cells},
+                        {rb->advantages, cells}, {rb->returns, cells}, {idx, 2 * batch}};
+    if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
+    const unsigned grid = lane_grid(batch, 256, 2048);
+    const int d = rb->obs_dim, a = rb->act_dim;
+#define GATHER_LAUNCH(D, A) \
+    ppo_gather_kernel<D, A><<<grid, 256, 0, (hipStream_t)stream>>>(*rb, idx, batch, obs, act, old_value, old_log_prob, adv, ret)
+    if (d == GOAL_ROW) GATHER_LAUNCH(GOAL_ROW, 2);  // GoalFace alone gets here: BoxFace::widths_ok has refused the width
+    else if (d == 4 && a == 1) GATHER_LAUNCH(4, 1);
+    else if (a == 1) GATHER_LAUNCH(8, 1);
+    else if (d == 4 && a == 2) GATHER_LAUNCH(4, 2);
+    else if (d == 4) GATHER_LAUNCH(4, 4);
+    else if (a == 2) GATHER_LAUNCH(8, 2);
+    else GATHER_LAUNCH(8, 4);
+#undef GATHER_LAUNCH
+    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -246,36 +334,17 @@ extern "C" int cstr_rollout_add_f32(const cstr_rollout_t *rb, int64_t *ctl, cons
                                     const float *terminal_value, float gamma, const float *done, float *ep_return, int32_t *ep_len,
                                     double *ep_stats, cstr_stream_t stream)
 {
-    const int rc = rollout_check(rb);
-    if (rc) return rc;
-    if (!ctl || !obs || !act || !reward || !episode_start || !value || !log_prob) return CSTR_E_BADARG;
-    if ((timeout == nullptr) != (terminal_value == nullptr)) return CSTR_E_BADARG;
-    if ((ep_stats == nullptr) != (ep_return == nullptr) || (ep_stats == nullptr) != (ep_len == nullptr) || (ep_stats && !done))
-        return CSTR_E_BADARG;  // the episode statistics: all three or none, and they need `done`
-    if ((done && (!aligned4(done) || overlap(done, rb->n_envs, episode_start, rb->n_envs))) ||
-        (ep_stats && (!aligned8(ep_stats) || !aligned4(ep_return) || !aligned4(ep_len))))
-        return CSTR_E_BADARG;
-    if (!aligned8(ctl) || !aligned16(obs) || !row_aligned(act, rb->act_dim) || !aligned4(reward) || !aligned4(episode_start) ||
-        !aligned4(value) || !aligned4(log_prob) || (timeout && (!aligned4(timeout) || !aligned4(terminal_value))))
-        return CSTR_E_BADARG;
-    const int64_t n = rb->n_envs, cells = rb->rows * n;
-    if (overlap(rb->obs, cells * rb->obs_dim, obs, n * rb->obs_dim) || overlap(rb->act, cells * rb->act_dim, act, n * rb->act_dim) ||
-        overlap(rb->rew, cells, reward, n) || overlap(rb->episode_start, cells, episode_start, n) || overlap(rb->values, cells, value, n) ||
-        overlap(rb->log_probs, cells, log_prob, n))
-        return CSTR_E_BADARG;
-    const unsigned grid = lane_grid(n, 64, 4096);
-    const int d = rb->obs_dim, a = rb->act_dim;
-#define ADD_LAUNCH(D, A)                                                                                                              \
-    rollout_add_kernel<D, A><<<grid, 64, 0, (hipStream_t)stream>>>(*rb, ctl, obs, act, reward, episode_start, value, log_prob, timeout, \
-                                                                  terminal_value, gamma, done, ep_return, ep_len, ep_stats)
-    if (d == 4 && a == 1) ADD_LAUNCH(4, 1);
-    else if (a == 1) ADD_LAUNCH(8, 1);
-    else if (d == 4 && a == 2) ADD_LAUNCH(4, 2);
-    else if (d == 4) ADD_LAUNCH(4, 4);
-    else if (a == 2) ADD_LAUNCH(8, 2);
-    else ADD_LAUNCH(8, 4);
-#undef ADD_LAUNCH
-    return (int)hipGetLastError();
+    return rollout_add<BoxFace>(rb, ctl, obs, act, reward, episode_start, value, log_prob, timeout, terminal_value, gamma, done, ep_return,
+                                ep_len, ep_stats, stream);
+}
+
+extern "C" int cstr_goal_rollout_add_f32(const cstr_rollout_t *rb, int64_t *ctl, const float *rows, const float *act, const float *reward,
+                                         float *episode_start, const float *value, const float *log_prob, const float *timeout,
+                                         const float *terminal_value, float gamma, const float *done, float *ep_return, int32_t *ep_len,
+                                         double *ep_stats, cstr_stream_t stream)
+{
+    return rollout_add<GoalFace>(rb, ctl, rows, act, reward, episode_start, value, log_prob, timeout, terminal_value, gamma, done, ep_return,
+                                 ep_len, ep_stats, stream);
 }
 
 extern "C" int cstr_gae_f32(const float *rewards, const float *values, const float *episode_starts, const float *last_values,
@@ -302,31 +371,13 @@ extern "C" int cstr_gae_f32(const float *rewards, const float *values, const flo
 extern "C" int cstr_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx, int64_t batch, float *obs, float *act, float *old_value,
                                    float *old_log_prob, float *adv, float *ret, cstr_stream_t stream)
 {
-    const int rc = rollout_check(rb);
-    if (rc) return rc;
-    if (!idx || !obs || !act || !old_value || !old_log_prob || !adv || !ret || batch <= 0) return CSTR_E_BADARG;
-    if (batch > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
-    if (!aligned8(idx) || !aligned16(obs) || !row_aligned(act, rb->act_dim) || !aligned4(old_value) || !aligned4(old_log_prob) ||
-        !aligned4(adv) || !aligned4(ret))
-        return CSTR_E_BADARG;
-    const int64_t cells = rb->rows * rb->n_envs;
-    const Buf outs[6] = {{obs, batch * rb->obs_dim}, {act, batch * rb->act_dim}, {old_value, batch}, {old_log_prob, batch}, {adv, batch},
-                         {ret, batch}};
-    const Buf ins[7] = {{rb->obs, cells * rb->obs_dim}, {rb->act, cells * rb->act_dim}, {rb->values, cells}, {rb->log_probs, cells},
-                        {rb->advantages, cells}, {rb->returns, cells}, {idx, 2 * batch}};
-    if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
-    const unsigned grid = lane_grid(batch, 256, 2048);
-    const int d = rb->obs_dim, a = rb->act_dim;
-#define GATHER_LAUNCH(D, A) \
-    ppo_gather_kernel<D, A><<<grid, 256, 0, (hipStream_t)stream>>>(*rb, idx, batch, obs, act, old_value, old_log_prob, adv, ret)
-    if (d == 4 && a == 1) GATHER_LAUNCH(4, 1);
-    else if (a == 1) GATHER_LAUNCH(8, 1);
-    else if (d == 4 && a == 2) GATHER_LAUNCH(4, 2);
-    else if (d == 4) GATHER_LAUNCH(4, 4);
-    else if (a == 2) GATHER_LAUNCH(8, 2);
-    else GATHER_LAUNCH(8, 4);
-#undef GATHER_LAUNCH
-    return (int)hipGetLastError();
+    return ppo_gather<BoxFace>(rb, idx, batch, obs, act, old_value, old_log_prob, adv, ret, stream);
+}
+
+extern "C" int cstr_goal_ppo_gather_f32(const cstr_rollout_t *rb, const int64_t *idx, int64_t batch, float *rows, float *act,
+                                        float *old_value, float *old_log_prob, float *adv, float *ret, cstr_stream_t stream)
+{
+    return ppo_gather<GoalFace>(rb, idx, batch, rows, act, old_value, old_log_prob, adv, ret, stream);
 }
 
 extern "C" int cstr_ppo_loss_f32(const cstr_ppo_loss_t *p, uint64_t *workspace, cstr_stream_t stream)

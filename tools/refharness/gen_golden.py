@@ -2,7 +2,7 @@
 """Generate tests/golden/*.npz by running the UNMODIFIED reference in the dev container.
 
 Usage (dev container only; /root/reference must exist):
-    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,ppo_discrete,a2c_discrete,ppo_multidiscrete,a2c_multidiscrete,init,vecenv,callbacks,rmsprop_tf]
+    python tools/refharness/gen_golden.py [--only env,sampler,replay,sac,sac_sde,td3,bcq,ppo,a2c,dqn,ppo_discrete,a2c_discrete,ppo_multidiscrete,a2c_multidiscrete,ppo_goal,a2c_goal,init,vecenv,callbacks,rmsprop_tf]
 
 Every array written is data (inputs + the reference's outputs); no reference source is copied.
 Injected quantities (never produced by the stand-in gymnasium): initial states, actions, batches.
@@ -1286,6 +1286,18 @@ def gen_bcq_predict():
 
 
 # --------------------------------------------------------------------------------------- PPO
+def _inner_env(e):
+    """the TwoSeriesCSTREnv behind a DummyVecEnv member: itself, or what the goal face's wrapper (_make_goal_venv) holds as `inner`"""
+    return getattr(e.unwrapped, "inner", e.unwrapped)
+
+
+def _obs_rows(o):
+    """observations as one float32 array; a dict of the goal face becomes its flat rows [achieved_goal | desired_goal | observation]"""
+    if isinstance(o, dict):
+        return np.concatenate([np.asarray(o[k], np.float32) for k in ("achieved_goal", "desired_goal", "observation")], axis=-1)
+    return np.array(o, np.float32).copy()
+
+
 class _PpoHooks:
     """Records, around the UNMODIFIED reference: every standard-normal draw of Normal.rsample, every np.random.permutation, the infos of
     every vec-step, and -- read from train()'s frame when it calls clip_grad_norm_ (core/ppo/ppo.py:277) -- each minibatch's values,
@@ -1337,7 +1349,8 @@ class _PpoHooks:
         self._dummy.step_wait = self._step_wait
 
 
-def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, target_kl=None, venv=None, **kw):
+def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, target_kl=None, venv=None,
+             policy="MlpPolicy", gaussian=None, **kw):
     """One teacher-forceable PPO iteration of the reference on the CPU: _setup_learn (which resets the envs), THEN the step counters of
     the envs in `late` are set near the time limit (set before learn() they would be undone by the reset), collect_rollouts, train()."""
     from core.common.logger import Logger
@@ -1349,23 +1362,23 @@ def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=()
     pk = {} if net_arch is None else dict(policy_kwargs=dict(net_arch=net_arch))
     with _w.catch_warnings():
         _w.simplefilter("ignore")
-        model = PPO("MlpPolicy", _make_venv(n_envs) if venv is None else venv, seed=seed, device="cpu", n_steps=n_steps, batch_size=batch_size, n_epochs=n_epochs,
+        model = PPO(policy, _make_venv(n_envs) if venv is None else venv, seed=seed, device="cpu", n_steps=n_steps, batch_size=batch_size, n_epochs=n_epochs,
                     learning_rate=lr, ent_coef=ent_coef, target_kl=target_kl, **pk, **kw)
     model.set_logger(Logger(folder=None, output_formats=[]))
     out = _flat_sd("before/policy", model.policy.state_dict())
     out["state_dict_keys"] = np.array(list(model.policy.state_dict().keys()))
     _, cb = model._setup_learn(n_envs * n_steps, None, True, "PPO", False)
     for i, st in late:
-        model.env.envs[i].unwrapped.current_step = st
-    out["init_obs"] = np.array(model._last_obs, np.float32).copy()
-    out["init_steps"] = np.array([e.unwrapped.current_step for e in model.env.envs], np.int32)
+        _inner_env(model.env.envs[i]).current_step = st
+    out["init_obs"] = _obs_rows(model._last_obs)
+    out["init_steps"] = np.array([_inner_env(e).current_step for e in model.env.envs], np.int32)
     with _PpoHooks() as hk:
         assert model.collect_rollouts(model.env, cb, model.rollout_buffer, n_steps)
         rb = model.rollout_buffer
         for f in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
-            out[f"rollout/{f}"] = np.array(getattr(rb, f), np.float32).copy()
+            out[f"rollout/{f}"] = _obs_rows(getattr(rb, f))
         assert len(hk.infos) == n_steps
-        if venv is None:  # a Discrete face samples through multinomial: no Normal draws; the indices are rollout/actions
+        if (venv is None if gaussian is None else gaussian):  # a Discrete face samples through multinomial: no Normal draws; the indices are rollout/actions
             assert len(hk.draws) == n_steps
             out["eps"] = np.stack([d.numpy() for d in hk.draws])
         else:
@@ -1375,7 +1388,7 @@ def _ppo_run(seed, n_envs, n_steps, batch_size, n_epochs, net_arch=None, late=()
         with th.no_grad():
             out["last_values"] = model.policy.predict_values(obs_as_tensor(model._last_obs, model.device)).numpy().reshape(-1).copy()
         out["dones"] = np.array(model._last_episode_starts, np.float32)
-        out["last_obs"] = np.array(model._last_obs, np.float32).copy()
+        out["last_obs"] = _obs_rows(model._last_obs)
         model.train()
     out["permutations"] = np.stack(hk.perms) if hk.perms else np.zeros((0, n_envs * n_steps), np.int64)
     for k, mb in enumerate(hk.minibatches):
@@ -1483,7 +1496,7 @@ class _A2cHooks(_PpoHooks):
 
 
 def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=0.01, iterations=2, opt_state=True, venv=None,
-             policy_kwargs=None, **kw):
+             policy_kwargs=None, policy="MlpPolicy", gaussian=None, **kw):
     """`iterations` consecutive teacher-forceable A2C iterations of the reference on the CPU (rollout, train, rollout, train: the
     second step meets a non-zero square_avg): _setup_learn, THEN the step counters of the envs in `late` are set near the time limit."""
     from core.a2c.a2c import A2C
@@ -1493,16 +1506,16 @@ def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=
     pk = {} if net_arch is None else dict(policy_kwargs=dict(net_arch=net_arch))
     if policy_kwargs:  # e.g. the optimiser class and its kwargs (gen_rmsprop_tf)
         pk = dict(policy_kwargs=dict(pk.get("policy_kwargs", {}), **policy_kwargs))
-    model = A2C("MlpPolicy", _make_venv(n_envs) if venv is None else venv, seed=seed, device="cpu", n_steps=n_steps, learning_rate=lr,
+    model = A2C(policy, _make_venv(n_envs) if venv is None else venv, seed=seed, device="cpu", n_steps=n_steps, learning_rate=lr,
                 ent_coef=ent_coef, **pk, **kw)
     model.set_logger(Logger(folder=None, output_formats=[]))
     out = _flat_sd("before/policy", model.policy.state_dict())
     out["state_dict_keys"] = np.array(list(model.policy.state_dict().keys()))
     _, cb = model._setup_learn(iterations * n_envs * n_steps, None, True, "A2C", False)
     for i, st in late:
-        model.env.envs[i].unwrapped.current_step = st
-    out["init_obs"] = np.array(model._last_obs, np.float32).copy()
-    out["init_steps"] = np.array([e.unwrapped.current_step for e in model.env.envs], np.int32)
+        _inner_env(model.env.envs[i]).current_step = st
+    out["init_obs"] = _obs_rows(model._last_obs)
+    out["init_steps"] = np.array([_inner_env(e).current_step for e in model.env.envs], np.int32)
     names = [n for n, _ in model.policy.named_parameters()]
     n_trunc = 0
     for it in range(iterations):
@@ -1511,9 +1524,9 @@ def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=
             assert model.collect_rollouts(model.env, cb, model.rollout_buffer, n_steps)
             rb = model.rollout_buffer
             for f in ("observations", "actions", "rewards", "episode_starts", "values", "log_probs", "advantages", "returns"):
-                out[f"{pre}rollout/{f}"] = np.array(getattr(rb, f), np.float32).copy()
+                out[f"{pre}rollout/{f}"] = _obs_rows(getattr(rb, f))
             assert len(hk.infos) == n_steps
-            if venv is None:  # a Discrete face samples through multinomial: no Normal draws; the indices are rollout/actions
+            if (venv is None if gaussian is None else gaussian):  # a Discrete face samples through multinomial: no Normal draws; the indices are rollout/actions
                 assert len(hk.draws) == n_steps
                 out[pre + "eps"] = np.stack([d.numpy() for d in hk.draws])
             else:
@@ -1524,7 +1537,7 @@ def _a2c_run(seed, n_envs, n_steps=5, net_arch=None, late=(), lr=3e-3, ent_coef=
             with th.no_grad():
                 out[pre + "last_values"] = model.policy.predict_values(obs_as_tensor(model._last_obs, model.device)).numpy().reshape(-1).copy()
             out[pre + "dones"] = np.array(model._last_episode_starts, np.float32)
-            out[pre + "last_obs"] = np.array(model._last_obs, np.float32).copy()
+            out[pre + "last_obs"] = _obs_rows(model._last_obs)
             model._update_current_progress_remaining(model.num_timesteps, iterations * n_envs * n_steps)
             model.train()
         assert len(hk.perms) == 1 and len(hk.minibatches) == 1
@@ -2335,10 +2348,79 @@ def gen_her():
     save("her_buffer_kat.npz", **out)
 
 
+# ------------------------------------------------------------------- PPO / A2C on the goal face
+GOAL_ONPOLICY_TARGETS = (0.15, 0.20, 0.25, 0.30, 0.35, 0.18, 0.22, 0.28)  # fixed per-env setpoints, mol/L
+
+
+def _goal_onpolicy_venv(n_envs):
+    return _make_goal_venv((400,) * n_envs, GOAL_ONPOLICY_TARGETS[:n_envs])
+
+
+def _goal_run_extras(out, n_envs):
+    """what a goal-face fixture records beside the Box face's: the per-env targets; init_obs / rollout/observations / last_obs already are
+    the flat rows [achieved_goal | desired_goal | observation] (_obs_rows)"""
+    out["targets"] = np.array(GOAL_ONPOLICY_TARGETS[:n_envs], np.float32)
+    return out
+
+
+def gen_ppo_goal():
+    """PPO("MultiInputPolicy") of the UNMODIFIED reference (MultiInputActorCriticPolicy, CombinedExtractor, DictRolloutBuffer:
+    core/common/policies.py:839-910, core/common/buffers.py:696-840) on the goal-face harness env: ppo_goal_train_kat_small.npz (4 envs,
+    n_steps 8, batch 12, 3 epochs, nets [32, 32], lr 3e-3), ppo_goal_train_kat_default.npz (class-default nets, 8 envs, n_steps 16,
+    batch 64, 2 epochs) and ppo_goal_predict_kat.npz (16 seeded dict observations)."""
+    late = ((1, 396), (2, 399), (3, 395))
+    small = dict(n_envs=4, n_steps=8, batch_size=12, n_epochs=3, net_arch=[32, 32], late=late, policy="MultiInputPolicy", gaussian=True)
+    for seed in range(7, 80):
+        model, out, hk = _ppo_run(seed, venv=_goal_onpolicy_venv(4), **small)
+        clipped = max(float(mb["scalars"][5]) for mb in hk.minibatches)
+        if clipped > 0 and int(out["n_truncations"]) >= 2 and _ppo_margins_ok(hk, 0.2, None):
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the small goal-face PPO fixture")
+    assert type(model.rollout_buffer).__name__ == "DictRolloutBuffer" and type(model.policy).__name__ == "MultiInputActorCriticPolicy"
+    assert model.policy.features_dim == 6 and tuple(out["before/policy/mlp_extractor.policy_net.0.weight"].shape) == (32, 6)
+    print(f"ppo goal small: seed {seed}, max clip_fraction {clipped:.3f}, truncations {int(out['n_truncations'])}")
+    save("ppo_goal_train_kat_small.npz", **_goal_run_extras(out, 4))
+    model, o, hk = _ppo_run(11, n_envs=8, n_steps=16, batch_size=64, n_epochs=2, late=((0, 390), (5, 397), (6, 399)), venv=_goal_onpolicy_venv(8),
+                            policy="MultiInputPolicy", gaussian=True)
+    assert int(o["n_truncations"]) >= 2 and _ppo_margins_ok(hk, 0.2, None)
+    save("ppo_goal_train_kat_default.npz", **_goal_run_extras(o, 8))
+    # predict: the trained small model on seeded dict observations, deterministic and sampled (the draw is recorded), and predict_values
+    model, _, _ = _ppo_run(int(out["seed"]), venv=_goal_onpolicy_venv(4), **small)
+    rows = np.random.default_rng(99).uniform(-1, 1, (16, 6)).astype(np.float32)
+    obs = {"achieved_goal": rows[:, 0:1].copy(), "desired_goal": rows[:, 1:2].copy(), "observation": rows[:, 2:6].copy()}
+    p = _flat_sd("policy", model.policy.state_dict())
+    p["rows"], p["net_arch"], p["seed"] = rows, np.array([32, 32], np.int64), out["seed"]
+    p["deterministic"], _ = model.predict(obs, deterministic=True)
+    with _PpoHooks() as hk:
+        p["sampled"], _ = model.predict(obs, deterministic=False)
+        p["eps"] = hk.draws[0].numpy()
+    with th.no_grad():
+        p["values"] = model.policy.predict_values({k: th.as_tensor(v) for k, v in obs.items()}).numpy()
+    save("ppo_goal_predict_kat.npz", **p)
+
+
+def gen_a2c_goal():
+    """A2C("MultiInputPolicy") of the unmodified reference on the goal-face harness env, two consecutive iterations:
+    a2c_goal_train_kat_small.npz (4 envs, n_steps 5, nets [32, 32], ent_coef 0.01, lr 3e-3; the clip engaged in both steps)."""
+    late = ((1, 396), (2, 399), (3, 392))
+    for seed in range(7, 80):
+        model, out = _a2c_run(seed, n_envs=4, net_arch=[32, 32], late=late, venv=_goal_onpolicy_venv(4), policy="MultiInputPolicy", gaussian=True)
+        norms = [float(out[f"it{k}/grad_norm"]) for k in range(2)]
+        trunc = [int(out[f"it{k}/timeouts"].sum()) for k in range(2)]
+        if min(norms) > 1.05 * 0.5 and min(trunc) >= 1:
+            break
+    else:
+        raise RuntimeError("no seed met the conditions of the small goal-face A2C fixture")
+    assert type(model.rollout_buffer).__name__ == "DictRolloutBuffer" and str(out["optimizer"]) == "RMSprop"
+    print(f"a2c goal small: seed {seed}, gradient norms {norms}, truncations {trunc}")
+    save("a2c_goal_train_kat_small.npz", **_goal_run_extras(out, 4))
+
+
 GENS = {"her": gen_her, "her_learners": gen_her_learners, "ppo_multidiscrete": gen_ppo_multidiscrete, "a2c_multidiscrete": gen_a2c_multidiscrete, "ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn,
-        "rmsprop_tf": gen_rmsprop_tf}
+        "rmsprop_tf": gen_rmsprop_tf, "ppo_goal": gen_ppo_goal, "a2c_goal": gen_a2c_goal}
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
