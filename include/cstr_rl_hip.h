@@ -1085,7 +1085,7 @@ int cstr_multicategorical_loss_f32(const cstr_multicategorical_loss_t *p, uint64
  * [achieved_goal | desired_goal | observation], rows 8-byte aligned. The reward is the reference's concentration term
  * (twoseriescstr.py:288-291) on (achieved, desired), in f32 and in this order:
  *   C2 = s_lo2 + (ag + 1) * s_span2 / 2;  T = s_lo2 + (dg + 1) * s_span2 / 2;  ne = |C2 - T| / conc_span;  r = -5 (ne ne) - 2 ne.
- * All three entry points validate on the host (NULL, non-positive sizes, a ring that is not (4, 2), misaligned or overlapping rows ->
+ * All four entry points validate on the host (NULL, non-positive sizes, a ring that is not (4, 2), misaligned or overlapping rows ->
  * CSTR_E_BADARG / CSTR_E_UNSUPPORTED) and then only enqueue. */
 #define CSTR_HER_FUTURE 0  /* GoalSelectionStrategy (core/her/goal_selection_strategy.py:12-17) */
 #define CSTR_HER_FINAL 1
@@ -1129,6 +1129,37 @@ int cstr_goal_vec_step_f32(const cstr_coef_t *coef, int integrator, int obs_dim,
  * change. The last workgroup advances ring_ctl like cstr_replay_add_f32. */
 int cstr_her_add_f32(const cstr_ring_t *ring, const cstr_her_t *her, int64_t *ring_ctl, const float *obs_rows, const float *next_rows,
                      const float *act, const float *rew, const float *done, const float *timeout, cstr_stream_t stream);
+
+/* The rollout's vec-step on the goal face in ONE launch, a lane per env: what cstr_collect_step_rng_f32 is on the Box face. Per env, in
+ * this order:
+ *   1. the action scaling chain of cstr_collect_step_f32 on policy_out [N][2] (squashed bit 0 set: tanh output, unscaled first; clear: a
+ *      warm-up action already in [act_low, act_high], both HOST pointers to 2 floats); noise [N][2] or NULL is added to the scaled action
+ *      and clipped to [-1, 1] (fminf / fmaxf as there: a NaN action with noise is clipped, without noise it reaches the env); the buffer
+ *      action is the scaled action, the env's action its unscale;
+ *   2. the body of cstr_goal_vec_step_f32 (the same device function): env step, goal reward on the lane's own target, the NaN path,
+ *      truncation, auto-reset from the env's PCG64 stream, the Philox target redraw with episode[i] += 1, step_count;
+ *   3. the body of cstr_her_add_f32 (the same device function) at ring_ctl[0]: the invalidation loop, the ring row (observation = the
+ *      env's own flat row as it stood before the step, next observation = the terminal observation where done, the buffer action),
+ *      ep_start / ep_length / cur_ep_start, row_valid / valid_bits;
+ *   4. Monitor's statistics as in cstr_collect_step_f32: ep_return [N] accumulates the reward; where an episode ends, ep_stats double[4]
+ *      += {1, return, step count the episode reached} by f64 atomicAdd (count and length sum exact in any order; the return sum may
+ *      differ in its last f64 bits between runs); both NULL or both given;
+ *   5. the last workgroup advances ring_ctl and, if policy_rng_ctl != NULL, adds policy_rng_advance to its offset word.
+ * State: env_obs [N][4] i/o; rows [N][6] i/o, the env's flat rows: each lane reads its own row as the transition's observation before
+ * it writes what VecEnv.step returns over it; step_count, pcg_state, static_init (or NULL), target, episode (or NULL: targets stay),
+ * goal_seed, goal_index_offset, goal_lo, goal_hi as in cstr_goal_vec_step_f32. N = ring->n_envs.
+ * Outputs, each may be NULL: reward_out / done_out / timeout_out [N], next_rows_out [N][6] (the next_rows of cstr_goal_vec_step_f32).
+ * Every array above and every ring / side array is bit-identical to: the chain's f32 statements, cstr_goal_vec_step_f32, cstr_her_add_f32.
+ * CSTR_E_BADARG: NULL required pointers, n_envs <= 0, act_high <= act_low, goal_lo > goal_hi with episode, misaligned rows, anything the
+ * launch writes overlapping anything else it touches, ep_return / ep_stats not given together. CSTR_E_UNSUPPORTED: a ring that is not
+ * (4, 2), obs_dim != 4, squashed with any bit but bit 0 (bit 1 = multi-agent), an unknown integrator, sizes beyond CSTR_HER_MAX_*.
+ * All checked before anything is enqueued. */
+int cstr_goal_collect_step_f32(const cstr_coef_t *coef, int integrator, int obs_dim, const cstr_ring_t *ring, const cstr_her_t *her,
+                               int64_t *ring_ctl, float *env_obs, float *rows, int32_t *step_count, uint64_t *pcg_state, double *static_init,
+                               float *target, int32_t *episode, uint64_t goal_seed, int64_t goal_index_offset, float goal_lo, float goal_hi,
+                               const float *policy_out, int squashed, const float *act_low, const float *act_high, const float *noise,
+                               float *reward_out, float *done_out, float *timeout_out, float *next_rows_out, float *ep_return,
+                               double *ep_stats, uint64_t *policy_rng_ctl, uint64_t policy_rng_advance, cstr_stream_t stream);
 
 /* HerReplayBuffer.sample (her_replay_buffer.py:186-384) in one launch on the legacy MT19937 stream:
  *   k = randint(0, n_valid, batch) (what np.random.choice(valid_indices, batch) draws) -> the k-th valid (row, env), row-major;

@@ -46,6 +46,7 @@ SYMBOLS = (
     "cstr_goal_vec_step_f32", "cstr_her_add_f32", "cstr_her_sample_f32",
     "cstr_eval_goal_episodes_f32",
     "cstr_goal_rollout_add_f32", "cstr_goal_ppo_gather_f32",
+    "cstr_goal_collect_step_f32",
 )
 
 

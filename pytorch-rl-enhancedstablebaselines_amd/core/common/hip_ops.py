@@ -1890,6 +1890,38 @@ def her_add(ring: DeviceRing, her: DeviceHer, obs_rows, next_rows, act, rew, don
                                     ptr(timeout), stream_ptr()), "cstr_her_add_f32")
 
 
+def goal_collect_step(coef, integrator: str, ring: DeviceRing, her: DeviceHer, env_obs, rows, step_count, pcg_state, target, policy_out, squashed,
+                      act_low, act_high, noise=None, static_init=None, episode=None, goal_seed: int = 0, goal_index_offset: int = 0,
+                      goal_lo: float = 0.0, goal_hi: float = 0.0, reward_out=None, done_out=None, timeout_out=None, next_rows_out=None,
+                      ep_return=None, ep_stats=None, rng_advance=None):
+    """The rollout's vec-step on the goal face in one launch (cstr_goal_collect_step_f32): the action scaling chain on `policy_out`,
+    `goal_vec_step` on the env's own arrays (`rows` = the env's flat rows, read as the transition's observation and then overwritten),
+    `her_add` at the device-resident ring position and Monitor's episode statistics. `rng_advance` as in `collect_step`."""
+    n = ring.n_envs
+    _chk(env_obs, "env_obs", (n, 4), th.float32), _chk(rows, "rows", (n, GOAL_ROW), th.float32), _chk(step_count, "step_count", (n,), th.int32)
+    _chk(pcg_state, "pcg_state", (n, nv.PCG_STATE_WORDS), th.int64), _opt(static_init, "static_init", (n, 4), th.float64)
+    _chk(target, "target", (n,), th.float32), _opt(episode, "episode", (n,), th.int32)
+    _chk(policy_out, "policy_out", (n, 2), th.float32), _opt(noise, "noise", (n, 2), th.float32)
+    for t, nm in ((reward_out, "reward_out"), (done_out, "done_out"), (timeout_out, "timeout_out"), (ep_return, "ep_return")):
+        _opt(t, nm, (n,), th.float32)
+    _opt(next_rows_out, "next_rows_out", (n, GOAL_ROW), th.float32), _opt(ep_stats, "ep_stats", (4,), th.float64)
+    if (ep_return is None) != (ep_stats is None):
+        raise ValueError("ep_return and ep_stats go together")
+    if len(act_low) != 2 or len(act_high) != 2:
+        raise ValueError("act_low/act_high need 2 entries")
+    lo = (C.c_float * 2)(*[float(v) for v in act_low])
+    hi = (C.c_float * 2)(*[float(v) for v in act_high])
+    rng_ctl, rng_count = rng_advance if rng_advance is not None else (None, 0)
+    _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    check(nv.lib().cstr_goal_collect_step_f32(C.byref(coef), C.c_int(INTEGRATORS[integrator]), C.c_int(4), C.byref(ring.c), C.byref(her.c),
+                                              ptr(ring.ctl), ptr(env_obs), ptr(rows), ptr(step_count), ptr(pcg_state), ptr(static_init),
+                                              ptr(target), ptr(episode), C.c_uint64(int(goal_seed) & (2**64 - 1)),
+                                              C.c_int64(int(goal_index_offset)), C.c_float(goal_lo), C.c_float(goal_hi), ptr(policy_out),
+                                              C.c_int(int(squashed)), lo, hi, ptr(noise), ptr(reward_out), ptr(done_out), ptr(timeout_out),
+                                              ptr(next_rows_out), ptr(ep_return), ptr(ep_stats), ptr(rng_ctl), C.c_uint64(int(rng_count)),
+                                              stream_ptr()), "cstr_goal_collect_step_f32")
+
+
 def her_sample(coef, ring: DeviceRing, her: DeviceHer, mt_state, batch: int, nb_virtual: int, strategy: str, out_obs, out_act, out_next_obs,
                out_done, out_rew, out_row_idx=None, out_env_idx=None, out_goal_row=None, forced_row=None, forced_env=None, forced_goal=None):
     """HerReplayBuffer.sample in one launch (cstr_her_sample_f32); her.status[0] tells afterwards whether anything was valid."""

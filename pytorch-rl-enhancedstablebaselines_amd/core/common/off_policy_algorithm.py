@@ -29,6 +29,10 @@ from core.common.vec_env import CSTRVecEnv, VecEnv
 # the captured iteration's rollout as ONE launch (policy + collect step + replay index draw; hip_ops.rollout_step). "0": the
 # separate policy / collect / sampler launches (A/B knob; both forms are bit-identical, tests/test_rollout_step.py)
 FUSED_ROLLOUT = os.environ.get("CSTR_FUSED_ROLLOUT", "1") != "0"
+# the goal face's vec-step as ONE launch (hip_ops.goal_collect_step). "0": the element-wise action chain, the row copy, the env step,
+# the HER add and the statistics ops as separate launches, never replayed from a graph (A/B knob; both forms are bit-identical,
+# tests/test_goal_collect.py)
+HER_FUSED_COLLECT = os.environ.get("CSTR_HER_FUSED_COLLECT", "1") != "0"
 
 
 class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
@@ -157,7 +161,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         self._graph = None  # captured graphs hold the old ring's pointers
 
     def _her_path(self) -> bool:
-        """The device rollout on the goal face: policy forward on the flat rows, cstr_goal_vec_step_f32, cstr_her_add_f32."""
+        """The device rollout on the goal face: policy forward on the flat rows, then cstr_goal_collect_step_f32 (env step + HER add)."""
         from core.her import HerReplayBuffer
 
         env, rb = self._denv, self.replay_buffer
@@ -237,7 +241,10 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
     def _graph_eligible(self, callback: BaseCallback) -> bool:
         from core.common.noise import DeviceNormalActionNoise, LegacyStreamNormalActionNoise, LegacyStreamOUActionNoise
 
-        return (self._fast_path() and self._callback_allows_replay(callback)
+        # the goal face replays its fused collect launch only, and only behind the eager iteration that made HerReplayBuffer.sample's
+        # one-time "has an episode ended" check (`_eager_iteration`): an unchecked model stays eager until it has
+        her = HER_FUSED_COLLECT and self._her_checked and self._her_path()
+        return ((her or self._fast_path()) and self._callback_allows_replay(callback)
                 and (self.action_noise is None
                      or isinstance(self.action_noise, (DeviceNormalActionNoise, LegacyStreamNormalActionNoise, LegacyStreamOUActionNoise)))
                 and self.train_freq == TrainFreq(1, TrainFrequencyUnit.STEP)
@@ -544,7 +551,16 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         self._last_obs = self._rollout_obs()
 
     def _collect_one_her(self, env: CSTRVecEnv, rb, action_noise, learning_starts: int) -> None:
-        """One vec-step on the goal face, entirely in HBM and without a host synchronisation: reference statements :561 (_sample_action,
+        """One vec-step on the goal face, entirely in HBM and without a host synchronisation: reference statements :561 (_sample_action),
+        :564 (env.step) and :580 (_store_transition -> HerReplayBuffer.add) with Monitor's episode statistics in one HIP launch after the
+        actor forward (cstr_goal_collect_step_f32): `_collect_one_fused`, whose observation (`_rollout_obs`) and launch
+        (`_device_collect_step`) are the goal face's here."""
+        if not HER_FUSED_COLLECT:
+            return self._collect_one_her_elementwise(env, rb, action_noise, learning_starts)
+        self._collect_one_fused(env, rb, action_noise, learning_starts)
+
+    def _collect_one_her_elementwise(self, env: CSTRVecEnv, rb, action_noise, learning_starts: int) -> None:
+        """`_collect_one_her` as the launches the fused one replaces (CSTR_HER_FUSED_COLLECT=0, the A/B form): :561 (_sample_action,
         :364-411: the same float32 expressions as the fused collect step, here as element-wise device ops), :564 (env.step =
         cstr_goal_vec_step_f32) and :580 (_store_transition -> HerReplayBuffer.add = cstr_her_add_f32), then Monitor's episode statistics."""
         n, dev = env.num_envs, self.device
@@ -594,10 +610,14 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         """The device rollout step behind the policy output `pol`, for the eager and the captured iteration alike: the fused collect
         launch (action scaling chain + env step + auto-reset + ring row write + episode statistics), then `_after_device_step`."""
         env, rb = self._denv, self.replay_buffer
-        hip_ops.collect_step(env.coef, env.integrator, rb.ring, env.obs, env.step_count, pol, squashed,
-                             self.action_space.low, self.action_space.high, noise=noise, pcg_state=env.pcg_state, static_init=env.static_init,
-                             reward_out=env._rew, done_out=env._done, ep_return=self._ep_return, ep_stats=self._ep_stats,
-                             rng_advance=self._take_rng_advance())
+        if env.goal_conditioned:  # the goal face: the env hands the launch its own arrays, the HER bookkeeping rides along
+            env.collect_step_device(rb.ring, rb.her, pol, squashed, self.action_space.low, self.action_space.high, noise=noise,
+                                    ep_return=self._ep_return, ep_stats=self._ep_stats, rng_advance=self._take_rng_advance())
+        else:
+            hip_ops.collect_step(env.coef, env.integrator, rb.ring, env.obs, env.step_count, pol, squashed,
+                                 self.action_space.low, self.action_space.high, noise=noise, pcg_state=env.pcg_state, static_init=env.static_init,
+                                 reward_out=env._rew, done_out=env._done, ep_return=self._ep_return, ep_stats=self._ep_stats,
+                                 rng_advance=self._take_rng_advance())
         self._after_device_step(action_noise)
 
     def _after_device_step(self, action_noise) -> None:

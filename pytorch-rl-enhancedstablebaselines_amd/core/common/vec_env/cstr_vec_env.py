@@ -366,6 +366,24 @@ class CSTRVecEnv(VecEnv):
             self.obs.copy_(self._reset_buf)
         return self.obs, self._rew, self._done, self._timeout, self._next_obs
 
+    def collect_step_device(self, ring, her, policy_out: th.Tensor, squashed: int, act_low, act_high, noise=None, ep_return=None, ep_stats=None,
+                            rng_advance=None):
+        """The rollout's vec-step on the goal face in ONE launch (hip_ops.goal_collect_step), no host sync: the action scaling chain on
+        `policy_out`, `step_device` on the env's own arrays and the HerReplayBuffer add of (`flat` before the step, the terminal-aware next
+        rows, the buffer action) into `ring` / `her`. `flat` is read as the transition's observation and then holds what VecEnv.step
+        returns. Returns the same device views as `step_device`."""
+        self._need_goal_face()
+        if not self._has_reset:
+            raise ValueError("Please call env.reset() to reset the env first!")  # twoseriescstr.py:401-402
+        with th.cuda.device(self.device):
+            lo_g, hi_g = self.goal_range if self.goal_range is not None else (0.0, 0.0)
+            hip_ops.goal_collect_step(self.coef, self.integrator, ring, her, self.obs, self.flat, self.step_count, self.pcg_state, self.targets,
+                                      policy_out, squashed, act_low, act_high, noise=noise, static_init=self.static_init, episode=self.episode,
+                                      goal_seed=self.goal_seed, goal_index_offset=self.seed_offset, goal_lo=lo_g, goal_hi=hi_g,
+                                      reward_out=self._rew, done_out=self._done, timeout_out=self._timeout, next_rows_out=self._next_rows,
+                                      ep_return=ep_return, ep_stats=ep_stats, rng_advance=rng_advance)
+        return self.flat, self._rew, self._done, self._timeout, self._next_rows
+
     def step_async(self, actions) -> None:
         if self.discrete_actions is not None:
             idx = actions.cpu().numpy() if isinstance(actions, th.Tensor) else np.asarray(actions)

@@ -186,7 +186,9 @@ class HerReplayBuffer(ReplayBuffer):
                         self._dev(reward, (n,)), self._dev(done, (n,)), self._dev(timeout, (n,)))
 
     def note_fused_add(self) -> None:
-        raise RuntimeError("the fused collect step does not keep HER's episode bookkeeping; use add_device")
+        """The goal face's fused collect launch (hip_ops.goal_collect_step) wrote a row with its episode bookkeeping and advanced the
+        device position: keep the host mirror (`pos` / `full` follow `_adds`) in step, as `add_device` does."""
+        self._adds += 1
 
     # ---- sample -------------------------------------------------------------------------------------------------------------------
     def alloc_batch(self, batch_size: int) -> ReplayBufferSamples:

@@ -2,6 +2,8 @@
 //   cstr_goal_vec_step_f32  VecEnv.step on the goal face: the env step of cstr_env_device.h, the goal reward with the lane's own
 //                           target, auto-reset from the env's PCG64 stream, the Philox target redraw, flat [ag | dg | obs] rows;
 //   cstr_her_add_f32        HerReplayBuffer.add + _compute_episode_length (core/her/her_replay_buffer.py:135-184), a lane per env;
+//   cstr_goal_collect_step_f32  the rollout's vec-step on the goal face in one launch: the action scaling chain of cstr_collect_step_f32, the
+//                           two launches above (their bodies, as shared device functions) and Monitor's episode statistics;
 //   cstr_her_sample_f32     HerReplayBuffer.sample (:186-384) in one launch on NumPy's legacy MT19937 stream.
 // The goal has one dimension: achieved_goal = observation[2] (normalised C2), so the ring stores no achieved goals.
 //
@@ -25,6 +27,57 @@ namespace {
 
 constexpr int HER_TPB = 256;
 // ---- VecEnv.step on the goal face (dummy_vec_env.py:56-73 over TwoSeriesCSTREnv.step) ------------------------------------------
+// What env i's step leaves in registers for the launch around it: the true next observation (terminal where done) with the OLD goal,
+// reward, done / truncated and the step count the episode has reached (before the auto-reset zeroes it).
+struct GoalStep { float on[4], dg, r; int32_t st; bool d, trunc; };
+
+// Env i of VecEnv.step on the goal face: the env step on action a[0..1], the goal reward on the lane's own target (NaN action or state:
+// old state, -10, truncated), auto-reset from the env's PCG64 stream, the Philox target redraw with episode[i] += 1, step_count, the
+// env state and the row VecEnv.step returns (rows_after). Shared by goal_step_kernel and goal_collect_step_kernel.
+template <int INTEG>
+__device__ __forceinline__ void goal_step_lane(const cstr_coef_t &k, float *env_obs, const float a[4], int32_t *step_count, uint64_t *pcg,
+                                               double *static_init, float *target, const GoalDraw &gd, float *rows_after, const int64_t i,
+                                               GoalStep &s)
+{
+    float o[2][4], raw[4], r;
+    load_obs<0>(env_obs, i, o);
+    int32_t st = step_count[i];
+    float tg = target[i];
+    bool bad = (a[0] != a[0]) || (a[1] != a[1]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) bad |= (o[0][j] != o[0][j]);
+    const bool trunc = cstr_step_lane<INTEG>(k, o[0], a[0], a[1], st, s.on, raw, r);
+    const float dg = goal_of_target(k, tg);
+    if (!bad) r = goal_reward(k.s_lo[2], k.s_span[2], k.conc_span, s.on[2], dg);  // NaN path: old state, -10, truncated
+    const bool d = trunc;
+    s.dg = dg; s.r = r; s.st = st; s.d = d; s.trunc = trunc;
+    if (d) {  // dummy_vec_env.py:68-72: the env's own reset stream, as cstr_reset_draw_f32 consumes it
+        uint64_t pst[4];
+        load_pcg(pcg, i, pst);
+        float ro[2][4];
+        reset_draw_env<0>(k, pst, static_init, i, ro);
+        *reinterpret_cast<ulonglong2 *>(pcg + 4 * i) = make_ulonglong2(pst[0], pst[1]);
+        store_obs<0>(env_obs, i, ro);
+        float dg2 = dg;
+        if (gd.episode) {  // target of the episode that starts now: counter (env index, episode ordinal, tag), key = goal seed
+            const int32_t e = gd.episode[i];
+            tg = goal_draw_target(gd, i, e);
+            target[i] = tg;
+            gd.episode[i] = e + 1;
+            dg2 = goal_of_target(k, tg);
+        }
+        store_row6(rows_after, i, dg2, ro[0]);
+        st = 0;
+    } else {
+        float oo[2][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) oo[0][j] = s.on[j];
+        store_obs<0>(env_obs, i, oo);
+        store_row6(rows_after, i, dg, s.on);
+    }
+    step_count[i] = st;
+}
+
 template <int INTEG>
 __global__ void goal_step_kernel(const cstr_coef_t k, float *__restrict__ env_obs, const float *__restrict__ act, int32_t *__restrict__ step_count,
                                  uint64_t *__restrict__ pcg, double *__restrict__ static_init, float *__restrict__ target, const GoalDraw gd,
@@ -32,47 +85,14 @@ __global__ void goal_step_kernel(const cstr_coef_t k, float *__restrict__ env_ob
                                  float *__restrict__ done, float *__restrict__ timeout, const int64_t n)
 {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float o[2][4], on[4], raw[4], a[4], r;
-        load_obs<0>(env_obs, i, o);
+        float a[4];
+        GoalStep s;
         load_act<2>(act, i, a);
-        int32_t st = step_count[i];
-        float tg = target[i];
-        bool bad = (a[0] != a[0]) || (a[1] != a[1]);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) bad |= (o[0][j] != o[0][j]);
-        const bool trunc = cstr_step_lane<INTEG>(k, o[0], a[0], a[1], st, on, raw, r);
-        const float dg = goal_of_target(k, tg);
-        if (!bad) r = goal_reward(k.s_lo[2], k.s_span[2], k.conc_span, on[2], dg);  // NaN path: old state, -10, truncated
-        const bool d = trunc;
-        store_row6(next_rows, i, dg, on);
-        reward[i] = r;
-        done[i] = d ? 1.0f : 0.0f;
-        timeout[i] = trunc ? 1.0f : 0.0f;
-        if (d) {  // dummy_vec_env.py:68-72: the env's own reset stream, as cstr_reset_draw_f32 consumes it
-            uint64_t pst[4];
-            load_pcg(pcg, i, pst);
-            float ro[2][4];
-            reset_draw_env<0>(k, pst, static_init, i, ro);
-            *reinterpret_cast<ulonglong2 *>(pcg + 4 * i) = make_ulonglong2(pst[0], pst[1]);
-            store_obs<0>(env_obs, i, ro);
-            float dg2 = dg;
-            if (gd.episode) {  // target of the episode that starts now: counter (env index, episode ordinal, tag), key = goal seed
-                const int32_t e = gd.episode[i];
-                tg = goal_draw_target(gd, i, e);
-                target[i] = tg;
-                gd.episode[i] = e + 1;
-                dg2 = goal_of_target(k, tg);
-            }
-            store_row6(rows_after, i, dg2, ro[0]);
-            st = 0;
-        } else {
-            float oo[2][4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) oo[0][j] = on[j];
-            store_obs<0>(env_obs, i, oo);
-            store_row6(rows_after, i, dg, on);
-        }
-        step_count[i] = st;
+        goal_step_lane<INTEG>(k, env_obs, a, step_count, pcg, static_init, target, gd, rows_after, i, s);
+        store_row6(next_rows, i, s.dg, s.on);
+        reward[i] = s.r;
+        done[i] = s.d ? 1.0f : 0.0f;
+        timeout[i] = s.trunc ? 1.0f : 0.0f;
     }
 }
 
@@ -88,51 +108,113 @@ __device__ __forceinline__ void her_set_valid(const cstr_her_t &h, const int64_t
     }
 }
 
+// Env i of HerReplayBuffer.add at ring row `pos`: x / y = observation / next observation (columns 2..5 of the flat rows), dg = column 1
+// of the observation row, a = the buffer action. Shared by her_add_kernel and goal_collect_step_kernel.
+__device__ __forceinline__ void her_add_lane(const cstr_ring_t &ring, const cstr_her_t &h, const int64_t pos, const int64_t words, const int64_t i,
+                                             const float4 x, const float4 y, const float dg, const float2 a, const float rw, const float dn,
+                                             const float to)
+{
+    const int64_t n = ring.n_envs, rows = ring.rows, o = pos * n + i;
+    // her_replay_buffer.py:148-154: writing onto an old episode deletes the whole of it
+    const int32_t len0 = h.ep_length[o];
+    if (len0 > 0) {
+        const int64_t end = (int64_t)h.ep_start[o] + len0;
+        for (int64_t j = pos; j < end; ++j) {  // np.arange(pos, episode_end) % buffer_size
+            const int64_t r = j % rows;
+            if (h.ep_length[r * n + i] > 0) her_set_valid(h, words, r, i, false);
+            h.ep_length[r * n + i] = 0;
+        }
+    }
+    const int32_t cs = h.cur_ep_start[i];
+    h.ep_start[o] = cs;  // :157
+    // :162, DictReplayBuffer.add: the row; achieved_goal is column 2 of the observation and is not stored
+    *reinterpret_cast<float4 *>(ring.obs + o * 4) = x;
+    *reinterpret_cast<float4 *>(ring.next_obs + o * 4) = y;
+    *reinterpret_cast<float2 *>(ring.act + o * 2) = a;
+    h.desired_goal[o] = dg;
+    ring.rew[o] = rw;
+    ring.done[o] = dn;
+    ring.timeout[o] = to;
+    if (dn != 0.0f) {  // :165-184, _compute_episode_length with self.pos already advanced by the add
+        const int64_t new_pos = (pos + 1 == rows) ? 0 : pos + 1;
+        int64_t end = new_pos;
+        if (end < cs) end += rows;
+        const int32_t len = (int32_t)(end - cs);
+        for (int64_t j = cs; j < end; ++j) {  // np.arange(episode_start, episode_end) % buffer_size
+            const int64_t r = j % rows;
+            h.ep_length[r * n + i] = len;
+            her_set_valid(h, words, r, i, true);
+        }
+        h.cur_ep_start[i] = (int32_t)new_pos;
+    }
+}
+
 __global__ void her_add_kernel(const cstr_ring_t ring, const cstr_her_t h, int64_t *__restrict__ ring_ctl, const float *__restrict__ obs_rows,
                                const float *__restrict__ next_rows, const float *__restrict__ act, const float *__restrict__ rew,
                                const float *__restrict__ done, const float *__restrict__ timeout)
 {
-    const int64_t n = ring.n_envs, rows = ring.rows, pos = ring_ctl[0], words = (n + 63) >> 6;
+    const int64_t n = ring.n_envs, pos = ring_ctl[0], words = (n + 63) >> 6;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t o = pos * n + i;
-        // her_replay_buffer.py:148-154: writing onto an old episode deletes the whole of it
-        const int32_t len0 = h.ep_length[o];
-        if (len0 > 0) {
-            const int64_t end = (int64_t)h.ep_start[o] + len0;
-            for (int64_t j = pos; j < end; ++j) {  // np.arange(pos, episode_end) % buffer_size
-                const int64_t r = j % rows;
-                if (h.ep_length[r * n + i] > 0) her_set_valid(h, words, r, i, false);
-                h.ep_length[r * n + i] = 0;
-            }
-        }
-        const int32_t cs = h.cur_ep_start[i];
-        h.ep_start[o] = cs;  // :157
-        // :162, DictReplayBuffer.add: the row; achieved_goal is column 2 of the observation and is not stored
         const float2 g = *reinterpret_cast<const float2 *>(obs_rows + 6 * i);
         const float2 x01 = *reinterpret_cast<const float2 *>(obs_rows + 6 * i + 2), x23 = *reinterpret_cast<const float2 *>(obs_rows + 6 * i + 4);
         const float2 y01 = *reinterpret_cast<const float2 *>(next_rows + 6 * i + 2), y23 = *reinterpret_cast<const float2 *>(next_rows + 6 * i + 4);
-        *reinterpret_cast<float4 *>(ring.obs + o * 4) = make_float4(x01.x, x01.y, x23.x, x23.y);
-        *reinterpret_cast<float4 *>(ring.next_obs + o * 4) = make_float4(y01.x, y01.y, y23.x, y23.y);
-        *reinterpret_cast<float2 *>(ring.act + o * 2) = *reinterpret_cast<const float2 *>(act + 2 * i);
-        h.desired_goal[o] = g.y;
-        ring.rew[o] = rew[i];
-        const float dn = done[i];
-        ring.done[o] = dn;
-        ring.timeout[o] = timeout[i];
-        if (dn != 0.0f) {  // :165-184, _compute_episode_length with self.pos already advanced by the add
-            const int64_t new_pos = (pos + 1 == rows) ? 0 : pos + 1;
-            int64_t end = new_pos;
-            if (end < cs) end += rows;
-            const int32_t len = (int32_t)(end - cs);
-            for (int64_t j = cs; j < end; ++j) {  // np.arange(episode_start, episode_end) % buffer_size
-                const int64_t r = j % rows;
-                h.ep_length[r * n + i] = len;
-                her_set_valid(h, words, r, i, true);
+        her_add_lane(ring, h, pos, words, i, make_float4(x01.x, x01.y, x23.x, x23.y), make_float4(y01.x, y01.y, y23.x, y23.y), g.y,
+                     *reinterpret_cast<const float2 *>(act + 2 * i), rew[i], done[i], timeout[i]);
+    }
+    ring_advance_last_block(ring_ctl, ring.rows);
+}
+
+// ---- the goal face's collect step: action chain + VecEnv.step + HerReplayBuffer.add + Monitor statistics, ONE launch ------------------
+// (off_policy_algorithm.py:364-411, :564, :580 on the goal face.) A lane per env; N x ~100 bytes, launch-latency-bound. Everything an env
+// needs besides its own rows is wave-uniform (kernarg segment); the ring position is read once in front of the arithmetic.
+struct GoalCollectArgs {
+    cstr_ring_t ring;
+    cstr_her_t her;
+    float *env_obs, *rows; int32_t *step_count; uint64_t *pcg; double *static_init; float *target;
+    GoalDraw gd;
+    int squashed; ActBounds ab;
+    const float *noise;
+    float *reward_out, *done_out, *timeout_out, *next_rows_out, *ep_return; double *ep_stats;
+};
+
+template <int INTEG>
+__global__ void goal_collect_step_kernel(const cstr_coef_t k, const GoalCollectArgs c, int64_t *__restrict__ ring_ctl,
+                                         const float *__restrict__ policy_out, uint64_t *__restrict__ policy_rng_ctl,
+                                         const uint64_t policy_rng_advance)
+{
+    const int64_t n = c.ring.n_envs, words = (n + 63) >> 6;
+    const int64_t pos = ring_ctl[0];  // wave-uniform scalar load
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float u[4], z[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sa[4], ea[4];
+        load_act<2>(policy_out, i, u);
+        if (c.noise) load_act<2>(c.noise, i, z);
+        // _last_obs: the env's own row is the transition's observation row; the step below writes what VecEnv.step returns over it
+        const float2 g = *reinterpret_cast<const float2 *>(c.rows + 6 * i);
+        const float2 x01 = *reinterpret_cast<const float2 *>(c.rows + 6 * i + 2), x23 = *reinterpret_cast<const float2 *>(c.rows + 6 * i + 4);
+        const float ep_ret = c.ep_return ? c.ep_return[i] : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) action_scale_chain(c.squashed, c.ab.lo[j], c.ab.hi[j], u[j], c.noise != nullptr, z[j], sa[j], ea[j]);
+        ea[2] = ea[3] = 0.0f;
+        GoalStep s;
+        goal_step_lane<INTEG>(k, c.env_obs, ea, c.step_count, c.pcg, c.static_init, c.target, c.gd, c.rows, i, s);
+        const float dn = s.d ? 1.0f : 0.0f, to = s.trunc ? 1.0f : 0.0f;
+        if (c.next_rows_out) store_row6(c.next_rows_out, i, s.dg, s.on);
+        if (c.reward_out) c.reward_out[i] = s.r;
+        if (c.done_out) c.done_out[i] = dn;
+        if (c.timeout_out) c.timeout_out[i] = to;
+        her_add_lane(c.ring, c.her, pos, words, i, make_float4(x01.x, x01.y, x23.x, x23.y), make_float4(s.on[0], s.on[1], s.on[2], s.on[3]), g.y,
+                     make_float2(sa[0], sa[1]), s.r, dn, to);
+        if (c.ep_return) {  // Monitor semantics: return / length of the episode that ends here (the convention of cstr_collect_step_f32)
+            const float ret = ep_ret + s.r;
+            c.ep_return[i] = s.d ? 0.0f : ret;
+            if (s.d) {
+                atomicAdd(c.ep_stats + 0, 1.0);
+                atomicAdd(c.ep_stats + 1, (double)ret);
+                atomicAdd(c.ep_stats + 2, (double)s.st);
             }
-            h.cur_ep_start[i] = (int32_t)new_pos;
         }
     }
-    ring_advance_last_block(ring_ctl, rows);
+    ring_advance_last_block(ring_ctl, c.ring.rows, policy_rng_ctl, policy_rng_advance);
 }
 
 // ---- HerReplayBuffer.sample --------------------------------------------------------------------------------------------------
@@ -351,6 +433,67 @@ extern "C" int cstr_her_add_f32(const cstr_ring_t *ring, const cstr_her_t *her, 
     int block, grid;
     env_launch_shape(n, block, grid);
     her_add_kernel<<<grid, block, 0, (hipStream_t)stream>>>(*ring, *her, ring_ctl, obs_rows, next_rows, act, rew, done, timeout);
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_goal_collect_step_f32(const cstr_coef_t *coef, int integrator, int obs_dim, const cstr_ring_t *ring, const cstr_her_t *her,
+                                          int64_t *ring_ctl, float *env_obs, float *rows, int32_t *step_count, uint64_t *pcg_state,
+                                          double *static_init, float *target, int32_t *episode, uint64_t goal_seed, int64_t goal_index_offset,
+                                          float goal_lo, float goal_hi, const float *policy_out, int squashed, const float *act_low,
+                                          const float *act_high, const float *noise, float *reward_out, float *done_out, float *timeout_out,
+                                          float *next_rows_out, float *ep_return, double *ep_stats, uint64_t *policy_rng_ctl,
+                                          uint64_t policy_rng_advance, cstr_stream_t stream)
+{
+    const int rc = check_her(ring, her);
+    if (rc) return rc;
+    if (!coef || !ring_ctl || !env_obs || !rows || !step_count || !pcg_state || !target || !policy_out || !act_low || !act_high) return CSTR_E_BADARG;
+    if ((ep_return == nullptr) != (ep_stats == nullptr)) return CSTR_E_BADARG;
+    if (obs_dim != 4 || (squashed & ~1) || (integrator != CSTR_INTEGRATOR_EULER && integrator != CSTR_INTEGRATOR_RK4)) return CSTR_E_UNSUPPORTED;
+    if (!aligned16(env_obs) || !aligned8(rows) || !aligned8(policy_out) || !aligned16(pcg_state) || !aligned4p(target) || !aligned4p(step_count) ||
+        !aligned8(ring_ctl) || (noise && !aligned8(noise)) || (episode && !aligned4p(episode)) || (static_init && !aligned8(static_init)) ||
+        (next_rows_out && !aligned8(next_rows_out)) || (reward_out && !aligned4p(reward_out)) || (done_out && !aligned4p(done_out)) ||
+        (timeout_out && !aligned4p(timeout_out)) || (ep_return && !aligned4p(ep_return)) || (ep_stats && !aligned8(ep_stats)) ||
+        (policy_rng_ctl && !aligned8(policy_rng_ctl)))
+        return CSTR_E_BADARG;
+    if (episode && !(goal_lo <= goal_hi)) return CSTR_E_BADARG;
+    ActBounds ab;
+    for (int j = 0; j < 4; ++j) {
+        ab.lo[j] = j < 2 ? act_low[j] : -1.0f;
+        ab.hi[j] = j < 2 ? act_high[j] : 1.0f;
+        if (!(ab.hi[j] > ab.lo[j])) return CSTR_E_BADARG;
+    }
+    // nothing the launch writes may overlap anything else it touches: state arrays, outputs, the ring and its side arrays
+    const int64_t n = ring->n_envs, cells = ring->rows * n, words = (n + 63) >> 6;
+    struct Span { const void *p; int64_t bytes; bool written; };
+    const Span spans[] = {
+        {policy_out, 8 * n, false}, {noise, 8 * n, false},
+        {env_obs, 16 * n, true}, {rows, 24 * n, true}, {step_count, 4 * n, true}, {pcg_state, 32 * n, true}, {static_init, 32 * n, true},
+        {target, 4 * n, true}, {episode, 4 * n, true}, {reward_out, 4 * n, true}, {done_out, 4 * n, true}, {timeout_out, 4 * n, true},
+        {next_rows_out, 24 * n, true}, {ep_return, 4 * n, true}, {ep_stats, 32, true}, {ring_ctl, 32, true}, {policy_rng_ctl, 16, true},
+        {ring->obs, 16 * cells, true}, {ring->next_obs, 16 * cells, true}, {ring->act, 8 * cells, true}, {ring->rew, 4 * cells, true},
+        {ring->done, 4 * cells, true}, {ring->timeout, 4 * cells, true}, {her->desired_goal, 4 * cells, true}, {her->ep_start, 4 * cells, true},
+        {her->ep_length, 4 * cells, true}, {her->cur_ep_start, 4 * n, true}, {her->row_valid, 4 * ring->rows, true},
+        {her->valid_bits, 8 * ring->rows * words, true}};
+    constexpr int n_spans = (int)(sizeof(spans) / sizeof(spans[0]));
+    for (int i = 0; i < n_spans; ++i)
+        for (int j = i + 1; j < n_spans; ++j)
+            if (spans[i].p && spans[j].p && (spans[i].written || spans[j].written) &&
+                spans_overlap(spans[i].p, spans[i].bytes, spans[j].p, spans[j].bytes))
+                return CSTR_E_BADARG;
+    GoalCollectArgs c;
+    c.ring = *ring; c.her = *her;
+    c.env_obs = env_obs; c.rows = rows; c.step_count = step_count; c.pcg = pcg_state; c.static_init = static_init; c.target = target;
+    c.gd = GoalDraw{goal_seed, goal_index_offset, goal_lo, goal_hi, episode};
+    c.squashed = squashed; c.ab = ab; c.noise = noise;
+    c.reward_out = reward_out; c.done_out = done_out; c.timeout_out = timeout_out; c.next_rows_out = next_rows_out;
+    c.ep_return = ep_return; c.ep_stats = ep_stats;
+    int block, grid;
+    env_launch_shape(n, block, grid);
+    hipStream_t s = (hipStream_t)stream;
+    if (integrator == CSTR_INTEGRATOR_EULER)
+        goal_collect_step_kernel<CSTR_INTEGRATOR_EULER><<<grid, block, 0, s>>>(*coef, c, ring_ctl, policy_out, policy_rng_ctl, policy_rng_advance);
+    else
+        goal_collect_step_kernel<CSTR_INTEGRATOR_RK4><<<grid, block, 0, s>>>(*coef, c, ring_ctl, policy_out, policy_rng_ctl, policy_rng_advance);
     return (int)hipGetLastError();
 }
 
