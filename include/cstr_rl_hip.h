@@ -459,6 +459,39 @@ int cstr_eval_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef
                            const float *act_high, const int32_t *targets, int64_t n_envs, int64_t max_vec_steps, double *ep_return,
                            int32_t *ep_len, int32_t *ep_done, cstr_stream_t stream);
 
+/* The recording form of cstr_eval_episodes_f32 on the (4, 2) layout: a trained policy rolled out into replay-ring rows in ONE launch,
+ * optionally epsilon-uniform -- the collection loop behind an offline dataset and behind closed-loop response curves. Every env of a
+ * workgroup's 16 runs exactly n_steps vec-steps (a fixed trip count: no targets, no early end). At vec-step t the lane of env i
+ *   a. forms the deterministic head value v_j of cstr_eval_episodes_f32 (head 0: tanh(mu), what eps = 0 gives; head 1: out_act(.));
+ *   b. when explore_prob > 0 takes ONE Philox4x32-10 block, key = (seed lo, seed hi), counter = (idx lo, idx hi, step_offset + t,
+ *      0xC011EC7D) with idx = index_offset + i; with u(w) = (w >> 8) * 2^-24: explore = u(w0) < explore_prob (float32 compare), and an
+ *      exploring row replaces v_j by a uniform draw over the action space -- squashed & 1: v_j = 2 u(w[1+j]) - 1; otherwise
+ *      v_j = low_j + u(w[1+j]) * (high_j - low_j), the product and the sum rounded separately (no FMA). explore_prob == 0 evaluates no block;
+ *   c. unsquashed actors (squashed == 0; PPO / A2C): v_j = clip(v_j, low_j, high_j), NaN kept -- predict()'s clip;
+ *   d. runs the action scaling chain of cstr_collect_step_f32 on v (no noise): sa = the buffer action, ea = the env's action;
+ *   e. steps the env and writes ring row row0 + t with the stores and values of cstr_collect_step_f32: obs = the observation before the
+ *      step, next_obs = the TERMINAL observation (never the reset one), act = sa, rew, done = timeout = truncated; explored (optional,
+ *      uint8 [ring rows][N]) gets the flag at [row0 + t][i];
+ *   f. adds the f32 reward to an f64 running return and counts the step; where the episode ends: if the env's episode count is below
+ *      ep_stride, ep_return[i][count] / ep_len[i][count] are stored; the count is incremented either way (episodes beyond ep_stride are
+ *      counted, not stored); then the PCG64 auto-reset draw of cstr_collect_step_f32, step_count = 0.
+ * After the loop env_obs / step_count / pcg_state (/ static_init) hold the env's state and ep_done[i] the count. The launch touches no
+ * control word: pos / full of a ring_ctl are the caller's. Arguments as in cstr_eval_episodes_f32, plus
+ *   ring: its n_envs / obs_dim / act_dim must be N / 4 / 2; rows row0 .. row0 + n_steps - 1 are written, all others left alone
+ *   ep_return double[N][ep_stride], ep_len int32[N][ep_stride] (both may be NULL when ep_stride is 0), ep_done int32[N] out.
+ * Bit-level contract: ring rows, env state and episode outputs equal what the step-by-step launches give -- cstr_policy_rows_fwd_f32
+ * (head 0: eps = 0), the statement of b. and c. on its output, cstr_collect_step_f32 without noise.
+ * CSTR_E_BADARG: NULL required pointers, n_envs <= 0, n_steps <= 0, row0 < 0 or row0 + n_steps > ring->rows, a ring whose n_envs / obs_dim /
+ * act_dim disagree with the env's, explore_prob outside [0, 1] or NaN, step_offset < 0 or step_offset + n_steps > 2^32, ep_stride < 0 or
+ * ep_stride > 0 without ep_return / ep_len, net->k0 != obs_dim, misaligned arrays, anything written (ring fields, explored, episode outputs,
+ * env state) overlapping anything read or anything else written. CSTR_E_UNSUPPORTED: what cstr_eval_episodes_f32 declines, and the (8, 2) /
+ * (8, 4) layouts. All checked before anything is enqueued. */
+int cstr_collect_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs,
+                              int32_t *step_count, uint64_t *pcg_state, double *static_init, int squashed, const float *act_low,
+                              const float *act_high, const cstr_ring_t *ring, int64_t row0, int64_t n_envs, int64_t n_steps,
+                              float explore_prob, uint64_t seed, int64_t index_offset, int64_t step_offset, double *ep_return,
+                              int32_t *ep_len, int64_t ep_stride, int32_t *ep_done, uint8_t *explored, cstr_stream_t stream);
+
 /* TD3 / MADDPG target policy smoothing (core/td3/td3.py:167-173; core/maddpg/maddpg.py:131-142) in one launch:
  * noise = clamp(N(0, sigma), -clip, clip); out = clamp(action + noise, -1, 1). action [B][A] contiguous (the target
  * actor's output); `noise` [B][A] (already scaled by sigma) is read when rng_ctl is NULL, otherwise sigma * N(0,1) is drawn

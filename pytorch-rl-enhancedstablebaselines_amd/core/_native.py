@@ -24,6 +24,7 @@ DQN_MAX_LEVELS = 16
 MCAT_MAX_LEVELS = 32
 HER_STRATEGIES = {"future": 0, "final": 1, "episode": 2}
 HER_MAX_BATCH, HER_MAX_ROWS, HER_MAX_ENVS, HER_GOAL_TAG = 1024, 8192, 1 << 24, 0x90A17A67
+COLLECT_TAG = 0xC011EC7D  # counter word 3 of cstr_collect_episodes_f32's exploration draw
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -47,6 +48,7 @@ SYMBOLS = (
     "cstr_eval_goal_episodes_f32",
     "cstr_goal_rollout_add_f32", "cstr_goal_ppo_gather_f32",
     "cstr_goal_collect_step_f32",
+    "cstr_collect_episodes_f32",
 )
 
 

@@ -15,6 +15,10 @@ episodes are walked inside the kernel and the host reads three arrays back. It c
 actor on a bare `CSTRVecEnv`; `supported()` tells whether it applies. On the goal face (`goal_conditioned=True`, SAC / TD3 / DDPG / PPO / A2C on
 "MultiInputPolicy") the launch is cstr_eval_goal_episodes_f32, and `evaluate_goal_tracking` returns what it knows per episode beyond the
 return: the setpoint that was drawn, how far C2 ended from it and the mean absolute gap on the way.
+
+`evaluate_trajectories` (specific to this package) returns the closed-loop trajectories themselves -- states, applied flows and rewards per
+episode -- from ONE launch of the recording kernel, cstr_collect_episodes_f32, into a temporary replay ring; the same launch is what
+`core.common.offline_dataset.collect_offline_dataset` and `twoseriescstr.evaluate_model` run.
 """
 import warnings
 from typing import Callable, Optional, Tuple, Union
@@ -260,6 +264,100 @@ def _launch(model, env, n_eval_episodes: int, tracking: bool = False):
     len_h = arrays[1]
     order = [(i, j) for _, i, j in sorted((int(len_h[i, :j + 1].sum()), i, j) for i in range(n) for j in range(int(targets[i])))]
     return order, arrays
+
+
+# ---- recorded rollouts: the same walk, every step left in a replay ring (cstr_collect_episodes_f32) --------------------------------
+
+def _why_not_collected(model, env) -> Optional[str]:
+    """Why the recording launch does not cover (model, env), or None: what `_why_not_fused` declines, the goal face and the 8-wide
+    observation layouts."""
+    why = _why_not_fused(model, env, True)
+    if why is None and env.goal_conditioned:
+        why = "the goal face (goal_conditioned=True): HerReplayBuffer datasets are not collected by this launch"
+    if why is None and (env.obs_dim, env.act_dim) != hip_ops.LAYOUTS[0]:
+        why = f"the ({env.obs_dim}, {env.act_dim}) observation layout: the recording launch exists for {hip_ops.LAYOUTS[0]}"
+    return why
+
+
+def _collect_launch(model, env, ring, n_steps: int, explore_prob: float = 0.0, seed: int = 0, ep_stride: int = 0, row0: int = 0,
+                    step_offset: int = 0):
+    """`n_steps` vec-steps of a supported (model, env) from the env's CURRENT state into rows `row0 ..` of `ring`, one launch.
+    Returns (ep_return, ep_len, ep_done) on the host."""
+    policy = getattr(model, "policy", model)
+    ops = _fused_operands(policy)
+    l1, l2 = ops["layers"]
+    with th.no_grad(), th.cuda.device(env.device):
+        w1, w2, w3 = _aligned(l1.weight), _aligned(l2.weight), _aligned(ops["w3"])
+        b1, b2, b3 = l1.bias.detach().contiguous(), l2.bias.detach().contiguous(), ops["b3"].detach().contiguous()
+        low, high = np.asarray(policy.action_space.low, np.float32), np.asarray(policy.action_space.high, np.float32)
+        out = hip_ops.collect_episodes(w1, b1, w2, b2, w3, b3, ops["act"], ops["head"], ops["out_act"], hip_ops.policy_swizzle(w2), env.coef,
+                                       env.integrator, env.obs, env.step_count, env.pcg_state, policy.squash_output, low, high, ring, n_steps,
+                                       row0=row0, explore_prob=explore_prob, seed=seed, index_offset=env.seed_offset, step_offset=step_offset,
+                                       ep_stride=ep_stride, static_init=env.static_init)
+        return tuple(t.cpu().numpy() for t in out)
+
+
+def segment_episodes(rewards: np.ndarray, dones: np.ndarray):
+    """Episodes of recorded [T, N] `rewards` / `dones` that ENDED within the T rows, in `evaluate_policy`'s order (the vec-step an episode
+    ends at, then the env index): a list of (env, first row, length) and the float64 sums of the float32 rewards -- what the launch's
+    ep_return holds, recomputed on the host."""
+    rewards, dones = np.asarray(rewards), np.asarray(dones)
+    spans, rets = [], []
+    start = np.zeros(rewards.shape[1], np.int64)
+    for t, i in zip(*np.nonzero(dones > 0)):  # row-major: by vec-step, then by env
+        spans.append((int(i), int(start[i]), int(t + 1 - start[i])))
+        rets.append(np.cumsum(rewards[start[i]:t + 1, i], dtype=np.float64)[-1])  # the kernel's order: one f64 add per step
+        start[i] = t + 1
+    return spans, np.asarray(rets, np.float64)
+
+
+def pad_episodes(field: np.ndarray, spans, l_max: Optional[int] = None) -> np.ndarray:
+    """[E, Lmax, ...] float64 from a recorded [T, N, ...] field and `segment_episodes`' spans; rows past an episode's end are NaN."""
+    field = np.asarray(field)
+    l_max = max((ln for _, _, ln in spans), default=0) if l_max is None else l_max
+    out = np.full((len(spans), l_max) + field.shape[2:], np.nan, np.float64)
+    for e, (i, s, ln) in enumerate(spans):
+        out[e, :ln] = field[s:s + ln, i]
+    return out
+
+
+def evaluate_trajectories(model, env, n_eval_episodes: int = 10) -> dict:
+    """Closed-loop trajectories of deterministic evaluation, from ONE launch (cstr_collect_episodes_f32 without exploration) into a
+    temporary ring: the env is reset, every env runs ceil(n_eval_episodes / n_envs) episodes' worth of vec-steps, and the first
+    `n_eval_episodes` episodes in `evaluate_policy`'s order (the vec-step an episode ends at, then the env index) are returned as
+      episode_rewards [E] float64 (f64 sums of the f32 step rewards), episode_lengths [E] int64,
+      states  [E, Lmax, 4] float64 -- the recorded float32 observation BEFORE each step as [C1, T1, C2, T2] in mol/L and K
+                                      (low + (o + 1) (high - low) / 2 in float32): row 0 is the reset state, the terminal state is not a row;
+      actions [E, Lmax, 2] float64 -- the coolant flows the env applied, L/min;
+      rewards [E, Lmax]    float64.
+    Episodes shorter than Lmax are padded with NaN (take nanmean over episodes). Raises ValueError where the launch does not apply."""
+    why = _why_not_collected(model, env)
+    if why is not None:
+        raise ValueError(f"evaluate_trajectories does not cover {why}")
+    n, limit = env.num_envs, int(env.coef.max_steps)
+    n_steps = -(-int(n_eval_episodes) // n) * limit
+    if n_steps <= 0:
+        raise ValueError("n_eval_episodes must be positive")
+    env.reset_device()
+    with th.cuda.device(env.device):
+        ring = hip_ops.DeviceRing(n_steps, n, env.obs_dim, env.act_dim, env.device)
+    _collect_launch(model, env, ring, n_steps)
+    return _trajectories(env, ring, n_eval_episodes)
+
+
+def _trajectories(env, ring, n_episodes: int) -> dict:
+    from twoseriescstr import TwoSeriesCSTREnv as E
+
+    rew, done = ring.rewards.cpu().numpy(), ring.dones.cpu().numpy()
+    spans, rets = segment_episodes(rew, done)
+    spans, rets = spans[:n_episodes], rets[:n_episodes]
+    obs, act = ring.observations.cpu().numpy(), ring.actions.cpu().numpy()
+    raw = E.raw_state_low + (obs + np.float32(1.0)) * (E.raw_state_high - E.raw_state_low) / np.float32(2.0)   # _denormalize_state
+    low, high = np.asarray(env.action_space.low, np.float32), np.asarray(env.action_space.high, np.float32)
+    ea = low + (np.float32(0.5) * (act + np.float32(1.0)) * (high - low))  # the env action behind the buffer action (unscale_action)
+    flow = E.raw_action_low + (np.clip(ea, -1.0, 1.0) + np.float32(1.0)) * (E.raw_action_high - E.raw_action_low) / np.float32(2.0)
+    return dict(episode_rewards=rets, episode_lengths=np.array([ln for _, _, ln in spans], np.int64), states=pad_episodes(raw, spans),
+                actions=pad_episodes(flow, spans), rewards=pad_episodes(rew, spans))
 
 
 def evaluate_policy_fused(model, env, n_eval_episodes: int = 10, deterministic: bool = True, reward_threshold: Optional[float] = None,

@@ -593,6 +593,78 @@ def eval_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, coef,
                                           ptr(ep_len), ptr(ep_done), stream_ptr()), "cstr_eval_episodes_f32")
 
 
+def collect_episodes_supported(k0: int, h1: int, h2: int, n_out: int, head: int, act_dim: int) -> bool:
+    """cstr_collect_episodes_f32 takes what cstr_eval_episodes_f32 takes, on the (4, 2) layout only."""
+    return (k0, act_dim) == LAYOUTS[0] and eval_episodes_supported(k0, h1, h2, n_out, head, act_dim)
+
+
+def collect_episodes(w1, b1, w2, b2, w3, b3, act: int, head: int, out_act: int, w2_swz, coef, integrator: str, env_obs, step_count, pcg_state,
+                     squashed: bool, act_low, act_high, ring: DeviceRing, n_steps: int, row0: int = 0, explore_prob: float = 0.0, seed: int = 0,
+                     index_offset: int = 0, step_offset: int = 0, ep_stride: int = 0, static_init=None, record_explored: bool = False):
+    """A policy rolled out into ring rows `row0 .. row0 + n_steps - 1` in ONE launch (cstr_collect_episodes_f32): every env runs `n_steps`
+    vec-steps with the network's deterministic action or, with probability `explore_prob` per (env, step), a uniform draw over the action
+    space from the Philox stream (`seed`, counter = (index_offset + env, step_offset + step, COLLECT_TAG)); the rows are those of
+    `collect_step` (terminal next observation, done = timeout). The env state in `env_obs` / `step_count` / `pcg_state` advances; the
+    ring's control words are not touched. Returns (ep_return float64 [N, ep_stride], ep_len int32 [N, ep_stride], ep_done int32 [N]) in
+    HBM -- episodes of an env beyond `ep_stride` are counted in ep_done, not stored -- and, with `record_explored`, the uint8 flags
+    [ring rows, N] behind them (rows outside the launch's stay 0)."""
+    n, d = env_obs.shape
+    h1, h2, n_out = w1.shape[0], w2.shape[0], w3.shape[0]
+    a = n_out // 2 if head == 0 else n_out
+    if (d, a) != LAYOUTS[0]:
+        raise ValueError(f"(obs_dim, act_dim) = {(d, a)}: collect_episodes covers the {LAYOUTS[0]} layout")
+    if (ring.n_envs, ring.obs_dim, ring.act_dim) != (n, d, a):
+        raise ValueError(f"ring is ({ring.n_envs}, {ring.obs_dim}, {ring.act_dim}), the env ({n}, {d}, {a})")
+    n_steps, row0, ep_stride = int(n_steps), int(row0), int(ep_stride)
+    if n_steps <= 0 or row0 < 0 or row0 + n_steps > ring.rows:
+        raise ValueError(f"rows {row0} .. {row0 + n_steps - 1} do not lie in a ring of {ring.rows} rows")
+    if not 0.0 <= float(explore_prob) <= 1.0:
+        raise ValueError(f"explore_prob = {explore_prob} is not a probability")
+    if ep_stride < 0 or step_offset < 0 or step_offset + n_steps > 1 << 32:
+        raise ValueError("ep_stride and step_offset must be non-negative, step_offset + n_steps at most 2^32")
+    _chk(env_obs, "env_obs", (n, d), th.float32), _chk(step_count, "step_count", (n,), th.int32)
+    _chk(pcg_state, "pcg_state", (n, nv.PCG_STATE_WORDS), th.int64)
+    _opt(static_init, "static_init", (n, 4), th.float64)
+    _chk(w1, "w1", (h1, d), th.float32), _chk(b1, "b1", (h1,), th.float32), _chk(w2, "w2", (h2, h1), th.float32)
+    _chk(b2, "b2", (h2,), th.float32), _chk(w3, "w3", (n_out, h2), th.float32), _chk(b3, "b3", (n_out,), th.float32)
+    if w2_swz is not None:
+        _chk(w2_swz, "w2_swz", (swizzled_numel(h2, h1),), th.float32)
+    _chk(ring.observations, "ring.observations", (ring.rows, n, d), th.float32), _chk(ring.next_observations, "ring.next_observations", (ring.rows, n, d), th.float32)
+    _chk(ring.actions, "ring.actions", (ring.rows, n, a), th.float32)
+    for t, nm in ((ring.rewards, "ring.rewards"), (ring.dones, "ring.dones"), (ring.timeouts, "ring.timeouts")):
+        _chk(t, nm, (ring.rows, n), th.float32)
+    if len(act_low) != a or len(act_high) != a:
+        raise ValueError(f"act_low/act_high need {a} entries")
+    dev = env_obs.device
+    ep_return = th.zeros(n, ep_stride, dtype=th.float64, device=dev)
+    ep_len = th.zeros(n, ep_stride, dtype=th.int32, device=dev)
+    ep_done = th.zeros(n, dtype=th.int32, device=dev)
+    explored = th.zeros(ring.rows, n, dtype=th.uint8, device=dev) if record_explored else None
+    collect_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, coef, integrator, env_obs, step_count, pcg_state, squashed, act_low,
+                          act_high, ring, n_steps, row0, explore_prob, seed, index_offset, step_offset, ep_return, ep_len, ep_stride, ep_done,
+                          explored, static_init)
+    return (ep_return, ep_len, ep_done) + ((explored,) if record_explored else ())
+
+
+def collect_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, coef, integrator, env_obs, step_count, pcg_state, squashed, act_low,
+                          act_high, ring, n_steps, row0, explore_prob, seed, index_offset, step_offset, ep_return, ep_len, ep_stride, ep_done,
+                          explored=None, static_init=None):
+    """`collect_episodes` into caller-owned result buffers; nothing is checked beyond what the entry point itself checks."""
+    n, d = env_obs.shape
+    n_out = w3.shape[0]
+    a = n_out // 2 if head == 0 else n_out
+    lo = (C.c_float * a)(*[float(v) for v in act_low])
+    hi = (C.c_float * a)(*[float(v) for v in act_high])
+    net = nv.PolicyMlp(d, w1.shape[0], w2.shape[0], a, act, head, out_act, 0, w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(),
+                       w3.data_ptr(), b3.data_ptr(), None if w2_swz is None else w2_swz.data_ptr())
+    check(nv.lib().cstr_collect_episodes_f32(C.byref(net), C.byref(coef), C.c_int(INTEGRATORS[integrator]), C.c_int(d), ptr(env_obs),
+                                             ptr(step_count), ptr(pcg_state), ptr(static_init), C.c_int(1 if squashed else 0), lo, hi,
+                                             C.byref(ring.c), C.c_int64(int(row0)), C.c_int64(n), C.c_int64(int(n_steps)),
+                                             C.c_float(float(explore_prob)), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_int64(int(index_offset)),
+                                             C.c_int64(int(step_offset)), ptr(ep_return), ptr(ep_len), C.c_int64(int(ep_stride)), ptr(ep_done),
+                                             ptr(explored), stream_ptr()), "cstr_collect_episodes_f32")
+
+
 def rollout_step_supported(k0: int, h1: int, h2: int, n_out: int, has_swizzled_w2: bool) -> bool:
     """cstr_rollout_step_f32 covers the pipelined policy kernel with a one-chunk first layer (see the header)."""
     return has_swizzled_w2 and k0 <= 16 and k0 % 4 == 0 and h1 <= 512 and h2 <= 512 and policy_rows_supported(k0, h1, h2, n_out)

@@ -65,9 +65,6 @@ __device__ __forceinline__ void philox_row(const uint64_t seed, const uint64_t c
     philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, tag, (uint32_t)seed, (uint32_t)(seed >> 32), x);
 }
 
-// a Philox word as a uniform in [0, 1): (word >> 8) * 2^-24
-__device__ __forceinline__ float philox_uniform(const uint32_t w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }
-
 // a teacher-forced level; outside the face: the caller's bug, clamped
 __device__ __forceinline__ int clamp_level(const int64_t t, const int K) { return t < 0 ? 0 : (t >= K ? K - 1 : (int)t); }
 

@@ -27,8 +27,13 @@
 // gap and the f64 sum of |achieved - desired| -- the numbers a lane has in registers when its episode ends. Its contract is bit-level
 // against cstr_policy_rows_fwd_f32 on the flat rows, predict()'s post-processing and cstr_goal_vec_step_f32.
 //
+// cstr_collect_episodes_f32 is the recording form on the (4, 2) layout (REC instantiations): no targets -- every env runs exactly n_steps
+// vec-steps -- and each step leaves the replay-ring row cstr_collect_step_f32 would write (action_scale_chain on the head value, the
+// stores of collect_env_lane), optionally with a uniform action drawn from Philox in place of the policy's (COLLECT_TAG). Its contract is
+// bit-level against cstr_policy_rows_fwd_f32, the draw's statement in the header and cstr_collect_step_f32.
+//
 // Termination: the loop over vec-steps is bounded by max_vec_steps whatever the data does; it ends earlier once the workgroup's 16 envs
-// have met their targets.
+// have met their targets (REC: the trip count is n_steps, fixed).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -61,16 +66,31 @@ struct GoalEvalArgs : EvalArgs {
     float *ep_goal, *ep_gap; double *ep_abs_gap;  // each optional
 };
 
-template <bool GOAL> struct EvalArgsOf { using type = EvalArgs; };
-template <> struct EvalArgsOf<true> { using type = GoalEvalArgs; };
+// the recording form (cstr_collect_episodes_f32): the Box arguments (max_vec_steps = n_steps, ep_done written only), then the ring rows the
+// launch fills and the exploration stream
+struct CollectEpArgs : EvalArgs {
+    cstr_ring_t ring; int64_t row0;
+    float explore_prob; uint64_t seed; int64_t index_offset; uint32_t step_offset;
+    uint8_t *explored;  // optional, [ring rows][n_envs]
+};
+
+template <bool GOAL, bool REC = false> struct EvalArgsOf { using type = EvalArgs; };
+template <> struct EvalArgsOf<true, false> { using type = GoalEvalArgs; };
+template <> struct EvalArgsOf<false, true> { using type = CollectEpArgs; };
+
+constexpr uint32_t COLLECT_TAG = 0xC011EC7Du;  // counter word 3 of the exploration draw: shares no counters with the other streams
 
 // GOAL = false: the Box faces, L = the env layout. GOAL = true (L = 0): the network reads the flat row [achieved | desired | observation]
 // (k0 = 6; the env state is columns 2..5 of the LDS row), the reward is goal_reward on the lane's own setpoint, and an episode's end
 // redraws the setpoint as cstr_goal_vec_step_f32 does.
-template <int ACT, int HEAD, int L, bool GOAL = false>
-__global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const typename EvalArgsOf<GOAL>::type a)
+// REC = true (GOAL = false, L = 0; cstr_collect_episodes_f32): every env runs exactly max_vec_steps vec-steps -- no targets, no early end --
+// and each of them leaves ring row row0 + t with the stores of collect_env_lane; the deterministic head value may be replaced by a
+// uniform draw over the action space (explore_prob) and goes through the collect step's action_scale_chain.
+template <int ACT, int HEAD, int L, bool GOAL = false, bool REC = false>
+__global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const typename EvalArgsOf<GOAL, REC>::type a)
 {
     static_assert(!GOAL || L == 0, "the goal face is the (4, 2) layout");
+    static_assert(!REC || (!GOAL && L == 0), "the recording form is the Box face's (4, 2) layout");
     constexpr int D = Lay<L>::D, A = Lay<L>::A, XS = 8;  // XS: row stride of the observation image
     constexpr int X0 = GOAL ? 2 : 0;                     // column of the env state in a row of the image
     extern __shared__ float eval_lds[];
@@ -103,7 +123,7 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
 #pragma unroll
         for (int j = 0; j < D; ++j) xs[lane * XS + X0 + j] = o[j >> 2][j & 3];
         st = a.step_count[env];
-        target = a.ep_done[env];
+        if constexpr (!REC) target = a.ep_done[env];
         if constexpr (GOAL) {
             tg = a.target[env];
             dg = goal_of_target(a.k, tg);
@@ -112,14 +132,18 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
             xs[lane * XS + 1] = dg;
         }
     }
-    if (wave == 0) {
-        const unsigned long long any = __ballot(env_lane && count < target);
-        if (lane == 0) go_s = any != 0ull;
+    if constexpr (!REC) {
+        if (wave == 0) {
+            const unsigned long long any = __ballot(env_lane && count < target);
+            if (lane == 0) go_s = any != 0ull;
+        }
     }
     __syncthreads();
 
     for (int64_t it = 0; it < a.max_vec_steps; ++it) {
-        if (!go_s) break;  // workgroup-uniform: written before the barrier that ends the previous trip
+        if constexpr (!REC) {
+            if (!go_s) break;  // workgroup-uniform: written before the barrier that ends the previous trip
+        }
         // ---- the policy network on the 16 observation rows (the stages of cstr_policy_rows_fwd_f32) ----
         // k0 <= 8: one k chunk. GOAL: W1's rows are 6 floats (24 bytes), so its operand loads are per element, bounded by k0 -- the
         // first-layer staging cstr_policy_rows_fwd_f32 takes for k0 = 6 (no 16-byte loads); columns 6, 7 of the image are zero
@@ -145,17 +169,37 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
         __syncthreads();
 
         // ---- predict()'s post-processing, env step, episode accounting, reset draw: a lane per env ----
-        const bool active = env_lane && count < target;
+        const bool active = REC ? env_lane : (env_lane && count < target);
         if (active) {
             const float *pr = ps + lane * 8;
             float ea[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            float sa[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // REC: the buffer action
+            uint32_t xw[4] = {0u, 0u, 0u, 0u};       // REC: the step's Philox block (word 0: the flag, words 1..A: the uniform action)
+            bool explore = false;
+            if constexpr (REC) {
+                if (a.explore_prob > 0.0f) {
+                    const uint64_t idx = (uint64_t)(a.index_offset + env);
+                    philox4x32_10((uint32_t)idx, (uint32_t)(idx >> 32), a.step_offset + (uint32_t)it, COLLECT_TAG, (uint32_t)a.seed,
+                                  (uint32_t)(a.seed >> 32), xw);
+                    explore = philox_uniform(xw[0]) < a.explore_prob;
+                }
+            }
 #pragma unroll
             for (int j = 0; j < A; ++j) {
                 float v, sd, u;
                 if (HEAD == 1) v = head_out_act(pr[j], a.out_act);
                 else sample_action_act(pr[j], pr[A + j], 0.0f, v, sd, u);  // the squashed Gaussian at its mode: what eps = 0 gives
                 const float lo = a.ab.lo[j], hi = a.ab.hi[j];
-                ea[j] = (a.squashed & 1) ? unscale_action(v, lo, hi) : clip_keep_nan(v, lo, hi);  // policies.py:375, :413 | :386
+                if constexpr (REC) {
+                    if (explore) {  // a uniform draw over the action space in place of the head value (the TU is built without contraction)
+                        const float uj = philox_uniform(xw[1 + j]);
+                        v = (a.squashed & 1) ? 2.0f * uj - 1.0f : lo + uj * (hi - lo);
+                    }
+                    if (!(a.squashed & 1)) v = clip_keep_nan(v, lo, hi);        // predict()'s clip (policies.py:386)
+                    action_scale_chain(a.squashed, lo, hi, v, false, 0.0f, sa[j], ea[j]);  // the statement of cstr_collect_step_f32
+                } else {
+                    ea[j] = (a.squashed & 1) ? unscale_action(v, lo, hi) : clip_keep_nan(v, lo, hi);  // policies.py:375, :413 | :386
+                }
             }
             float o[2][4], on[2][4], rew;
 #pragma unroll
@@ -174,11 +218,23 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
                 gap = on[0][2] - dg;
                 abs_gap += (double)fabsf(gap);
             }
+            if constexpr (REC) {  // ring row row0 + it: obs = the observation before the step, next_obs = the terminal one (collect_env_lane)
+                const int64_t e = (a.row0 + it) * a.n + env;
+                store_ring_obs<L>(a.ring.obs, e, o);
+                store_ring_obs<L>(a.ring.next_obs, e, on);
+                store_ring_act<A>(a.ring.act, e, sa);
+                store_ring_f32(a.ring.rew, e, rew);
+                store_ring_f32(a.ring.done, e, done ? 1.0f : 0.0f);
+                store_ring_f32(a.ring.timeout, e, done ? 1.0f : 0.0f);
+                if (a.explored) a.explored[e] = explore ? 1 : 0;
+            }
             cur_ret += (double)rew;  // current_rewards: float64 (evaluation.py:84, :97)
             cur_len += 1;
             if (done) {
-                a.ep_return[env * a.ep_stride + count] = cur_ret;
-                a.ep_len[env * a.ep_stride + count] = cur_len;
+                if (!REC || count < a.ep_stride) {  // REC: episodes beyond ep_stride are counted, not stored
+                    a.ep_return[env * a.ep_stride + count] = cur_ret;
+                    a.ep_len[env * a.ep_stride + count] = cur_len;
+                }
                 if constexpr (GOAL) {
                     if (a.ep_goal) a.ep_goal[env * a.ep_stride + count] = dg;
                     if (a.ep_gap) a.ep_gap[env * a.ep_stride + count] = gap;
@@ -208,9 +264,11 @@ __global__ __launch_bounds__(64 * POLICY_WAVES) void eval_episodes_kernel(const 
                 xs[lane * XS + 1] = dg;
             }
         }
-        if (wave == 0) {
-            const unsigned long long any = __ballot(env_lane && count < target);
-            if (lane == 0) go_s = any != 0ull;
+        if constexpr (!REC) {
+            if (wave == 0) {
+                const unsigned long long any = __ballot(env_lane && count < target);
+                if (lane == 0) go_s = any != 0ull;
+            }
         }
         __syncthreads();
     }
@@ -381,5 +439,79 @@ extern "C" int cstr_eval_goal_episodes_f32(const cstr_policy_mlp_t *net, const c
     if (n.head == 0) { if (n.act == 0) EVG(0, 0); else if (n.act == 1) EVG(1, 0); else EVG(2, 0); }
     else { if (n.act == 0) EVG(0, 1); else if (n.act == 1) EVG(1, 1); else EVG(2, 1); }
 #undef EVG
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_collect_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t *coef, int integrator, int obs_dim, float *env_obs,
+                                         int32_t *step_count, uint64_t *pcg_state, double *static_init, int squashed, const float *act_low,
+                                         const float *act_high, const cstr_ring_t *ring, int64_t row0, int64_t n_envs, int64_t n_steps,
+                                         float explore_prob, uint64_t seed, int64_t index_offset, int64_t step_offset, double *ep_return,
+                                         int32_t *ep_len, int64_t ep_stride, int32_t *ep_done, uint8_t *explored, cstr_stream_t stream)
+{
+    if (!net || !coef || !env_obs || !step_count || !pcg_state || !act_low || !act_high || !ring || !ep_done) return CSTR_E_BADARG;
+    if (n_envs <= 0 || n_steps <= 0 || (squashed & ~1)) return CSTR_E_BADARG;
+    const cstr_policy_mlp_t &n = *net;
+    if (!n.w1 || !n.b1 || !n.w2 || !n.b2 || !n.w3 || !n.b3 || n.k0 <= 0 || n.h1 <= 0 || n.h2 <= 0 || n.act_dim <= 0 || n.reserved) return CSTR_E_BADARG;
+    const cstr_ring_t &rg = *ring;
+    if (!rg.obs || !rg.next_obs || !rg.act || !rg.rew || !rg.done || !rg.timeout || rg.rows <= 0) return CSTR_E_BADARG;
+    if (layout_of(obs_dim, n.act_dim) < 0 || (integrator != CSTR_INTEGRATOR_EULER && integrator != CSTR_INTEGRATOR_RK4)) return CSTR_E_UNSUPPORTED;
+    if (n.k0 != obs_dim) return CSTR_E_BADARG;  // the policy reads the env's observation rows
+    if (rg.n_envs != n_envs || rg.obs_dim != obs_dim || rg.act_dim != n.act_dim) return CSTR_E_BADARG;  // the ring is this env's
+    if (layout_of(obs_dim, n.act_dim) != 0) return CSTR_E_UNSUPPORTED;  // the recording form exists for the (4, 2) layout
+    if (row0 < 0 || n_steps > rg.rows || row0 > rg.rows - n_steps) return CSTR_E_BADARG;
+    if (!(explore_prob >= 0.0f && explore_prob <= 1.0f)) return CSTR_E_BADARG;  // NaN included
+    if (step_offset < 0 || n_steps > (int64_t)1 << 32 || step_offset > ((int64_t)1 << 32) - n_steps) return CSTR_E_BADARG;  // counter word 2
+    if (ep_stride < 0 || (ep_stride > 0 && (!ep_return || !ep_len))) return CSTR_E_BADARG;
+    // the shapes of cstr_policy_rows_fwd_f32
+    if (n.act < 0 || n.act > 2 || n.out_act < 0 || n.out_act > 2 || n.head < 0 || n.head > 1 || (n.h1 & 3) || (n.h2 & 3) ||
+        (size_t)POLICY_ROWS * (n.h1 + 4 + n.h2 + 4) * sizeof(float) > 64 * 1024 || eval_lds_bytes(n) > 64 * 1024 ||
+        (n_envs + POLICY_ROWS - 1) / POLICY_ROWS > 0x7fffffff)
+        return CSTR_E_UNSUPPORTED;
+    if (rg.rows > INT64_MAX / (64 * n_envs) || (ep_stride > 0 && n_envs > INT64_MAX / (8 * ep_stride))) return CSTR_E_UNSUPPORTED;  // byte extents
+    const auto aligned4 = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; };
+    if (!aligned16(env_obs) || !aligned16(pcg_state) || !aligned16(n.w1) || !aligned16(n.w2) || !aligned16(n.w3) ||
+        (n.w2_swizzled && !aligned16(n.w2_swizzled)) || !aligned8(ep_return) || (static_init && !aligned8(static_init)) ||
+        !aligned4(step_count) || !aligned4(ep_len) || !aligned4(ep_done) || !aligned16(rg.obs) || !aligned16(rg.next_obs) || !aligned8(rg.act) ||
+        !aligned4(rg.rew) || !aligned4(rg.done) || !aligned4(rg.timeout))
+        return CSTR_E_BADARG;
+    constexpr int A = 2, D = 4;
+    ActBounds ab;
+    for (int j = 0; j < 4; ++j) {
+        ab.lo[j] = j < A ? act_low[j] : -1.0f;
+        ab.hi[j] = j < A ? act_high[j] : 1.0f;
+        if (!(ab.hi[j] > ab.lo[j])) return CSTR_E_BADARG;
+    }
+    {   // nothing the launch writes may overlap anything it reads or anything else it writes (the env state is read and written)
+        const int n_out = (n.head == 0 ? 2 : 1) * A, kc1 = (n.h1 + 15) / 16, kc2 = (n.h2 + 15) / 16;
+        const int64_t cells = rg.rows * n_envs, slots = n_envs * ep_stride;
+        constexpr int NW = 14, NR = 7;
+        const Span wr[NW] = {span_of(rg.obs, 4 * D * cells), span_of(rg.next_obs, 4 * D * cells), span_of(rg.act, 4 * A * cells),
+                             span_of(rg.rew, 4 * cells), span_of(rg.done, 4 * cells), span_of(rg.timeout, 4 * cells), span_of(explored, cells),
+                             span_of(ep_return, 8 * slots), span_of(ep_len, 4 * slots), span_of(ep_done, 4 * n_envs),
+                             span_of(env_obs, 4 * D * n_envs), span_of(step_count, 4 * n_envs), span_of(pcg_state, 32 * n_envs),
+                             span_of(static_init, 32 * n_envs)};
+        const Span rd[NR] = {span_of(n.w1, 4LL * n.h1 * n.k0), span_of(n.b1, 4LL * n.h1), span_of(n.w2, 4LL * n.h2 * n.h1), span_of(n.b2, 4LL * n.h2),
+                             span_of(n.w3, 4LL * n_out * n.h2), span_of(n.b3, 4LL * n_out), span_of(n.w2_swizzled, 1024LL * kc1 * kc2)};
+        for (int i = 0; i < NW; ++i) {
+            for (int j = 0; j < NR; ++j)
+                if (overlaps(wr[i], rd[j])) return CSTR_E_BADARG;
+            for (int j = i + 1; j < NW; ++j)
+                if (overlaps(wr[i], wr[j])) return CSTR_E_BADARG;
+        }
+    }
+    CollectEpArgs a;
+    static_cast<EvalArgs &>(a) = EvalArgs{n.w1, n.b1, n.w2, n.b2, n.w3, n.b3, n.w2_swizzled, n.k0, n.h1, n.h2, A, n.out_act, policy_runs_split_k_head(n) ? 1 : 0,
+                                          *coef, env_obs, step_count, pcg_state, static_init, squashed, integrator, ab, ep_return, ep_len, ep_done,
+                                          ep_stride, n_envs, n_steps};
+    a.ring = rg; a.row0 = row0;
+    a.explore_prob = explore_prob; a.seed = seed; a.index_offset = index_offset; a.step_offset = (uint32_t)step_offset;
+    a.explored = explored;
+    const unsigned grid = (unsigned)((n_envs + POLICY_ROWS - 1) / POLICY_ROWS);
+    const size_t lds = eval_lds_bytes(n);
+    hipStream_t s = (hipStream_t)stream;
+#define EVR(A_, H_) eval_episodes_kernel<A_, H_, 0, false, true><<<grid, 64 * POLICY_WAVES, lds, s>>>(a)
+    if (n.head == 0) { if (n.act == 0) EVR(0, 0); else if (n.act == 1) EVR(1, 0); else EVR(2, 0); }
+    else { if (n.act == 0) EVR(0, 1); else if (n.act == 1) EVR(1, 1); else EVR(2, 1); }
+#undef EVR
     return (int)hipGetLastError();
 }

@@ -19,6 +19,9 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
     out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
+// a Philox word as a uniform in [0, 1): (word >> 8) * 2^-24 (the discrete heads' draws, the episode collector's exploration draw)
+__device__ __forceinline__ float philox_uniform(const uint32_t w) { return (float)(w >> 8) * (1.0f / 16777216.0f); }
+
 // Box-Muller in two independent halves (the rollout kernel gives them to two waves): z0 = radius(a) * cos, z1 = radius(a) * sin
 __device__ __forceinline__ float box_muller_radius(uint32_t a)
 {

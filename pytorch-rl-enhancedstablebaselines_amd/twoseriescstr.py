@@ -161,3 +161,88 @@ class TwoSeriesCSTREnv:
 
     def close(self):
         self._vec = None
+
+
+def _plot_episode_states(episode_states: np.ndarray, plt) -> None:
+    """The 2 x 2 figure of the reference's evaluate_model: per state the mean over the episodes with a +-1 std band, the C2 target line."""
+    fig, axes = plt.subplots(2, 2, figsize=(12, 6))
+    names = ["Reactor 1 Concentration", "Reactor 1 Temperature", "Reactor 2 Concentration", "Reactor 2 Temperature"]
+    for k, ax in enumerate(axes.reshape(-1)):
+        mean, std = np.nanmean(episode_states[:, :, k], axis=0), np.nanstd(episode_states[:, :, k], axis=0)
+        ax.plot(mean, color="blue", label="Average " + names[k])
+        ax.fill_between(range(len(mean)), mean - std, mean + std, color="lightblue", alpha=0.3, label="±1 Std Dev")
+        if k == 2:
+            ax.axhline(y=0.2, color="red", linestyle="--")
+        ax.set_title("Average with Standard Deviation")
+        ax.legend()
+    plt.show()
+    plt.close()
+
+
+def evaluate_model(model, env, num_episodes: int = 10, plot: Optional[bool] = None):
+    """reference: twoseriescstr.py:522-588 -> (episode_rewards, episode_states): the closed-loop response of a trained controller.
+    `episode_rewards` is a list with one return per episode, `episode_states` [num_episodes, Lmax, 4] holds [C1, T1, C2, T2] in mol/L and K
+    BEFORE each step (row 0 is the reset state; shorter episodes are padded with NaN). The reference's lines are printed.
+
+    `env`: a `CSTRVecEnv`, which is also what this package's `DummyVecEnv([...])` returns. With ONE env the reference's loop is followed:
+    `env.reset()` in front of every episode, then one launch of `max_steps` vec-steps (cstr_collect_episodes_f32) -- the reset stream takes
+    the auto-reset draw at the episode's end AND the explicit reset, as the reference's does, and the return is accumulated with the
+    reference's own statement on the float32 step rewards. With MORE envs (an extension: the reference's `while not done` only works
+    for one) the episodes are spread over the envs in one launch, `evaluate_trajectories`' order.
+    `plot`: None = the reference's 2 x 2 figure if matplotlib imports and its backend is interactive, False = never, True = always
+    (ImportError if matplotlib is missing). Models / envs the launch does not cover raise ValueError."""
+    from core.common import evaluation, hip_ops
+    from core.common.vec_env import CSTRVecEnv
+
+    if not isinstance(env, CSTRVecEnv):
+        raise ValueError(f"evaluate_model: pass a CSTRVecEnv or this package's DummyVecEnv([...]) of TwoSeriesCSTREnv, got {type(env).__name__}")
+    why = evaluation._why_not_collected(model, env)
+    if why is not None:
+        raise ValueError(f"evaluate_model does not cover {why}")
+    if int(num_episodes) <= 0:
+        raise ValueError(f"num_episodes must be positive, got {num_episodes}")
+    plt = None
+    if plot is None or plot:
+        try:
+            import matplotlib
+            import matplotlib.pyplot as plt
+        except ImportError:
+            if plot:
+                raise
+            plt = None
+        if plt is not None and plot is None:
+            interactive = [b.lower() for b in getattr(matplotlib.rcsetup, "interactive_bk", [])]
+            if matplotlib.get_backend().lower() not in interactive:
+                plt = None
+    if env.num_envs == 1:
+        import torch as th
+
+        limit = int(env.coef.max_steps)
+        with th.cuda.device(env.device):
+            ring = hip_ops.DeviceRing(limit, 1, env.obs_dim, env.act_dim, env.device)
+        episode_rewards, states = [], []
+        for _ in range(int(num_episodes)):
+            env.reset_device()
+            evaluation._collect_launch(model, env, ring, limit)
+            traj = evaluation._trajectories(env, ring, 1)
+            total_reward = 0
+            for r in ring.rewards.cpu().numpy()[:int(traj["episode_lengths"][0]), 0]:
+                total_reward += r
+            episode_rewards.append(total_reward)
+            states.append(traj["states"][0])
+        l_max = max(s.shape[0] for s in states)
+        episode_states = np.full((len(states), l_max, 4), np.nan)
+        for e, s in enumerate(states):
+            episode_states[e, :s.shape[0]] = s[:s.shape[0]]
+    else:
+        traj = evaluation.evaluate_trajectories(model, env, int(num_episodes))
+        episode_rewards, episode_states = list(traj["episode_rewards"]), traj["states"]
+    if plt is not None:
+        _plot_episode_states(episode_states, plt)
+    lengths = (~np.isnan(episode_states[:, :, 0])).sum(axis=1)
+    for i in range(episode_states.shape[0]):
+        final = episode_states[i, max(int(lengths[i]) - 1, 0), :] if episode_states.shape[1] else episode_states[i, :0, :]
+        print(f"Episode {i+1} 的最终稳态:[C1, T1, C2, T2]={final}")
+    print(f"平均回合奖励: {np.mean(episode_rewards)}")
+    print(f"奖励标准差: {np.std(episode_rewards)}")
+    return episode_rewards, episode_states

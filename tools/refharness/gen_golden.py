@@ -912,6 +912,51 @@ def gen_eval():
     save("evaluate_policy_kat.npz", **out)
 
 
+def gen_evalmodel():
+    """The reference's evaluate_model (twoseriescstr.py:522-588), unmodified, under the Agg backend: a seeded, untrained TD3 with
+    net_arch [16, 16] on DummyVecEnv([TwoSeriesCSTREnv(init_mode=m)]) for m in static, random; 3 episodes each. Stored per mode: the
+    returned episode_rewards and episode_states [3, 400, 4], and the actions `model.predict` returned, taken by a recording proxy around
+    the model (the reference only calls `.predict` on it); once: the actor's weights and the env seed."""
+    import contextlib
+    import io
+
+    os.environ["MPLBACKEND"] = "Agg"
+    import matplotlib
+
+    matplotlib.use("Agg", force=True)
+    from core.common.vec_env.dummy_vec_env import DummyVecEnv
+    from core.td3.td3 import TD3
+    from twoseriescstr import TwoSeriesCSTREnv, evaluate_model
+
+    env_seed, model_seed, n_episodes = 21, 4, 3
+
+    class Recorder:
+        def __init__(self, model):
+            self.model, self.actions = model, []
+
+        def predict(self, *a, **kw):
+            out = self.model.predict(*a, **kw)
+            self.actions.append(np.array(out[0], np.float32).reshape(-1))
+            return out
+
+    model = TD3("MlpPolicy", DummyVecEnv([lambda: TwoSeriesCSTREnv()]), seed=model_seed, device="cpu", policy_kwargs=dict(net_arch=[16, 16]))
+    sd = {k: v.detach().cpu().numpy().copy() for k, v in model.actor.mu.state_dict().items()}
+    out = dict(dims=np.array([env_seed, model_seed, n_episodes, 16, 16], np.int64), w1=sd["0.weight"], b1=sd["0.bias"], w2=sd["2.weight"],
+               b2=sd["2.bias"], w3=sd["4.weight"], b3=sd["4.bias"])
+    for mode in ("static", "random"):
+        venv = DummyVecEnv([lambda: TwoSeriesCSTREnv(init_mode=mode)])
+        venv.seed(env_seed)
+        rec = Recorder(model)
+        with contextlib.redirect_stdout(io.StringIO()):
+            rewards, states = evaluate_model(rec, venv, num_episodes=n_episodes)
+        assert states.shape == (n_episodes, 400, 4) and len(rec.actions) == n_episodes * 400
+        out[f"{mode}/episode_rewards"] = np.asarray(rewards, np.float64)
+        out[f"{mode}/episode_rewards_dtype"] = np.array(str(np.asarray(rewards).dtype))
+        out[f"{mode}/episode_states"] = np.asarray(states)
+        out[f"{mode}/actions"] = np.stack(rec.actions).reshape(n_episodes, 400, 2)
+    save("evaluate_model_kat.npz", **out)
+
+
 def gen_info():
     """The 16-key `info` dict of TwoSeriesCSTREnv.step (twoseriescstr.py:441-452) with the nine compute_reward diagnostics (:379-389),
     five of which carry weight 0.0 and per-env memory: a seeded 80-step trajectory that approaches the target (stability counter runs),
@@ -2417,7 +2462,7 @@ def gen_a2c_goal():
     save("a2c_goal_train_kat_small.npz", **_goal_run_extras(out, 4))
 
 
-GENS = {"her": gen_her, "her_learners": gen_her_learners, "ppo_multidiscrete": gen_ppo_multidiscrete, "a2c_multidiscrete": gen_a2c_multidiscrete, "ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
+GENS = {"her": gen_her, "her_learners": gen_her_learners, "ppo_multidiscrete": gen_ppo_multidiscrete, "a2c_multidiscrete": gen_a2c_multidiscrete, "ppo_discrete": gen_ppo_discrete, "a2c_discrete": gen_a2c_discrete, "callbacks": gen_callbacks, "a2c": gen_a2c, "ppo": gen_ppo, "bcq": lambda: (gen_bcq(), gen_bcq_predict()), "maddpg_default": gen_maddpg_default, "maddpg4_default": gen_maddpg4_default, "maddpg4": gen_maddpg4, "ddpg": gen_ddpg, "eval": gen_eval, "evalmodel": gen_evalmodel, "info": gen_info, "config1": gen_config1, "env": gen_env, "resets": gen_resets, "vecnorm": gen_vecnorm, "vecenv": gen_vecenv, "sampler": gen_sampler, "replay": gen_replay, "sac": gen_sac,
         "sac_ncrit": gen_sac_ncrit, "sac_sde": gen_sac_sde, "td3_ncrit": gen_td3_ncrit,
         "td3": gen_td3, "init": gen_init, "maddpg": gen_maddpg, "iddpg": gen_iddpg, "checkpoint": gen_checkpoint, "dqn": gen_dqn,
         "rmsprop_tf": gen_rmsprop_tf, "ppo_goal": gen_ppo_goal, "a2c_goal": gen_a2c_goal}
