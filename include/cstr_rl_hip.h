@@ -617,6 +617,41 @@ int cstr_sde_param_grad_f32(const float *h, int64_t ldh, int64_t batch, int late
 /* Deterministic-policy actor loss (core/td3/td3.py:194, core/maddpg/maddpg.py:174): loss = -mean(q), gq = -1/B. */
 int cstr_neg_mean_loss_f32(const float *q, float *gq, float *loss_out, float *loss_sum, int64_t batch, cstr_stream_t stream);
 
+/* ---- TD3+BC (csrc/cstr_td3bc.hip; core/td3bc/td3bc.py; Fujimoto & Gu 2021) -------------------------------------------------------
+ * TD3's gradient step on a fixed dataset with one more term in the actor loss. Both entry points validate on the host without
+ * dereferencing anything and then only enqueue; f32; deterministic and bit-identical on relaunch (no float atomics).
+ *
+ * cstr_td3bc_actor_loss_f32 (one launch, one 256-thread workgroup; it stands where TD3 launches cstr_neg_mean_loss_f32):
+ *   lam  = alpha / (sum_b |q_b| / B)                         a constant of the batch: no gradient flows through it
+ *   loss = -(lam * (sum_b q_b / B)) + sum_{b,j} (pi_bj - act_bj)^2 / (B * A)
+ *   gq[b] = -(lam / B) for every row;  aux (3 floats, may be NULL) = {lam, -(lam * mean q), the second term}
+ *   loss_out (may be NULL) is stored, loss_sum (may be NULL) accumulated: the loss heads' convention.
+ * d(loss)/d(pi) = 2 (pi - act) / (B A) is NOT written here: cstr_td3bc_act_bwd_rows_f32 adds it where the gradient is consumed.
+ * Reduction order: thread t of 256 sums rows t, t + 256, ... in ascending order (sum |q| in a first pass; sum q and, row by row with
+ * the columns ascending, sum (pi - act)^2 in a second); each partial goes through a 64-lane shuffle tree (offsets 32, 16, ... 1),
+ * the four wave sums combine as (s0 + s1) + (s2 + s3). The sums are accumulated in float64 (pi - act and its square are exact
+ * there) and lam, gq, the two terms and the loss are each rounded to float32 once, lam first: the others follow from the float32
+ * lam. sum |q| == 0 is not guarded: lam = alpha / 0 = inf (NaN for alpha == 0), gq = -inf, the Q term and the loss NaN -- what
+ * the float32 torch statement gives (the published code's behaviour).
+ * q [batch] contiguous; pi / act [batch][act_dim] with row strides ldpi / ldact >= act_dim floats (the action columns of packed critic
+ * inputs), 4-byte aligned. CSTR_E_BADARG: NULL q / pi / act / gq, batch <= 0, act_dim <= 0, ld* < act_dim, a pointer off a 4-byte
+ * boundary, alpha negative or NaN, an output overlapping an input or another output. CSTR_E_UNSUPPORTED: batch >
+ * CSTR_TD3BC_MAX_BATCH, act_dim > CSTR_TD3BC_MAX_ACT.
+ *
+ * cstr_td3bc_act_bwd_rows_f32 (one launch; it stands where the deterministic actor's last layer launches cstr_bias_act_bwd_rows_f32):
+ *   gz[m][n] = (gy[m][n] + coef * (y[m][n] - act[m][n])) * act'(y[m][n]),   coef = 2 / (B * A) for the loss above
+ * with cstr_bias_act_bwd_rows_f32's expressions for act' (NONE: 1; RELU: y > 0; TANH: 1 - y * y) and its rounding points (the build
+ * does not contract). coef == 0 adds nothing and is bit-identical to cstr_bias_act_bwd_rows_f32. gy / y / act are column blocks of
+ * row-major matrices (row strides ldgy / ldy / ldact >= n floats, 4-byte aligned), gz is contiguous [m][n]; y is needed for every
+ * act_kind. CSTR_E_BADARG: NULL pointers, m or n <= 0, ld* < n, a pointer off a 4-byte boundary, gz overlapping an input.
+ * CSTR_E_UNSUPPORTED: an unknown act_kind, m or n beyond 32 bits. */
+#define CSTR_TD3BC_MAX_BATCH CSTR_MAX_SAMPLE_BATCH /* 16384, as the other single-workgroup loss heads */
+#define CSTR_TD3BC_MAX_ACT (2 * CSTR_MAX_HEAD_ACT)  /* 8: the widest row the action-head kernels handle (mean | log_std) */
+int cstr_td3bc_actor_loss_f32(const float *q, const float *pi, int64_t ldpi, const float *act, int64_t ldact, float alpha, float *gq,
+                              float *loss_out, float *loss_sum, float *aux, int64_t batch, int act_dim, cstr_stream_t stream);
+int cstr_td3bc_act_bwd_rows_f32(const float *gy, int64_t ldgy, const float *y, int64_t ldy, const float *act, int64_t ldact, float coef,
+                                int act_kind, float *gz, int64_t m, int64_t n, cstr_stream_t stream);
+
 /* cstr_linear_bwd_weight_sets_f32 with the OPTIMISER STEP inside (single-GPU training: no collective sits between a gradient and
  * its Adam step; torch.optim.Adam's arithmetic, core/sac/sac.py:266-268, :279-281): the workgroup that has reduced a 16 x 16 tile of
  * dW (and db) applies Adam to exactly those parameters -- parameter / moment quads requested at entry, one launch instead of two.

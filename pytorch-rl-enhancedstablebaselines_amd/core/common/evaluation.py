@@ -191,8 +191,27 @@ def _fused_operands(policy) -> Optional[dict]:
         if net is None:
             return None
         l1, l2, act = net
+        if getattr(policy, "normalize_states", False):  # TD3+BC: the env's raw observations go through the dataset's statistics
+            l1 = _fold_obs_norm(l1, getattr(policy, "obs_norm", None))
         return dict(layers=(l1, l2), w3=mods[4].weight, b3=mods[4].bias, act=act, head=1, out_act=2, goal=goal)
     return None
+
+
+def _fold_obs_norm(l1: nn.Linear, obs_norm):
+    """The first layer on (o - mean) / std as a layer on o: W' = W / std per input column, b' = b - W' @ mean. Temporaries of one
+    call (float64 arithmetic, float32 storage); the model's parameters are untouched. A policy trained on normalised observations
+    without its statistics is an error, never a launch on the raw network."""
+    if obs_norm is None or obs_norm[0] is None or obs_norm[1] is None:
+        raise RuntimeError("the policy was trained on normalised observations (normalize_states=True) and its statistics are missing: "
+                           "the one-launch evaluation would step the env with a policy that sees raw observations")
+    from types import SimpleNamespace
+
+    with th.no_grad():
+        mean, std = (t.to(l1.weight.device, th.float64) for t in obs_norm)
+        w = l1.weight.detach().to(th.float64) / std
+        b = l1.bias.detach().to(th.float64) - w @ mean
+        return SimpleNamespace(weight=w.to(th.float32).contiguous(), bias=b.to(th.float32).contiguous(), in_features=l1.in_features,
+                               out_features=l1.out_features)
 
 
 def _why_not_fused(model, env, deterministic: bool) -> Optional[str]:

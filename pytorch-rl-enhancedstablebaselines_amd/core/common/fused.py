@@ -16,6 +16,8 @@ leaves every GEMM to PyTorch-ROCm (`torch.mm` -> rocBLAS) with the HIP epilogues
   * deterministic actors write their action into the critic input and read its gradient columns in place (`_LinearXbufFn`,
     `_ActorGroupFn`): no torch.cat, no gather copies;
   * `squashed_gaussian([mean | log_std], eps)` = 1 launch forward, 1 launch backward (analytic);
+  * TD3+BC (`PerLayerTwinCritic.td3bc_pass`): the actor loss with its batch-wide normaliser = 1 launch where TD3 launches -mean(Q1),
+    the behaviour-cloning gradient inside the backward launch of the actor's last layer (`_LinearXbufFn`'s `bc`, `bc_tap`);
   * BCQ (`FastBcq`): the VAE latent (`_VaeLatentFn`) and the perturbation step (`_PerturbFn`) = 1 launch forward, 1 backward each,
     candidates expanded into the decoder / perturbation / critic inputs by one launch.
 
@@ -166,11 +168,13 @@ class _LinearXbufFn(th.autograd.Function):
     gradient in place (cstr_bias_act_bwd_rows_f32: no gather copy). The buffer is the output."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, act: int, train_params: bool, below, xbuf):
+    def forward(ctx, x, weight, bias, act: int, train_params: bool, below, xbuf, bc=None):
+        """`bc` = (dataset actions [M, N], coef): TD3+BC's behaviour-cloning gradient coef * (y - actions) joins the gradient of the
+        action columns in the backward's own launch (cstr_td3bc_act_bwd_rows_f32 in place of cstr_bias_act_bwd_rows_f32)."""
         n = weight.shape[0]
         y = xbuf[:, xbuf.shape[1] - n:]
         hip_ops.linear_act_fwd_sets([(x, weight, bias, y)], act)
-        ctx.act, ctx.train_params, ctx.below, ctx.n = act, train_params, below, n
+        ctx.act, ctx.train_params, ctx.below, ctx.n, ctx.bc = act, train_params, below, n, bc
         ctx.save_for_backward(x, weight)
         ctx.y = y.detach()
         ctx.wgrad, ctx.bgrad = (weight.grad, bias.grad) if train_params else (None, None)
@@ -183,13 +187,37 @@ class _LinearXbufFn(th.autograd.Function):
         if g_buf.stride(1) != 1:
             g_buf = g_buf.contiguous()
         gy = g_buf[:, g_buf.shape[1] - ctx.n:]
-        if ctx.act != ACT_NONE:
+        if ctx.bc is not None:
+            gz = hip_ops.td3bc_act_bwd_rows(gy, ctx.y, ctx.bc[0], ctx.bc[1], ctx.act, th.empty(gy.shape, dtype=gy.dtype, device=gy.device))
+        elif ctx.act != ACT_NONE:
             gz = hip_ops.bias_act_bwd_rows(gy, ctx.y, ctx.act, th.empty(gy.shape, dtype=gy.dtype, device=gy.device))
         else:
             gz = gy.contiguous()
         _param_grads(ctx, gz, x)
         dx = _input_grad(gz, weight, x, ctx.below) if ctx.needs_input_grad[0] else None
-        return dx, None, None, None, None, None, None
+        return dx, None, None, None, None, None, None, None
+
+
+class _BcTapFn(th.autograd.Function):
+    """Identity on a deterministic actor's output `pi` [M, N] whose backward adds TD3+BC's behaviour-cloning gradient
+    coef * (pi - actions) to what arrives (cstr_td3bc_act_bwd_rows_f32 without an activation): the form for the passes that do not
+    write the action into the critic input (`_LinearXbufFn`): rocBLAS GEMMs, a one-column action."""
+
+    @staticmethod
+    def forward(ctx, pi, actions, coef: float):
+        ctx.pi, ctx.actions, ctx.coef = pi.detach(), actions, coef
+        return pi.view_as(pi)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g.stride(-1) != 1:
+            g = g.contiguous()
+        gz = hip_ops.td3bc_act_bwd_rows(g, ctx.pi, ctx.actions, ctx.coef, ACT_NONE, th.empty(g.shape, dtype=g.dtype, device=g.device))
+        return gz, None, None
+
+
+def bc_tap(pi: th.Tensor, actions: th.Tensor, coef: float) -> th.Tensor:
+    return _BcTapFn.apply(pi, actions, coef)
 
 
 def linear(x: th.Tensor, weight: th.Tensor, bias: th.Tensor, act: int, train_params: bool, below=None,
@@ -295,14 +323,15 @@ class FastMLP:
                 and lin.weight.is_contiguous() and lin.weight.data_ptr() % 16 == 0 and not (len(layers) == 2 and layers[-1][0].out_features == 1))
 
     def __call__(self, x: th.Tensor, train_params: bool = True, out_grad_is_dz: bool = False, xbuf: Optional[th.Tensor] = None,
-                 gather=None, smooth: Optional[dict] = None) -> th.Tensor:
+                 gather=None, smooth: Optional[dict] = None, bc=None) -> th.Tensor:
         """`out_grad_is_dz`: the consumer is a fused layer built with `below=self.tail_below(...)` (see _input_grad).
         `xbuf` [M, W]: the output is written into its last out_features columns and the BUFFER is returned (a deterministic actor's
         action straight into the critic input, differentiable).
         `gather` = ReplayBuffer.take_predrawn(pb) (inference only, `gather_supported`): x is the not-yet-gathered next-observation
         block of `pb`; the first layer fetches the sampled rows from the ring and writes `pb` for the launches behind it.
         `smooth` = dict(noise | rng_ctl, sigma, clip, out) (inference only, `smooth_supported`): the last layer adds the target policy
-        smoothing and writes the result into `out` (the action columns of the target critic's input), which is returned."""
+        smoothing and writes the result into `out` (the action columns of the target critic's input), which is returned.
+        `bc` = (dataset actions, coef) (with `xbuf` only): see `_LinearXbufFn.forward`."""
         layers = self.layers
         if smooth is not None and (th.is_grad_enabled() or train_params or xbuf is not None or not self.smooth_supported(x)):
             raise NotImplementedError("FastMLP smooth: a no-grad inference pass through the per-layer kernels only")
@@ -326,7 +355,9 @@ class FastMLP:
             lin, act = layers[-1]
             if train_params and (lin.weight.grad is None or lin.bias.grad is None):
                 raise RuntimeError("fused linear: parameter gradients must be views of a ParamArena gradient buffer")
-            return _LinearXbufFn.apply(x, lin.weight, lin.bias, act, train_params, below if x.requires_grad else None, xbuf)
+            return _LinearXbufFn.apply(x, lin.weight, lin.bias, act, train_params, below if x.requires_grad else None, xbuf, bc)
+        if bc is not None:
+            raise NotImplementedError("FastMLP bc: with xbuf only (elsewhere: fused.bc_tap on the output)")
         if self._whole_net_ok(x, train_params):  # a deterministic actor's rollout pass: ONE launch, nothing kept
             (l1, act), (l2, _), (l3, out_act) = layers
             out = th.empty(x.shape[0], l3.out_features, dtype=x.dtype, device=x.device)
@@ -1394,6 +1425,17 @@ class PerLayerTwinCritic:
         else:
             hip_ops.neg_mean_loss(qs_pi[0], gq[0], loss_out, loss_sum)
             backward_q(qs_pi, gq)
+
+    def td3bc_pass(self, x_pi: th.Tensor, pi: th.Tensor, actions: th.Tensor, alpha: float, loss_out, loss_sum, aux) -> th.Tensor:
+        """TD3+BC's actor loss -lam * mean(Q1(x_pi)) + mean((pi - actions)^2), lam = alpha / mean|Q1| a constant, through the first
+        (frozen) critic, and its backward: the non-riding branch of `neg_mean_pass` with cstr_td3bc_actor_loss_f32 as the loss launch
+        (lam needs the whole batch's |Q| before any row's gradient exists, so the loss cannot ride in the backward's first launch).
+        The behaviour-cloning gradient is added by whatever produced `pi` (`_LinearXbufFn`'s bc, `bc_tap`). Returns Q1(x_pi)."""
+        qs_pi = self.critic.forward_input(x_pi, train_params=False, only_first=True)
+        gq = self._scratch(qs_pi[0])
+        hip_ops.td3bc_actor_loss(qs_pi[0].detach(), pi.detach(), actions, alpha, gq[0], loss_out, loss_sum, aux)
+        backward_q(qs_pi, gq)
+        return qs_pi[0].detach()
 
     def sac_actor_pass(self, x_pi: th.Tensor, log_prob: th.Tensor, ent_coef: th.Tensor, loss_out, loss_sum) -> None:
         """mean(ent_coef * log_prob - min_i Q_i(x_pi)) through all (frozen) critics; backward from both roots, the Q values and

@@ -1332,6 +1332,43 @@ def neg_mean_loss(q, gq, loss_out=None, loss_sum=None):
           "cstr_neg_mean_loss_f32")
 
 
+# ---- TD3+BC (csrc/cstr_td3bc.hip) ---------------------------------------------------------------------------------------------------
+def td3bc_supported(batch: int, act_dim: int) -> bool:
+    return 0 < batch <= nv.TD3BC_MAX_BATCH and 0 < act_dim <= nv.TD3BC_MAX_ACT
+
+
+def td3bc_actor_loss(q, pi, act, alpha: float, gq, loss_out=None, loss_sum=None, aux=None):
+    """TD3+BC's actor loss -lam * mean(q) + mean((pi - act)^2), lam = alpha / mean|q| (a constant), as a backward root
+    (cstr_td3bc_actor_loss_f32): gq = -lam / B; aux [3] = {lam, -lam * mean(q), the second term}. pi / act [B, A] may be column
+    blocks of wider row-major matrices."""
+    b = q.numel()
+    _vec(q, "q", b), _vec(gq, "gq", b)
+    if pi.dim() != 2 or pi.shape[0] != b:
+        raise ValueError(f"pi: needs a [{b}, A] matrix, got shape {tuple(pi.shape)}")
+    a = pi.shape[1]
+    ldpi, ldact = _rows(pi, "pi", b, a), _rows(act, "act", b, a)
+    if aux is not None:
+        _vec(aux, "aux", 3)
+    for t, nm in ((loss_out, "loss_out"), (loss_sum, "loss_sum")):
+        if t is not None:
+            _vec(t, nm, 1)
+    check(nv.lib().cstr_td3bc_actor_loss_f32(ptr(q), ptr(pi), C.c_int64(ldpi), ptr(act), C.c_int64(ldact), C.c_float(alpha), ptr(gq),
+                                             ptr(loss_out), ptr(loss_sum), ptr(aux), C.c_int64(b), C.c_int(a), stream_ptr()),
+          "cstr_td3bc_actor_loss_f32")
+
+
+def td3bc_act_bwd_rows(gy, y, act, coef: float, act_kind: int, gz):
+    """gz = (gy + coef * (y - act)) * act'(y) (cstr_td3bc_act_bwd_rows_f32): `bias_act_bwd_rows` with the behaviour-cloning gradient
+    added where the incoming gradient is read; gy / y / act may be column blocks of wider row-major matrices, gz is contiguous."""
+    m, n = gz.shape
+    _chk(gz, "gz", (m, n), th.float32)
+    ldg, ldy, lda = _rows(gy, "gy", m, n), _rows(y, "y", m, n), _rows(act, "act", m, n)
+    check(nv.lib().cstr_td3bc_act_bwd_rows_f32(ptr(gy), C.c_int64(ldg), ptr(y), C.c_int64(ldy), ptr(act), C.c_int64(lda), C.c_float(coef),
+                                               C.c_int(act_kind), ptr(gz), C.c_int64(m), C.c_int64(n), stream_ptr()),
+          "cstr_td3bc_act_bwd_rows_f32")
+    return gz
+
+
 # ---- row-chain kernels (csrc/cstr_chain.hip, include/cstr_rl_hip.h "row-chain kernels") -------------------------------------------
 def chain_supported(h1: int, h2: int, batch: int) -> bool:
     """Widths multiples of 4; forward launches hold a 16 x (H1 + 4) panel and W1 staged as [H1][8 or 16] in 64 KB of LDS."""

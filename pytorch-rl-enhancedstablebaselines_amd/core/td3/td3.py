@@ -136,7 +136,7 @@ class TD3(OffPolicyAlgorithm):
             self.critic.optimizer.step()
             actor_loss = None
             if n_updates % self.policy_delay == 0:  # :192-206
-                actor_loss = -self.critic.q1_forward(replay_data.observations, self.actor(replay_data.observations)).mean()
+                actor_loss = self._actor_loss_torch(replay_data)
                 self._loss_sums["actor"] += actor_loss.detach()
                 self.actor.optimizer.zero_grad()
                 actor_loss.backward()
@@ -186,14 +186,7 @@ class TD3(OffPolicyAlgorithm):
         self.critic.optimizer.step()
         actor_done = False
         if n_updates % self.policy_delay == 0:  # :192-206
-            if pb is not None and fused.USE_FUSED_LINEAR and self._fast_actor.layers[-1][0].out_features > 1:
-                # the actor's last layer writes into x_pi = (obs | .): no torch.cat, and its backward reads the action columns
-                # of the critic's input gradient in place
-                x_pi = self._fast_actor(rd.observations, xbuf=pb.x_pi.detach())
-            else:
-                x_pi = th.cat([rd.observations, self._fast_actor(rd.observations)], dim=1)
-            a_out, a_sum = self._loss_slot("actor")
-            blk.neg_mean_pass(x_pi, a_out, a_sum)  # -mean(Q1) (:194) through the (frozen) first Q network
+            a_out = self._actor_pass_fused(pb, rd, blk)
             self._allreduce_grads(pol.actor_arena)
             # the actor's step, the critics' soft update (disjoint arenas) and the actor target's soft update (by the threads that
             # have just computed the new actor weights) in ONE launch (:199, :204, :205)
@@ -204,6 +197,24 @@ class TD3(OffPolicyAlgorithm):
             actor_done = True
         if self.debug_capture:
             self.last_train_tensors = blk.captured(qs, self._target_q, c_out, a_out if actor_done else None)
+
+    # ---- the actor pass: what a subclass with another actor loss replaces (core/td3bc/td3bc.py) --------------------------------
+    def _actor_loss_torch(self, replay_data) -> th.Tensor:
+        """:194 as the reference's torch statement"""
+        return -self.critic.q1_forward(replay_data.observations, self.actor(replay_data.observations)).mean()
+
+    def _actor_pass_fused(self, pb, rd, blk) -> th.Tensor:
+        """:192-197 on the fused path: the actor's forward, the loss and the backward down to the actor's gradients; returns the
+        tensor the loss value was stored in."""
+        if pb is not None and fused.USE_FUSED_LINEAR and self._fast_actor.layers[-1][0].out_features > 1:
+            # the actor's last layer writes into x_pi = (obs | .): no torch.cat, and its backward reads the action columns
+            # of the critic's input gradient in place
+            x_pi = self._fast_actor(rd.observations, xbuf=pb.x_pi.detach())
+        else:
+            x_pi = th.cat([rd.observations, self._fast_actor(rd.observations)], dim=1)
+        a_out, a_sum = self._loss_slot("actor")
+        blk.neg_mean_pass(x_pi, a_out, a_sum)  # -mean(Q1) (:194) through the (frozen) first Q network
+        return a_out
 
     def _target_actor_gathers(self, pb) -> bool:
         return self._fast_actor_target.gather_supported(pb.samples.next_observations)
