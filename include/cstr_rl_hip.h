@@ -652,6 +652,62 @@ int cstr_td3bc_actor_loss_f32(const float *q, const float *pi, int64_t ldpi, con
 int cstr_td3bc_act_bwd_rows_f32(const float *gy, int64_t ldgy, const float *y, int64_t ldy, const float *act, int64_t ldact, float coef,
                                 int act_kind, float *gz, int64_t m, int64_t n, cstr_stream_t stream);
 
+/* ---- CQL (csrc/cstr_cql.hip; core/cql/cql.py; Kumar et al. 2020, the importance-sampled CQL(H) term on SAC) -------------------------
+ * SAC's gradient step on a fixed dataset with a conservative term in the critic loss. Both entry points validate on the host without
+ * dereferencing anything and then only enqueue; f32; deterministic and bit-identical on relaunch (no float atomics). B = batch,
+ * N = n_actions (<= CSTR_CQL_MAX_ACTIONS, so that a state's 3N + 1 entries fit the 64 lanes of a wave), D = obs_dim, A = act_dim.
+ *
+ * cstr_cql_candidates_f32 (one launch, one thread per output row): from obs [B][ldo] and the actor's distribution parameters
+ * params_cur / params_next [B][ldp] = [mean | raw log_std] of s and s' it writes the critic-input rows
+ *   x [B * 3N][ldx], row b * 3N + j = [obs_b | a_bj]:  j in [0, N) uniform in [-1, 1)^A, [N, 2N) ~ pi(.|s_b), [2N, 3N) ~ pi(.|s'_b)
+ * (all three at the CURRENT state's observation) and, unless corr is NULL, the importance corrections
+ *   corr [B][3N] = log_unif (= A * logf(0.5f), evaluated by the caller) | log pi(a_bj | s_b) | log pi(a_bj | s'_b).
+ * A sampled action is sample_action_act(mean, raw, eps) and its log-prob sum_c gaussian_logp_term - sum_c tanh_correction_term
+ * (csrc/cstr_gaussian_device.h), both sums over the action dimension in ascending c: the bits of cstr_gaussian_head_fwd_f32 for the
+ * same (mean, raw, eps). Noise, exactly one source:
+ *   u_in [B][N][A] (uniforms in [-1, 1), copied) AND eps_in [B][2N][A] (rows [0, N) for pi(.|s), [N, 2N) for pi(.|s')), or
+ *   rng_ctl [CSTR_RNG_CTL_WORDS]: Philox4x32-10 keyed by rng_ctl[0] on CQL's own stream, counter words
+ *     (lo32(c), hi32(c), sub, 0xC0175E4A) with c = rng_ctl[1] + b * N + k for sample k of state b (a 64-bit sum: carries into word 1):
+ *     sub 0:     output word j -> column j of the uniform action, 2 * ((word >> 8) * 2^-24) - 1
+ *                (cstr_collect_episodes_f32's conversion);
+ *     sub 1 + p: Box-Muller(words 0, 1) -> eps of columns 2p, 2p + 1 of the pi(.|s) sample,
+ *                Box-Muller(words 2, 3) -> eps of columns 2p, 2p + 1 of the pi(.|s') sample (cstr_gaussian_head_fwd_f32's Box-Muller).
+ *   The last workgroup advances rng_ctl[1] by B * N (cstr_bcq_expand_f32's ticket), so a graph replay continues the stream.
+ * CSTR_E_BADARG: NULL obs / params / x, sizes <= 0, ldo < D, ldp < 2A, ldx < D + A, a pointer off a 4-byte boundary (rng_ctl: 8),
+ * both or neither noise source (u_in without eps_in counts as neither), an output overlapping an input or the other output.
+ * CSTR_E_UNSUPPORTED: A > CSTR_MAX_HEAD_ACT, N > CSTR_CQL_MAX_ACTIONS, more than CSTR_BCQ_MAX_ROWS output rows.
+ *
+ * cstr_cql_q_loss_f32 (one launch, one 1024-thread workgroup; everything between the critic forward and its backward):
+ *   q [2][q_stride]: each critic's output over the (1 + 3N) B rows [B data rows | B * 3N candidate rows in x's order].
+ *   t_b      = rew_b + (1 - done_b) * gamma * (min(q1_t_b, q2_t_b) - ent_coef[0] * next_logp_b)   (no entropy term when next_logp is
+ *              NULL): cstr_td_twin_q_loss_f32's statement and rounding points, target_out [B] (may be NULL) has its bits
+ *   c_i[b,j] = q_i[B + b 3N + j] - corr[b][j]   (corr NULL: no correction; with_data = 1 appends c_i[b,3N] = q_i[b]; corr NULL needs it)
+ *   lse_i[b] = temp * (log(sum_j exp(c_i[b,j] / temp - m)) + m),  m = max_j c_i[b,j] / temp  (an infinite m counts as 0; a NaN entry
+ *              makes that state's lse, its softmax shares and the loss NaN, as torch.logsumexp)
+ *   loss     = 0.5 * sum_i [ mean_b (q_i[b] - t_b)^2 + w * (mean_b lse_i[b] - mean_b q_i[b]) ]
+ *   gq [2][(1 + 3N) B] = d loss / d q:  data rows (0.5 * 2 / B) * (q_i[b] - t_b) - (0.5 w) / B (+ ((0.5 w) / B) * softmax share of the
+ *              appended entry when with_data), candidate rows ((0.5 w) / B) * softmax_j(c_i[b,:] / temp). No batch mean enters a
+ *              gradient; w == 0 leaves exact zeros on the candidate rows and cstr_td_twin_q_loss_f32's bits (scale 0.5) on the data rows.
+ *   loss_out (may be NULL) is stored, loss_sum (may be NULL) accumulated: the loss heads' convention.
+ *   aux [4] (may be NULL) = {0.5 sum_i mean_b (q_i - t)^2,  0.5 w sum_i (mean_b lse_i - mean_b q_i),  mean_b mean_i lse_i,
+ *              mean_b mean_i q_i[b]}: loss = aux[0] + aux[1] up to the final rounding.
+ * Reduction order: wave v of the sixteen takes the states v, v + 16, ... in ascending order, both critics side by side; a state's entries
+ * sit in lanes 0 .. 3N (maximum and sum through xor-shuffle butterflies, offsets 32, 16, ... 1); each wave adds (q_i - t)^2, lse_i and q_i
+ * of its states to float64 sums; the sixteen wave sums of a quantity combine in a binary tree (neighbours s0 + s1, s2 + s3, ..., then
+ * pairs of pairs, ...), and loss / aux are rounded to float32 once.
+ * CSTR_E_BADARG: NULL q / q1_t / q2_t / rew / done / gq, batch or n_actions <= 0, with_data not 0 / 1, corr NULL with with_data 0,
+ * next_logp without ent_coef, w negative or NaN, temp <= 0 or NaN, gamma NaN, q_stride < (1 + 3N) B, a pointer off a 4-byte
+ * boundary, an output overlapping an input or another output. CSTR_E_UNSUPPORTED: N > CSTR_CQL_MAX_ACTIONS, batch >
+ * CSTR_MAX_SAMPLE_BATCH. */
+#define CSTR_CQL_MAX_ACTIONS 21 /* 3 * 21 + 1 = 64 entries: one wave */
+int cstr_cql_candidates_f32(const float *obs, int64_t ldo, const float *params_cur, const float *params_next, int64_t ldp, int64_t batch,
+                            int n_actions, int obs_dim, int act_dim, const float *u_in, const float *eps_in, uint64_t *rng_ctl,
+                            float log_unif, float *x, int64_t ldx, float *corr, cstr_stream_t stream);
+int cstr_cql_q_loss_f32(const float *q, int64_t q_stride, const float *corr, int with_data, const float *q1_t, const float *q2_t,
+                        const float *next_logp, const float *rew, const float *done, const float *ent_coef, float gamma, float w,
+                        float temp, float *target_out, float *gq, float *loss_out, float *loss_sum, float *aux, int64_t batch,
+                        int n_actions, cstr_stream_t stream);
+
 /* cstr_linear_bwd_weight_sets_f32 with the OPTIMISER STEP inside (single-GPU training: no collective sits between a gradient and
  * its Adam step; torch.optim.Adam's arithmetic, core/sac/sac.py:266-268, :279-281): the workgroup that has reduced a 16 x 16 tile of
  * dW (and db) applies Adam to exactly those parameters -- parameter / moment quads requested at entry, one launch instead of two.

@@ -18,6 +18,9 @@ leaves every GEMM to PyTorch-ROCm (`torch.mm` -> rocBLAS) with the HIP epilogues
   * `squashed_gaussian([mean | log_std], eps)` = 1 launch forward, 1 launch backward (analytic);
   * TD3+BC (`PerLayerTwinCritic.td3bc_pass`): the actor loss with its batch-wide normaliser = 1 launch where TD3 launches -mean(Q1),
     the behaviour-cloning gradient inside the backward launch of the actor's last layer (`_LinearXbufFn`'s `bc`, `bc_tap`);
+  * CQL (`PerLayerTwinCritic.cql_step`): the twin critic's ONE forward and ONE backward on [B data rows | B * 3N candidate rows] with
+    the TD target, the Bellman term, the log-sum-exp and its softmax gradient as 1 launch between them; the candidates and their
+    importance corrections = 1 launch from the head outputs of the 2B-row actor pass (`action_log_prob_pair`'s `params_out`);
   * BCQ (`FastBcq`): the VAE latent (`_VaeLatentFn`) and the perturbation step (`_PerturbFn`) = 1 launch forward, 1 backward each,
     candidates expanded into the decoder / perturbation / critic inputs by one launch.
 
@@ -729,10 +732,11 @@ class FastSacActor:
                 and layers[1][0].out_features % 4 == 0 and len(q) in (0, 2) and self._hw.is_contiguous()
                 and all(lin.weight.grad is not None and lin.bias.grad is not None for lin, _ in layers))
 
-    def action_log_prob_pair(self, pb, gather=None):
+    def action_log_prob_pair(self, pb, gather=None, params_out=None):
         """(x_pi, log pi(a|obs)) with gradients and (x_next, log pi(a'|next_obs)) without, from ONE 2B-row pass (_ActorPairFn).
         `gather` = ReplayBuffer.take_predrawn(pb): the batch has not been gathered yet -- the pass's first layer reads the sampled
-        rows from the ring itself and writes `pb` for the launches behind it (hip_ops.linear_act_fwd_gather)."""
+        rows from the ring itself and writes `pb` for the launches behind it (hip_ops.linear_act_fwd_gather). `params_out` [2B, 2A]:
+        receives the head's [mean | raw log_std] rows, obs rows first (CQL's candidate sampling reads them)."""
         dist = self.actor.action_dist
         b, a = pb.x_pi.shape[0], self.act_dim
         eps2 = None
@@ -744,7 +748,8 @@ class FastSacActor:
         grads = (l1.weight.grad, l1.bias.grad, l2.weight.grad, l2.bias.grad, self._hwg, self._hbg)
         x2 = pb.x_pn[:, :pb.obs_dim]
         return _ActorPairFn.apply(x2, l1.weight, l1.bias, l2.weight, l2.bias, self._hw, self._hb, grads, act, eps2, self.rng_ctl,
-                                  pb.x_pi.detach(), pb.x_next.detach(), True, gather, l1.weight, l2.weight, self.mu.weight, self.log_std.weight)
+                                  pb.x_pi.detach(), pb.x_next.detach(), True, gather, params_out, l1.weight, l2.weight, self.mu.weight,
+                                  self.log_std.weight)
 
     def dist_params(self, obs: th.Tensor, train_params: bool = True) -> th.Tensor:
         """[B, 2A] = [mean | log_std_raw]"""
@@ -1108,7 +1113,10 @@ class _ActorPairFn(th.autograd.Function):
     of the two separate launches (counter = offset + row, obs rows first). Two hidden layers + the merged head only."""
 
     @staticmethod
-    def forward(ctx, x2, w1, b1, w2, b2, hw, hb, grads, act: int, eps2, rng_ctl, xbuf_pi, xbuf_next, train_params: bool, gather, *owners):
+    def forward(ctx, x2, w1, b1, w2, b2, hw, hb, grads, act: int, eps2, rng_ctl, xbuf_pi, xbuf_next, train_params: bool, gather, params_out,
+                *owners):
+        """`params_out` [2B, 2A] or None: the caller's buffer for the head's [mean | raw log_std] rows of obs and next_obs (CQL samples
+        its candidate actions from them: no second trunk pass)."""
         n2, a = x2.shape[0], hw.shape[0] // 2
         n = n2 // 2
         if gather is not None:  # the sampled rows come straight from the ring; x2 (a view of pb.x_pn) is written by this launch
@@ -1118,7 +1126,7 @@ class _ActorPairFn(th.autograd.Function):
         else:
             h1 = hip_ops.linear_act_fwd(x2, w1, b1, act)
         h2 = hip_ops.linear_act_fwd(h1, w2, b2, act)
-        params = th.empty(n2, 2 * a, dtype=h2.dtype, device=h2.device)
+        params = params_out if params_out is not None else th.empty(n2, 2 * a, dtype=h2.dtype, device=h2.device)
         logp = th.empty(n2, dtype=h2.dtype, device=h2.device)
         if eps2 is None:
             eps2 = th.empty(n2, a, dtype=h2.dtype, device=h2.device)
@@ -1155,7 +1163,7 @@ class _ActorPairFn(th.autograd.Function):
             _weight_grad(g_params, h2, hwg, hbg)
             _weight_grad(dz2, h1, w2g, b2g)
             _weight_grad(dz1, x, w1g, b1g)
-        return (None,) * (15 + ctx.n_owners)
+        return (None,) * (16 + ctx.n_owners)
 
 
 class _TwinPairFn(th.autograd.Function):
@@ -1353,6 +1361,7 @@ class PerLayerTwinCritic:
         self.critic, self.target, self.ensemble, self.loss_roots = critic, target, ensemble, loss_roots
         self.gq: Optional[th.Tensor] = None      # [max(G, 2), B, 1]: d(loss)/dQ of the loss heads (a loss root keeps its own in LDS)
         self.g_logp: Optional[th.Tensor] = None  # [B]: SAC's d(actor loss)/d(log pi)
+        self.gq_wide: Optional[th.Tensor] = None  # [2, (1 + 3N) B, 1]: d(loss)/dQ of CQL's wide critic pass (`cql_step`)
 
     def _scratch(self, q: th.Tensor, logp: bool = False):
         """The gradient buffers for the batch of `q` [B, 1], re-made when B changes (first made by an eager step, never inside a capture)."""
@@ -1414,6 +1423,29 @@ class PerLayerTwinCritic:
         gq = self._scratch(qs[0])
         hip_ops.twin_q_loss(qs[0], qs[1], target_q, scale, gq[0], gq[1], loss_out, loss_sum)
         backward_q(qs, gq)
+
+    def cql_step(self, x_wide: th.Tensor, corr, with_data: bool, x_next: th.Tensor, rd, gamma: float, w: float, temp: float, target_out,
+                 loss_out, loss_sum, aux, next_logp=None, ent_coef=None, after_loss=None) -> th.Tensor:
+        """CQL's critic step (core/cql/cql.py): the target critics on x_next, ONE forward of the twin critic on x_wide = [B data rows |
+        B * 3N candidate rows], cstr_cql_q_loss_f32 (TD target, Bellman term, T * logsumexp over a state's candidates, its softmax
+        gradient, aux), ONE backward (x_wide asks for no gradient, so nothing is computed below the first layer). The wide pass has a
+        gradient scratch of its own: `_scratch` is keyed by one row count and the actor pass behind this step has B rows, so sharing it
+        would re-make the buffer twice per step (and inside a capture). With a stacked critic output nothing persistent is allocated
+        after the first step; a critic without stacked views pays one th.stack of the Q tensors per step (caching allocator). Returns
+        the critics' output [2, (1 + 3N) B, 1] (detached)."""
+        with th.no_grad():
+            qs_t = self.target.forward_input(x_next, train_params=False)
+        qs = self.critic.forward_input(x_wide)
+        q_all = (qs.stacked if qs.stacked is not None else th.stack(list(qs))).detach()
+        if self.gq_wide is None or self.gq_wide.shape != q_all.shape:
+            self.gq_wide = th.empty_like(q_all)
+        gq = self.gq_wide
+        hip_ops.cql_q_loss(q_all, corr, with_data, qs_t[0], qs_t[1], next_logp, rd.rewards, rd.dones, ent_coef, gamma, w, temp, target_out, gq,
+                           loss_out, loss_sum, aux)
+        if after_loss is not None:
+            after_loss()
+        backward_q(qs, gq)
+        return q_all
 
     def neg_mean_pass(self, x_pi: th.Tensor, loss_out, loss_sum) -> None:
         """-mean(Q1(x_pi)) through the first (frozen) critic and its backward into whatever produced x_pi's action columns."""

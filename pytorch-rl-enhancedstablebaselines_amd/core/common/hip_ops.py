@@ -5,6 +5,7 @@ mis-shaped operand must never reach a hand-written kernel), passes raw device po
 current HIP stream, and raises on a non-zero return code. Nothing here computes on the CPU.
 """
 import ctypes as C
+import math
 from typing import Optional
 
 import torch as th
@@ -1367,6 +1368,67 @@ def td3bc_act_bwd_rows(gy, y, act, coef: float, act_kind: int, gz):
                                                C.c_int(act_kind), ptr(gz), C.c_int64(m), C.c_int64(n), stream_ptr()),
           "cstr_td3bc_act_bwd_rows_f32")
     return gz
+
+
+# ---- CQL (csrc/cstr_cql.hip) --------------------------------------------------------------------------------------------------------
+CQL_LOG_UNIF_1 = C.c_float(math.log(0.5)).value  # logf(0.5f): the uniform density's log per action dimension of the box (-1, 1)
+
+
+def cql_supported(n_actions: int, act_dim: int) -> bool:
+    return 0 < n_actions <= nv.CQL_MAX_ACTIONS and 0 < act_dim <= nv.MAX_HEAD_ACT
+
+
+def cql_log_unif(act_dim: int) -> float:
+    """A * logf(0.5f) in float32: the correction of a uniform candidate, evaluated once on the host"""
+    return C.c_float(float(act_dim) * CQL_LOG_UNIF_1).value  # two float32 values, their product rounded to float32 once
+
+
+def cql_candidates(obs, params_cur, params_next, n_actions: int, x, corr=None, u=None, eps=None, rng_ctl=None):
+    """x [B * 3N, D + A] row b * 3N + j = [obs_b | a_bj] (j < N uniform, < 2N ~ pi(.|s_b), < 3N ~ pi(.|s'_b)) and corr [B, 3N] =
+    A log 0.5 | log pi(a | s) | log pi(a | s') from params_* [B, 2A] = [mean | raw log_std] (cstr_cql_candidates_f32). Noise: u [B, N, A]
+    and eps [B, 2N, A] (read), or rng_ctl (drawn on CQL's Philox stream). obs / params_* / x may be row-strided."""
+    if (u is None) != (eps is None) or (u is None) == (rng_ctl is None):
+        raise ValueError("cql_candidates needs exactly one noise source: (u, eps) tensors or rng_ctl")
+    b, d = obs.shape
+    a = params_cur.shape[1] // 2
+    n = int(n_actions)
+    ldo = _rows(obs, "obs", b, d)
+    ldp = _rows(params_cur, "params_cur", b, 2 * a)
+    if _rows(params_next, "params_next", b, 2 * a) != ldp:
+        raise ValueError("params_cur and params_next must share their row stride")
+    ldx = _rows(x, "x", b * 3 * n, d + a)
+    _opt(corr, "corr", (b, 3 * n), th.float32), _opt(u, "u", (b, n, a), th.float32), _opt(eps, "eps", (b, 2 * n, a), th.float32)
+    _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    check(nv.lib().cstr_cql_candidates_f32(ptr(obs), C.c_int64(ldo), ptr(params_cur), ptr(params_next), C.c_int64(ldp), C.c_int64(b),
+                                           C.c_int(n), C.c_int(d), C.c_int(a), ptr(u), ptr(eps), ptr(rng_ctl), C.c_float(cql_log_unif(a)),
+                                           ptr(x), C.c_int64(ldx), ptr(corr), stream_ptr()), "cstr_cql_candidates_f32")
+    return x
+
+
+def cql_q_loss(q, corr, with_data: bool, q1_t, q2_t, next_logp, rew, done, ent_coef, gamma: float, w: float, temp: float, target_out, gq,
+               loss_out=None, loss_sum=None, aux=None):
+    """CQL's critic loss as a backward root (cstr_cql_q_loss_f32): q [2, (1 + 3N) B(, 1)] = both critics on [data rows | candidate
+    rows], corr [B, 3N] or None (then with_data); gq of q's shape = d loss / d q; aux [4] = {bellman, conservative (x w), mean lse,
+    mean Q(s, a)}."""
+    b = rew.numel()
+    if not (isinstance(q, th.Tensor) and q.is_cuda and q.dtype == th.float32 and q.is_contiguous() and q.shape[0] == 2 and q[0].numel() % b == 0):
+        raise ValueError("q: needs a contiguous float32 device tensor [2, (1 + 3N) B(, 1)]")
+    rows = q[0].numel()
+    n3 = rows // b - 1
+    if n3 <= 0 or n3 % 3:
+        raise ValueError(f"q: {rows} rows per critic are not (1 + 3N) * {b}")
+    _vec(gq, "gq", 2 * rows)
+    for t, nm in ((q1_t, "q1_t"), (q2_t, "q2_t"), (rew, "rew"), (done, "done")):
+        _vec(t, nm, b)
+    for t, nm, k in ((next_logp, "next_logp", b), (ent_coef, "ent_coef", 1), (target_out, "target_out", b), (loss_out, "loss_out", 1),
+                     (loss_sum, "loss_sum", 1), (aux, "aux", 4)):
+        if t is not None:
+            _vec(t, nm, k)
+    _opt(corr, "corr", (b, n3), th.float32)
+    check(nv.lib().cstr_cql_q_loss_f32(ptr(q), C.c_int64(rows), ptr(corr), C.c_int(int(bool(with_data))), ptr(q1_t), ptr(q2_t), ptr(next_logp),
+                                       ptr(rew), ptr(done), ptr(ent_coef), C.c_float(gamma), C.c_float(w), C.c_float(temp), ptr(target_out),
+                                       ptr(gq), ptr(loss_out), ptr(loss_sum), ptr(aux), C.c_int64(b), C.c_int(n3 // 3), stream_ptr()),
+          "cstr_cql_q_loss_f32")
 
 
 # ---- row-chain kernels (csrc/cstr_chain.hip, include/cstr_rl_hip.h "row-chain kernels") -------------------------------------------
