@@ -708,6 +708,45 @@ int cstr_cql_q_loss_f32(const float *q, int64_t q_stride, const float *corr, int
                         float temp, float *target_out, float *gq, float *loss_out, float *loss_sum, float *aux, int64_t batch,
                         int n_actions, cstr_stream_t stream);
 
+/* ---- IQL (csrc/cstr_iql.hip; core/iql/iql.py; Kostrikov, Nair & Levine 2021, implicit Q-learning) ---------------------------------
+ * cstr_iql_loss_f32 (one launch, one 256-thread workgroup): everything between the forward passes of an IQL gradient step and its
+ * three backward passes. It validates on the host without dereferencing anything and then only enqueues; f32; deterministic and
+ * bit-identical on relaunch (no float atomics). B = batch, A = act_dim, tau_e = expectile, M = exp_adv_max. Per row b:
+ *   u      = min(qt1_b, qt2_b) - v_b                                  (the target critics at (s, a), V(s)); adv_out [B]
+ *   value  : we = |tau_e - 1[u < 0]| (u == 0 and a NaN u take tau_e);  term we * u^2;  g_v[b] = -(2 we u) / B
+ *   critic : y = rew_b + (1 - done_b) * gamma * v_next_b;  gq_i[b] = (0.5 * 2 / B) * (q_i[b] - y);  target_out [B] = y.
+ *            This is cstr_td_twin_q_loss_f32's statement, rounding points and float32 reduction (csrc/cstr_td_device.h is the one
+ *            place that states them): fed v_next as both target values, no next_logp and scale 0.5, that launch's gq1, gq2,
+ *            target_out and loss have this launch's bits.
+ *   actor  : w = min(exp(beta * u), M), a constant of the actor step (an overflowing exp is clipped to M, a NaN stays a NaN);
+ *            params [B][ldp] = [mean | raw log_std], ls = clamp(raw, -20, 2), sd = exp(ls);  act [B][ldact] the dataset action;
+ *            g_j = atanh(clamp(act_j, -1 + eps32, 1 - eps32)) = 0.5 * (log1p(x) - log1p(-x)), eps32 = 2^-23;
+ *            logp = sum_j [-(g_j - mean_j)^2 / (2 sd_j^2) - log(sd_j) - 0.5 log(2 pi)] - sum_j log(1 - act_j^2 + 1e-6)
+ *            (csrc/cstr_gaussian_device.h's terms, two sums in ascending j; the correction takes the UNclamped action, so |act_j| > 1
+ *            gives NaN in that row's logp, as torch; it is not guarded); logp_out [B];
+ *            g_params [B][2A] (contiguous): mean columns -(w / B) * ((g_j - mean_j) / sd_j^2), raw log_std columns
+ *            -(w / B) * ((g_j - mean_j)^2 / sd_j^2 - 1) where -20 <= raw <= 2 (torch's clamp passes the gradient on the closed
+ *            interval), else 0 (a NaN raw included).
+ *   loss_out [3] (stored) / loss_sum [3] (accumulated) = {mean_b we u^2,  0.5 sum_i mean_b (q_i - y)^2,  mean_b -(w logp)}
+ *   aux [6] = {mean u, mean w, share of rows with exp(beta u) > M, mean logp, mean v, mean y}
+ * Optional, each group as a whole (NULL = not written): g_v; (gq1, gq2) together; g_params; loss_out; loss_sum; aux; target_out;
+ * adv_out; logp_out. Every input is required: the three losses and aux are always evaluated.
+ * v and v_next may be the two halves of one [2B] array (V's ONE forward on [s; s']).
+ * Reduction order: thread t of 256 sums rows t, t + 256, ... in ascending order; each partial goes through a 64-lane shuffle tree
+ * (offsets 32, 16, ... 1), the four wave sums combine as (s0 + s1) + (s2 + s3). The critic's two sums of (q_i - y)^2 are float32 (the
+ * twin TD loss head's bits); all others are float64 sums of float32 values (products of float32 factors formed in float64), each
+ * result rounded to float32 once.
+ * All vectors [B] contiguous; params / act rows on 4-byte boundaries with ldp >= 2A, ldact >= A floats.
+ * CSTR_E_BADARG: a NULL input, batch or act_dim <= 0, ldp < 2A, ldact < A, one of gq1 / gq2 without the other, a pointer off a
+ * 4-byte boundary, an output overlapping an input or another output, expectile outside (0, 1) or NaN, beta negative or NaN,
+ * exp_adv_max <= 0 or NaN. CSTR_E_UNSUPPORTED: batch > CSTR_IQL_MAX_BATCH, act_dim > CSTR_MAX_HEAD_ACT. */
+#define CSTR_IQL_MAX_BATCH CSTR_MAX_SAMPLE_BATCH /* 16384, as the other single-workgroup loss heads */
+int cstr_iql_loss_f32(const float *qt1, const float *qt2, const float *v, const float *v_next, const float *q1, const float *q2,
+                      const float *params, int64_t ldp, const float *act, int64_t ldact, const float *rew, const float *done, float gamma,
+                      float expectile, float beta, float exp_adv_max, float *g_v, float *gq1, float *gq2, float *g_params,
+                      float *loss_out, float *loss_sum, float *aux, float *target_out, float *adv_out, float *logp_out, int64_t batch,
+                      int act_dim, cstr_stream_t stream);
+
 /* cstr_linear_bwd_weight_sets_f32 with the OPTIMISER STEP inside (single-GPU training: no collective sits between a gradient and
  * its Adam step; torch.optim.Adam's arithmetic, core/sac/sac.py:266-268, :279-281): the workgroup that has reduced a 16 x 16 tile of
  * dW (and db) applies Adam to exactly those parameters -- parameter / moment quads requested at entry, one launch instead of two.

@@ -27,6 +27,7 @@ HER_MAX_BATCH, HER_MAX_ROWS, HER_MAX_ENVS, HER_GOAL_TAG = 1024, 8192, 1 << 24, 0
 COLLECT_TAG = 0xC011EC7D  # counter word 3 of cstr_collect_episodes_f32's exploration draw
 TD3BC_MAX_BATCH, TD3BC_MAX_ACT = 16384, 8  # CSTR_TD3BC_MAX_BATCH, CSTR_TD3BC_MAX_ACT of include/cstr_rl_hip.h
 CQL_MAX_ACTIONS, CQL_TAG = 21, 0xC0175E4A  # CSTR_CQL_MAX_ACTIONS; counter word 3 of cstr_cql_candidates_f32's draws
+IQL_MAX_BATCH = 16384  # CSTR_IQL_MAX_BATCH
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -53,6 +54,7 @@ SYMBOLS = (
     "cstr_collect_episodes_f32",
     "cstr_td3bc_actor_loss_f32", "cstr_td3bc_act_bwd_rows_f32",
     "cstr_cql_candidates_f32", "cstr_cql_q_loss_f32",
+    "cstr_iql_loss_f32",
 )
 
 

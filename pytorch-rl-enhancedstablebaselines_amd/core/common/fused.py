@@ -21,6 +21,8 @@ leaves every GEMM to PyTorch-ROCm (`torch.mm` -> rocBLAS) with the HIP epilogues
   * CQL (`PerLayerTwinCritic.cql_step`): the twin critic's ONE forward and ONE backward on [B data rows | B * 3N candidate rows] with
     the TD target, the Bellman term, the log-sum-exp and its softmax gradient as 1 launch between them; the candidates and their
     importance corrections = 1 launch from the head outputs of the 2B-row actor pass (`action_log_prob_pair`'s `params_out`);
+  * IQL (`FastValuePair`): the state-value network on the 2B rows [s; s'] in one gradient-free forward, its backward on the B rows of s;
+    the three losses between the step's forwards and backwards = 1 launch (hip_ops.iql_loss, core/iql/iql.py);
   * BCQ (`FastBcq`): the VAE latent (`_VaeLatentFn`) and the perturbation step (`_PerturbFn`) = 1 launch forward, 1 backward each,
     candidates expanded into the decoder / perturbation / critic inputs by one launch.
 
@@ -1493,6 +1495,64 @@ class PerLayerTwinCritic:
         """model.last_train_tensors of a debug_capture step."""
         return dict(target_q=target_q.clone(), current_q=[q.detach().clone() for q in qs], critic_loss=critic_loss.clone(),
                     actor_loss=None if actor_loss is None else actor_loss.clone(), **more)
+
+
+class FastValuePair:
+    """IQL's state-value network (core/iql/policies.py ValueNetwork: create_mlp(obs_dim, 1, net_arch), at least one hidden layer) on the
+    2B rows [s; s'] in ONE gradient-free forward, and its backward from d(loss)/dV(s) on the FIRST B rows only: V(s') enters the step
+    as a constant of the TD target, so nothing of its rows is differentiated. No autograd graph: the forward keeps its activations,
+    `backward` walks them (the hidden-head launch, then per layer the input gradient with the activation gradient of the layer below)
+    and leaves dW / db of all layers in the gradient arena through ONE launch (`deferred_weight_grads`)."""
+
+    def __init__(self, value_net):
+        self.mlp = FastMLP(value_net.v_net)
+        self._saved = None
+
+    @staticmethod
+    def supported(value_net) -> bool:
+        if not FastMLP.supported(value_net.v_net):
+            return False
+        layers = FastMLP(value_net.v_net).layers
+        return (len(layers) >= 2 and layers[-1][0].out_features == 1 and layers[-1][1] == ACT_NONE
+                and all(lin.weight.grad is not None and lin.bias.grad is not None for lin, _ in layers))
+
+    def forward(self, x2: th.Tensor) -> th.Tensor:
+        """V on x2 [2B, D] (rows may be strided) -> [2B, 1], no gradient"""
+        layers = self.mlp.layers
+        with th.no_grad():
+            acts, h = [x2], x2
+            for lin, act in layers[:-2]:
+                h = _linear_fwd(h, lin.weight, lin.bias, act)
+                acts.append(h)
+            (l1, act), (l2, _) = layers[-2:]
+            y = _hidden_gemm(h, l1.weight)
+            v = th.empty(y.shape[0], 1, dtype=y.dtype, device=y.device)
+            hip_ops.hidden_head_fwd_(y, l1.bias, act, l2.weight, l2.bias, v)  # y now holds act(z + b1)
+        self._saved = (acts, y)
+        return v
+
+    def backward(self, g_v: th.Tensor) -> None:
+        """parameter gradients from g_v [B] = d(loss)/dV of the first B rows of the last `forward`"""
+        layers = self.mlp.layers
+        acts, y = self._saved
+        b = g_v.numel()
+        (l1, act), (l2, _) = layers[-2:]
+        with th.no_grad(), deferred_weight_grads():
+            dz = th.empty(b, y.shape[1], dtype=y.dtype, device=y.device)
+            hip_ops.hidden_head_bwd(g_v.view(b, 1), y[:b], act, l2.weight, dz, l1.bias.grad, l2.weight.grad, l2.bias.grad)
+            self._wgrad(dz, acts[-1][:b], l1.weight.grad, None)  # its bias gradient came out of the head launch
+            for i in range(len(layers) - 3, -1, -1):
+                lin, act_i = layers[i]
+                dz = _input_grad(dz, layers[i + 1][0].weight, acts[i + 1][:b], (act_i, None))
+                self._wgrad(dz, acts[i][:b], lin.weight.grad, lin.bias.grad)
+
+    @staticmethod
+    def _wgrad(dz: th.Tensor, x: th.Tensor, wgrad: th.Tensor, bgrad: Optional[th.Tensor]) -> None:
+        if USE_FUSED_LINEAR:
+            return _weight_grad(dz, x, wgrad, bgrad)
+        th.mm(dz.t(), x, out=wgrad)
+        if bgrad is not None:
+            hip_ops.bias_act_bwd(dz, None, ACT_NONE, dz, bgrad)
 
 
 def twin_groups(q_networks) -> list:

@@ -1431,6 +1431,40 @@ def cql_q_loss(q, corr, with_data: bool, q1_t, q2_t, next_logp, rew, done, ent_c
           "cstr_cql_q_loss_f32")
 
 
+# ---- IQL (csrc/cstr_iql.hip) --------------------------------------------------------------------------------------------------------
+def iql_supported(batch: int, act_dim: int) -> bool:
+    return 0 < batch <= nv.IQL_MAX_BATCH and 0 < act_dim <= nv.MAX_HEAD_ACT
+
+
+def iql_loss(qt1, qt2, v, v_next, q1, q2, params, act, rew, done, gamma: float, expectile: float, beta: float, exp_adv_max: float,
+             g_v=None, gq1=None, gq2=None, g_params=None, loss_out=None, loss_sum=None, aux=None, target_out=None, adv_out=None,
+             logp_out=None):
+    """IQL's three losses as backward roots (cstr_iql_loss_f32): u = min(qt1, qt2) - v; g_v of the expectile value loss; gq1 / gq2 of the
+    critic loss against y = rew + (1 - done) gamma v_next (the twin TD loss head's bits); g_params [B, 2A] of the advantage-weighted
+    log-prob of the dataset action `act` [B, A] under params [B, 2A] = [mean | raw log_std]. loss_out / loss_sum [3] = {value, critic,
+    actor}; aux [6] = {mean u, mean w, clipped share, mean logp, mean v, mean y}; target_out / adv_out / logp_out [B]. params / act may be
+    column blocks of wider row-major matrices; v and v_next may be the halves of one [2B] tensor."""
+    b = rew.numel()
+    for t, nm in ((qt1, "qt1"), (qt2, "qt2"), (v, "v"), (v_next, "v_next"), (q1, "q1"), (q2, "q2"), (rew, "rew"), (done, "done")):
+        _vec(t, nm, b)
+    if not isinstance(act, th.Tensor) or act.dim() != 2 or act.shape[0] != b:
+        raise ValueError(f"act: needs a [{b}, A] matrix, got {tuple(act.shape) if isinstance(act, th.Tensor) else type(act)}")
+    a = act.shape[1]
+    ldact, ldp = _rows(act, "act", b, a), _rows(params, "params", b, 2 * a)
+    if (gq1 is None) != (gq2 is None):
+        raise ValueError("gq1 and gq2 are one group: both or neither")
+    for t, nm, k in ((g_v, "g_v", b), (gq1, "gq1", b), (gq2, "gq2", b), (g_params, "g_params", b * 2 * a), (loss_out, "loss_out", 3),
+                     (loss_sum, "loss_sum", 3), (aux, "aux", 6), (target_out, "target_out", b), (adv_out, "adv_out", b),
+                     (logp_out, "logp_out", b)):
+        if t is not None:
+            _vec(t, nm, k)
+    check(nv.lib().cstr_iql_loss_f32(ptr(qt1), ptr(qt2), ptr(v), ptr(v_next), ptr(q1), ptr(q2), ptr(params), C.c_int64(ldp), ptr(act),
+                                     C.c_int64(ldact), ptr(rew), ptr(done), C.c_float(gamma), C.c_float(expectile), C.c_float(beta),
+                                     C.c_float(exp_adv_max), ptr(g_v), ptr(gq1), ptr(gq2), ptr(g_params), ptr(loss_out), ptr(loss_sum),
+                                     ptr(aux), ptr(target_out), ptr(adv_out), ptr(logp_out), C.c_int64(b), C.c_int(a), stream_ptr()),
+          "cstr_iql_loss_f32")
+
+
 # ---- row-chain kernels (csrc/cstr_chain.hip, include/cstr_rl_hip.h "row-chain kernels") -------------------------------------------
 def chain_supported(h1: int, h2: int, batch: int) -> bool:
     """Widths multiples of 4; forward launches hold a 16 x (H1 + 4) panel and W1 staged as [H1][8 or 16] in 64 KB of LDS."""

@@ -23,6 +23,7 @@
 #include "cstr_rng_device.h"
 #include "cstr_adam_device.h"
 #include "cstr_policy_device.h"
+#include "cstr_td_device.h"
 
 namespace {
 
@@ -109,25 +110,7 @@ __global__ __launch_bounds__(WAVES * 64) void bias_act_bwd_kernel(const float *g
     }
 }
 
-// ---- block reduction helper ---------------------------------------------------------------------------
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float block_sum_256(float v, float *sm)
-{
-    v = wave_sum(v);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) sm[wave] = v;
-    __syncthreads();
-    const float r = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    __syncthreads();
-    return r;
-}
+// ---- block reduction helper: wave_sum / block_sum_256 are cstr_td_device.h's -----------------------------
 
 // ---- small-batch Linear + bias + activation forward on the f32 matrix cores ----------------------------------------
 // y[m][n] = act(sum_k x[m][k] * W[n][k] + b[n]) for the learners' shapes (M = 256..4096 rows, N, K <= a few hundred):
@@ -2040,14 +2023,13 @@ __global__ __launch_bounds__(256) void td_twin_q_loss_kernel(const float *__rest
     const bool with_alpha = ap.log_alpha != nullptr;
     const float la = with_alpha ? ap.log_alpha[0] : 0.0f;
     const float ec = with_alpha ? expf(la) : (ent_coef ? ent_coef[0] : 0.0f);
-    const float k = scale * 2.0f / (float)batch;
+    const float k = td_q_grad_scale(scale, batch);
     float a1 = 0.0f, a2 = 0.0f, aa = 0.0f;
     for (int b = threadIdx.x; b < batch; b += 256) {
-        float q = fminf(q1_t[b], q2_t[b]);
-        if (next_logp) q = q - ec * next_logp[b];
-        const float t = rew[b] + (1.0f - done[b]) * gamma * q;
+        float d1, d2;  // the row's arithmetic is cstr_td_device.h's: cstr_iql_loss_f32 shares it
+        const float t = td_twin_row(q1_t[b], q2_t[b], next_logp != nullptr, ec, next_logp ? next_logp[b] : 0.0f, rew[b], done[b], gamma,
+                                    q1[b], q2[b], d1, d2);
         if (target_out) target_out[b] = t;
-        const float d1 = q1[b] - t, d2 = q2[b] - t;
         gq1[b] = k * d1;
         gq2[b] = k * d2;
         a1 += d1 * d1;
@@ -2057,7 +2039,7 @@ __global__ __launch_bounds__(256) void td_twin_q_loss_kernel(const float *__rest
     const float s1 = block_sum_256(a1, sm), s2 = block_sum_256(a2, sm);
     const float mean = with_alpha ? block_sum_256(aa, sm) / (float)batch : 0.0f;
     if (threadIdx.x == 0) {
-        const float loss = scale * (s1 / (float)batch + s2 / (float)batch);
+        const float loss = td_twin_loss(scale, s1, s2, batch);
         if (loss_out) loss_out[0] = loss;
         if (loss_sum) loss_sum[0] += loss;
         if (with_alpha) {
