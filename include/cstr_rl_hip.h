@@ -747,6 +747,43 @@ int cstr_iql_loss_f32(const float *qt1, const float *qt2, const float *v, const 
                       float *loss_out, float *loss_sum, float *aux, float *target_out, float *adv_out, float *logp_out, int64_t batch,
                       int act_dim, cstr_stream_t stream);
 
+/* ---- TQC (csrc/cstr_tqc.hip; core/tqc/tqc.py; Kuznetsov et al. 2020, truncated quantile critics) ----------------------------------
+ * What lies between the critics' forward passes of a TQC gradient step and its backward passes. Both entry points validate on the
+ * host without dereferencing anything and then only enqueue; f32 in and out, float64 inside; deterministic and bit-identical on
+ * relaunch (no float atomics, no workgroup waiting for another). G = n_critics, Nq = n_quantiles, k = drop_per_net, B = batch,
+ * M = G * Nq atoms per state, n_keep = M - k * G, tau_i = (i + 0.5) / Nq. Atom tensors are [G][B][Nq] contiguous (the stacked critic
+ * output).
+ * cstr_tqc_supported: 1 <= G <= CSTR_MAX_ENS_CRITICS, Nq >= 1, M <= CSTR_TQC_MAX_ATOMS, 0 <= k < Nq.
+ * cstr_tqc_critic_loss_f32 (two launches: one workgroup per row, then one workgroup over the per-row sums in ws):
+ *   per row b: the M atoms of z_next are ranked, rank_m = #{j : z'_j < z'_m or (z'_j == z'_m and j < m)} with j, m = g * Nq + i; the
+ *   n_keep atoms of rank < n_keep are kept (exactly n_keep, whatever ties there are), and
+ *     y_rank = rew_b + (1 - done_b) * gamma * (z' - alpha * next_logp_b);   target_out [B][n_keep] = y, ascending in each row;
+ *   alpha = exp(log_alpha[0]) when the entropy-coefficient part rides along (its value BEFORE this step's update), else ent_coef[0].
+ *   For every atom z_m of the row and every y_j: delta = y_j - z_m, H = 0.5 delta^2 if |delta| <= 1 else |delta| - 0.5,
+ *     rho = |tau_i - 1[delta < 0]| * H;   loss = mean over (b, m, j) of rho;
+ *     gz[m] = -(1 / (B M n_keep)) * sum_j |tau_i - 1[delta < 0]| * clamp(delta, -1, 1)       (j ascending)
+ *   loss_out [1] (stored) / loss_sum [1] (accumulated); means_out [2] (stored) / means_sum [2] (accumulated) = {mean over (b, j) of y,
+ *   mean over (b, m) of z}. Every difference, Huber term and sum is float64 on the float32 inputs; each output is rounded to
+ *   float32 once. ws: double [3 * B] scratch (the per-row sums), 8-byte aligned. `alpha` (NULL or log_alpha NULL = absent): SAC's
+ *   entropy-coefficient part as in cstr_td_twin_q_loss_f32, here with a float64 mean and exp.
+ *   Reduction order: a row's lanes through a 64-lane shuffle tree (offsets 32 .. 1), wave sums in wave order; rows t, t + 256, ...
+ *   in ascending order on lane t of the finishing workgroup, the same tree.
+ *   Optional (NULL = not written): loss_out, loss_sum, target_out, means_out, means_sum, alpha.
+ *   CSTR_E_BADARG: a NULL required pointer, batch <= 0, G or Nq <= 0, k < 0 or k >= Nq, gamma negative or NaN, neither ent_coef nor
+ *   the alpha part, an incomplete alpha part, a pointer off a 4-byte (ws: 8-byte) boundary, an output overlapping an input or another
+ *   output. CSTR_E_UNSUPPORTED: not cstr_tqc_supported, batch > CSTR_MAX_SAMPLE_BATCH.
+ * cstr_tqc_actor_loss_f32 (one launch, one 256-thread workgroup): loss = mean_b(ent_coef * logp_b - mean_{g,i} z_pi[g][b][i]);
+ *   gz_pi [G][B][Nq] = -1 / (B M), g_logp [B] = ent_coef / B, z_pi_mean [B] (optional) the row means; loss_out / loss_sum [1] optional.
+ *   Lane t sums rows t, t + 256, ... (each row's atoms in (g, i) order), then the tree above. Errors as above. */
+#define CSTR_TQC_MAX_ATOMS 256
+int cstr_tqc_supported(int n_critics, int n_quantiles, int drop_per_net);
+int cstr_tqc_critic_loss_f32(const float *z, const float *z_next, const float *next_logp, const float *rew, const float *done,
+                             const float *ent_coef, double gamma, int n_critics, int n_quantiles, int drop_per_net, float *gz,
+                             float *loss_out, float *loss_sum, float *target_out, float *means_out, float *means_sum, double *ws,
+                             const cstr_alpha_part_t *alpha, int64_t batch, cstr_stream_t stream);
+int cstr_tqc_actor_loss_f32(const float *z_pi, const float *logp, const float *ent_coef, int n_critics, int n_quantiles, float *gz_pi,
+                            float *g_logp, float *loss_out, float *loss_sum, float *z_pi_mean, int64_t batch, cstr_stream_t stream);
+
 /* cstr_linear_bwd_weight_sets_f32 with the OPTIMISER STEP inside (single-GPU training: no collective sits between a gradient and
  * its Adam step; torch.optim.Adam's arithmetic, core/sac/sac.py:266-268, :279-281): the workgroup that has reduced a 16 x 16 tile of
  * dW (and db) applies Adam to exactly those parameters -- parameter / moment quads requested at entry, one launch instead of two.

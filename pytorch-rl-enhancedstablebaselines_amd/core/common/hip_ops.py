@@ -1465,6 +1465,68 @@ def iql_loss(qt1, qt2, v, v_next, q1, q2, params, act, rew, done, gamma: float, 
           "cstr_iql_loss_f32")
 
 
+# ---- TQC (csrc/cstr_tqc.hip) --------------------------------------------------------------------------------------------------------
+def tqc_supported(n_critics: int, n_quantiles: int, drop_per_net: int) -> bool:
+    """cstr_tqc_supported: 1 <= G <= MAX_ENS_CRITICS, G * Nq <= TQC_MAX_ATOMS, 0 <= k < Nq."""
+    return bool(nv.lib().cstr_tqc_supported(C.c_int(int(n_critics)), C.c_int(int(n_quantiles)), C.c_int(int(drop_per_net))))
+
+
+def _atoms(t, name):
+    if not (isinstance(t, th.Tensor) and t.is_cuda and t.dtype == th.float32 and t.dim() == 3 and t.is_contiguous()):
+        raise ValueError(f"{name}: needs a contiguous float32 device tensor [G, B, Nq]")
+    return tuple(t.shape)
+
+
+def tqc_critic_loss(z, z_next, next_logp, rew, done, ent_coef, gamma: float, drop_per_net: int, gz, ws, loss_out=None, loss_sum=None,
+                    target_out=None, means_out=None, means_sum=None, alpha=None):
+    """TQC's critic loss as a backward root (cstr_tqc_critic_loss_f32): z / z_next [G, B, Nq] = the critics' atoms at (s, a) / the target
+    critics' at (s', a'); per row the G * Nq - k * G smallest target atoms give y = rew + (1 - done) gamma (z' - alpha next_logp)
+    (target_out [B, n_keep], ascending), gz [G, B, Nq] = d(mean quantile-Huber loss)/dz. means_out / means_sum [2] = {mean y, mean z}.
+    ws: float64 [3 B] scratch. `alpha`: SAC's entropy-coefficient part (the dict of `td_twin_q_loss`); without it ent_coef [1]."""
+    g, b, nq = _atoms(z, "z")
+    if _atoms(z_next, "z_next") != (g, b, nq) or _atoms(gz, "gz") != (g, b, nq):
+        raise ValueError(f"z_next / gz: need z's shape {(g, b, nq)}")
+    k = int(drop_per_net)
+    for t, nm in ((next_logp, "next_logp"), (rew, "rew"), (done, "done")):
+        _vec(t, nm, b)
+    if not (isinstance(ws, th.Tensor) and ws.is_cuda and ws.dtype == th.float64 and ws.is_contiguous() and ws.numel() == 3 * b):
+        raise ValueError(f"ws: needs a contiguous float64 device tensor with {3 * b} elements")
+    for t, nm, n in ((loss_out, "loss_out", 1), (loss_sum, "loss_sum", 1), (means_out, "means_out", 2), (means_sum, "means_sum", 2),
+                     (target_out, "target_out", b * max(g * nq - k * g, 0))):
+        if t is not None:
+            _vec(t, nm, n)
+    part = None
+    if alpha is not None:
+        _vec(alpha["logp_pi"], "logp_pi", b)
+        for nm in ("log_alpha", "grad_out", "ent_coef_out"):
+            _vec(alpha[nm], nm, 1)
+        part = nv.AlphaPart(alpha["log_alpha"].data_ptr(), alpha["logp_pi"].data_ptr(), float(alpha["target_entropy"]),
+                            alpha["grad_out"].data_ptr(), alpha["ent_coef_out"].data_ptr(),
+                            *(None if alpha.get(key) is None else alpha[key].data_ptr() for key in ("loss_out", "loss_sum", "ent_coef_sum")))
+    elif ent_coef is None:
+        raise ValueError("the entropy term needs ent_coef or the alpha part")
+    else:
+        _vec(ent_coef, "ent_coef", 1)
+    check(nv.lib().cstr_tqc_critic_loss_f32(ptr(z), ptr(z_next), ptr(next_logp), ptr(rew), ptr(done), ptr(None if alpha is not None else ent_coef),
+                                            C.c_double(gamma), C.c_int(g), C.c_int(nq), C.c_int(k), ptr(gz), ptr(loss_out), ptr(loss_sum),
+                                            ptr(target_out), ptr(means_out), ptr(means_sum), ptr(ws), None if part is None else C.byref(part),
+                                            C.c_int64(b), stream_ptr()), "cstr_tqc_critic_loss_f32")
+
+
+def tqc_actor_loss(z_pi, logp, ent_coef, gz_pi, g_logp, loss_out=None, loss_sum=None, z_pi_mean=None):
+    """TQC's actor loss as a backward root (cstr_tqc_actor_loss_f32): loss = mean_b(ent_coef * logp - mean over (g, i) of z_pi [G, B, Nq]);
+    gz_pi [G, B, Nq] = -1 / (B G Nq), g_logp [B] = ent_coef / B, z_pi_mean [B] the row means."""
+    g, b, nq = _atoms(z_pi, "z_pi")
+    if _atoms(gz_pi, "gz_pi") != (g, b, nq):
+        raise ValueError(f"gz_pi: needs z_pi's shape {(g, b, nq)}")
+    _vec(logp, "logp", b), _vec(g_logp, "g_logp", b), _vec(ent_coef, "ent_coef", 1)
+    for t, nm, n in ((loss_out, "loss_out", 1), (loss_sum, "loss_sum", 1), (z_pi_mean, "z_pi_mean", b)):
+        if t is not None:
+            _vec(t, nm, n)
+    check(nv.lib().cstr_tqc_actor_loss_f32(ptr(z_pi), ptr(logp), ptr(ent_coef), C.c_int(g), C.c_int(nq), ptr(gz_pi), ptr(g_logp), ptr(loss_out),
+                                           ptr(loss_sum), ptr(z_pi_mean), C.c_int64(b), stream_ptr()), "cstr_tqc_actor_loss_f32")
+
+
 # ---- row-chain kernels (csrc/cstr_chain.hip, include/cstr_rl_hip.h "row-chain kernels") -------------------------------------------
 def chain_supported(h1: int, h2: int, batch: int) -> bool:
     """Widths multiples of 4; forward launches hold a 16 x (H1 + 4) panel and W1 staged as [H1][8 or 16] in 64 KB of LDS."""
