@@ -2847,6 +2847,17 @@ extern "C" int cstr_linear_bwd_input_f32(const float *gz, const float *w, const 
     return (int)hipGetLastError();
 }
 
+// The weight-gradient tile reduces over the ROWS, in whole batches of 16 * WAVES * UNROLL of them: its buffer loads form 32-bit byte
+// offsets for rows up to m + 206 (taken as m + 272 below), and count on the descriptor's range check to read the rows past the matrix
+// as zeros. A row stride of millions of floats under a short matrix (a column block of a very wide one) let such an offset pass
+// 2^32 and wrap back INTO the descriptor's range: the row then read whatever lies between the real rows, and 0 * NaN from there
+// reached every dW of the tile.
+// Offsets that stay below 2^31 neither wrap nor overflow the int they are computed in.
+static bool wgrad_offsets_fit(const int64_t m, const int64_t n, const int64_t ldx, const int64_t k)
+{
+    return (m + 272) * ldx + k < (1 << 29) && (m + 272) * n + n < (1 << 29);
+}
+
 extern "C" int cstr_linear_bwd_weight_f32(const float *dz, const float *x, int64_t x_group_stride, int64_t ldx, float *dw, float *db,
                                           int64_t groups, int64_t m, int64_t n, int64_t k, cstr_stream_t stream)
 {
@@ -2854,7 +2865,8 @@ extern "C" int cstr_linear_bwd_weight_f32(const float *dz, const float *x, int64
     if (m > 0x7fffff || n > 0x7fffff || k > 0x7fffff || groups > 65535 || (n + 15) / 16 > 65535) return CSTR_E_UNSUPPORTED;
     const dim3 grid((unsigned)((k + 15) / 16), (unsigned)((n + 15) / 16), (unsigned)groups);
     hipStream_t s = (hipStream_t)stream;
-    const bool buf = m * n < (1 << 28) && m * ldx < (1 << 28);  // buffer descriptors with 32-bit byte offsets: below 1 GiB
+    // buffer descriptors with 32-bit byte offsets: below 1 GiB, and no offset of a row past the matrix beyond 2^31
+    const bool buf = m * n < (1 << 28) && m * ldx < (1 << 28) && wgrad_offsets_fit(m, n, ldx, k);
 #define LBW(W, B) linear_bwd_weight_kernel<W, B><<<grid, 64 * W, 0, s>>>(dz, x, x_group_stride, (int)ldx, dw, db, (int)m, (int)n, (int)k)
     if (m > 32) { if (buf) LBW(4, true); else LBW(4, false); }
     else { if (buf) LBW(1, true); else LBW(1, false); }
@@ -2880,7 +2892,8 @@ extern "C" int cstr_linear_bwd_weight_sets_f32(const cstr_wgrad_set_t *sets, int
     const dim3 grid((unsigned)kt, (unsigned)nt, (unsigned)n_sets);
     hipStream_t s = (hipStream_t)stream;
     bool buf = true;  // operands through buffer descriptors with 32-bit byte offsets: every matrix below 1 GiB
-    for (int i = 0; i < n_sets; ++i) buf = buf && sets[i].m * sets[i].n < (1 << 28) && sets[i].m * sets[i].ldx < (1 << 28);
+    for (int i = 0; i < n_sets; ++i)
+        buf = buf && sets[i].m * sets[i].n < (1 << 28) && sets[i].m * sets[i].ldx < (1 << 28) && wgrad_offsets_fit(sets[i].m, sets[i].n, sets[i].ldx, sets[i].k);
     if (m_min > 32) { if (buf) linear_bwd_weight_sets_kernel<4, true><<<grid, 256, 0, s>>>(t); else linear_bwd_weight_sets_kernel<4, false><<<grid, 256, 0, s>>>(t); }
     else { if (buf) linear_bwd_weight_sets_kernel<1, true><<<grid, 64, 0, s>>>(t); else linear_bwd_weight_sets_kernel<1, false><<<grid, 64, 0, s>>>(t); }
     return (int)hipGetLastError();
