@@ -1176,6 +1176,48 @@ int cstr_dqn_loss_f32(const float *q, int64_t ldq, const float *next_q, int64_t 
                       const float *done, float gamma, int64_t batch, int n_actions, int levels, float *g_q, float *loss_out,
                       float *loss_sum, float *cur_q_out, float *target_out, uint64_t *workspace, cstr_stream_t stream);
 
+/* ---- QR-DQN on the discrete valve face (csrc/cstr_qrdqn.hip; core/qrdqn/qrdqn.py; Dabney et al. 2018, quantile-regression DQN) -------
+ * What QR-DQN adds to DQN's launches: the folded head its action selection runs on, and everything between the two forward passes of
+ * a gradient step and loss.backward(). Both entry points validate on the host without dereferencing anything and then only enqueue;
+ * f32 in and out, float64 inside; deterministic and bit-identical on relaunch (no float atomics, no workgroup waiting for another).
+ * The face is the DQN block's: M = n_actions = levels * levels, 2 <= levels <= CSTR_DQN_MAX_LEVELS. Nq = n_quantiles, B = batch,
+ * tau_i = (i + 0.5) / Nq. ATOM LAYOUT: a row holds Nq * M floats, atom i of action a at i * M + a (`quantiles.view(-1, Nq, M)`, what
+ * the network's last Linear layer leaves).
+ * cstr_qrdqn_supported: the DQN face check and 1 <= Nq <= CSTR_QRDQN_MAX_QUANTILES.
+ * cstr_qrdqn_fold_head_f32 (one launch): the mean over the atoms is linear, so greedy action selection needs only the FOLDED last
+ *   layer: w_mean[a][k] = (sum_i w[i * M + a][k]) / Nq, b_mean[a] = (sum_i bias[i * M + a]) / Nq; w [Nq * M][H] and w_mean [M][H]
+ *   contiguous. Each sum runs over i ascending in float64, is divided by Nq and rounded to float32 once. One lane per output element,
+ *   consecutive lanes on consecutive k: each of a wave's Nq loads is one contiguous 256-byte run; eight loads are in flight per lane.
+ *   The folded layer feeds cstr_linear_act_fwd_f32 and cstr_dqn_act_f32 unchanged: there is no act kernel over full atom rows.
+ *   No cap on Nq. CSTR_E_BADARG: a NULL pointer, n_actions, Nq or H <= 0, a pointer off a 4-byte boundary, an output overlapping an
+ *   input or the other output. CSTR_E_UNSUPPORTED: more than 2^30 output elements.
+ * cstr_qrdqn_loss_f32 (two launches: one workgroup per row, then one workgroup over the per-row sums in ws). z [B][ldz] the online
+ *   network's atoms at s, z_next [B][ldn] the target network's at s', ldz, ldn >= Nq * M; valve [B][2] the stored valve pair. Per row b:
+ *     S_a = sum_i z_next[b][i][a] (i ascending, float64);  a* = the first maximum of S (a NaN counts as the greatest value, the first
+ *     one wins: cstr_dqn_act_f32's convention);  y_j = reward_b + (1 - done_b) * gamma * z_next[b][j][a*]           j = 0 .. Nq - 1
+ *     a = level(valve[b][0]) * levels + level(valve[b][1]) (the DQN block's inverse);  z_i = z[b][i][a];  delta = y_j - z_i,
+ *     H = 0.5 delta^2 if |delta| <= 1 else |delta| - 0.5,  rho = |tau_i - 1[delta < 0]| * H
+ *     gz[b][i][a] = -(1 / (B Nq)) * sum_j |tau_i - 1[delta < 0]| * clamp(delta, -1, 1)   (j ascending); every other entry of the
+ *     row's Nq * M is stored as 0. gz has z's shape and row stride.
+ *   loss = (sum over (b, i, j) of rho) / (B Nq): the sum over the current quantile, the mean over batch and target quantile
+ *   (`quantile_huber_loss(current, target, sum_over_quantiles=True)`). loss_out [1] (stored) / loss_sum [1] (+= loss, one float32
+ *   addition). cur_out [B][Nq] = z_i, target_out [B][Nq] = y_j, next_index_out int64 [B] = a*. Every difference, Huber term and sum is
+ *   float64 on the float32 inputs; each output is rounded to float32 once. ws: double [B] scratch (the per-row sums), 8-byte aligned.
+ *   Reduction order: a row's lanes through a 64-lane shuffle tree (offsets 32 .. 1), wave sums in wave order; rows t, t + 256, ...
+ *   in ascending order on lane t of the finishing workgroup, the same tree (the TQC block's).
+ *   Optional (NULL = not written): loss_out, loss_sum, cur_out, target_out, next_index_out.
+ *   CSTR_E_BADARG: a NULL required pointer, batch, n_actions, levels or Nq <= 0, ldz or ldn < Nq * M, gamma negative or NaN, a pointer
+ *   off a 4-byte (valve, next_index_out, ws: 8-byte) boundary, an output overlapping an input or another output.
+ *   CSTR_E_UNSUPPORTED: not cstr_qrdqn_supported, batch > CSTR_MAX_SAMPLE_BATCH. */
+#define CSTR_QRDQN_MAX_QUANTILES 256
+int cstr_qrdqn_supported(int n_actions, int levels, int n_quantiles);
+int cstr_qrdqn_fold_head_f32(const float *w, const float *bias, int n_actions, int n_quantiles, int64_t H, float *w_mean, float *b_mean,
+                             cstr_stream_t stream);
+int cstr_qrdqn_loss_f32(const float *z, int64_t ldz, const float *z_next, int64_t ldn, const float *valve, const float *reward,
+                        const float *done, double gamma, int64_t batch, int n_actions, int levels, int n_quantiles, float *gz,
+                        float *loss_out, float *loss_sum, float *cur_out, float *target_out, int64_t *next_index_out, double *ws,
+                        cstr_stream_t stream);
+
 /* ---- Categorical head of PPO / A2C on the discrete valve face (core/common/distributions.py:263-311, core/ppo/ppo.py:213-264,
  * core/a2c/a2c.py:150-171) ---------------------------------------------------------------------------------------------------------
  * Same conventions as the PPO block: f32 data, host-side validation (NULL, non-positive sizes, misaligned or overlapping rows ->

@@ -29,6 +29,7 @@ TD3BC_MAX_BATCH, TD3BC_MAX_ACT = 16384, 8  # CSTR_TD3BC_MAX_BATCH, CSTR_TD3BC_MA
 CQL_MAX_ACTIONS, CQL_TAG = 21, 0xC0175E4A  # CSTR_CQL_MAX_ACTIONS; counter word 3 of cstr_cql_candidates_f32's draws
 IQL_MAX_BATCH = 16384  # CSTR_IQL_MAX_BATCH
 TQC_MAX_ATOMS = 256  # CSTR_TQC_MAX_ATOMS
+QRDQN_MAX_QUANTILES = 256  # CSTR_QRDQN_MAX_QUANTILES
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -57,6 +58,7 @@ SYMBOLS = (
     "cstr_cql_candidates_f32", "cstr_cql_q_loss_f32",
     "cstr_iql_loss_f32",
     "cstr_tqc_supported", "cstr_tqc_critic_loss_f32", "cstr_tqc_actor_loss_f32",
+    "cstr_qrdqn_supported", "cstr_qrdqn_fold_head_f32", "cstr_qrdqn_loss_f32",
 )
 
 

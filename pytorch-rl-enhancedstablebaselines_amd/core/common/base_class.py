@@ -387,6 +387,7 @@ class BaseAlgorithm:
         if "train_freq" in data and isinstance(data["train_freq"], list):
             ctor["train_freq"] = (int(data["train_freq"][0]), str(data["train_freq"][1]))
         ctor.update(kwargs)
+        cls._check_load_arguments(data, ctor)
         model = cls._construct_for_load(env, device, ctor)
         model.set_parameters(params, exact_match=True)
         for name, value in (variables or {}).items():
@@ -404,6 +405,11 @@ class BaseAlgorithm:
     @classmethod
     def _check_archive(cls, data: dict, env) -> None:
         """Hook of load(): refuse an archive that does not fit `env` before anything is built."""
+
+    @classmethod
+    def _check_load_arguments(cls, data: dict, ctor: dict) -> None:
+        """Hook of load(): refuse constructor arguments (the archive's, overridden by load()'s own keywords) that do not fit what the
+        archive's parameters were written for, before anything is built."""
 
     def _restore_extra(self, data: dict) -> None:
         """Hook of load(): the class's own counters out of the archive's `data`."""

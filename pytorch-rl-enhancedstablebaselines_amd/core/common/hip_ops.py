@@ -1986,6 +1986,54 @@ def dqn_loss(q, next_q, valve, reward, done, gamma: float, levels: int, g_q, los
                                      ptr(target_out), ptr(workspace), stream_ptr()), "cstr_dqn_loss_f32")
 
 
+# ---- QR-DQN on the discrete valve face: folded head, greedy target + gathers + quantile-Huber loss (csrc/cstr_qrdqn.hip) ------------
+def qrdqn_supported(n_actions: int, levels: int, n_quantiles: int) -> bool:
+    """cstr_qrdqn_supported: DQN's face and 1 <= n_quantiles <= QRDQN_MAX_QUANTILES."""
+    return bool(nv.lib().cstr_qrdqn_supported(C.c_int(int(n_actions)), C.c_int(int(levels)), C.c_int(int(n_quantiles))))
+
+
+def qrdqn_fold_head(weight, bias, n_actions: int, w_mean, b_mean):
+    """The quantile network's last layer folded over its atoms (cstr_qrdqn_fold_head_f32): weight [Nq * M, H], bias [Nq * M], row
+    i * M + a = atom i of action a; w_mean [M, H] = mean_i weight[i * M + a], b_mean [M] = mean_i bias[i * M + a] (float64 sums, i
+    ascending). The mean of the atoms is the folded layer applied to the same hidden activations."""
+    m = int(n_actions)
+    if not (isinstance(weight, th.Tensor) and weight.dim() == 2 and m >= 1 and weight.shape[0] >= m and weight.shape[0] % m == 0):
+        raise ValueError(f"weight: needs a [n_quantiles * {m}, H] matrix")
+    rows, h = weight.shape
+    _chk(weight, "weight", (rows, h), th.float32), _chk(bias, "bias", (rows,), th.float32)
+    _chk(w_mean, "w_mean", (m, h), th.float32), _chk(b_mean, "b_mean", (m,), th.float32)
+    check(nv.lib().cstr_qrdqn_fold_head_f32(ptr(weight), ptr(bias), C.c_int(m), C.c_int(rows // m), C.c_int64(h), ptr(w_mean), ptr(b_mean),
+                                            stream_ptr()), "cstr_qrdqn_fold_head_f32")
+
+
+def qrdqn_loss(z, z_next, valve, reward, done, gamma: float, levels: int, n_quantiles: int, gz, ws, loss_out=None, loss_sum=None, cur_out=None,
+               target_out=None, next_index_out=None):
+    """QR-DQN's loss as a backward root (cstr_qrdqn_loss_f32): z / z_next [B, Nq * M] (rows may be strided) = the online network's atoms
+    at s / the target network's at s', atom i of action a at i * M + a. Greedy a* over the atom means of z_next, y_j = reward +
+    (1 - done) gamma z_next[b, j, a*] (target_out [B, Nq]), the taken action's atoms (cur_out [B, Nq]) from the stored valve pair,
+    loss_out = the pairwise quantile-Huber loss summed over the current quantile and averaged over batch and target quantile, gz =
+    d loss / d z (z's shape and row stride, zeros off the taken action). next_index_out int64 [B] = a*. ws: float64 [B] scratch."""
+    b, nm = z.shape
+    nq, k = int(n_quantiles), int(levels)
+    if nq < 1 or nm != nq * k * k:
+        raise ValueError(f"z: {nm} columns are not n_quantiles * levels^2 = {nq} * {k * k}")
+    ldz = _rows(z, "z", b, nm)
+    ldn = _rows(z_next, "z_next", b, nm)
+    if _rows(gz, "gz", b, nm) != ldz:
+        raise ValueError("gz must have z's row stride")
+    _chk(valve, "valve", (b, 2), th.float32)
+    for t, nm_ in ((reward, "reward"), (done, "done")):
+        _vec(t, nm_, b)
+    _chk(ws, "ws", (b,), th.float64)
+    for t, nm_, n in ((loss_out, "loss_out", 1), (loss_sum, "loss_sum", 1), (cur_out, "cur_out", b * nq), (target_out, "target_out", b * nq)):
+        if t is not None:
+            _vec(t, nm_, n)
+    _opt(next_index_out, "next_index_out", (b,), th.int64)
+    check(nv.lib().cstr_qrdqn_loss_f32(ptr(z), C.c_int64(ldz), ptr(z_next), C.c_int64(ldn), ptr(valve), ptr(reward), ptr(done), C.c_double(gamma),
+                                       C.c_int64(b), C.c_int(k * k), C.c_int(k), C.c_int(nq), ptr(gz), ptr(loss_out), ptr(loss_sum), ptr(cur_out),
+                                       ptr(target_out), ptr(next_index_out), ptr(ws), stream_ptr()), "cstr_qrdqn_loss_f32")
+
+
 # ---- Categorical head of PPO / A2C on the discrete valve face (csrc/cstr_categorical.hip) -------------------------------------------
 def categorical_supported(obs_dim: int, n_actions: int, levels: int) -> bool:
     return obs_dim in (4, 8) and dqn_supported(n_actions, levels)

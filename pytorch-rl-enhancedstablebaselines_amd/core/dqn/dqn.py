@@ -93,7 +93,6 @@ class DQN(OffPolicyAlgorithm):
                                                           n_envs=self.n_envs, optimize_memory_usage=self.optimize_memory_usage,
                                                           **self.replay_buffer_kwargs)
         super()._setup_model()
-        self.q_net, self.q_net_target = self.policy.q_net, self.policy.q_net_target  # _create_aliases (:164-166)
         self.exploration_schedule = get_linear_fn(self.exploration_initial_eps, self.exploration_final_eps, self.exploration_fraction)
         if self.n_envs > 1 and self.n_envs > self.target_update_interval:
             warnings.warn("The number of environments used is greater than the target network "
@@ -103,10 +102,7 @@ class DQN(OffPolicyAlgorithm):
         dev, n = self.device, self.n_envs
         from core.common.arena import FlatAdam
 
-        if not (fused.FastMLP.supported(self.q_net.q_net) and hip_ops.dqn_supported(int(self.action_space.n), self.levels)):
-            raise NotImplementedError("DQN: the Q network must be Linear (+ ReLU / Tanh) layers over a valve face of 2..16 levels")
-        self._fast_q = fused.FastMLP(self.q_net.q_net)
-        self._fast_q_target = fused.FastMLP(self.q_net_target.q_net)
+        self._setup_networks()
         self.fused_learner = isinstance(self.policy.optimizer, FlatAdam)
         self.policy.greedy_index = self._greedy_index
         z = lambda: th.zeros(1, dtype=th.float32, device=dev)  # noqa: E731
@@ -122,6 +118,14 @@ class DQN(OffPolicyAlgorithm):
         self._predict_eps = th.zeros(1, dtype=th.float64, device=dev)
         lo, hi = env.valve_space.low, env.valve_space.high
         self._valve_low, self._valve_high = [float(v) for v in lo], [float(v) for v in hi]
+
+    def _setup_networks(self) -> None:
+        """the policy's two networks under the reference's names (_create_aliases, :164-166) and as per-layer kernel passes"""
+        self.q_net, self.q_net_target = self.policy.q_net, self.policy.q_net_target
+        if not (fused.FastMLP.supported(self.q_net.q_net) and hip_ops.dqn_supported(int(self.action_space.n), self.levels)):
+            raise NotImplementedError("DQN: the Q network must be Linear (+ ReLU / Tanh) layers over a valve face of 2..16 levels")
+        self._fast_q = fused.FastMLP(self.q_net.q_net)
+        self._fast_q_target = fused.FastMLP(self.q_net_target.q_net)
 
     def _reseed_device_rng(self, seed: int) -> None:
         super()._reseed_device_rng(seed)
@@ -272,7 +276,12 @@ class DQN(OffPolicyAlgorithm):
                 if self.debug_capture:
                     self.train_capture.append(dict(current_q=cur.detach().reshape(-1).clone(), target_q=target.reshape(-1).clone(),
                                                    loss=loss.detach().reshape(1).clone(), grad_norm=self._grad_norm.clone(),
-                                                   batch_inds=None if bi is None else bi.clone(), env_indices=None if ei is None else ei.clone()))
+                                                   batch_inds=None if bi is None else bi.clone(), env_indices=None if ei is None else ei.clone(),
+                                                   **self._capture_extra()))
+
+    def _capture_extra(self) -> dict:
+        """what a subclass's gradient step adds to a `train_capture` entry"""
+        return {}
 
     def _gradient_step_fused(self, rd):
         """:195-220 on the kernel path"""

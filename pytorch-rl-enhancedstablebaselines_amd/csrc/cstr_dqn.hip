@@ -26,13 +26,6 @@ namespace {
 
 constexpr uint32_t DQN_STREAM_TAG = 0xD09A11C7u;  // counter word 3: never shares counters with the other heads' streams
 
-// its inverse on a stored valve value: rint((v + 1) (K - 1) / 2), clamped into [0, K - 1] (a NaN gives 0)
-__device__ __forceinline__ int level_of(const float v, const int K)
-{
-    const float x = ((v + 1.0f) * (float)(K - 1)) / 2.0f;
-    return (int)rintf(fminf(fmaxf(x, 0.0f), (float)(K - 1)));
-}
-
 // first maximum of a row; a NaN is the greatest value (torch.argmax / torch.max)
 __device__ __forceinline__ int row_argmax(const float *__restrict__ row, const int M, float &best)
 {

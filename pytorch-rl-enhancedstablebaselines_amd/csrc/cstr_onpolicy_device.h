@@ -1,5 +1,5 @@
-// cstr_onpolicy_device.h -- what the on-policy kernels share (cstr_ppo.hip, cstr_a2c.hip, cstr_dqn.hip, cstr_categorical.hip,
-// cstr_multicategorical.hip; internal, not part of the ABI):
+// cstr_onpolicy_device.h -- what the on-policy kernels share (cstr_ppo.hip, cstr_a2c.hip, cstr_dqn.hip, cstr_qrdqn.hip,
+// cstr_categorical.hip, cstr_multicategorical.hip; internal, not part of the ABI):
 //   * row loads and stores, the diagonal Gaussian's log-prob, the discrete faces' valve values;
 //   * the loss core between a head's log-prob and the logged scalars: advantage_stats, policy_term, value_term, reduce_partials,
 //     write_scalars, and the one loss kernel of the diagonal Gaussian head (PPO and A2C are its two instantiations);
@@ -63,6 +63,13 @@ template <int A> __device__ __forceinline__ float diag_log_prob(const float (&ac
 
 // v(q) of the discrete valve face (core/common/vec_env/cstr_vec_env.py): f32(-1) + f32(2 q) / f32(K - 1), in that order
 __device__ __forceinline__ float valve_of(const int q, const int K) { return -1.0f + (float)(2 * q) / (float)(K - 1); }
+
+// its inverse on a stored valve value: rint((v + 1) (K - 1) / 2), clamped into [0, K - 1] (a NaN gives 0)
+__device__ __forceinline__ int level_of(const float v, const int K)
+{
+    const float x = ((v + 1.0f) * (float)(K - 1)) / 2.0f;
+    return (int)rintf(fminf(fmaxf(x, 0.0f), (float)(K - 1)));
+}
 
 // sum of v over the workgroup's 256 threads in a fixed tree; every thread gets the result
 __device__ __forceinline__ double block_sum_f64(double v, double *red)
