@@ -22,7 +22,7 @@
 // teacher-forced through action_in.
 // Batch reductions: lane 0 of every wave sums its rows in f64; from there the convention at the top of cstr_onpolicy_device.h.
 // Entropy: H = -sum_j p_j * max(logp_j, -FLT_MAX) (torch clamps the logits to the least finite value, so p = 0 contributes 0).
-// NaN: fminf / fmaxf in the clips DROP a NaN operand where torch.min / clamp propagate it (as in cstr_ppo.hip).
+// NaN: the loss launch propagates a NaN log-prob, advantage or value as torch.min / clamp do (stated in cstr_ppo.hip's header).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>

@@ -17,7 +17,7 @@
 // Uniforms are READ when given and DRAWN otherwise: Philox4x32-10 keyed by rng_ctl[0], counter (rng_ctl[1] + row, 0, tag), words 0
 // and 1 of the one block as (word >> 8) * 2^-24 for valves 0 and 1; the last workgroup advances rng_ctl[1] by the row count.
 // Batch reductions: lane 0 of every wave sums its rows in f64; from there the convention at the top of cstr_onpolicy_device.h.
-// NaN: fminf / fmaxf in the clips DROP a NaN operand where torch.min / clamp propagate it (as in cstr_ppo.hip).
+// NaN: the loss launch propagates a NaN log-prob, advantage or value as torch.min / clamp do (stated in cstr_ppo.hip's header).
 #include <hip/hip_runtime.h>
 #include <float.h>
 #include <math.h>

@@ -128,12 +128,15 @@ __device__ __forceinline__ PolicyTerm policy_term(const bool ppo, const float lo
         const float lr = logp - old_log_prob[b];
         const float ratio = expf(lr);
         const float pl1 = advn * ratio, pl2 = advn * fminf(fmaxf(ratio, lo), hi);
-        t.part0 = (double)fminf(pl1, pl2);
+        // fminf / fmaxf drop a NaN operand where torch.clamp / torch.min propagate it: a NaN ratio stays one (pl1 carries a NaN
+        // advantage by itself, and fminf of two NaNs is NaN)
+        t.part0 = (double)(ratio != ratio ? ratio : fminf(pl1, pl2));
         t.part2 = (double)((ratio - 1.0f) - lr);
         t.part3 = fabsf(ratio - 1.0f) > cr ? 1.0 : 0.0;
         // d min(pl1, pl2) / d ratio: the clamp passes the gradient on the closed interval (there pl1 == pl2, torch splits the
-        // gradient between the two equal operands and both halves arrive); outside it only pl1 carries one
-        const float dmin = ((ratio >= lo && ratio <= hi) || pl1 < pl2) ? advn : 0.0f;
+        // gradient between the two equal operands and both halves arrive); outside it only pl1 carries one. torch.min zeroes
+        // pl1's share only where pl1 > pl2, so a NaN product (of a NaN advantage or a NaN ratio) keeps it and the gradient is NaN
+        const float dmin = ((ratio >= lo && ratio <= hi) || !(pl1 >= pl2)) ? advn : 0.0f;
         t.g_logp = -(inv_b * dmin) * ratio;
     } else {
         t.part0 = (double)(advn * logp);
@@ -155,8 +158,8 @@ __device__ __forceinline__ ValueTerm value_term(const float v, const float ret, 
     bool pass = true;
     if (vclip) {
         const float vo = old_values[b], dv = v - vo;
-        vp = vo + fminf(fmaxf(dv, -cv), cv);
-        pass = dv >= -cv && dv <= cv;
+        vp = vo + (dv != dv ? dv : fminf(fmaxf(dv, -cv), cv));  // torch.clamp: a NaN step stays one, the value loss goes NaN
+        pass = dv >= -cv && dv <= cv;                           // ... and its mask passes no gradient for it: g_value = 0
     }
     const float dr = ret - vp;
     ValueTerm t;

@@ -19,8 +19,12 @@
 // NOT a batch reduction, and not order-deterministic: the Monitor-style episode statistics of the add launch (ep_stats: f64
 // atomicAdd per finished episode, the convention of cstr_collect_step_f32). The count and the sum of lengths are integers in f64 and
 // so exact in any order; the sum of returns, which only feeds the logged rollout/ep_rew_mean, may differ in its last f64 bits.
-// NaN: fminf / fmaxf in the clips DROP a NaN operand where torch.min / clamp propagate it; the losses still go NaN through the
-// unclipped terms.
+// NaN: the loss launch propagates a NaN as torch does (policy_term / value_term of cstr_onpolicy_device.h select around fminf /
+// fmaxf, which DROP a NaN operand where torch.min / clamp keep it). A NaN log-prob or advantage of a row makes policy_loss, loss,
+// d/d log_std and that row's d/d mean NaN (a NaN log-prob also approx_kl; clip_fraction stays finite, the comparison is false). A NaN
+// value makes value_loss and loss NaN; its row's d/d value is NaN without the value clip and 0 with it (clamp's mask passes no
+// gradient for a NaN step). Every other row's gradient keeps its bits. The rollout head's np.clip of the action (env_action) still
+// goes through fminf / fmaxf: a NaN action reaches the env as `low`.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
