@@ -1450,6 +1450,72 @@ int cstr_eval_goal_episodes_f32(const cstr_policy_mlp_t *net, const cstr_coef_t 
                                 const float *act_high, const int32_t *targets, int64_t n_envs, int64_t max_vec_steps, double *ep_return,
                                 int32_t *ep_len, int32_t *ep_done, float *ep_goal, float *ep_gap, double *ep_abs_gap, cstr_stream_t stream);
 
+/* ---- Augmented Random Search (csrc/cstr_ars.hip; Mania, Guy & Recht 2018, sb3_contrib.ARS) ----------------------------------------
+ * One update = 2 n_delta whole-episode evaluations of perturbed copies of a small deterministic policy (one launch), then selection
+ * and the parameter step (a second launch). No backward pass, no optimiser state.
+ *
+ * The policy: nn.Sequential(create_mlp(obs_dim, act_dim, net_arch, activation, with_bias, squash_output)), its parameters one flat
+ * float vector `theta` in parameters() order without padding: per layer W [out][in] row-major, then b [out] when with_bias.
+ *   n_hidden 0 (u = K x (+ b)), 1 or 2; h1, h2 in 1 .. CSTR_ARS_MAX_WIDTH (ignored where the layer does not exist);
+ *   act 1 = ReLU, 2 = Tanh (CSTR_ACT_*; ignored with n_hidden = 0); squash: a Tanh behind the last layer, and predict() un-scales
+ *   low + 0.5 (y + 1) (high - low); without it predict() clips into [low, high] (NaN passes).
+ * A dot product is acc = 0, acc += w[i] * x[i] for i ascending, then + bias, then the activation: one summation order.
+ *
+ * THE DELTAS ARE NEVER STORED: delta[k][p] (k < n_delta, p < P) is, with q = p >> 2 and e = p & 3,
+ *   words = Philox4x32-10(counter words (q, k, (uint32_t)update_index, 0xA4500D17), key words ((uint32_t)seed, (uint32_t)(seed >> 32)))
+ *   z0 = r(words[0]) cos(a(words[1])), z1 = r(words[0]) sin(a(words[1])), z2, z3 likewise from words[2], words[3];  delta[k][p] = z_e
+ *   r(w) = sqrtf(-2 logf(((w >> 8) + 0.5) * 2^-24)),  a(w) = 2 pi ((w >> 8) + 0.5) * 2^-24     (float arithmetic)
+ * Counter word 3 is this stream's own tag. Both launches regenerate the deltas from (seed, update_index).
+ * Candidates (float: product rounded, then the sum): job c = k is theta + delta_std * delta_k, job c = n_delta + k is theta - ... . */
+#define CSTR_ARS_MAX_WIDTH 64   /* hidden units per layer: one lane each */
+#define CSTR_ARS_MAX_DELTA 4096 /* n_delta: the update launch ranks by counting inside one workgroup */
+
+typedef struct {
+    int32_t obs_dim, act_dim, n_hidden, h1, h2, act, with_bias, squash;
+} cstr_ars_policy_t;
+
+/* Host only, touches no GPU: 1 when the two launches take this policy, n_delta in 1 .. CSTR_ARS_MAX_DELTA and n_top in 1 .. n_delta;
+ * else 0. (obs_dim, act_dim) must be a CSTR layout. */
+int cstr_ars_supported(int obs_dim, int act_dim, int n_hidden_layers, int h1, int h2, int act, int with_bias, int squash, int n_delta,
+                       int n_top);
+
+/* The population launch. Job c (0 .. 2 n_delta - 1) runs on env slot c % n_envs; a slot handles its jobs in increasing c, one after
+ * another. A job: the slot's reset draw (its PCG64 stream and static_init entry, the arithmetic of cstr_reset_draw_f32; step_count = 0),
+ * then n_eval_episodes episodes: per step the policy, predict()'s un-scale / clip against act_low / act_high (host arrays [act_dim]), the
+ * env step of cstr_vec_step_f32; an episode ends when the step truncates (max_steps, or the NaN path) and is followed by the auto-reset
+ * draw.  returns[c] = sum over the job's episodes, in order, of (the f64 sum of the episode's f32 step rewards)
+ *                     + alive_bonus_offset * (double)lengths[c];  lengths[c] = the job's steps over all its episodes.
+ * n_envs = 1: the env's random stream is consumed as by a sequential loop over the candidates; slots >= 2 n_delta do nothing and
+ * their state is untouched; env_obs [N][obs_dim], step_count [N], pcg_state [N][4], static_init f64 [N][4 or 8] or NULL are left as
+ * each slot's last job left them.
+ * stats double[4] i/o: [0] sum of lengths, [1] sum of returns, [2] number of NaN returns -- fixed-order sums, written by the workgroup
+ * that finishes last; [3] is the launch's 64-bit ticket: ZERO on entry, zero again on exit.
+ * Mappings: n_hidden = 0: a slot per lane; otherwise a slot per wave (lane j owns unit j; one wave per workgroup, no cross-wave
+ * barrier). At most ceil(2 n_delta / n_envs) * n_eval_episodes * max(coef->max_steps, 1) steps per slot whatever the data does.
+ * CSTR_E_BADARG: NULL required pointers, n_envs <= 0, n_delta < 1, n_eval_episodes < 1, delta_std <= 0 or NaN, NaN alive_bonus_offset,
+ * update_index outside 0 .. 2^32 - 1, act_high <= act_low, misaligned buffers (env_obs, pcg_state 16; returns, stats, static_init 8;
+ * others 4), anything written overlapping theta or anything else written; CSTR_E_UNSUPPORTED: a policy cstr_ars_supported declines,
+ * n_delta > CSTR_ARS_MAX_DELTA, unknown integrator. All checked before anything is enqueued. */
+int cstr_ars_population_f32(const cstr_ars_policy_t *policy, const float *theta, float delta_std, uint64_t seed, int64_t update_index,
+                            int n_delta, int n_eval_episodes, double alive_bonus_offset, const cstr_coef_t *coef, int integrator,
+                            float *env_obs, int32_t *step_count, uint64_t *pcg_state, double *static_init, const float *act_low,
+                            const float *act_high, int64_t n_envs, double *returns, int32_t *lengths, double *stats,
+                            cstr_stream_t stream);
+
+/* The update launch, on returns double[2 n_delta] (R+_k = returns[k], R-_k = returns[n_delta + k]):
+ *   top_k = max(R+_k, R-_k), NaN if either is; directions in descending top_k, a NaN counting as the greatest and ties (two NaNs
+ *   included) going to the lower k; the first n_top are kept: kept int32[n_top], in that order;
+ *   return_std = unbiased standard deviation over the 2 n_top kept returns (R+ of the kept in order, then R-), float64;
+ *   step_size = learning_rate / (n_top * return_std + 1e-6), float64;
+ *   theta[p] = (float)((double)theta[p] + step_size * sum over the kept k, in order, of (R+_k - R-_k) * (double)delta[k][p]).
+ * out double[2] = {step_size, return_std}. A kept NaN return makes step_size and every theta[p] NaN, as published. Sums have a fixed
+ * order; no float atomics.
+ * CSTR_E_BADARG: NULL pointers, n_params < 1, n_delta < 1, n_top outside 1 .. n_delta, update_index outside 0 .. 2^32 - 1, NaN
+ * learning_rate, misaligned buffers, outputs overlapping returns or each other; CSTR_E_UNSUPPORTED: n_delta > CSTR_ARS_MAX_DELTA,
+ * n_params > 4996 (net_arch [64, 64] on the (8, 4) layout). */
+int cstr_ars_update_f32(float *theta, int64_t n_params, const double *returns, int n_delta, int n_top, double learning_rate, uint64_t seed,
+                        int64_t update_index, double *out, int32_t *kept, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ CQL_MAX_ACTIONS, CQL_TAG = 21, 0xC0175E4A  # CSTR_CQL_MAX_ACTIONS; counter word 
 IQL_MAX_BATCH = 16384  # CSTR_IQL_MAX_BATCH
 TQC_MAX_ATOMS = 256  # CSTR_TQC_MAX_ATOMS
 QRDQN_MAX_QUANTILES = 256  # CSTR_QRDQN_MAX_QUANTILES
+ARS_MAX_WIDTH, ARS_MAX_DELTA, ARS_TAG = 64, 4096, 0xA4500D17  # CSTR_ARS_MAX_WIDTH, CSTR_ARS_MAX_DELTA; counter word 3 of the delta stream
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -59,6 +60,7 @@ SYMBOLS = (
     "cstr_iql_loss_f32",
     "cstr_tqc_supported", "cstr_tqc_critic_loss_f32", "cstr_tqc_actor_loss_f32",
     "cstr_qrdqn_supported", "cstr_qrdqn_fold_head_f32", "cstr_qrdqn_loss_f32",
+    "cstr_ars_supported", "cstr_ars_population_f32", "cstr_ars_update_f32",
 )
 
 
@@ -212,6 +214,11 @@ class MultiCategoricalLoss(C.Structure):
         ("batch", C.c_int64), ("levels0", C.c_int32), ("levels1", C.c_int32), ("objective", C.c_int32), ("normalize_advantage", C.c_int32),
         ("clip_range", C.c_double), ("clip_range_vf", C.c_double), ("ent_coef", C.c_float), ("vf_coef", C.c_float)] + [(n, C.c_void_p) for n in (
             "g_logits", "g_value", "scalars_out", "scalars_sum", "log_prob_out")]
+
+
+class ArsPolicy(C.Structure):
+    """cstr_ars_policy_t"""
+    _fields_ = [(n, C.c_int32) for n in ("obs_dim", "act_dim", "n_hidden", "h1", "h2", "act", "with_bias", "squash")]
 
 
 class NativeError(RuntimeError):

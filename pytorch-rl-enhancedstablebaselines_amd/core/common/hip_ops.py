@@ -2330,3 +2330,70 @@ def goal_eval_episodes_into(w1, b1, w2, b2, w3, b3, act, head, out_act, w2_swz, 
                                                C.c_float(goal_hi), C.c_int(1 if squashed else 0), lo, hi, targets.ctypes.data_as(C.c_void_p),
                                                C.c_int64(n), C.c_int64(int(max_vec_steps)), ptr(ep_return), ptr(ep_len), ptr(ep_done),
                                                ptr(ep_goal), ptr(ep_gap), ptr(ep_abs_gap), stream_ptr()), "cstr_eval_goal_episodes_f32")
+
+
+# ---- Augmented Random Search (csrc/cstr_ars.hip) -----------------------------------------------------------------------------------
+
+ARS_STATS_WORDS = 4  # {sum of lengths, sum of returns, NaN returns, the launch's ticket (zero between launches)}
+
+
+def ars_n_params(obs_dim: int, act_dim: int, hidden, with_bias: bool) -> int:
+    """parameters of create_mlp(obs_dim, act_dim, hidden, with_bias=with_bias): the length of `theta`"""
+    dims, b = [obs_dim, *hidden, act_dim], 1 if with_bias else 0
+    return sum(o * (i + b) for i, o in zip(dims[:-1], dims[1:]))
+
+
+def ars_supported(obs_dim: int, act_dim: int, hidden, act: int, with_bias: bool, squash: bool, n_delta: int, n_top: int) -> bool:
+    """cstr_ars_supported: host only. `hidden`: the hidden widths (0, 1 or 2 of them, each 1..64); act: ACT["relu"] / ACT["tanh"]."""
+    hidden = [int(h) for h in hidden]
+    if len(hidden) > 2:
+        return False
+    h1, h2 = (hidden + [0, 0])[:2]
+    return bool(nv.lib().cstr_ars_supported(C.c_int(obs_dim), C.c_int(act_dim), C.c_int(len(hidden)), C.c_int(h1), C.c_int(h2), C.c_int(int(act)),
+                                            C.c_int(1 if with_bias else 0), C.c_int(1 if squash else 0), C.c_int(int(n_delta)), C.c_int(int(n_top))))
+
+
+def _ars_policy(obs_dim: int, act_dim: int, hidden, act: int, with_bias: bool, squash: bool) -> "nv.ArsPolicy":
+    hidden = [int(h) for h in hidden]
+    if len(hidden) > 2:
+        raise ValueError(f"ARS kernels take 0, 1 or 2 hidden layers, got {hidden}")
+    h1, h2 = (hidden + [0, 0])[:2]
+    return nv.ArsPolicy(obs_dim, act_dim, len(hidden), h1, h2, int(act), 1 if with_bias else 0, 1 if squash else 0)
+
+
+def ars_population(theta, hidden, act: int, with_bias: bool, squash: bool, delta_std: float, seed: int, update_index: int, n_delta: int,
+                   n_eval_episodes: int, alive_bonus_offset: float, coef, integrator: str, env_obs, step_count, pcg_state, act_low, act_high,
+                   returns, lengths, stats, static_init=None):
+    """The population launch (cstr_ars_population_f32): the 2 n_delta candidates theta +- delta_std * delta_k of update `update_index`
+    evaluated on the env arrays, candidate c on slot c % n_envs. Writes returns float64 [2 n_delta], lengths int32 [2 n_delta] and the
+    statistics block stats float64 [ARS_STATS_WORDS] (word 3 must be zero on entry and is zero on exit); advances the env arrays."""
+    n, d = env_obs.shape
+    a = len(act_low)
+    if (d, a) not in LAYOUTS:
+        raise ValueError(f"(obs_dim, act_dim) = {(d, a)} is not a CSTR layout {LAYOUTS}")
+    if len(act_high) != a:
+        raise ValueError(f"act_low/act_high need {a} entries each")
+    pol = _ars_policy(d, a, hidden, act, with_bias, squash)
+    _chk(theta, "theta", (ars_n_params(d, a, hidden, with_bias),), th.float32)
+    _chk(env_obs, "env_obs", (n, d), th.float32), _chk(step_count, "step_count", (n,), th.int32)
+    _chk(pcg_state, "pcg_state", (n, nv.PCG_STATE_WORDS), th.int64)
+    _opt(static_init, "static_init", (n, 8 if a == 4 else 4), th.float64)
+    _chk(returns, "returns", (2 * n_delta,), th.float64), _chk(lengths, "lengths", (2 * n_delta,), th.int32)
+    _chk(stats, "stats", (ARS_STATS_WORDS,), th.float64)
+    lo = (C.c_float * a)(*[float(v) for v in act_low])
+    hi = (C.c_float * a)(*[float(v) for v in act_high])
+    check(nv.lib().cstr_ars_population_f32(C.byref(pol), ptr(theta), C.c_float(delta_std), C.c_uint64(int(seed) & (2**64 - 1)),
+                                           C.c_int64(int(update_index)), C.c_int(int(n_delta)), C.c_int(int(n_eval_episodes)),
+                                           C.c_double(float(alive_bonus_offset)), C.byref(coef), C.c_int(INTEGRATORS[integrator]), ptr(env_obs),
+                                           ptr(step_count), ptr(pcg_state), ptr(static_init), lo, hi, C.c_int64(n), ptr(returns), ptr(lengths),
+                                           ptr(stats), stream_ptr()), "cstr_ars_population_f32")
+
+
+def ars_update(theta, returns, n_delta: int, n_top: int, learning_rate: float, seed: int, update_index: int, out, kept):
+    """The update launch (cstr_ars_update_f32): ranking, return_std, step_size and theta += step_size * sum (R+ - R-) delta in place.
+    out float64 [2] = {step_size, return_std}; kept int32 [n_top] = the kept directions in rank order."""
+    _chk(theta, "theta", (theta.numel(),), th.float32), _chk(returns, "returns", (2 * n_delta,), th.float64)
+    _chk(out, "out", (2,), th.float64), _chk(kept, "kept", (n_top,), th.int32)
+    check(nv.lib().cstr_ars_update_f32(ptr(theta), C.c_int64(theta.numel()), ptr(returns), C.c_int(int(n_delta)), C.c_int(int(n_top)),
+                                       C.c_double(float(learning_rate)), C.c_uint64(int(seed) & (2**64 - 1)), C.c_int64(int(update_index)),
+                                       ptr(out), ptr(kept), stream_ptr()), "cstr_ars_update_f32")
