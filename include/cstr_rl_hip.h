@@ -1516,6 +1516,119 @@ int cstr_ars_population_f32(const cstr_ars_policy_t *policy, const float *theta,
 int cstr_ars_update_f32(float *theta, int64_t n_params, const double *returns, int n_delta, int n_top, double learning_rate, uint64_t seed,
                         int64_t update_index, double *out, int32_t *kept, cstr_stream_t stream);
 
+/* ---- TRPO: trust-region policy steps on Fisher-vector products (csrc/cstr_trpo.hip) --------------------------------------------
+ * At theta0 the new and the old distribution coincide, so the Hessian of the mean KL is the Fisher matrix and
+ *   Fvp(v) = (1/R) sum_r J_r^T M_r J_r v + damping v
+ * is a tangent (forward-mode) pass through the actor's Linear layers (cstr_linear_tangent_fwd_f32), the head's metric
+ * (cstr_trpo_fisher_head_f32), the per-layer backward (cstr_linear_bwd_input_f32 / cstr_linear_bwd_weight_sets_f32) and one
+ * conjugate-gradient launch (cstr_trpo_cg_step_f32), which folds the damping term in. Vectors over the parameters (g, x, r, p, s)
+ * are ARENA-sized float arrays whose entries outside the actor's tensors are exactly zero.
+ * Batch sums and dot products are float64 in a fixed order (no float atomics); a given shape always reduces the same way.
+ * The control block, double[CSTR_TRPO_CTL_WORDS], lives on the device; the host reads none of it while train() runs. */
+#define CSTR_TRPO_HEAD_GAUSSIAN 0         /* diagonal Gaussian, state-independent log_std: k0 = act_dim (2 or 4) */
+#define CSTR_TRPO_HEAD_CATEGORICAL 1      /* k0 logits, 2 .. CSTR_TRPO_MAX_LOGITS */
+#define CSTR_TRPO_HEAD_MULTICATEGORICAL 2 /* k0 + k1 logits in th.split order, 2 .. 32 each */
+#define CSTR_TRPO_MAX_LOGITS 64
+#define CSTR_TRPO_CTL_WORDS 16
+#define CSTR_TRPO_CTL_RR 0        /* r . r of the conjugate-gradient iteration */
+#define CSTR_TRPO_CTL_ALPHA 1
+#define CSTR_TRPO_CTL_BETA 2
+#define CSTR_TRPO_CTL_PAP 3       /* p . (F p + damping p) */
+#define CSTR_TRPO_CTL_DONE 4      /* 1.0 once the iteration has returned: later step launches do nothing */
+#define CSTR_TRPO_CTL_ITERS 5     /* step launches that did something */
+#define CSTR_TRPO_CTL_SFS 6       /* s . (F s + damping s) */
+#define CSTR_TRPO_CTL_STEP 7      /* sqrt(2 target_kl / sFs) */
+#define CSTR_TRPO_CTL_COEFF 8     /* the line search's coefficient */
+#define CSTR_TRPO_CTL_OBJECTIVE 9 /* the objective and the KL of the gradient-mode launch (the base of the line search) */
+#define CSTR_TRPO_CTL_KL 10
+#define CSTR_TRPO_CTL_LS_OBJECTIVE 11 /* ... of the last line-search launch */
+#define CSTR_TRPO_CTL_LS_KL 12
+#define CSTR_TRPO_CG_INIT 0
+#define CSTR_TRPO_CG_STEP 1
+#define CSTR_TRPO_CG_FINISH 2
+#define CSTR_TRPO_MAX_VECTOR (1 << 24) /* floats of an arena-sized vector */
+
+/* z_dot[m][n] = f'(y) * (x w_dot^T + x_dot w^T + b_dot): the tangent of one Linear + activation layer. f: CSTR_ACT_NONE, CSTR_ACT_TANH
+ * (1 - y^2 from the stored output y[m][n]) or CSTR_ACT_RELU (y > 0). x [m][ldx >= k], x_dot [m][ldxd >= k] or NULL (the first layer: an
+ * observation has no tangent), w, w_dot [n][k], b_dot [n], y and z_dot contiguous. One wave per 16 x 16 output tile on the f32 matrix
+ * cores (v_mfma_f32_16x16x4_f32); the two products run in two independent accumulators that meet in the epilogue.
+ * CSTR_E_BADARG: NULL pointers (y only with an activation), sizes < 1, a row stride below k, buffers not 4-byte aligned, z_dot
+ * overlapping an input; CSTR_E_UNSUPPORTED: unknown activation, m, n or k above 2^23 - 1, more than 65535 row tiles, a row stride
+ * above 2^31 - 1. */
+int cstr_linear_tangent_fwd_f32(const float *x, int64_t ldx, const float *x_dot, int64_t ldxd, const float *w, const float *w_dot,
+                                const float *b_dot, const float *y, int act, float *z_dot, int64_t m, int64_t n, int64_t k,
+                                cstr_stream_t stream);
+
+typedef struct {
+    const float *dist;        /* the action mean [R][ld] or the logits [R][ld] at the current parameters */
+    int64_t ld;
+    const float *log_std;     /* Gaussian head: [k0] at the current parameters; NULL otherwise */
+    const float *old_dist;    /* the same two at theta0, held constant (may be the very same buffers) */
+    int64_t old_ld;
+    const float *old_log_std;
+    const float *actions;     /* [R][k0] (Gaussian), [R] the index as a float, [R][2] the level pair as floats */
+    const float *old_log_prob;/* [R], the rollout buffer's */
+    const float *adv;         /* [R] */
+    int64_t batch;            /* R */
+    int32_t head, k0, k1, normalize_advantage;
+    int32_t line_search, reserved;
+    double target_kl, shrink; /* line-search mode */
+    float *g_dist;            /* gradient mode: d objective / d dist, [R][width] contiguous */
+    float *g_log_std;         /* gradient mode, Gaussian head: d objective / d log_std [k0] */
+    float *scalars_out;       /* [2]: objective, kl; may be NULL */
+    double *ctl;              /* the control block */
+    int32_t *accepted;        /* line-search mode: 1 iff kl' < target_kl and objective' > objective */
+} cstr_trpo_objective_t;
+
+/* One launch for everything between the actor's outputs and the backward: adv = (adv - mean) / (std + 1e-8) over the R rows (with
+ * normalize_advantage; std unbiased), log_prob (the heads' shared device functions, in double), ratio = exp(log_prob - old_log_prob),
+ * objective = mean(adv ratio), kl = mean_r KL(new_r || old_r) summed over action dimensions or sub-distributions.
+ * Gradient mode (line_search = 0): also d objective / d (mean, log_std) or d objective / d logits; ctl[OBJECTIVE], ctl[KL] are
+ * written and ctl[COEFF] = 1. Line-search mode: no gradients; *accepted = kl < target_kl && objective > ctl[OBJECTIVE];
+ * ctl[LS_OBJECTIVE], ctl[LS_KL] are written and ctl[COEFF] *= shrink when the step was not accepted.
+ * Every per-row quantity is formed in double from the float inputs; stores are float. Any R up to CSTR_PPO_MAX_ROWS: the grid is
+ * capped at CSTR_PPO_MAX_BLOCKS workgroups, which stride over the rows. workspace: uint64[CSTR_PPO_WS_WORDS], zero before first use.
+ * CSTR_E_BADARG: NULL struct or required pointers, R < 1, strides below the width, misaligned buffers, an output overlapping an input or
+ * another output, target_kl <= 0 or shrink outside (0, 1) in line-search mode; CSTR_E_UNSUPPORTED: a head or width outside the list. */
+int cstr_trpo_objective_f32(const cstr_trpo_objective_t *p, uint64_t *workspace, cstr_stream_t stream);
+
+/* The Fisher metric of the head in distribution-parameter space, times the tangent, over R: upstream [R][width] contiguous is what the
+ * per-layer backward takes as d / d (mean | logits).
+ *   Gaussian: upstream[r][a] = dist_dot[r][a] * exp(-2 log_std[a]) / R, and g_log_std[a] = 2 v_log_std[a] (no cross terms);
+ *   (Multi)Categorical, per block of logits with p = softmax(dist[r]): upstream[r] = (p * dist_dot[r] - p (p . dist_dot[r])) / R.
+ * dist_dot [R][ldd]: the tangent of the mean / logits. dist [R][ld]: the logits at theta0 (discrete heads; NULL for the Gaussian).
+ * CSTR_E_BADARG / CSTR_E_UNSUPPORTED as for cstr_trpo_objective_f32. */
+int cstr_trpo_fisher_head_f32(int head, int k0, int k1, const float *dist_dot, int64_t ldd, const float *dist, int64_t ld,
+                              const float *log_std, const float *v_log_std, int64_t batch, float *upstream, float *g_log_std,
+                              cstr_stream_t stream);
+
+/* One conjugate-gradient launch (a single workgroup) over n-float vectors; ap = F v WITHOUT the damping term, as the backward left
+ * it; the launch adds damping * v itself. Scalars and dot products are double in ctl.
+ *   CSTR_TRPO_CG_INIT   (ap = F x): r = g - (ap + damping x); p = r; rr = r . r; done = rr < residual_tol; iters = 0.
+ *   CSTR_TRPO_CG_STEP   (ap = F p): nothing when done. Otherwise Ap = ap + damping p; alpha = rr / (p . Ap); x += alpha p; with
+ *                       `last` (the iteration max_iter - 1) done = 1 and return; r -= alpha Ap; new_rr = r . r; if new_rr <
+ *                       residual_tol done = 1 and return; beta = new_rr / rr; rr = new_rr; p = r + beta p.
+ *   CSTR_TRPO_CG_FINISH (ap = F x): sFs = x . (ap + damping x); step = sqrt(2 target_kl / sFs); coeff = 1. r, p, g may be NULL.
+ * CSTR_E_BADARG: NULL or misaligned pointers, overlapping vectors, n < 1, unknown mode, negative or NaN damping / residual_tol,
+ * target_kl <= 0 in the finishing form; CSTR_E_UNSUPPORTED: n > CSTR_TRPO_MAX_VECTOR. */
+int cstr_trpo_cg_step_f32(int mode, float *x, float *r, float *p, const float *ap, const float *g, int64_t n, double damping,
+                          double residual_tol, double target_kl, int last, double *ctl, cstr_stream_t stream);
+
+/* theta[i] = theta0[i] + (ctl[COEFF] * ctl[STEP]) * s[i] where mask[i] != 0 (the actor's tensors); every other float of theta is left
+ * untouched. CSTR_E_BADARG: NULL / misaligned pointers, n < 1, theta overlapping an input; CSTR_E_UNSUPPORTED: n > CSTR_TRPO_MAX_VECTOR. */
+int cstr_trpo_apply_step_f32(float *theta, const float *theta0, const float *s, const float *mask, int64_t n, const double *ctl,
+                             cstr_stream_t stream);
+
+/* The critic minibatch's loss launch (a single workgroup): loss = mean((returns - values)^2), g_value[b] = 2 (values[b] - returns[b]) /
+ * batch; loss_out[0] = loss and loss_sum[0] += loss where given. CSTR_E_BADARG: NULL / misaligned pointers, batch < 1, overlaps. */
+int cstr_trpo_value_loss_f32(const float *values, const float *returns, int64_t batch, float *g_value, float *loss_out, float *loss_sum,
+                             cstr_stream_t stream);
+
+/* x[i] = scale * N(0, 1) where mask[i] != 0, 0 elsewhere: the conjugate gradient's start. Philox4x32-10 keyed by rng_ctl[0], counter
+ * (rng_ctl[1] + i / 2, 0, 0x7290C6A5), one Box-Muller pair per counter for the floats 2j and 2j + 1; the last workgroup advances
+ * rng_ctl[1] by (n + 1) / 2. CSTR_E_BADARG: NULL / misaligned pointers, n < 1, overlaps; CSTR_E_UNSUPPORTED: n > CSTR_TRPO_MAX_VECTOR. */
+int cstr_trpo_x0_f32(float *x, const float *mask, int64_t n, float scale, uint64_t *rng_ctl, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

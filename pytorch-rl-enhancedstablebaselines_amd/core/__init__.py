@@ -1,4 +1,4 @@
-"""`core` -- MI355X-native drop-in for the reference's `core` package on the SAC/TQC/TD3/MADDPG/BCQ/TD3BC/CQL/IQL/PPO/A2C/DQN/QRDQN/ARS + two-series
+"""`core` -- MI355X-native drop-in for the reference's `core` package on the SAC/TQC/TD3/MADDPG/BCQ/TD3BC/CQL/IQL/PPO/A2C/TRPO/DQN/QRDQN/ARS + two-series
 CSTR path (reference: core/__init__.py:1-40). Algorithms are imported lazily so that host-only
 utilities (and the CPU test-suite) do not need a GPU."""
 import os
@@ -6,7 +6,7 @@ import os
 with open(os.path.join(os.path.dirname(__file__), "version.txt")) as _fh:  # the reference forgot to ship this file
     __version__ = _fh.read().strip()
 
-__all__ = ["SAC", "TQC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "TD3BC", "CQL", "IQL", "PPO", "A2C", "DQN", "QRDQN", "ARS", "HerReplayBuffer", "__version__"]
+__all__ = ["SAC", "TQC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "TD3BC", "CQL", "IQL", "PPO", "A2C", "DQN", "QRDQN", "ARS", "TRPO", "HerReplayBuffer", "__version__"]
 
 
 def __getattr__(name):
@@ -52,6 +52,9 @@ def __getattr__(name):
     if name == "ARS":
         from core.ars import ARS
         return ARS
+    if name == "TRPO":
+        from core.trpo import TRPO
+        return TRPO
     if name == "HerReplayBuffer":
         from core.her import HerReplayBuffer
         return HerReplayBuffer

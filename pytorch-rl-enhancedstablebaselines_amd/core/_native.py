@@ -31,6 +31,11 @@ IQL_MAX_BATCH = 16384  # CSTR_IQL_MAX_BATCH
 TQC_MAX_ATOMS = 256  # CSTR_TQC_MAX_ATOMS
 QRDQN_MAX_QUANTILES = 256  # CSTR_QRDQN_MAX_QUANTILES
 ARS_MAX_WIDTH, ARS_MAX_DELTA, ARS_TAG = 64, 4096, 0xA4500D17  # CSTR_ARS_MAX_WIDTH, CSTR_ARS_MAX_DELTA; counter word 3 of the delta stream
+# TRPO (csrc/cstr_trpo.hip): the heads, the control block's words (CSTR_TRPO_CTL_*), the conjugate-gradient launch's forms, the x0 stream's tag
+TRPO_HEAD_GAUSSIAN, TRPO_HEAD_CATEGORICAL, TRPO_HEAD_MULTICATEGORICAL = 0, 1, 2
+TRPO_MAX_LOGITS, TRPO_CTL_WORDS, TRPO_MAX_VECTOR, TRPO_TAG = 64, 16, 1 << 24, 0x7290C6A5
+TRPO_CTL = dict(rr=0, alpha=1, beta=2, pap=3, done=4, iters=5, sfs=6, step=7, coeff=8, objective=9, kl=10, ls_objective=11, ls_kl=12)
+TRPO_CG_INIT, TRPO_CG_STEP, TRPO_CG_FINISH = 0, 1, 2
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -61,6 +66,8 @@ SYMBOLS = (
     "cstr_tqc_supported", "cstr_tqc_critic_loss_f32", "cstr_tqc_actor_loss_f32",
     "cstr_qrdqn_supported", "cstr_qrdqn_fold_head_f32", "cstr_qrdqn_loss_f32",
     "cstr_ars_supported", "cstr_ars_population_f32", "cstr_ars_update_f32",
+    "cstr_linear_tangent_fwd_f32", "cstr_trpo_objective_f32", "cstr_trpo_fisher_head_f32", "cstr_trpo_cg_step_f32", "cstr_trpo_apply_step_f32",
+    "cstr_trpo_value_loss_f32", "cstr_trpo_x0_f32",
 )
 
 
@@ -219,6 +226,15 @@ class MultiCategoricalLoss(C.Structure):
 class ArsPolicy(C.Structure):
     """cstr_ars_policy_t"""
     _fields_ = [(n, C.c_int32) for n in ("obs_dim", "act_dim", "n_hidden", "h1", "h2", "act", "with_bias", "squash")]
+
+
+class TrpoObjective(C.Structure):
+    """cstr_trpo_objective_t"""
+    _fields_ = [("dist", C.c_void_p), ("ld", C.c_int64), ("log_std", C.c_void_p), ("old_dist", C.c_void_p), ("old_ld", C.c_int64),
+                ("old_log_std", C.c_void_p), ("actions", C.c_void_p), ("old_log_prob", C.c_void_p), ("adv", C.c_void_p), ("batch", C.c_int64),
+                ("head", C.c_int32), ("k0", C.c_int32), ("k1", C.c_int32), ("normalize_advantage", C.c_int32), ("line_search", C.c_int32),
+                ("reserved", C.c_int32), ("target_kl", C.c_double), ("shrink", C.c_double), ("g_dist", C.c_void_p), ("g_log_std", C.c_void_p),
+                ("scalars_out", C.c_void_p), ("ctl", C.c_void_p), ("accepted", C.c_void_p)]
 
 
 class NativeError(RuntimeError):

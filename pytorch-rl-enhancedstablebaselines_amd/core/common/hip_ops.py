@@ -2397,3 +2397,138 @@ def ars_update(theta, returns, n_delta: int, n_top: int, learning_rate: float, s
     check(nv.lib().cstr_ars_update_f32(ptr(theta), C.c_int64(theta.numel()), ptr(returns), C.c_int(int(n_delta)), C.c_int(int(n_top)),
                                        C.c_double(float(learning_rate)), C.c_uint64(int(seed) & (2**64 - 1)), C.c_int64(int(update_index)),
                                        ptr(out), ptr(kept), stream_ptr()), "cstr_ars_update_f32")
+
+
+# ---- TRPO: tangent layers, the objective / line-search launch, the Fisher head, conjugate gradient (csrc/cstr_trpo.hip) ----------------
+def trpo_head(head: int, k0: int, k1: int = 0):
+    """(width of the distribution parameters, floats per stored action row) of a TRPO head; raises for a head the kernels decline"""
+    if head == nv.TRPO_HEAD_GAUSSIAN and k0 in (2, 4):
+        return k0, k0
+    if head == nv.TRPO_HEAD_CATEGORICAL and 2 <= k0 <= nv.TRPO_MAX_LOGITS:
+        return k0, 1
+    if head == nv.TRPO_HEAD_MULTICATEGORICAL and 2 <= k0 <= 32 and 2 <= k1 <= 32:
+        return k0 + k1, 2
+    raise ValueError(f"TRPO head {head} with widths ({k0}, {k1}) is not built")
+
+
+def trpo_supported(head: int, k0: int, k1: int = 0) -> bool:
+    try:
+        trpo_head(head, k0, k1)
+        return True
+    except ValueError:
+        return False
+
+
+def new_trpo_ctl(device) -> th.Tensor:
+    """double[CSTR_TRPO_CTL_WORDS]: the conjugate gradient's and the line search's scalars (nv.TRPO_CTL names the words)"""
+    return th.zeros(nv.TRPO_CTL_WORDS, dtype=th.float64, device=device)
+
+
+def linear_tangent_fwd(x, x_dot, weight, w_dot, b_dot, y, act: int, out=None):
+    """z_dot = f'(y) * (x @ w_dot^T + x_dot @ weight^T + b_dot): the tangent of one Linear + activation layer in one launch. x [M, K]
+    (rows may be strided), x_dot the same or None (the first layer), weight / w_dot [N, K], b_dot [N], y [M, N] the layer's stored
+    output (needed with an activation)."""
+    m, k = x.shape
+    n = weight.shape[0]
+    ldx = max(_rows(x, "x", m, k), k)
+    ldxd = 0 if x_dot is None else max(_rows(x_dot, "x_dot", m, k), k)
+    _chk(weight, "weight", (n, k), th.float32), _chk(w_dot, "w_dot", (n, k), th.float32), _vec(b_dot, "b_dot", n)
+    if act != 0:
+        _chk(y, "y", (m, n), th.float32)
+    z = th.empty(m, n, dtype=th.float32, device=x.device) if out is None else _chk(out, "out", (m, n), th.float32)
+    check(nv.lib().cstr_linear_tangent_fwd_f32(ptr(x), C.c_int64(ldx), ptr(x_dot), C.c_int64(ldxd), ptr(weight), ptr(w_dot), ptr(b_dot),
+                                               ptr(y if act != 0 else None), C.c_int(act), ptr(z), C.c_int64(m), C.c_int64(n), C.c_int64(k),
+                                               stream_ptr()), "cstr_linear_tangent_fwd_f32")
+    return z
+
+
+def trpo_objective(head: int, k0: int, k1: int, dist, log_std, old_dist, old_log_std, actions, old_log_prob, adv, normalize_advantage: bool,
+                   ctl, workspace, g_dist=None, g_log_std=None, scalars_out=None, accepted=None, target_kl: float = 0.0,
+                   shrink: float = 0.0):
+    """The objective launch. Gradient mode (accepted None): objective, kl and d objective / d (dist, log_std) into g_dist [R, width] and
+    g_log_std [k0]; ctl's objective / kl / coeff words are set. Line-search mode (accepted int32 [1]): the decision against ctl's base
+    objective and target_kl, the coefficient shrunk by `shrink` on a rejection. dist / old_dist [R, width] (rows may be strided)."""
+    width, aw = trpo_head(head, k0, k1)
+    b = dist.shape[0]
+    ld, old_ld = _rows(dist, "dist", b, width), _rows(old_dist, "old_dist", b, width)
+    gauss = head == nv.TRPO_HEAD_GAUSSIAN
+    if gauss:
+        _vec(log_std, "log_std", width), _vec(old_log_std, "old_log_std", width)
+    _vec(actions, "actions", b * aw)
+    for t, nm in ((old_log_prob, "old_log_prob"), (adv, "adv")):
+        _vec(t, nm, b)
+    _chk(ctl, "ctl", (nv.TRPO_CTL_WORDS,), th.float64), _chk(workspace, "workspace", (nv.PPO_WS_WORDS,), th.int64)
+    line_search = accepted is not None
+    if line_search:
+        _chk(accepted, "accepted", (1,), th.int32)
+    else:
+        _chk(g_dist, "g_dist", (b, width), th.float32)
+        if gauss:
+            _vec(g_log_std, "g_log_std", width)
+    if scalars_out is not None:
+        _vec(scalars_out, "scalars_out", 2)
+    dp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    p = nv.TrpoObjective(dist.data_ptr(), ld, dp(log_std) if gauss else None, old_dist.data_ptr(), old_ld, dp(old_log_std) if gauss else None,
+                         actions.data_ptr(), old_log_prob.data_ptr(), adv.data_ptr(), b, int(head), int(k0), int(k1),
+                         int(bool(normalize_advantage)), int(line_search), 0, float(target_kl), float(shrink), dp(g_dist),
+                         dp(g_log_std) if gauss else None, dp(scalars_out), ctl.data_ptr(), dp(accepted))
+    check(nv.lib().cstr_trpo_objective_f32(C.byref(p), ptr(workspace), stream_ptr()), "cstr_trpo_objective_f32")
+
+
+def trpo_fisher_head(head: int, k0: int, k1: int, dist_dot, dist, log_std, v_log_std, upstream, g_log_std):
+    """upstream [R, width] = (the head's Fisher metric) @ dist_dot / R; the Gaussian head also writes g_log_std = 2 v_log_std."""
+    width, _ = trpo_head(head, k0, k1)
+    b = dist_dot.shape[0]
+    ldd = _rows(dist_dot, "dist_dot", b, width)
+    gauss = head == nv.TRPO_HEAD_GAUSSIAN
+    ld = 0
+    if gauss:
+        _vec(log_std, "log_std", width), _vec(v_log_std, "v_log_std", width), _vec(g_log_std, "g_log_std", width)
+    else:
+        ld = _rows(dist, "dist", b, width)
+    _chk(upstream, "upstream", (b, width), th.float32)
+    check(nv.lib().cstr_trpo_fisher_head_f32(C.c_int(head), C.c_int(k0), C.c_int(k1), ptr(dist_dot), C.c_int64(ldd), ptr(None if gauss else dist),
+                                             C.c_int64(ld), ptr(log_std if gauss else None), ptr(v_log_std if gauss else None), C.c_int64(b),
+                                             ptr(upstream), ptr(g_log_std if gauss else None), stream_ptr()), "cstr_trpo_fisher_head_f32")
+
+
+def trpo_cg_step(mode: int, x, r, p, ap, g, damping: float, residual_tol: float, ctl, target_kl: float = 0.0, last: bool = False):
+    """One conjugate-gradient launch over flat float32 vectors of one length (nv.TRPO_CG_INIT / _STEP / _FINISH); `ap` is the
+    Fisher-vector product WITHOUT the damping term."""
+    n = x.numel()
+    _vec(x, "x", n), _vec(ap, "ap", n)
+    for t, nm in ((r, "r"), (p, "p"), (g, "g")):
+        if t is not None:
+            _vec(t, nm, n)
+    _chk(ctl, "ctl", (nv.TRPO_CTL_WORDS,), th.float64)
+    check(nv.lib().cstr_trpo_cg_step_f32(C.c_int(mode), ptr(x), ptr(r), ptr(p), ptr(ap), ptr(g), C.c_int64(n), C.c_double(float(damping)),
+                                         C.c_double(float(residual_tol)), C.c_double(float(target_kl)), C.c_int(int(bool(last))), ptr(ctl),
+                                         stream_ptr()), "cstr_trpo_cg_step_f32")
+
+
+def trpo_apply_step(theta, theta0, s, mask, ctl):
+    """theta = theta0 + ctl[coeff] * ctl[step] * s where mask != 0; every other float of theta keeps its bits"""
+    n = theta.numel()
+    for t, nm in ((theta, "theta"), (theta0, "theta0"), (s, "s"), (mask, "mask")):
+        _vec(t, nm, n)
+    _chk(ctl, "ctl", (nv.TRPO_CTL_WORDS,), th.float64)
+    check(nv.lib().cstr_trpo_apply_step_f32(ptr(theta), ptr(theta0), ptr(s), ptr(mask), C.c_int64(n), ptr(ctl), stream_ptr()),
+          "cstr_trpo_apply_step_f32")
+
+
+def trpo_value_loss(values, returns, g_value, loss_out=None, loss_sum=None):
+    """mse(returns, values) and its gradient 2 (values - returns) / B in one launch; loss_sum[0] += loss"""
+    b = values.numel()
+    _vec(values, "values", b), _vec(returns, "returns", b), _vec(g_value, "g_value", b)
+    for t, nm in ((loss_out, "loss_out"), (loss_sum, "loss_sum")):
+        if t is not None:
+            _vec(t, nm, 1)
+    check(nv.lib().cstr_trpo_value_loss_f32(ptr(values), ptr(returns), C.c_int64(b), ptr(g_value), ptr(loss_out), ptr(loss_sum), stream_ptr()),
+          "cstr_trpo_value_loss_f32")
+
+
+def trpo_x0(x, mask, scale: float, rng_ctl):
+    """x = scale * N(0, 1) where mask != 0 and 0 elsewhere, drawn on TRPO's own Philox stream (nv.TRPO_TAG)"""
+    n = x.numel()
+    _vec(x, "x", n), _vec(mask, "mask", n), _chk(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    check(nv.lib().cstr_trpo_x0_f32(ptr(x), ptr(mask), C.c_int64(n), C.c_float(float(scale)), ptr(rng_ctl), stream_ptr()), "cstr_trpo_x0_f32")

@@ -20,6 +20,7 @@
 namespace {
 
 constexpr float LOG_SQRT_2PI = 0.918938533204672742f;  // math.log(math.sqrt(2 * math.pi)) (torch Normal.log_prob)
+constexpr double LOG_SQRT_2PI_F64 = 0.918938533204672742;  // rounds to LOG_SQRT_2PI
 constexpr float HALF_LOG_2PI_E = 1.418938533204672742f;  // 0.5 + 0.5 * math.log(2 * math.pi) (torch Normal.entropy)
 constexpr int WS_PART0 = 8;    // workspace word of the first partial (word 0: the ticket; 64-byte offset keeps it on its own line)
 constexpr int WS_STRIDE = 8;   // partial words per workgroup of the PPO / A2C loss launches (8 + 64 * 8 words fit CSTR_PPO_WS_WORDS)
@@ -50,13 +51,14 @@ template <int W> __device__ __forceinline__ void store_row(float *p, const float
 
 // distributions.py DiagGaussianDistribution.log_prob = sum over the action dimensions of torch's Normal.log_prob:
 // -((a - mu)^2) / (2 sigma^2) - log(sigma) - log(sqrt(2 pi)), sigma = exp(log_std)
-template <int A> __device__ __forceinline__ float diag_log_prob(const float (&act)[A], const float (&mu)[A], const float (&sig)[A])
+// T: float (every rollout head and loss launch) or double (cstr_trpo.hip, whose batch scalars are checked against float64 statements)
+template <int A, typename T = float> __device__ __forceinline__ T diag_log_prob(const T (&act)[A], const T (&mu)[A], const T (&sig)[A])
 {
-    float lp = 0.0f;
+    T lp = (T)0;
 #pragma unroll
     for (int k = 0; k < A; ++k) {
-        const float d = act[k] - mu[k];
-        lp += (-(d * d) / (2.0f * (sig[k] * sig[k])) - logf(sig[k])) - LOG_SQRT_2PI;
+        const T d = act[k] - mu[k];
+        lp += (-(d * d) / ((T)2 * (sig[k] * sig[k])) - log(sig[k])) - (T)LOG_SQRT_2PI_F64;
     }
     return lp;
 }
@@ -97,17 +99,19 @@ __device__ __forceinline__ double consume_f64(unsigned long long *w)
 // Mean and unbiased standard deviation (+ 1e-8) of the advantages over the whole minibatch (ppo.py:219, a2c.py:156): every workgroup
 // computes them itself, in the same order. The caller owns the guard: PPO skips the call for a single row (ppo.py:217), A2C has no
 // such guard (a2c.py:155-156) and one row gives 0 / 0 = NaN, as torch.std of one element does.
-__device__ __forceinline__ void advantage_stats(const float *__restrict__ adv, const int64_t B, double *red, float &a_mean, float &a_den)
+// T: the type the statistics are formed and returned in, float (PPO, A2C) or double (cstr_trpo.hip).
+template <typename T = float>
+__device__ __forceinline__ void advantage_stats(const float *__restrict__ adv, const int64_t B, double *red, T &a_mean, T &a_den)
 {
     double s = 0.0;
     for (int64_t i = threadIdx.x; i < B; i += 256) s += (double)adv[i];
-    a_mean = (float)(block_sum_f64(s, red) / (double)B);
+    a_mean = (T)(block_sum_f64(s, red) / (double)B);
     double q = 0.0;
     for (int64_t i = threadIdx.x; i < B; i += 256) {
-        const float d = adv[i] - a_mean;
+        const T d = (T)adv[i] - a_mean;
         q += (double)(d * d);
     }
-    a_den = (float)sqrt(block_sum_f64(q, red) / (double)(B - 1)) + 1e-8f;
+    a_den = (T)sqrt(block_sum_f64(q, red) / (double)(B - 1)) + (T)1e-8;
 }
 
 // one row's share of the policy objective: the summands of slots SLOT_POLICY, SLOT_KL and SLOT_CLIPPED and d loss / d log_prob
