@@ -1218,6 +1218,70 @@ int cstr_qrdqn_loss_f32(const float *z, int64_t ldz, const float *z_next, int64_
                         float *loss_out, float *loss_sum, float *cur_out, float *target_out, int64_t *next_index_out, double *ws,
                         cstr_stream_t stream);
 
+/* ---- Prioritized experience replay on the replay ring (csrc/cstr_per.hip; Schaul et al. 2016, the proportional variant) --------------
+ * A radix-64 sum tree over C = rows * n_envs priorities, float64. Leaf row * n_envs + env belongs to ring slot (row, env) and holds
+ * p^alpha, or 0 for a slot never written. Level 0 is the C leaves; level l + 1 has ceil(n_l / 64) nodes, up to a single root (a tree
+ * always has at least one level above the leaves: 2 levels up to C = 64, 3 up to 64^2, 5 at C = 2^20). All levels lie in ONE
+ * allocation of `words` doubles, level l at offset[l] with count[l] nodes, each padded with zeros to a multiple of 64 (the caller
+ * allocates zeros; no launch writes the padding). cstr_per_tree_layout fills everything but `node` for a capacity; the launching entry
+ * points take a struct only if it equals that layout (CSTR_E_BADARG otherwise; capacity > CSTR_PER_MAX_CAPACITY: CSTR_E_UNSUPPORTED).
+ * A node is always RECOMPUTED as the sum of its 64 children, one per lane, by the xor butterfly 32, 16, .. 1 -- never adjusted, no
+ * float atomics: at rest the tree is a pure function of its leaves, and cstr_per_rebuild_f64 reproduces it bit for bit. Dependent
+ * levels are separated by a workgroup barrier inside one workgroup or by a launch boundary.
+ * per_ctl: uint64[CSTR_PER_CTL_WORDS] in HBM = { max_priority (the bits of a double; the caller starts it at 1.0: the RAW priority,
+ * not its alpha power), Philox seed, Philox offset, the sample launch's ticket (zero between launches), - }.
+ * Every entry point validates on the host without dereferencing device memory (NULL, sizes, alignment, outputs overlapping inputs or
+ * each other -> CSTR_E_BADARG; caps -> CSTR_E_UNSUPPORTED) and then only enqueues.
+ * cstr_per_rebuild_f64: every level from the leaves, one launch per level, a wave per node.
+ * cstr_per_add_f64 (one launch, one workgroup): runs BEHIND a launch that wrote a ring row and advanced ring_ctl; the row written is
+ *   (ring_ctl[0] - 1) mod rows. Its n_envs leaves become max_priority^alpha (pow in float64), then the ancestors are recomputed: the
+ *   leaves are contiguous, so each level's affected nodes are one range. rows * n_envs must equal the tree's capacity.
+ * cstr_per_sample_f32 (one launch, a wave per sample j < B): mass = (j + u_j) * total / B in float64, total = the root; u_j a float32
+ *   uniform in [0, 1), READ from u_in [B] when given and DRAWN otherwise: Philox4x32-10 keyed by per_ctl[1], counter (per_ctl[2] + j, 0,
+ *   0x9E7A11ED), word 0 as (word >> 8) * 2^-24; the last workgroup then advances per_ctl[2] by B. From the root down, the wave loads the
+ *   node's 64 children, forms their inclusive prefix over ascending lanes (offsets 1, 2, .. 32), takes the FIRST lane whose prefix
+ *   exceeds the mass, subtracts the prefix below it and descends; when rounding has left the mass at or beyond the node's sum it takes
+ *   the LAST lane whose child is non-zero, so a zero leaf is never returned while the tree holds a positive one. leaf_out[j] (int64) =
+ *   the leaf, prob_out[j] (double) = leaf / total, and the slot's five fields are gathered as cstr_replay_sample_mt19937_f32 writes them
+ *   (out_done = done * (1 - timeout)). The launch's last workgroup writes weight_out[j] = (float)((N P_j)^-beta / max_k (N P_k)^-beta),
+ *   float64 arithmetic, N = the filled slots by ring_ctl ({pos, full}), beta read from a DEVICE double (a replayed graph is fed a new
+ *   value). B <= CSTR_PER_MAX_BATCH (CSTR_E_UNSUPPORTED beyond); ring layouts as the uniform sampler's.
+ * cstr_per_update_f64 (one launch, one workgroup): leaf[leaf_idx[j]] = (|td_abs[j]| + min_priority)^alpha for j < B; of several j with
+ *   one leaf the LARGEST j wins (the sequential loop of the published implementations); a non-finite |td_abs[j]| stores the
+ *   max_priority the launch found, to its alpha power, and does not raise it; an index outside [0, C) is skipped. max_priority =
+ *   max(max_priority, max_j (|td_abs[j]| + min_priority)) over the finite j. Then the ancestors, level by level. alpha >= 0,
+ *   min_priority > 0 (CSTR_E_BADARG otherwise); B <= CSTR_PER_MAX_BATCH.
+ * cstr_dqn_loss_weighted_f32: cstr_dqn_loss_f32 (the same kernel body, a compile-time variant) with importance weights [batch]:
+ *   loss = mean_b w_b smooth_l1(d_b), g_q[b][index] = (w_b * clamp(d_b, -1, 1)) / batch (product and quotient in float64, rounded to
+ *   float32 once), and td_abs_out [batch] = |d_b|, d_b = cur - target. With w = 1 every output equals cstr_dqn_loss_f32's bit for bit
+ *   (a float32 quotient of two float32 values survives the detour through float64 unchanged). */
+#define CSTR_PER_MAX_LEVELS 6
+#define CSTR_PER_MAX_CAPACITY (1ll << 30)
+#define CSTR_PER_CTL_WORDS 8
+#define CSTR_PER_MAX_BATCH 1024
+typedef struct {
+    double *node;    /* level 0 (the leaves) first */
+    int64_t capacity;
+    int64_t words;   /* doubles in the allocation */
+    int32_t n_levels;
+    int32_t reserved;
+    int64_t offset[CSTR_PER_MAX_LEVELS];
+    int64_t count[CSTR_PER_MAX_LEVELS];
+} cstr_per_tree_t;
+int cstr_per_tree_layout(int64_t capacity, cstr_per_tree_t *tree);
+int cstr_per_rebuild_f64(const cstr_per_tree_t *tree, cstr_stream_t stream);
+int cstr_per_add_f64(const cstr_per_tree_t *tree, const int64_t *ring_ctl, int64_t rows, int64_t n_envs, const uint64_t *per_ctl,
+                     double alpha, cstr_stream_t stream);
+int cstr_per_sample_f32(const cstr_ring_t *ring, const int64_t *ring_ctl, const cstr_per_tree_t *tree, uint64_t *per_ctl,
+                        const double *beta, const float *u_in, int64_t batch, float *out_obs, float *out_act, float *out_next_obs,
+                        float *out_done, float *out_rew, int64_t *leaf_out, double *prob_out, float *weight_out, cstr_stream_t stream);
+int cstr_per_update_f64(const cstr_per_tree_t *tree, uint64_t *per_ctl, const int64_t *leaf_idx, const float *td_abs, int64_t batch,
+                        double alpha, double min_priority, cstr_stream_t stream);
+int cstr_dqn_loss_weighted_f32(const float *q, int64_t ldq, const float *next_q, int64_t ldn, const float *valve, const float *reward,
+                               const float *done, const float *weights, float gamma, int64_t batch, int n_actions, int levels, float *g_q,
+                               float *loss_out, float *loss_sum, float *cur_q_out, float *target_out, float *td_abs_out,
+                               uint64_t *workspace, cstr_stream_t stream);
+
 /* ---- Categorical head of PPO / A2C on the discrete valve face (core/common/distributions.py:263-311, core/ppo/ppo.py:213-264,
  * core/a2c/a2c.py:150-171) ---------------------------------------------------------------------------------------------------------
  * Same conventions as the PPO block: f32 data, host-side validation (NULL, non-positive sizes, misaligned or overlapping rows ->

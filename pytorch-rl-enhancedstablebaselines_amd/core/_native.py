@@ -36,6 +36,9 @@ TRPO_HEAD_GAUSSIAN, TRPO_HEAD_CATEGORICAL, TRPO_HEAD_MULTICATEGORICAL = 0, 1, 2
 TRPO_MAX_LOGITS, TRPO_CTL_WORDS, TRPO_MAX_VECTOR, TRPO_TAG = 64, 16, 1 << 24, 0x7290C6A5
 TRPO_CTL = dict(rr=0, alpha=1, beta=2, pap=3, done=4, iters=5, sfs=6, step=7, coeff=8, objective=9, kl=10, ls_objective=11, ls_kl=12)
 TRPO_CG_INIT, TRPO_CG_STEP, TRPO_CG_FINISH = 0, 1, 2
+# prioritized replay (csrc/cstr_per.hip): CSTR_PER_*; the words of per_ctl; counter word 3 of the sampler's stratum draws
+PER_MAX_LEVELS, PER_MAX_CAPACITY, PER_CTL_WORDS, PER_MAX_BATCH, PER_TAG = 6, 1 << 30, 8, 1024, 0x9E7A11ED
+PER_CTL = dict(max_priority=0, seed=1, offset=2, ticket=3)
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -68,6 +71,7 @@ SYMBOLS = (
     "cstr_ars_supported", "cstr_ars_population_f32", "cstr_ars_update_f32",
     "cstr_linear_tangent_fwd_f32", "cstr_trpo_objective_f32", "cstr_trpo_fisher_head_f32", "cstr_trpo_cg_step_f32", "cstr_trpo_apply_step_f32",
     "cstr_trpo_value_loss_f32", "cstr_trpo_x0_f32",
+    "cstr_per_tree_layout", "cstr_per_rebuild_f64", "cstr_per_add_f64", "cstr_per_sample_f32", "cstr_per_update_f64", "cstr_dqn_loss_weighted_f32",
 )
 
 
@@ -235,6 +239,12 @@ class TrpoObjective(C.Structure):
                 ("head", C.c_int32), ("k0", C.c_int32), ("k1", C.c_int32), ("normalize_advantage", C.c_int32), ("line_search", C.c_int32),
                 ("reserved", C.c_int32), ("target_kl", C.c_double), ("shrink", C.c_double), ("g_dist", C.c_void_p), ("g_log_std", C.c_void_p),
                 ("scalars_out", C.c_void_p), ("ctl", C.c_void_p), ("accepted", C.c_void_p)]
+
+
+class PerTree(C.Structure):
+    """cstr_per_tree_t"""
+    _fields_ = [("node", C.c_void_p), ("capacity", C.c_int64), ("words", C.c_int64), ("n_levels", C.c_int32), ("reserved", C.c_int32),
+                ("offset", C.c_int64 * PER_MAX_LEVELS), ("count", C.c_int64 * PER_MAX_LEVELS)]
 
 
 class NativeError(RuntimeError):

@@ -8,6 +8,9 @@
     stream -- bit-identical to the reference's `batch_inds` / `env_indices` -- and gathers the five
     fields in the same launch.
 
+`PrioritizedReplayBuffer` is that buffer with proportional prioritized sampling (Schaul et al. 2016): a radix-64 sum tree over the ring's
+slots in HBM, kept by one launch behind every add and one behind every gradient step; a sample is one launch (csrc/cstr_per.hip).
+
 `RolloutBuffer` (reference: core/common/buffers.py:343-521) is the on-policy counterpart: SoA in HBM with the reference's array names
 and `[T, N, ...]` shapes, `add` one launch at a device-resident position, GAE one launch, minibatches gathered by the host-drawn
 permutation (the reference's `np.random.permutation` stream), copied to the device once per epoch.
@@ -23,7 +26,7 @@ import torch as th
 
 from core.common import hip_ops, legacy_rng
 from core.common.spaces import as_box, as_discrete, as_multi_discrete, get_action_dim, get_obs_shape
-from core.common.type_aliases import GoalRolloutBufferSamples, ReplayBufferSamples, RolloutBufferSamples
+from core.common.type_aliases import GoalRolloutBufferSamples, PrioritizedReplayBufferSamples, ReplayBufferSamples, RolloutBufferSamples
 from core.common.utils import get_device
 
 
@@ -275,6 +278,169 @@ class ReplayBuffer(BaseBuffer):
         bi = th.empty(batch_size, dtype=th.int64, device=self.device)
         ei = th.empty(batch_size, dtype=th.int64, device=self.device)
         return self.sample_into(self.alloc_batch(batch_size), bi, ei), bi, ei
+
+
+class PrioritizedReplayBuffer(ReplayBuffer):
+    """Proportional prioritized experience replay (Schaul et al. 2016) over the HBM ring: P(i) = p_i^alpha / sum_k p_k^alpha, importance
+    weights w_i = (N P(i))^-beta / max_j w_j, N = the filled slots. The priorities live in a radix-64 sum tree of float64 in HBM
+    (hip_ops.DevicePerTree): leaf row * n_envs + env belongs to ring slot (row, env). A new row enters with the largest priority seen so
+    far (1.0 at the start); `update_priorities` stores (|td| + min_priority)^alpha for the sampled leaves. A batch is B stratified draws:
+    the j-th from the j-th of B equal slices of the total mass.
+
+    `add` / `note_fused_add` are followed by the add launch, `sample*` return PrioritizedReplayBufferSamples (the five fields, `weights`
+    [B, 1], `leaf_indices` [B]); at most hip_ops' PER_MAX_BATCH = 1024 rows per batch. The strata's uniforms come from the buffer's own
+    Philox stream (`seed_strata`), not from the legacy MT19937 stream the uniform sampler mirrors. Packed and pre-drawn batches (the
+    continuous algorithms' critic-input rows) are not built: those methods raise.
+
+    :param alpha: how much prioritisation is used (0: uniform), >= 0
+    :param beta: importance-sampling exponent at the start, in [0, 1]; `final_beta` the value the owner anneals it to (`set_beta`)
+    :param min_priority: added to |td| so that no sampled slot ever gets priority 0, > 0
+    """
+
+    def __init__(self, buffer_size: int, observation_space, action_space, device: Union[th.device, str] = "auto", n_envs: int = 1,
+                 optimize_memory_usage: bool = False, handle_timeout_termination: bool = True, sampler_stream: Optional[th.Tensor] = None,
+                 alpha: float = 0.6, beta: float = 0.4, final_beta: float = 1.0, min_priority: float = 1e-6):
+        self._check_hyper(alpha, beta, final_beta, min_priority)
+        super().__init__(buffer_size, observation_space, action_space, device, n_envs=n_envs, optimize_memory_usage=optimize_memory_usage,
+                         handle_timeout_termination=handle_timeout_termination, sampler_stream=sampler_stream)
+        self.alpha, self.beta, self.final_beta, self.min_priority = float(alpha), float(beta), float(final_beta), float(min_priority)
+        self._make_tree()
+
+    @staticmethod
+    def _check_hyper(alpha: float, beta: float, final_beta: float, min_priority: float) -> None:
+        if not (alpha >= 0 and np.isfinite(alpha)):
+            raise ValueError(f"PrioritizedReplayBuffer: alpha must be >= 0, got {alpha}")
+        if not (0 <= beta <= 1 and 0 <= final_beta <= 1):
+            raise ValueError(f"PrioritizedReplayBuffer: beta and final_beta must lie in [0, 1], got {beta} and {final_beta}")
+        if not (min_priority > 0 and np.isfinite(min_priority)):
+            raise ValueError(f"PrioritizedReplayBuffer: min_priority must be > 0, got {min_priority}")
+
+    def _make_tree(self, seed: int = 0) -> None:
+        with th.cuda.device(self.device):
+            self.tree = hip_ops.DevicePerTree(self.buffer_size, self.n_envs, self.device, seed)
+        self._beta_dev = th.full((1,), self.beta, dtype=th.float64, device=self.device)  # the sample launch reads beta from HBM
+        self._beta_now = self.beta
+        self._prob: dict = {}  # batch size -> the sample launch's float64 [B] of probabilities
+
+    # ---- what the tree exposes ---------------------------------------------------------------------------
+    @property
+    def priorities(self) -> th.Tensor:
+        """the leaves, p^alpha per ring slot (0: never written): float64 [rows, n_envs], a view"""
+        return self.tree.levels[0].view(self.buffer_size, self.n_envs)
+
+    @property
+    def tree_levels(self) -> list:
+        """the per-level device tensors, the leaves first, the root last"""
+        return self.tree.levels
+
+    @property
+    def max_priority(self) -> float:
+        return float(self.tree.max_priority)
+
+    def seed_strata(self, seed: int) -> None:
+        """restart the Philox stream the strata's uniforms are drawn from"""
+        self.tree.ctl[1:3].copy_(th.tensor([int(seed) & 0x7FFFFFFFFFFFFFFF, 0], dtype=th.int64))
+
+    def set_beta(self, value: float) -> None:
+        """the importance-sampling exponent of the coming samples: one asynchronous fill, and only when the value changes"""
+        value = float(value)
+        if not 0 <= value <= 1:
+            raise ValueError(f"beta must lie in [0, 1], got {value}")
+        if value != self._beta_now:
+            self._beta_dev.fill_(value)
+            self._beta_now = value
+
+    # ---- pickling: the ring's form plus the leaves and max_priority; the upper levels are rebuilt ------------------------
+    def __getstate__(self) -> dict:
+        st = super().__getstate__()
+        st.update(alpha=self.alpha, beta=self.beta, final_beta=self.final_beta, min_priority=self.min_priority, beta_now=self._beta_now,
+                  priorities=self.priorities.cpu().numpy(), max_priority=self.max_priority, strata_stream=self.tree.ctl[1:3].cpu().numpy())
+        return st
+
+    def __setstate__(self, st: dict) -> None:
+        super().__setstate__(st)
+        self.alpha, self.beta, self.final_beta, self.min_priority = st["alpha"], st["beta"], st["final_beta"], st["min_priority"]
+        self._make_tree()
+        self.set_beta(st["beta_now"])
+        self.tree.ctl[1:3].copy_(th.from_numpy(np.ascontiguousarray(st["strata_stream"], dtype=np.int64)))
+        self._load_priorities(st["priorities"], st["max_priority"])
+
+    def _load_priorities(self, leaves, max_priority: float) -> None:
+        self.priorities.copy_(th.from_numpy(np.ascontiguousarray(leaves, dtype=np.float64)).reshape(self.buffer_size, self.n_envs))
+        self.tree.max_priority.fill_(float(max_priority))
+        with th.cuda.device(self.device):
+            hip_ops.per_rebuild(self.tree)
+
+    @classmethod
+    def from_arrays(cls, *args, alpha: float = 0.6, beta: float = 0.4, final_beta: float = 1.0, min_priority: float = 1e-6,
+                    **kwargs) -> "PrioritizedReplayBuffer":
+        """ReplayBuffer.from_arrays with this class's own arguments; every filled slot starts at the initial priority 1"""
+        cls._check_hyper(alpha, beta, final_beta, min_priority)
+        rb = super().from_arrays(*args, **kwargs)
+        rb.alpha, rb.beta, rb.final_beta, rb.min_priority = float(alpha), float(beta), float(final_beta), float(min_priority)
+        rb.set_beta(rb.beta)
+        leaves = np.zeros((rb.buffer_size, rb.n_envs))
+        leaves[:rb.size()] = 1.0
+        rb._load_priorities(leaves, 1.0)
+        return rb
+
+    def reset(self) -> None:
+        super().reset()
+        self.tree.node.zero_()
+        self.tree.max_priority.fill_(1.0)
+
+    # ---- add ---------------------------------------------------------------------------------------------
+    def _add_launch(self) -> None:
+        """the row the launch in front wrote enters the tree at max_priority^alpha"""
+        with th.cuda.device(self.device):
+            hip_ops.per_add(self.tree, self.ring, self.alpha)
+
+    def add(self, obs, next_obs, action, reward, done, infos: Optional[list]) -> None:
+        super().add(obs, next_obs, action, reward, done, infos)
+        self._add_launch()
+
+    def note_fused_add(self, launch: bool = True) -> None:
+        """`launch=False`: the add launch was recorded into a replayed graph behind the collect launch; only the host mirror moves"""
+        super().note_fused_add()
+        if launch:
+            self._add_launch()
+
+    # ---- sample ------------------------------------------------------------------------------------------
+    def alloc_batch(self, batch_size: int) -> PrioritizedReplayBufferSamples:
+        b = super().alloc_batch(batch_size)
+        return PrioritizedReplayBufferSamples(*b, th.empty(batch_size, 1, dtype=th.float32, device=self.device),
+                                              th.empty(batch_size, dtype=th.int64, device=self.device))
+
+    def sample_into(self, out: PrioritizedReplayBufferSamples, row_idx=None, env_idx=None, env=None, u=None) -> PrioritizedReplayBufferSamples:
+        """`sample` into caller-owned (static, graph-capturable) tensors. `u` [B] float32 in [0, 1): the strata's uniforms (teacher
+        forcing); drawn on the device otherwise. row_idx / env_idx (optional, int64 [B]) receive leaf // n_envs and leaf % n_envs."""
+        if self.size() == 0:
+            raise ValueError("cannot sample from an empty PrioritizedReplayBuffer")
+        batch = out.observations.shape[0]
+        prob = self._prob.get(batch)
+        if prob is None or prob.device != self.tree.node.device:
+            prob = self._prob[batch] = th.empty(batch, dtype=th.float64, device=self.device)
+        with th.cuda.device(self.device):
+            hip_ops.per_sample(self.ring, self.tree, self._beta_dev, batch, out.observations, out.actions, out.next_observations, out.dones,
+                               out.rewards, out.leaf_indices, prob, out.weights, u=u)
+            if row_idx is not None:
+                th.div(out.leaf_indices, self.n_envs, rounding_mode="floor", out=row_idx)
+            if env_idx is not None:
+                th.remainder(out.leaf_indices, self.n_envs, out=env_idx)
+        env = self.normalizer if env is None else env
+        if env is not None:
+            env.normalize_batch_(out.observations, out.next_observations, out.rewards)
+        return out
+
+    def update_priorities(self, leaf_indices: th.Tensor, td_abs: th.Tensor) -> None:
+        """new priorities (|td| + min_priority) for the sampled leaves, one launch: leaf_indices int64 [B], td_abs float32 [B] or [B, 1]"""
+        with th.cuda.device(self.device):
+            hip_ops.per_update(self.tree, leaf_indices, td_abs, self.alpha, self.min_priority)
+
+    def _not_built(self, *_args, **_kwargs):
+        raise NotImplementedError("PrioritizedReplayBuffer: packed and pre-drawn batches are not built (sample / sample_into only)")
+
+    alloc_packed_batch = sample_packed_into = predraw_indices = note_predrawn = take_predrawn = _not_built
 
 
 class PackedBatch:

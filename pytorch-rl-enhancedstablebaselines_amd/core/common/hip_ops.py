@@ -1964,9 +1964,11 @@ def dqn_act(q, levels: int, mode: int, valve_out, index_out=None, eps=None, flag
 
 
 def dqn_loss(q, next_q, valve, reward, done, gamma: float, levels: int, g_q, loss_out, workspace, loss_sum=None, cur_q_out=None,
-             target_out=None):
+             target_out=None, weights=None, td_abs_out=None):
     """dqn.py:195-212 in one launch: target = reward + ((1 - done) * f32(gamma)) * max next_q, cur = q[b, index(valve[b])], loss_out =
-    mean Huber loss (beta 1), g_q = d loss / d q (q's shape and row stride). c_float rounds gamma."""
+    mean Huber loss (beta 1), g_q = d loss / d q (q's shape and row stride). c_float rounds gamma. With `weights` [B] (prioritized
+    replay; `td_abs_out` [B] goes with them) the weighted variant runs (cstr_dqn_loss_weighted_f32): loss = mean w * Huber, g_q carries
+    w, td_abs_out = |cur - target|."""
     b, m = q.shape
     ldq = _rows(q, "q", b, m)
     ldn = _rows(next_q, "next_q", b, m)
@@ -1981,9 +1983,85 @@ def dqn_loss(q, next_q, valve, reward, done, gamma: float, levels: int, g_q, los
     for t, nm in ((cur_q_out, "cur_q_out"), (target_out, "target_out")):
         if t is not None:
             _vec(t, nm, b)
-    check(nv.lib().cstr_dqn_loss_f32(ptr(q), C.c_int64(ldq), ptr(next_q), C.c_int64(ldn), ptr(valve), ptr(reward), ptr(done), C.c_float(gamma),
-                                     C.c_int64(b), C.c_int(m), C.c_int(levels), ptr(g_q), ptr(loss_out), ptr(loss_sum), ptr(cur_q_out),
-                                     ptr(target_out), ptr(workspace), stream_ptr()), "cstr_dqn_loss_f32")
+    if (weights is None) != (td_abs_out is None):
+        raise ValueError("weights and td_abs_out go together")
+    if weights is None:
+        check(nv.lib().cstr_dqn_loss_f32(ptr(q), C.c_int64(ldq), ptr(next_q), C.c_int64(ldn), ptr(valve), ptr(reward), ptr(done), C.c_float(gamma),
+                                         C.c_int64(b), C.c_int(m), C.c_int(levels), ptr(g_q), ptr(loss_out), ptr(loss_sum), ptr(cur_q_out),
+                                         ptr(target_out), ptr(workspace), stream_ptr()), "cstr_dqn_loss_f32")
+        return
+    _vec(weights, "weights", b), _vec(td_abs_out, "td_abs_out", b)
+    check(nv.lib().cstr_dqn_loss_weighted_f32(ptr(q), C.c_int64(ldq), ptr(next_q), C.c_int64(ldn), ptr(valve), ptr(reward), ptr(done),
+                                              ptr(weights), C.c_float(gamma), C.c_int64(b), C.c_int(m), C.c_int(levels), ptr(g_q),
+                                              ptr(loss_out), ptr(loss_sum), ptr(cur_q_out), ptr(target_out), ptr(td_abs_out), ptr(workspace),
+                                              stream_ptr()), "cstr_dqn_loss_weighted_f32")
+
+
+# ---- Prioritized experience replay: the radix-64 sum tree over the ring's slots (csrc/cstr_per.hip) ---------------------------------
+class DevicePerTree:
+    """cstr_per_tree_t + per_ctl over torch tensors (HBM) for a ring of `rows` x `n_envs` slots. `node`: every level in one float64
+    allocation, zeros (the padding stays zero); `levels[l]`: the count[l] nodes of level l as a view, level 0 = the leaves;
+    `ctl`: int64 [PER_CTL_WORDS], word 0 the bits of max_priority (1.0), words 1 / 2 the Philox seed / offset of the stratum draws."""
+
+    def __init__(self, rows: int, n_envs: int, device, seed: int = 0):
+        self.rows, self.n_envs = int(rows), int(n_envs)
+        self.c = nv.PerTree()
+        check(nv.lib().cstr_per_tree_layout(C.c_int64(self.rows * self.n_envs), C.byref(self.c)), "cstr_per_tree_layout")
+        self.node = th.zeros(self.c.words, dtype=th.float64, device=device)
+        self.c.node = self.node.data_ptr()
+        self.levels = [self.node[self.c.offset[l]:self.c.offset[l] + self.c.count[l]] for l in range(self.c.n_levels)]
+        self.ctl = th.zeros(nv.PER_CTL_WORDS, dtype=th.int64, device=device)
+        self.ctl[nv.PER_CTL["seed"]] = int(seed) & 0x7FFFFFFFFFFFFFFF
+        self.max_priority.fill_(1.0)
+
+    @property
+    def max_priority(self) -> th.Tensor:
+        """the raw max_priority: a float64 view of per_ctl's word 0"""
+        return self.ctl[:1].view(th.float64)
+
+    @property
+    def root(self) -> th.Tensor:
+        return self.levels[-1]
+
+
+def per_rebuild(tree: DevicePerTree):
+    """every level of the tree from its leaves (after the leaves were written from outside): one launch per level"""
+    check(nv.lib().cstr_per_rebuild_f64(C.byref(tree.c), stream_ptr()), "cstr_per_rebuild_f64")
+
+
+def per_add(tree: DevicePerTree, ring: DeviceRing, alpha: float):
+    """behind a launch that wrote a ring row and advanced ring.ctl: that row's leaves = max_priority^alpha, ancestors recomputed"""
+    check(nv.lib().cstr_per_add_f64(C.byref(tree.c), ptr(ring.ctl), C.c_int64(ring.rows), C.c_int64(ring.n_envs), ptr(tree.ctl),
+                                    C.c_double(alpha), stream_ptr()), "cstr_per_add_f64")
+
+
+def per_sample(ring: DeviceRing, tree: DevicePerTree, beta, batch: int, out_obs, out_act, out_next_obs, out_done, out_rew, leaf_out, prob_out,
+               weight_out, u=None):
+    """B stratified proportional draws, the gather of their slots and the importance weights in one launch (cstr_per_sample_f32). `beta`:
+    a device double. `u` [B] float32 in [0, 1): the strata's uniforms, read when given and drawn from the tree's Philox stream otherwise.
+    leaf_out int64 [B], prob_out float64 [B] = leaf / total, weight_out float32 [B] (or [B, 1])."""
+    d, a = ring.obs_dim, ring.act_dim
+    _chk(beta, "beta", (1,), th.float64), _opt(u, "u", (batch,), th.float32)
+    _chk(out_obs, "out_obs", (batch, d), th.float32), _chk(out_next_obs, "out_next_obs", (batch, d), th.float32)
+    _chk(out_act, "out_act", (batch, a), th.float32)
+    _chk(out_done, "out_done", (batch, 1), th.float32), _chk(out_rew, "out_rew", (batch, 1), th.float32)
+    _chk(leaf_out, "leaf_out", (batch,), th.int64), _chk(prob_out, "prob_out", (batch,), th.float64), _vec(weight_out, "weight_out", batch)
+    if not 0 < batch <= nv.PER_MAX_BATCH:
+        raise ValueError(f"batch_size must be in [1, {nv.PER_MAX_BATCH}] for prioritized sampling, got {batch}")
+    check(nv.lib().cstr_per_sample_f32(C.byref(ring.c), ptr(ring.ctl), C.byref(tree.c), ptr(tree.ctl), ptr(beta), ptr(u), C.c_int64(batch),
+                                       ptr(out_obs), ptr(out_act), ptr(out_next_obs), ptr(out_done), ptr(out_rew), ptr(leaf_out),
+                                       ptr(prob_out), ptr(weight_out), stream_ptr()), "cstr_per_sample_f32")
+
+
+def per_update(tree: DevicePerTree, leaf_idx, td_abs, alpha: float, min_priority: float):
+    """leaf[leaf_idx[j]] = (|td_abs[j]| + min_priority)^alpha (the largest j of equal indices wins, a non-finite error stores
+    max_priority^alpha), max_priority follows, ancestors recomputed: one launch (cstr_per_update_f64)"""
+    b = leaf_idx.numel()
+    _chk(leaf_idx, "leaf_idx", (b,), th.int64), _vec(td_abs, "td_abs", b)
+    if not 0 < b <= nv.PER_MAX_BATCH:
+        raise ValueError(f"a priority update takes 1 .. {nv.PER_MAX_BATCH} indices, got {b}")
+    check(nv.lib().cstr_per_update_f64(C.byref(tree.c), ptr(tree.ctl), ptr(leaf_idx), ptr(td_abs), C.c_int64(b), C.c_double(alpha),
+                                       C.c_double(min_priority), stream_ptr()), "cstr_per_update_f64")
 
 
 # ---- QR-DQN on the discrete valve face: folded head, greedy target + gathers + quantile-Huber loss (csrc/cstr_qrdqn.hip) ------------

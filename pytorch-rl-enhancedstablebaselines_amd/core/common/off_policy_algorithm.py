@@ -18,7 +18,7 @@ import torch as th
 
 from core.common import blas, chain, fused, hip_ops
 from core.common.base_class import BaseAlgorithm
-from core.common.buffers import ReplayBuffer
+from core.common.buffers import PrioritizedReplayBuffer, ReplayBuffer
 from core.common.callbacks import BaseCallback, MaybeCallback
 from core.common.graph_replay import GraphReplay
 from core.common.logger import DeviceMean
@@ -40,6 +40,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
     packed_batch_with_pi = True             # the packed batch carries x_pi = (obs | pi(obs)) rows for the actor step
     chain_type: Optional[type] = None       # the row-chain form of this class's gradient step (core/common/chain.py)
     _single_step = False                    # this train() call is ONE gradient step whose loss kernels store the logged values
+    supports_prioritized_replay = False     # the class's loss launch takes importance weights and returns |td| (DQN)
 
     def __init__(self, policy, env, learning_rate, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = (1, "step"),
@@ -65,6 +66,8 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         self.action_noise = action_noise
         self.optimize_memory_usage = optimize_memory_usage
         self.replay_buffer: Optional[ReplayBuffer] = None
+        if isinstance(replay_buffer_class, type) and issubclass(replay_buffer_class, PrioritizedReplayBuffer) and not self.supports_prioritized_replay:
+            raise NotImplementedError(f"{type(self).__name__} does not take a PrioritizedReplayBuffer: its loss kernels have no importance weights (DQN does)")
         self.replay_buffer_class = replay_buffer_class
         self.replay_buffer_kwargs = replay_buffer_kwargs or {}
         self.train_freq = train_freq
@@ -148,6 +151,8 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
 
         self.replay_buffer = load_from_pkl(path, self.verbose)
         assert isinstance(self.replay_buffer, ReplayBuffer), "The replay buffer must inherit from ReplayBuffer class"
+        if isinstance(self.replay_buffer, PrioritizedReplayBuffer) and not self.supports_prioritized_replay:
+            raise NotImplementedError(f"{type(self).__name__} does not take a PrioritizedReplayBuffer")
         if isinstance(self.replay_buffer, HerReplayBuffer) != (self.goal_space is not None):
             raise ValueError("load_replay_buffer: a HerReplayBuffer belongs to a model of the goal face, and only to such a model")
         self.replay_buffer.to(self.device)  # :252-253
@@ -173,7 +178,8 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
     def _fast_path(self) -> bool:
         rb = self.replay_buffer
         env = self._denv
-        return (env is not None and type(rb) is ReplayBuffer and rb.n_envs == env.num_envs
+        stock = type(rb) is ReplayBuffer or (self.supports_prioritized_replay and type(rb) is PrioritizedReplayBuffer)
+        return (env is not None and stock and rb.n_envs == env.num_envs
                 and rb.obs_shape[0] == env.obs_dim and rb.action_dim == env.act_dim)
 
     # ---- learn ----------------------------------------------------------------------------------------------------

@@ -13,6 +13,18 @@ class ReplayBufferSamples(NamedTuple):
     rewards: th.Tensor
 
 
+class PrioritizedReplayBufferSamples(NamedTuple):
+    """What PrioritizedReplayBuffer samples: the five fields, the importance weights [B, 1] and the sum-tree leaf of every row [B]
+    (leaf = ring row * n_envs + env), which `update_priorities` takes back."""
+    observations: th.Tensor
+    actions: th.Tensor
+    next_observations: th.Tensor
+    dones: th.Tensor
+    rewards: th.Tensor
+    weights: th.Tensor
+    leaf_indices: th.Tensor
+
+
 class DictReplayBufferSamples(NamedTuple):
     """reference: core/common/type_aliases.py (DictReplayBufferSamples); observations / next_observations: {key: tensor}"""
     observations: dict

@@ -19,6 +19,15 @@ rate changes every vec-step, so it lives in HBM: before a replay the host evalua
 the values into a slot array; each recorded launch reads its own slot. Target updates are part of the body; the cache key carries the
 in-body positions at which `_n_calls` hits the update period.
 
+PRIORITIZED REPLAY (`replay_buffer_class=PrioritizedReplayBuffer`, core/common/buffers.py; Schaul et al. 2016, proportional). A gradient
+step is then: the prioritized sample launch (stratified draws on the sum tree, gather, importance weights w), the two forwards, the
+WEIGHTED loss launch (loss = mean w * Huber, the gradient carries w, |td| is kept), backward, clip, Adam, and the priority-update launch
+on the sampled leaves; every vec-step's collect launch is followed by the buffer's add launch. beta runs linearly from the buffer's
+`beta` to its `final_beta` over the training progress and is written to the HBM double the sample launch reads before each train() or
+replay. `per_uniform_queue` teacher-forces the strata's uniforms ([B] float32 per gradient step). A replayed graph holds one body
+(unroll 1): beta is one value per replay. `train/per_beta`, `train/per_weight_mean` (the last batch's) and `train/per_max_priority` are
+logged lazily. `_gradient_step_torch` carries the same weighted statement in torch.
+
 Not built (each raises where reachable): CnnPolicy / MultiInputPolicy, a VecNormalize-wrapped env, data-parallel training
 (world_size > 1), optimize_memory_usage, HER (core/her and the env's goal face serve SAC, TD3 and DDPG)."""
 import warnings
@@ -29,7 +38,7 @@ import torch as th
 from torch.nn import functional as F
 
 from core.common import fused, hip_ops
-from core.common.buffers import ReplayBuffer
+from core.common.buffers import PrioritizedReplayBuffer, ReplayBuffer
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
 from core.common.spaces import Discrete
@@ -41,9 +50,17 @@ from core.dqn.policies import MlpPolicy
 EPS_SLOTS = 1024  # exploration-rate slots in HBM: vec-steps one replayed graph may hold (train_freq * unroll)
 
 
+class BatchMean(DeviceMean):
+    """the mean of a device tensor's elements as they are when the logger writes; float() syncs"""
+
+    def __float__(self):
+        return float(self.total.mean())
+
+
 class DQN(OffPolicyAlgorithm):
     policy_aliases = {"MlpPolicy": MlpPolicy}
     train_batch_size = 100
+    supports_prioritized_replay = True
 
     def __init__(self, policy, env, learning_rate=1e-4, buffer_size: int = 1_000_000, learning_starts: int = 100, batch_size: int = 32,
                  tau: float = 1.0, gamma: float = 0.99, train_freq: Union[int, tuple] = 4, gradient_steps: int = 1,
@@ -79,6 +96,7 @@ class DQN(OffPolicyAlgorithm):
         # and uniforms [n_envs, 2] the next vec-steps' action selection reads instead of drawing
         self.batch_queue: List[tuple] = []
         self.uniform_queue: List[th.Tensor] = []
+        self.per_uniform_queue: List[th.Tensor] = []  # prioritized replay: the strata's uniforms [batch] of the next gradient steps
         if _init_setup_model:
             self._setup_model()
 
@@ -92,6 +110,7 @@ class DQN(OffPolicyAlgorithm):
             self.replay_buffer = self.replay_buffer_class(self.buffer_size, self.observation_space, env.valve_space, device=self.device,
                                                           n_envs=self.n_envs, optimize_memory_usage=self.optimize_memory_usage,
                                                           **self.replay_buffer_kwargs)
+        self._per = isinstance(self.replay_buffer, PrioritizedReplayBuffer)
         super()._setup_model()
         self.exploration_schedule = get_linear_fn(self.exploration_initial_eps, self.exploration_final_eps, self.exploration_fraction)
         if self.n_envs > 1 and self.n_envs > self.target_update_interval:
@@ -131,6 +150,8 @@ class DQN(OffPolicyAlgorithm):
         super()._reseed_device_rng(seed)
         if getattr(self, "_rng_ctl", None) is None:  # the exploration stream follows the seed from the start
             self._rng_ctl = hip_ops.new_rng_ctl(seed, self.device)
+        if getattr(self, "_per", False):  # ... and so does the stream of the prioritized sampler's strata
+            self.replay_buffer.seed_strata(seed)
 
     # ---- action selection -----------------------------------------------------------------------------------------
     def _q_values(self, obs: th.Tensor) -> th.Tensor:
@@ -228,9 +249,13 @@ class DQN(OffPolicyAlgorithm):
         super()._alloc_step_tensors(batch_size)
         e = lambda *s: th.empty(*s, dtype=th.float32, device=self.device)  # noqa: E731
         self._g_q, self._cur_q = e(batch_size, int(self.action_space.n)), e(batch_size, 1)
+        self._td_abs = e(batch_size)  # |current - target| per row: the prioritized buffer's new priorities
 
     def _train_host_pre(self) -> None:
         self._update_learning_rate(self.policy.optimizer)
+        if self._per:  # beta, linear in the training progress, into the HBM double the sample launch reads
+            rb = self.replay_buffer
+            rb.set_beta(rb.beta + (rb.final_beta - rb.beta) * min(max(1.0 - self._current_progress_remaining, 0.0), 1.0))
 
     def _graph_host_pre(self) -> None:
         """A replayed body trains AFTER its train_freq vec-steps: the learning-rate schedule sees the progress train() would see then,
@@ -249,10 +274,21 @@ class DQN(OffPolicyAlgorithm):
         self._n_updates += gradient_steps
         self.logger.record("train/n_updates", self._n_updates, exclude="tensorboard")
         self.logger.record("train/loss", DeviceMean(self._loss_sums["loss"], gradient_steps))
+        if self._per and self._static_batch is not None:
+            rb = self.replay_buffer
+            self.logger.record("train/per_beta", rb._beta_now)
+            self.logger.record("train/per_weight_mean", BatchMean(self._static_batch.weights, 1))
+            self.logger.record("train/per_max_priority", DeviceMean(rb.tree.max_priority, 1))
 
     def _next_batch(self, batch_size: int):
         """(samples, batch_inds, env_indices): the next teacher-forced batch, else a sample of the ring"""
         rd = self._batch(batch_size)
+        if self._per:
+            if self.batch_queue:
+                raise ValueError("batch_queue teacher-forces whole batches; with a PrioritizedReplayBuffer force the draws (per_uniform_queue)")
+            u = self.per_uniform_queue.pop(0).to(self.device, th.float32).reshape(-1).contiguous() if self.per_uniform_queue else None
+            bi, ei = ((th.empty(batch_size, dtype=th.int64, device=self.device) for _ in range(2)) if self.debug_capture else (None, None))
+            return self.replay_buffer.sample_into(rd, bi, ei, u=u), bi, ei
         if self.batch_queue:
             obs, index, next_obs, reward, done = self.batch_queue.pop(0)
             valve = decode_valve_index(np.asarray(index).reshape(-1), self.levels)
@@ -278,6 +314,8 @@ class DQN(OffPolicyAlgorithm):
                                                    loss=loss.detach().reshape(1).clone(), grad_norm=self._grad_norm.clone(),
                                                    batch_inds=None if bi is None else bi.clone(), env_indices=None if ei is None else ei.clone(),
                                                    **self._capture_extra()))
+                    if self._per:
+                        self.train_capture[-1].update(weights=rd.weights.reshape(-1).clone(), leaf_indices=rd.leaf_indices.clone())
 
     def _capture_extra(self) -> dict:
         """what a subclass's gradient step adds to a `train_capture` entry"""
@@ -290,12 +328,15 @@ class DQN(OffPolicyAlgorithm):
         q = self._fast_q(rd.observations, train_params=True)
         l_out, l_sum = self._loss_slot("loss")
         cap = self.debug_capture
+        per = dict(weights=rd.weights, td_abs_out=self._td_abs) if self._per else {}
         hip_ops.dqn_loss(q.detach(), next_q, rd.actions, rd.rewards, rd.dones, self.gamma, self.levels, self._g_q, l_out, self._ws,
-                         loss_sum=l_sum, cur_q_out=self._cur_q if cap else None, target_out=self._target_q if cap else None)
+                         loss_sum=l_sum, cur_q_out=self._cur_q if cap else None, target_out=self._target_q if cap else None, **per)
         with fused.deferred_weight_grads():
             th.autograd.backward([q], [self._g_q])
         hip_ops.grad_clip(self.policy.arena.grad, self.max_grad_norm, self._ws, self._grad_norm)
         self.policy.optimizer.step()
+        if self._per:
+            self.replay_buffer.update_priorities(rd.leaf_indices, self._td_abs)
         return self._cur_q, self._target_q, l_out
 
     def _gradient_step_torch(self, rd):
@@ -310,13 +351,19 @@ class DQN(OffPolicyAlgorithm):
             target_q_values = rd.rewards + (1 - rd.dones) * self.gamma * next_q_values
         current_q_values = self.q_net(rd.observations)
         current_q_values = th.gather(current_q_values, dim=1, index=index)
-        loss = F.smooth_l1_loss(current_q_values, target_q_values)
+        if self._per:  # importance-weighted Huber loss; |td| are the sampled slots' new priorities
+            loss = (rd.weights * F.smooth_l1_loss(current_q_values, target_q_values, reduction="none")).mean()
+            self._td_abs.copy_((current_q_values.detach() - target_q_values).abs().reshape(-1))
+        else:
+            loss = F.smooth_l1_loss(current_q_values, target_q_values)
         self._loss_sums["loss"] += loss.detach()
         self.policy.optimizer.zero_grad()
         loss.backward()
         norm = th.nn.utils.clip_grad_norm_(self.policy.parameters(), self.max_grad_norm)
         self._grad_norm.copy_(norm.detach().reshape(1))
         self.policy.optimizer.step()
+        if self._per:
+            self.replay_buffer.update_priorities(rd.leaf_indices, self._td_abs)
         return current_q_values, target_q_values, loss
 
     # ---- hipGraph replay: the hooks of core/common/graph_replay.py for a body of train_freq vec-steps ---------------------
@@ -332,7 +379,7 @@ class DQN(OffPolicyAlgorithm):
         tf = self.train_freq
         return (self._fast_path() and self._callback_allows_replay(callback) and tf.unit == TrainFrequencyUnit.STEP
                 and self.gradient_steps >= 1 and self.num_timesteps >= self.learning_starts and not self.debug_capture
-                and not self.batch_queue and not self.uniform_queue and tf.frequency * max(self.graph_unroll, 1) <= EPS_SLOTS)
+                and not self.batch_queue and not self.uniform_queue and not self.per_uniform_queue and tf.frequency * max(self.graph_unroll, 1) <= EPS_SLOTS)
 
     def _graph_phase(self) -> int:
         return sum(1 << k for k in self._update_positions(self._n_calls, self.train_freq.frequency))
@@ -340,7 +387,10 @@ class DQN(OffPolicyAlgorithm):
     def _graph_cache_key(self, unroll: int) -> tuple:
         tf = self.train_freq.frequency
         return (id(self._denv.coef), self.batch_size, self.gradient_steps, tf, self.faithful_quirks, self.fused_learner,
-                self._update_positions(self._n_calls, tf * unroll), unroll)
+                self._update_positions(self._n_calls, tf * unroll), self._per, unroll)
+
+    def _graph_unroll_now(self) -> int:
+        return 1 if self._per else super()._graph_unroll_now()  # beta is one value per replay
 
     def _graph_body(self) -> None:
         tf = self.train_freq.frequency
@@ -349,6 +399,8 @@ class DQN(OffPolicyAlgorithm):
         for k in range(tf):
             s = self._slot_base + k
             self._device_vec_step(self._eps_slots[s:s + 1])
+            if self._per:
+                self.replay_buffer._add_launch()  # note_fused_add's launch; the host mirror moves in _graph_host_bookkeeping
             if k in updates:
                 self._target_update()
         self.policy.set_training_mode(True)
@@ -361,7 +413,7 @@ class DQN(OffPolicyAlgorithm):
 
     def _graph_host_bookkeeping(self, log_interval) -> None:
         for _ in range(self.train_freq.frequency):
-            self.replay_buffer.note_fused_add()
+            self.replay_buffer.note_fused_add(**(dict(launch=False) if self._per else {}))
             self.num_timesteps += self.n_envs
             self._update_current_progress_remaining(self.num_timesteps, self._total_timesteps)
             self._n_calls += 1  # the host half of _on_step: the target update is a launch of the body

@@ -49,6 +49,7 @@ def quantile_huber_loss(current_quantiles: th.Tensor, target_quantiles: th.Tenso
 
 class QRDQN(DQN):
     policy_aliases = {"MlpPolicy": MlpPolicy}
+    supports_prioritized_replay = False  # the quantile-Huber loss launch takes no importance weights
 
     def __init__(self, policy, env, learning_rate=5e-5, buffer_size: int = 1_000_000, learning_starts: int = 100, batch_size: int = 32,
                  tau: float = 1.0, gamma: float = 0.99, train_freq: Union[int, tuple] = 4, gradient_steps: int = 1,

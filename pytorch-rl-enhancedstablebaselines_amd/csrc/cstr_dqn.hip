@@ -112,13 +112,16 @@ __global__ __launch_bounds__(64) void dqn_act_kernel(const float *__restrict__ q
     if (draw && last_block_ticket(reinterpret_cast<unsigned long long *>(rng_ctl + 2)) && threadIdx.x == 0) rng_ctl[1] = base + (uint64_t)n;
 }
 
-// dqn.py:195-212
+// dqn.py:195-212. WEIGHTED (prioritized replay, cstr_dqn_loss_weighted_f32): every row's Huber term and gradient carry the importance
+// weight w_b, and |d_b| goes to td_abs_out; without it `weights` and `td_abs_out` are never read and the arithmetic is the statement's.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void dqn_loss_kernel(const float *__restrict__ q, const int64_t ldq, const float *__restrict__ next_q,
                                                        const int64_t ldn, const float *__restrict__ valve, const float *__restrict__ reward,
                                                        const float *__restrict__ done, const float gamma, const int64_t B, const int M,
                                                        const int K, float *__restrict__ g_q, float *__restrict__ loss_out,
                                                        float *__restrict__ loss_sum, float *__restrict__ cur_q_out,
-                                                       float *__restrict__ target_out, unsigned long long *__restrict__ ws)
+                                                       float *__restrict__ target_out, unsigned long long *__restrict__ ws,
+                                                       const float *__restrict__ weights, float *__restrict__ td_abs_out)
 {
     __shared__ double red[256];
     __shared__ double tot[1];
@@ -132,10 +135,18 @@ __global__ __launch_bounds__(256) void dqn_loss_kernel(const float *__restrict__
         const int a = level_of(v.x, K) * K + level_of(v.y, K);     // in [0, M) by construction
         const float cur = q[b * ldq + a];                           // th.gather(current_q_values, 1, actions)
         const float d = cur - target, z = fabsf(d);
-        acc[0] += (double)(z < 1.0f ? (0.5f * z) * z : z - 0.5f);      // smooth_l1_loss, beta = 1 (a NaN takes the second branch)
+        const float h = z < 1.0f ? (0.5f * z) * z : z - 0.5f;        // smooth_l1_loss, beta = 1 (a NaN takes the second branch)
         float *g = g_q + b * ldq;
         for (int c = 0; c < M; ++c) g[c] = 0.0f;
-        g[a] = d != d ? d : fminf(fmaxf(d, -1.0f), 1.0f) / fB;      // d smooth_l1 / d cur = clamp(d, -1, 1), mean over B; a NaN stays one
+        if (WEIGHTED) {
+            const float w = weights[b];
+            acc[0] += (double)w * (double)h;  // the product and the quotient below are formed in f64 and rounded once: with w = 1
+            g[a] = d != d ? d : (float)(((double)w * (double)fminf(fmaxf(d, -1.0f), 1.0f)) / (double)fB);  // both are the f32 statement's bits
+            td_abs_out[b] = z;
+        } else {
+            acc[0] += (double)h;
+            g[a] = d != d ? d : fminf(fmaxf(d, -1.0f), 1.0f) / fB;  // d smooth_l1 / d cur = clamp(d, -1, 1), mean over B; a NaN stays one
+        }
         if (cur_q_out) cur_q_out[b] = cur;
         if (target_out) target_out[b] = target;
     }
@@ -195,30 +206,51 @@ extern "C" int cstr_dqn_act_f32(const float *q, int64_t ldq, int64_t n, int n_ac
     return (int)hipGetLastError();
 }
 
-extern "C" int cstr_dqn_loss_f32(const float *q, int64_t ldq, const float *next_q, int64_t ldn, const float *valve, const float *reward,
-                                 const float *done, float gamma, int64_t batch, int n_actions, int levels, float *g_q, float *loss_out,
-                                 float *loss_sum, float *cur_q_out, float *target_out, uint64_t *workspace, cstr_stream_t stream)
+// cstr_dqn_loss_f32 (weights, td_abs_out NULL) and cstr_dqn_loss_weighted_f32: validation and launch
+template <bool WEIGHTED>
+static int dqn_loss_launch(const float *q, int64_t ldq, const float *next_q, int64_t ldn, const float *valve, const float *reward,
+                           const float *done, const float *weights, float gamma, int64_t batch, int n_actions, int levels, float *g_q,
+                           float *loss_out, float *loss_sum, float *cur_q_out, float *target_out, float *td_abs_out, uint64_t *workspace,
+                           cstr_stream_t stream)
 {
     if (!q || !next_q || !valve || !reward || !done || !g_q || !loss_out || !workspace || batch <= 0 || n_actions <= 0 || levels <= 0 ||
         ldq < n_actions || ldn < n_actions || gamma != gamma)
         return CSTR_E_BADARG;
+    if (WEIGHTED && (!weights || !td_abs_out)) return CSTR_E_BADARG;
     const int rc = face_check(n_actions, levels);
     if (rc) return rc;
     if (batch > CSTR_PPO_MAX_ROWS) return CSTR_E_UNSUPPORTED;
     if (!aligned4(q) || !aligned4(next_q) || !aligned8(valve) || !aligned4(reward) || !aligned4(done) || !aligned4(g_q) || !aligned4(loss_out) ||
         (loss_sum && !aligned4(loss_sum)) || (cur_q_out && !aligned4(cur_q_out)) || (target_out && !aligned4(target_out)) ||
-        !aligned8(workspace))
+        !aligned8(workspace) || !aligned4(weights) || !aligned4(td_abs_out))
         return CSTR_E_BADARG;
     {
         const int64_t B = batch;
-        const Buf ins[5] = {{q, span(B, ldq, n_actions)}, {next_q, span(B, ldn, n_actions)}, {valve, 2 * B}, {reward, B}, {done, B}};
-        const Buf outs[6] = {{g_q, span(B, ldq, n_actions)}, {loss_out, 1}, {loss_sum, 1}, {cur_q_out, B}, {target_out, B},
-                             {workspace, 2 * CSTR_PPO_WS_WORDS}};
+        const Buf ins[6] = {{q, span(B, ldq, n_actions)}, {next_q, span(B, ldn, n_actions)}, {valve, 2 * B}, {reward, B}, {done, B}, {weights, B}};
+        const Buf outs[7] = {{g_q, span(B, ldq, n_actions)}, {loss_out, 1}, {loss_sum, 1}, {cur_q_out, B}, {target_out, B},
+                             {workspace, 2 * CSTR_PPO_WS_WORDS}, {td_abs_out, B}};
         if (outputs_overlap(ins, outs)) return CSTR_E_BADARG;
     }
     const unsigned grid = lane_grid(batch, 256, CSTR_PPO_MAX_BLOCKS);
-    dqn_loss_kernel<<<grid, 256, 0, (hipStream_t)stream>>>(q, ldq, next_q, ldn, valve, reward, done, gamma, batch, n_actions, levels, g_q,
-                                                          loss_out, loss_sum, cur_q_out, target_out,
-                                                          reinterpret_cast<unsigned long long *>(workspace));
+    dqn_loss_kernel<WEIGHTED><<<grid, 256, 0, (hipStream_t)stream>>>(q, ldq, next_q, ldn, valve, reward, done, gamma, batch, n_actions, levels,
+                                                                    g_q, loss_out, loss_sum, cur_q_out, target_out,
+                                                                    reinterpret_cast<unsigned long long *>(workspace), weights, td_abs_out);
     return (int)hipGetLastError();
+}
+
+extern "C" int cstr_dqn_loss_f32(const float *q, int64_t ldq, const float *next_q, int64_t ldn, const float *valve, const float *reward,
+                                 const float *done, float gamma, int64_t batch, int n_actions, int levels, float *g_q, float *loss_out,
+                                 float *loss_sum, float *cur_q_out, float *target_out, uint64_t *workspace, cstr_stream_t stream)
+{
+    return dqn_loss_launch<false>(q, ldq, next_q, ldn, valve, reward, done, nullptr, gamma, batch, n_actions, levels, g_q, loss_out, loss_sum,
+                                  cur_q_out, target_out, nullptr, workspace, stream);
+}
+
+extern "C" int cstr_dqn_loss_weighted_f32(const float *q, int64_t ldq, const float *next_q, int64_t ldn, const float *valve,
+                                          const float *reward, const float *done, const float *weights, float gamma, int64_t batch,
+                                          int n_actions, int levels, float *g_q, float *loss_out, float *loss_sum, float *cur_q_out,
+                                          float *target_out, float *td_abs_out, uint64_t *workspace, cstr_stream_t stream)
+{
+    return dqn_loss_launch<true>(q, ldq, next_q, ldn, valve, reward, done, weights, gamma, batch, n_actions, levels, g_q, loss_out, loss_sum,
+                                 cur_q_out, target_out, td_abs_out, workspace, stream);
 }
