@@ -1693,6 +1693,48 @@ int cstr_trpo_value_loss_f32(const float *values, const float *returns, int64_t 
  * rng_ctl[1] by (n + 1) / 2. CSTR_E_BADARG: NULL / misaligned pointers, n < 1, overlaps; CSTR_E_UNSUPPORTED: n > CSTR_TRPO_MAX_VECTOR. */
 int cstr_trpo_x0_f32(float *x, const float *mask, int64_t n, float scale, uint64_t *rng_ctl, cstr_stream_t stream);
 
+/* ---- layer-normalised, dropout-regularised critics (csrc/cstr_layernorm.hip; DroQ, Hiraoka et al. 2022) -------------------------------
+ * A hidden layer of a Q network as [Linear, Dropout(p), LayerNorm(n), act] (SBX's order; LayerNorm as torch's: eps 1e-5, affine, biased
+ * variance), for G stacked networks. All f32; a workgroup owns 16 rows of one network across all n columns, so n <= CSTR_LN_MAX_WIDTH.
+ * cstr_ln_supported: k >= 1, 1 <= n <= CSTR_LN_MAX_WIDTH, 0 <= p < 1, act CSTR_ACT_RELU or CSTR_ACT_TANH.
+ *
+ * Dropout: keep = u >= p, the kept values times 1 / (1 - p). p == 0: neither u_in nor rng_ctl. p > 0: exactly one of
+ *   u_in [G][m][n]: the uniforms are read;
+ *   rng_ctl [CSTR_RNG_CTL_WORDS] = { seed, pass counter, ticket, ... }: u = (word >> 8) * 2^-24 of Philox4x32-10 keyed by rng_ctl[0], counter
+ *     words (row, column / 4 | group << 8 | layer << 16, lo32(pass), CSTR_LN_TAG ^ hi32(pass)), word column & 3. The forward reads pass =
+ *     rng_ctl[1] on the device, stores it to pass_out[0] where given, and with advance != 0 its last workgroup sets rng_ctl[1] = pass + 1
+ *     (the launch that ends a pass of the network: every layer of the pass has then read the same counter). The backward is handed the
+ *     recorded word (pass_ctr) and regenerates the mask; rng_ctl is only read there.
+ *
+ * cstr_linear_ln_act_fwd_f32 (one launch): y = act(LN(drop(x w^T + bias)) * gamma + beta), xhat = the normalised value before the affine
+ *   map, rstd [G][m] = 1 / sqrt(var + eps). x [G][m][ldx >= k] groups x_group_stride floats apart (0: one input shared by all groups);
+ *   w [G][n][k], bias / gamma / beta [G][n], y / xhat [G][m][n], contiguous.
+ * cstr_ln_linear_bwd_input_f32: gz [G][m][n] = d(loss)/d(x w^T + bias) of THIS layer from gz_next [G][m][n_next] = the same quantity of
+ *   the layer that consumes y (w_next [G][n_next][n]; n_next == 1, the scalar Q head: gz_next = d(loss)/dq) and this layer's stored y,
+ *   xhat, rstd: g_ln = (gz_next w_next) act'(y); g_xhat = g_ln gamma; gz = rstd (g_xhat - mean(g_xhat) - xhat mean(g_xhat xhat)) keep /
+ *   (1 - p). With dgamma / dbeta [G][n] (both or neither, then with parts: float64 [G][ceil(m / 16)][2][n] scratch) a second launch
+ *   behind the same entry point leaves d gamma = sum_rows g_ln xhat and d beta = sum_rows g_ln there (overwritten), summed in float64 in
+ *   a fixed order. No float atomics: relaunching gives the same bits.
+ * cstr_ln_dropout_uniform_f32: u_out [G][m][n] = the uniforms a launch with these (rng_ctl, layer) draws at pass counter pass_ctr[0]
+ *   (NULL: rng_ctl[1]); nothing advances.
+ * CSTR_E_BADARG: NULL required pointers, sizes < 1, ldx < k, layer outside 0 .. 65535, p negative or NaN, u_in / rng_ctl not matching p,
+ *   the stream's backward without pass_ctr, one of dgamma / dbeta / parts without the others, a pointer off a 4-byte (rng_ctl, pass_*,
+ *   parts: 8-byte) boundary, an output overlapping an input or another output. CSTR_E_UNSUPPORTED: not cstr_ln_supported, G >
+ *   CSTR_MAX_ENS_CRITICS, m > 2^20, 2^31 or more elements in a tensor. */
+#define CSTR_LN_MAX_WIDTH 512
+#define CSTR_LN_TAG 0x1A7E2D0Bu
+int cstr_ln_supported(int64_t k, int64_t n, double p, int act);
+int cstr_linear_ln_act_fwd_f32(const float *x, int64_t x_group_stride, int64_t ldx, const float *w, const float *bias, const float *gamma,
+                               const float *beta, int act, double p, const float *u_in, uint64_t *rng_ctl, int advance, uint64_t *pass_out,
+                               int layer, float *y, float *xhat, float *rstd, int64_t groups, int64_t m, int64_t n, int64_t k,
+                               cstr_stream_t stream);
+int cstr_ln_linear_bwd_input_f32(const float *gz_next, const float *w_next, int64_t n_next, const float *y, const float *xhat,
+                                 const float *rstd, const float *gamma, int act, double p, const float *u_in, const uint64_t *rng_ctl,
+                                 const uint64_t *pass_ctr, int layer, float *gz, double *parts, float *dgamma, float *dbeta, int64_t groups,
+                                 int64_t m, int64_t n, cstr_stream_t stream);
+int cstr_ln_dropout_uniform_f32(float *u_out, const uint64_t *rng_ctl, const uint64_t *pass_ctr, int layer, int64_t groups, int64_t m,
+                                int64_t n, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

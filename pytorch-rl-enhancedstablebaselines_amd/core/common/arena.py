@@ -58,7 +58,7 @@ class ParamArena:
             for q in members:
                 self.offsets.append(off)
                 off += q.numel()
-            if len(members) > 1:
+            if id(members[0]) in in_group:  # (a group of one too: a single layer-normalised Q network's [1, ...] views)
                 self.group_spans[in_group[id(members[0])]] = (start, len(members), tuple(members[0].shape))
             off = -(-off // _ALIGN) * _ALIGN
         self.numel = max(off, _ALIGN)

@@ -39,9 +39,22 @@ class BaseAlgorithm:
             raise ValueError(f"{name} on the goal face does not run data-parallel (world_size = {self.world_size})")
         if self.use_sde:
             raise ValueError(f"{name} on the goal face does not support gSDE (use_sde=True)")
+        if self._wants_norm_critics():
+            raise ValueError(f"{name} on the goal face (HER) does not take layer_norm / dropout_rate critics")
         self.goal_space = env.observation_space
         one = np.ones(self.goal_space.flat_dim(), np.float32)
         self.observation_space = Box(-one, one, dtype=np.float32)
+
+    norm_critic_classes: tuple = ()  # SAC: ("SAC",), TD3: ("TD3",) -- the classes themselves, not their subclasses, take layer_norm / dropout_rate
+
+    def _wants_norm_critics(self) -> bool:
+        return bool(self.policy_kwargs.get("layer_norm")) or bool(self.policy_kwargs.get("dropout_rate"))
+
+    def _check_norm_critic_keys(self) -> None:
+        """policy_kwargs layer_norm / dropout_rate build LayerNorm / dropout critics for SAC and TD3 only (not their subclasses)"""
+        if ("layer_norm" in self.policy_kwargs or "dropout_rate" in self.policy_kwargs) and type(self).__name__ not in self.norm_critic_classes:
+            raise ValueError(f"{type(self).__name__} does not take policy_kwargs layer_norm / dropout_rate: layer-normalised, dropout-regularised "
+                             "critics are built for SAC and TD3")
 
     def _goal_face_policy_message(self, policy) -> str:
         """what a policy without the CombinedExtractor is told on a Dict observation space (reference: base_class.py:210)"""
@@ -51,13 +64,14 @@ class BaseAlgorithm:
                  tensorboard_log: Optional[str] = None, verbose: int = 0, device: Union[th.device, str] = "auto",
                  support_multi_env: bool = False, monitor_wrapper: bool = True, seed: Optional[int] = None,
                  use_sde: bool = False, sde_sample_freq: int = -1, supported_action_spaces: Optional[tuple] = None):
+        self.policy_kwargs = {} if policy_kwargs is None else policy_kwargs
+        self._check_norm_critic_keys()
         if isinstance(policy, str):
             self.policy_class = self._get_policy_from_name(policy)
         else:
             self.policy_class = policy
         self.device = get_device(device)
         self.verbose = verbose
-        self.policy_kwargs = {} if policy_kwargs is None else policy_kwargs
         self.num_timesteps = 0
         self._total_timesteps = 0
         self._num_timesteps_at_start = 0

@@ -1486,7 +1486,7 @@ class PerLayerTwinCritic:
             hip_ops.sac_actor_loss(log_prob, qs_pi[0], qs_pi[1], ent_coef, g_lp, gq[0], gq[1], loss_out, loss_sum)
         with _loss_root(root), deferred_weight_grads():
             if qs_pi.stacked is not None:
-                th.autograd.backward([log_prob, qs_pi.stacked], [g_lp, gq])
+                th.autograd.backward([log_prob, qs_pi.stacked], [g_lp, gq if gq.shape[0] == n else gq[:n]])  # (one stacked critic: [1, B, 1])
             else:
                 th.autograd.backward([log_prob, *qs_pi], [g_lp, *(gq[i] for i in range(n))])
 
@@ -1557,28 +1557,179 @@ class FastValuePair:
 
 def twin_groups(q_networks) -> list:
     """Arena groups that make `FastTwinCritic`'s stacked views possible: for every layer, the weights of all Q networks
-    back to back, then their biases. Empty for a single Q network or non-identical architectures."""
+    back to back, then their biases. Empty for a single Q network or non-identical architectures. Layer-normalised critics
+    (`FastLnCritic`) add, BEHIND those, per LayerNorm its weights (gamma) and then its biases (beta) of all Q networks, and are
+    grouped even when there is one network: the row-owning kernels read stacked [G, N] operands."""
     seqs = [[m for m in q if isinstance(m, nn.Linear)] for q in q_networks]
-    if len(seqs) < 2 or len({tuple((l.in_features, l.out_features) for l in sq) for sq in seqs}) != 1:
+    norms = [[m for m in q if isinstance(m, nn.LayerNorm)] for q in q_networks]
+    has_norms = bool(norms) and bool(norms[0])
+    if (len(seqs) < 2 and not has_norms) or len({tuple((l.in_features, l.out_features) for l in sq) for sq in seqs}) != 1:
         return []
     groups = []
     for li in range(len(seqs[0])):
         groups.append([sq[li].weight for sq in seqs])
         groups.append([sq[li].bias for sq in seqs])
+    if has_norms and len({len(nq) for nq in norms}) == 1:
+        for li in range(len(norms[0])):
+            groups.append([nq[li].weight for nq in norms])
+            groups.append([nq[li].bias for nq in norms])
     return groups
 
 
-def twin_stack(arena, first_group: int = 0, n_layers: Optional[int] = None):
+def twin_stack(arena, first_group: int = 0, n_layers: Optional[int] = None, n_norm: int = 0):
     """[(W [G,N,K], W.grad view | None, b [G,N], b.grad view | None)] per layer from an arena built with `twin_groups`
-    (`first_group` / `n_layers`: the slice of groups of one agent when several critics share an arena)."""
+    (`first_group` / `n_layers`: the slice of groups of one agent when several critics share an arena; `n_norm`: the LayerNorm
+    groups behind the Linear ones, see `norm_stack`)."""
     if n_layers is None:
-        n_layers = len(arena.group_spans) // 2
+        n_layers = (len(arena.group_spans) - 2 * n_norm) // 2
     out = []
     for li in range(n_layers):
         w, wg = arena.stacked(first_group + 2 * li)
         b, bg = arena.stacked(first_group + 2 * li + 1)
         out.append((w, wg, b.view(b.shape[0], -1), None if bg is None else bg.view(bg.shape[0], -1)))
     return out or None
+
+
+def norm_stack(arena, n_norm: int):
+    """[(gamma [G,N], gamma.grad view | None, beta [G,N], beta.grad view | None)] per LayerNorm: the last 2 * n_norm groups of `twin_groups`"""
+    first = len(arena.group_spans) - 2 * n_norm
+    return [arena.stacked(first + 2 * li) + arena.stacked(first + 2 * li + 1) for li in range(n_norm)]
+
+
+def ln_layers(q: nn.Sequential):
+    """([(Linear, dropout p, LayerNorm, act)] per hidden layer, head Linear) of a layer-normalised Q network
+    [Linear, (Dropout), LayerNorm, ReLU | Tanh] * n + [Linear(., 1)], or None for anything else."""
+    mods, hidden, i = list(q), [], 0
+    while i < len(mods) - 1:
+        lin, p = mods[i], 0.0
+        i += 1
+        if isinstance(mods[i], nn.Dropout):
+            p, i = float(mods[i].p), i + 1
+        if not (isinstance(lin, nn.Linear) and i + 1 < len(mods) and isinstance(mods[i], nn.LayerNorm) and type(mods[i + 1]) in (nn.ReLU, nn.Tanh)):
+            return None
+        ln = mods[i]
+        if not (ln.elementwise_affine and ln.bias is not None and tuple(ln.normalized_shape) == (lin.out_features,) and ln.eps == 1e-5
+                and lin.bias is not None):
+            return None
+        hidden.append((lin, p, ln, ACT_RELU if isinstance(mods[i + 1], nn.ReLU) else ACT_TANH))
+        i += 2
+    head = mods[-1] if mods else None
+    if not hidden or i != len(mods) - 1 or not isinstance(head, nn.Linear) or head.out_features != 1 or head.bias is None:
+        return None
+    return hidden, head
+
+
+class _LnCriticFn(th.autograd.Function):
+    """All G layer-normalised Q networks on one critic input: per hidden layer ONE launch forward (cstr_linear_ln_act_fwd_f32) and one
+    entry point backward (cstr_ln_linear_bwd_input_f32: this layer's gz from the consumer's gz and weights, d gamma / d beta), the scalar
+    head on the plain Linear kernel. Between the layers travels gz, the gradient w.r.t. a layer's pre-activation: a layer's backward
+    launch does its consumer's input-gradient GEMM itself, so the walk is one Function, not one per layer. dW / db run on the existing
+    weight-gradient launches from gz and the layer's input, the first layer's input gradient on cstr_linear_bwd_input_f32."""
+
+    @staticmethod
+    def forward(ctx, x, critic, g: int, train_params: bool, *owners):
+        q, ctx.saved, ctx.word = critic.run(x, g)
+        ctx.x, ctx.critic, ctx.g, ctx.train_params, ctx.n_owners = x, critic, g, train_params, len(owners)
+        return q
+
+    @staticmethod
+    def backward(ctx, gq):
+        c, g, train = ctx.critic, ctx.g, ctx.train_params
+        gz_next = gq.contiguous()
+        for li in range(len(c.norms) - 1, -1, -1):
+            (gm, gmg, _, btg), (w_next, wg_next, _, bg_next) = c.norms[li], c.lin[li + 1]
+            y, xhat, rstd = ctx.saved[li]
+            gz = hip_ops.ln_linear_bwd_input(gz_next, w_next[:g], y, xhat, rstd, gm[:g], c.acts[li], c.p, rng_ctl=c.rng_ctl if c.p > 0 else None,
+                                             pass_ctr=ctx.word, layer=li, parts=c.parts(g, y.shape[1], y.shape[2], y.device) if train else None,
+                                             dgamma=gmg if train else None, dbeta=btg if train else None)
+            if train:
+                _weight_grad(gz_next, y, wg_next, bg_next)
+            gz_next = gz
+        w0, wg0, _, bg0 = c.lin[0]
+        if train:
+            _weight_grad(gz_next, ctx.x, wg0, bg0)
+        dx = hip_ops.linear_bwd_input(gz_next, w0[:g], None, ACT_NONE, sum_groups=True) if ctx.needs_input_grad[0] else None
+        return (dx,) + (None,) * (3 + ctx.n_owners)
+
+
+class FastLnCritic:
+    """`FastTwinCritic` for a ContinuousCritic built with layer_norm=True (and dropout_rate): the same interface on the row-owning
+    kernels of csrc/cstr_layernorm.hip. `lin` = `twin_stack`, `norms` = `norm_stack` of the critic's arena. Dropout is active in every
+    pass, with a draw of its own: `rng_ctl`'s pass counter advances on the device in the last hidden layer's launch. `stack` is None:
+    the loss-root launches, the four-network pair chain and the row-chain kernels decline such a critic, as they decline TQC's."""
+
+    stack = None
+
+    def __init__(self, critic, lin, norms, rng_ctl: Optional[th.Tensor] = None):
+        hidden, _ = ln_layers(critic.q_networks[0])
+        self.nets = list(critic.q_networks)
+        self.lin, self.norms, self.rng_ctl = lin, norms, rng_ctl
+        self.acts, self.p = [act for _, _, _, act in hidden], hidden[0][1]
+        self.owners = [p for q in critic.q_networks for p in q.parameters()]
+        if self.p > 0 and rng_ctl is None:
+            raise ValueError("a critic with dropout needs the Philox control block of its stream")
+        # scratch, made once: a ring of pass-counter words (a pass's word lives until its backward, and at most the target's, the
+        # critic's and one policy pass are in flight) and the float64 column partials per shape (used inside one entry point)
+        self._words = th.zeros(8, dtype=th.int64, device=rng_ctl.device) if self.p > 0 else None
+        self._next_word, self._parts = 0, {}
+
+    def parts(self, g: int, m: int, n: int, device) -> th.Tensor:
+        key = (g, m, n)
+        if key not in self._parts:
+            self._parts[key] = hip_ops.ln_parts(g, m, n, device)
+        return self._parts[key]
+
+    @staticmethod
+    def supported(critic) -> bool:
+        nets = [ln_layers(q) for q in critic.q_networks]
+        if not nets or any(n is None for n in nets) or not 1 <= len(nets) <= hip_ops.nv.MAX_ENS_CRITICS:
+            return False
+        sig = lambda n: [(l.in_features, l.out_features, p, act) for l, p, _, act in n[0]]  # noqa: E731
+        if any(sig(n) != sig(nets[0]) for n in nets) or len({p for _, p, _, _ in nets[0][0]}) != 1:
+            return False
+        return all(hip_ops.ln_supported(l.in_features, l.out_features, p, act) for l, p, _, act in nets[0][0])
+
+    def __call__(self, obs: th.Tensor, actions: th.Tensor, train_params: bool = True, only_first: bool = False):
+        return self.forward_input(th.cat([obs, actions], dim=1), train_params, only_first)
+
+    def run(self, x: th.Tensor, g: int):
+        """q [g, B, 1], per hidden layer (y, xhat, rstd), the pass-counter word of this pass's masks (None without dropout)"""
+        drop = self.p > 0
+        word = None
+        if drop:
+            word, self._next_word = self._words[self._next_word:self._next_word + 1], (self._next_word + 1) % 8
+        h, saved, last = x, [], len(self.norms) - 1
+        for li, ((w, _, b, _), (gm, _, bt, _)) in enumerate(zip(self.lin, self.norms)):
+            out = hip_ops.linear_ln_act_fwd(h, w[:g], b[:g], gm[:g], bt[:g], self.acts[li], self.p, rng_ctl=self.rng_ctl if drop else None,
+                                            advance=drop and li == last, pass_out=word if li == 0 else None, layer=li)
+            saved.append(out)
+            h = out[0]
+        wq, _, bq, _ = self.lin[-1]
+        return hip_ops.linear_act_fwd(h, wq[:g], bq[:g], ACT_NONE), saved, word
+
+    def forward_input(self, x: th.Tensor, train_params: bool = True, only_first: bool = False):
+        """Q values for an already assembled critic input [B, features + actions] (shared by the Q networks)."""
+        g = 1 if only_first else len(self.nets)
+        if train_params and g != len(self.nets):
+            raise RuntimeError("stacked critic: parameter gradients need all Q networks in the pass")
+        if th.is_grad_enabled() and (x.requires_grad or train_params):
+            q = _LnCriticFn.apply(x, self, g, train_params, *(self.owners if train_params else ()))
+        else:
+            q = self.run(x, g)[0]
+        out = QOut(q[i] for i in range(g))
+        out.stacked = q
+        return out
+
+
+def make_ln_critics(algo):
+    """(FastLnCritic of algo.critic, of algo.critic_target) on one dropout stream seeded from the model's seed"""
+    pol, n_norm = algo.policy, len(ln_layers(algo.critic.q_networks[0])[0])
+    ctl = None
+    if algo.critic.dropout_rate > 0:
+        ctl = th.zeros(hip_ops.nv.RNG_CTL_WORDS, dtype=th.int64, device=algo.device)
+        ctl[0] = (0 if algo.seed is None else int(algo.seed)) + hip_ops.nv.LN_TAG
+    return tuple(FastLnCritic(c, twin_stack(a, n_norm=n_norm), norm_stack(a, n_norm), ctl)
+                 for c, a in ((algo.critic, pol.critic_arena), (algo.critic_target, pol.critic_target_arena)))
 
 
 class FastActorCritic:

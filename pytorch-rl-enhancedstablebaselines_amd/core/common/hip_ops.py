@@ -2610,3 +2610,99 @@ def trpo_x0(x, mask, scale: float, rng_ctl):
     n = x.numel()
     _vec(x, "x", n), _vec(mask, "mask", n), _chk(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
     check(nv.lib().cstr_trpo_x0_f32(ptr(x), ptr(mask), C.c_int64(n), C.c_float(float(scale)), ptr(rng_ctl), stream_ptr()), "cstr_trpo_x0_f32")
+
+
+# ---- LayerNorm / dropout critics (csrc/cstr_layernorm.hip) ---------------------------------------------------------------------------
+def ln_supported(k: int, n: int, p: float = 0.0, act: int = 1) -> bool:
+    """cstr_ln_supported: a hidden layer [Linear(k, n), Dropout(p), LayerNorm(n), act] runs on the row-owning kernels: k >= 1,
+    1 <= n <= LN_MAX_WIDTH, 0 <= p < 1, act ReLU (1) or Tanh (2)."""
+    return bool(nv.lib().cstr_ln_supported(C.c_int64(int(k)), C.c_int64(int(n)), C.c_double(float(p)), C.c_int(int(act))))
+
+
+def _ln_noise(p, u_in, rng_ctl, shape):
+    if u_in is not None:
+        _chk(u_in, "u_in", shape, th.float32)
+    if rng_ctl is not None:
+        _chk(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+
+
+def _ln_word(t, name):
+    if t is not None and not (isinstance(t, th.Tensor) and t.is_cuda and t.dtype == th.int64 and t.numel() == 1):
+        raise ValueError(f"{name}: needs a one-word int64 device tensor")
+    return t
+
+
+def linear_ln_act_fwd(x, weight, bias, gamma, beta, act: int, p: float = 0.0, u_in=None, rng_ctl=None, advance: bool = False, pass_out=None,
+                      layer: int = 0, out=None):
+    """(y, xhat, rstd) of y = act(LN(drop(x @ W^T + b)) * gamma + beta) for G stacked networks in one launch. x [G, M, K] or a shared
+    [M, K] with unit inner stride (rows / groups may be strided); weight [G, N, K], bias / gamma / beta [G, N] contiguous. Dropout
+    (p > 0): the uniforms u_in [G, M, N], or the stream rng_ctl (pass counter rng_ctl[1], recorded in pass_out, advanced with `advance`).
+    out: (y, xhat [G, M, N], rstd [G, M]) to write into."""
+    g, n, k = weight.shape
+    if x.dim() == 2:
+        gs, ldx, m = 0, x.stride(0), x.shape[0]
+    else:
+        gs, ldx, m = x.stride(0), x.stride(1), x.shape[1]
+    if not (x.is_cuda and x.dtype == th.float32 and x.stride(-1) == 1 and x.shape[-1] == k and (x.dim() == 2 or x.shape[0] == g)):
+        raise ValueError(f"x: needs a float32 device tensor [G, M, {k}] or [M, {k}] with unit inner stride")
+    if m == 1:
+        ldx = max(ldx, k)
+    _f32c(weight, "weight")
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        _chk(t, nm, (g, n), th.float32)
+    _ln_noise(p, u_in, rng_ctl, (g, m, n))
+    if out is None:
+        y, xhat = th.empty(g, m, n, dtype=th.float32, device=x.device), th.empty(g, m, n, dtype=th.float32, device=x.device)
+        rstd = th.empty(g, m, dtype=th.float32, device=x.device)
+    else:
+        y, xhat, rstd = _chk(out[0], "y", (g, m, n), th.float32), _chk(out[1], "xhat", (g, m, n), th.float32), _chk(out[2], "rstd", (g, m), th.float32)
+    check(nv.lib().cstr_linear_ln_act_fwd_f32(ptr(x), C.c_int64(gs), C.c_int64(ldx), ptr(weight), ptr(bias), ptr(gamma), ptr(beta), C.c_int(act),
+                                              C.c_double(float(p)), ptr(u_in), ptr(rng_ctl), C.c_int(int(advance)), ptr(_ln_word(pass_out, "pass_out")),
+                                              C.c_int(int(layer)), ptr(y), ptr(xhat), ptr(rstd), C.c_int64(g), C.c_int64(m), C.c_int64(n), C.c_int64(k),
+                                              stream_ptr()), "cstr_linear_ln_act_fwd_f32")
+    return y, xhat, rstd
+
+
+def ln_parts(g: int, m: int, n: int, device) -> th.Tensor:
+    """the float64 scratch of `ln_linear_bwd_input`'s column partials"""
+    return th.empty(g, (m + 15) // 16, 2, n, dtype=th.float64, device=device)
+
+
+def ln_linear_bwd_input(gz_next, w_next, y, xhat, rstd, gamma, act: int, p: float = 0.0, u_in=None, rng_ctl=None, pass_ctr=None, layer: int = 0,
+                        parts=None, dgamma=None, dbeta=None, out=None):
+    """gz [G, M, N] of a LayerNorm layer from gz_next [G, M, N_next] of its consumer (w_next [G, N_next, N]; N_next = 1: the scalar Q head)
+    and the layer's stored y, xhat, rstd; with dgamma / dbeta [G, N] (views of the gradient arena) and parts (`ln_parts`) also the affine
+    parameters' gradients. Dropout: u_in, or rng_ctl with the pass counter the forward recorded (pass_ctr)."""
+    g, m, n = y.shape
+    nn_ = gz_next.shape[-1]
+    _chk(gz_next, "gz_next", (g, m, nn_), th.float32), _f32c(gz_next, "gz_next"), _f32c(w_next, "w_next")
+    if w_next.numel() != g * nn_ * n:
+        raise ValueError(f"w_next {tuple(w_next.shape)} does not match gz_next {tuple(gz_next.shape)} and y {tuple(y.shape)}")
+    _f32c(y, "y"), _f32c(_chk(xhat, "xhat", (g, m, n), th.float32), "xhat"), _f32c(_chk(rstd, "rstd", (g, m), th.float32), "rstd")
+    _f32c(_chk(gamma, "gamma", (g, n), th.float32), "gamma")
+    _ln_noise(p, u_in, rng_ctl, (g, m, n))
+    if (dgamma is None) != (dbeta is None):
+        raise ValueError("dgamma and dbeta: both or neither")
+    if dgamma is not None:
+        _f32c(_chk(dgamma, "dgamma", (g, n), th.float32), "dgamma"), _f32c(_chk(dbeta, "dbeta", (g, n), th.float32), "dbeta")
+        if parts is None:
+            parts = ln_parts(g, m, n, y.device)
+        if not (parts.is_cuda and parts.dtype == th.float64 and parts.is_contiguous() and parts.numel() == g * ((m + 15) // 16) * 2 * n):
+            raise ValueError("parts: needs ln_parts(G, M, N)")
+    else:
+        parts = None
+    gz = th.empty(g, m, n, dtype=th.float32, device=y.device) if out is None else _f32c(_chk(out, "gz", (g, m, n), th.float32), "gz")
+    check(nv.lib().cstr_ln_linear_bwd_input_f32(ptr(gz_next), ptr(w_next), C.c_int64(nn_), ptr(y), ptr(xhat), ptr(rstd), ptr(gamma), C.c_int(act),
+                                                C.c_double(float(p)), ptr(u_in), ptr(rng_ctl), ptr(_ln_word(pass_ctr, "pass_ctr")), C.c_int(int(layer)),
+                                                ptr(gz), ptr(parts), ptr(dgamma), ptr(dbeta), C.c_int64(g), C.c_int64(m), C.c_int64(n), stream_ptr()),
+          "cstr_ln_linear_bwd_input_f32")
+    return gz
+
+
+def ln_dropout_uniform(rng_ctl, g: int, m: int, n: int, layer: int = 0, pass_ctr=None, out=None):
+    """u [G, M, N]: the uniforms a launch on (rng_ctl, layer) draws at the pass counter pass_ctr (None: rng_ctl[1]); nothing advances"""
+    _chk(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    u = th.empty(g, m, n, dtype=th.float32, device=rng_ctl.device) if out is None else _f32c(_chk(out, "u", (g, m, n), th.float32), "u")
+    check(nv.lib().cstr_ln_dropout_uniform_f32(ptr(u), ptr(rng_ctl), ptr(_ln_word(pass_ctr, "pass_ctr")), C.c_int(int(layer)), C.c_int64(g), C.c_int64(m),
+                                               C.c_int64(n), stream_ptr()), "cstr_ln_dropout_uniform_f32")
+    return u

@@ -96,6 +96,11 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
 
     def _setup_model(self) -> None:
         """reference: off_policy_algorithm.py:172-212"""
+        if self._wants_norm_critics():  # layer_norm / dropout_rate critics: single-process runs on the Box face without gSDE
+            if self.world_size > 1:
+                raise ValueError(f"{type(self).__name__} with layer_norm / dropout_rate critics does not run data-parallel (world_size = {self.world_size})")
+            if self.use_sde:
+                raise ValueError(f"{type(self).__name__} with layer_norm / dropout_rate critics does not support gSDE (use_sde=True)")
         self._chain_cache = {}  # row-chain step objects hold raw pointers of the policy's tensors: rebuilt with the policy
         self._setup_lr_schedule()
         blas.configure()
@@ -421,8 +426,8 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         """The row-chain form of the gradient step for this batch size (`chain_type`), or None: per-layer fused path. What is cached
         depends on shapes, architecture and the module flags alone; whether batches are packed follows the replay buffer's normaliser,
         which every learn() sets again, and is asked on every call."""
-        if not self._use_packed_batch():
-            return None
+        if not self._use_packed_batch() or isinstance(getattr(self, "_fast_critic", None), fused.FastLnCritic):
+            return None  # (the row-chain kernels decline layer-normalised critics, as they decline TQC's)
         cache, key = self._chain_cache, (batch_size, chain.USE_CHAIN, fused.USE_FUSED_LINEAR)
         if key not in cache:
             cache[key] = self.chain_type(self, batch_size) if self.chain_type.supported(self, batch_size) else None

@@ -140,15 +140,19 @@ class ContinuousCritic(BaseModel):
 
     def __init__(self, observation_space, action_space, net_arch: list, features_extractor: nn.Module, features_dim: int,
                  activation_fn=nn.ReLU, normalize_images: bool = True, n_critics: int = 2,
-                 share_features_extractor: bool = True):
+                 share_features_extractor: bool = True, layer_norm: bool = False, dropout_rate: float = 0.0):
         super().__init__(observation_space, action_space, features_extractor=features_extractor,
                          normalize_images=normalize_images)
+        if not 0.0 <= float(dropout_rate) < 1.0:
+            raise ValueError(f"dropout_rate must lie in [0, 1), got {dropout_rate}")
+        self.layer_norm, self.dropout_rate = bool(layer_norm), float(dropout_rate)
         action_dim = get_action_dim(self.action_space)
         self.share_features_extractor = share_features_extractor
         self.n_critics = n_critics
         self.q_networks: list = []
         for idx in range(n_critics):
-            q_net = nn.Sequential(*create_mlp(features_dim + action_dim, 1, net_arch, activation_fn))
+            q_net = nn.Sequential(*create_mlp(features_dim + action_dim, 1, net_arch, activation_fn, layer_norm=self.layer_norm,
+                                                dropout_rate=self.dropout_rate))
             self.add_module(f"qf{idx}", q_net)
             self.q_networks.append(q_net)
 

@@ -35,11 +35,17 @@ class CombinedExtractor(nn.Module):
 
 
 def create_mlp(input_dim: int, output_dim: int, net_arch: list, activation_fn=nn.ReLU, squash_output: bool = False,
-               with_bias: bool = True) -> list:
+               with_bias: bool = True, layer_norm: bool = False, dropout_rate: float = 0.0) -> list:
+    """layer_norm / dropout_rate (DroQ, SBX's order): [Linear, Dropout(p) if p > 0, LayerNorm(width) if layer_norm, activation] per hidden
+    layer. Neither module draws random numbers when it is created: the Linear layers' initial weights are those of the plain network."""
     modules: list = []
     last = input_dim
     for width in net_arch:
         modules.append(nn.Linear(last, width, bias=with_bias))
+        if dropout_rate > 0.0:
+            modules.append(nn.Dropout(p=dropout_rate))
+        if layer_norm:
+            modules.append(nn.LayerNorm(width))
         modules.append(activation_fn())
         last = width
     if output_dim > 0:

@@ -82,7 +82,8 @@ class SACPolicy(BasePolicy):
                  activation_fn=nn.ReLU, use_sde: bool = False, log_std_init: float = -3, use_expln: bool = False,
                  clip_mean: float = 2.0, full_std: bool = True, features_extractor_class=FlattenExtractor, features_extractor_kwargs=None,
                  normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs: Optional[dict] = None,
-                 n_critics: int = 2, share_features_extractor: bool = False):
+                 n_critics: int = 2, share_features_extractor: bool = False, layer_norm: bool = False,
+                 dropout_rate: float = 0.0):
         super().__init__(observation_space, action_space, features_extractor_class, features_extractor_kwargs,
                          optimizer_class=optimizer_class, optimizer_kwargs=optimizer_kwargs, squash_output=True,
                          normalize_images=normalize_images)
@@ -94,6 +95,8 @@ class SACPolicy(BasePolicy):
         self.net_arch, self.activation_fn = net_arch, activation_fn
         self.actor_arch, self.critic_arch, self.n_critics = actor_arch, critic_arch, n_critics
         self.share_features_extractor = share_features_extractor
+        # DroQ-style critics: [Linear, Dropout, LayerNorm, act] per hidden layer (ContinuousCritic); the actor is untouched
+        self.critic_kwargs = dict(layer_norm=bool(layer_norm), dropout_rate=float(dropout_rate)) if layer_norm or dropout_rate else {}
         self.use_sde = use_sde
         self.sde_kwargs = dict(use_sde=use_sde, log_std_init=log_std_init, full_std=full_std, use_expln=use_expln, clip_mean=clip_mean)
         self._lr_schedule = lr_schedule
@@ -107,7 +110,7 @@ class SACPolicy(BasePolicy):
     def make_critic(self) -> ContinuousCritic:
         fe = self.make_features_extractor()
         return ContinuousCritic(self.observation_space, self.action_space, self.critic_arch, fe, fe.features_dim,
-                                self.activation_fn, n_critics=self.n_critics, share_features_extractor=False)
+                                self.activation_fn, n_critics=self.n_critics, share_features_extractor=False, **self.critic_kwargs)
 
     def _build(self, lr_schedule) -> None:
         """Module creation order of the reference (sac/policies.py:280-310): actor, critic, critic_target."""
@@ -140,8 +143,9 @@ class SACPolicy(BasePolicy):
                                                                   extra_grad=64)  # tail: the entropy coefficient's gradient
         self.critic_target_arena = ParamArena(self.critic_target.parameters(), device, with_grad=False,
                                               groups=fused.twin_groups(self.critic_target.q_networks))
-        self.critic_stack = fused.twin_stack(self.critic_arena)
-        self.critic_target_stack = fused.twin_stack(self.critic_target_arena)
+        n_norm = sum(isinstance(m, nn.LayerNorm) for m in self.critic.q_networks[0])
+        self.critic_stack = fused.twin_stack(self.critic_arena, n_norm=n_norm)
+        self.critic_target_stack = fused.twin_stack(self.critic_target_arena, n_norm=n_norm)
         for p in self.critic_target.parameters():
             p.requires_grad_(False)
 
@@ -165,6 +169,9 @@ class SACPolicy(BasePolicy):
     def set_training_mode(self, mode: bool) -> None:
         self.actor.set_training_mode(mode)
         self.critic.set_training_mode(mode)
+        for m in self.critic_target.modules():  # DroQ: the target critic's pass of a gradient step draws a dropout mask too
+            if isinstance(m, nn.Dropout):
+                m.train(mode)
         self.training = mode
 
 

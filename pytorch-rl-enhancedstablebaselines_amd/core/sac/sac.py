@@ -25,6 +25,7 @@ class SAC(OffPolicyAlgorithm):
     goal_face_support = True  # HER on the goal face of the env
     train_batch_size = 64
     chain_type = SacChain
+    norm_critic_classes = ("SAC",)
 
     def __init__(self, policy, env, learning_rate=3e-4, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = 1,
@@ -84,17 +85,22 @@ class SAC(OffPolicyAlgorithm):
         self.fused_learner = self._fused_supported()
         if self.fused_learner:
             self._fast_actor = fused.FastSacActor(self.actor, self.policy.actor_head)
-            self._fast_critic = fused.FastTwinCritic(self.critic, self.policy.critic_stack)
-            self._fast_critic_target = fused.FastTwinCritic(self.critic_target, self.policy.critic_target_stack)
+            if getattr(self.critic, "layer_norm", False):  # the row-owning LayerNorm kernels (csrc/cstr_layernorm.hip), every loss a launch of its own
+                self._fast_critic, self._fast_critic_target = fused.make_ln_critics(self)
+            else:
+                self._fast_critic = fused.FastTwinCritic(self.critic, self.policy.critic_stack)
+                self._fast_critic_target = fused.FastTwinCritic(self.critic_target, self.policy.critic_target_stack)
             # critic ensembles (policy_kwargs n_critics != 2): the N-critic loss heads, per-layer critic passes
-            self._critic_block = fused.PerLayerTwinCritic(self._fast_critic, self._fast_critic_target, ensemble=len(self.critic.q_networks) != 2)
+            self._critic_block = fused.PerLayerTwinCritic(self._fast_critic, self._fast_critic_target, ensemble=len(self.critic.q_networks) != 2,
+                                                          loss_roots=not getattr(self.critic, "layer_norm", False))
         if self.use_sde:  # the ATen path differentiates the matrices as torch expressions; the fused head reads the draw buffers
             self.actor.action_dist.torch_matrices = not self.fused_learner
 
     def _fused_supported(self) -> bool:
         return (1 <= len(self.critic.q_networks) <= hip_ops.nv.MAX_ENS_CRITICS and isinstance(self.actor.optimizer, FlatAdam)
                 and isinstance(self.critic.optimizer, FlatAdam) and fused.FastMLP.supported(self.actor.latent_pi)
-                and all(fused.FastMLP.supported(q) for q in self.critic.q_networks))
+                and (fused.FastLnCritic.supported(self.critic) if getattr(self.critic, "layer_norm", False)
+                     else all(fused.FastMLP.supported(q) for q in self.critic.q_networks)))
 
     def _policy_out_device(self, obs: th.Tensor) -> th.Tensor:
         if not self.fused_learner:

@@ -35,7 +35,8 @@ class TD3Policy(BasePolicy):
     def __init__(self, observation_space, action_space, lr_schedule, net_arch: Optional[Union[list, dict]] = None,
                  activation_fn=nn.ReLU, features_extractor_class=FlattenExtractor, features_extractor_kwargs=None,
                  normalize_images: bool = True, optimizer_class=th.optim.Adam, optimizer_kwargs: Optional[dict] = None,
-                 n_critics: int = 2, share_features_extractor: bool = False):
+                 n_critics: int = 2, share_features_extractor: bool = False, layer_norm: bool = False,
+                 dropout_rate: float = 0.0):
         super().__init__(observation_space, action_space, features_extractor_class, features_extractor_kwargs,
                          optimizer_class=optimizer_class, optimizer_kwargs=optimizer_kwargs, squash_output=True,
                          normalize_images=normalize_images)
@@ -46,6 +47,8 @@ class TD3Policy(BasePolicy):
         self.actor_arch, self.critic_arch = get_actor_critic_arch(net_arch)
         self.net_arch, self.activation_fn, self.n_critics = net_arch, activation_fn, n_critics
         self.share_features_extractor = share_features_extractor
+        # DroQ-style critics: [Linear, Dropout, LayerNorm, act] per hidden layer (ContinuousCritic); the actor is untouched
+        self.critic_kwargs = dict(layer_norm=bool(layer_norm), dropout_rate=float(dropout_rate)) if layer_norm or dropout_rate else {}
         self._lr_schedule = lr_schedule
         self._build(lr_schedule)
 
@@ -56,7 +59,7 @@ class TD3Policy(BasePolicy):
     def make_critic(self) -> ContinuousCritic:
         fe = self.make_features_extractor()
         return ContinuousCritic(self.observation_space, self.action_space, self.critic_arch, fe, fe.features_dim,
-                                self.activation_fn, n_critics=self.n_critics, share_features_extractor=False)
+                                self.activation_fn, n_critics=self.n_critics, share_features_extractor=False, **self.critic_kwargs)
 
     def _build(self, lr_schedule) -> None:
         """Creation order of the reference (td3/policies.py:172-208): actor, actor_target, critic, critic_target."""
@@ -81,8 +84,9 @@ class TD3Policy(BasePolicy):
         self.actor_target_arena = ParamArena(self.actor_target.parameters(), device, with_grad=False)
         self.critic_target_arena = ParamArena(self.critic_target.parameters(), device, with_grad=False,
                                               groups=fused.twin_groups(self.critic_target.q_networks))
-        self.critic_stack = fused.twin_stack(self.critic_arena)
-        self.critic_target_stack = fused.twin_stack(self.critic_target_arena)
+        n_norm = sum(isinstance(m, nn.LayerNorm) for m in self.critic.q_networks[0])
+        self.critic_stack = fused.twin_stack(self.critic_arena, n_norm=n_norm)
+        self.critic_target_stack = fused.twin_stack(self.critic_target_arena, n_norm=n_norm)
         for p in list(self.actor_target.parameters()) + list(self.critic_target.parameters()):
             p.requires_grad_(False)
 
@@ -102,6 +106,9 @@ class TD3Policy(BasePolicy):
     def set_training_mode(self, mode: bool) -> None:
         self.actor.set_training_mode(mode)
         self.critic.set_training_mode(mode)
+        for m in self.critic_target.modules():  # DroQ: the target critic's pass of a gradient step draws a dropout mask too
+            if isinstance(m, nn.Dropout):
+                m.train(mode)
         self.training = mode
 
 

@@ -17,6 +17,7 @@ class TD3(OffPolicyAlgorithm):
     goal_face_support = True  # HER on the goal face of the env (DDPG inherits it)
     train_batch_size = 100
     chain_type = Td3Chain
+    norm_critic_classes = ("TD3",)
 
     def __init__(self, policy, env, learning_rate=1e-3, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = 1,
@@ -52,13 +53,19 @@ class TD3(OffPolicyAlgorithm):
         from core.common.arena import FlatAdam
 
         self.fused_learner = (isinstance(self.actor.optimizer, FlatAdam) and isinstance(self.critic.optimizer, FlatAdam)
-                              and fused.FastMLP.supported(self.actor.mu) and all(fused.FastMLP.supported(q) for q in self.critic.q_networks))
+                              and fused.FastMLP.supported(self.actor.mu)
+                              and (fused.FastLnCritic.supported(self.critic) if getattr(self.critic, "layer_norm", False)
+                                   else all(fused.FastMLP.supported(q) for q in self.critic.q_networks)))
         if self.fused_learner:
             self._fast_actor, self._fast_actor_target = fused.FastMLP(self.actor.mu, self.actor.optimizer), fused.FastMLP(self.actor_target.mu)
-            self._fast_critic, self._fast_critic_target = fused.FastTwinCritic(self.critic, self.policy.critic_stack), fused.FastTwinCritic(self.critic_target, self.policy.critic_target_stack)
+            if getattr(self.critic, "layer_norm", False):  # the row-owning LayerNorm kernels (csrc/cstr_layernorm.hip), every loss a launch of its own
+                self._fast_critic, self._fast_critic_target = fused.make_ln_critics(self)
+            else:
+                self._fast_critic, self._fast_critic_target = fused.FastTwinCritic(self.critic, self.policy.critic_stack), fused.FastTwinCritic(self.critic_target, self.policy.critic_target_stack)
             # critic ensembles (policy_kwargs n_critics > 2): min over all N targets, the loss and backward through all N critics;
             # n_critics == 1 (DDPG) stays on the twin loss head
-            self._critic_block = fused.PerLayerTwinCritic(self._fast_critic, self._fast_critic_target, ensemble=len(self.critic.q_networks) > 2)
+            self._critic_block = fused.PerLayerTwinCritic(self._fast_critic, self._fast_critic_target, ensemble=len(self.critic.q_networks) > 2,
+                                                          loss_roots=not getattr(self.critic, "layer_norm", False))
 
     def _policy_out_device(self, obs: th.Tensor) -> th.Tensor:
         if not self.fused_learner:
