@@ -1735,6 +1735,41 @@ int cstr_ln_linear_bwd_input_f32(const float *gz_next, const float *w_next, int6
 int cstr_ln_dropout_uniform_f32(float *u_out, const uint64_t *rng_ctl, const uint64_t *pass_ctr, int layer, int64_t groups, int64_t m,
                                 int64_t n, cstr_stream_t stream);
 
+/* ---- LSTM sequence kernels (csrc/cstr_lstm.hip; RecurrentPPO) ---------------------------------------------------------------------------
+ * A single-layer torch.nn.LSTM over ragged segments, all f32: gate order i, f, g, o; w_ih [4H][K], w_hh [4H][H] (16-byte aligned),
+ * b_ih / b_hh [4H]. Before step t of a sequence, h and c are multiplied by 1 - episode_start[t] (sb3_contrib's _process_sequence).
+ *
+ * Rows: x [n_rows][K], episode_start [n_rows] and every [n_rows][.] tensor below share one row index. A SEGMENT s is the rows
+ * first .. first + length - 1 (consecutive time steps of one env) with its initial state in row `init` of state_h / state_c
+ * [n_state_rows][H]. The table is int32 [n_seg][3] = { first, length, init }, handed over twice: seg_host (read by the entry point: every
+ * check below happens before anything is enqueued) and seg_dev (the same words in device memory, read by the kernel). Segments are in
+ * ascending row order and share no row. A workgroup owns 16 consecutive segments and all 4H gate columns.
+ *
+ * cstr_lstm_seq_fwd_f32: hn / cn [n_seg][H] = the state after each segment's last row (not multiplied by any later mask). out [n_rows][H] =
+ *   h_t (NULL: not stored). Training mode = gates, c_seq and h_prev all given (then out as well): gates [n_rows][4H] = the activated gates
+ *   [i | f | g | o], c_seq [n_rows][H] = c_t, h_prev [n_rows][H] = the masked h_{t-1} that step t multiplied with w_hh. All three NULL: the
+ *   rollout mode (length-1 segments, one per env), which stores nothing but hn / cn (and out where given).
+ * cstr_lstm_seq_bwd_f32: from dout [n_rows][H] = d loss / d h_t and the forward's gates / c_seq / state_c / table, dgates [n_rows][4H] = d loss /
+ *   d (gate pre-activations), dh0 / dc0 [n_seg][H] = d loss / d (the segment's initial state, before its first mask). The weight gradients are
+ *   cstr_linear_bwd_weight_f32 (or its Adam-fused sibling) on dgates against h_prev (w_hh) and x (w_ih); both biases take its column sums.
+ * force_stream != 0: w_hh is streamed through L2 even where it would fit in LDS (cstr_lstm_resident: it fits in 160 KB beside the tiles).
+ * No float atomics; a repeated launch writes the same bits. Rows of no segment are left untouched in every output.
+ * CSTR_E_BADARG: a NULL required pointer, n_rows / n_state_rows / n_seg < 1, K or H < 1, part of the training-mode outputs, a pointer off a
+ *   4-byte (w_hh: 16-byte) boundary, an output overlapping an input or another output, a segment of length < 1, out of order, leaving
+ *   [0, n_rows) or with its state row outside [0, n_state_rows). CSTR_E_UNSUPPORTED: H no multiple of 16, H > CSTR_LSTM_MAX_HIDDEN, K >
+ *   CSTR_LSTM_MAX_INPUT, 2^31 or more rows, a device that grants a workgroup less LDS than the streamed form needs. */
+#define CSTR_LSTM_MAX_HIDDEN 256
+#define CSTR_LSTM_MAX_INPUT 256
+int cstr_lstm_supported(int64_t k, int64_t h);
+int cstr_lstm_resident(int64_t k, int64_t h, int backward);
+int cstr_lstm_seq_fwd_f32(const float *x, const float *episode_start, int64_t n_rows, const float *w_ih, const float *w_hh, const float *b_ih,
+                          const float *b_hh, const float *state_h, const float *state_c, int64_t n_state_rows, const int32_t *seg_host,
+                          const int32_t *seg_dev, int64_t n_seg, float *out, float *hn, float *cn, float *gates, float *c_seq, float *h_prev,
+                          int64_t k, int64_t h, int force_stream, cstr_stream_t stream);
+int cstr_lstm_seq_bwd_f32(const float *dout, const float *gates, const float *c_seq, const float *state_c, int64_t n_state_rows,
+                          const float *episode_start, int64_t n_rows, const float *w_hh, const int32_t *seg_host, const int32_t *seg_dev,
+                          int64_t n_seg, float *dgates, float *dh0, float *dc0, int64_t h, int force_stream, cstr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

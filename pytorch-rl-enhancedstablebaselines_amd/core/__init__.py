@@ -6,7 +6,7 @@ import os
 with open(os.path.join(os.path.dirname(__file__), "version.txt")) as _fh:  # the reference forgot to ship this file
     __version__ = _fh.read().strip()
 
-__all__ = ["SAC", "TQC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "TD3BC", "CQL", "IQL", "PPO", "A2C", "DQN", "QRDQN", "ARS", "TRPO", "HerReplayBuffer", "__version__"]
+__all__ = ["SAC", "TQC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "TD3BC", "CQL", "IQL", "PPO", "A2C", "DQN", "QRDQN", "ARS", "TRPO", "RecurrentPPO", "HerReplayBuffer", "__version__"]
 
 
 def __getattr__(name):
@@ -55,6 +55,9 @@ def __getattr__(name):
     if name == "TRPO":
         from core.trpo import TRPO
         return TRPO
+    if name == "RecurrentPPO":
+        from core.ppo_recurrent import RecurrentPPO
+        return RecurrentPPO
     if name == "HerReplayBuffer":
         from core.her import HerReplayBuffer
         return HerReplayBuffer

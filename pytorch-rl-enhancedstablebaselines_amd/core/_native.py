@@ -40,6 +40,7 @@ TRPO_CG_INIT, TRPO_CG_STEP, TRPO_CG_FINISH = 0, 1, 2
 PER_MAX_LEVELS, PER_MAX_CAPACITY, PER_CTL_WORDS, PER_MAX_BATCH, PER_TAG = 6, 1 << 30, 8, 1024, 0x9E7A11ED
 PER_CTL = dict(max_priority=0, seed=1, offset=2, ticket=3)
 LN_MAX_WIDTH, LN_TAG = 512, 0x1A7E2D0B  # CSTR_LN_MAX_WIDTH; counter word 3 of the LayerNorm critics' dropout stream (csrc/cstr_layernorm.hip)
+LSTM_MAX_HIDDEN, LSTM_MAX_INPUT, LSTM_SEGS = 256, 256, 16  # CSTR_LSTM_MAX_HIDDEN, CSTR_LSTM_MAX_INPUT; segments per workgroup (csrc/cstr_lstm.hip)
 
 SYMBOLS = (
     "cstr_abi_version", "cstr_error_string", "cstr_default_coef", "cstr_vec_step_f32", "cstr_reset_draw_f32",
@@ -74,6 +75,7 @@ SYMBOLS = (
     "cstr_trpo_value_loss_f32", "cstr_trpo_x0_f32",
     "cstr_per_tree_layout", "cstr_per_rebuild_f64", "cstr_per_add_f64", "cstr_per_sample_f32", "cstr_per_update_f64", "cstr_dqn_loss_weighted_f32",
     "cstr_ln_supported", "cstr_linear_ln_act_fwd_f32", "cstr_ln_linear_bwd_input_f32", "cstr_ln_dropout_uniform_f32",
+    "cstr_lstm_supported", "cstr_lstm_resident", "cstr_lstm_seq_fwd_f32", "cstr_lstm_seq_bwd_f32",
 )
 
 

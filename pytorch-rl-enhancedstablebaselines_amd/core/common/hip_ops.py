@@ -2706,3 +2706,78 @@ def ln_dropout_uniform(rng_ctl, g: int, m: int, n: int, layer: int = 0, pass_ctr
     check(nv.lib().cstr_ln_dropout_uniform_f32(ptr(u), ptr(rng_ctl), ptr(_ln_word(pass_ctr, "pass_ctr")), C.c_int(int(layer)), C.c_int64(g), C.c_int64(m),
                                                C.c_int64(n), stream_ptr()), "cstr_ln_dropout_uniform_f32")
     return u
+
+
+# ---- LSTM sequence kernels (csrc/cstr_lstm.hip; RecurrentPPO) -----------------------------------------------------------------------
+def lstm_supported(k: int, h: int) -> bool:
+    """cstr_lstm_supported: input width 1 .. LSTM_MAX_INPUT, hidden width a multiple of 16 up to LSTM_MAX_HIDDEN"""
+    return bool(nv.lib().cstr_lstm_supported(C.c_int64(k), C.c_int64(h)))
+
+
+def lstm_resident(k: int, h: int, backward: bool = False) -> bool:
+    """cstr_lstm_resident: weight_hh fits in LDS beside the launch's tiles (otherwise it is streamed through L2 every step)"""
+    return bool(nv.lib().cstr_lstm_resident(C.c_int64(k), C.c_int64(h), C.c_int(int(backward))))
+
+
+class LstmSegments:
+    """A segment table int32 [n_seg, 3] = (first row, length, row of the initial state), once on the host (the entry points check it
+    before they enqueue anything) and once in HBM (the kernels read it). `part(a, b)`: the segments a .. b - 1 as views of both."""
+
+    def __init__(self, table, device, _dev=None):
+        import numpy as np
+
+        self.host = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, 3)
+        self.dev = th.from_numpy(self.host).to(device) if _dev is None else _dev
+        self.n = int(self.host.shape[0])
+
+    def part(self, a: int, b: int) -> "LstmSegments":
+        return LstmSegments(self.host[a:b], None, self.dev[a:b])
+
+    def shifted(self, rows: int) -> "LstmSegments":
+        """the same segments with `rows` taken off every first row (a chunk's table in the chunk's own row numbers)"""
+        t = self.host.copy()
+        t[:, 0] -= rows
+        return LstmSegments(t, self.dev.device)
+
+
+def _lstm_table(segs: "LstmSegments"):
+    if segs.n < 1:
+        raise ValueError("an LSTM launch needs at least one segment")
+    _chk(segs.dev, "segs.dev", (segs.n, 3), th.int32)
+    return segs.host.ctypes.data_as(C.c_void_p), ptr(segs.dev), C.c_int64(segs.n)
+
+
+def lstm_seq_fwd(x, episode_start, w_ih, w_hh, b_ih, b_hh, state_h, state_c, segs: LstmSegments, hn, cn, out=None, gates=None, c_seq=None,
+                 h_prev=None, force_stream: bool = False):
+    """A single-layer nn.LSTM over the segments of `segs`, h and c multiplied by 1 - episode_start[t] before step t. x [R, K], episode_start
+    [R], state_h / state_c [S0, H] (the rows the table's third column names), hn / cn [n_seg, H]. out [R, H] = h_t. Training mode: gates
+    [R, 4H], c_seq [R, H], h_prev [R, H] (all three, with out) keep what lstm_seq_bwd and the weight-gradient launches need."""
+    r, k = x.shape
+    h = w_hh.shape[1]
+    s0 = state_h.shape[0]
+    _chk(x, "x", (r, k), th.float32), _chk(episode_start, "episode_start", (r,), th.float32)
+    _chk(w_ih, "w_ih", (4 * h, k), th.float32), _chk(w_hh, "w_hh", (4 * h, h), th.float32)
+    _chk(b_ih, "b_ih", (4 * h,), th.float32), _chk(b_hh, "b_hh", (4 * h,), th.float32)
+    _chk(state_h, "state_h", (s0, h), th.float32), _chk(state_c, "state_c", (s0, h), th.float32)
+    _chk(hn, "hn", (segs.n, h), th.float32), _chk(cn, "cn", (segs.n, h), th.float32)
+    _opt(out, "out", (r, h), th.float32), _opt(gates, "gates", (r, 4 * h), th.float32)
+    _opt(c_seq, "c_seq", (r, h), th.float32), _opt(h_prev, "h_prev", (r, h), th.float32)
+    check(nv.lib().cstr_lstm_seq_fwd_f32(ptr(x), ptr(episode_start), C.c_int64(r), ptr(w_ih), ptr(w_hh), ptr(b_ih), ptr(b_hh), ptr(state_h),
+                                         ptr(state_c), C.c_int64(s0), *_lstm_table(segs), ptr(out), ptr(hn), ptr(cn), ptr(gates), ptr(c_seq),
+                                         ptr(h_prev), C.c_int64(k), C.c_int64(h), C.c_int(int(force_stream)), stream_ptr()),
+          "cstr_lstm_seq_fwd_f32")
+
+
+def lstm_seq_bwd(dout, gates, c_seq, state_c, episode_start, w_hh, segs: LstmSegments, dgates, dh0, dc0, force_stream: bool = False):
+    """Backward through time of lstm_seq_fwd's training mode: dout [R, H] = d loss / d h_t -> dgates [R, 4H] (w.r.t. the gate
+    pre-activations), dh0 / dc0 [n_seg, H] (w.r.t. each segment's initial state). Weight gradients: linear_bwd_weight(dgates, h_prev, dW_hh)
+    and linear_bwd_weight(dgates, x, dW_ih, db)."""
+    r, h = dout.shape
+    s0 = state_c.shape[0]
+    _chk(dout, "dout", (r, h), th.float32), _chk(gates, "gates", (r, 4 * h), th.float32), _chk(c_seq, "c_seq", (r, h), th.float32)
+    _chk(state_c, "state_c", (s0, h), th.float32), _chk(episode_start, "episode_start", (r,), th.float32)
+    _chk(w_hh, "w_hh", (4 * h, h), th.float32), _chk(dgates, "dgates", (r, 4 * h), th.float32)
+    _chk(dh0, "dh0", (segs.n, h), th.float32), _chk(dc0, "dc0", (segs.n, h), th.float32)
+    check(nv.lib().cstr_lstm_seq_bwd_f32(ptr(dout), ptr(gates), ptr(c_seq), ptr(state_c), C.c_int64(s0), ptr(episode_start), C.c_int64(r),
+                                         ptr(w_hh), *_lstm_table(segs), ptr(dgates), ptr(dh0), ptr(dc0), C.c_int64(h),
+                                         C.c_int(int(force_stream)), stream_ptr()), "cstr_lstm_seq_bwd_f32")

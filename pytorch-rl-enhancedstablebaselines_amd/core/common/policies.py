@@ -218,7 +218,7 @@ class ActorCriticPolicy(BasePolicy):
         self._lr_schedule = lr_schedule
         self.fast = None
         # :585-631
-        self.mlp_extractor = MlpExtractor(self.features_dim, net_arch=self.net_arch, activation_fn=self.activation_fn)
+        self.mlp_extractor = MlpExtractor(self._mlp_input_dim(), net_arch=self.net_arch, activation_fn=self.activation_fn)
         if self.discrete or self.multi_discrete:  # the logits layer; a (Multi)Categorical head has no log_std (neither parameter nor attribute)
             self.action_net = self.action_dist.proba_distribution_net(latent_dim=self.mlp_extractor.latent_dim_pi)
         else:
@@ -229,6 +229,10 @@ class ActorCriticPolicy(BasePolicy):
             for module, gain in ((self.mlp_extractor, np.sqrt(2)), (self.action_net, 0.01), (self.value_net, 1)):
                 module.apply(lambda m, gain=gain: self.init_weights(m, gain=gain))
         self.optimizer = None  # to_device_arenas
+
+    def _mlp_input_dim(self) -> int:
+        """the width `mlp_extractor` reads: the features (a recurrent policy: its LSTM's hidden width)"""
+        return self.features_dim
 
     @staticmethod
     def init_weights(module: nn.Module, gain: float = 1) -> None:
