@@ -209,6 +209,48 @@ int cstr_replay_gather_packed_f32(const cstr_ring_t *ring, int64_t *ring_ctl, in
                                   float *x_pi, float *out_done, float *out_rew, int64_t *out_row_idx, int64_t *out_env_idx,
                                   cstr_stream_t stream);
 
+/* ---- n-step samples (NStepReplayBuffer._get_samples) ----
+ * For a sampled pair (row r, env e) the steps are the ring slots ((r + k) % rows, e), k = 0 .. n_steps - 1 (the same env column of the
+ * rows that follow in time; the ring stores true next observations).
+ *   stop_k = done_k | timeout_k | (slot k is the newest written row); j = the first k with stop_k, else n_steps - 1; m = j + 1
+ *   rewards = sum_{k <= j} gpow[k] r_k   (f32, accumulated in the order k = 0 .. j)
+ *   observations, actions: step 0; next_observations: the ring's next_obs at step j
+ *   dones = done_j (1 - timeout_j) with the stored flags; discounts = gpow[m]
+ *   fold = 1 - (1 - dones) gpow[m - 1], so that (1 - fold) gamma == (1 - dones) gamma^m: what a TD-target launch with a scalar gamma
+ *   takes in place of `dones`. n_steps = 1: fold == dones and every output equals the one-step sampler's, bit for bit.
+ * The newest written row is ring_ctl[0] - 1 (mod rows) -- or ring_ctl[0] itself where a rollout launch has written the row and left
+ * the ring advance pending (advance_ring != 0 below). No sample crosses it or runs into unwritten rows; the ring is never written.
+ * gpow: BY VALUE, gpow.g[k] = (float)pow((double)gamma, k), k = 0 .. CSTR_NSTEP_MAX, computed on the host; the kernels never
+ * exponentiate, and discounts is exactly the f32 rounding of the f64 power.
+ * CSTR_E_BADARG: NULL / misaligned pointers (out_row_idx, out_env_idx and x_pi may be NULL), batch <= 0.
+ * CSTR_E_UNSUPPORTED: n_steps outside [1, CSTR_NSTEP_MAX], not a CSTR layout, batch > CSTR_MAX_SAMPLE_BATCH. */
+#define CSTR_NSTEP_MAX 16
+typedef struct cstr_nstep_gpow {
+    float g[CSTR_NSTEP_MAX + 1];
+} cstr_nstep_gpow_t;
+
+/* cstr_replay_sample_mt19937_f32's index draw (same bounds, same order, same words consumed) + the n-step gather into
+ * contiguous tensors; out_done / out_rew / out_discount / out_fold [B]. */
+int cstr_replay_sample_nstep_mt19937_f32(const cstr_ring_t *ring, const int64_t *ring_ctl, uint32_t *mt_state, int64_t batch,
+                                         int n_steps, cstr_nstep_gpow_t gpow, float *out_obs, float *out_act, float *out_next_obs,
+                                         float *out_done, float *out_rew, float *out_discount, float *out_fold,
+                                         int64_t *out_row_idx, int64_t *out_env_idx, cstr_stream_t stream);
+
+/* The same into the critics' packed rows, laid out as cstr_replay_sample_packed_mt19937_f32 lays them out. */
+int cstr_replay_sample_nstep_packed_mt19937_f32(const cstr_ring_t *ring, const int64_t *ring_ctl, uint32_t *mt_state, int64_t batch,
+                                                int n_steps, cstr_nstep_gpow_t gpow, float *x_data, float *x_next, float *x_pi,
+                                                float *out_done, float *out_rew, float *out_discount, float *out_fold,
+                                                int64_t *out_row_idx, int64_t *out_env_idx, cstr_stream_t stream);
+
+/* The n-step gather for index pairs drawn earlier by cstr_rollout_step_f32; advance_ring / rng_ctl / rng_advance as in
+ * cstr_replay_gather_packed_f32. ring_ctl is always needed (the write head). A lane group per sampled row over up to 32 workgroups;
+ * the control words are updated by the last workgroup out (ring_ctl's ticket word), after every read of them. */
+int cstr_replay_gather_nstep_packed_f32(const cstr_ring_t *ring, int64_t *ring_ctl, int advance_ring, uint64_t *rng_ctl,
+                                        uint64_t rng_advance, const int32_t *sample_idx, int64_t batch, int n_steps,
+                                        cstr_nstep_gpow_t gpow, float *x_data, float *x_next, float *x_pi, float *out_done,
+                                        float *out_rew, float *out_discount, float *out_fold, int64_t *out_row_idx,
+                                        int64_t *out_env_idx, cstr_stream_t stream);
+
 /* ReplayBuffer.sample's gather FUSED INTO ITS FIRST CONSUMER: y [M][n] = act(x W^T + b) where the input rows x are the sampled
  * transitions themselves, read from the ring by the index pairs of cstr_rollout_step_f32 (sample_idx as in
  * cstr_replay_gather_packed_f32). both != 0: M = 2 batch, rows [0, batch) = observations, rows [batch, 2 batch) = next

@@ -6,7 +6,7 @@ import os
 with open(os.path.join(os.path.dirname(__file__), "version.txt")) as _fh:  # the reference forgot to ship this file
     __version__ = _fh.read().strip()
 
-__all__ = ["SAC", "TQC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "TD3BC", "CQL", "IQL", "PPO", "A2C", "DQN", "QRDQN", "ARS", "TRPO", "RecurrentPPO", "HerReplayBuffer", "__version__"]
+__all__ = ["SAC", "TQC", "TD3", "MADDPG", "IDDPG", "DDPG", "BCQ", "TD3BC", "CQL", "IQL", "PPO", "A2C", "DQN", "QRDQN", "ARS", "TRPO", "RecurrentPPO", "HerReplayBuffer", "NStepReplayBuffer", "__version__"]
 
 
 def __getattr__(name):
@@ -61,4 +61,7 @@ def __getattr__(name):
     if name == "HerReplayBuffer":
         from core.her import HerReplayBuffer
         return HerReplayBuffer
+    if name == "NStepReplayBuffer":
+        from core.common.buffers import NStepReplayBuffer
+        return NStepReplayBuffer
     raise AttributeError(f"module 'core' has no attribute {name!r}")

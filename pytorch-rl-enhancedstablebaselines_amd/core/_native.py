@@ -76,6 +76,7 @@ SYMBOLS = (
     "cstr_per_tree_layout", "cstr_per_rebuild_f64", "cstr_per_add_f64", "cstr_per_sample_f32", "cstr_per_update_f64", "cstr_dqn_loss_weighted_f32",
     "cstr_ln_supported", "cstr_linear_ln_act_fwd_f32", "cstr_ln_linear_bwd_input_f32", "cstr_ln_dropout_uniform_f32",
     "cstr_lstm_supported", "cstr_lstm_resident", "cstr_lstm_seq_fwd_f32", "cstr_lstm_seq_bwd_f32",
+    "cstr_replay_sample_nstep_mt19937_f32", "cstr_replay_sample_nstep_packed_mt19937_f32", "cstr_replay_gather_nstep_packed_f32",
 )
 
 
@@ -93,6 +94,18 @@ class Ring(C.Structure):
     """cstr_ring_t"""
     _fields_ = [(n, C.c_void_p) for n in ("obs", "next_obs", "act", "rew", "done", "timeout")] + [
         ("rows", C.c_int64), ("n_envs", C.c_int64), ("obs_dim", C.c_int32), ("act_dim", C.c_int32)]
+
+
+NSTEP_MAX = 16  # CSTR_NSTEP_MAX
+
+
+class NStepGpow(C.Structure):
+    """cstr_nstep_gpow_t: g[k] = float32(gamma ** k) from the float64 power, passed by value"""
+    _fields_ = [("g", C.c_float * (NSTEP_MAX + 1))]
+
+    @classmethod
+    def of(cls, gamma: float) -> "NStepGpow":
+        return cls((C.c_float * (NSTEP_MAX + 1))(*[float(gamma) ** k for k in range(NSTEP_MAX + 1)]))
 
 
 class Her(C.Structure):

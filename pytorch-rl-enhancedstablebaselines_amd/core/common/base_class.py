@@ -372,6 +372,8 @@ class BaseAlgorithm:
             if rb is not None and hasattr(rb, "n_sampled_goal"):
                 data["her_kwargs"] = {"n_sampled_goal": int(rb.n_sampled_goal), "goal_selection_strategy": rb.strategy_key}
         data.update(self._extra_save_data())
+        if getattr(self, "supports_n_steps", False) and getattr(self, "n_steps", 1) > 1:  # the off-policy classes' n-step returns
+            data["n_steps"] = int(self.n_steps)
         for k in (exclude or []):
             data.pop(k, None)
         _, var_names = self._get_torch_save_params()
@@ -398,6 +400,8 @@ class BaseAlgorithm:
             from core.her import HerReplayBuffer
 
             ctor["replay_buffer_class"], ctor["replay_buffer_kwargs"] = HerReplayBuffer, dict(data.get("her_kwargs", {}))
+        if "n_steps" in data and getattr(cls, "supports_n_steps", False):  # an off-policy model saved with n_steps > 1
+            ctor["n_steps"] = int(data["n_steps"])
         if "train_freq" in data and isinstance(data["train_freq"], list):
             ctor["train_freq"] = (int(data["train_freq"][0]), str(data["train_freq"][1]))
         ctor.update(kwargs)

@@ -26,7 +26,8 @@ import torch as th
 
 from core.common import hip_ops, legacy_rng
 from core.common.spaces import as_box, as_discrete, as_multi_discrete, get_action_dim, get_obs_shape
-from core.common.type_aliases import GoalRolloutBufferSamples, PrioritizedReplayBufferSamples, ReplayBufferSamples, RolloutBufferSamples
+from core.common.type_aliases import (GoalRolloutBufferSamples, NStepReplayBufferSamples, PrioritizedReplayBufferSamples, ReplayBufferSamples,
+                                      RolloutBufferSamples)
 from core.common.utils import get_device
 
 
@@ -441,6 +442,100 @@ class PrioritizedReplayBuffer(ReplayBuffer):
         raise NotImplementedError("PrioritizedReplayBuffer: packed and pre-drawn batches are not built (sample / sample_into only)")
 
     alloc_packed_batch = sample_packed_into = predraw_indices = note_predrawn = take_predrawn = _not_built
+
+
+class NStepReplayBuffer(ReplayBuffer):
+    """`ReplayBuffer` whose samples carry n-step returns (Stable-Baselines3's NStepReplayBuffer): for a sampled (row, env) the window is
+    the same env column of the following rows; it ends at the first done / timeout, at the newest written row, or after `n_steps`
+    steps, m in all. rewards = sum_k gamma^k r_k over the window, next_observations / dones belong to its last step, discounts =
+    gamma^m, fold = 1 - (1 - dones) gamma^(m-1) (NStepReplayBufferSamples). The index draw is the one-step sampler's, word for word;
+    the window walk, the return and the copies are one launch with it (hip_ops.replay_sample_nstep*, a lane group per sampled row).
+
+    Indices a rollout launch drew ahead are gathered by hip_ops.replay_gather_nstep_packed: `take_predrawn` hands nothing to a first
+    layer, whose gather reads single slots. `n_steps == 1` runs the one-step launches; `fold` is then the `dones` tensor itself.
+
+    :param n_steps: window length, 1 .. 16
+    :param gamma: the discount of the return (the owning model's)
+    """
+
+    def __init__(self, buffer_size: int, observation_space, action_space, device: Union[th.device, str] = "auto", n_envs: int = 1,
+                 optimize_memory_usage: bool = False, handle_timeout_termination: bool = True, sampler_stream: Optional[th.Tensor] = None,
+                 n_steps: int = 3, gamma: float = 0.99):
+        self.n_steps, self.gamma = self._check_n_steps(n_steps), float(gamma)
+        super().__init__(buffer_size, observation_space, action_space, device, n_envs=n_envs, optimize_memory_usage=optimize_memory_usage,
+                         handle_timeout_termination=handle_timeout_termination, sampler_stream=sampler_stream)
+
+    @staticmethod
+    def _check_n_steps(n_steps) -> int:
+        if isinstance(n_steps, bool) or int(n_steps) != n_steps or not 1 <= int(n_steps) <= hip_ops.nv.NSTEP_MAX:
+            raise ValueError(f"n_steps must be an integer in [1, {hip_ops.nv.NSTEP_MAX}], got {n_steps!r}")
+        return int(n_steps)
+
+    def __getstate__(self) -> dict:
+        st = super().__getstate__()
+        st.update(n_steps=self.n_steps, gamma=self.gamma)
+        return st
+
+    def __setstate__(self, st: dict) -> None:
+        self.n_steps, self.gamma = self._check_n_steps(st["n_steps"]), float(st["gamma"])
+        super().__setstate__(st)
+
+    @classmethod
+    def from_arrays(cls, *args, n_steps: int = 3, gamma: float = 0.99, **kwargs) -> "NStepReplayBuffer":
+        rb = super().from_arrays(*args, **kwargs)
+        rb.n_steps, rb.gamma = cls._check_n_steps(n_steps), float(gamma)
+        return rb
+
+    def _with_nstep_fields(self, five: ReplayBufferSamples) -> NStepReplayBufferSamples:
+        b = five.dones.shape[0]
+        if self.n_steps == 1:  # the one-step launches fill the five fields; a window of one step has gamma^1 and fold == dones
+            return NStepReplayBufferSamples(*five, th.full((b, 1), np.float32(self.gamma), dtype=th.float32, device=self.device), five.dones)
+        e = lambda: th.empty(b, 1, dtype=th.float32, device=self.device)  # noqa: E731
+        return NStepReplayBufferSamples(*five, e(), e())
+
+    def alloc_batch(self, batch_size: int) -> NStepReplayBufferSamples:
+        return self._with_nstep_fields(super().alloc_batch(batch_size))
+
+    def alloc_packed_batch(self, batch_size: int, with_pi: bool = True) -> "PackedBatch":
+        pb = super().alloc_packed_batch(batch_size, with_pi)
+        pb.samples = self._with_nstep_fields(pb.samples)
+        return pb
+
+    def sample_into(self, out: NStepReplayBufferSamples, row_idx=None, env_idx=None, env=None) -> NStepReplayBufferSamples:
+        if self.n_steps == 1:
+            return super().sample_into(out, row_idx, env_idx, env)
+        if self.size() == 0:
+            raise ValueError("high <= 0")
+        if env is not None or self.normalizer is not None:
+            raise NotImplementedError("NStepReplayBuffer: VecNormalize would have to normalise each reward before the sum; not built")
+        self._no_predrawn("NStepReplayBuffer.sample")
+        with th.cuda.device(self.device):
+            hip_ops.replay_sample_nstep(self.ring, self.sampler_stream, out.observations.shape[0], self.n_steps, self.gamma, out.observations,
+                                        out.actions, out.next_observations, out.dones, out.rewards, out.discounts, out.fold, row_idx, env_idx)
+        return out
+
+    def sample_packed_into(self, pb: "PackedBatch", row_idx=None, env_idx=None) -> "PackedBatch":
+        if self.n_steps == 1:
+            return super().sample_packed_into(pb, row_idx, env_idx)
+        if self.size() == 0:
+            raise ValueError("high <= 0")
+        if self.normalizer is not None:
+            raise ValueError("packed batches do not go through VecNormalize")
+        s, batch = pb.samples, pb.x_data.shape[0]
+        with th.cuda.device(self.device):
+            if self._predrawn is not None:  # the rollout launch's indices: the row it wrote at the ring position is the newest one
+                (idx, rng_advance), self._predrawn = self._predrawn, None
+                if idx.shape[1] != batch:
+                    raise RuntimeError(f"pre-drawn sample of {idx.shape[1]} rows, batch of {batch}")
+                hip_ops.replay_gather_nstep_packed(self.ring, idx, batch, self.n_steps, self.gamma, pb.x_data, pb.x_next, pb.x_pi, s.dones,
+                                                   s.rewards, s.discounts, s.fold, row_idx, env_idx, advance_ring=True, rng_advance=rng_advance)
+            else:
+                hip_ops.replay_sample_nstep_packed(self.ring, self.sampler_stream, batch, self.n_steps, self.gamma, pb.x_data, pb.x_next,
+                                                   pb.x_pi, s.dones, s.rewards, s.discounts, s.fold, row_idx, env_idx)
+        return pb
+
+    def take_predrawn(self, pb: "PackedBatch"):
+        return super().take_predrawn(pb) if self.n_steps == 1 else None
 
 
 class PackedBatch:

@@ -32,6 +32,7 @@ from torch import nn
 
 from core import _native as nv
 from core.common import fused, hip_ops
+from core.common.type_aliases import td_done
 
 USE_CHAIN = os.environ.get("CSTR_CHAIN", "1") != "0"
 # single GPU: the dW / db launch applies the Adam step to the tiles it has reduced (cstr_linear_bwd_weight_adam_sets_f32): 8 launches
@@ -127,7 +128,7 @@ class TwinCriticBlock:
 
     def td_root(self, rd, gamma: float, scale: float, target_out, loss_out, loss_sum, **kw):
         """kw: next_logp, ent_coef, alpha, rng_advance, adam_advance of hip_ops.chain_root."""
-        return hip_ops.chain_root("td", self.B, self.q_part4, self.b3s, self.n_q4, gamma=gamma, scale=scale, rew=rd.rewards, done=rd.dones,
+        return hip_ops.chain_root("td", self.B, self.q_part4, self.b3s, self.n_q4, gamma=gamma, scale=scale, rew=rd.rewards, done=td_done(rd),
                                   target_out=target_out, q_out=self.q_out, gq_out=self.gq, loss_out=loss_out, loss_sum=loss_sum, **kw)
 
     def pi_root(self, mode: str, **kw):
@@ -321,7 +322,8 @@ class SacChain:
             else:
                 model.actor.optimizer.step()
         if model.debug_capture:
-            model.last_train_tensors = blk.captured(model._target_q, c_out, a_out, ent_coef=ent_coef.detach().clone(), log_prob=self.logp_pi.clone())
+            model.last_train_tensors = blk.captured(model._target_q, c_out, a_out, ent_coef=ent_coef.detach().clone(), log_prob=self.logp_pi.clone(),
+                                                    next_log_prob=self.logp_next.clone())
 
 
 class Td3Chain:

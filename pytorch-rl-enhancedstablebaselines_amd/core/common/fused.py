@@ -37,6 +37,7 @@ import torch as th
 from torch import nn
 
 from core.common import hip_ops
+from core.common.type_aliases import td_done
 
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2
 
@@ -1400,14 +1401,14 @@ class PerLayerTwinCritic:
         gq, n = self._scratch(qs[0]), len(qs)
         root = None
         if n == 2 and self._rides(qs):  # the reductions ride in the critic backward's first launch
-            root = dict(mode="td", q1_t=qs_t[0], q2_t=qs_t[1], next_logp=next_logp, rew=rd.rewards, done=rd.dones, ent_coef=ent_coef,
+            root = dict(mode="td", q1_t=qs_t[0], q2_t=qs_t[1], next_logp=next_logp, rew=rd.rewards, done=td_done(rd), ent_coef=ent_coef,
                         gamma=gamma, scale=scale, q1=qs[0].detach(), q2=qs[1].detach(), target_out=target_out, loss_out=loss_out,
                         loss_sum=loss_sum, alpha=alpha)
         elif self.ensemble:  # the min over all N targets, the loss over all N critics
-            hip_ops.td_ens_q_loss(qs_t, next_logp, rd.rewards, rd.dones, ent_coef, gamma, qs, scale, target_out, gq if gq.shape[0] == n else gq[:n],
+            hip_ops.td_ens_q_loss(qs_t, next_logp, rd.rewards, td_done(rd), ent_coef, gamma, qs, scale, target_out, gq if gq.shape[0] == n else gq[:n],
                                   loss_out, loss_sum, alpha=alpha)
         else:  # (one critic: loss = mse(q1, t) is half the doubled term)
-            hip_ops.td_twin_q_loss(qs_t[0], qs_t[-1], next_logp, rd.rewards, rd.dones, ent_coef, gamma, qs[0], qs[-1], scale if n == 2 else 0.5 * scale,
+            hip_ops.td_twin_q_loss(qs_t[0], qs_t[-1], next_logp, rd.rewards, td_done(rd), ent_coef, gamma, qs[0], qs[-1], scale if n == 2 else 0.5 * scale,
                                    target_out, gq[0], gq[1], loss_out, loss_sum, alpha=alpha)
         if root is None and after_loss is not None:
             after_loss()

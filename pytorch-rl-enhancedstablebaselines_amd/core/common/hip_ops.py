@@ -232,6 +232,63 @@ def replay_gather_packed(ring: DeviceRing, sample_idx, batch: int, x_data, x_nex
           "cstr_replay_gather_packed_f32")
 
 
+def _nstep_common(batch: int, n_steps: int, gamma: float, out_done, out_rew, out_discount, out_fold, out_row_idx, out_env_idx):
+    """the operands every n-step launch shares -> the by-value gamma-power table"""
+    if not 1 <= int(n_steps) <= nv.NSTEP_MAX:
+        raise ValueError(f"n_steps must be in [1, {nv.NSTEP_MAX}], got {n_steps}")
+    if not 0 < batch <= nv.MAX_SAMPLE_BATCH:
+        raise ValueError(f"batch_size must be in [1, {nv.MAX_SAMPLE_BATCH}], got {batch}")
+    for t, nm in ((out_done, "out_done"), (out_rew, "out_rew"), (out_discount, "out_discount"), (out_fold, "out_fold")):
+        _chk(t, nm, (batch, 1), th.float32)
+    _opt(out_row_idx, "out_row_idx", (batch,), th.int64), _opt(out_env_idx, "out_env_idx", (batch,), th.int64)
+    return nv.NStepGpow.of(gamma)
+
+
+def replay_sample_nstep(ring: DeviceRing, mt_state, batch: int, n_steps: int, gamma: float, out_obs, out_act, out_next_obs, out_done, out_rew,
+                        out_discount, out_fold, out_row_idx=None, out_env_idx=None):
+    """`replay_sample`'s index draw with the n-step gather behind it (cstr_replay_sample_nstep_mt19937_f32): rewards = the discounted
+    return up to the first stop, next observations / dones from that step, discounts = gamma^m, fold = 1 - (1 - dones) gamma^(m-1)."""
+    d, a = ring.obs_dim, ring.act_dim
+    _chk(mt_state, "mt_state", (nv.MT_STATE_WORDS,), th.int32)
+    _chk(out_obs, "out_obs", (batch, d), th.float32), _chk(out_next_obs, "out_next_obs", (batch, d), th.float32)
+    _chk(out_act, "out_act", (batch, a), th.float32)
+    gpow = _nstep_common(batch, n_steps, gamma, out_done, out_rew, out_discount, out_fold, out_row_idx, out_env_idx)
+    check(nv.lib().cstr_replay_sample_nstep_mt19937_f32(C.byref(ring.c), ptr(ring.ctl), ptr(mt_state), C.c_int64(batch), C.c_int(n_steps), gpow,
+                                                        ptr(out_obs), ptr(out_act), ptr(out_next_obs), ptr(out_done), ptr(out_rew),
+                                                        ptr(out_discount), ptr(out_fold), ptr(out_row_idx), ptr(out_env_idx), stream_ptr()),
+          "cstr_replay_sample_nstep_mt19937_f32")
+
+
+def replay_sample_nstep_packed(ring: DeviceRing, mt_state, batch: int, n_steps: int, gamma: float, x_data, x_next, x_pi, out_done, out_rew,
+                               out_discount, out_fold, out_row_idx=None, out_env_idx=None):
+    """`replay_sample_nstep` gathered into the critic-input rows of `replay_sample_packed`."""
+    w = ring.obs_dim + ring.act_dim
+    _chk(mt_state, "mt_state", (nv.MT_STATE_WORDS,), th.int32)
+    _chk(x_data, "x_data", (batch, w), th.float32), _chk(x_next, "x_next", (batch, w), th.float32), _opt(x_pi, "x_pi", (batch, w), th.float32)
+    gpow = _nstep_common(batch, n_steps, gamma, out_done, out_rew, out_discount, out_fold, out_row_idx, out_env_idx)
+    check(nv.lib().cstr_replay_sample_nstep_packed_mt19937_f32(C.byref(ring.c), ptr(ring.ctl), ptr(mt_state), C.c_int64(batch), C.c_int(n_steps),
+                                                               gpow, ptr(x_data), ptr(x_next), ptr(x_pi), ptr(out_done), ptr(out_rew),
+                                                               ptr(out_discount), ptr(out_fold), ptr(out_row_idx), ptr(out_env_idx), stream_ptr()),
+          "cstr_replay_sample_nstep_packed_mt19937_f32")
+
+
+def replay_gather_nstep_packed(ring: DeviceRing, sample_idx, batch: int, n_steps: int, gamma: float, x_data, x_next, x_pi, out_done, out_rew,
+                               out_discount, out_fold, out_row_idx=None, out_env_idx=None, advance_ring: bool = False, rng_advance=None):
+    """The n-step gather for index pairs drawn by `rollout_step` (sample_idx int32 [2, batch]), with `replay_gather_packed`'s control-word
+    updates. advance_ring: the rollout launch has written the row at the ring position, which is then the newest row."""
+    w = ring.obs_dim + ring.act_dim
+    _chk(sample_idx, "sample_idx", (2, batch), th.int32)
+    _chk(x_data, "x_data", (batch, w), th.float32), _chk(x_next, "x_next", (batch, w), th.float32), _opt(x_pi, "x_pi", (batch, w), th.float32)
+    gpow = _nstep_common(batch, n_steps, gamma, out_done, out_rew, out_discount, out_fold, out_row_idx, out_env_idx)
+    rng_ctl, rng_count = rng_advance if rng_advance is not None else (None, 0)
+    _opt(rng_ctl, "rng_ctl", (nv.RNG_CTL_WORDS,), th.int64)
+    check(nv.lib().cstr_replay_gather_nstep_packed_f32(C.byref(ring.c), ptr(ring.ctl), C.c_int(1 if advance_ring else 0), ptr(rng_ctl),
+                                                       C.c_uint64(int(rng_count)), ptr(sample_idx), C.c_int64(batch), C.c_int(n_steps), gpow,
+                                                       ptr(x_data), ptr(x_next), ptr(x_pi), ptr(out_done), ptr(out_rew), ptr(out_discount),
+                                                       ptr(out_fold), ptr(out_row_idx), ptr(out_env_idx), stream_ptr()),
+          "cstr_replay_gather_nstep_packed_f32")
+
+
 def linear_act_fwd_gather(ring: DeviceRing, sample_idx, batch: int, both: bool, weight, bias, act: int, x_data, x_next, x_pi, out_done,
                           out_rew, advance_ring: bool = False, rng_advance=None, out=None):
     """`replay_gather_packed` fused into the first Linear layer behind it (cstr_linear_act_fwd_gather_f32): y = act(x W^T + b) with

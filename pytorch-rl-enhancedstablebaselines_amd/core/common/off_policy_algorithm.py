@@ -18,7 +18,7 @@ import torch as th
 
 from core.common import blas, chain, fused, hip_ops
 from core.common.base_class import BaseAlgorithm
-from core.common.buffers import PrioritizedReplayBuffer, ReplayBuffer
+from core.common.buffers import NStepReplayBuffer, PrioritizedReplayBuffer, ReplayBuffer
 from core.common.callbacks import BaseCallback, MaybeCallback
 from core.common.graph_replay import GraphReplay
 from core.common.logger import DeviceMean
@@ -41,6 +41,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
     chain_type: Optional[type] = None       # the row-chain form of this class's gradient step (core/common/chain.py)
     _single_step = False                    # this train() call is ONE gradient step whose loss kernels store the logged values
     supports_prioritized_replay = False     # the class's loss launch takes importance weights and returns |td| (DQN)
+    supports_n_steps = True                 # n-step returns (NStepReplayBuffer): not the offline and the multi-agent classes
 
     def __init__(self, policy, env, learning_rate, buffer_size: int = 1_000_000, learning_starts: int = 100,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = (1, "step"),
@@ -48,7 +49,10 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
                  optimize_memory_usage: bool = False, policy_kwargs: Optional[dict] = None, stats_window_size: int = 100,
                  tensorboard_log: Optional[str] = None, verbose: int = 0, device="auto", support_multi_env: bool = False,
                  monitor_wrapper: bool = True, seed: Optional[int] = None, use_sde: bool = False, sde_sample_freq: int = -1,
-                 use_sde_at_warmup: bool = False, sde_support: bool = True, supported_action_spaces: Optional[tuple] = None):
+                 use_sde_at_warmup: bool = False, sde_support: bool = True, supported_action_spaces: Optional[tuple] = None, *,
+                 n_steps: int = 1):
+        n_steps = NStepReplayBuffer._check_n_steps(n_steps)
+        self._check_n_step_buffer(n_steps, replay_buffer_class, replay_buffer_kwargs)
         if use_sde and not sde_support:  # TD3 / DDPG / MADDPG / IDDPG (sde_support=False in the reference too)
             raise ValueError(f"{type(self).__name__} does not support gSDE (use_sde=True)")
         super().__init__(policy=policy, env=env, learning_rate=learning_rate, policy_kwargs=policy_kwargs,
@@ -70,6 +74,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
             raise NotImplementedError(f"{type(self).__name__} does not take a PrioritizedReplayBuffer: its loss kernels have no importance weights (DQN does)")
         self.replay_buffer_class = replay_buffer_class
         self.replay_buffer_kwargs = replay_buffer_kwargs or {}
+        self.n_steps = n_steps
         self.train_freq = train_freq
         self.use_sde_at_warmup = use_sde_at_warmup
         self._init_graph_state()
@@ -80,6 +85,48 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         self._ep_window = (0.0, 0.0, 0.0)
 
     # ---- setup ----------------------------------------------------------------------------------------------------
+    @classmethod
+    def _check_n_step_buffer(cls, n_steps: int, replay_buffer_class, replay_buffer_kwargs) -> None:
+        """What n-step returns are not built with, refused before anything is allocated."""
+        is_nstep = isinstance(replay_buffer_class, type) and issubclass(replay_buffer_class, NStepReplayBuffer)
+        kw_steps = (replay_buffer_kwargs or {}).get("n_steps", None)
+        if is_nstep and kw_steps is not None:
+            kw_steps = NStepReplayBuffer._check_n_steps(kw_steps)
+            if n_steps > 1 and kw_steps != n_steps:
+                raise ValueError(f"n_steps={n_steps} and replay_buffer_kwargs['n_steps']={kw_steps} disagree")
+        if n_steps == 1 and not is_nstep:
+            return
+        if not cls.supports_n_steps:
+            raise NotImplementedError(f"{cls.__name__} does not take n-step returns (n_steps > 1 / NStepReplayBuffer): not built for the offline "
+                                      "and the multi-agent classes")
+        if n_steps > 1 and replay_buffer_class is not None and not is_nstep:
+            from core.her import HerReplayBuffer
+
+            what = ("PrioritizedReplayBuffer" if issubclass(replay_buffer_class, PrioritizedReplayBuffer) else
+                    "HerReplayBuffer (the goal face)" if issubclass(replay_buffer_class, HerReplayBuffer) else replay_buffer_class.__name__)
+            raise NotImplementedError(f"n_steps={n_steps} does not combine with {what}: n-step returns come from NStepReplayBuffer")
+
+    def _n_step_setup(self) -> None:
+        """n_steps > 1 and no buffer class named: NStepReplayBuffer(n_steps, gamma); a named NStepReplayBuffer gets the model's gamma."""
+        is_nstep = isinstance(self.replay_buffer_class, type) and issubclass(self.replay_buffer_class, NStepReplayBuffer)
+        if self.n_steps == 1 and not is_nstep:
+            return
+        what = f"{type(self).__name__} with n-step returns"
+        if self.goal_space is not None:
+            raise NotImplementedError(f"{what} does not run on the goal face (HerReplayBuffer)")
+        if self._vec_normalize_env is not None:
+            raise NotImplementedError(f"{what} does not take a VecNormalize-wrapped env: each reward would have to be normalised before the sum")
+        if self.world_size > 1:
+            raise NotImplementedError(f"{what} does not run data-parallel (world_size = {self.world_size})")
+        if self.replay_buffer_class is None:
+            self.replay_buffer_class = NStepReplayBuffer
+        kw = dict(self.replay_buffer_kwargs)
+        if self.n_steps > 1:
+            kw["n_steps"] = self.n_steps
+        kw["gamma"] = self.gamma
+        self.replay_buffer_kwargs = kw
+        self.n_steps = int(kw.get("n_steps", 3))
+
     def _convert_train_freq(self) -> None:
         """reference: off_policy_algorithm.py:148-170"""
         if not isinstance(self.train_freq, TrainFreq):
@@ -107,6 +154,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
         if self.world_size > 1 and self._denv is not None:
             self._denv.seed_offset = self.rank * self.n_envs  # seed_r = seed + rank * n_envs
         self.set_random_seed(self.seed)
+        self._n_step_setup()
         if self.replay_buffer_class is None:
             self.replay_buffer_class = ReplayBuffer
         from core.her import HerReplayBuffer
@@ -183,7 +231,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
     def _fast_path(self) -> bool:
         rb = self.replay_buffer
         env = self._denv
-        stock = type(rb) is ReplayBuffer or (self.supports_prioritized_replay and type(rb) is PrioritizedReplayBuffer)
+        stock = type(rb) in (ReplayBuffer, NStepReplayBuffer) or (self.supports_prioritized_replay and type(rb) is PrioritizedReplayBuffer)
         return (env is not None and stock and rb.n_envs == env.num_envs
                 and rb.obs_shape[0] == env.obs_dim and rb.action_dim == env.act_dim)
 
@@ -374,7 +422,7 @@ class OffPolicyAlgorithm(GraphReplay, BaseAlgorithm):
 
     def _stock_buffer(self) -> bool:
         """The HBM `ReplayBuffer` itself, without a VecNormalize normaliser: its rows can be sampled straight into critic-input rows."""
-        return type(self.replay_buffer) is ReplayBuffer and self.replay_buffer.normalizer is None
+        return type(self.replay_buffer) in (ReplayBuffer, NStepReplayBuffer) and self.replay_buffer.normalizer is None
 
     def _batch(self, batch_size: int):
         """The contiguous sample tensors (and this class's step tensors) for `batch_size`; they replace a packed batch."""

@@ -76,6 +76,8 @@ class OfflineAlgorithm(OffPolicyAlgorithm):
     """reference :52-371. `behavior_cloning_warmup`, `conservative_weight` and `n_eval_episodes` are stored; what the reference does
     with them is the subclass's."""
 
+    supports_n_steps = False  # the dataset's transitions are one-step tuples
+
     def __init__(self, policy, env, learning_rate, dataset: Union[str, ReplayBuffer, None] = None, buffer_size: int = 1_000_000,
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, gradient_steps: int = 1, dataset_buffer_class=None,
                  dataset_buffer_kwargs: Optional[dict] = None, n_eval_episodes: int = 10, behavior_cloning_warmup: int = 0,

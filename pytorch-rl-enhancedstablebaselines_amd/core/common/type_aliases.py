@@ -25,6 +25,29 @@ class PrioritizedReplayBufferSamples(NamedTuple):
     leaf_indices: th.Tensor
 
 
+class NStepReplayBufferSamples(NamedTuple):
+    """What NStepReplayBuffer samples: the five fields (rewards = the discounted n-step return, next_observations / dones of the step
+    the window ends at), then `discounts` [B, 1] = gamma^m for a window of m steps and `fold` [B, 1] = 1 - (1 - dones) gamma^(m-1):
+    the value a TD-target launch with a scalar gamma takes in place of `dones`, (1 - fold) gamma == (1 - dones) discounts."""
+    observations: th.Tensor
+    actions: th.Tensor
+    next_observations: th.Tensor
+    dones: th.Tensor
+    rewards: th.Tensor
+    discounts: th.Tensor
+    fold: th.Tensor
+
+
+def td_done(samples) -> th.Tensor:
+    """The termination operand of the TD-target launches: `fold` of an n-step sample, `dones` of every other one."""
+    return getattr(samples, "fold", samples.dones)
+
+
+def td_discount(samples, gamma: float):
+    """The discount of the torch-statement targets, rewards + (1 - dones) * discount * next_q: `discounts` of an n-step sample, else gamma."""
+    return getattr(samples, "discounts", gamma)
+
+
 class DictReplayBufferSamples(NamedTuple):
     """reference: core/common/type_aliases.py (DictReplayBufferSamples); observations / next_observations: {key: tensor}"""
     observations: dict

@@ -42,7 +42,7 @@ from core.common.buffers import PrioritizedReplayBuffer, ReplayBuffer
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
 from core.common.spaces import Discrete
-from core.common.type_aliases import TrainFrequencyUnit
+from core.common.type_aliases import TrainFrequencyUnit, td_discount, td_done
 from core.common.utils import get_linear_fn
 from core.common.vec_env.cstr_vec_env import decode_valve_index
 from core.dqn.policies import MlpPolicy
@@ -68,12 +68,12 @@ class DQN(OffPolicyAlgorithm):
                  target_update_interval: int = 10000, exploration_fraction: float = 0.1, exploration_initial_eps: float = 1.0,
                  exploration_final_eps: float = 0.05, max_grad_norm: float = 10, stats_window_size: int = 100,
                  tensorboard_log: Optional[str] = None, policy_kwargs: Optional[dict] = None, verbose: int = 0, seed: Optional[int] = None,
-                 device: Union[th.device, str] = "auto", _init_setup_model: bool = True, faithful_quirks: bool = True):
+                 device: Union[th.device, str] = "auto", _init_setup_model: bool = True, faithful_quirks: bool = True, *, n_steps: int = 1):
         super().__init__(policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq, gradient_steps,
                          action_noise=None, replay_buffer_class=replay_buffer_class, replay_buffer_kwargs=replay_buffer_kwargs,
                          policy_kwargs=policy_kwargs, stats_window_size=stats_window_size, tensorboard_log=tensorboard_log,
                          verbose=verbose, device=device, seed=seed, sde_support=False, optimize_memory_usage=optimize_memory_usage,
-                         supported_action_spaces=(Discrete,), support_multi_env=True)
+                         supported_action_spaces=(Discrete,), support_multi_env=True, n_steps=n_steps)
         if self.env is None:
             raise ValueError("DQN needs its environment at construction: CSTRVecEnv(num_envs, discrete_actions=K)")
         if self._vec_normalize_env is not None:
@@ -105,6 +105,7 @@ class DQN(OffPolicyAlgorithm):
         env = self._denv
         self.levels = env.discrete_actions
         if self.replay_buffer is None:  # the ring holds the valve pair: the buffer is built over the env's valve space
+            self._n_step_setup()  # n_steps > 1: NStepReplayBuffer with the model's gamma
             if self.replay_buffer_class is None:
                 self.replay_buffer_class = ReplayBuffer
             self.replay_buffer = self.replay_buffer_class(self.buffer_size, self.observation_space, env.valve_space, device=self.device,
@@ -290,6 +291,8 @@ class DQN(OffPolicyAlgorithm):
             bi, ei = ((th.empty(batch_size, dtype=th.int64, device=self.device) for _ in range(2)) if self.debug_capture else (None, None))
             return self.replay_buffer.sample_into(rd, bi, ei, u=u), bi, ei
         if self.batch_queue:
+            if hasattr(rd, "fold") and rd.fold is not rd.dones:
+                raise ValueError("batch_queue teacher-forces one-step batches: it carries no discounts / fold for n_steps > 1")
             obs, index, next_obs, reward, done = self.batch_queue.pop(0)
             valve = decode_valve_index(np.asarray(index).reshape(-1), self.levels)
             for dst, src in zip((rd.observations, rd.actions, rd.next_observations, rd.dones, rd.rewards), (obs, valve, next_obs, done, reward)):
@@ -329,7 +332,7 @@ class DQN(OffPolicyAlgorithm):
         l_out, l_sum = self._loss_slot("loss")
         cap = self.debug_capture
         per = dict(weights=rd.weights, td_abs_out=self._td_abs) if self._per else {}
-        hip_ops.dqn_loss(q.detach(), next_q, rd.actions, rd.rewards, rd.dones, self.gamma, self.levels, self._g_q, l_out, self._ws,
+        hip_ops.dqn_loss(q.detach(), next_q, rd.actions, rd.rewards, td_done(rd), self.gamma, self.levels, self._g_q, l_out, self._ws,
                          loss_sum=l_sum, cur_q_out=self._cur_q if cap else None, target_out=self._target_q if cap else None, **per)
         with fused.deferred_weight_grads():
             th.autograd.backward([q], [self._g_q])
@@ -348,7 +351,7 @@ class DQN(OffPolicyAlgorithm):
             next_q_values = self.q_net_target(rd.next_observations)
             next_q_values, _ = next_q_values.max(dim=1)
             next_q_values = next_q_values.reshape(-1, 1)
-            target_q_values = rd.rewards + (1 - rd.dones) * self.gamma * next_q_values
+            target_q_values = rd.rewards + (1 - rd.dones) * td_discount(rd, self.gamma) * next_q_values
         current_q_values = self.q_net(rd.observations)
         current_q_values = th.gather(current_q_values, dim=1, index=index)
         if self._per:  # importance-weighted Huber loss; |td| are the sampled slots' new priorities

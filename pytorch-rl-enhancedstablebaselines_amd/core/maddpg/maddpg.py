@@ -36,6 +36,7 @@ BATCH_AGENT_CRITIC_STEPS = os.environ.get("CSTR_MADDPG_BATCH_AGENTS", "1") != "0
 class MADDPG(OffPolicyAlgorithm):
     policy_aliases = {"MlpPolicy": MlpPolicy}
     chain_type = MaddpgCriticChain  # the critic steps (and the actor loss through the critic) only
+    supports_n_steps = False
 
     def __init__(self, n_agents: int, policy, env, observation_splits: List[List[int]], action_splits: List[List[int]],
                  learning_rate_list=1e-3, buffer_size: int = 1_000_000, learning_starts: int = 100, batch_size: int = 256,

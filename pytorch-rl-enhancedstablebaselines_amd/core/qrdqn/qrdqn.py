@@ -29,6 +29,7 @@ from typing import Optional, Union
 import torch as th
 
 from core.common import fused, hip_ops
+from core.common.type_aliases import td_discount, td_done
 from core.dqn.dqn import DQN
 from core.qrdqn.policies import MlpPolicy
 
@@ -57,7 +58,7 @@ class QRDQN(DQN):
                  target_update_interval: int = 10000, exploration_fraction: float = 0.005, exploration_initial_eps: float = 1.0,
                  exploration_final_eps: float = 0.01, max_grad_norm: Optional[float] = None, stats_window_size: int = 100,
                  tensorboard_log: Optional[str] = None, policy_kwargs: Optional[dict] = None, verbose: int = 0, seed: Optional[int] = None,
-                 device: Union[th.device, str] = "auto", _init_setup_model: bool = True, faithful_quirks: bool = True):
+                 device: Union[th.device, str] = "auto", _init_setup_model: bool = True, faithful_quirks: bool = True, *, n_steps: int = 1):
         policy_kwargs = self.default_policy_kwargs(policy_kwargs, batch_size)
         self.n_quantiles = int(policy_kwargs.get("n_quantiles", 200))
         super().__init__(policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq, gradient_steps,
@@ -66,7 +67,7 @@ class QRDQN(DQN):
                          exploration_fraction=exploration_fraction, exploration_initial_eps=exploration_initial_eps,
                          exploration_final_eps=exploration_final_eps, max_grad_norm=max_grad_norm, stats_window_size=stats_window_size,
                          tensorboard_log=tensorboard_log, policy_kwargs=policy_kwargs, verbose=verbose, seed=seed, device=device,
-                         _init_setup_model=_init_setup_model, faithful_quirks=faithful_quirks)
+                         _init_setup_model=_init_setup_model, faithful_quirks=faithful_quirks, n_steps=n_steps)
 
     @staticmethod
     def default_policy_kwargs(policy_kwargs: Optional[dict], batch_size: int) -> dict:
@@ -130,7 +131,7 @@ class QRDQN(DQN):
         z = self._fast_q(rd.observations, train_params=True)
         l_out, l_sum = self._loss_slot("loss")
         cap = self.debug_capture
-        hip_ops.qrdqn_loss(z.detach(), z_next, rd.actions, rd.rewards, rd.dones, self.gamma, self.levels, self.n_quantiles, self._gz,
+        hip_ops.qrdqn_loss(z.detach(), z_next, rd.actions, rd.rewards, td_done(rd), self.gamma, self.levels, self.n_quantiles, self._gz,
                            self._row_ws, loss_out=l_out, loss_sum=l_sum, cur_out=self._cur_z if cap else None,
                            target_out=self._target_z if cap else None, next_index_out=self._next_index if cap else None)
         with fused.deferred_weight_grads():
@@ -152,7 +153,7 @@ class QRDQN(DQN):
             self._next_index.copy_(next_greedy_actions.reshape(-1))
             next_greedy_actions = next_greedy_actions.expand(batch_size, nq, 1)
             next_quantiles = next_quantiles.gather(dim=2, index=next_greedy_actions).squeeze(dim=2)
-            target_quantiles = rd.rewards + (1 - rd.dones) * self.gamma * next_quantiles
+            target_quantiles = rd.rewards + (1 - rd.dones) * td_discount(rd, self.gamma) * next_quantiles
         current_quantiles = self.quantile_net(rd.observations)
         actions = index[..., None].expand(batch_size, nq, 1)
         current_quantiles = th.gather(current_quantiles, dim=2, index=actions).squeeze(dim=2)

@@ -17,6 +17,7 @@ from core.common.arena import FlatAdam, ParamArena
 from core.common.chain import SacChain
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
+from core.common.type_aliases import td_discount, td_done
 from core.sac.policies import MlpPolicy, MultiInputPolicy
 
 
@@ -34,9 +35,9 @@ class SAC(OffPolicyAlgorithm):
                  target_entropy: Union[str, float] = "auto", use_sde: bool = False, sde_sample_freq: int = -1,
                  use_sde_at_warmup: bool = False, stats_window_size: int = 100, tensorboard_log: Optional[str] = None,
                  policy_kwargs: Optional[dict] = None, verbose: int = 0, seed: Optional[int] = None, device="auto",
-                 _init_setup_model: bool = True):
+                 _init_setup_model: bool = True, *, n_steps: int = 1):
         super().__init__(policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq,
-                         gradient_steps, action_noise, replay_buffer_class=replay_buffer_class,
+                         gradient_steps, action_noise, n_steps=n_steps, replay_buffer_class=replay_buffer_class,
                          replay_buffer_kwargs=replay_buffer_kwargs, policy_kwargs=policy_kwargs,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, verbose=verbose, device=device,
                          seed=seed, use_sde=use_sde, sde_sample_freq=sde_sample_freq, use_sde_at_warmup=use_sde_at_warmup,
@@ -217,7 +218,7 @@ class SAC(OffPolicyAlgorithm):
 
         if self.debug_capture:
             self.last_train_tensors = blk.captured(qs, self._target_q, c_out, a_out, ent_coef=ent_coef.detach().clone(),
-                                                   log_prob=log_prob.detach().clone())
+                                                   log_prob=log_prob.detach().clone(), next_log_prob=next_log_prob.detach().clone())
 
     def _ent_coef_step(self) -> None:
         self._allreduce_grads(self._ent_arena)
@@ -257,11 +258,11 @@ class SAC(OffPolicyAlgorithm):
                 q1_t, q2_t = qs_t
                 target_q_values = self._target_q
                 hip_ops.td_target_min(q1_t.contiguous(), q2_t.contiguous(), next_log_prob.reshape(-1, 1).contiguous(),
-                                      replay_data.rewards, replay_data.dones, ent_coef.contiguous(), self.gamma, target_q_values)
+                                      replay_data.rewards, td_done(replay_data), ent_coef.contiguous(), self.gamma, target_q_values)
             else:  # critic ensembles: the reference's own statements (:248-253)
                 next_q_values, _ = th.min(th.cat(qs_t, dim=1), dim=1, keepdim=True)
                 next_q_values = next_q_values - ent_coef * next_log_prob.reshape(-1, 1)
-                target_q_values = replay_data.rewards + (1 - replay_data.dones) * self.gamma * next_q_values
+                target_q_values = replay_data.rewards + (1 - replay_data.dones) * td_discount(replay_data, self.gamma) * next_q_values
 
         current_q_values = self.critic(replay_data.observations, replay_data.actions)  # :258
         critic_loss = 0.5 * sum(F.mse_loss(current_q, target_q_values) for current_q in current_q_values)  # :261

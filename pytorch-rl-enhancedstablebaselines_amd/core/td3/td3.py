@@ -9,6 +9,7 @@ from core.common import fused, hip_ops
 from core.common.chain import Td3Chain
 from core.common.logger import DeviceMean
 from core.common.off_policy_algorithm import OffPolicyAlgorithm
+from core.common.type_aliases import td_discount, td_done
 from core.td3.policies import MlpPolicy, MultiInputPolicy
 
 
@@ -25,9 +26,9 @@ class TD3(OffPolicyAlgorithm):
                  optimize_memory_usage: bool = False, policy_delay: int = 2, target_policy_noise: float = 0.2,
                  target_noise_clip: float = 0.5, stats_window_size: int = 100, tensorboard_log: Optional[str] = None,
                  policy_kwargs: Optional[dict] = None, verbose: int = 0, seed: Optional[int] = None, device="auto",
-                 _init_setup_model: bool = True):
+                 _init_setup_model: bool = True, *, n_steps: int = 1):
         super().__init__(policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq,
-                         gradient_steps, action_noise=action_noise, replay_buffer_class=replay_buffer_class,
+                         gradient_steps, action_noise=action_noise, n_steps=n_steps, replay_buffer_class=replay_buffer_class,
                          replay_buffer_kwargs=replay_buffer_kwargs, policy_kwargs=policy_kwargs,
                          stats_window_size=stats_window_size, tensorboard_log=tensorboard_log, verbose=verbose, device=device,
                          seed=seed, sde_support=False, optimize_memory_usage=optimize_memory_usage,
@@ -128,12 +129,12 @@ class TD3(OffPolicyAlgorithm):
                 qs = self.critic_target(replay_data.next_observations, next_actions)
                 if len(qs) <= 2:
                     q1_t, q2_t = qs[0], qs[-1]  # n_critics == 1 (DDPG): min over one network
-                    hip_ops.td_target_min(q1_t.contiguous(), q2_t.contiguous(), None, replay_data.rewards, replay_data.dones,
+                    hip_ops.td_target_min(q1_t.contiguous(), q2_t.contiguous(), None, replay_data.rewards, td_done(replay_data),
                                           None, self.gamma, self._target_q)
                     target_q_values = self._target_q
                 else:  # critic ensembles: the reference's own statements (:174-176)
                     next_q_values, _ = th.min(th.cat(qs, dim=1), dim=1, keepdim=True)
-                    target_q_values = replay_data.rewards + (1 - replay_data.dones) * self.gamma * next_q_values
+                    target_q_values = replay_data.rewards + (1 - replay_data.dones) * td_discount(replay_data, self.gamma) * next_q_values
             current_q_values = self.critic(replay_data.observations, replay_data.actions)
             critic_loss = sum(F.mse_loss(current_q, target_q_values) for current_q in current_q_values)  # no 0.5 (:182)
             self._loss_sums["critic"] += critic_loss.detach()
@@ -255,11 +256,11 @@ class DDPG(TD3):
                  batch_size: int = 256, tau: float = 0.005, gamma: float = 0.99, train_freq: Union[int, tuple] = 1,
                  gradient_steps: int = 1, action_noise=None, replay_buffer_class=None, replay_buffer_kwargs=None,
                  optimize_memory_usage: bool = False, tensorboard_log: Optional[str] = None, policy_kwargs: Optional[dict] = None,
-                 verbose: int = 0, seed: Optional[int] = None, device="auto", _init_setup_model: bool = True):
+                 verbose: int = 0, seed: Optional[int] = None, device="auto", _init_setup_model: bool = True, *, n_steps: int = 1):
         policy_kwargs = dict(policy_kwargs or {})
         policy_kwargs.setdefault("n_critics", 1)
         super().__init__(policy, env, learning_rate, buffer_size, learning_starts, batch_size, tau, gamma, train_freq,
                          gradient_steps, action_noise, replay_buffer_class, replay_buffer_kwargs, optimize_memory_usage,
                          policy_delay=1, target_policy_noise=0.1, target_noise_clip=0.0, tensorboard_log=tensorboard_log,
                          policy_kwargs=policy_kwargs, verbose=verbose, seed=seed, device=device,
-                         _init_setup_model=_init_setup_model)
+                         _init_setup_model=_init_setup_model, n_steps=n_steps)

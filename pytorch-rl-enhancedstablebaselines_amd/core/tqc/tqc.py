@@ -28,6 +28,7 @@ import torch as th
 
 from core.common import fused, hip_ops
 from core.common.logger import DeviceMean
+from core.common.type_aliases import td_discount, td_done
 from core.common.vec_env import unwrap_vec_normalize
 from core.sac.sac import SAC
 from core.tqc.policies import MlpPolicy
@@ -57,7 +58,7 @@ class TQC(SAC):
                  target_entropy: Union[str, float] = "auto", top_quantiles_to_drop_per_net: int = 2, use_sde: bool = False,
                  sde_sample_freq: int = -1, use_sde_at_warmup: bool = False, stats_window_size: int = 100,
                  tensorboard_log: Optional[str] = None, policy_kwargs: Optional[dict] = None, verbose: int = 0, seed: Optional[int] = None,
-                 device="auto", _init_setup_model: bool = True):
+                 device="auto", _init_setup_model: bool = True, *, n_steps: int = 1):
         from core.her import HerReplayBuffer
 
         if use_sde or (policy_kwargs and policy_kwargs.get("use_sde")):
@@ -79,7 +80,7 @@ class TQC(SAC):
                          action_noise, replay_buffer_class=replay_buffer_class, replay_buffer_kwargs=replay_buffer_kwargs,
                          optimize_memory_usage=optimize_memory_usage, ent_coef=ent_coef, target_update_interval=target_update_interval,
                          target_entropy=target_entropy, stats_window_size=stats_window_size, tensorboard_log=tensorboard_log,
-                         policy_kwargs=policy_kwargs, verbose=verbose, seed=seed, device=device, _init_setup_model=False)
+                         policy_kwargs=policy_kwargs, verbose=verbose, seed=seed, device=device, _init_setup_model=False, n_steps=n_steps)
         if self.world_size > 1:
             raise NotImplementedError("data-parallel TQC is not built")
         if _init_setup_model:
@@ -163,7 +164,7 @@ class TQC(SAC):
             s["ent_coef"] += ent_coef
         single = self._single_step
         # truncation, targets, the pairwise quantile-Huber loss and its gradient; the entropy coefficient's loss rides along
-        hip_ops.tqc_critic_loss(z.detach(), z_next, next_log_prob.detach(), rd.rewards, rd.dones, ent_coef, self.gamma,
+        hip_ops.tqc_critic_loss(z.detach(), z_next, next_log_prob.detach(), rd.rewards, td_done(rd), ent_coef, self.gamma,
                                 self.top_quantiles_to_drop_per_net, self._gz, self._tqc_ws, loss_out=c_out, loss_sum=c_sum,
                                 target_out=self._target_y, means_out=s["means"] if single else None, means_sum=None if single else s["means"],
                                 alpha=alpha)
@@ -217,7 +218,7 @@ class TQC(SAC):
             z_next = self.critic_target(rd.next_observations, next_actions)  # [B, G, Nq]
             z_sorted, _ = th.sort(z_next.reshape(z_next.shape[0], -1), dim=1)
             z_kept = z_sorted[:, :self.n_target_quantiles]
-            y = rd.rewards + (1 - rd.dones) * self.gamma * (z_kept - ent_coef * next_log_prob.reshape(-1, 1))  # [B, n_keep]
+            y = rd.rewards + (1 - rd.dones) * td_discount(rd, self.gamma) * (z_kept - ent_coef * next_log_prob.reshape(-1, 1))  # [B, n_keep]
 
         z = self.critic(rd.observations, rd.actions)  # [B, G, Nq]
         critic_loss = quantile_huber_loss(z, y)

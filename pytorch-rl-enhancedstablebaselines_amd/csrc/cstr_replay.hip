@@ -201,6 +201,136 @@ __global__ __launch_bounds__(TPB) void replay_gather_kernel(const cstr_ring_t ri
     }
 }
 
+// ---- n-step samples (NStepReplayBuffer._get_samples) -----------------------------------------------------------------------
+// A sampled pair (row r, env e) owns the window of ring slots ((r + k) % rows, e), k < n_steps: the same env column of the rows that
+// follow in time. A GROUP of G lanes (G = 2, 4, 8, 16: the power of two >= n_steps; groups never straddle a wave) serves one pair:
+//   1. lane k loads rew / done / timeout of step k: every address follows from (r, e, k), so a pair costs one load latency, not n;
+//   2. stop_k = done_k | timeout_k | (slot k is the newest written row); the group's slice of one __ballot and __ffsll give the first
+//      stop j (else n_steps - 1). Nothing is written to the ring: the write head is a comparison;
+//   3. the return sum_{k <= j} gpow[k] r_k is accumulated in f32 in the fixed order k = 0 .. j from shuffled values (every lane of
+//      the group holds it; no atomics, no dependence on the launch shape);
+//   4. the copies -- observation and action of step 0, next observation of step j -- are split over the group's lanes as 8-byte
+//      units (rows of the packed batch are 8-byte aligned, the ring's rows 16-byte), lane 0 stores the scalars.
+// gpow[k] = (float)pow((double)gamma, k) comes from the host in the kernel arguments and is staged in LDS, where the data-dependent
+// entries gpow[j], gpow[j + 1] are read; the kernel never exponentiates. fold = 1 - (1 - dones) gpow[j] is what the TD-target
+// launches take in place of `dones` with their scalar gamma: (1 - fold) gamma == (1 - dones) gamma^(j + 1).
+struct NStepOut {  // PACKED: obs = x_data [B][W], act = x_pi [B][W] or NULL, next_obs = x_next [B][W]
+    float *obs, *act, *next_obs, *done, *rew, *discount, *fold;
+    int64_t *row_idx, *env_idx;
+};
+
+// Called by every lane of the launch with the same `g_first` / `g_count` per group: group g serves pairs g, g + g_count, ...
+template <int D, int A, bool PACKED, int G>
+__device__ __forceinline__ void gather_nstep(const cstr_ring_t &ring, const int32_t *row_idx, const int32_t *env_idx, const int batch,
+                                             const int64_t newest, const int n_steps, const cstr_nstep_gpow_t &tab, float *sg,
+                                             const NStepOut &out, const int g_first, const int g_count)
+{
+    static_assert(G == 2 || G == 4 || G == 8 || G == 16, "a group is a power-of-two slice of a wave");
+    constexpr int HD = D / 2, HA = A / 2, UNITS = 2 * HD + HA, W = D + A;
+    const int t = threadIdx.x, lane = t & 63, k = lane & (G - 1), base = lane & ~(G - 1);
+#pragma unroll
+    for (int i = 0; i <= CSTR_NSTEP_MAX; ++i)
+        if (t == i) sg[i] = tab.g[i];
+    __syncthreads();
+    const int64_t n = ring.n_envs, R = ring.rows;
+    const unsigned long long gmask = (1ULL << G) - 1ULL, last = 1ULL << (n_steps - 1);
+    for (int b = g_first; b < batch; b += g_count) {  // b is shared by the lanes of a group: whole groups enter or leave
+        const int64_t r = row_idx[b], e = env_idx[b];
+        const int64_t rk = (r + k) % R, ok = rk * n + e, o0 = r * n + e;
+        float rw = 0.0f, dn = 0.0f, to = 0.0f;
+        if (k < n_steps) { rw = ring.rew[ok]; dn = ring.done[ok]; to = ring.timeout[ok]; }
+        const bool stop = k < n_steps && (dn != 0.0f || to != 0.0f || rk == newest);
+        const unsigned long long bal = __ballot(stop);
+        const int j = __ffsll((long long)(((bal >> base) & gmask) | last)) - 1;  // first stop, else n_steps - 1
+        float ret = 0.0f;
+#pragma unroll
+        for (int i = 0; i < G; ++i) {
+            const float ri = __shfl(rw, base + i, 64);
+            if (i <= j) ret = ret + sg[i] * ri;
+        }
+        const float dnj = __shfl(dn, base + j, 64), toj = __shfl(to, base + j, 64);
+        const int64_t oj = ((r + j) % R) * n + e;
+        float *dst_obs = out.obs + (int64_t)b * (PACKED ? W : D);
+        float *dst_next = out.next_obs + (int64_t)b * (PACKED ? W : D);
+        float *dst_act = PACKED ? dst_obs + D : out.act + (int64_t)b * A;
+        float *dst_pi = (PACKED && out.act) ? out.act + (int64_t)b * W : nullptr;
+        for (int u = k; u < UNITS; u += G) {
+            const float *src;
+            float *dst, *dst2 = nullptr;
+            if (u < HD) { src = ring.obs + o0 * D + 2 * u; dst = dst_obs + 2 * u; if (dst_pi) dst2 = dst_pi + 2 * u; }
+            else if (u < 2 * HD) { src = ring.next_obs + oj * D + 2 * (u - HD); dst = dst_next + 2 * (u - HD); }
+            else { src = ring.act + o0 * A + 2 * (u - 2 * HD); dst = dst_act + 2 * (u - 2 * HD); }
+            const float2 v = *reinterpret_cast<const float2 *>(src);
+            *reinterpret_cast<float2 *>(dst) = v;
+            if (dst2) *reinterpret_cast<float2 *>(dst2) = v;
+        }
+        if (k == 0) {
+            const float d = dnj * (1.0f - toj);  // buffers.py:322, with the flags of step j
+            out.done[b] = d;
+            out.rew[b] = ret;
+            out.discount[b] = sg[j + 1];
+            out.fold[b] = 1.0f - (1.0f - d) * sg[j];
+            if (out.row_idx) out.row_idx[b] = r;
+            if (out.env_idx) out.env_idx[b] = e;
+        }
+    }
+}
+
+// The newest written row: pos - 1 (mod rows), or pos itself while the rollout launch's ring advance is pending.
+__device__ __forceinline__ int64_t nstep_newest(const int64_t pos, const int64_t rows, const bool pending)
+{
+    return pending ? pos : (pos == 0 ? rows - 1 : pos - 1);
+}
+
+template <int D, int A, bool PACKED, int G>
+__global__ __launch_bounds__(TPB) void replay_sample_nstep_kernel(const cstr_ring_t ring, const int64_t *__restrict__ ring_ctl,
+                                                                  uint32_t *__restrict__ mt_state, const int batch, const int n_steps,
+                                                                  const cstr_nstep_gpow_t tab, const NStepOut out)
+{
+    __shared__ SampleShared sh;
+    __shared__ float sg[CSTR_NSTEP_MAX + 1];
+    extern __shared__ __align__(16) int32_t idx[];  // [2][batch]
+    int32_t *row_idx = idx, *env_idx = idx + batch;
+    const int t = threadIdx.x;
+    for (int i = t; i < MT_N; i += TPB) sh.mt[i] = mt_state[i];
+    int pos = (int)mt_state[MT_N];
+    __syncthreads();
+
+    const int64_t upper = ring_ctl[1] ? ring.rows : ring_ctl[0];  // the draws of replay_sample_kernel, word for word
+    pos = mt_randint_fill(sh, pos, (uint32_t)(upper - 1), batch, row_idx);
+    pos = mt_randint_fill(sh, pos, (uint32_t)(ring.n_envs - 1), batch, env_idx);
+    __syncthreads();
+
+    for (int i = t; i < MT_N; i += TPB) mt_state[i] = sh.mt[i];
+    if (t == 0) mt_state[MT_N] = (uint32_t)pos;
+
+    gather_nstep<D, A, PACKED, G>(ring, row_idx, env_idx, batch, nstep_newest(ring_ctl[0], ring.rows, false), n_steps, tab, sg, out,
+                                  t / G, TPB / G);
+}
+
+// The n-step gather alone, for index pairs the rollout launch drew. Groups are spread over the workgroups of the launch; every
+// workgroup reads ring_ctl[0] before it takes the ticket, and the last one out performs the control-word updates.
+template <int D, int A, int G>
+__global__ __launch_bounds__(TPB) void replay_gather_nstep_kernel(const cstr_ring_t ring, int64_t *ring_ctl, const int advance_ring,
+                                                                  uint64_t *rng_ctl, const uint64_t rng_advance,
+                                                                  const int32_t *__restrict__ idx, const int batch, const int n_steps,
+                                                                  const cstr_nstep_gpow_t tab, const NStepOut out)
+{
+    __shared__ float sg[CSTR_NSTEP_MAX + 1];
+    const int64_t newest = nstep_newest(ring_ctl[0], ring.rows, advance_ring != 0);
+    gather_nstep<D, A, true, G>(ring, idx, idx + batch, batch, newest, n_steps, tab, sg, out,
+                                (int)(blockIdx.x * (TPB / G) + threadIdx.x / G), (int)(gridDim.x * (TPB / G)));
+    if (last_block_ticket(reinterpret_cast<unsigned long long *>(ring_ctl + 2)) && threadIdx.x == 0) {
+        if (advance_ring) {
+            int64_t pos = ring_ctl[0] + 1;
+            if (pos == ring.rows) { ring_ctl[1] = 1; pos = 0; }
+            ring_ctl[0] = pos;
+            ring_ctl[3] += 1;
+        }
+        if (rng_ctl) rng_ctl[1] += rng_advance;
+    }
+}
+
 // ---- np.random.normal on the same stream (exploration noise, core/common/noise.py:44-45, :141-142) -----------------
 // numpy's legacy_gauss is the polar Box-Muller method: an attempt eats two 53-bit doubles (four 32-bit words), is
 // rejected with probability 1 - pi/4, and an accepted attempt yields TWO deviates (f*x2 first, f*x1 cached for the next
@@ -432,5 +562,96 @@ extern "C" int cstr_replay_gather_packed_f32(const cstr_ring_t *ring, int64_t *r
     else if (ring->act_dim == 2) replay_gather_kernel<8, 2><<<1, TPB, 0, s>>>(GATHER_ARGS);
     else replay_gather_kernel<8, 4><<<1, TPB, 0, s>>>(GATHER_ARGS);
 #undef GATHER_ARGS
+    return (int)hipGetLastError();
+}
+
+// ---- n-step entry points -----------------------------------------------------------------------------------------------------
+static int nstep_check(const cstr_ring_t *ring, const void *ring_ctl, int64_t batch, int n_steps, const float *const *f32_out, int n_out,
+                       const void *a, const void *b, const void *c, const void *c_opt)
+{
+    if (!ring || !ring->obs || !ring->next_obs || !ring->act || !ring->rew || !ring->done || !ring->timeout || !ring_ctl) return CSTR_E_BADARG;
+    if (!a || !b || !c || batch <= 0) return CSTR_E_BADARG;
+    for (int i = 0; i < n_out; ++i)
+        if (!f32_out[i]) return CSTR_E_BADARG;
+    const bool lay_ok = (ring->obs_dim == 4 && ring->act_dim == 2) || (ring->obs_dim == 8 && (ring->act_dim == 2 || ring->act_dim == 4));
+    if (!lay_ok || n_steps < 1 || n_steps > CSTR_NSTEP_MAX) return CSTR_E_UNSUPPORTED;
+    if (batch > CSTR_MAX_SAMPLE_BATCH || ring->rows < 1 || ring->n_envs < 1 || ring->rows >= 0xFFFFFFFFLL || ring->n_envs >= 0xFFFFFFFFLL)
+        return CSTR_E_UNSUPPORTED;
+    if (!aligned16(ring->obs) || !aligned16(ring->next_obs) || !aligned8(ring->act) || !aligned8(a) || !aligned8(b) || !aligned8(c) ||
+        (c_opt && !aligned8(c_opt)))
+        return CSTR_E_BADARG;
+    return CSTR_OK;
+}
+
+static inline int nstep_group(int n_steps) { return n_steps <= 2 ? 2 : n_steps <= 4 ? 4 : n_steps <= 8 ? 8 : 16; }
+
+// KERNEL<D, A, ..., G> for the ring's layout and the lane group of n_steps
+#define NSTEP_BY_GROUP(LAUNCH, D_, A_)                                                                                     \
+    switch (nstep_group(n_steps)) {                                                                                        \
+    case 2: LAUNCH(D_, A_, 2); break;                                                                                      \
+    case 4: LAUNCH(D_, A_, 4); break;                                                                                      \
+    case 8: LAUNCH(D_, A_, 8); break;                                                                                      \
+    default: LAUNCH(D_, A_, 16); break;                                                                                    \
+    }
+#define NSTEP_DISPATCH(LAUNCH)                                                                                             \
+    if (ring->obs_dim == 4) { NSTEP_BY_GROUP(LAUNCH, 4, 2) }                                                               \
+    else if (ring->act_dim == 2) { NSTEP_BY_GROUP(LAUNCH, 8, 2) }                                                          \
+    else { NSTEP_BY_GROUP(LAUNCH, 8, 4) }
+
+extern "C" int cstr_replay_sample_nstep_mt19937_f32(const cstr_ring_t *ring, const int64_t *ring_ctl, uint32_t *mt_state, int64_t batch,
+                                                    int n_steps, cstr_nstep_gpow_t gpow, float *out_obs, float *out_act, float *out_next_obs,
+                                                    float *out_done, float *out_rew, float *out_discount, float *out_fold,
+                                                    int64_t *out_row_idx, int64_t *out_env_idx, cstr_stream_t stream)
+{
+    const float *const scalars[] = {out_done, out_rew, out_discount, out_fold};
+    if (!mt_state) return CSTR_E_BADARG;
+    const int rc = nstep_check(ring, ring_ctl, batch, n_steps, scalars, 4, out_obs, out_act, out_next_obs, nullptr);
+    if (rc != CSTR_OK) return rc;
+    const NStepOut out = {out_obs, out_act, out_next_obs, out_done, out_rew, out_discount, out_fold, out_row_idx, out_env_idx};
+    const size_t dyn = sizeof(int32_t) * 2 * (size_t)batch;
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(D_, A_, G_) replay_sample_nstep_kernel<D_, A_, false, G_><<<1, TPB, dyn, s>>>(*ring, ring_ctl, mt_state, (int)batch, n_steps, gpow, out)
+    NSTEP_DISPATCH(LAUNCH)
+#undef LAUNCH
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_replay_sample_nstep_packed_mt19937_f32(const cstr_ring_t *ring, const int64_t *ring_ctl, uint32_t *mt_state,
+                                                           int64_t batch, int n_steps, cstr_nstep_gpow_t gpow, float *x_data, float *x_next,
+                                                           float *x_pi, float *out_done, float *out_rew, float *out_discount, float *out_fold,
+                                                           int64_t *out_row_idx, int64_t *out_env_idx, cstr_stream_t stream)
+{
+    const float *const scalars[] = {out_done, out_rew, out_discount, out_fold};
+    if (!mt_state) return CSTR_E_BADARG;
+    const int rc = nstep_check(ring, ring_ctl, batch, n_steps, scalars, 4, x_data, x_next, x_data, x_pi);
+    if (rc != CSTR_OK) return rc;
+    const NStepOut out = {x_data, x_pi, x_next, out_done, out_rew, out_discount, out_fold, out_row_idx, out_env_idx};
+    const size_t dyn = sizeof(int32_t) * 2 * (size_t)batch;
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(D_, A_, G_) replay_sample_nstep_kernel<D_, A_, true, G_><<<1, TPB, dyn, s>>>(*ring, ring_ctl, mt_state, (int)batch, n_steps, gpow, out)
+    NSTEP_DISPATCH(LAUNCH)
+#undef LAUNCH
+    return (int)hipGetLastError();
+}
+
+extern "C" int cstr_replay_gather_nstep_packed_f32(const cstr_ring_t *ring, int64_t *ring_ctl, int advance_ring, uint64_t *rng_ctl,
+                                                   uint64_t rng_advance, const int32_t *sample_idx, int64_t batch, int n_steps,
+                                                   cstr_nstep_gpow_t gpow, float *x_data, float *x_next, float *x_pi, float *out_done,
+                                                   float *out_rew, float *out_discount, float *out_fold, int64_t *out_row_idx,
+                                                   int64_t *out_env_idx, cstr_stream_t stream)
+{
+    const float *const scalars[] = {out_done, out_rew, out_discount, out_fold};
+    if (!sample_idx) return CSTR_E_BADARG;
+    const int rc = nstep_check(ring, ring_ctl, batch, n_steps, scalars, 4, x_data, x_next, x_data, x_pi);
+    if (rc != CSTR_OK) return rc;
+    const NStepOut out = {x_data, x_pi, x_next, out_done, out_rew, out_discount, out_fold, out_row_idx, out_env_idx};
+    const int G = nstep_group(n_steps);
+    const int64_t want = (batch * G + TPB - 1) / TPB;  // a lane group per sampled row
+    const int grid = (int)(want < 32 ? want : 32);
+    hipStream_t s = (hipStream_t)stream;
+#define LAUNCH(D_, A_, G_) \
+    replay_gather_nstep_kernel<D_, A_, G_><<<grid, TPB, 0, s>>>(*ring, ring_ctl, advance_ring, rng_ctl, rng_advance, sample_idx, (int)batch, n_steps, gpow, out)
+    NSTEP_DISPATCH(LAUNCH)
+#undef LAUNCH
     return (int)hipGetLastError();
 }
