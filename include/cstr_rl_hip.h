@@ -1260,6 +1260,56 @@ int cstr_qrdqn_loss_f32(const float *z, int64_t ldz, const float *z_next, int64_
                         float *loss_out, float *loss_sum, float *cur_out, float *target_out, int64_t *next_index_out, double *ws,
                         cstr_stream_t stream);
 
+/* ---- C51 on the discrete valve face (csrc/cstr_c51.hip; core/c51/c51.py; Bellemare, Dabney & Munos 2017, categorical DQN) -------------
+ * What C51 adds to DQN's launches: the fused atom head its action selection runs on, and everything between the two forward passes of
+ * a gradient step and loss.backward(). The entry points validate on the host without dereferencing anything and then only enqueue;
+ * f32 in and out; deterministic and bit-identical on relaunch (no float atomics, no workgroup waiting for another).
+ * The face is the DQN block's: M = n_actions = levels * levels, 2 <= levels <= CSTR_DQN_MAX_LEVELS. N = n_atoms, B = batch, the support
+ * z_i = v_min + i * dz, dz = (v_max - v_min) / (N - 1), formed in float64 from the two doubles. ATOM LAYOUT: a row holds M * N floats,
+ * atom i of action a at a * N + i (`logits.view(-1, M, N)`): action-major, unlike the QR-DQN block, so one action's N rows of the
+ * last layer are contiguous.
+ * cstr_c51_supported: the DQN face check, 2 <= N <= CSTR_C51_MAX_ATOMS, H a positive multiple of 4 and at most 512. H matters to the
+ *   head alone: H = 4 asks about the loss.
+ * cstr_c51_head_q_f32 (one launch): h [n][ldh] the last hidden activations (H columns used), w [M * N][H] and bias [M * N] the last
+ *   Linear layer as it lies in the arena (no copy, no re-layout);  q[r][a] = sum_i z_i softmax_i(h[r] . w[a * N + i] + bias[a * N + i])
+ *   into q [n][ldq]. The head GEMM, the softmax over the atoms and the expectation in one kernel: a workgroup owns 16 rows (hidden
+ *   tile in LDS), its four waves split the actions, a wave walks an action's ceil(N / 16) column tiles with the f32 16x16x4 MFMA (four
+ *   tiles per pass over H) and folds each pass into a running softmax per row (maximum, rescaled sum e, rescaled sum z e; expf;
+ *   reductions over the 16 lanes of a row's columns by xor shuffles). The logits are never stored. f32 arithmetic, z_i rounded to f32
+ *   from float64. Columns beyond N count as -inf; rows beyond n are computed on the clamped last row and not stored. A NaN (or +inf)
+ *   logit makes that (row, action)'s q NaN, which cstr_dqn_act_f32 takes as the greatest value. q feeds cstr_dqn_act_f32 unchanged.
+ *   CSTR_E_BADARG: a NULL pointer, n, n_actions, levels, N or H <= 0, ldh < H, ldq < M, v_max <= v_min or either not finite, a pointer
+ *   off a 4-byte (w: 16-byte) boundary, q overlapping an input. CSTR_E_UNSUPPORTED: not cstr_c51_supported, n > CSTR_PPO_MAX_ROWS.
+ * cstr_c51_loss_f32 (two launches: one workgroup per row, then one workgroup over the per-row sums in ws). z [B][ldz] the online
+ *   network's logits at s, z_next [B][ldn] the target network's at s', ldz, ldn >= M * N; valve [B][2] the stored valve pair. Per row
+ *   b, float64 on the float32 inputs, each output rounded to float32 once:
+ *     e_a[i] = exp(z_next[b][a][i] - max_i),  Q'_a = (sum_i z_i e_a[i]) / (sum_i e_a[i])  (i ascending);  a* = the first maximum of Q'
+ *     (a NaN counts as the greatest value, the first one wins: cstr_dqn_act_f32's convention);  p_j = e_a*[j] / sum_i e_a*[i]
+ *     Tz_j = clamp(reward_b + (1 - done_b) * gamma * z_j, v_min, v_max),  b_j = clamp((Tz_j - v_min) / dz, 0, N - 1)
+ *     m_i = sum_j p_j * max(0, 1 - |b_j - i|)  (j ascending over all N): the projection of the paper's eq. 7 as a gather; it equals the
+ *     floor / ceil scatter and needs no special case for an integer b_j
+ *     a = level(valve[b][0]) * levels + level(valve[b][1]) (the DQN block's inverse);  x_i = z[b][a][i] - max_i z[b][a][i],
+ *     lp_i = x_i - log(sum_k exp(x_k)),  loss_b = -sum_i m_i lp_i
+ *     gz[b][a][i] = ((exp(x_i) / sum_k exp(x_k)) * (sum_k m_k) - m_i) / B, what autograd gives for the statement; every other entry
+ *     of the row's M * N is stored as 0. gz has z's shape and row stride.
+ *   loss = (sum_b loss_b) / B. loss_out [1] (stored) / loss_sum [1] (+= loss, one float32 addition). m_out [B][N] = m, logp_out [B][N] =
+ *   lp, next_index_out int64 [B] = a*, row_loss_out [B] = loss_b. `done` enters only as (1 - done) * gamma: an n-step batch passes its
+ *   fold. ws: double [B] scratch (the per-row sums), 8-byte aligned.
+ *   Reduction order: a row's lanes through a 64-lane shuffle tree (offsets 32 .. 1), wave sums in wave order; rows t, t + 256, ...
+ *   in ascending order on lane t of the finishing workgroup, the same tree (the QR-DQN block's).
+ *   Optional (NULL = not written): loss_out, loss_sum, m_out, logp_out, next_index_out, row_loss_out.
+ *   CSTR_E_BADARG: a NULL required pointer, batch, n_actions, levels or N <= 0, ldz or ldn < M * N, gamma negative or NaN, v_max <= v_min
+ *   or either not finite, a pointer off a 4-byte (valve, next_index_out, ws: 8-byte) boundary, an output overlapping an input or
+ *   another output. CSTR_E_UNSUPPORTED: not cstr_c51_supported(.., 4), batch > CSTR_MAX_SAMPLE_BATCH. */
+#define CSTR_C51_MAX_ATOMS 256
+int cstr_c51_supported(int n_actions, int levels, int n_atoms, int64_t H);
+int cstr_c51_head_q_f32(const float *h, int64_t ldh, const float *w, const float *bias, int64_t n, int n_actions, int levels, int n_atoms,
+                        int64_t H, double v_min, double v_max, float *q, int64_t ldq, cstr_stream_t stream);
+int cstr_c51_loss_f32(const float *z, int64_t ldz, const float *z_next, int64_t ldn, const float *valve, const float *reward,
+                      const float *done, double gamma, double v_min, double v_max, int64_t batch, int n_actions, int levels, int n_atoms,
+                      float *gz, float *loss_out, float *loss_sum, float *m_out, float *logp_out, int64_t *next_index_out,
+                      float *row_loss_out, double *ws, cstr_stream_t stream);
+
 /* ---- Prioritized experience replay on the replay ring (csrc/cstr_per.hip; Schaul et al. 2016, the proportional variant) --------------
  * A radix-64 sum tree over C = rows * n_envs priorities, float64. Leaf row * n_envs + env belongs to ring slot (row, env) and holds
  * p^alpha, or 0 for a slot never written. Level 0 is the C leaves; level l + 1 has ceil(n_l / 64) nodes, up to a single root (a tree

@@ -30,6 +30,7 @@ CQL_MAX_ACTIONS, CQL_TAG = 21, 0xC0175E4A  # CSTR_CQL_MAX_ACTIONS; counter word 
 IQL_MAX_BATCH = 16384  # CSTR_IQL_MAX_BATCH
 TQC_MAX_ATOMS = 256  # CSTR_TQC_MAX_ATOMS
 QRDQN_MAX_QUANTILES = 256  # CSTR_QRDQN_MAX_QUANTILES
+C51_MAX_ATOMS = 256  # CSTR_C51_MAX_ATOMS
 ARS_MAX_WIDTH, ARS_MAX_DELTA, ARS_TAG = 64, 4096, 0xA4500D17  # CSTR_ARS_MAX_WIDTH, CSTR_ARS_MAX_DELTA; counter word 3 of the delta stream
 # TRPO (csrc/cstr_trpo.hip): the heads, the control block's words (CSTR_TRPO_CTL_*), the conjugate-gradient launch's forms, the x0 stream's tag
 TRPO_HEAD_GAUSSIAN, TRPO_HEAD_CATEGORICAL, TRPO_HEAD_MULTICATEGORICAL = 0, 1, 2
@@ -70,6 +71,7 @@ SYMBOLS = (
     "cstr_iql_loss_f32",
     "cstr_tqc_supported", "cstr_tqc_critic_loss_f32", "cstr_tqc_actor_loss_f32",
     "cstr_qrdqn_supported", "cstr_qrdqn_fold_head_f32", "cstr_qrdqn_loss_f32",
+    "cstr_c51_supported", "cstr_c51_head_q_f32", "cstr_c51_loss_f32",
     "cstr_ars_supported", "cstr_ars_population_f32", "cstr_ars_update_f32",
     "cstr_linear_tangent_fwd_f32", "cstr_trpo_objective_f32", "cstr_trpo_fisher_head_f32", "cstr_trpo_cg_step_f32", "cstr_trpo_apply_step_f32",
     "cstr_trpo_value_loss_f32", "cstr_trpo_x0_f32",

@@ -2169,6 +2169,60 @@ def qrdqn_loss(z, z_next, valve, reward, done, gamma: float, levels: int, n_quan
                                        ptr(target_out), ptr(next_index_out), ptr(ws), stream_ptr()), "cstr_qrdqn_loss_f32")
 
 
+# ---- C51 on the discrete valve face: fused atom head, projection + cross-entropy loss (csrc/cstr_c51.hip) ---------------------------
+def c51_supported(n_actions: int, levels: int, n_atoms: int, hidden: int = 4) -> bool:
+    """cstr_c51_supported: DQN's face, 2 <= n_atoms <= C51_MAX_ATOMS and, for the head launch, `hidden` a multiple of 4 up to 512
+    (the default 4 asks about the loss launch alone)."""
+    return bool(nv.lib().cstr_c51_supported(C.c_int(int(n_actions)), C.c_int(int(levels)), C.c_int(int(n_atoms)), C.c_int64(int(hidden))))
+
+
+def c51_head_q(h, weight, bias, levels: int, v_min: float, v_max: float, q):
+    """The categorical network's last layer, the softmax over the atoms and the expectation in one launch (cstr_c51_head_q_f32):
+    h [n, H] (rows may be strided), weight [M * N, H] and bias [M * N] with atom i of action a in row a * N + i, M = levels^2;
+    q [n, M] (rows may be strided) = sum_i z_i softmax_i(h @ weight[a]^T + bias[a]) on the support z = linspace(v_min, v_max, N)."""
+    n, hid = h.shape
+    m = int(levels) * int(levels)
+    if not (isinstance(weight, th.Tensor) and weight.dim() == 2 and weight.shape[1] == hid and weight.shape[0] >= m and weight.shape[0] % m == 0):
+        raise ValueError(f"weight: needs a [n_atoms * {m}, {hid}] matrix")
+    rows = weight.shape[0]
+    ldh = _rows(h, "h", n, hid)
+    ldq = _rows(q, "q", n, m)
+    _chk(weight, "weight", (rows, hid), th.float32), _chk(bias, "bias", (rows,), th.float32)
+    check(nv.lib().cstr_c51_head_q_f32(ptr(h), C.c_int64(ldh), ptr(weight), ptr(bias), C.c_int64(n), C.c_int(m), C.c_int(int(levels)),
+                                       C.c_int(rows // m), C.c_int64(hid), C.c_double(v_min), C.c_double(v_max), ptr(q), C.c_int64(ldq),
+                                       stream_ptr()), "cstr_c51_head_q_f32")
+
+
+def c51_loss(z, z_next, valve, reward, done, gamma: float, levels: int, n_atoms: int, v_min: float, v_max: float, gz, ws, loss_out=None,
+             loss_sum=None, m_out=None, logp_out=None, next_index_out=None, row_loss_out=None):
+    """C51's loss as a backward root (cstr_c51_loss_f32): z / z_next [B, M * N] (rows may be strided) = the online network's logits at
+    s / the target network's at s', atom i of action a at a * N + i. Greedy a* over the expected values of z_next, its distribution
+    shifted by reward + (1 - done) gamma z and projected onto the support (m_out [B, N]), the log-softmax of the taken action's logits
+    (logp_out [B, N]) from the stored valve pair, loss_out = mean_b -sum_i m_i logp_i (row_loss_out [B] the summands), gz = d loss / d z
+    (z's shape and row stride, zeros off the taken action). next_index_out int64 [B] = a*. ws: float64 [B] scratch."""
+    b, nm = z.shape
+    n, k = int(n_atoms), int(levels)
+    if n < 1 or nm != n * k * k:
+        raise ValueError(f"z: {nm} columns are not n_atoms * levels^2 = {n} * {k * k}")
+    ldz = _rows(z, "z", b, nm)
+    ldn = _rows(z_next, "z_next", b, nm)
+    if _rows(gz, "gz", b, nm) != ldz:
+        raise ValueError("gz must have z's row stride")
+    _chk(valve, "valve", (b, 2), th.float32)
+    for t, nm_ in ((reward, "reward"), (done, "done")):
+        _vec(t, nm_, b)
+    _chk(ws, "ws", (b,), th.float64)
+    for t, nm_, cnt in ((loss_out, "loss_out", 1), (loss_sum, "loss_sum", 1), (m_out, "m_out", b * n), (logp_out, "logp_out", b * n),
+                        (row_loss_out, "row_loss_out", b)):
+        if t is not None:
+            _vec(t, nm_, cnt)
+    _opt(next_index_out, "next_index_out", (b,), th.int64)
+    check(nv.lib().cstr_c51_loss_f32(ptr(z), C.c_int64(ldz), ptr(z_next), C.c_int64(ldn), ptr(valve), ptr(reward), ptr(done), C.c_double(gamma),
+                                     C.c_double(v_min), C.c_double(v_max), C.c_int64(b), C.c_int(k * k), C.c_int(k), C.c_int(n), ptr(gz),
+                                     ptr(loss_out), ptr(loss_sum), ptr(m_out), ptr(logp_out), ptr(next_index_out), ptr(row_loss_out), ptr(ws),
+                                     stream_ptr()), "cstr_c51_loss_f32")
+
+
 # ---- Categorical head of PPO / A2C on the discrete valve face (csrc/cstr_categorical.hip) -------------------------------------------
 def categorical_supported(obs_dim: int, n_actions: int, levels: int) -> bool:
     return obs_dim in (4, 8) and dqn_supported(n_actions, levels)
